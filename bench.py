@@ -3,6 +3,15 @@
 K2 greedy set cover) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S4|S2|S3]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.
+`--full` adds everything else the line can report: the digest and property
+checks, the CPU baselines, the untimed one-chain and E_dirty passes behind the
+roofline figures, -c 0.9, M2, the overlapped-groups figure and the S3 / S5
+legs.  `--dump-outputs DIR` writes the picks of every group of the last timed
+step (candidate ids in pick order; S5: the selected probes as character codes)
+as DIR/<name>.npy in float64.
 
 Workload (default S4 = BASELINE.json configs[3], the largest configuration
 that fits one GPU; configs[4], the V-All-scale input, is `--workload S5`): the
@@ -31,7 +40,7 @@ no data-path collective.  The picks must equal the committed digests whatever N.
 `value` is the resident-input rate the measurement contract prescribes (inputs
 already in HBM when the timed region starts).  The wall-clock the metric also
 names -- SURVEY 8(d) M2: pack + H2D + front end + scan + solve + ids out, from
-host strings, nothing resident -- is measured in the same run through the
+host strings, nothing resident -- is measured with --full in the same run through the
 plugin's own path (SetCoverFilter._filter_genomes_device, which packs and
 uploads group i + 1 on an upload context while group i is scanned and solved):
 `m2_setcoverfilter_wall_s`, `value_incl_h2d`, and the same without the overlap
@@ -480,6 +489,26 @@ def digest_in_order(ids):
     return hashlib.sha256(np.asarray(ids, dtype="<i8").tobytes()).hexdigest()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64, rows in the order the timed path returned them.
+    Past DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of its rows (in their order), and
+    out_dir/<name>_rows.npy says which."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    total = sum(8 * a.size for a in arrays.values())
+    keep = min(1.0, DUMP_LIMIT_BYTES / 2.0 / max(total, 1))
+    for name, a in arrays.items():
+        a = a.astype(np.float64)
+        if keep < 1.0 and a.shape[0] > 0:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def golden_digests(workload, scale):
     """tests/golden/full_size_picks.json (made in the authoring container by
     tests/golden/make_full_size.py with the pinned CPU oracle)."""
@@ -826,16 +855,27 @@ def bench_design_large(args):
         steps.append(tm)
     engine.default_context().sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the probe strings as character codes, one row per probe, sorted (the digest's notion of the set)
+        s = sorted(set(probes))
+        codes = np.zeros((len(s), max(map(len, s), default=PROBE_LEN)), dtype=np.uint8)
+        if len(set(map(len, s))) == 1:
+            codes[:] = np.frombuffer("".join(s).encode(), dtype=np.uint8).reshape(codes.shape)
+        else:
+            for i, p in enumerate(s):
+                codes[i, :len(p)] = np.frombuffer(p.encode(), dtype=np.uint8)
+        dump_outputs(args.dump_outputs, {"probes": codes})
     K = args.steps
     per = {k: sum(st[k] for st in steps) / K for k in steps[0] if isinstance(steps[0][k], (int, float))}
     units = per.get("probe_bp_units", 0.0)
     dg = probes_digest(probes)
     gold = None
-    try:
-        with open(os.path.join(REPO, "tests", "golden", "full_size_picks.json")) as f:
-            gold = json.load(f).get("%s:%g" % (args.workload, args.scale), {}).get("design")
-    except (OSError, ValueError):
-        pass
+    if args.full:
+        try:
+            with open(os.path.join(REPO, "tests", "golden", "full_size_picks.json")) as f:
+                gold = json.load(f).get("%s:%g" % (args.workload, args.scale), {}).get("design")
+        except (OSError, ValueError):
+            pass
     seeds, dropped, hits = per.get("seed_hits", 0), per.get("seeds_dropped", 0), per.get("raw_hits", 0)
     vb = seed_verify_bytes(seeds, dropped, hits)
     rows = per.get("rows", 0)
@@ -887,13 +927,13 @@ def bench_design_large(args):
         "step_seconds": [st["wall_s"] for st in steps],
         "device_memory": engine.pool_stats(),
     }
-    if not args.no_cpu_baseline and args.scale == 1.0:
+    if args.full and not args.no_cpu_baseline and args.scale == 1.0:
         base, gpu_s, same = cpu_baseline_s5()
         out["cpu_baseline"] = base
         out["parity_vs_oracle_on_cpu_sample"] = same
         out["gpu_ms_on_cpu_sample"] = gpu_s * 1e3
         out["speedup_vs_cpu_oracle_on_sample"] = base["seconds"] / gpu_s
-    if not args.no_solver_check:
+    if args.full and not args.no_solver_check:
         # property check where no oracle digest exists: the two kernel families of the frontier solver
         # (set-parallel fused / row-parallel flat) must select the same probes
         cur_flat = per.get("flat_rows_streamed", 0) > 0
@@ -938,7 +978,16 @@ def main():
     ap.add_argument("--also-s5-scale", type=float, default=1.0)
     ap.add_argument("--no-solver-check", action="store_true",
                     help="S5: skip the extra pass through the other solver family")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: digest checks, property checks, CPU "
+                         "baselines, one-chain and E_dirty passes, -c 0.9, M2, overlapped groups, the S3 / S5 legs "
+                         "(each still subject to its --no-* switch); without it the run only sets up, warms up, "
+                         "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.preflight:
         args.steps, args.warmup = 1, 0
         args.no_cpu_baseline = args.no_m2 = args.no_partial = args.no_overlap_figure = True
@@ -998,12 +1047,22 @@ def main():
     elapsed = time.perf_counter() - t0
     pool1 = engine.pool_stats()
     my_elapsed = elapsed
+    if args.dump_outputs:
+        # every group's picks (candidate ids in pick order) of the last timed step, gathered on rank 0
+        mine_picks = {gi: np.asarray(ids, dtype=np.int64) for gi, ids in picks.items()
+                      if rank == 0 or gi not in sharded_idx}
+        if dist is not None:
+            for part in W.allgather(mine_picks):
+                for gi, ids in part.items():
+                    mine_picks.setdefault(gi, ids)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"picks_group%02d" % gi: ids for gi, ids in sorted(mine_picks.items())})
 
-    # one extra, untimed step with the E_dirty statistics on (SURVEY 8(d) K2's byte formula wants them), and one
-    # whose solutions are replayed by the independent check kernels
+    # (--full) one extra, untimed step with the E_dirty statistics on (SURVEY 8(d) K2's byte formula wants them), and
+    # one whose solutions are replayed by the independent check kernels
     dirty_stats, prop = None, None
     alone_stats, alone_ms = None, None
-    if world == 1 and not args.preflight and stepper.union_pool is not None:
+    if args.full and world == 1 and not args.preflight and stepper.union_pool is not None:
         # the timed steps run two chains side by side (the large groups | the union instance): their per-kernel
         # event times include what the other stream's kernels took.  Two more untimed steps one chain after the
         # other give every kernel's time on an otherwise idle device -- reported beside the timed figures
@@ -1014,7 +1073,7 @@ def main():
         run_step(alone_stats, beside=False)
         stepper.sync()
         alone_ms = (time.perf_counter() - ta) * 1e3
-    if world == 1 and not args.preflight:
+    if args.full and world == 1 and not args.preflight:
         os.environ["CATCHHIP_FLAT_COUNT_DIRTY"] = "1"
         try:
             st_d = []
@@ -1043,8 +1102,8 @@ def main():
                 npairs, nbad = ndf_bucket_independence(kept, tabs, NdfGroup.HAMMING)
                 prop = dict(prop or {}, ndf_kept=int(at.size), ndf_pairs_sharing_a_bucket=npairs, ndf_pairs_too_close=nbad)
                 prop["ok"] = bool(prop.get("ok", True) and nbad == 0)
-    # identical picks whatever N: every group against the committed digests
-    gold = golden_digests(args.workload, args.scale)
+    # identical picks whatever N: every group against the committed digests (--full, --preflight)
+    gold = golden_digests(args.workload, args.scale) if (args.full or args.preflight) else None
     gold_ok, gold_n = True, 0
     if gold is not None:
         for gi, ids in picks.items():
@@ -1336,7 +1395,7 @@ def main():
                                        algorithmic_bytes_per_launch=k3_bytes / nf,
                                        avg_launch_ms=per.get("ndf_ms", 0.0) / nf, launches_per_step=nf,
                                        device_ms_per_step=per.get("ndf_ms", 0.0))
-        if world == 1 and not args.no_cpu_baseline and Stepper.ndf:
+        if args.full and world == 1 and not args.no_cpu_baseline and Stepper.ndf:
             # configs[2]: the oracle's chain (Hamming filter, then the set cover) on a down-scaled S3 of the
             # same generator, and the GPU on that same input
             base, gpu_s, same = cpu_baseline_s3(stepper.ctxs[0])
@@ -1344,7 +1403,7 @@ def main():
             out["parity_vs_oracle"] = same
             out["gpu_ms_on_cpu_sample"] = gpu_s * 1e3
             out["speedup_vs_cpu_oracle"] = base["seconds"] / gpu_s
-        elif world == 1 and not args.no_cpu_baseline:
+        elif args.full and world == 1 and not args.no_cpu_baseline:
             order = sorted(range(len(groups)), key=lambda i: bases[i])
             by_idx_ok = set(g.index for g in stepper.resident)
             sample, acc = [], 0
@@ -1390,7 +1449,7 @@ def main():
             out["speedup_note"] = ("CPU seconds per pass over the sample's groups / GPU seconds for the same "
                                    "groups (resident inputs); `value` / cpu_baseline.value is NOT comparable: "
                                    "probe*bp grows quadratically with the group size")
-        if world == 1 and not args.no_partial and not Stepper.ndf and args.workload in ("S4", "S4i"):
+        if args.full and world == 1 and not args.no_partial and not Stepper.ndf and args.workload in ("S4", "S4i"):
             # the same resident groups under -c 0.9 (partial coverage): frontier rounds with the universe
             # test; digests of the picks in order against the committed ones
             def c09_pass(collect):
@@ -1428,7 +1487,7 @@ def main():
                                        "note": "one pass over the resident instances of the timed step (large groups one after "
                                                "the other, the small ones as one instance); digests are of every group's "
                                                "picks in its own pick order"}
-        if world == 1 and not args.no_m2 and not Stepper.ndf:
+        if args.full and world == 1 and not args.no_m2 and not Stepper.ndf:
             engine.pool_trim()        # (the resident passes' cached blocks: the passes below allocate on other contexts)
             # M2: from host strings to ids on the host, nothing resident, through the
             # plugin's pipelined path; then one pass without the overlap for comparison
@@ -1444,7 +1503,7 @@ def main():
             out["m2_note"] = ("pack + H2D + device front end + scan + solve + ids out per pass, host strings in, "
                               "via SetCoverFilter._filter_genomes_device; the upload context packs group i+1 "
                               "while group i is scanned and solved (m2_serial_wall_s: the same without overlap)")
-        if world == 1 and not args.no_overlap_figure and not args.no_cpu_baseline:   # (both extras off under the profiler)
+        if args.full and world == 1 and not args.no_overlap_figure and not args.no_cpu_baseline:   # (both extras off under the profiler)
             # The same work with every group on one of three streams (what the plugin's
             # CATCHHIP_GROUPS_IN_FLIGHT does): faster, but kernels of different groups then
             # share the CUs and their HIP-event times stop meaning anything -- which is why
@@ -1473,8 +1532,8 @@ def main():
                                         "note": "not the headline: per-kernel times (roofline) are only "
                                                 "meaningful when kernels run alone"}
             st2.close()
-        if (world == 1 and args.workload == "S4" and args.scale == 1.0 and not args.no_also and not args.no_cpu_baseline
-                and not args.preflight):
+        if (args.full and world == 1 and args.workload == "S4" and args.scale == 1.0 and not args.no_also
+                and not args.no_cpu_baseline and not args.preflight):
             # BASELINE configs[2] (S3: --filter-with-lsh-hamming in the step) and configs[4] (S5: the design_large chain)
             # in the same driver-run line: each in a process of its own, after this one has given its memory back
             import subprocess
@@ -1494,7 +1553,7 @@ def main():
                 ta = time.perf_counter()
                 try:
                     r = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra +
-                                       ["--no-m2", "--no-partial", "--no-overlap-figure", "--no-also"],
+                                       ["--full", "--no-m2", "--no-partial", "--no-overlap-figure", "--no-also"],
                                        capture_output=True, text=True, timeout=1200)
                     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
                     sub = json.loads(line)

@@ -3,27 +3,29 @@
 # profiles/ for the current round: the bench JSON line, the rocprofv3
 # kernel-trace summary of the same command, and the HBM traffic counters
 # (FETCH_SIZE / WRITE_SIZE in separate passes, as MI355X_MICROARCH.md says).
-#   tools/collect_profiles.sh <tag> [workload] [extra]   -> gpurun_out/profiles_<tag>/
+#   tools/collect_profiles.sh <tag> [workload] [extra]   -> prof_out/profiles_<tag>/
 # extra = "all" also profiles the clustering pre-step and the device front end
+R=$(cd "$(dirname "$0")/.." && pwd)
+mkdir -p $R/prof_out
 tag=${1:-r04}; wl=${2:-S4}; extra=${3:-}
-out=/root/repo/gpurun_out/profiles_$tag
+out=$R/prof_out/profiles_$tag
 rm -rf $out
 mkdir -p $out
-cd /root/repo
-python bench.py --workload $wl > $out/bench.json 2> $out/bench.err
+cd $R
+python bench.py --full --workload $wl > $out/bench.json 2> $out/bench.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python /root/repo/bench.py --workload $wl --no-cpu-baseline --no-m2 --no-partial --no-overlap-figure --no-property-checks > $out/bench_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --full --workload $wl --no-cpu-baseline --no-m2 --no-partial --no-overlap-figure --no-property-checks > $out/bench_under_rocprof.json 2>/dev/null
 # the same with one chain at a time (the union instance after the large groups, not beside them): the summary whose
 # per-kernel times back the line's `roofline` (a unit's launches with the device to themselves)
-CATCHHIP_BENCH_UNION_BESIDE=0 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_one_chain -- python /root/repo/bench.py --workload $wl --no-cpu-baseline --no-m2 --no-partial --no-overlap-figure --no-property-checks --no-also > $out/bench_under_rocprof_one_chain.json 2>/dev/null
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_fetch -- python /root/repo/bench.py --workload $wl --steps 2 --warmup 1 --no-cpu-baseline --no-m2 --no-partial --no-overlap-figure --no-property-checks > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/pmc_write -- python /root/repo/bench.py --workload $wl --steps 2 --warmup 1 --no-cpu-baseline --no-m2 --no-partial --no-overlap-figure --no-property-checks > /dev/null 2>&1
+CATCHHIP_BENCH_UNION_BESIDE=0 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_one_chain -- python $R/bench.py --full --workload $wl --no-cpu-baseline --no-m2 --no-partial --no-overlap-figure --no-property-checks --no-also > $out/bench_under_rocprof_one_chain.json 2>/dev/null
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_fetch -- python $R/bench.py --full --workload $wl --steps 2 --warmup 1 --no-cpu-baseline --no-m2 --no-partial --no-overlap-figure --no-property-checks > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/pmc_write -- python $R/bench.py --full --workload $wl --steps 2 --warmup 1 --no-cpu-baseline --no-m2 --no-partial --no-overlap-figure --no-property-checks > /dev/null 2>&1
 if [ "$extra" = "all" ]; then
   # the kernels outside the bench's hot path: clustering pre-step and the device front end
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_cluster -- python /root/repo/tools/cluster_bench.py --scale 0.25 --cpu-sample 0 > $out/cluster_bench.json 2>/dev/null
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_frontend -- python /root/repo/tools/e2e_profile.py S4 0.5 > $out/frontend_e2e.txt 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_cluster -- python $R/tools/cluster_bench.py --scale 0.25 --cpu-sample 0 > $out/cluster_bench.json 2>/dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_frontend -- python $R/tools/e2e_profile.py S4 0.5 > $out/frontend_e2e.txt 2>&1
 fi
-cd /root/repo
+cd $R
 for t in cluster frontend; do
   f=$(ls -t $out/trace_$t/*/*kernel_stats.csv 2>/dev/null | head -1)
   [ -n "$f" ] && cp "$f" $out/${t}_kernel_stats.csv

@@ -9,7 +9,7 @@ R=$PWD
 out=$R/gpurun_out/units_${tag}_${wl}
 rm -rf $out; mkdir -p $out
 export CATCHHIP_TEST_HOOKS=1
-args="--workload $wl --scale $sc --steps $steps --warmup 1 --no-cpu-baseline --no-m2 --no-partial --no-overlap-figure --no-property-checks --no-solver-check --no-also"
+args="--full --workload $wl --scale $sc --steps $steps --warmup 1 --no-cpu-baseline --no-m2 --no-partial --no-overlap-figure --no-property-checks --no-solver-check --no-also"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py $args > $out/bench_under_rocprof.json 2>/dev/null
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_fetch -- python $R/bench.py $args > /dev/null 2>&1

@@ -1,13 +1,15 @@
 #!/bin/bash
 # usage (GPU box): tools/pmc_kernel.sh <workload> <scale> <kernel-substring> "<counters...>" [more bench args]
+R=$(cd "$(dirname "$0")/.." && pwd)
+mkdir -p $R/prof_out
 w=$1; sc=$2; kern=$3; ctrs=$4; shift 4
 cd /tmp && export TMPDIR=/tmp
-rm -rf /root/repo/gpurun_out/pmck
-rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d /root/repo/gpurun_out/pmck -- python /root/repo/bench.py --workload $w --scale $sc --steps 1 --warmup 1 --no-cpu-baseline --groups-in-flight 1 "$@" > /dev/null 2>&1
-cd /root/repo
+rm -rf $R/prof_out/pmck
+rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $R/prof_out/pmck -- python $R/bench.py --full --workload $w --scale $sc --steps 1 --warmup 1 --no-cpu-baseline --groups-in-flight 1 "$@" > /dev/null 2>&1
+cd $R
 KERN="$kern" python - <<'PY'
 import csv, glob, collections, os
-f = glob.glob("gpurun_out/pmck/*/*counter_collection.csv")[0]
+f = glob.glob("prof_out/pmck/*/*counter_collection.csv")[0]
 acc = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()
 for r in csv.DictReader(open(f)):
     if os.environ["KERN"] not in r["Kernel_Name"]: continue

@@ -1,13 +1,15 @@
 #!/bin/bash
 # usage (GPU box): tools/trace_rounds.sh <workload> <scale> : per-launch durations of the solver-round kernels of the longest solve
+R=$(cd "$(dirname "$0")/.." && pwd)
+mkdir -p $R/prof_out
 w=$1; sc=$2; shift 2
 cd /tmp && export TMPDIR=/tmp
-rm -rf /root/repo/gpurun_out/trr
-rocprofv3 --kernel-trace --output-format csv -d /root/repo/gpurun_out/trr -- python /root/repo/bench.py --workload $w --scale $sc --steps 1 --warmup 1 --no-cpu-baseline --groups-in-flight 1 "$@" > /dev/null 2>&1
-cd /root/repo
+rm -rf $R/prof_out/trr
+rocprofv3 --kernel-trace --output-format csv -d $R/prof_out/trr -- python $R/bench.py --full --workload $w --scale $sc --steps 1 --warmup 1 --no-cpu-baseline --groups-in-flight 1 "$@" > /dev/null 2>&1
+cd $R
 python - <<'PY'
 import csv, glob
-f = glob.glob("gpurun_out/trr/*/*kernel_trace.csv")[0]
+f = glob.glob("prof_out/trr/*/*kernel_trace.csv")[0]
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
 solves, cur = [], []
 for r in rows:
