@@ -98,6 +98,15 @@ PROTOTYPES = {
         ctypes.POINTER(c_vp), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
         ctypes.c_int32, ctypes.c_int32, c_i64p, ctypes.POINTER(c_i64p),
         ctypes.POINTER(c_f64p), ctypes.POINTER(c_i64p), c_i64p, c_i64p]),
+    "catchhip_rows_extend": (ctypes.c_int, [
+        c_vp, c_vp, c_vp, ctypes.c_int32, c_i32p, c_vpp, c_i64p]),
+    "catchhip_rows_fetch_gain0": (ctypes.c_int, [
+        c_vp, c_vp, ctypes.c_int64, c_u32p, c_i64p]),
+    "catchhip_setcover_grid": (ctypes.c_int, [
+        c_vp, c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+        ctypes.c_int32, ctypes.c_int32, c_i32p, ctypes.c_int64, c_i64p, c_f64p,
+        ctypes.POINTER(c_i64p), c_i64p, c_i64p]),
+    "catchhip_ctx_last_grid_counters": (ctypes.c_int, [c_vp, c_i64p]),
     "catchhip_comm_unique_id": (ctypes.c_int, [c_u8p]),
     "catchhip_comm_init": (ctypes.c_int, [
         c_vp, c_u8p, ctypes.c_int32, ctypes.c_int32]),

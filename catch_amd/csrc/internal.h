@@ -123,6 +123,7 @@ struct catchhip_ctx {
     i64 solver_counters[4] = {};   // row-parallel solver: records streamed, rows counted again, bitmap words read, owner words looked at
     i64 seeds_dropped = 0;   // of counters[1]: work-list entries the seed look-up's anchor-pair filter left empty
     i64 join_counters[4] = {};     // last key-grouped join: hit positions, pairs verified, lane slots of wave-wide runs, tasks of cut runs
+    i64 grid_counters[4] = {};     // last catchhip_setcover_grid: scans, derived tables, solves, rows of the e = 0 scan
     // pinned staging word(s) for small device->host reads
     u64 *h_pin = nullptr;
     // larger pinned staging area (grown on demand) so that result read-backs are
@@ -235,6 +236,9 @@ struct catchhip_rows {
     // the scan's probes / targets carried group numbers (a union of independent instances, catchhip_*_set_groups): its
     // coordinate space is a row of unlike groups, which the row-parallel solver cuts into more, smaller tiles
     bool grouped = false;
+    // cover extension of the merged rows of a cover scan (or of catchhip_rows_extend); -1: anything else (host rows,
+    // unmerged ranges, deferred rows) -- catchhip_rows_extend derives only from rows made at 0
+    i32 ext = -1;
     DevBuf<u32> info;
     mutable double seed_ratio_seen = 0.0;   // filled by the deferred solve: seeds per target base of the scan
     DevBuf<i32> set_id;

@@ -2172,6 +2172,7 @@ static int cover_scan_impl(catchhip_ctx *ctx, const catchhip_probes *P, const ca
     R->ngenomes = T->ngenomes;
     R->h_genome_off = T->h_genome_off;
     R->grouped = P->has_groups && T->has_groups;
+    R->ext = merge ? cover_extension : -1;
     int rc = 0;
     do {
         if ((rc = R->genome_off.alloc((size_t)T->ngenomes + 1))) break;

@@ -217,6 +217,12 @@ class Context:
                       "flat_owner_words"), (int(x) for x in sc)))
         return d
 
+    def grid_counters(self):
+        """catchhip_ctx_last_grid_counters of the last setcover_grid call."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._L.catchhip_ctx_last_grid_counters(self._h, _ptr(out, c_i64p)))
+        return dict(zip(("scans", "derived", "solves", "rows0"), (int(x) for x in out)))
+
     def pyset_order(self, hashes):
         """catchhip_pyset_order_device: engine.pyset_order computed on the device."""
         h = np.ascontiguousarray(hashes, dtype=np.int64)
@@ -666,6 +672,29 @@ class Rows:
             _ptr(en, c_i64p), n, _ptr(gl, c_i64p), ng, ctypes.byref(h)))
         return Rows(ctx, h, n)
 
+    def extend(self, targets, cover_extensions):
+        """catchhip_rows_extend: these rows (a cover scan at cover_extension 0)
+        at every extension given -> one Rows per extension, equal to a scan of
+        the same probes and targets at that extension."""
+        ext = np.ascontiguousarray(cover_extensions, dtype=np.int32)
+        n = int(ext.size)
+        hs = (ctypes.c_void_p * max(n, 1))()
+        nr = np.zeros(max(n, 1), dtype=np.int64)
+        check(self.ctx._L.catchhip_rows_extend(
+            self.ctx._h, self._h, targets._h, n,
+            _ptr(ext, c_i32p) if n else None, hs, _ptr(nr, c_i64p)))
+        return [Rows(self.ctx, ctypes.c_void_p(hs[i]), nr[i]) for i in range(n)]
+
+    def fetch_gain0(self, num_sets):
+        """catchhip_rows_fetch_gain0 -> uint32[min(num_sets, held)] (None: the rows hold no gain0)."""
+        out = np.zeros(max(int(num_sets), 1), dtype=np.uint32)
+        held = ctypes.c_int64(0)
+        check(self.ctx._L.catchhip_rows_fetch_gain0(self.ctx._h, self._h, int(num_sets), _ptr(out, c_u32p),
+                                                    ctypes.byref(held)))
+        if held.value == 0:
+            return None
+        return out[:min(int(num_sets), held.value)]
+
     def fetch(self):
         n = max(self.n, 1)
         si = np.zeros(n, np.int32); un = np.zeros(n, np.int32)
@@ -1021,6 +1050,30 @@ def setcover_filter_many(groups, mismatches, lcf_thres, island,
 
 
 _solution_checks = None
+
+
+def setcover_grid(ctx, probes, targets, mismatches, lcf_thres, island,
+                  cover_extensions, num_sets, ranks=None, universe_p=None,
+                  mode=SCAN_AUTO):
+    """catchhip_setcover_grid: one scan at cover extension 0, the rows at
+    every extension derived from it and solved.  Returns [(picked set ids in
+    pick order, number of cover rows)] per extension."""
+    ext = np.ascontiguousarray(cover_extensions, dtype=np.int32)
+    n = int(ext.size)
+    num_sets = int(num_sets)
+    outs = [np.zeros(max(num_sets, 1), dtype=np.int64) for _ in range(n)]
+    out_p = (c_i64p * max(n, 1))(*[_ptr(o, c_i64p) for o in outs])
+    n_out = np.zeros(max(n, 1), dtype=np.int64)
+    nrows = np.zeros(max(n, 1), dtype=np.int64)
+    rk = None if ranks is None else np.ascontiguousarray(ranks, np.int64)
+    up = None if universe_p is None else np.ascontiguousarray(universe_p, np.float64)
+    check(ctx._L.catchhip_setcover_grid(
+        ctx._h, probes._h, targets._h, int(mismatches), int(lcf_thres),
+        int(island), int(mode), n, _ptr(ext, c_i32p) if n else None, num_sets,
+        None if rk is None else _ptr(rk, c_i64p),
+        None if up is None else _ptr(up, c_f64p), out_p,
+        _ptr(n_out, c_i64p), _ptr(nrows, c_i64p)))
+    return [(outs[i][:n_out[i]].tolist(), int(nrows[i])) for i in range(n)]
 
 
 def collect_solution_checks(sink):

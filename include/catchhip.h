@@ -256,6 +256,47 @@ int catchhip_setcover_filter_many(int32_t n, catchhip_ctx *const *ctxs,
                                   int64_t *const *out_ids, int64_t *n_out,
                                   int64_t *nrows);
 
+/* ---- grid design: several cover extensions from one scan ----------------
+ * Replaces the cover extension of SetCoverFilter._make_sets
+ * (catch/filter/set_cover_filter.py:424-453 + catch/utils/interval.py
+ * :288-316: every cover range extended by e, clipped to its sequence, the
+ * ranges of a (set, universe) normalised) for n_ext values of e at once, from
+ * the rows of ONE catchhip_cover_scan made with cover_extension = 0: row [s, t)
+ * becomes [max(seqstart(s), s - e), min(seqend(t - 1), t + e)) and rows that
+ * then overlap or touch merge.  The reference has no counterpart: it runs its
+ * scan again for every e (README option #3 runs design.py once per grid point).
+ * out[n_ext] receives n_ext row objects (for catchhip_setcover_greedy,
+ * catchhip_rows_fetch, catchhip_rows_destroy), equal row for row to a scan at
+ * that e, and nrows[n_ext] (may be NULL) their row counts.  CATCHHIP_EINVAL for a negative e, rows0 not from a cover scan at
+ * e = 0, rows of a scan with group numbers (a union), or other targets. */
+int catchhip_rows_extend(catchhip_ctx *ctx, const catchhip_rows *rows0,
+                         const catchhip_targets *targets, int32_t n_ext,
+                         const int32_t *ext, catchhip_rows **out,
+                         int64_t *nrows);
+/* gain0 of a rows object (per set id, the total length of its rows: the first
+ * round's gains of a full-coverage solve; setcover_flat.inc reads it instead
+ * of counting): copies min(n, *n_out) entries; *n_out = entries held (0: none).
+ * No reference counterpart (the reference counts every round). */
+int catchhip_rows_fetch_gain0(catchhip_ctx *ctx, const catchhip_rows *rows,
+                              int64_t n, uint32_t *gain0, int64_t *n_out);
+/* One (probes, targets, mismatches) instance over n_ext cover extensions: the
+ * reference's design.py run once per e (set_cover_filter.py:816-846 each time).
+ * Scans once at e = 0, derives the rows at each ext[i] (catchhip_rows_extend,
+ * one table at a time, the rows never leave the device) and solves each with
+ * ranks / universe_p as catchhip_setcover_greedy: out_ids[i] (room for
+ * num_sets ids), n_out[i], nrows[i] (may be NULL) per extension.  Test hook
+ * CATCHHIP_GRID_RESCAN=1 scans afresh at each e instead. */
+int catchhip_setcover_grid(catchhip_ctx *ctx, const catchhip_probes *probes,
+                           const catchhip_targets *targets, int32_t mismatches,
+                           int32_t lcf_thres, int32_t island, int32_t mode,
+                           int32_t n_ext, const int32_t *ext, int64_t num_sets,
+                           const int64_t *ranks, const double *universe_p,
+                           int64_t *const *out_ids, int64_t *n_out,
+                           int64_t *nrows);
+/* Work of the last catchhip_setcover_grid on this context, 4 values: cover
+ * scans, derived row tables, solves, rows of the e = 0 scan. */
+int catchhip_ctx_last_grid_counters(catchhip_ctx *ctx, int64_t *out4);
+
 /* Multi-GPU, one process per GPU: an RCCL communicator attached to a context
  * (the reference has no counterpart: it forks a process pool,
  * catch/probe.py:727-743, catch/filter/set_cover_filter.py:848-900).  With a
