@@ -50,7 +50,7 @@ void chip_set_error(const char *fmt, ...);
 // Environment switches.  Four are part of the product and read with getenv(): CATCHHIP_TIMING (host-side wall
 // times on stderr), CATCHHIP_RCCL_PATH, CATCHHIP_POOL_SOFT_LIMIT_GB, CATCHHIP_GATHER_THREADS (README.md lists them
 // with the Python side's).  Everything else is a TEST HOOK -- it forces one of several exact code paths (the radix
-// row build, the set-parallel solver on a large instance, striped tiles ...) so that tests/ and bench.py can
+// row build, the fused solver on a large instance, striped tiles ...) so that tests/ and bench.py can
 // compare them -- and is only honoured when CATCHHIP_TEST_HOOKS=1 is set (tests/conftest.py and bench.py do).
 static inline const char *chip_test_env(const char *name) {
     static const bool on = [] { const char *e = getenv("CATCHHIP_TEST_HOOKS"); return e && atoi(e) != 0; }();
@@ -297,6 +297,8 @@ struct PhaseTimer {
 // if total != nullptr, *total (device u64) receives the grand total.
 int chip_exclusive_scan_u32(catchhip_ctx *ctx, const u32 *in, u32 *out, i64 n,
                             DevBuf<u32> &tmp);
+// the scratch that scan needs for up to n values, reserved in tmp ahead of time
+int chip_exclusive_scan_reserve(DevBuf<u32> &tmp, i64 n);
 // Stable LSD radix sort of (u64 key, u32 value) pairs on bits [first_bit, first_bit + key_bits).
 // Result ends in keys/vals (the alt buffers are scratch of the same size).
 int chip_radix_sort_pairs(catchhip_ctx *ctx, DevBuf<u64> &keys, DevBuf<u64> &keys_alt,

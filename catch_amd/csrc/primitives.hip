@@ -94,12 +94,16 @@ static int scan_rec(catchhip_ctx *ctx, const u32 *in, u32 *out, i64 n, u32 *tmp,
     return 0;
 }
 
-int chip_exclusive_scan_u32(catchhip_ctx *ctx, const u32 *in, u32 *out, i64 n, DevBuf<u32> &tmp) {
-    if (n <= 0) return 0;
+int chip_exclusive_scan_reserve(DevBuf<u32> &tmp, i64 n) {
     i64 need = 0;
     for (i64 m = div_up(n, SCAN_TILE); m > 1; m = div_up(m, SCAN_TILE)) need += m;
     need += 4;
-    TRY(tmp.reserve((size_t)need));
+    return tmp.reserve((size_t)need);
+}
+
+int chip_exclusive_scan_u32(catchhip_ctx *ctx, const u32 *in, u32 *out, i64 n, DevBuf<u32> &tmp) {
+    if (n <= 0) return 0;
+    TRY(chip_exclusive_scan_reserve(tmp, n));
     TRY(scan_rec(ctx, in, out, n, tmp.p, (i64)tmp.n));
     HIP_TRY(hipGetLastError());
     return 0;

@@ -11,7 +11,7 @@
 // iteration order of the reference's set of dense ids), ranks gate which sets
 // may be considered (set_cover.py:497-526).
 //
-// Three solvers, all exact (catchhip_setcover_greedy picks one):
+// Two solvers, all exact (catchhip_setcover_greedy picks one):
 //
 // Frontier rounds (setcover_batched.inc; every universe fully covered -- the
 // default): all locally-maximal sets are accepted per
@@ -28,10 +28,8 @@
 // remaining-need became binding re-evaluates min(left, count) for their
 // segments, (5) refreshes the dirty blocks of the max structure.
 //
-// Multi-GPU solver (catchhip_comm_init): rank r evaluates the sets
-// s % nranks == r with a full-recompute gain kernel, the winner is agreed by
-// one RCCL all-reduce(MAX) of the packed 64-bit (gain, ~id) key per pick, and
-// every rank applies it to its replica of the bitmap.
+// One instance with its universes sharded over GPUs runs the frontier rounds
+// with an all-reduce between their launches (setcover_sharded.inc).
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -157,15 +155,13 @@ seg_flag_kernel(const i32 *__restrict__ row_set, const i32 *__restrict__ row_uni
 
 __global__ void __launch_bounds__(256)
 seg_fill_kernel(const u32 *__restrict__ flag, const u32 *__restrict__ idx, const i32 *__restrict__ row_set,
-                const i32 *__restrict__ row_univ, u32 nrows, u32 nseg, u32 *__restrict__ seg_row,
-                u32 *__restrict__ seg_univ, u32 *__restrict__ seg_set, u32 *__restrict__ row_seg) {
+                const i32 *__restrict__ row_univ, u32 nrows, u32 *__restrict__ seg_univ, u32 *__restrict__ seg_set,
+                u32 *__restrict__ row_seg) {
     u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r == 0) seg_row[nseg] = nrows;
     if (r >= nrows) return;
     u32 q = idx[r] + flag[r] - 1;  // segment of this row
     row_seg[r] = q;
     if (!flag[r]) return;
-    seg_row[q] = r;
     seg_univ[q] = (u32)row_univ[r];
     seg_set[q] = (u32)row_set[r];
 }
@@ -662,99 +658,6 @@ greedy_wg_kernel(GreedyArgs a) {
 #include "setcover_flat.inc"
 
 // ------------------------------------------------------------------------
-// multi-launch solver (one gain launch + one apply launch per pick); used when
-// the candidate sets are sharded over several GPUs
-// ------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-gain_kernel(const u64 *__restrict__ bm, const u32 *__restrict__ gs, const u32 *__restrict__ ge,
-            const u32 *__restrict__ seg_row, const u32 *__restrict__ seg_univ,
-            const u32 *__restrict__ set_seg_ptr, const u32 *__restrict__ left,
-            const u32 *__restrict__ rank, const u32 *__restrict__ picked, u32 nsets, u32 nranks,
-            u32 myrank, GreedyState *__restrict__ st) {
-    __shared__ unsigned long long wkey[4];
-    if (st->done) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u32 slot = blockIdx.x * 4 + wave;
-    const u32 s = slot * nranks + myrank;
-    unsigned long long key = 0;
-    if (s < nsets && !picked[s] && rank[s] == st->cur_rank) {
-        u32 g = 0;
-        const u32 sb = set_seg_ptr[s], se = set_seg_ptr[s + 1];
-        for (u32 q = sb + lane; q < se; q += WAVE) {
-            u32 c = 0;
-            for (u32 r = seg_row[q]; r < seg_row[q + 1]; ++r) c += range_popcount(bm, gs[r], ge[r]);
-            u32 l = left[seg_univ[q]];
-            g += c < l ? c : l;
-        }
-        unsigned long long g64 = g;
-        for (int d = 32; d > 0; d >>= 1) g64 += __shfl_down(g64, d, WAVE);
-        if (lane == 0 && g64 > 0) key = (g64 << ID_BITS) | (unsigned long long)(ID_MASK - s);
-    }
-    if (lane == 0) wkey[wave] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long k = wkey[0];
-        k = wkey[1] > k ? wkey[1] : k;
-        k = wkey[2] > k ? wkey[2] : k;
-        k = wkey[3] > k ? wkey[3] : k;
-        if (k) atomicMax(&st->best_key, k);
-    }
-}
-
-__global__ void __launch_bounds__(256)
-apply_kernel(unsigned long long *__restrict__ bm, const u32 *__restrict__ gs, const u32 *__restrict__ ge,
-             const i32 *__restrict__ row_univ, const u32 *__restrict__ set_ptr,
-             const u32 *__restrict__ seg_univ, const u32 *__restrict__ set_seg_ptr, u32 *__restrict__ usize,
-             const u32 *__restrict__ can, u32 *__restrict__ left, u32 *__restrict__ picked,
-             u32 *__restrict__ picks, GreedyState *__restrict__ st) {
-    if (st->done) return;
-    const unsigned long long key = st->best_key;
-    __syncthreads();
-    if ((key >> ID_BITS) == 0) {
-        if (threadIdx.x == 0) {
-            st->best_key = 0;
-            st->iters++;
-            st->cur_rank++;
-            if (st->cur_rank >= st->nrank) st->done = 2;
-        }
-        return;
-    }
-    const u32 s = ID_MASK - (u32)(key & ID_MASK);
-    for (u32 r = set_ptr[s] + threadIdx.x; r < set_ptr[s + 1]; r += blockDim.x) {
-        u32 a = gs[r], e = ge[r];
-        u32 w0 = a >> 6, w1 = (e - 1) >> 6;
-        u32 cleared = 0;
-        for (u32 w = w0; w <= w1; ++w) {
-            u64 m = ~0ull;
-            if (w == w0) m &= ~0ull << (a & 63);
-            if (w == w1) m &= ~0ull >> (63 - ((e - 1) & 63));
-            u64 old = atomicAnd(&bm[w], ~m);
-            cleared += (u32)__popcll(old & m);
-        }
-        if (cleared) atomicSub(&usize[row_univ[r]], cleared);
-    }
-    __syncthreads();
-    for (u32 q = set_seg_ptr[s] + threadIdx.x; q < set_seg_ptr[s + 1]; q += blockDim.x) {
-        u32 u = seg_univ[q];
-        u32 n = LD(&usize[u]);
-        u32 c = can[u];
-        u32 nl = n > c ? n - c : 0u;
-        u32 ol = left[u];
-        left[u] = nl;
-        if (ol > 0 && nl == 0) atomicSub(&st->n_need, 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        picked[s] = 1;
-        picks[st->npicks] = s;
-        st->npicks++;
-        st->iters++;
-        st->best_key = 0;
-        if (LD(&st->n_need) == 0) st->done = 1;
-    }
-}
-
-// ------------------------------------------------------------------------
 // Which RCCL.  A process that imported torch first has torch's own librccl mapped
 // under the same soname this library was linked against, and the loader would
 // bind these calls to whichever copy came first.  The communicator therefore goes
@@ -1097,8 +1000,6 @@ extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *
     HIP_TRY(hipSetDevice(ctx->device));
     const u32 nrows = (u32)R->n, nsets = (u32)num_sets, nuniv = (u32)R->ngenomes;
     hipStream_t s = ctx->stream;
-    // a communicator (even of one rank) selects the sharded multi-launch solver
-    const bool distributed = ctx->comm != nullptr;
 
     std::vector<u32> h_rank;
     const u32 nrank = dense_ranks(ranks, nsets, h_rank);
@@ -1111,7 +1012,7 @@ extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *
 
     // every universe fully covered: batched rounds (many independent picks per
     // round); otherwise one pick per iteration
-    bool batched = !distributed && !chip_test_env("CATCHHIP_GREEDY_SEQUENTIAL");
+    bool batched = !chip_test_env("CATCHHIP_GREEDY_SEQUENTIAL");
     if (universe_p)
         for (u32 u = 0; u < nuniv && batched; ++u) batched = universe_p[u] == 1.0;
 
@@ -1132,11 +1033,11 @@ extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *
     // row-parallel kernels with the universe test (setcover_flat.inc, "PARTIAL") whatever the size --
     // the one-workgroup solvers below take 3.9 ms per pick on S4's largest group (54.6 s for S4 under
     // -c 0.9 against 0.17 s under -c 1.0)
-    if (universe_p && !distributed && R->lmax <= 257 && nsets <= GR_MAX_SETS && !chip_test_env("CATCHHIP_GREEDY_SEQUENTIAL") &&
+    if (universe_p && R->lmax <= 257 && nsets <= GR_MAX_SETS && !chip_test_env("CATCHHIP_GREEDY_SEQUENTIAL") &&
         !chip_test_env("CATCHHIP_PARTIAL_SEQUENTIAL") && (i64)nrows >= (chip_test_env("CATCHHIP_PARTIAL_MIN_ROWS") ? atoll(chip_test_env("CATCHHIP_PARTIAL_MIN_ROWS")) : 0))
         return greedy_flat(ctx, R, nsets, ranks ? h_rank.data() : nullptr, nrank, out_ids, n_out, universe_p);
 
-    DevBuf<u32> set_ptr, flag, idx, tmp, seg_row, seg_univ, seg_set, row_seg, set_seg_ptr, usize, can, left, rank,
+    DevBuf<u32> set_ptr, flag, idx, tmp, seg_univ, seg_set, row_seg, set_seg_ptr, usize, can, left, rank,
         picked, picks;
     DevBuf<unsigned long long> bm;
     DevBuf<double> d_p;
@@ -1176,124 +1077,87 @@ extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *
     tm.launch(5);
     HIP_TRY(hipGetLastError());
 
-    u32 nseg = 0;
-    if (!batched) {
-        // (set, universe) segments of the row table
-        TRY(flag.alloc(nrows));
-        TRY(idx.alloc(nrows));
-        TRY(row_seg.alloc(nrows));
-        TRY(set_seg_ptr.alloc(nsets + 1));
-        hipLaunchKernelGGL(seg_flag_kernel, dim3(rb), dim3(256), 0, s, R->set_id.p, R->univ.p, R->gs.p, R->ge.p, nrows,
-                           flag.p, st.p);
-        TRY(chip_exclusive_scan_u32(ctx, flag.p, idx.p, nrows, tmp));
-        HIP_TRY(hipMemcpyAsync(ctx->h_pin, idx.p + (nrows - 1), sizeof(u32), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync((u32 *)ctx->h_pin + 1, flag.p + (nrows - 1), sizeof(u32), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        nseg = ((volatile u32 *)ctx->h_pin)[0] + ((volatile u32 *)ctx->h_pin)[1];
-        TRY(seg_row.alloc(nseg + 1));
-        TRY(seg_univ.alloc(nseg + 1));
-        TRY(seg_set.alloc(nseg + 1));
-        hipLaunchKernelGGL(seg_fill_kernel, dim3(rb), dim3(256), 0, s, flag.p, idx.p, R->set_id.p, R->univ.p, nrows, nseg,
-                           seg_row.p, seg_univ.p, seg_set.p, row_seg.p);
-        hipLaunchKernelGGL(set_seg_ptr_kernel, dim3(sb), dim3(256), 0, s, set_ptr.p, idx.p, nrows, nsets, nseg,
-                           set_seg_ptr.p);
-        tm.launch(6);
-    }
-    int rc = 0;
-    if (!distributed) {
-        // ---- persistent single-workgroup solver ---------------------------
-        DevBuf<u32> prowcnt, segcnt, segcontrib, gain, dirty, pos_row, pos_row_alt, useg, useg_alt, useg_ptr,
-            bucket;
-        DevBuf<u64> pos_key, pos_key_alt, ukeys, ukeys_alt;
-        DevBuf<uint4> pent, wrow;
-        const u32 nbuckets = (u32)(R->total >> BUCKET_SHIFT) + 2;
-        TRY(prowcnt.alloc(nrows));
-        TRY(segcnt.alloc(nseg));
-        TRY(segcontrib.alloc(nseg));
-        TRY(gain.alloc(nsets));
-        TRY(dirty.alloc(nrows));
-        TRY(pos_key.alloc(nrows));
-        TRY(pos_row.alloc(nrows));
-        TRY(pent.alloc(nrows));
-        TRY(wrow.alloc(nrows));
-        TRY(bucket.alloc(nbuckets));
-        TRY(ukeys.alloc(nseg));
-        TRY(useg.alloc(nseg));
-        TRY(useg_ptr.alloc(nuniv + 1));
-        HIP_TRY(hipMemsetAsync(segcnt.p, 0, sizeof(u32) * nseg, s));
-        hipLaunchKernelGGL(rowcnt_init_kernel, dim3(rb), dim3(256), 0, s, R->gs.p, R->ge.p, row_seg.p, nrows, segcnt.p);
-        hipLaunchKernelGGL(seg_init_kernel, dim3((unsigned)div_up(nseg, 256)), dim3(256), 0, s, segcnt.p, seg_univ.p,
-                           seg_set.p, left.p, nseg, segcontrib.p, st.p, ukeys.p, useg.p);
-        hipLaunchKernelGGL(gain_init_kernel, dim3(sb), dim3(256), 0, s, segcontrib.p, set_seg_ptr.p, nsets, gain.p);
-        hipLaunchKernelGGL(wrow_fill_kernel, dim3(rb), dim3(256), 0, s, R->gs.p, R->ge.p, R->set_id.p, R->univ.p,
-                           row_seg.p, can.p, nrows, wrow.p);
-        hipLaunchKernelGGL(pos_key_kernel, dim3(rb), dim3(256), 0, s, R->gs.p, nrows, pos_key.p, pos_row.p);
-        TRY(chip_radix_sort_pairs(ctx, pos_key, pos_key_alt, pos_row, pos_row_alt, nrows,
-                                  std::max(1, ceil_log2_u64((u64)R->total + 1))));
-        hipLaunchKernelGGL(pent_fill_kernel, dim3(rb), dim3(256), 0, s, pos_row.p, R->gs.p, R->ge.p, R->set_id.p,
-                           row_seg.p, nrows, pent.p, prowcnt.p);
-        hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)div_up(nbuckets, 256)), dim3(256), 0, s, pos_key.p, nrows,
-                           nbuckets, BUCKET_SHIFT, bucket.p);
-        TRY(chip_radix_sort_pairs(ctx, ukeys, ukeys_alt, useg, useg_alt, nseg,
-                                  std::max(1, ceil_log2_u64((u64)nuniv + 1))));
-        hipLaunchKernelGGL(useg_ptr_kernel, dim3((unsigned)div_up(nuniv + 1, 256)), dim3(256), 0, s, ukeys.p, nseg,
-                           nuniv, useg_ptr.p);
-        GreedyArgs a;
-        a.bm = bm.p; a.wrow = wrow.p; a.set_ptr = set_ptr.p; a.set_seg_ptr = set_seg_ptr.p;
-        a.seg_univ = seg_univ.p; a.seg_set = seg_set.p; a.pent = pent.p; a.prowcnt = prowcnt.p;
-        a.bucket = bucket.p; a.useg_ptr = useg_ptr.p; a.useg = useg.p; a.can = can.p;
-        a.rank = rank.p; a.usize = usize.p; a.left = left.p; a.segcnt = segcnt.p; a.segcontrib = segcontrib.p;
-        a.gain = gain.p; a.picked = picked.p; a.picks = picks.p; a.dirty = dirty.p; a.st = st.p;
-        a.nrows = nrows; a.nsets = nsets; a.nuniv = nuniv; a.chunk = (u32)div_up(nsets, GW_THREADS);
-        hipLaunchKernelGGL(greedy_wg_kernel, dim3(1), dim3(GW_THREADS), 0, s, a);
-        tm.launch(6);
-        tm.stop();
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&h_st, st.p, sizeof(h_st), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        tm.finish();
-        ctx->phase_launches[PHASE_GREEDY] = h_st.iters;  // greedy iterations inside the persistent launch
-        ctx->counters[2] = h_st.iters; ctx->counters[3] = h_st.npicks; ctx->counters[4] = (i64)h_st.n_wrows;
-        ctx->counters[5] = (i64)h_st.n_recount; ctx->counters[6] = (i64)h_st.n_words;
+    // (set, universe) segments of the row table
+    TRY(flag.alloc(nrows));
+    TRY(idx.alloc(nrows));
+    TRY(row_seg.alloc(nrows));
+    TRY(set_seg_ptr.alloc(nsets + 1));
+    hipLaunchKernelGGL(seg_flag_kernel, dim3(rb), dim3(256), 0, s, R->set_id.p, R->univ.p, R->gs.p, R->ge.p, nrows,
+                       flag.p, st.p);
+    TRY(chip_exclusive_scan_u32(ctx, flag.p, idx.p, nrows, tmp));
+    HIP_TRY(hipMemcpyAsync(ctx->h_pin, idx.p + (nrows - 1), sizeof(u32), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync((u32 *)ctx->h_pin + 1, flag.p + (nrows - 1), sizeof(u32), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const u32 nseg = ((volatile u32 *)ctx->h_pin)[0] + ((volatile u32 *)ctx->h_pin)[1];
+    TRY(seg_univ.alloc(nseg + 1));
+    TRY(seg_set.alloc(nseg + 1));
+    hipLaunchKernelGGL(seg_fill_kernel, dim3(rb), dim3(256), 0, s, flag.p, idx.p, R->set_id.p, R->univ.p, nrows,
+                       seg_univ.p, seg_set.p, row_seg.p);
+    hipLaunchKernelGGL(set_seg_ptr_kernel, dim3(sb), dim3(256), 0, s, set_ptr.p, idx.p, nrows, nsets, nseg,
+                       set_seg_ptr.p);
+    tm.launch(6);
+    // ---- persistent single-workgroup solver ---------------------------
+    DevBuf<u32> prowcnt, segcnt, segcontrib, gain, dirty, pos_row, pos_row_alt, useg, useg_alt, useg_ptr,
+        bucket;
+    DevBuf<u64> pos_key, pos_key_alt, ukeys, ukeys_alt;
+    DevBuf<uint4> pent, wrow;
+    const u32 nbuckets = (u32)(R->total >> BUCKET_SHIFT) + 2;
+    TRY(prowcnt.alloc(nrows));
+    TRY(segcnt.alloc(nseg));
+    TRY(segcontrib.alloc(nseg));
+    TRY(gain.alloc(nsets));
+    TRY(dirty.alloc(nrows));
+    TRY(pos_key.alloc(nrows));
+    TRY(pos_row.alloc(nrows));
+    TRY(pent.alloc(nrows));
+    TRY(wrow.alloc(nrows));
+    TRY(bucket.alloc(nbuckets));
+    TRY(ukeys.alloc(nseg));
+    TRY(useg.alloc(nseg));
+    TRY(useg_ptr.alloc(nuniv + 1));
+    HIP_TRY(hipMemsetAsync(segcnt.p, 0, sizeof(u32) * nseg, s));
+    hipLaunchKernelGGL(rowcnt_init_kernel, dim3(rb), dim3(256), 0, s, R->gs.p, R->ge.p, row_seg.p, nrows, segcnt.p);
+    hipLaunchKernelGGL(seg_init_kernel, dim3((unsigned)div_up(nseg, 256)), dim3(256), 0, s, segcnt.p, seg_univ.p,
+                       seg_set.p, left.p, nseg, segcontrib.p, st.p, ukeys.p, useg.p);
+    hipLaunchKernelGGL(gain_init_kernel, dim3(sb), dim3(256), 0, s, segcontrib.p, set_seg_ptr.p, nsets, gain.p);
+    hipLaunchKernelGGL(wrow_fill_kernel, dim3(rb), dim3(256), 0, s, R->gs.p, R->ge.p, R->set_id.p, R->univ.p,
+                       row_seg.p, can.p, nrows, wrow.p);
+    hipLaunchKernelGGL(pos_key_kernel, dim3(rb), dim3(256), 0, s, R->gs.p, nrows, pos_key.p, pos_row.p);
+    TRY(chip_radix_sort_pairs(ctx, pos_key, pos_key_alt, pos_row, pos_row_alt, nrows,
+                              std::max(1, ceil_log2_u64((u64)R->total + 1))));
+    hipLaunchKernelGGL(pent_fill_kernel, dim3(rb), dim3(256), 0, s, pos_row.p, R->gs.p, R->ge.p, R->set_id.p,
+                       row_seg.p, nrows, pent.p, prowcnt.p);
+    hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)div_up(nbuckets, 256)), dim3(256), 0, s, pos_key.p, nrows,
+                       nbuckets, BUCKET_SHIFT, bucket.p);
+    TRY(chip_radix_sort_pairs(ctx, ukeys, ukeys_alt, useg, useg_alt, nseg,
+                              std::max(1, ceil_log2_u64((u64)nuniv + 1))));
+    hipLaunchKernelGGL(useg_ptr_kernel, dim3((unsigned)div_up(nuniv + 1, 256)), dim3(256), 0, s, ukeys.p, nseg,
+                       nuniv, useg_ptr.p);
+    GreedyArgs a;
+    a.bm = bm.p; a.wrow = wrow.p; a.set_ptr = set_ptr.p; a.set_seg_ptr = set_seg_ptr.p;
+    a.seg_univ = seg_univ.p; a.seg_set = seg_set.p; a.pent = pent.p; a.prowcnt = prowcnt.p;
+    a.bucket = bucket.p; a.useg_ptr = useg_ptr.p; a.useg = useg.p; a.can = can.p;
+    a.rank = rank.p; a.usize = usize.p; a.left = left.p; a.segcnt = segcnt.p; a.segcontrib = segcontrib.p;
+    a.gain = gain.p; a.picked = picked.p; a.picks = picks.p; a.dirty = dirty.p; a.st = st.p;
+    a.nrows = nrows; a.nsets = nsets; a.nuniv = nuniv; a.chunk = (u32)div_up(nsets, GW_THREADS);
+    hipLaunchKernelGGL(greedy_wg_kernel, dim3(1), dim3(GW_THREADS), 0, s, a);
+    tm.launch(6);
+    tm.stop();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h_st, st.p, sizeof(h_st), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    tm.finish();
+    ctx->phase_launches[PHASE_GREEDY] = h_st.iters;  // greedy iterations inside the persistent launch
+    ctx->counters[2] = h_st.iters; ctx->counters[3] = h_st.npicks; ctx->counters[4] = (i64)h_st.n_wrows;
+    ctx->counters[5] = (i64)h_st.n_recount; ctx->counters[6] = (i64)h_st.n_words;
 #ifdef CATCHHIP_PROFILE
-        if (chip_test_env("CATCHHIP_PROF")) {
-            fprintf(stderr, "[catchhip] greedy wg: iters=%u picks=%u ms=%.3f ticks/iter:", h_st.iters, h_st.npicks,
-                    ctx->phase_ms[PHASE_GREEDY]);
-            for (int i = 0; i < 4; ++i) fprintf(stderr, " p%d=%.0f", i, (double)h_st.prof[i] / (h_st.iters ? h_st.iters : 1));
-            fprintf(stderr, "\n");
-        }
-#endif
-    } else {
-        const u32 nranks = (u32)ctx->nranks, myrank = (u32)ctx->rank;
-        const u32 my_sets = (u32)div_up((i64)nsets, nranks);
-        const unsigned gb = (unsigned)div_up(my_sets, 4);
-        const int BATCH = 64;
-        const i64 max_iters = (i64)nsets + nrank + 2;
-        i64 issued = 0;
-        for (;;) {
-            for (int b = 0; b < BATCH; ++b) {
-                hipLaunchKernelGGL(gain_kernel, dim3(gb), dim3(256), 0, s, (const u64 *)bm.p, R->gs.p, R->ge.p,
-                                   seg_row.p, seg_univ.p, set_seg_ptr.p, left.p, rank.p, picked.p, nsets, nranks,
-                                   myrank, st.p);
-                ncclResult_t r = rccl().AllReduce(&st.p->best_key, &st.p->best_key, 1, ncclUint64, ncclMax,
-                                                  (ncclComm_t)ctx->comm, s);
-                if (r != ncclSuccess) { chip_set_error("ncclAllReduce: %s", rccl().GetErrorString(r)); return CATCHHIP_ECOMM; }
-                hipLaunchKernelGGL(apply_kernel, dim3(1), dim3(256), 0, s, bm.p, R->gs.p, R->ge.p, R->univ.p,
-                                   set_ptr.p, seg_univ.p, set_seg_ptr.p, usize.p, can.p, left.p, picked.p, picks.p,
-                                   st.p);
-            }
-            tm.launch(2 * BATCH);
-            issued += BATCH;
-            HIP_TRY(hipMemcpyAsync(&h_st, st.p, sizeof(h_st), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(hipGetLastError());
-            if (h_st.done) break;
-            if (issued > max_iters) { chip_set_error("setcover: iteration cap exceeded"); rc = CATCHHIP_EINVAL; break; }
-        }
-        tm.stop();
-        tm.finish();
+    if (chip_test_env("CATCHHIP_PROF")) {
+        fprintf(stderr, "[catchhip] greedy wg: iters=%u picks=%u ms=%.3f ticks/iter:", h_st.iters, h_st.npicks,
+                ctx->phase_ms[PHASE_GREEDY]);
+        for (int i = 0; i < 4; ++i) fprintf(stderr, " p%d=%.0f", i, (double)h_st.prof[i] / (h_st.iters ? h_st.iters : 1));
+        fprintf(stderr, "\n");
     }
-    if (rc) return rc;
+#endif
     if (h_st.done == 2) {
         chip_set_error("setcover: ranks exhausted while coverage is still required");
         return CATCHHIP_ERANK;

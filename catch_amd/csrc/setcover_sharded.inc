@@ -11,318 +11,89 @@
 // (BASELINE.json's "all-reduce of per-probe marginal coverage each greedy
 // iteration" -- per ROUND of the frontier solver, not per pick):
 //
-//   gs_count        local uncovered elements of every live set  -> gainbuf[s]
-//                   (+ gainbuf[nsets] = local universes still in need)
-//   all-reduce SUM  u32 x (nsets + 2)                           -> global gains
-//   gs_claim        key = (global gain, ~id); sets of the current rank raise
-//                   owner[word] to their key on THEIR local words
-//   gs_check        a claimant that lost a local word           -> lostbuf[s] = 1
-//   all-reduce MAX  u8 x nsets                                  -> lost anywhere
-//   gs_apply        claimants that lost nowhere are accepted on every rank:
+//   count           local uncovered elements of every live set  -> acc[s]
+//                   (+ acc[nsets] = local universes still in need)
+//   all-reduce SUM  u32 gains                                   -> global gains
+//   claim           key = (global gain, ~id); sets of the current rank raise
+//                   owner[word] to their key on THEIR local words, the losers
+//                   of a word are marked                         -> lost[s]
+//   all-reduce MAX  u8 lost marks                               -> lost anywhere
+//   apply           claimants that lost nowhere are accepted on every rank:
 //                   clear the local bits, credit the local universes, record
-//                   (set, key); build the next round's live lists
+//                   (set, key)
 //
-// gain[], picked[], claimed[], the rank under consideration and the pick set
-// are identical on all ranks after every round (they are functions of the
-// all-reduced buffers only), so no further agreement is needed; the picks are
-// put into the sequential order on the host by their keys, as in the
-// unsharded solver.  Rows of at most 257 bases; other groups are solved whole
-// on one rank (catch_amd/parallel.py).  Partial coverage (p < 1, round 4) is
-// sharded by the row-parallel kernels only: the universe test of a candidate
-// runs on every rank over its own universes (gr_verdict_kernel) and failures
-// travel as lost marks in a second exchange of that buffer before gs_apply /
-// gr_apply (catchhip_shard_verdict).
+// The kernels are the row-parallel ones of setcover_flat.inc in their sharded
+// mode (FlatArgs.sharded).  gain[], picked[], claimed[], the rank under
+// consideration and the pick set are identical on all ranks after every round
+// (they are functions of the all-reduced buffers only), so no further
+// agreement is needed; the picks are put into the sequential order on the host
+// by their keys, as in the unsharded solver.  Instances of at most 2^25 sets
+// with rows of at most 257 bases; other groups are solved whole on one rank
+// (catch_amd/parallel.py).  Partial coverage (p < 1): the universe test of a
+// candidate runs on every rank over its own universes (gr_verdict_kernel) and
+// failures travel as lost marks in a second exchange of that buffer before the
+// apply launch (catchhip_shard_verdict).
 //
-// Live sets: per tile of GS_TILE consecutive set ids the live ones are listed
-// at live[tile * GS_TILE ...] (count in tilecnt[tile]): deterministic, no
-// cursor atomics, and the buffers of the exchanges stay indexed by set id.
-#define GS_TILE 1024
+// Packed exchange.  A set whose GLOBAL gain has reached zero never gains again,
+// and only sets with a global gain can claim or lose: so the ranks exchange the
+// gains and lost marks of the sets that were alive at the last read-back -- a
+// list every rank derives from the same all-reduced gains, in set order (a set
+// that has died since carries zeros).  On S4's largest group (3.96 M sets, 19
+// rounds) that is ~4 x 16 MB of gains and ~4 x 4 MB of marks per solve instead
+// of 19 x (16 + 16) MB.  Rounds are queued in batches (catchhip_shard_solve: as
+// the unsharded solver queues them; the step API: batches of one round), the
+// list is compacted once per batch from the all-reduced gains of its last round,
+// and its new length comes back with the solver's state in the batch's one
+// read-back.  The done flag stops the launches of rounds queued beyond the end;
+// their collectives still run, on every rank alike (the batch length is the
+// same everywhere).
 
-struct ShardArgs {
-    unsigned long long *bm;
-    unsigned long long *owner[2];
-    const uint2 *frow;
-    const i32 *row_univ;
-    const u32 *set_ptr, *rank;
-    u32 *usize;
-    u32 *gain;          // global gains as of the last exchange
-    u32 *gainbuf;       // nsets + 2: local gains in, global gains out; [nsets] = universes in need
-    u8 *lostbuf;        // nsets
-    u32 *claimed, *picked, *picks;
-    unsigned long long *pick_key;
-    u8 *rowflag;
-    u32 *live[2], *tilecnt[2];
-    GreedyState *st;
-    u32 nsets, nwords, ntiles;
-};
-
-// the live sets of tile `tile` in round `round`: count and list base
-__device__ __forceinline__ u32 gs_tile_sets(const ShardArgs &a, u32 tile, u32 round, const u32 **list) {
-    const u32 t0 = tile * GS_TILE;
-    if (round == 0) { *list = nullptr; return min((u32)GS_TILE, a.nsets - t0); }
-    *list = a.live[round & 1] + t0;
-    return a.tilecnt[round & 1][tile];
-}
-
-template <int G>
-__global__ void __launch_bounds__(GF_THREADS)
-gs_count_kernel(ShardArgs a, u32 round) {
-    constexpr u32 GF_SETS = GF_THREADS / G;
-    GreedyState *st = a.st;
-    if (st->done) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { st->iters = round + 1; a.gainbuf[a.nsets] = st->n_need; }
-    const u32 sub = threadIdx.x & (G - 1), grp = threadIdx.x / G;
-    for (u32 tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const u32 *list;
-        const u32 n = gs_tile_sets(a, tile, round, &list);
-        for (u32 li = grp; li < n; li += GF_SETS) {
-            const u32 s = list ? list[li] : tile * GS_TILE + li;
-            const u32 pk = a.picked[s], r0 = a.set_ptr[s], r1 = a.set_ptr[s + 1];
-            if (pk) continue;   // gainbuf was zeroed
-            u32 cnt = 0;
-            for (u32 j = r0 + sub; j < r1; j += G) {
-                const u32 oldfl = round ? (u32)a.rowflag[j] : 1u;
-                const uint2 wr = a.frow[j];
-                if (oldfl == 0) continue;   // fully covered earlier
-                const u32 x = wr.x, e = wr.y;
-                const u32 w0 = x >> 6, nwd = ((e - 1) >> 6) - w0 + 1;
-                const u64 m0 = ~0ull << (x & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
-                u32 fl = 0;
-                if (round == 0) {
-                    cnt += e - x;
-                    fl = (1u << nwd) - 1u;
-                } else {
-                    u64 v[RP_MAXW];
-#pragma unroll
-                    for (u32 t = 0; t < RP_MAXW; ++t) v[t] = a.bm[w0 + min(t, nwd - 1)];
-#pragma unroll
-                    for (u32 t = 0; t < RP_MAXW; ++t) {
-                        u64 m = ~0ull;
-                        if (t == 0) m &= m0;
-                        if (t == nwd - 1) m &= m1;
-                        const u64 um = t < nwd ? (v[t] & m) : 0ull;
-                        cnt += (u32)__popcll(um);
-                        fl |= um ? (1u << t) : 0u;
-                    }
-                }
-                a.rowflag[j] = (u8)fl;
-            }
-            cnt = group_sum<G>(cnt);
-            if (sub == 0) a.gainbuf[s] = cnt;
-        }
-    }
-}
-
-template <int G>
-__global__ void __launch_bounds__(GF_THREADS)
-gs_claim_kernel(ShardArgs a, u32 round) {
-    constexpr u32 GF_SETS = GF_THREADS / G;
-    __shared__ u32 s_claim, s_done;
-    GreedyState *st = a.st;
-    // (flags that another workgroup may write during this launch are read once
-    // per workgroup, so that all its threads take the same branch)
-    if (threadIdx.x == 0) { s_claim = 0; s_done = st->done; }
-    __syncthreads();
-    if (s_done) return;
-    // every universe of every rank covered: finished (all gains are zero then,
-    // so the blocks that do not see the flag yet claim nothing)
-    if (a.gainbuf[a.nsets] == 0) { if (blockIdx.x == 0 && threadIdx.x == 0) st->done = 1; return; }
-    const u32 par = round & 1;
-    const u32 cur_rank = st->cur_rank;
-    const u32 sub = threadIdx.x & (G - 1), grp = threadIdx.x / G;
-    unsigned long long *owner = a.owner[par];
-    bool any_claim = false;
-    for (u32 tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const u32 *list;
-        const u32 n = gs_tile_sets(a, tile, round, &list);
-        for (u32 li = grp; li < n; li += GF_SETS) {
-            const u32 s = list ? list[li] : tile * GS_TILE + li;
-            const u32 pk = a.picked[s], g = a.gainbuf[s], r0 = a.set_ptr[s], r1 = a.set_ptr[s + 1], rk = a.rank[s];
-            if (sub == 0) a.gain[s] = pk ? 0u : g;
-            if (pk || g == 0 || rk != cur_rank) continue;
-            any_claim = true;   // decided by the global gain: the same on every rank
-            const unsigned long long key = ((unsigned long long)g << ID_BITS) | (unsigned long long)(ID_MASK - s);
-            for (u32 j = r0 + sub; j < r1; j += G) {
-                const u32 fl = a.rowflag[j];
-                if (!fl) continue;
-                const u32 w0 = a.frow[j].x >> 6;
-                unsigned long long seen[RP_MAXW];
-#pragma unroll
-                for (u32 t = 0; t < RP_MAXW; ++t) seen[t] = owner[w0 + t];   // owner has slack words
-#pragma unroll
-                for (u32 t = 0; t < RP_MAXW; ++t)
-                    if ((fl & (1u << t)) && seen[t] < key) atomicMax(&owner[w0 + t], key);
-            }
-            if (sub == 0) a.claimed[s] = round + 1;
-        }
-    }
-    if (any_claim && sub == 0) s_claim = 1;
-    __syncthreads();
-    if (threadIdx.x == 0 && s_claim) st->fr_claim[par] = 1;
-}
-
-template <int G>
-__global__ void __launch_bounds__(GF_THREADS)
-gs_check_kernel(ShardArgs a, u32 round) {
-    constexpr u32 GF_SETS = GF_THREADS / G;
-    GreedyState *st = a.st;
-    if (st->done) return;
-    const u32 par = round & 1;
-    const u32 sub = threadIdx.x & (G - 1), grp = threadIdx.x / G;
-    const unsigned long long *owner = a.owner[par];
-    for (u32 tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const u32 *list;
-        const u32 n = gs_tile_sets(a, tile, round, &list);
-        for (u32 li = grp; li < n; li += GF_SETS) {
-            const u32 s = list ? list[li] : tile * GS_TILE + li;
-            const u32 cl = a.claimed[s], r0 = a.set_ptr[s], r1 = a.set_ptr[s + 1], g0 = a.gain[s];
-            if (cl != round + 1) continue;
-            const unsigned long long key = ((unsigned long long)g0 << ID_BITS) | (unsigned long long)(ID_MASK - s);
-            u32 lost = 0;
-            for (u32 j = r0 + sub; j < r1; j += G) {
-                const u32 fl = a.rowflag[j];
-                if (!fl) continue;
-                const u32 w0 = a.frow[j].x >> 6;
-                unsigned long long ow[RP_MAXW];
-#pragma unroll
-                for (u32 t = 0; t < RP_MAXW; ++t) ow[t] = owner[w0 + t];
-#pragma unroll
-                for (u32 t = 0; t < RP_MAXW; ++t)
-                    if ((fl & (1u << t)) && ow[t] != key) lost = 1;
-            }
-            lost = group_sum<G>(lost);
-            if (lost && sub == 0) a.lostbuf[s] = 1;
-        }
-    }
-}
-
-template <int G>
-__global__ void __launch_bounds__(GF_THREADS)
-gs_apply_kernel(ShardArgs a, u32 round) {
-    constexpr u32 GF_SETS = GF_THREADS / G;
-    __shared__ u32 s_done;
-    GreedyState *st = a.st;
-    if (threadIdx.x == 0) s_done = st->done;
-    __syncthreads();
-    if (s_done) return;
-    const u32 par = round & 1;
-    const u32 sub = threadIdx.x & (G - 1), grp = threadIdx.x / G;
-    // the other owner buffer serves the next round
-    for (u32 i = blockIdx.x * GF_THREADS + threadIdx.x; i < a.nwords; i += gridDim.x * GF_THREADS)
-        a.owner[par ^ 1][i] = 0ull;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const u32 claimed = st->fr_claim[par];
-        st->fr_claim[par ^ 1] = 0;
-        if (claimed == 0) {
-            // no set of this rank covers anything still needed anywhere: next rank
-            const u32 nr = st->cur_rank + 1;
-            st->cur_rank = nr;
-            if (nr >= st->nrank) st->done = 2;
-        }
-    }
-    for (u32 tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const u32 *list;
-        const u32 n = gs_tile_sets(a, tile, round, &list);
-        for (u32 li = grp; li < n; li += GF_SETS) {
-            const u32 s = list ? list[li] : tile * GS_TILE + li;
-            const u32 cl = a.claimed[s], r0 = a.set_ptr[s], r1 = a.set_ptr[s + 1], g0 = a.gain[s], ls = a.lostbuf[s];
-            if (cl != round + 1 || ls) continue;
-            // accepted (on every rank): clear the local bits, credit the local universes
-            for (u32 j = r0 + sub; j < r1; j += G) {
-                const u32 fl = a.rowflag[j];
-                if (!fl) continue;
-                const uint2 wr = a.frow[j];
-                const u32 x = wr.x, e = wr.y;
-                const u32 w0 = x >> 6, nwd = ((e - 1) >> 6) - w0 + 1;
-                const u64 m0 = ~0ull << (x & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
-                u32 cleared = 0;
-#pragma unroll
-                for (u32 t = 0; t < RP_MAXW; ++t) {
-                    if (!(fl & (1u << t))) continue;
-                    u64 m = ~0ull;
-                    if (t == 0) m &= m0;
-                    if (t == nwd - 1) m &= m1;
-                    cleared += (u32)__popcll(atomicAnd(&a.bm[w0 + t], ~m) & m);
-                }
-                a.rowflag[j] = 0;
-                if (cleared) {
-                    const u32 before = atomicSub(&a.usize[a.row_univ[j]], cleared);
-                    if (before == cleared) atomicSub(&st->n_need, 1u);
-                }
-            }
-            if (sub == 0) {
-                const u32 slot = atomicAdd(&st->npicks, 1u);
-                a.picks[slot] = s;
-                a.pick_key[slot] = ((unsigned long long)g0 << ID_BITS) | (unsigned long long)(ID_MASK - s);
-                a.picked[s] = 1u;
-            }
-        }
-    }
-    // next round's live lists, tile by tile: something left to offer and not
-    // chosen before this launch (a set chosen in this launch may still be
-    // listed: its picked flag makes the next count skip it)
-    __shared__ u32 s_cnt[GF_THREADS / 64];
-    for (u32 tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        constexpr int PER = GS_TILE / GF_THREADS;
-        const u32 t0 = tile * GS_TILE;
-        u32 mask = 0, mine = 0;
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const u32 s = t0 + threadIdx.x * PER + q;     // ascending inside the tile
-            const bool lv = s < a.nsets && a.gain[s] != 0 && !a.picked[s];
-            mask |= lv ? (1u << q) : 0u;
-            mine += lv ? 1u : 0u;
-        }
-        u32 inc = mine;
-        const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const u32 t = __shfl_up(inc, d, WAVE); if ((int)lane >= d) inc += t; }
-        __syncthreads();
-        if (lane == 63) s_cnt[wave] = inc;
-        __syncthreads();
-        u32 woff = 0, tot = 0;
-        for (int w = 0; w < GF_THREADS / 64; ++w) { if (w < (int)wave) woff += s_cnt[w]; tot += s_cnt[w]; }
-        if (threadIdx.x == 0) a.tilecnt[par ^ 1][tile] = tot;
-        u32 o = t0 + woff + inc - mine;
-#pragma unroll
-        for (int q = 0; q < PER; ++q)
-            if (mask & (1u << q)) a.live[par ^ 1][o++] = t0 + threadIdx.x * PER + q;
-    }
-}
+// the most shards one process may exchange among themselves (their buffers travel as a kernel argument)
+#define SHARD_LOCAL_MAX 64
+struct ShardBufs { void *p[SHARD_LOCAL_MAX]; };
 
 // n buffers of `count` elements on one device: every buffer <- reduction of all
-// (the exchange of several shards living in ONE process; catchhip_shard_allreduce_local)
 template <typename T, bool IS_MAX>
 __global__ void __launch_bounds__(256)
-local_allreduce_kernel(T *const *bufs, int n, size_t count) {
+local_allreduce_kernel(ShardBufs bufs, int n, size_t count) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
-        T acc = bufs[0][i];
-        for (int b = 1; b < n; ++b) { const T v = bufs[b][i]; acc = IS_MAX ? (v > acc ? v : acc) : (T)(acc + v); }
-        for (int b = 0; b < n; ++b) bufs[b][i] = acc;
+        T acc = ((const T *)bufs.p[0])[i];
+        for (int b = 1; b < n; ++b) { const T v = ((const T *)bufs.p[b])[i]; acc = IS_MAX ? (v > acc ? v : acc) : (T)(acc + v); }
+        for (int b = 0; b < n; ++b) ((T *)bufs.p[b])[i] = acc;
     }
 }
 
-// Packed exchange of the flat shards.  A set whose GLOBAL gain has reached zero
-// never gains again, and only sets with a global gain can claim or lose: so the
-// ranks exchange the gains of the sets that were alive after the previous round
-// and the lost marks (one byte each) of the sets alive in this one -- lists that
-// every rank derives from the same all-reduced gains, in set order.  On S4's
-// largest group (3.96 M sets, 19 rounds) that is ~4 x 16 MB of gains and ~4 x 4
-// MB of marks per solve instead of 19 x (16 + 16) MB.
-//   xg[i] = acc[list[i]] (list == null: i), xg[n], xg[n + 1] = the two extra slots
+// xg[i] = acc[list[i]] (list == null: i), xg[n], xg[n + 1] = the two extra slots
 __global__ void __launch_bounds__(256)
 sx_pack_gain_kernel(const u32 *__restrict__ acc, const u32 *__restrict__ list, u32 n, u32 nsets, u32 *__restrict__ xg) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) xg[i] = acc[list ? list[i] : i];
     else if (i < n + 2) xg[i] = acc[nsets + (i - n)];
 }
-// the all-reduced gains back into acc; flag[i] = set list[i] is still alive
+// the all-reduced gains back into acc
 __global__ void __launch_bounds__(256)
-sx_unpack_gain_kernel(u32 *__restrict__ acc, const u32 *__restrict__ list, u32 n, u32 nsets, const u32 *__restrict__ xg,
-                      u32 *__restrict__ flag) {
+sx_unpack_gain_kernel(u32 *__restrict__ acc, const u32 *__restrict__ list, u32 n, u32 nsets, const u32 *__restrict__ xg) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { const u32 g = xg[i]; acc[list ? list[i] : i] = g; flag[i] = g ? 1u : 0u; }
-    else if (i < n + 2) { acc[nsets + (i - n)] = xg[i]; if (i == n) flag[n] = 0u; }
+    if (i < n) acc[list ? list[i] : i] = xg[i];
+    else if (i < n + 2) acc[nsets + (i - n)] = xg[i];
+}
+// the lost marks of the listed sets, one byte each
+__global__ void __launch_bounds__(256)
+sxl_pack_lost_kernel(const u32 *__restrict__ lost, const u32 *__restrict__ list, u32 n, u32 tag, u8 *__restrict__ xl) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) xl[i] = lost[list ? list[i] : i] == tag ? 1 : 0;
+}
+__global__ void __launch_bounds__(256)
+sxl_unpack_lost_kernel(u32 *__restrict__ lost, const u32 *__restrict__ list, u32 n, u32 tag, const u8 *__restrict__ xl) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && xl[i]) lost[list ? list[i] : i] = tag;
+}
+// flag[i] = set list[i] still has a global gain; flag[n] = 0 (its scanned slot receives the count)
+__global__ void __launch_bounds__(256)
+sx_flag_alive_kernel(const u32 *__restrict__ acc, const u32 *__restrict__ list, u32 n, u32 *__restrict__ flag) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) flag[i] = acc[list ? list[i] : i] ? 1u : 0u;
+    else if (i == n) flag[n] = 0u;
 }
 // next list = the alive entries of this one, in order (pos = exclusive scan of flag)
 __global__ void __launch_bounds__(256)
@@ -332,46 +103,28 @@ sx_compact_kernel(const u32 *__restrict__ list, u32 n, const u32 *__restrict__ f
     if (i < n && flag[i]) next[pos[i]] = list ? list[i] : i;
     if (i == 0) *n_next = pos[n];
 }
-__global__ void __launch_bounds__(256)
-sx_pack_lost_kernel(const u32 *__restrict__ lost, const u32 *__restrict__ list, u32 n, u32 tag, u8 *__restrict__ xl) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) xl[i] = lost[list[i]] == tag ? 1 : 0;
-}
-__global__ void __launch_bounds__(256)
-sx_unpack_lost_kernel(u32 *__restrict__ lost, const u32 *__restrict__ list, u32 n, u32 tag, const u8 *__restrict__ xl) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && xl[i]) lost[list[i]] = tag;
-}
 
 struct catchhip_shard {
     catchhip_ctx *ctx = nullptr;
-    // large shards run the row-parallel kernels of setcover_flat.inc in their
-    // sharded mode (gains = acc[round & 1], lost marks = round tags, both u32)
-    FlatSolve *flat = nullptr;
-    ~catchhip_shard() { delete flat; }
-    DevBuf<u8> arena;
-    ShardArgs a;
+    FlatSolve F;                 // gains = acc[round & 1], lost marks = round tags, both u32
     std::vector<u32> h_rank;
     bool has_ranks = false;
     bool partial = false;        // some universe may stay partly uncovered: a third exchange per round (catchhip_shard_verdict)
-    bool wide = false;
-    unsigned gblocks = 1;
+    u32 nsets = 0;
     u32 round = 0;
-    size_t zero_bytes = 0;
-    GreedyState h_st;
-    int done = 0;
-    // packed exchange (flat shards): xg / xl are what the transports all-reduce
+    GreedyState h_st = {};       // as of the last read-back
+    int done = 0;                // 1 finished, -1 rank list exhausted: the shard is spent
+    // packed exchange: xg / xl are what the transports all-reduce
     DevBuf<u32> xg, xlist[2], xflag, xpos, xtmp;
     DevBuf<u8> xl;
-    u32 n_prev = 0, n_cur = 0;   // sets alive after the previous round (their gains travel) / in this one (their marks)
-    int lprev = -1;              // which of xlist holds the previous round's list (-1: every set, round 0)
+    u32 cap = 0;                 // listed sets = the sets alive at the last read-back
+    int lcur = -1;               // which of xlist holds the list (-1: every set, until the first read-back)
 
-    // the exchange buffers as the transports see them
-    void *xptr(i32 which) { return which == 0 ? (flat ? (void *)xg.p : (void *)a.gainbuf) : (flat ? (void *)xl.p : (void *)a.lostbuf); }
-    size_t xcount(i32 which) const {
-        if (!flat) return which == 0 ? (size_t)a.nsets + 2 : (size_t)a.nsets;
-        return which == 0 ? (size_t)n_prev + 2 : (size_t)n_cur;
-    }
+    const u32 *list() const { return lcur < 0 ? nullptr : xlist[lcur].p; }
+    int lnext() const { return lcur < 0 ? 0 : lcur ^ 1; }
+    // the exchange buffers as the transports see them; both sized by the list (gains: + 2 slots)
+    void *xptr(i32 which) { return which == 0 ? (void *)xg.p : (void *)xl.p; }
+    size_t xcount(i32 which) const { return which == 0 ? (size_t)cap + 2 : (size_t)cap; }
     size_t xelem(i32 which) const { return which == 0 ? 4 : 1; }
 };
 
@@ -391,9 +144,9 @@ extern "C" int catchhip_shard_create_p(catchhip_ctx *ctx, const catchhip_rows *R
 }
 
 // instance_partial: whether ANY universe of the WHOLE instance (on any rank) is covered partially -- 1 / 0, the same
-// on every rank, so that every rank takes the same kernels, the same shape of a round and the same refusals even
-// when its own universes all have p == 1 (coverage given in bases with genomes shorter than it: set_cover_filter.py
-// :761-792); -1 = decide from this shard's universe_p alone (a single-shard caller).
+// on every rank, so that every rank takes the same shape of a round even when its own universes all have p == 1
+// (coverage given in bases with genomes shorter than it: set_cover_filter.py:761-792); -1 = decide from this shard's
+// universe_p alone (a single-shard caller).
 extern "C" int catchhip_shard_create_pi(catchhip_ctx *ctx, const catchhip_rows *R, i64 num_sets, const i64 *ranks,
                                         const double *universe_p, int instance_partial, catchhip_shard **out) {
     ARG_CHECK(ctx && R && out && num_sets > 0 && R->ctx == ctx && !R->deferred);
@@ -411,94 +164,33 @@ extern "C" int catchhip_shard_create_pi(catchhip_ctx *ctx, const catchhip_rows *
         partial = true;
         if (!universe_p) { ones.assign((size_t)std::max<i64>(R->ngenomes, 1), 1.0); universe_p = ones.data(); }
     }
-    if (num_sets >= (i64)ID_MASK) { chip_set_error("shard: too many sets"); return CATCHHIP_EINVAL; }
+    // (the caller -- every rank alike -- solves such a group whole)
+    if (num_sets > (i64)GR_MAX_SETS || (R->n > 0 && R->lmax > 257)) {
+        chip_set_error("shard: more than 2^%d sets or rows longer than 257 bases are solved unsharded", GR_SET_BITS);
+        return CATCHHIP_EINVAL;
+    }
     if (R->n >= ((i64)1 << 31)) { chip_set_error("shard: too many rows"); return CATCHHIP_EINVAL; }
-    if (R->n > 0 && R->lmax > 257) { chip_set_error("shard: rows longer than 257 bases are solved unsharded"); return CATCHHIP_EINVAL; }
     HIP_TRY(hipSetDevice(ctx->device));
     PoolScope pool_scope(ctx);
     catchhip_shard *S = new catchhip_shard();
     S->ctx = ctx;
-    const u32 nsets = (u32)num_sets, nrows = (u32)R->n, nuniv = (u32)R->ngenomes;
+    const u32 nsets = (u32)num_sets;
     const u32 nrank = dense_ranks(ranks, nsets, S->h_rank);
     S->has_ranks = ranks != nullptr;
-    S->a.nsets = nsets;
-    // Which kernels: decided by something every rank agrees on (the exchange
-    // buffers differ in width) -- the number of sets, not the local rows.  An
-    // instance worth sharding has millions of rows: the row-parallel kernels.
-    const bool use_flat = chip_test_env("CATCHHIP_SHARD_FLAT") ? atoi(chip_test_env("CATCHHIP_SHARD_FLAT")) != 0 : (nsets >= 65536u && nsets <= GR_MAX_SETS);
     S->partial = partial;
-    if (partial && !use_flat) {
-        // (the caller -- every rank alike: it depends on the number of sets only -- solves the group whole)
-        chip_set_error("shard: partial coverage is sharded by the row-parallel kernels only (65,536 to 2^25 sets)");
-        delete S;
-        return CATCHHIP_EINVAL;
-    }
-    if (use_flat) {
-        S->flat = new FlatSolve();
-        int rcf = S->flat->setup(ctx, R, nsets, S->has_ranks ? S->h_rank.data() : nullptr, nrank, true, nullptr,
-                                 partial ? universe_p : nullptr);
-        if (!rcf) rcf = S->xg.alloc((size_t)nsets + 2);
-        if (!rcf) rcf = S->xl.alloc((size_t)nsets + 16);
-        if (!rcf) rcf = S->xlist[0].alloc(nsets);
-        if (!rcf) rcf = S->xlist[1].alloc(nsets);
-        if (!rcf) rcf = S->xflag.alloc((size_t)nsets + 1);
-        if (!rcf) rcf = S->xpos.alloc((size_t)nsets + 1);
-        S->n_prev = nsets;
-        if (!rcf && hipStreamSynchronize(ctx->stream) != hipSuccess) rcf = CATCHHIP_EHIP;
-        if (rcf) { delete S; return rcf; }
-        *out = S;
-        return 0;
-    }
-    const size_t nwords = (size_t)(R->total / 64 + 2);
-    const u32 ntiles = (u32)div_up(nsets, GS_TILE);
-    S->wide = (i64)nrows >= 32 * (i64)nsets;
-    S->gblocks = (unsigned)std::min<i64>(ntiles, (i64)ctx->num_cus * 16);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_bm = take(8 * nwords), o_ow0 = take(8 * (nwords + 8)), o_ow1 = take(8 * (nwords + 8)),
-                 o_st = take(sizeof(GreedyState)), o_picked = take(4 * (size_t)nsets),
-                 o_claimed = take(4 * (size_t)nsets), o_rank = take(4 * (size_t)nsets),
-                 o_gain = take(4 * (size_t)nsets), o_gainbuf = take(4 * ((size_t)nsets + 2)),
-                 o_lost = take((size_t)nsets + 16);
-    S->zero_bytes = off;
-    const size_t o_usize = take(4 * (size_t)std::max<u32>(nuniv, 1)), o_setptr = take(4 * ((size_t)nsets + 1)),
-                 o_frow = take(8 * (size_t)std::max<u32>(nrows, 1)), o_flag = take(std::max<u32>(nrows, 1)),
-                 o_picks = take(4 * (size_t)nsets), o_keys = take(8 * (size_t)nsets),
-                 o_live0 = take(4 * (size_t)ntiles * GS_TILE), o_live1 = take(4 * (size_t)ntiles * GS_TILE),
-                 o_tc0 = take(4 * (size_t)ntiles), o_tc1 = take(4 * (size_t)ntiles);
-    int rc = S->arena.alloc(off);
+    S->nsets = S->cap = nsets;
+    // everything a round or a batch needs is allocated here: nothing can fail to allocate between two collectives
+    int rc = S->F.setup(ctx, R, nsets, S->has_ranks ? S->h_rank.data() : nullptr, nrank, true, nullptr,
+                        partial ? universe_p : nullptr);
+    if (!rc) rc = S->xg.alloc((size_t)nsets + 2);
+    if (!rc) rc = S->xl.alloc((size_t)nsets + 16);
+    if (!rc) rc = S->xlist[0].alloc(nsets);
+    if (!rc) rc = S->xlist[1].alloc(nsets);
+    if (!rc) rc = S->xflag.alloc((size_t)nsets + 1);
+    if (!rc) rc = S->xpos.alloc((size_t)nsets + 1);
+    if (!rc) rc = chip_exclusive_scan_reserve(S->xtmp, (i64)nsets + 1);
+    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = CATCHHIP_EHIP;
     if (rc) { delete S; return rc; }
-    u8 *A = S->arena.p;
-    hipStream_t s = ctx->stream;
-    ShardArgs &a = S->a;
-    a.bm = (unsigned long long *)(A + o_bm);
-    a.owner[0] = (unsigned long long *)(A + o_ow0); a.owner[1] = (unsigned long long *)(A + o_ow1);
-    a.frow = (const uint2 *)(A + o_frow); a.row_univ = (const i32 *)R->univ.p;
-    a.set_ptr = (const u32 *)(A + o_setptr); a.rank = (const u32 *)(A + o_rank);
-    a.usize = (u32 *)(A + o_usize); a.gain = (u32 *)(A + o_gain); a.gainbuf = (u32 *)(A + o_gainbuf);
-    a.lostbuf = A + o_lost; a.claimed = (u32 *)(A + o_claimed); a.picked = (u32 *)(A + o_picked);
-    a.picks = (u32 *)(A + o_picks); a.pick_key = (unsigned long long *)(A + o_keys); a.rowflag = A + o_flag;
-    a.live[0] = (u32 *)(A + o_live0); a.live[1] = (u32 *)(A + o_live1);
-    a.tilecnt[0] = (u32 *)(A + o_tc0); a.tilecnt[1] = (u32 *)(A + o_tc1);
-    a.st = (GreedyState *)(A + o_st);
-    a.nsets = nsets; a.nwords = (u32)nwords; a.ntiles = ntiles;
-    do {
-        if (hipMemsetAsync(A, 0, S->zero_bytes, s) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-        if (S->has_ranks &&
-            hipMemcpyAsync(A + o_rank, S->h_rank.data(), 4 * (size_t)nsets, hipMemcpyHostToDevice, s) != hipSuccess) {
-            rc = CATCHHIP_EHIP; break;
-        }
-        // rows -> {gs, ge} records + local bitmap + set pointers; |U_u| of the local universes
-        hipLaunchKernelGGL(gf_build_kernel, dim3((unsigned)div_up(std::max(nrows, nsets + 1), 256)), dim3(256), 0, s,
-                           (const i32 *)R->set_id.p, (const i32 *)R->univ.p, (const u32 *)R->gs.p, (const u32 *)R->ge.p,
-                           nrows, (const u32 *)nullptr, nsets, nrank, (uint2 *)(A + o_frow), a.bm, (u32 *)(A + o_setptr),
-                           a.st);
-        if (nuniv)
-            hipLaunchKernelGGL(gf_universe_kernel, dim3(nuniv), dim3(256), 0, s, (const unsigned long long *)a.bm,
-                               (const u32 *)R->genome_off.p, a.usize, a.st, (const u32 *)nullptr);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-    } while (0);
-    if (rc) { chip_set_error("shard: set-up failed"); delete S; return rc; }
     *out = S;
     return 0;
 }
@@ -512,28 +204,116 @@ extern "C" int catchhip_shard_destroy(catchhip_shard *S) {
     return 0;
 }
 
-#define GS_LAUNCH(kern)                                                                                         \
-    do {                                                                                                        \
-        if (S->wide) hipLaunchKernelGGL(kern<64>, dim3(S->gblocks), dim3(GF_THREADS), 0, s, S->a, S->round);    \
-        else hipLaunchKernelGGL(kern<16>, dim3(S->gblocks), dim3(GF_THREADS), 0, s, S->a, S->round);            \
-    } while (0)
+// ---- the phases of a round and the end of a batch: the step API and catchhip_shard_solve run the same ones --------
+#define SX_GRID(n) dim3((unsigned)div_up((i64)(n), 256)), dim3(256), 0, S->ctx->stream
 
-extern "C" int catchhip_shard_count(catchhip_shard *S) {
-    ARG_CHECK(S != nullptr);
-    HIP_TRY(hipSetDevice(S->ctx->device));
-    hipStream_t s = S->ctx->stream;
-    if (S->flat) {
-        S->flat->launch_count(S->round);
-        const u32 n = S->n_prev;
-        hipLaunchKernelGGL(sx_pack_gain_kernel, dim3((unsigned)div_up((i64)n + 2, 256)), dim3(256), 0, s,
-                           (const u32 *)S->flat->fa.acc[S->round & 1], S->lprev < 0 ? (const u32 *)nullptr : (const u32 *)S->xlist[S->lprev].p,
-                           n, S->a.nsets, S->xg.p);
-        HIP_TRY(hipGetLastError());
+// count + pack the gains
+static void shard_count(catchhip_shard *S) {
+    S->F.launch_count(S->round);
+    hipLaunchKernelGGL(sx_pack_gain_kernel, SX_GRID((i64)S->cap + 2), (const u32 *)S->F.fa.acc[S->round & 1], S->list(),
+                       S->cap, S->nsets, S->xg.p);
+}
+
+// the all-reduced gains back into place + claim + pack the lost marks
+static void shard_claim(catchhip_shard *S) {
+    hipLaunchKernelGGL(sx_unpack_gain_kernel, SX_GRID((i64)S->cap + 2), S->F.fa.acc[S->round & 1], S->list(), S->cap,
+                       S->nsets, (const u32 *)S->xg.p);
+    S->F.launch_claim(S->round);
+    if (S->cap)
+        hipLaunchKernelGGL(sxl_pack_lost_kernel, SX_GRID(S->cap), (const u32 *)S->F.fa.lost, S->list(), S->cap,
+                           S->round + 1, S->xl.p);
+}
+
+// partial coverage: the all-reduced marks back into place + the universe test of every candidate left on this
+// rank's universes (a failure is one more lost mark) + pack the marks again
+static void shard_verdict(catchhip_shard *S) {
+    if (S->cap)
+        hipLaunchKernelGGL(sxl_unpack_lost_kernel, SX_GRID(S->cap), S->F.fa.lost, S->list(), S->cap, S->round + 1,
+                           (const u8 *)S->xl.p);
+    S->F.launch_verdict(S->round);
+    if (S->cap)
+        hipLaunchKernelGGL(sxl_pack_lost_kernel, SX_GRID(S->cap), (const u32 *)S->F.fa.lost, S->list(), S->cap,
+                           S->round + 1, S->xl.p);
+}
+
+// the all-reduced marks back into place + apply; the round is over
+static void shard_apply(catchhip_shard *S) {
+    if (S->cap)
+        hipLaunchKernelGGL(sxl_unpack_lost_kernel, SX_GRID(S->cap), S->F.fa.lost, S->list(), S->cap, S->round + 1,
+                           (const u8 *)S->xl.p);
+    S->F.launch_apply(S->round);
+    S->round++;
+}
+
+// The end of a batch, enqueued: the list compacted to the sets that still have a global gain (the all-reduced gains
+// of the batch's last round: the same on every rank); its length lands in the scanned flag slot.
+static int shard_compact(catchhip_shard *S) {
+    const u32 *lp = S->list();
+    hipLaunchKernelGGL(sx_flag_alive_kernel, SX_GRID((i64)S->cap + 1), (const u32 *)S->F.fa.acc[(S->round - 1) & 1], lp,
+                       S->cap, S->xflag.p);
+    TRY(chip_exclusive_scan_u32(S->ctx, S->xflag.p, S->xpos.p, (i64)S->cap + 1, S->xtmp));   // (scratch reserved at creation)
+    hipLaunchKernelGGL(sx_compact_kernel, SX_GRID(std::max<u32>(S->cap, 1)), lp, S->cap, (const u32 *)S->xflag.p,
+                       (const u32 *)S->xpos.p, S->xlist[S->lnext()].p, S->xflag.p + S->cap);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ... and its one read-back: the solver's state and the list's new length, published unless the solve has ended
+// (the rounds queued past the end did nothing: their list is not one to continue from)
+static int shard_read_back(catchhip_shard *S) {
+    catchhip_ctx *c = S->ctx;
+    static_assert(sizeof(GreedyState) + sizeof(u32) <= 64 * sizeof(u64), "ctx->h_pin holds the state and one more word");
+    u32 *h_n = (u32 *)((u8 *)c->h_pin + sizeof(GreedyState));
+    HIP_TRY(hipMemcpyAsync(c->h_pin, S->F.fa.st, sizeof(GreedyState), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h_n, S->xflag.p + S->cap, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(&S->h_st, c->h_pin, sizeof(GreedyState));
+    S->done = S->h_st.done == 2 ? -1 : (S->h_st.done ? 1 : 0);
+    if (S->done) return 0;
+    S->cap = *(volatile u32 *)h_n;
+    S->lcur = S->lnext();
+    if ((i64)S->round > 2 * (i64)S->nsets + 4) {      // (a round accepts a set or moves on to the next rank)
+        chip_set_error("shard: round cap exceeded");
+        return CATCHHIP_EINVAL;
+    }
+    return 0;
+}
+
+// One all-reduce of every shard's buffer `which` (0: gains, SUM; 1: lost marks, MAX) at its current size: over the
+// context's communicator (transport 0: one shard per process) or among the n shards of this process (transport 1:
+// one device, on shards[0]'s stream).  Allocates nothing.
+static int shard_exchange(i32 n, catchhip_shard *const *sh, i32 which, i32 transport) {
+    const size_t count = sh[0]->xcount(which);
+    if (count == 0) return 0;      // (the same on every rank: the lists derive from the all-reduced gains)
+    catchhip_ctx *c = sh[0]->ctx;
+    if (transport == 0) {
+        void *buf = sh[0]->xptr(which);
+        const ncclResult_t r = which == 0 ? rccl().AllReduce(buf, buf, count, ncclUint32, ncclSum, (ncclComm_t)c->comm, c->stream)
+                                          : rccl().AllReduce(buf, buf, count, ncclUint8, ncclMax, (ncclComm_t)c->comm, c->stream);
+        if (r != ncclSuccess) { chip_set_error("ncclAllReduce: %s", rccl().GetErrorString(r)); return CATCHHIP_ECOMM; }
         return 0;
     }
-    HIP_TRY(hipMemsetAsync(S->a.gainbuf, 0, 4 * ((size_t)S->a.nsets + 2), s));
-    HIP_TRY(hipMemsetAsync(S->a.lostbuf, 0, (size_t)S->a.nsets, s));
-    GS_LAUNCH(gs_count_kernel);
+    if (n == 1) return 0;
+    ShardBufs b;
+    for (i32 i = 0; i < n; ++i) b.p[i] = sh[i]->xptr(which);
+    const unsigned blocks = (unsigned)std::min<size_t>(div_up((i64)count, 256), 4096);
+    if (which == 0) hipLaunchKernelGGL((local_allreduce_kernel<u32, false>), dim3(blocks), dim3(256), 0, c->stream, b, n, count);
+    else hipLaunchKernelGGL((local_allreduce_kernel<u8, true>), dim3(blocks), dim3(256), 0, c->stream, b, n, count);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- the step API: a batch of one round --------------------------------------------------------------------------
+static int shard_step_check(catchhip_shard *S) {
+    ARG_CHECK(S != nullptr);
+    if (S->done) { chip_set_error("shard: the solve has ended (a shard is single-use)"); return CATCHHIP_EINVAL; }
+    HIP_TRY(hipSetDevice(S->ctx->device));
+    return 0;
+}
+
+extern "C" int catchhip_shard_count(catchhip_shard *S) {
+    TRY(shard_step_check(S));
+    shard_count(S);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -548,90 +328,30 @@ extern "C" int catchhip_shard_buffers(catchhip_shard *S, void **gain, i64 *gain_
 }
 
 extern "C" int catchhip_shard_claim_check(catchhip_shard *S) {
-    ARG_CHECK(S != nullptr);
-    HIP_TRY(hipSetDevice(S->ctx->device));
-    hipStream_t s = S->ctx->stream;
-    if (S->flat) {
-        // the all-reduced gains back into place; the sets still alive form this round's list
-        PoolScope pool_scope(S->ctx);
-        const u32 n = S->n_prev, tag = S->round + 1;
-        const u32 *lp = S->lprev < 0 ? (const u32 *)nullptr : (const u32 *)S->xlist[S->lprev].p;
-        const int lc = S->lprev < 0 ? 0 : S->lprev ^ 1;
-        u32 *acc = S->flat->fa.acc[S->round & 1];
-        hipLaunchKernelGGL(sx_unpack_gain_kernel, dim3((unsigned)div_up((i64)n + 2, 256)), dim3(256), 0, s, acc, lp, n,
-                           S->a.nsets, (const u32 *)S->xg.p, S->xflag.p);
-        TRY(chip_exclusive_scan_u32(S->ctx, S->xflag.p, S->xpos.p, (i64)n + 1, S->xtmp));
-        static_assert(sizeof(GreedyState) + sizeof(u32) <= 64 * sizeof(u64), "ctx->h_pin holds the state and one more word");
-        u32 *h_n = (u32 *)((u8 *)S->ctx->h_pin + sizeof(GreedyState));
-        u32 *d_n = S->xflag.p + n;     // (its flag slot has been scanned: reused for the count)
-        hipLaunchKernelGGL(sx_compact_kernel, dim3((unsigned)div_up((i64)std::max<u32>(n, 1), 256)), dim3(256), 0, s, lp, n,
-                           (const u32 *)S->xflag.p, (const u32 *)S->xpos.p, S->xlist[lc].p, d_n);
-        HIP_TRY(hipMemcpyAsync(h_n, d_n, sizeof(u32), hipMemcpyDeviceToHost, s));
-        S->flat->launch_claim(S->round);
-        // The ONE host synchronisation of a round (round 4; two until then): the alive count the packed exchange
-        // needs and, in the same read-back, the solver state -- the claim launch is what ends a solve (no row with
-        // an uncovered element on any rank: st->done = 1), the apply launch only ever moves on to the next rank
-        // (exhausting them is noticed one round later, by launches that do nothing).
-        HIP_TRY(hipMemcpyAsync(S->ctx->h_pin, S->flat->fa.st, sizeof(GreedyState), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));
-        memcpy(&S->h_st, S->ctx->h_pin, sizeof(GreedyState));
-        S->n_cur = *(volatile u32 *)h_n;
-        S->lprev = lc;                 // from here on "previous" for the next round; this round's marks use it too
-        if (S->n_cur)
-            hipLaunchKernelGGL(sx_pack_lost_kernel, dim3((unsigned)div_up((i64)S->n_cur, 256)), dim3(256), 0, s,
-                               (const u32 *)S->flat->fa.lost, (const u32 *)S->xlist[lc].p, S->n_cur, tag, S->xl.p);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    GS_LAUNCH(gs_claim_kernel);
-    GS_LAUNCH(gs_check_kernel);
+    TRY(shard_step_check(S));
+    shard_claim(S);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// Partial coverage only, between the lost exchange and catchhip_shard_apply: the all-reduced marks back into place,
-// the universe test of every candidate that is left on this rank's universes (gr_verdict_kernel: a failure is one
-// more lost mark), the marks packed again -- the caller exchanges them once more (which = 1), then applies.
+// Partial coverage only, between the lost exchange and catchhip_shard_apply; the caller exchanges the marks once
+// more (which = 1), then applies.
 extern "C" int catchhip_shard_verdict(catchhip_shard *S) {
-    ARG_CHECK(S != nullptr);
+    TRY(shard_step_check(S));
     if (!S->partial) return 0;
-    HIP_TRY(hipSetDevice(S->ctx->device));
-    hipStream_t s = S->ctx->stream;
-    if (S->n_cur) {
-        hipLaunchKernelGGL(sx_unpack_lost_kernel, dim3((unsigned)div_up((i64)S->n_cur, 256)), dim3(256), 0, s,
-                           S->flat->fa.lost, (const u32 *)S->xlist[S->lprev].p, S->n_cur, S->round + 1, (const u8 *)S->xl.p);
-        S->flat->launch_verdict(S->round);
-        hipLaunchKernelGGL(sx_pack_lost_kernel, dim3((unsigned)div_up((i64)S->n_cur, 256)), dim3(256), 0, s,
-                           (const u32 *)S->flat->fa.lost, (const u32 *)S->xlist[S->lprev].p, S->n_cur, S->round + 1, S->xl.p);
-    }
+    shard_verdict(S);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
+// the end of the round and of its batch: the one host synchronisation of a round
 extern "C" int catchhip_shard_apply(catchhip_shard *S, i32 *done) {
-    ARG_CHECK(S && done);
-    HIP_TRY(hipSetDevice(S->ctx->device));
-    hipStream_t s = S->ctx->stream;
-    if (S->flat) {
-        if (S->n_cur)
-            hipLaunchKernelGGL(sx_unpack_lost_kernel, dim3((unsigned)div_up((i64)S->n_cur, 256)), dim3(256), 0, s,
-                               S->flat->fa.lost, (const u32 *)S->xlist[S->lprev].p, S->n_cur, S->round + 1, (const u8 *)S->xl.p);
-        S->flat->launch_apply(S->round);
-        S->n_prev = S->n_cur;      // their gains travel in the next round
-    } else GS_LAUNCH(gs_apply_kernel);
-    HIP_TRY(hipGetLastError());
-    if (!S->flat) {
-        HIP_TRY(hipMemcpyAsync(S->ctx->h_pin, S->a.st, sizeof(GreedyState), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        memcpy(&S->h_st, S->ctx->h_pin, sizeof(GreedyState));
-    }   // (row-parallel kernels: the state was read with the alive count in claim_check; no second synchronisation)
-    S->round++;
-    S->done = S->h_st.done == 2 ? -1 : (S->h_st.done ? 1 : 0);
-    if (!S->done && (i64)S->round > (i64)S->a.nsets + S->h_st.nrank + 2) {
-        chip_set_error("shard: round cap exceeded");
-        return CATCHHIP_EINVAL;
-    }
+    ARG_CHECK(done != nullptr);
+    TRY(shard_step_check(S));
+    PoolScope pool_scope(S->ctx);
+    shard_apply(S);
+    TRY(shard_compact(S));
+    TRY(shard_read_back(S));
     *done = S->done;
     return 0;
 }
@@ -639,46 +359,21 @@ extern "C" int catchhip_shard_apply(catchhip_shard *S, i32 *done) {
 extern "C" int catchhip_shard_picks(catchhip_shard *S, i64 *out_ids, i64 *n_out) {
     ARG_CHECK(S && n_out);
     HIP_TRY(hipSetDevice(S->ctx->device));
-    hipStream_t s = S->ctx->stream;
     if (S->done == -1) { chip_set_error("setcover: ranks exhausted while coverage is still required"); return CATCHHIP_ERANK; }
-    if (S->flat) {   // the picks of the last apply launch: the state as it is now
-        HIP_TRY(hipMemcpyAsync(S->ctx->h_pin, S->flat->fa.st, sizeof(GreedyState), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        memcpy(&S->h_st, S->ctx->h_pin, sizeof(GreedyState));
-    }
-    const u32 np = S->h_st.npicks;
+    const u32 np = S->h_st.npicks;     // (the state of the last read-back: every apply is followed by one)
     *n_out = np;
     if (!np) return 0;
     ARG_CHECK(out_ids != nullptr);
-    if (S->flat) {
-        TRY(S->flat->picks(np, S->has_ranks ? S->h_rank.data() : nullptr, out_ids));
-        S->ctx->counters[2] = S->h_st.iters; S->ctx->counters[3] = np;
-        return 0;
-    }
-    std::vector<u32> h_picks(np);
-    std::vector<unsigned long long> h_keys(np);
-    HIP_TRY(hipMemcpyAsync(h_picks.data(), S->a.picks, 4 * (size_t)np, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(h_keys.data(), S->a.pick_key, 8 * (size_t)np, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    // sequential pick order = by rank, then by descending accept-time key
-    std::vector<u32> ord(np);
-    for (u32 i = 0; i < np; ++i) ord[i] = i;
-    const bool hr = S->has_ranks;
-    std::sort(ord.begin(), ord.end(), [&](u32 x, u32 y) {
-        const u32 rx = hr ? S->h_rank[h_picks[x]] : 0u, ry = hr ? S->h_rank[h_picks[y]] : 0u;
-        if (rx != ry) return rx < ry;
-        return h_keys[x] > h_keys[y];
-    });
-    for (u32 i = 0; i < np; ++i) out_ids[i] = h_picks[ord[i]];
+    TRY(S->F.picks(np, S->has_ranks ? S->h_rank.data() : nullptr, out_ids));
     S->ctx->counters[2] = S->h_st.iters; S->ctx->counters[3] = np;
     return 0;
 }
 
-// out4 = {gain elements (uint32) and lost elements (uint8) of the NEXT exchange -- the flat shards pack their
-// buffers, so the counts change from round to round --, bytes per lost element, 1 if the flat kernels run}
+// out4 = {gain elements (uint32) and lost elements (uint8) of the NEXT exchange -- the buffers are packed, so the
+// counts change from batch to batch --, bytes per lost element, 1 | 2 if partial}
 extern "C" int catchhip_shard_info(catchhip_shard *S, i64 *out4) {
     ARG_CHECK(S && out4);
-    out4[0] = (i64)S->xcount(0); out4[1] = (i64)S->xcount(1); out4[2] = 1; out4[3] = (S->flat ? 1 : 0) | (S->partial ? 2 : 0);
+    out4[0] = (i64)S->xcount(0); out4[1] = (i64)S->xcount(1); out4[2] = 1; out4[3] = 1 | (S->partial ? 2 : 0);
     return 0;
 }
 
@@ -698,44 +393,22 @@ extern "C" int catchhip_shard_buffer_copy(catchhip_shard *S, i32 which, void *ho
 
 // exchange between shards that live in one process on one device
 extern "C" int catchhip_shard_allreduce_local(i32 n, catchhip_shard *const *shards, i32 which) {
-    ARG_CHECK(n >= 1 && shards && (which == 0 || which == 1));
+    ARG_CHECK(n >= 1 && n <= SHARD_LOCAL_MAX && shards && (which == 0 || which == 1));
     for (i32 i = 0; i < n; ++i) {
-        ARG_CHECK(shards[i] != nullptr && shards[i]->a.nsets == shards[0]->a.nsets);
+        ARG_CHECK(shards[i] != nullptr && shards[i]->nsets == shards[0]->nsets);
         if (shards[i]->ctx->device != shards[0]->ctx->device) {
             chip_set_error("shard_allreduce_local: shards must be on one device (use RCCL across devices)");
+            return CATCHHIP_EINVAL;
+        }
+        if (shards[i]->round != shards[0]->round || shards[i]->xcount(which) != shards[0]->xcount(which)) {
+            chip_set_error("shard_allreduce_local: the shards disagree on the round or the size of the exchange");
             return CATCHHIP_EINVAL;
         }
     }
     catchhip_ctx *c0 = shards[0]->ctx;
     HIP_TRY(hipSetDevice(c0->device));
-    PoolScope pool_scope(c0);
     for (i32 i = 0; i < n; ++i) HIP_TRY(hipStreamSynchronize(shards[i]->ctx->stream));
-    const bool flat = shards[0]->flat != nullptr;
-    for (i32 i = 0; i < n; ++i)
-        if ((shards[i]->flat != nullptr) != flat || shards[i]->round != shards[0]->round) {
-            chip_set_error("shard_allreduce_local: shards of one instance must use the same kernels and round");
-            return CATCHHIP_EINVAL;
-        }
-    std::vector<void *> h(n);
-    for (i32 i = 0; i < n; ++i) {
-        catchhip_shard *q = shards[i];
-        h[i] = q->xptr(which);
-        if (q->xcount(which) != shards[0]->xcount(which)) {
-            chip_set_error("shard_allreduce_local: the shards disagree on the size of the exchange");
-            return CATCHHIP_EINVAL;
-        }
-    }
-    DevBuf<void *> d;
-    TRY(d.alloc(n));
-    HIP_TRY(hipMemcpyAsync(d.p, h.data(), sizeof(void *) * n, hipMemcpyHostToDevice, c0->stream));
-    const size_t count = shards[0]->xcount(which);
-    if (count == 0) return 0;
-    const unsigned blocks = (unsigned)std::min<size_t>(div_up((i64)count, 256), 4096);
-    if (which == 0)
-        hipLaunchKernelGGL((local_allreduce_kernel<u32, false>), dim3(blocks), dim3(256), 0, c0->stream, (u32 *const *)d.p, n, count);
-    else
-        hipLaunchKernelGGL((local_allreduce_kernel<u8, true>), dim3(blocks), dim3(256), 0, c0->stream, (u8 *const *)d.p, n, count);
-    HIP_TRY(hipGetLastError());
+    TRY(shard_exchange(n, shards, which, 1));
     HIP_TRY(hipStreamSynchronize(c0->stream));
     return 0;
 }
@@ -743,191 +416,50 @@ extern "C" int catchhip_shard_allreduce_local(i32 n, catchhip_shard *const *shar
 // exchange over the context's RCCL communicator (one process per GPU)
 extern "C" int catchhip_shard_allreduce(catchhip_shard *S, i32 which) {
     ARG_CHECK(S && (which == 0 || which == 1));
-    catchhip_ctx *c = S->ctx;
-    if (!c->comm) { chip_set_error("shard_allreduce: no communicator (catchhip_comm_init)"); return CATCHHIP_ECOMM; }
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t count = S->xcount(which);
-    if (count == 0) return 0;      // (the same on every rank: the lists derive from the all-reduced gains)
-    void *buf = S->xptr(which);
-    const ncclResult_t r = which == 0 ? rccl().AllReduce(buf, buf, count, ncclUint32, ncclSum, (ncclComm_t)c->comm, c->stream)
-                                      : rccl().AllReduce(buf, buf, count, ncclUint8, ncclMax, (ncclComm_t)c->comm, c->stream);
-    if (r != ncclSuccess) { chip_set_error("ncclAllReduce: %s", rccl().GetErrorString(r)); return CATCHHIP_ECOMM; }
-    return 0;
+    if (!S->ctx->comm) { chip_set_error("shard_allreduce: no communicator (catchhip_comm_init)"); return CATCHHIP_ECOMM; }
+    HIP_TRY(hipSetDevice(S->ctx->device));
+    return shard_exchange(1, &S, which, 0);
 }
 
 // ---- the round loop under the C ABI (round 6) -------------------------------------------------------------------------
-// catch_amd/parallel.py drove the rounds of a sharded solve from the interpreter until round 5: count -> exchange ->
-// claim_check -> exchange -> [verdict -> exchange] -> apply, a handful of library calls and ONE host synchronisation per
-// round -- the packed exchange needs the number of sets that are still alive, which only the device knows -- plus,
-// per round and shard, the flag / scan / compact launches that keep the packed list dense.  Here several rounds are
-// queued per read-back, as the unsharded solver queues them, and the LIST IS KEPT for the whole batch: what travels
-// are the gains and marks of the sets that were alive at the last read-back (a set that has died since carries zeros;
-// a set whose global gain reached zero never gains again, so nothing outside the list can matter).  A round is then
-// count, pack, all-reduce, unpack, claim, pack, all-reduce, unpack, apply -- four per-set launches instead of nine --,
-// the list is compacted once per batch from the all-reduced gains of its last round (the same list on every rank),
-// and its new length comes back with the solver's state in the batch's one read-back.  The done flag stops the
-// launches of rounds queued beyond the end; their collectives still run, on every rank alike (the batch length is
-// the same everywhere).
-// (the marks of the listed sets; list == null: every set)
-__global__ void __launch_bounds__(256)
-sxl_pack_lost_kernel(const u32 *__restrict__ lost, const u32 *__restrict__ list, u32 n, u32 tag, u8 *__restrict__ xl) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) xl[i] = lost[list ? list[i] : i] == tag ? 1 : 0;
-}
-__global__ void __launch_bounds__(256)
-sxl_unpack_lost_kernel(u32 *__restrict__ lost, const u32 *__restrict__ list, u32 n, u32 tag, const u8 *__restrict__ xl) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && xl[i]) lost[list ? list[i] : i] = tag;
-}
-__global__ void __launch_bounds__(256)
-sx_flag_alive_kernel(const u32 *__restrict__ acc, const u32 *__restrict__ list, u32 n, u32 *__restrict__ flag) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) flag[i] = acc[list ? list[i] : i] ? 1u : 0u;
-    else if (i == n) flag[n] = 0u;
-}
-
-// one all-reduce of `count` elements of every shard's buffer `which`: over the communicator (transport 0: one shard
-// per process) or between the shards of this process (transport 1: one device, one stream)
-static int shard_exchange_n(i32 n, catchhip_shard *const *sh, i32 which, size_t count, i32 transport, DevBuf<void *> &d_ptrs) {
-    if (count == 0) return 0;
-    catchhip_ctx *c = sh[0]->ctx;
-    if (transport == 0) {
-        void *buf = sh[0]->xptr(which);
-        const ncclResult_t r = which == 0 ? rccl().AllReduce(buf, buf, count, ncclUint32, ncclSum, (ncclComm_t)c->comm, c->stream)
-                                          : rccl().AllReduce(buf, buf, count, ncclUint8, ncclMax, (ncclComm_t)c->comm, c->stream);
-        if (r != ncclSuccess) { chip_set_error("ncclAllReduce: %s", rccl().GetErrorString(r)); return CATCHHIP_ECOMM; }
-        return 0;
-    }
-    if (n == 1) return 0;
-    void **slot = d_ptrs.p + (size_t)which * n;      // (the pointers of both buffers were uploaded once)
-    const unsigned blocks = (unsigned)std::min<size_t>(div_up((i64)count, 256), 4096);
-    if (which == 0)
-        hipLaunchKernelGGL((local_allreduce_kernel<u32, false>), dim3(blocks), dim3(256), 0, c->stream, (u32 *const *)slot, n, count);
-    else
-        hipLaunchKernelGGL((local_allreduce_kernel<u8, true>), dim3(blocks), dim3(256), 0, c->stream, (u8 *const *)slot, n, count);
-    return 0;
-}
-
-// Runs the instance to its end.  shards: the n shards THIS process holds (transport 0 = RCCL over the context's
-// communicator: n == 1; transport 1 = the shards exchange among themselves: one context).  rounds_per_sync >= 1.
-// *done: 1 finished, -1 the rank list ran out (catchhip_shard_picks then reports it).  Set-parallel shards (small
-// instances) synchronise every round as before -- their launches are the cheap part.
+// Runs the instance to its end, rounds_per_sync >= 1 rounds per read-back.  shards: the n shards THIS process holds
+// (transport 0 = RCCL over the context's communicator: n == 1; transport 1 = the shards exchange among themselves: one
+// context).  *done: 1 finished, -1 the rank list ran out (catchhip_shard_picks then reports it).
 extern "C" int catchhip_shard_solve(i32 n, catchhip_shard *const *shards, i32 transport, i32 rounds_per_sync, i32 *done) {
-    ARG_CHECK(n >= 1 && shards && done && (transport == 0 || transport == 1) && rounds_per_sync >= 1);
+    ARG_CHECK(n >= 1 && n <= SHARD_LOCAL_MAX && shards && done && (transport == 0 || transport == 1) && rounds_per_sync >= 1);
     catchhip_shard *S0 = shards[0];
     ARG_CHECK(S0 != nullptr);
     catchhip_ctx *c = S0->ctx;
     for (i32 i = 0; i < n; ++i) {
-        ARG_CHECK(shards[i] != nullptr && shards[i]->a.nsets == S0->a.nsets);
-        if (shards[i]->ctx != c || (shards[i]->flat != nullptr) != (S0->flat != nullptr) || shards[i]->partial != S0->partial ||
-            shards[i]->round != 0) {
-            chip_set_error("shard_solve: the shards of one process share a context, a kernel family and start at round 0");
+        ARG_CHECK(shards[i] != nullptr && shards[i]->nsets == S0->nsets);
+        if (shards[i]->ctx != c || shards[i]->partial != S0->partial || shards[i]->round != 0) {
+            chip_set_error("shard_solve: the shards of one process share a context, the coverage and start at round 0");
             return CATCHHIP_EINVAL;
         }
     }
     if (transport == 0 && (n != 1 || !c->comm)) { chip_set_error("shard_solve: RCCL needs one shard per process and a communicator"); return CATCHHIP_ECOMM; }
     HIP_TRY(hipSetDevice(c->device));
     PoolScope pool_scope(c);
-    hipStream_t s = c->stream;
-    if (!S0->flat) {
-        // set-parallel shards: the existing entry points, round by round
-        for (;;) {
-            for (i32 i = 0; i < n; ++i) TRY(catchhip_shard_count(shards[i]));
-            if (transport == 0) TRY(catchhip_shard_allreduce(S0, 0)); else TRY(catchhip_shard_allreduce_local(n, shards, 0));
-            for (i32 i = 0; i < n; ++i) TRY(catchhip_shard_claim_check(shards[i]));
-            if (transport == 0) TRY(catchhip_shard_allreduce(S0, 1)); else TRY(catchhip_shard_allreduce_local(n, shards, 1));
-            i32 d0 = 0;
-            for (i32 i = 0; i < n; ++i) {
-                i32 d = 0;
-                TRY(catchhip_shard_apply(shards[i], &d));
-                if (i == 0) d0 = d;
-                else if (d != d0) { chip_set_error("shard_solve: shards disagree on termination"); return CATCHHIP_EINVAL; }
-            }
-            if (d0) { *done = d0; return 0; }
-        }
-    }
-    const u32 nsets = S0->a.nsets;
-    DevBuf<void *> d_ptrs;
-    if (transport == 1 && n > 1) {
-        std::vector<void *> h((size_t)2 * n);
-        for (i32 i = 0; i < n; ++i) { h[(size_t)i] = shards[i]->xptr(0); h[(size_t)n + i] = shards[i]->xptr(1); }
-        TRY(d_ptrs.alloc((size_t)2 * n));
-        HIP_TRY(hipMemcpyAsync(d_ptrs.p, h.data(), sizeof(void *) * 2 * n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    u32 cap = nsets;          // listed sets = the sets alive at the last read-back
-    int lcur = -1;            // which of xlist holds the list (-1: every set)
-    u32 round = 0;
-    const i64 max_rounds = 2 * (i64)nsets + 4;      // (a round accepts a set or moves on to the next rank)
     for (;;) {
-        const unsigned gb_gain = (unsigned)div_up((i64)cap + 2, 256), gb_cap = (unsigned)div_up((i64)std::max<u32>(cap, 1), 256);
-        for (i32 r = 0; r < rounds_per_sync; ++r, ++round) {
-            const u32 tag = round + 1;
-            for (i32 i = 0; i < n; ++i) {
-                catchhip_shard *S = shards[i];
-                S->flat->launch_count(round);
-                hipLaunchKernelGGL(sx_pack_gain_kernel, dim3(gb_gain), dim3(256), 0, s, (const u32 *)S->flat->fa.acc[round & 1],
-                                   lcur < 0 ? (const u32 *)nullptr : (const u32 *)S->xlist[lcur].p, cap, nsets, S->xg.p);
-            }
-            TRY(shard_exchange_n(n, shards, 0, (size_t)cap + 2, transport, d_ptrs));
-            for (i32 i = 0; i < n; ++i) {
-                catchhip_shard *S = shards[i];
-                const u32 *lp = lcur < 0 ? (const u32 *)nullptr : (const u32 *)S->xlist[lcur].p;
-                hipLaunchKernelGGL(sx_unpack_gain_kernel, dim3(gb_gain), dim3(256), 0, s, S->flat->fa.acc[round & 1], lp, cap, nsets,
-                                   (const u32 *)S->xg.p, S->xflag.p);
-                S->flat->launch_claim(round);
-                if (cap) hipLaunchKernelGGL(sxl_pack_lost_kernel, dim3(gb_cap), dim3(256), 0, s, (const u32 *)S->flat->fa.lost, lp, cap, tag, S->xl.p);
-            }
-            TRY(shard_exchange_n(n, shards, 1, (size_t)cap, transport, d_ptrs));
+        for (i32 r = 0; r < rounds_per_sync; ++r) {
+            for (i32 i = 0; i < n; ++i) shard_count(shards[i]);
+            TRY(shard_exchange(n, shards, 0, transport));
+            for (i32 i = 0; i < n; ++i) shard_claim(shards[i]);
+            TRY(shard_exchange(n, shards, 1, transport));
             if (S0->partial) {
-                for (i32 i = 0; i < n; ++i) {
-                    catchhip_shard *S = shards[i];
-                    const u32 *lp = lcur < 0 ? (const u32 *)nullptr : (const u32 *)S->xlist[lcur].p;
-                    if (cap) hipLaunchKernelGGL(sxl_unpack_lost_kernel, dim3(gb_cap), dim3(256), 0, s, S->flat->fa.lost, lp, cap, tag, (const u8 *)S->xl.p);
-                    S->flat->launch_verdict(round);
-                    if (cap) hipLaunchKernelGGL(sxl_pack_lost_kernel, dim3(gb_cap), dim3(256), 0, s, (const u32 *)S->flat->fa.lost, lp, cap, tag, S->xl.p);
-                }
-                TRY(shard_exchange_n(n, shards, 1, (size_t)cap, transport, d_ptrs));
+                for (i32 i = 0; i < n; ++i) shard_verdict(shards[i]);
+                TRY(shard_exchange(n, shards, 1, transport));
             }
-            for (i32 i = 0; i < n; ++i) {
-                catchhip_shard *S = shards[i];
-                const u32 *lp = lcur < 0 ? (const u32 *)nullptr : (const u32 *)S->xlist[lcur].p;
-                if (cap) hipLaunchKernelGGL(sxl_unpack_lost_kernel, dim3(gb_cap), dim3(256), 0, s, S->flat->fa.lost, lp, cap, tag, (const u8 *)S->xl.p);
-                S->flat->launch_apply(round);
+            for (i32 i = 0; i < n; ++i) shard_apply(shards[i]);
+        }
+        for (i32 i = 0; i < n; ++i) TRY(shard_compact(shards[i]));
+        for (i32 i = 0; i < n; ++i) {
+            TRY(shard_read_back(shards[i]));
+            if (shards[i]->done != S0->done || shards[i]->cap != S0->cap) {
+                chip_set_error("shard_solve: shards disagree (alive sets or termination)");
+                return CATCHHIP_EINVAL;
             }
         }
-        // the end of a batch: the list compacted to the sets that still have a global gain (the all-reduced gains of
-        // the last round: the same on every rank), then the one read-back -- every shard's state and the list's length
-        const int lnext = lcur < 0 ? 0 : lcur ^ 1;
-        for (i32 i = 0; i < n; ++i) {
-            catchhip_shard *S = shards[i];
-            const u32 *lp = lcur < 0 ? (const u32 *)nullptr : (const u32 *)S->xlist[lcur].p;
-            hipLaunchKernelGGL(sx_flag_alive_kernel, dim3((unsigned)div_up((i64)cap + 1, 256)), dim3(256), 0, s,
-                               (const u32 *)S->flat->fa.acc[(round - 1) & 1], lp, cap, S->xflag.p);
-            TRY(chip_exclusive_scan_u32(c, S->xflag.p, S->xpos.p, (i64)cap + 1, S->xtmp));
-            hipLaunchKernelGGL(sx_compact_kernel, dim3(gb_cap), dim3(256), 0, s, lp, cap, (const u32 *)S->xflag.p,
-                               (const u32 *)S->xpos.p, S->xlist[lnext].p, S->xflag.p + cap);     // (the count lands in the scanned flag slot)
-        }
-        HIP_TRY(hipGetLastError());
-        u32 n_alive = 0;
-        int d0 = 0;
-        for (i32 i = 0; i < n; ++i) {
-            catchhip_shard *S = shards[i];
-            static_assert(sizeof(GreedyState) + sizeof(u32) <= 64 * sizeof(u64), "ctx->h_pin holds the state and one more word");
-            u32 *h_n = (u32 *)((u8 *)c->h_pin + sizeof(GreedyState));
-            HIP_TRY(hipMemcpyAsync(c->h_pin, S->flat->fa.st, sizeof(GreedyState), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(h_n, S->xflag.p + cap, sizeof(u32), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            memcpy(&S->h_st, c->h_pin, sizeof(GreedyState));
-            const u32 na = *(volatile u32 *)h_n;
-            const int d = S->h_st.done == 2 ? -1 : (S->h_st.done ? 1 : 0);
-            if (i == 0) { n_alive = na; d0 = d; }
-            else if (na != n_alive || d != d0) { chip_set_error("shard_solve: shards disagree (alive sets or termination)"); return CATCHHIP_EINVAL; }
-            S->round = round; S->done = d; S->n_prev = S->n_cur = na; S->lprev = lnext;
-        }
-        if (d0) { *done = d0; return 0; }
-        if ((i64)round > max_rounds) { chip_set_error("shard: round cap exceeded"); return CATCHHIP_EINVAL; }
-        cap = n_alive;
-        lcur = lnext;
+        if (S0->done) { *done = S0->done; return 0; }
     }
 }

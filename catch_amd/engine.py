@@ -177,6 +177,9 @@ class Context:
         self.device = int(device)
 
     def close(self):
+        """Destroys the context.  An object made on it that is still open is not destroyed afterwards (its device
+        memory stays allocated): the garbage collector may finalize a context before such objects when they are
+        part of one cycle (e.g. the frame of a failed test), and their destroy calls would read the freed context."""
         if self._h:
             self._L.catchhip_ctx_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -379,7 +382,7 @@ class Targets:
                                                       _ptr(g, c_i32p)))
 
     def close(self):
-        if self._h:
+        if self._h and self.ctx._h:      # (see Context.close)
             self.ctx._L.catchhip_targets_destroy(self._h)
             self._h = ctypes.c_void_p()
 
@@ -428,7 +431,7 @@ class Probes:
                                                      _ptr(g, c_i32p)))
 
     def close(self):
-        if self._h:
+        if self._h and self.ctx._h:      # (see Context.close)
             self.ctx._L.catchhip_probes_destroy(self._h)
             self._h = ctypes.c_void_p()
 
@@ -560,7 +563,7 @@ class Candidates:
         return p
 
     def close(self):
-        if self._h:
+        if self._h and self.ctx._h:      # (see Context.close)
             self.ctx._L.catchhip_candidates_destroy(self._h)
             self._h = ctypes.c_void_p()
 
@@ -720,7 +723,7 @@ class Rows:
         return out[:n_out.value].tolist()
 
     def close(self):
-        if self._h:
+        if self._h and self.ctx._h:      # (see Context.close)
             self.ctx._L.catchhip_rows_destroy(self._h)
             self._h = ctypes.c_void_p()
 
@@ -789,9 +792,9 @@ class Shard:
         check(self.ctx._L.catchhip_shard_allreduce(self._h, int(which)))
 
     def _exchange_shape(self):
-        """(gain elements, lost elements, lost dtype) of the NEXT exchange: shards
-        that run the flat kernels pack their buffers (only the sets still alive
-        travel), so the sizes change from round to round."""
+        """(gain elements, lost elements, lost dtype) of the NEXT exchange: the
+        buffers are packed (only the sets alive at the last apply travel), so
+        the sizes change from round to round."""
         info = np.zeros(4, dtype=np.int64)
         check(self.ctx._L.catchhip_shard_info(self._h, _ptr(info, c_i64p)))
         return int(info[0]), int(info[1]), (np.uint32 if info[2] == 4 else np.uint8)
@@ -821,7 +824,7 @@ class Shard:
         return out[:n.value].tolist()
 
     def close(self):
-        if self._h:
+        if self._h and self.ctx._h:      # (see Context.close)
             self.ctx._L.catchhip_shard_destroy(self._h)
             self._h = ctypes.c_void_p()
 
@@ -888,7 +891,7 @@ class Signatures:
             ctypes.byref(self._h)))
 
     def close(self):
-        if self._h:
+        if self._h and self.ctx._h:      # (see Context.close)
             self.ctx._L.catchhip_sigs_destroy(self._h)
             self._h = ctypes.c_void_p()
 

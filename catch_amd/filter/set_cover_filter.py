@@ -346,8 +346,7 @@ class SetCoverFilter(BaseFilter):
         group above an even share of the bases is sharded over ALL ranks by
         universes: every rank scans the group's candidates against its own
         range of genomes and the frontier solver's rounds exchange the
-        per-candidate gains (RCCL all-reduce, catch_amd/parallel.py).  Sharding
-        needs full coverage; groups under partial coverage stay whole.  Ranks
+        per-candidate gains (RCCL all-reduce, catch_amd/parallel.py).  Ranks
         (identify / avoided genomes) are computed by every rank for the groups
         it shares.  Every rank returns every group's selection."""
         import os
@@ -420,9 +419,8 @@ class SetCoverFilter(BaseFilter):
                                              instance_partial=part)
                         qualifies = True
                     except ValueError as exc:
-                        # the expected refusals: rows too long for the sharded kernels, partial coverage with too few
-                        # sets for the row-parallel ones -> whole group
-                        if "longer than 257" not in str(exc) and "row-parallel kernels only" not in str(exc):
+                        # the expected refusal: rows too long or too many sets for the sharded kernels -> whole group
+                        if "solved unsharded" not in str(exc):
                             raise
                 except Exception as exc:          # noqa: BLE001 -- reported collectively
                     err = "%s: %s" % (type(exc).__name__, exc)

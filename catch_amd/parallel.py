@@ -65,7 +65,7 @@ def merge_picks(picks, keys, ranks=None):
 # ---------------------------------------------------------------------------
 # the round loop of a universe-sharded solve (include/catchhip.h,
 # catchhip_shard_*).  `shard` is anything with count() / claim_check() /
-# apply() / picks(); `exchange(which)` performs the all-reduce of the gain
+# verdict() / apply() / picks(); `exchange(which)` performs the all-reduce of the gain
 # (which = 0, SUM) or lost (which = 1, MAX) buffers of all shards of the
 # instance.  The same loop serves one process per GPU (RCCL), several shards in
 # one process (tests on one GPU) and the CPU stand-ins of the gloo tests.
@@ -79,8 +79,8 @@ def sharded_solve(shards, exchange, native=None):
     "local" (the shards of this process, one context): the loop runs under the
     C ABI (catchhip_shard_solve, round 6: several rounds per host read-back)
     and `exchange` is not used; None: the loop below, one library call per
-    step and whatever transport `exchange` is (the host / TCP fallback, the
-    CPU stand-ins of the tests)."""
+    step, one host read-back per round (in apply) and whatever transport
+    `exchange` is (the host / TCP fallback, the CPU stand-ins of the tests)."""
     if native is not None:
         from catch_amd import engine
         return engine.shards_solve(shards, native)
@@ -149,8 +149,7 @@ def plan_with_sharding(group_costs, world, min_cost=0, slack=1.08, eligible=None
 # goes over catch_amd.netstore.TcpGroup (plain sockets; no torch anywhere in the product: the gloo stand-in the CPU
 # tests use lives in tests/gloo_group.py since round 6); the data path's exchanges
 # are RCCL all-reduces on device buffers (catchhip_shard_allreduce) over a communicator attached to a context of
-# its own (a context with a communicator switches catchhip_setcover_greedy to the per-pick sharded form, which
-# the whole-group solves must not take).
+# its own.
 # ---------------------------------------------------------------------------
 class World:
     def __init__(self, rank=0, size=1, group=None, comm_ctx=None, rccl=False):

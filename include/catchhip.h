@@ -299,10 +299,10 @@ int catchhip_ctx_last_grid_counters(catchhip_ctx *ctx, int64_t *out4);
 
 /* Multi-GPU, one process per GPU: an RCCL communicator attached to a context
  * (the reference has no counterpart: it forks a process pool,
- * catch/probe.py:727-743, catch/filter/set_cover_filter.py:848-900).  With a
- * communicator catchhip_setcover_greedy takes the per-pick form: every rank
- * holds the full rows, rank r evaluates the gains of sets s with s % nranks ==
- * r and the winner is agreed by one all-reduce(MAX) of a 64-bit key per pick. */
+ * catch/probe.py:727-743, catch/filter/set_cover_filter.py:848-900).  The
+ * communicator carries the exchanges of universe-sharded instances
+ * (catchhip_shard_allreduce, catchhip_shard_solve); every other call on the
+ * context runs as on any other context. */
 int catchhip_comm_unique_id(uint8_t *id128);
 int catchhip_comm_init(catchhip_ctx *ctx, const uint8_t *id128, int32_t nranks,
                        int32_t rank);
@@ -332,12 +332,16 @@ int catchhip_comm_info(char *buf, int64_t len);
  *                                          _allreduce_local for shards of one process)
  *     catchhip_shard_claim_check  claims + local losses (enqueued)
  *     all-reduce MAX of the lost buffer   (which = 1)
- *     catchhip_shard_apply        accepted sets applied; synchronises; *done =
+ *     catchhip_shard_apply        accepted sets applied; synchronises (the one
+ *                                 host synchronisation of a round); *done =
  *                                 1 finished, -1 ranks exhausted, 0 next round
  * and catchhip_shard_picks returns the picks in the sequential pick order --
- * the same list on every rank, identical to the unsharded solver's.  Rows of
- * at most 257 bases; other instances are solved whole on one rank
- * (catch_amd/parallel.py).
+ * the same list on every rank, identical to the unsharded solver's.  A shard is
+ * single-use: once it has reported done, the steps and catchhip_shard_solve
+ * refuse it (CATCHHIP_EINVAL); only _picks, _info and _destroy remain.
+ * Instances of 1 to 2^25 sets with rows of at most 257 bases, full or partial
+ * coverage; anything else is refused with CATCHHIP_EINVAL ("... solved
+ * unsharded") and solved whole on one rank (catch_amd/parallel.py).
  * Partial coverage (catchhip_shard_create_p with universe_p, one fraction per
  * LOCAL universe, some below 1; set_cover.py:362-373, 393-433): need[u] and the
  * acceptance thresholds of a universe live on the rank that owns it; a claimant
@@ -346,16 +350,15 @@ int catchhip_comm_info(char *buf, int64_t len);
  *     catchhip_shard_verdict      local universe tests of the candidates left; a
  *                                 failure is one more lost mark (enqueued)
  *     all-reduce MAX of the lost buffer once more (which = 1)
- * (a no-op for shards created without universe_p).  Sharded by the row-parallel
- * kernels only (65,536 to 2^25 sets; CATCHHIP_EINVAL otherwise: solve it whole).
+ * (a no-op for shards created without universe_p).
  * catchhip_shard_buffers exposes the two exchange buffers (device pointers:
  * uint32[gain_count], uint8[lost_count]) for callers with their own
- * transport.  Ask again before EVERY exchange: large shards pack their
- * buffers -- only the sets whose global gain was still positive after the
- * previous round (gains) / is positive in this one (marks) travel, in set
- * order, a list every rank derives from the same all-reduced gains -- so the
- * counts shrink from round to round (they are the same on every rank) and may
- * reach 0, in which case there is nothing to exchange. */
+ * transport.  Ask again after EVERY apply: the buffers are packed -- only the
+ * sets whose global gain was still positive at the last apply travel, in set
+ * order, a list every rank derives from the same all-reduced gains (gain_count
+ * = lost_count + 2) -- so the counts shrink from round to round (they are the
+ * same on every rank) and may reach 0, in which case there is nothing to
+ * exchange but the two extra gain slots. */
 typedef struct catchhip_shard catchhip_shard;
 int catchhip_shard_create(catchhip_ctx *ctx, const catchhip_rows *rows,
                           int64_t num_sets, const int64_t *ranks,
@@ -384,12 +387,12 @@ int catchhip_shard_buffers(catchhip_shard *shard, void **gain,
 int catchhip_shard_picks(catchhip_shard *shard, int64_t *out_ids,
                          int64_t *n_out);
 /* out4 = {elements of the gain buffer (uint32) and of the lost buffer (uint8)
- * in the NEXT exchange, bytes per lost element (1), 1 if the row-parallel
- * kernels of large shards run}. */
+ * in the NEXT exchange, bytes per lost element (1), 1 | 2 if the instance is
+ * partial}. */
 int catchhip_shard_info(catchhip_shard *shard, int64_t *out4);
 /* which: 0 = gain buffer (SUM), 1 = lost buffer (MAX).  _allreduce uses the
  * context's RCCL communicator (stream-ordered); _allreduce_local reduces the
- * buffers of n shards that live in this process on one device. */
+ * buffers of n <= 64 shards that live in this process on one device. */
 int catchhip_shard_allreduce(catchhip_shard *shard, int32_t which);
 /* Exchange buffer `which` to (to_host != 0) or from a host array of the
  * buffer's size (synchronous): for a transport of the caller's own. */
@@ -401,7 +404,8 @@ int catchhip_shard_allreduce_local(int32_t n, catchhip_shard *const *shards,
  * interpreter, one host synchronisation per round, until then): count -> all-reduce SUM -> claim -> all-reduce MAX ->
  * [partial coverage: verdict -> all-reduce MAX] -> apply, queued stream-ordered rounds_per_sync rounds at a time; the
  * exchange buffers keep the capacity of the last read-back, the done flag and the number of sets still alive are read
- * back once per batch.  shards: the n shards this process holds, fresh (round 0); transport 0: RCCL over the
+ * back once per batch (the step functions above are batches of one round).  shards: the n <= 64 shards this process
+ * holds, fresh (round 0); transport 0: RCCL over the
  * context's communicator (one shard per process, one process per GPU: the production path, replaces the worker pool
  * of catch/filter/set_cover_filter.py:848-900 for a group that is sharded), 1: the shards of this process exchange
  * among themselves (one context; tests, and one-GPU runs of several ranges).  *done: 1 finished, -1 rank list

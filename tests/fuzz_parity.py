@@ -46,7 +46,7 @@ def rand_group(rnd):
 
 
 SOLVER_ENV = ("CATCHHIP_FLAT_MIN_ROWS", "CATCHHIP_FLAT_STRIPED", "CATCHHIP_GF_LONG", "CATCHHIP_SEED_LIST",
-              "CATCHHIP_SHARD_FLAT", "CATCHHIP_FLAT_COUNT_ROUND0")
+              "CATCHHIP_FLAT_COUNT_ROUND0")
 
 
 def one_case(seed, ctx):
@@ -55,7 +55,6 @@ def one_case(seed, ctx):
     for name in SOLVER_ENV:
         os.environ.pop(name, None)
     variant = random.Random(seed * 7919 + 13).choice(["default", "flat", "flat_striped", "flat_count0", "long", "seed_list"])
-    os.environ["CATCHHIP_SHARD_FLAT"] = "1" if seed % 2 else "0"
     if variant.startswith("flat"):
         os.environ["CATCHHIP_FLAT_MIN_ROWS"] = "0"
         if variant == "flat_striped":
@@ -132,9 +131,9 @@ def one_case(seed, ctx):
         a = rows.fetch()
         ok_len = a[0].size == 0 or int((a[3] - a[2]).max()) <= 257
         whole = rows.greedy(len(cands[0]))
-        # ... and under partial coverage (row-parallel shards only: odd seeds), fractions per universe
+        # ... and under partial coverage, fractions per universe
         up = None
-        if seed % 2 and ok_len:
+        if ok_len:
             up = [rnd.choice([1.0, 0.9, 0.5, 0.25]) for _ in groups[0]]
             if all(x >= 1.0 for x in up):
                 up[0] = 0.8

@@ -49,16 +49,21 @@ def main():
     want = [sorted(c[i] for i in ids) for c, ids in zip(cands, exp)]
     ok = ok and got == want and f.last_timings.get("sharded_groups") == [1]
     # -c 0.9 (round 4): the sharded group's universes keep their needs and acceptance thresholds on the rank that
-    # owns them; with the row-parallel kernels forced (an instance this small would take the set-parallel ones,
-    # which refuse partial coverage: then the group is solved whole -- both ways the oracle's selection)
+    # owns them
     exp = orc.set_cover_filter(cands, groups, 2, 100, coverage=0.9, cover_extension=50)
     want = [sorted(c[i] for i in ids) for c, ids in zip(cands, exp)]
-    for forced in ("1", "0"):
-        os.environ["CATCHHIP_SHARD_FLAT"] = forced
-        f = SetCoverFilter(mismatches=2, lcf_thres=100, coverage=0.9, cover_extension=50)
-        out = f.filter([[probe.Probe.from_str(s) for s in c] for c in cands], gen, input_is_grouped=True)
-        got = [sorted(p.seq_str for p in g) for g in out]
-        ok = ok and got == want and f.last_timings.get("sharded_groups") == [1]
+    f = SetCoverFilter(mismatches=2, lcf_thres=100, coverage=0.9, cover_extension=50)
+    out = f.filter([[probe.Probe.from_str(s) for s in c] for c in cands], gen, input_is_grouped=True)
+    got = [sorted(p.seq_str for p in g) for g in out]
+    ok = ok and got == want and f.last_timings.get("sharded_groups") == [1]
+    # rows longer than 257 bases (cover extension 80): every rank's shard is refused and the group planned for
+    # sharding is solved whole -- the oracle's selection
+    exp = orc.set_cover_filter(cands, groups, 2, 100, coverage=1.0, cover_extension=80)
+    want = [sorted(c[i] for i in ids) for c, ids in zip(cands, exp)]
+    f = SetCoverFilter(mismatches=2, lcf_thres=100, coverage=1.0, cover_extension=80)
+    out = f.filter([[probe.Probe.from_str(s) for s in c] for c in cands], gen, input_is_grouped=True)
+    got = [sorted(p.seq_str for p in g) for g in out]
+    ok = ok and got == want and f.last_timings.get("sharded_groups") == [1]
     # coverage given in BASES: the sharded group's first nine genomes are shorter than the
     # coverage asked for (p == 1.0), the last five longer (p < 1): with two ranks the first rank's own universes are
     # all full-coverage ones -- it must still build a partial shard and run the partial rounds (the instance is)
@@ -68,12 +73,10 @@ def main():
     gen_b = [[genome.Genome.from_one_seq(g[0]) for g in grp] for grp in groups_b]
     exp = orc.set_cover_filter(cands_b, groups_b, 2, 100, coverage=4500, cover_extension=50)
     want = [sorted(c[i] for i in ids) for c, ids in zip(cands_b, exp)]
-    os.environ["CATCHHIP_SHARD_FLAT"] = "1"
     f = SetCoverFilter(mismatches=2, lcf_thres=100, coverage=4500, cover_extension=50)
     out = f.filter([[probe.Probe.from_str(s) for s in c] for c in cands_b], gen_b, input_is_grouped=True)
     got = [sorted(p.seq_str for p in g) for g in out]
     ok = ok and got == want and f.last_timings.get("sharded_groups") == [1]
-    os.environ.pop("CATCHHIP_SHARD_FLAT", None)
     res = W.allgather(ok)
     if W.rank == 0:
         print("MULTIRANK_PLUGIN_OK" if all(res) else "MULTIRANK_PLUGIN_MISMATCH %s" % res)

@@ -864,10 +864,10 @@ def test_ndf_hamming_matches_oracle_large(ctx, oracle):
 
 
 # ---------------------------------------------------------------- RCCL path
-def test_greedy_rccl_solver_single_rank_matches(oracle):
-    """The sharded multi-launch solver (gain kernel + RCCL all-reduce(MAX) +
-    apply kernel) with a one-rank communicator must give the same picks in
-    the same order as the oracle (and hence as the persistent solver)."""
+def test_greedy_rccl_solver_single_rank_matches(ctx, oracle):
+    """A context with a (one-rank) communicator solves a whole instance like
+    any other context: the same picks in the same order as the oracle and as
+    a context without one."""
     engine = _engine()
     c2 = engine.Context(0)
     with pytest.raises(ValueError):
@@ -891,6 +891,9 @@ def test_greedy_rccl_solver_single_rank_matches(oracle):
         exp = oracle.approx_multiuniverse(r[:, 0], r[:, 1], r[:, 2], r[:, 3], P, U,
                                           None, up, ranks)
         dev = engine.Rows.from_host(c2, r[:, 0], r[:, 1], r[:, 2], r[:, 3], glen)
+        assert dev.greedy(P, ranks, up) == exp
+        dev.close()
+        dev = engine.Rows.from_host(ctx, r[:, 0], r[:, 1], r[:, 2], r[:, 3], glen)
         assert dev.greedy(P, ranks, up) == exp
         dev.close()
     c2.close()
@@ -919,18 +922,16 @@ def _sharded_picks(engine, ctx, probes, genomes, bounds, n_sets, ranks, exchange
             h.close()
 
 
-@pytest.mark.parametrize("flat", ["0", "1"])
+@pytest.mark.parametrize("partial", [0, 1])
 @pytest.mark.parametrize("with_ranks", [False, True])
-def test_universe_sharded_solver_equals_unsharded(ctx, oracle, monkeypatch, with_ranks, flat):
+def test_universe_sharded_solver_equals_unsharded(ctx, oracle, with_ranks, partial):
     """One group cut into 1, 2, 3 and 5 universe ranges (split_universes), each
     scanned and held by its own shard, solved in rounds with the two
     all-reduces per round (here: between shards of this process): the picks
-    and their order equal the unsharded solver's and the oracle's."""
+    and their order equal the unsharded solver's and the oracle's.
+    partial = 0: full coverage, and the one refusal; 1: partial coverage."""
     from catch_amd import parallel
     engine, probe = _engine(), _probe_mod()
-    # both kernel families behind the shard API: set-parallel (small instances)
-    # and row-parallel tile-ordered (what an instance worth sharding takes)
-    monkeypatch.setenv("CATCHHIP_SHARD_FLAT", flat)
     rng = np.random.Generator(np.random.PCG64(99))
     from catch_amd.utils import synthetic
     genomes = synthetic.make_species(rng, [6000], 23, 3, 0.06, 0.012)
@@ -947,20 +948,30 @@ def test_universe_sharded_solver_equals_unsharded(ctx, oracle, monkeypatch, with
     assert want == exp and len(want) > 20
     rows.close(); t.close()
     lens = [sum(len(s) for s in g) for g in genomes]
-    for world in (1, 2, 3, 5):
-        bounds = parallel.split_universes(lens, world)
-        assert bounds[0] == 0 and bounds[-1] == len(genomes) and len(bounds) == world + 1
-        got = _sharded_picks(engine, ctx, p, genomes, bounds, len(cand), ranks,
+    if not partial:
+        for world in (1, 2, 3, 5):
+            bounds = parallel.split_universes(lens, world)
+            assert bounds[0] == 0 and bounds[-1] == len(genomes) and len(bounds) == world + 1
+            got = _sharded_picks(engine, ctx, p, genomes, bounds, len(cand), ranks,
+                                 lambda sh: (lambda w: engine.shards_allreduce_local(sh, w)))
+            assert got == want, world
+        # a rank without genomes (more ranks than genomes can feed) still takes part
+        got = _sharded_picks(engine, ctx, p, genomes, [0, 0, 10, 23, 23], len(cand), ranks,
                              lambda sh: (lambda w: engine.shards_allreduce_local(sh, w)))
-        assert got == want, world
-    # a rank without genomes (more ranks than genomes can feed) still takes part
-    got = _sharded_picks(engine, ctx, p, genomes, [0, 0, 10, 23, 23], len(cand), ranks,
-                         lambda sh: (lambda w: engine.shards_allreduce_local(sh, w)))
-    assert got == want
-    # partial coverage (round 4; row-parallel kernels only): need[u] and the acceptance thresholds of a universe on
-    # the rank that owns it, the candidates' verdicts exchanged with the lost marks -- the unsharded picks, in order;
-    # uniform and mixed fractions (a shard whose own universes all want full cover still takes part in the third step)
-    if flat == "1":
+        assert got == want
+        # the one refusal: rows longer than 257 bases (100-base probes, cover extension 80) -- the caller solves the group
+        # whole
+        t = engine.Targets(ctx, genomes)
+        rows = engine.Rows.scan(ctx, p, t, 2, 100, 0, 80)
+        with pytest.raises(ValueError, match="solved unsharded"):
+            engine.Shard(rows, len(cand), ranks)
+        with pytest.raises(ValueError, match="solved unsharded"):
+            engine.Shard(rows, len(cand), ranks, [0.9] * len(genomes))
+        rows.close(); t.close()
+    else:
+        # partial coverage (round 4): need[u] and the acceptance thresholds of a universe on
+        # the rank that owns it, the candidates' verdicts exchanged with the lost marks -- the unsharded picks, in order;
+        # uniform and mixed fractions (a shard whose own universes all want full cover still takes part in the third step)
         for up in ([0.9] * len(genomes), [1.0] * 12 + [0.6] * (len(genomes) - 12), [0.35, 1.0] * (len(genomes) // 2) + [0.8]):
             t = engine.Targets(ctx, genomes)
             rows = engine.Rows.scan(ctx, p, t, 2, 100, 0, 50)
@@ -973,23 +984,15 @@ def test_universe_sharded_solver_equals_unsharded(ctx, oracle, monkeypatch, with
                 got = _sharded_picks(engine, ctx, p, genomes, bounds, len(cand), ranks,
                                      lambda sh: (lambda w: engine.shards_allreduce_local(sh, w)), up)
                 assert got == want_p, (up[:3], bounds)
-    else:
-        t = engine.Targets(ctx, genomes)
-        rows = engine.Rows.scan(ctx, p, t, 2, 100, 0, 50)
-        with pytest.raises(ValueError, match="row-parallel kernels only"):
-            engine.Shard(rows, len(cand), ranks, [0.9] * len(genomes))
-        rows.close(); t.close()
     p.close()
 
 
-@pytest.mark.parametrize("flat", ["0", "1"])
-def test_universe_sharded_solver_over_rccl_single_rank(oracle, monkeypatch, flat):
+def test_universe_sharded_solver_over_rccl_single_rank(oracle):
     """The same round loop with the exchanges going through RCCL
-    (catchhip_shard_allreduce) on a one-rank communicator; with the row-parallel
-    kernels the exchange is packed (only the sets still alive travel): its sizes
-    never grow, and what travels last is next to nothing."""
+    (catchhip_shard_allreduce) on a one-rank communicator; the exchange is
+    packed (only the sets alive at the last apply travel): its sizes never
+    grow, and what travels last is next to nothing."""
     engine, probe = _engine(), _probe_mod()
-    monkeypatch.setenv("CATCHHIP_SHARD_FLAT", flat)
     c2 = engine.Context(0)
     c2.comm_init(engine.Context.comm_unique_id(), 1, 0)
     genomes = small_species(seed=17, n=9, length=4000)
@@ -1010,28 +1013,24 @@ def test_universe_sharded_solver_over_rccl_single_rank(oracle, monkeypatch, flat
     assert got == sel
     gains = [n for w, n in shapes if w == 0]
     marks = [n for w, n in shapes if w == 1]
-    assert gains[0] == len(cand) + 2 and marks[0] <= len(cand)
-    if flat == "1":
-        assert all(a >= b for a, b in zip(gains, gains[1:])) and all(a >= b for a, b in zip(marks, marks[1:]))
-        assert gains[-1] < gains[0] // 4 and all(g == m + 2 for g, m in zip(gains[1:], marks))
-    else:
-        assert all(n == len(cand) + 2 for n in gains)
+    assert gains[0] == len(cand) + 2 and marks[0] == len(cand) and len(gains) == len(marks)
+    assert all(a >= b for a, b in zip(gains, gains[1:])) and all(a >= b for a, b in zip(marks, marks[1:]))
+    assert gains[-1] < gains[0] // 4 and all(g == m + 2 for g, m in zip(gains, marks))
     p.close()
     c2.close()
 
 
-@pytest.mark.parametrize("flat", ["0", "1"])
-def test_round_loop_under_the_c_abi_equals_the_interpreters_loop(ctx, oracle, monkeypatch, flat):
+@pytest.mark.parametrize("partial", [0, 1])
+def test_round_loop_under_the_c_abi_equals_the_interpreters_loop(ctx, oracle, partial):
     """catchhip_shard_solve (round 6: the whole round loop of a sharded instance in one call, several rounds queued
     per host read-back, exchange buffers at the capacity of the last read-back) == parallel.sharded_solve's loop in
-    the interpreter (one read-back per round, exact exchange sizes) == the unsharded picks == the oracle, in pick
-    order: 1, 2, 3 and 5 universe ranges exchanging among themselves (transport "local"), 1 / 3 / 16 rounds per
-    read-back, with and without ranks, full and partial coverage (uniform and mixed fractions; row-parallel kernels),
-    a shard without genomes; and over RCCL on a one-rank communicator (transport "rccl")."""
+    the interpreter (the step functions: one read-back per round, in apply) == the unsharded picks == the oracle, in
+    pick order: 1, 2, 3 and 5 universe ranges exchanging among themselves (transport "local"), 1 / 3 / 16 rounds per
+    read-back, with and without ranks, full and partial coverage (uniform and mixed fractions), a shard without
+    genomes; and over RCCL on a one-rank communicator (transport "rccl").  partial = 0: full coverage, 1: partial."""
     from catch_amd import parallel
     from catch_amd.utils import synthetic
     engine, probe = _engine(), _probe_mod()
-    monkeypatch.setenv("CATCHHIP_SHARD_FLAT", flat)
     rng = np.random.Generator(np.random.PCG64(199))
     genomes = synthetic.make_species(rng, [6000], 21, 3, 0.06, 0.012)
     cand = candidates(genomes, 100, 50)
@@ -1060,8 +1059,7 @@ def test_round_loop_under_the_c_abi_equals_the_interpreters_loop(ctx, oracle, mo
 
     for with_ranks in (False, True):
         ranks = rng.integers(0, 3, size=len(cand)) if with_ranks else None
-        ups = [None] + ([[0.9] * len(genomes), [0.35, 1.0] * (len(genomes) // 2) + [0.8]] if flat == "1" else [])
-        for up in ups:
+        for up in ([[0.9] * len(genomes), [0.35, 1.0] * (len(genomes) // 2) + [0.8]] if partial else [None]):
             t = engine.Targets(ctx, genomes)
             rows = engine.Rows.scan(ctx, p, t, 2, 100, 0, 50)
             want = rows.greedy(len(cand), ranks, up)
@@ -1083,9 +1081,10 @@ def test_round_loop_under_the_c_abi_equals_the_interpreters_loop(ctx, oracle, mo
     sid, un, st, en = rows.fetch()
     want = oracle.lazy_greedy(sid, un, st, en, len(cand), glen, None, None)
     rows.close(); t.close()
-    for rps in (1, 4):
-        assert solve(c2, p2, [0, len(genomes)], None, None, "rccl", rps) == want
-    if flat == "1":
+    if not partial:
+        for rps in (1, 4):
+            assert solve(c2, p2, [0, len(genomes)], None, None, "rccl", rps) == want
+    else:
         up = [0.9] * len(genomes)
         assert solve(c2, p2, [0, len(genomes)], None, up, "rccl", 4) == oracle.lazy_greedy(sid, un, st, en, len(cand), glen, up, None)
     p2.close()

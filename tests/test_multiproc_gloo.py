@@ -7,7 +7,7 @@ per-set gain and lost buffers, here over a real gloo process group).  Only the
 device is missing, so the shard object behind the loop is a NumPy stand-in with
 the interface of engine.Shard (count / claim_check / apply / picks /
 buffer_to_host / buffer_from_host); its per-rank arithmetic restates what the
-gs_* kernels do on their local rows (test infrastructure, like the oracle).
+sharded kernels do on their local rows (test infrastructure, like the oracle).
 The result must equal the oracle's sequential greedy, on every rank.
 """
 import os

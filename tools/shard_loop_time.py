@@ -1,6 +1,6 @@
 """Round loop of a sharded solve, timed (GPU box): S4's largest group cut into N universe ranges on ONE device, the
-interpreter's loop (parallel.sharded_solve: one library call per step, one read-back per round, exact exchange sizes)
-against catchhip_shard_solve with 1 / 2 / 4 / 8 rounds per read-back.   tools/shard_loop_time.py [N ...]"""
+interpreter's loop (parallel.sharded_solve: one library call per step, one read-back per round in apply -- a batch of
+one round) against catchhip_shard_solve with 1 / 2 / 4 / 8 rounds per read-back.   tools/shard_loop_time.py [N ...]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("CATCHHIP_TEST_HOOKS", "1")
