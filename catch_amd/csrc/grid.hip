@@ -248,8 +248,7 @@ extern "C" int catchhip_setcover_grid(catchhip_ctx *ctx, const catchhip_probes *
     for (int i = 0; i < 4; ++i) ctx->grid_counters[i] = 0;
     if (n_ext == 0) return 0;
     // test hook: a fresh scan at every e instead of the derivation (the two must agree)
-    const char *hook = chip_test_env("CATCHHIP_GRID_RESCAN");
-    const bool rescan = hook && atoi(hook) != 0;
+    const bool rescan = chip_test_env_int("CATCHHIP_GRID_RESCAN", 0) != 0;
     const bool timing = getenv("CATCHHIP_TIMING") != nullptr;
     using clk = std::chrono::steady_clock;
     double scan_ms = 0.0, derive_ms = 0.0, solve_ms = 0.0;

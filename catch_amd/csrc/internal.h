@@ -49,12 +49,19 @@ void chip_set_error(const char *fmt, ...);
 
 // Environment switches.  Four are part of the product and read with getenv(): CATCHHIP_TIMING (host-side wall
 // times on stderr), CATCHHIP_RCCL_PATH, CATCHHIP_POOL_SOFT_LIMIT_GB, CATCHHIP_GATHER_THREADS (README.md lists them
-// with the Python side's).  Everything else is a TEST HOOK -- it forces one of several exact code paths (the radix
-// row build, the fused solver on a large instance, striped tiles ...) so that tests/ and bench.py can
+// with the Python side's).  Everything else is a TEST HOOK -- it forces one of several exact code paths (the
+// sequential solver, the fused solver on a large instance, striped tiles ...) so that tests/ and bench.py can
 // compare them -- and is only honoured when CATCHHIP_TEST_HOOKS=1 is set (tests/conftest.py and bench.py do).
+// A hook exists only while a test, bench.py or a script under tools/ sets it (tests/test_host_logic.py checks), and
+// it is read at every decision it takes part in, never cached: a test may set it between two calls.
 static inline const char *chip_test_env(const char *name) {
     static const bool on = [] { const char *e = getenv("CATCHHIP_TEST_HOOKS"); return e && atoi(e) != 0; }();
     return on ? getenv(name) : nullptr;
+}
+// an integer hook: its value, `unset` when it is not set
+static inline long long chip_test_env_int(const char *name, long long unset) {
+    const char *e = chip_test_env(name);
+    return e ? atoll(e) : unset;
 }
 
 // Caching device allocator (core.hip): hipMalloc/hipFree cost tens of

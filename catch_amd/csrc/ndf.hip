@@ -181,7 +181,6 @@ ndf_node_round_kernel(u32 *__restrict__ status, u32 *__restrict__ flags, u32 n, 
 
 struct HammingFamily {       // ndf_near on the padded rows; the earlier tables' sampled positions lie k entries apart
     static constexpr bool WAVE_NEAR = false;     // (a comparison is a few XORs and popcounts: nothing to share)
-    static constexpr int wave_near_max = 0;
     static constexpr bool WAVE64 = false;
     struct Scratch { u32 unused; };
     __device__ __forceinline__ bool near_wave(u32, u32, Scratch &, u32) const { return false; }
@@ -256,12 +255,8 @@ __device__ __forceinline__ void ndf_mark(u32 *st2, u32 i, u32 v) {
 // took 118-126 and 82 vector registers = 4 and 5 wavefronts (the probe pass also held to 5 by 32 KB of LDS per workgroup).
 // Per S5 step with one worker under rocprofv3, round-0 pass / probe passes: as compiled 486 / 424 ms; 5 / 6 wavefronts 354 /
 // 325; 6 / 8: 273 / 284 (80 / 64 registers, ~100 bytes of spill); 8 / 8: 317 / 276.
-#ifndef NDF_LAZY_WAVES
 #define NDF_LAZY_WAVES 6
-#endif
-#ifndef NDF_PROBE_WAVES
 #define NDF_PROBE_WAVES 8
-#endif
 template <class Family, bool WAKE, bool DRAIN = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NDF_LAZY_WAVES)))
 ndf_lazy_kernel(Family fam, u32 n, const u64 *__restrict__ keys_all, const u32 *__restrict__ vals_all,
@@ -346,7 +341,7 @@ ndf_lazy_kernel(Family fam, u32 n, const u64 *__restrict__ keys_all, const u32 *
         bool is_near = false;
         unsigned long long wb = __ballot(want);
         if (!wb) return false;
-        if (!Family::WAVE_NEAR || __popcll(wb) >= fam.wave_near_max) {
+        if (!Family::WAVE_NEAR || __popcll(wb) >= NDF_WAVE_NEAR_MAX) {
             if (want) is_near = fam.near(tt, pi, pj);
         } else {
             while (wb) {
@@ -832,13 +827,12 @@ static int ndf_lazy_rounds(catchhip_ctx *ctx, u32 nn, size_t tn, DevBuf<u32> &co
     }
     u32 left = nn, nlist = probe_round0 ? nn : (u32)tn, nslot = nn;
     const bool trace = getenv("CATCHHIP_TIMING") && atoi(getenv("CATCHHIP_TIMING")) > 1;
-    const bool compacting = wake && !chip_test_env("CATCHHIP_NDF_NO_COMPACTION");
     DevBuf<u64> skeys2;
     DevBuf<u32> svals2, cflag, cpos, ctmp;
     auto t_round = std::chrono::steady_clock::now();
     for (u32 round = 0; left && round <= nn + 1; ++round) {
         // the tables without the dropped probes' slots: before the passes 2, 4, 8, 16, ... if a quarter or more would go
-        if (compacting && round >= 2 && (round & (round - 1)) == 0 && nslot > 4096) {
+        if (wake && round >= 2 && (round & (round - 1)) == 0 && nslot > 4096) {
             const size_t tcur = (size_t)ntables * nslot;
             TRY(cflag.reserve(tcur + 1));
             TRY(cpos.reserve(tcur + 1));
@@ -1060,7 +1054,7 @@ int chip_ndf_hamming_device(catchhip_ctx *ctx, const u8 *d_rows, i64 n, i32 L, c
                                e_j.p, count.p, cap, d_grp, pstride,
                                // (with two or three tables the look at the earlier tables' positions costs more than
                                // the comparisons it saves: S3, 2 tables, 15.1 -> 18.0 ms)
-                               (ntables < 4 || chip_test_env("CATCHHIP_MH_NO_DEDUPE")) ? 0 : t);
+                               ntables < 4 ? 0 : t);
             tm.launch(2 + 24);
         }
         HIP_TRY(hipGetLastError());
@@ -1458,7 +1452,6 @@ struct MinHashFamily {       // same signature in table t (the key only groups),
     const u32 *need_tab;     // by |A| + |B|: the smallest intersection for which 1 - m / (|A| + |B| - m) <= thres
     const unsigned long long *fp;     // MH_FPW words per probe
     const u32 *fp_excess;
-    int wave_near_max;       // lanes wanting a comparison from which every lane runs its own (NDF_WAVE_NEAR_MAX)
     const u32 *kc;           // [probe][kstride] 2-bit codes of the distinct k-mers, MH_KC_NONE-padded (row[0] == NONE: not packable)
     u32 kstride;
     const u32 *sig0T;        // [probe][tstride]: the first value of every table's signature
@@ -1833,17 +1826,9 @@ static int ndf_minhash_impl(catchhip_ctx *ctx, const u8 *bytes, const i64 *probe
                            (const u32 *)xs.p, (const u32 *)d_koff.p, nn, (const u64 *)d_ab.p, (int)k, (int)ntables, 0,
                            (int)ntables, grp, sig.p, keys_all.p, sig0T.p, tstride);
         tm.launch(1);
-        if (chip_test_env("CATCHHIP_MH_SORT_ONE_BY_ONE")) {      // (test hook: round 4's table-by-table sorts)
-            for (int t = 0; t < ntables; ++t) {
-                hipLaunchKernelGGL(mh_table_kernel, dim3(nb), dim3(256), 0, s, (const u64 *)(keys_all.p + (size_t)t * nn), nn,
-                                   keys.p, vals.p, 32);
-                TRY(chip_radix_sort_pairs(ctx, keys, keys_alt, vals, vals_alt, nn, 32));
-                HIP_TRY(hipMemcpyAsync(skeys.p + (size_t)t * nn, keys.p, sizeof(u64) * nn, hipMemcpyDeviceToDevice, s));
-                HIP_TRY(hipMemcpyAsync(svals.p + (size_t)t * nn, vals.p, sizeof(u32) * nn, hipMemcpyDeviceToDevice, s));
-                tm.launch(1 + 24 + 2);
-            }
-        } else {
-            // all tables' (key, probe) pairs side by side, sorted as segments by one set of launches
+        {
+            // all tables' (key, probe) pairs side by side, sorted as segments by one set of launches (in a scope of
+            // its own: the sort's second buffers go back to the pool before the rounds)
             DevBuf<u64> skeys_alt;
             DevBuf<u32> svals_alt;
             hipLaunchKernelGGL(mh_tables_kernel, dim3((unsigned)div_up((i64)tn, 256)), dim3(256), 0, s, (const u64 *)keys_all.p, nn,
@@ -1854,7 +1839,6 @@ static int ndf_minhash_impl(catchhip_ctx *ctx, const u8 *bytes, const i64 *probe
         lap("signatures + sorts", t_lap);
         MinHashFamily fam{(const u32 *)d_koff.p, (const u32 *)nuniq.p, (const u64 *)id_hi.p, (const u64 *)id_lo.p, (const u32 *)sig.p,
                           (int)k, nn, grp, (const u32 *)need_tab.p, (const unsigned long long *)fp.p, (const u32 *)fp_excess.p,
-                          chip_test_env("CATCHHIP_NDF_WAVE_NEAR_MAX") ? atoi(chip_test_env("CATCHHIP_NDF_WAVE_NEAR_MAX")) : NDF_WAVE_NEAR_MAX,
                           (const u32 *)kc.p, kstride, (const u32 *)sig0T.p, tstride};
         const int rc = ndf_lazy_rounds(ctx, nn, tn, count, status, flags, pairs, tm, keep,
                                        [&](bool wake, const u32 *list, u32 nlist, u32 *next, u32 *next_count, u32 *left_tables, const u32 *inv, u32 nslot, NdfQueue Q, int mode) {
@@ -1900,7 +1884,7 @@ static int ndf_minhash_impl(catchhip_ctx *ctx, const u8 *bytes, const i64 *probe
                                (const u32 *)(sig.p + (size_t)tc * nn * k), (int)k, (const u32 *)need_tab.p,
                                (const unsigned long long *)fp.p, (const u32 *)fp_excess.p, nn,
                                (const u64 *)keys.p, (const u32 *)vals.p, grp, e_i.p, e_j.p, count.p, cap,
-                               (const u32 *)sig.p, chip_test_env("CATCHHIP_MH_NO_DEDUPE") ? 0 : tc);
+                               (const u32 *)sig.p, tc);
             tm.launch(2 + 24);
         }
         HIP_TRY(hipGetLastError());

@@ -85,7 +85,7 @@ scan1_kernel(const u32 *in, u32 *__restrict__ out, u32 n, u32 *__restrict__ tota
              const u32 *__restrict__ aux, u32 *__restrict__ auxmax_out) {
     __shared__ u32 s_part[16], s_mx[16], s_amx[16];
     const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // any multiple of 64 threads up to 1024 (CATCHHIP_SCAN1_THREADS; measured on
+    // any multiple of 64 threads up to 1024 (launched with 1024; measured on
     // S2 with two groups in flight: 256 or 512 threads need more dependent load
     // batches and cost 10 us per group more than 1024)
     const u32 nthreads = blockDim.x, nwaves = nthreads >> 6;

@@ -1317,7 +1317,7 @@ static int seed_table_lookup_async(catchhip_ctx *ctx, const catchhip_probes *P, 
     TRY(S.sseq.reserve(S.scap));
     if (!res) { TRY(S.dummy.reserve(8)); res = S.dummy.p; }
     // presence bits: for the pigeonhole tables of a whole-genome scan (most positions miss); 4 per slot
-    const bool pres = P->pigeonhole && capacity >= (1u << 16) && capacity <= (1u << 29) && !chip_test_env("CATCHHIP_SEED_NO_PRESENCE");
+    const bool pres = P->pigeonhole && capacity >= (1u << 16) && capacity <= (1u << 29);
     const u32 pwords = pres ? capacity / 8 : 0;      // 4 * capacity bits
     if (pres) TRY(S.present.reserve(pwords));
     SeedTable t = {S.slot.p, S.cnt.p, S.ents.p, capacity - 1, filt ? (const uint4 *)S.sib.p : nullptr,
@@ -1399,8 +1399,7 @@ static int run_general(catchhip_ctx *ctx, const catchhip_probes *P, const catchh
     // packed image: their anchors go into the hash table of the seed scan and
     // every target position does one look-up (the extension below re-checks the
     // k-mer on the bytes).  Anything else is joined through a sort of byte hashes.
-    const bool table = P->dna5 && T->dna5 && P->L > 0 && P->L <= 256 && P->pwords >= 1 && P->k <= P->L &&
-                       !chip_test_env("CATCHHIP_GENERAL_SORTJOIN");
+    const bool table = P->dna5 && T->dna5 && P->L > 0 && P->L <= 256 && P->pwords >= 1 && P->k <= P->L;
     SeedRun S;
     DevBuf<u64> keys, keys_alt;
     DevBuf<u32> vals, vals_alt, sa, sb, scount;
@@ -1460,7 +1459,7 @@ static int run_general(catchhip_ctx *ctx, const catchhip_probes *P, const catchh
     }
     HitBuf ob = {H.a.p, H.b.p, H.c.p, H.count.p, nseeds, H.want_seed ? H.d.p : nullptr,
                  H.want_seed ? H.e.p : nullptr};
-    extend_planes_fn planes = table && !chip_test_env("CATCHHIP_EXTEND_BYTES") ? pick_extend_planes((int)P->pwords) : nullptr;
+    extend_planes_fn planes = table ? pick_extend_planes((int)P->pwords) : nullptr;
     DevBuf<u32> cut;
     const u32 cut_cap = 1u << 22;
     if (planes) {
@@ -1537,8 +1536,7 @@ static int bucket_scan(catchhip_ctx *ctx, BucketBuild &B, const u32 *in, u32 *ou
                        const u32 *aux, u32 *auxmax_out, PhaseTimer &tm) {
     hipStream_t s = ctx->stream;
     if (n <= 16384) {
-        static const int s1t = chip_test_env("CATCHHIP_SCAN1_THREADS") ? atoi(chip_test_env("CATCHHIP_SCAN1_THREADS")) : 1024;
-        hipLaunchKernelGGL(scan1_kernel, dim3(1), dim3(s1t), 0, s, in, out, n, total_out, (u32 *)nullptr, aux,
+        hipLaunchKernelGGL(scan1_kernel, dim3(1), dim3(1024), 0, s, in, out, n, total_out, (u32 *)nullptr, aux,
                            auxmax_out);
         tm.launch(1);
         return 0;
@@ -1559,11 +1557,10 @@ static int bucket_scan(catchhip_ctx *ctx, BucketBuild &B, const u32 *in, u32 *ou
 // B.cap, when nrec_dev is given).
 // grouped: the producer (run_join) has scanned the bucket sizes and written its records at their places in B.S.
 static int bucket_finish_async(catchhip_ctx *ctx, BucketBuild &B, u32 nrec, const u32 *nrec_dev, bool want_sum,
-                               bool merge, PhaseTimer &tm, bool dedupe = false, bool grouped = false,
+                               PhaseTimer &tm, bool dedupe = false, bool grouped = false,
                                const u32 *run_cnt = nullptr, int run_stride = 0, int nruns = 0) {
     hipStream_t s = ctx->stream;
     if (!grouped) TRY(bucket_scan(ctx, B, B.bcnt.p, B.bstart.p, B.nb, B.res.p + 2, nullptr, nullptr, tm));
-    if (!merge) return 0;   // radix build: only the bucket offsets are needed
     if (nrec && !grouped)
         hipLaunchKernelGGL(bucket_scatter_kernel, dim3((unsigned)div_up((i64)nrec, 256)), dim3(256), 0, s,
                            (const uint4 *)B.rec.p, (const u32 *)B.rank.p, nrec, nrec_dev, (const u32 *)B.bstart.p,
@@ -1658,12 +1655,11 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
     TRY(S.ents.reserve(nent));
     TRY(S.slot_of.reserve(nent));
     TRY(S.ctr.reserve(4));
-    const bool pres = capacity >= (1u << 16) && capacity <= (1u << 29) && !chip_test_env("CATCHHIP_SEED_NO_PRESENCE");
+    const bool pres = capacity >= (1u << 16) && capacity <= (1u << 29);
     // One presence bit per slot (4 MB for the 32 M slots of S4's largest group: mostly L2 hits; the seed-list scan's
     // 4 bits per slot are 16 MB: every probe a trip to the memory-side cache).  Measured on S4, whole scan phase:
     // 4 bits 33.8 ms, 1 bit 30.5, half a bit 30.4, a quarter 30.8 (more false positives go on to the slot array).
-    static const int pshift = chip_test_env("CATCHHIP_PRESENCE_SHIFT") ? atoi(chip_test_env("CATCHHIP_PRESENCE_SHIFT")) : 2;
-    const u32 pbits = pres ? std::max<u32>((4u * capacity) >> pshift, 1u << 16) : 0;
+    const u32 pbits = pres ? std::max<u32>(capacity, 1u << 16) : 0;
     const u32 pwords = pbits / 32;
     if (pres) TRY(S.present.reserve(pwords));
     SeedTable t = {S.slot.p, S.cnt.p, S.ents.p, capacity - 1, nullptr, pres ? S.present.p : (u32 *)nullptr,
@@ -1711,11 +1707,10 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
     A.bucket_of = sink.bucket_of; A.seq_genome = sink.seq_genome; A.ext = sink.ext;
     A.probe_group = sink.probe_group; A.seq_group = sink.seq_group;
     A.giant = J.giant.p; A.giant_n = J.giant_n.p; A.giant_cap = KJ_GIANT_CAP;
-    A.giant_pairs = chip_test_env("CATCHHIP_JOIN_GIANT_PAIRS") ? (u32)atoi(chip_test_env("CATCHHIP_JOIN_GIANT_PAIRS")) : KJ_GIANT_PAIRS;
     // hit masks of the counting pass for the writing pass (scan_join.inc): 6 words per hit position hold S4's
     // (2 per position there); a run that finds the store full is simply verified again
     A.masks = nullptr; A.mbase = A.gmbase = nullptr; A.mcursor = J.pairs.p + 128; A.mask_cap = 0;   // (zeroed with the statistics)
-    if (J.nhit && !chip_test_env("CATCHHIP_JOIN_NO_MASKS")) {
+    if (J.nhit) {
         const size_t mcap = (size_t)std::min<u64>((u64)1 << 26, std::max<u64>((u64)1 << 20, 6ull * J.nhit));
         TRY(J.masks.reserve(mcap));
         TRY(J.mbase.reserve(J.nhit));
@@ -1878,7 +1873,7 @@ static int scan_and_group(catchhip_ctx *ctx, const catchhip_probes *P, const cat
                           bool dedupe = false, bool want_first = false) {
     const bool seed_ok = seed_path_ok(P, T, mismatches, lcf_thres, island);
     const bool tiled_ok = fast_path_ok(P, T, mismatches, lcf_thres, island);
-    const bool want_tiled = mode == CATCHHIP_SCAN_FAST || (mode == CATCHHIP_SCAN_AUTO && chip_test_env("CATCHHIP_SCAN_TILED"));
+    const bool want_tiled = mode == CATCHHIP_SCAN_FAST;
     const bool use_fast = tiled_ok && want_tiled && !(want_first && mode == CATCHHIP_SCAN_AUTO);
     if (use_fast && want_first) {
         chip_set_error("cover_scan_first_seen: the tiled scan does not know which anchor seeded a hit");
@@ -1887,7 +1882,6 @@ static int scan_and_group(catchhip_ctx *ctx, const catchhip_probes *P, const cat
     O.from_seeds = false;
     const bool use_seed = seed_ok && !use_fast && mode != CATCHHIP_SCAN_GENERAL && mode != CATCHHIP_SCAN_FAST;
     const u32 nb = by_sequence ? (u32)P->nprobes : (u32)P->nbuckets;
-    const bool force_radix = chip_test_env("CATCHHIP_ROWS_RADIX") != nullptr && !dedupe;
     HitSink sink;
     sink.bucket_of = by_sequence || P->bucket_identity ? nullptr : P->bucket_of.p;   // (null: the probe index itself)
     sink.seq_genome = by_sequence ? nullptr : T->seq_genome.p;
@@ -1915,8 +1909,8 @@ static int scan_and_group(catchhip_ctx *ctx, const catchhip_probes *P, const cat
             O.nrec = 0; O.nrec_dev = nullptr;
             tr.restart();
             // (buckets = probes: every bucket is its probe's anchor runs side by side, each in position order)
-            const bool runs = sink.bucket_of == nullptr && O.J.A.ntab <= BK_RUNS_MAX && !chip_test_env("CATCHHIP_MERGE_NO_RUNS");
-            TRY(bucket_finish_async(ctx, O.B, 0, nullptr, true, !force_radix, tr, dedupe, true,
+            const bool runs = sink.bucket_of == nullptr && O.J.A.ntab <= BK_RUNS_MAX;
+            TRY(bucket_finish_async(ctx, O.B, 0, nullptr, true, tr, dedupe, true,
                                     runs ? (const u32 *)O.J.ecnt.p : (const u32 *)nullptr, O.J.A.nanch, O.J.A.ntab));
             tr.stop();
             HIP_TRY(hipGetLastError());
@@ -1928,13 +1922,14 @@ static int scan_and_group(catchhip_ctx *ctx, const catchhip_probes *P, const cat
     } else if (use_seed) {
         O.from_seeds = true;
         O.S.scap = seed_capacity(P, T);
-        if (const char *e = chip_test_env("CATCHHIP_SEED_CAP")) O.S.scap = (u32)std::max(1, atoi(e));   // tests: force the retry
+        const long long forced_cap = chip_test_env_int("CATCHHIP_SEED_CAP", -1);     // tests: force the retry
+        if (forced_cap >= 0) O.S.scap = (u32)std::max<long long>(1, forced_cap);
         for (int attempt = 0;; ++attempt) {
             const auto dbg0 = std::chrono::steady_clock::now();
             TRY(bucket_prepare(O.B, nb, O.S.scap, true));
             sink.rec = O.B.rec.p; sink.rank = O.B.rank.p; sink.bcnt = O.B.bcnt.p;
             // (the first-discovery keys pair record d with seed d: not compact then)
-            O.B.compact = !want_first && !chip_test_env("CATCHHIP_HITS_SPARSE");
+            O.B.compact = !want_first;
             sink.wcnt = O.B.compact ? O.B.wcnt.p : nullptr;
             ts.restart();
             TRY(run_seed_async(ctx, P, T, mismatches, O.S, sink, nb, O.B.res.p, ts));
@@ -1944,7 +1939,7 @@ static int scan_and_group(catchhip_ctx *ctx, const catchhip_probes *P, const cat
             ts.stop();
             O.nrec = O.S.scap; O.nrec_dev = O.S.ctr.p + 1;
             tr.restart();
-            TRY(bucket_finish_async(ctx, O.B, O.nrec, O.nrec_dev, true, !force_radix, tr, dedupe));
+            TRY(bucket_finish_async(ctx, O.B, O.nrec, O.nrec_dev, true, tr, dedupe));
             tr.stop();
             HIP_TRY(hipGetLastError());
             u32 *h = (u32 *)ctx->h_pin;
@@ -1984,7 +1979,7 @@ static int scan_and_group(catchhip_ctx *ctx, const catchhip_probes *P, const cat
                                (u32)(P->L > 0 ? P->L : 0), H.n, (const u32 *)T->seq_off.p, (u32)T->nseq, sink);
             tr.launch();
         }
-        TRY(bucket_finish_async(ctx, O.B, O.nrec, O.nrec_dev, true, !force_radix, tr, dedupe));
+        TRY(bucket_finish_async(ctx, O.B, O.nrec, O.nrec_dev, true, tr, dedupe));
         tr.stop();
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(ctx->h_pin, O.B.res.p, 8 * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
@@ -1992,7 +1987,7 @@ static int scan_and_group(catchhip_ctx *ctx, const catchhip_probes *P, const cat
     }
     ts.finish();
     const volatile u32 *h = (const volatile u32 *)ctx->h_pin;
-    O.overflow = h[1] != 0 || force_radix;
+    O.overflow = h[1] != 0;
     O.nhits = h[2]; O.maxbucket = h[3]; O.nrows = h[4]; O.lmax = h[5];
     ctx->counters[0] = O.nhits;
     tr.finish();
@@ -2013,8 +2008,8 @@ int chip_cover_scan_nosync(catchhip_ctx *ctx, const catchhip_probes *P, const ca
     *out = nullptr;
     if (P->nprobes == 0 || T->total == 0) return 1;
     if (!seed_path_ok(P, T, mismatches, lcf_thres, island)) return 1;
-    if (!(mode == CATCHHIP_SCAN_SEED || (mode == CATCHHIP_SCAN_AUTO && !chip_test_env("CATCHHIP_SCAN_TILED")))) return 1;
-    if (chip_test_env("CATCHHIP_ROWS_RADIX") || chip_test_env("CATCHHIP_SEED_CAP") || chip_test_env("CATCHHIP_FUSED_SYNC")) return 1;
+    if (!(mode == CATCHHIP_SCAN_SEED || mode == CATCHHIP_SCAN_AUTO)) return 1;
+    if (chip_test_env("CATCHHIP_SEED_CAP")) return 1;
     const i64 scap64 = seed_capacity(P, T);
     if (scap64 > ((i64)1 << 26)) return 1;   // keep the capacity-sized row arrays small
     HIP_TRY(hipSetDevice(ctx->device));
@@ -2054,7 +2049,7 @@ int chip_cover_scan_nosync(catchhip_ctx *ctx, const catchhip_probes *P, const ca
         if ((rc = run_seed_async(ctx, P, T, mismatches, O.S, sink, nb, O.B.res.p, ts))) break;
         ts.stop();
         PhaseTimer tr(ctx, PHASE_ROWS);
-        if ((rc = bucket_finish_async(ctx, O.B, O.S.scap, O.S.ctr.p + 1, false, true, tr))) break;
+        if ((rc = bucket_finish_async(ctx, O.B, O.S.scap, O.S.ctr.p + 1, false, tr))) break;
         hipLaunchKernelGGL(rows_emit_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream,
                            (const u32 *)O.B.rstart.p, O.B.nb, (const u32 *)O.B.bstart.p,
                            P->bucket_identity ? (const i32 *)nullptr : (const i32 *)P->bucket_set.p,

@@ -144,7 +144,6 @@ struct JoinArgs {
     const u32 *bucket_of; const i32 *seq_genome; u32 ext;
     const i32 *probe_group; const i32 *seq_group;
     uint4 *giant; u32 *giant_n; u32 giant_cap;   // tasks {first hit, windows, first entry, entries}
-    u32 giant_pairs;                              // a run of more pairs is cut into tasks (KJ_GIANT_PAIRS)
     // hit masks: the counting pass keeps, per 64-entry block and 64-window chunk of a wave-wide run, one 64-bit
     // ballot per entry (which windows it hit); the writing pass replays them instead of testing every pair again.
     // mbase[first hit of the run] / gmbase[task] = where the run's masks start (KJ_NOMASK: the store was full,
@@ -517,9 +516,9 @@ kj_verify_kernel(JoinArgs A) {
         bb &= bb - 1;
         const u32 bi = (u32)__builtin_amdgcn_readlane((int)i, src), bW = (u32)__builtin_amdgcn_readlane((int)W, src);
         const u32 bf = (u32)__builtin_amdgcn_readlane((int)first, src), bQ = (u32)__builtin_amdgcn_readlane((int)Q, src);
-        if ((unsigned long long)bW * bQ > A.giant_pairs) {
+        if ((unsigned long long)bW * bQ > KJ_GIANT_PAIRS) {
             if (!WRITE) {   // (the writing pass finds the tasks where the counting pass left them)
-                const u32 qsub = max(1u, A.giant_pairs / bW), nt = (bQ + qsub - 1u) / qsub;
+                const u32 qsub = max(1u, KJ_GIANT_PAIRS / bW), nt = (bQ + qsub - 1u) / qsub;
                 u32 g0 = 0;
                 if (lane == 0) g0 = atomicAdd(A.giant_n, nt);
                 g0 = (u32)__builtin_amdgcn_readfirstlane((int)g0);

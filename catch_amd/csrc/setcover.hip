@@ -51,7 +51,6 @@ struct GreedyState {
     u32 smax;      // largest (set, universe) element count
     u32 fr_claim[2];   // frontier solver: some set of the current rank claimed, by round parity
     u32 fr_live[2];    // frontier solver: sizes of the live-set lists (large instances), by round parity
-    unsigned long long prof[8];  // shader-clock ticks per phase (thread 0)
     unsigned long long n_wrows, n_recount, n_words;  // work counters
     u32 need_live, ticket;   // row-parallel solver, partial coverage: universes still in need (being counted) / workgroups done
     u32 nwon;                // row-parallel solver, full coverage: npicks when this round began -- the sets accepted in it are picks[nwon .. npicks)
@@ -66,11 +65,6 @@ struct GreedyState {
 #define LD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define DRAIN() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
-#ifdef CATCHHIP_PROFILE   // per-phase shader-clock accounting (make CXXFLAGS+=-DCATCHHIP_PROFILE)
-#define PROF(i) do { if (tid == 0) { unsigned long long t_ = __builtin_readcyclecounter(); st->prof[i] += t_ - t_prev; t_prev = t_; } } while (0)
-#else
-#define PROF(i) do { (void)t_prev; } while (0)
-#endif
 
 __device__ __forceinline__ u32 range_popcount(const u64 *__restrict__ bm, u32 s, u32 e) {
     u32 w0 = s >> 6, w1 = (e - 1) >> 6;
@@ -412,7 +406,6 @@ greedy_wg_kernel(GreedyArgs a) {
     u32 my_rank = 0xffffffffu;                                     // rank the chunk scan is valid for
     u32 cur_rank = st->cur_rank, stop = 0;                         // uniform across the workgroup
     const u32 nrank = st->nrank;
-    unsigned long long t_prev = __builtin_readcyclecounter();
 
     for (;;) {
         // ---- A: arg-max.  Only chunks whose gains changed are re-scanned ----
@@ -450,7 +443,6 @@ greedy_wg_kernel(GreedyArgs a) {
         // global access between the scan and the apply phase
         unsigned long long key = wave_max_u64(lane < GW_WAVES ? s_red[lane] : 0ull);
         key = __shfl(key, 0, WAVE);
-        PROF(0);
         if ((key >> ID_BITS) == 0) {
             // no set of this rank covers anything still needed: next rank
             // (set_cover.py:522-526); chunks re-scan because my_rank != cur_rank
@@ -513,7 +505,6 @@ greedy_wg_kernel(GreedyArgs a) {
             }
         }
         __syncthreads();
-        PROF(1);
 
         // ---- C1: remaining need per touched universe (single writer) ---------
         // (wave 0 only, so that its dependent loads overlap the other waves' C2 chain)
@@ -614,7 +605,6 @@ greedy_wg_kernel(GreedyArgs a) {
         }
         DRAIN();
         __syncthreads();
-        PROF(2);
 
         // ---- D: universes with partial cover: exact min(left, count) ---------
         if (s_ndirty | s_nbind) {
@@ -638,7 +628,6 @@ greedy_wg_kernel(GreedyArgs a) {
             DRAIN();
             __syncthreads();
         }
-        PROF(3);
         if (s_need == 0) break;
     }
     atomicAdd(&s_nrecount, (unsigned long long)cnt_recount);
@@ -820,7 +809,7 @@ static int greedy_frontier(catchhip_ctx *ctx, const catchhip_rows *R, u32 nsets,
                  o_setptr = take(4 * ((size_t)nsets + 1)), o_frow = take(8 * (size_t)nrows),
                  o_flag = take(nrows), o_picks = take(4 * (size_t)nsets), o_keys = take(8 * (size_t)nsets);
     // live-set lists only where walking every set each round would dominate
-    const bool use_list = nsets > 65536 && !chip_test_env("CATCHHIP_GF_NOLIST");
+    const bool use_list = nsets > 65536;
     const size_t o_live0 = use_list ? take(4 * (size_t)nsets) : 0, o_live1 = use_list ? take(4 * (size_t)nsets) : 0;
     DevBuf<u8> arena;
     TRY(arena.alloc(off));
@@ -1012,7 +1001,8 @@ extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *
 
     // every universe fully covered: batched rounds (many independent picks per
     // round); otherwise one pick per iteration
-    bool batched = !chip_test_env("CATCHHIP_GREEDY_SEQUENTIAL");
+    const bool sequential = chip_test_env("CATCHHIP_GREEDY_SEQUENTIAL") != nullptr;
+    bool batched = !sequential;
     if (universe_p)
         for (u32 u = 0; u < nuniv && batched; ++u) batched = universe_p[u] == 1.0;
 
@@ -1025,7 +1015,7 @@ extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *
     // 1.68 (11.1 vs 8.0); 3.4 M (configs[2]): 5.96 vs 3.12 (20.1 vs 13.5 -- the fused family also reads back every
     // round).  So: 2^18 rows.  (Smaller instances never get here through the fused filter: below ~11 Mbases of
     // targets it queues scan and solve without a synchronisation, chip_greedy_deferred.)
-    const i64 flat_min_rows = chip_test_env("CATCHHIP_FLAT_MIN_ROWS") ? atoll(chip_test_env("CATCHHIP_FLAT_MIN_ROWS")) : (i64)1 << 18;
+    const i64 flat_min_rows = chip_test_env_int("CATCHHIP_FLAT_MIN_ROWS", (i64)1 << 18);
     if (batched && R->lmax <= 257 && (i64)nrows >= flat_min_rows && nsets <= GR_MAX_SETS)
         return greedy_flat(ctx, R, nsets, ranks ? h_rank.data() : nullptr, nrank, out_ids, n_out);
     if (batched) return greedy_frontier(ctx, R, nsets, ranks ? h_rank.data() : nullptr, nrank, out_ids, n_out, &no_retry);
@@ -1033,8 +1023,7 @@ extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *
     // row-parallel kernels with the universe test (setcover_flat.inc, "PARTIAL") whatever the size --
     // the one-workgroup solvers below take 3.9 ms per pick on S4's largest group (54.6 s for S4 under
     // -c 0.9 against 0.17 s under -c 1.0)
-    if (universe_p && R->lmax <= 257 && nsets <= GR_MAX_SETS && !chip_test_env("CATCHHIP_GREEDY_SEQUENTIAL") &&
-        !chip_test_env("CATCHHIP_PARTIAL_SEQUENTIAL") && (i64)nrows >= (chip_test_env("CATCHHIP_PARTIAL_MIN_ROWS") ? atoll(chip_test_env("CATCHHIP_PARTIAL_MIN_ROWS")) : 0))
+    if (universe_p && R->lmax <= 257 && nsets <= GR_MAX_SETS && !sequential && !chip_test_env("CATCHHIP_PARTIAL_SEQUENTIAL"))
         return greedy_flat(ctx, R, nsets, ranks ? h_rank.data() : nullptr, nrank, out_ids, n_out, universe_p);
 
     DevBuf<u32> set_ptr, flag, idx, tmp, seg_univ, seg_set, row_seg, set_seg_ptr, usize, can, left, rank,
@@ -1150,14 +1139,6 @@ extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *
     ctx->phase_launches[PHASE_GREEDY] = h_st.iters;  // greedy iterations inside the persistent launch
     ctx->counters[2] = h_st.iters; ctx->counters[3] = h_st.npicks; ctx->counters[4] = (i64)h_st.n_wrows;
     ctx->counters[5] = (i64)h_st.n_recount; ctx->counters[6] = (i64)h_st.n_words;
-#ifdef CATCHHIP_PROFILE
-    if (chip_test_env("CATCHHIP_PROF")) {
-        fprintf(stderr, "[catchhip] greedy wg: iters=%u picks=%u ms=%.3f ticks/iter:", h_st.iters, h_st.npicks,
-                ctx->phase_ms[PHASE_GREEDY]);
-        for (int i = 0; i < 4; ++i) fprintf(stderr, " p%d=%.0f", i, (double)h_st.prof[i] / (h_st.iters ? h_st.iters : 1));
-        fprintf(stderr, "\n");
-    }
-#endif
     if (h_st.done == 2) {
         chip_set_error("setcover: ranks exhausted while coverage is still required");
         return CATCHHIP_ERANK;

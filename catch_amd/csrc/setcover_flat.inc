@@ -50,29 +50,12 @@
 //
 // Same preconditions as the fused kernels: every universe fully covered
 // (p == 1), rows of at most 257 bases (<= 5 bitmap words).
-#ifndef GR_THREADS
 #define GR_THREADS 512                   // (a step of 2,048 rows per tile-counter atomic; rounds per S4 step: 512 x 4 rows per lane 64.7 ms,
                                          //  256 x 4: 67.6, 768 x 4: 67.8, 512 x 2: 69.2, 256 x 8: 72.8, 1024 x 4: 75.6 -- apply at 256 throughout;
                                          //  again with the 8-byte records of round 4: 512 x 4 50.9, 256 x 6 54.2, 384 x 4 59.5, 640 x 4 61.2,
                                          //  512 x 6 62.4, 512 x 8 66.8)
-#endif
 #define GR_WAVES (GR_THREADS / 64)
-// The record streams are read once and written once per launch: marked non-temporal they do not push the gathered bitmap /
-// owner lines (which ARE reused, by the neighbouring sets of the same step) out of the 32-KB vector L1 -- four workgroup
-// steps of 16 KB of records are in flight per CU.  (Measured, round 6: 18.19 vs 18.06 ms in the rounds of S4's largest group -- no difference; GR_NT=1 builds it.)
-#ifndef GR_NT
-#define GR_NT 0
-#endif
-#if GR_NT
-#define GR_STREAM_LOAD(p) __builtin_nontemporal_load(p)
-#define GR_STREAM_STORE(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define GR_STREAM_LOAD(p) (*(p))
-#define GR_STREAM_STORE(p, v) (*(p) = (v))
-#endif
-#ifndef GR_UNR
 #define GR_UNR 4                         // 64-row chunks a wavefront has in flight
-#endif
 #define GR_WCH (64 * GR_UNR)             // rows per wavefront step
 #define GR_BCH (GR_WAVES * GR_WCH)       // rows per workgroup step
 
@@ -92,21 +75,6 @@
 #define GR_KEY_NOFLAGS(k) ((k) & ~(0x1full << GR_SET_BITS))
 #define GR_KEY_MAKE(loc, len, flags, set) (((unsigned long long)(loc) << (GR_SET_BITS + 14)) | ((unsigned long long)(len) << (GR_SET_BITS + 5)) | \
                                            ((unsigned long long)(flags) << GR_SET_BITS) | (unsigned long long)(set))
-
-// partial coverage: acceptance thresholds per universe, one per LEVEL of what the candidate still covers there -- up to
-// 8, 16, ... elements, the last level up to smax.  GR_UT_LEVELS = 1 is the rule of rounds 3-5 (one threshold, bound
-// smax).  Measured in round 6 with 6 levels on S4 at -c 0.9 (every group's picks still the oracle's, in order): 1,316
-// -> 1,205 rounds, but gr_usel computes six thresholds instead of one and the solves take 450 instead of 379 ms --
-// what keeps the plateau's rounds at 10-25 picks is not the size of the bound.  So: 1.
-#ifndef GR_UT_LEVELS
-#define GR_UT_LEVELS 1
-#endif
-__device__ __forceinline__ u32 gr_ut_level(u32 c) {
-    u32 j = 0;
-    while (j + 1 < GR_UT_LEVELS && c > (8u << j)) ++j;
-    return j;
-}
-__device__ __forceinline__ u32 gr_ut_bound(u32 level, u32 smax) { return level + 1 >= GR_UT_LEVELS ? smax : min(8u << level, smax); }
 
 struct FlatArgs {
     unsigned long long *bm;
@@ -165,7 +133,6 @@ struct FlatArgs {
     u32 count0_done;                // acc[0] was filled from the row build's per-set totals: round 0 has no count launch
     u32 pretested;                  // partial coverage, sharded: the universe test of the candidates ran in gr_verdict_kernel
                                     // on every rank and failures travelled with the lost marks -- gr_apply accepts what is left
-    u32 bm_in_round0;               // the universe bitmap is OR-ed together by round 0's count launch (no gr_bitmap pass)
     unsigned long long inv;         // ~0: bm holds the COVERED positions (starts all zero: nothing to build), 0: the uncovered ones
 };
 
@@ -183,33 +150,16 @@ __device__ __forceinline__ u32 wave_incl_scan_dpp(u32 v) {
 
 // inclusive sum over runs of equal keys in adjacent lanes; *tail = this lane ends its run.  Round 6: the wave's plain
 // prefix sum by DPP moves minus its value just before the run's first lane -- one LDS permute instead of six (the six-step
-// segmented scan through ds_bpermute was ~30 of the count launch's 190 VALU instructions per 64 rows).  GR_SEGSUM_BPERMUTE=1
-// builds the old form.
-#ifndef GR_SEGSUM_BPERMUTE
-#define GR_SEGSUM_BPERMUTE 0
-#endif
+// segmented scan through ds_bpermute was ~30 of the count launch's 190 VALU instructions per 64 rows).
 __device__ __forceinline__ u32 wave_segsum(u32 v, u32 key, bool *tail) {
     const u32 lane = threadIdx.x & 63;
-#if GR_SEGSUM_BPERMUTE
-    const u32 kprev = __shfl_up(key, 1, WAVE);
-#else
     const u32 kprev = (u32)__builtin_amdgcn_update_dpp((int)key, (int)key, 0x138, 0xf, 0xf, false);   // wave_shr:1 (lane 0: its own key, unused)
-#endif
     const unsigned long long heads = __ballot(lane == 0 || kprev != key);
     // first lane of this lane's run: highest head at or below it
     const u32 start = 63u - (u32)__clzll(heads & (~0ull >> (63 - lane)));
     *tail = lane == 63 || ((heads >> (lane + 1)) & 1ull);
-#if GR_SEGSUM_BPERMUTE
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 ov = __shfl_up(v, d, WAVE);
-        if (lane >= start + (u32)d) v += ov;
-    }
-    return v;
-#else
     const u32 incl = wave_incl_scan_dpp(v);
     return incl - (u32)__shfl((int)(incl - v), (int)start, WAVE);      // minus the sum of the lanes before the run
-#endif
 }
 
 // global start of a record of tile t (contiguous tiles: t << shift; striped: 4-kbase stripes dealt round robin)
@@ -227,7 +177,7 @@ __device__ __forceinline__ void load_records(const FlatArgs &a, u32 buf, u32 bba
 #pragma unroll
     for (int u = 0; u < GR_UNR; ++u) {
         const u32 r = wbase + u * 64;
-        k[u] = r < end ? GR_STREAM_LOAD(&a.key[buf][r]) : 0ull;
+        k[u] = r < end ? a.key[buf][r] : 0ull;
         x[u] = gr_start(GR_KEY_LOC(k[u]), t, a.tile_shift);
     }
 }
@@ -337,18 +287,6 @@ gr_count_kernel(FlatArgs a, u32 round) {
                     // nothing is covered yet and the universe is the union of the rows
                     cnt = len;
                     nf[u] = fl;
-                    if (!PARTIAL && a.bm_in_round0) {
-                        // ... which this launch builds on the way (its counts do not need it; the tile's words
-                        // are L2-resident; deep coverage makes most ORs redundant: look first)
-                        const u32 w1 = (e - 1) >> 6;
-                        const u64 m0 = ~0ull << (x[u] & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
-                        for (u32 w = w0; w <= w1; ++w) {
-                            u64 m = ~0ull;
-                            if (w == w0) m &= m0;
-                            if (w == w1) m &= m1;
-                            if ((a.bm[w] & m) != m) atomicOr(&a.bm[w], m);
-                        }
-                    }
                 } else {
                     if (chg) {   // SURVEY 8(d)'s E_dirty: rows that hold a word the last picks changed, and their words
                         const u32x2 q = *(const u32x2 *)(chg + (w0 >> 5));
@@ -418,7 +356,7 @@ gr_count_kernel(FlatArgs a, u32 round) {
         for (int u = 0; u < GR_UNR; ++u) {
             if (nf[u]) {
                 const u32 pos = o + (u32)__popcll(alive[u] & ((1ull << lane) - 1ull));
-                GR_STREAM_STORE(&a.key[ob][pos], GR_KEY_NOFLAGS(k[u]) | ((unsigned long long)nf[u] << GR_SET_BITS));
+                a.key[ob][pos] = GR_KEY_NOFLAGS(k[u]) | ((unsigned long long)nf[u] << GR_SET_BITS);
                 if (PARTIAL) a.uni[ob][pos] = uv[u];
             }
             o += (u32)__popcll(alive[u]);
@@ -502,7 +440,7 @@ gr_claim_kernel(FlatArgs a, u32 round) {
         // Three passes over the step's rows (round 6).  The raises RETURN the word's previous owner, and a lane that
         // looks at one before it issues the next waits a full round trip to the L2 per raise: up to 20 of them in a
         // row per wavefront step (4 chunks x 5 words), 1.3 of the 2.5 ms of the first claim launch on S4's largest
-        // group (the replayed loads of the same launch take 1.2 ms, tools/pmc_rounds.sh / CATCHHIP_FLAT_PROBE).  So:
+        // group (the replayed loads of the same launch take 1.2 ms, tools/pmc_rounds.sh).  So:
         // every raise of the step is issued first, the answers are looked at afterwards.
         u32 gg[GR_UNR];
         bool claims[GR_UNR];
@@ -572,56 +510,6 @@ gr_claim_kernel(FlatArgs a, u32 round) {
     if (threadIdx.x == 0 && s_claim) st->fr_claim[par] = 1;
 }
 
-// Measurement only (CATCHHIP_FLAT_PROBE, a test hook; tools/pmc_rounds.sh): side-effect-free replays of a claim / count
-// launch's memory work, ingredient by ingredient, launched beside the real launches of the first rounds so that a
-// kernel trace prices each one on the live data.  MODE 0: the record stream alone; 1: + the gains by the runs' first
-// lanes and the lane permute; 2: + the owner (claim) or bitmap (count) words of every row; 3 (count side): + the
-// per-row popcounts and the segmented sum, without the atomics and without writing the survivors.  The result goes to a
-// sink that is never read.
-template <int MODE, bool COUNT_SIDE>
-__global__ void __launch_bounds__(GR_THREADS)
-gr_probe_kernel(FlatArgs a, u32 round, u32 buf, unsigned long long *sink) {
-    const u32 *acc = a.acc[round & 1];
-    const unsigned long long *words = COUNT_SIDE ? a.bm : a.owner[round & 1];
-    unsigned long long h = 0;
-    for_each_step(a, buf, [&](u32, u32, u32, u32, unsigned long long (&k)[GR_UNR], u32 (&x)[GR_UNR]) {
-        const u32 lane = threadIdx.x & 63;
-        u32 g[GR_UNR], hl[GR_UNR];
-        unsigned long long v[GR_UNR][RP_MAXW];
-#pragma unroll
-        for (int u = 0; u < GR_UNR; ++u) {
-            g[u] = 0; hl[u] = 0;
-#pragma unroll
-            for (u32 w = 0; w < RP_MAXW; ++w) v[u][w] = 0;
-            if (MODE >= 1 && !COUNT_SIDE) {
-                const u32 s = GR_KEY_SET(k[u]);
-                const u32 s_prev = __shfl_up(s, 1, WAVE);
-                const unsigned long long heads = __ballot(lane == 0 || s_prev != s);
-                hl[u] = 63u - (u32)__clzll(heads & (~0ull >> (63 - lane)));
-                if ((heads >> lane) & 1ull) g[u] = acc[s];
-            }
-            if (MODE >= 2 && GR_KEY_FLAGS(k[u])) load_words5(words + (x[u] >> 6), v[u], GR_KEY_FLAGS(k[u]));
-        }
-#pragma unroll
-        for (int u = 0; u < GR_UNR; ++u) {
-            h += k[u] ^ x[u];
-            if (MODE >= 1 && !COUNT_SIDE) h += __shfl(g[u], (int)hl[u], WAVE);
-            if (MODE >= 2) {
-                u32 cnt = 0;
-#pragma unroll
-                for (u32 w = 0; w < RP_MAXW; ++w) { h ^= v[u][w]; if (MODE >= 3) cnt += (u32)__popcll(v[u][w]); }
-                if (MODE >= 3) {
-                    bool tail;
-                    const u32 fl = GR_KEY_FLAGS(k[u]);
-                    const u32 tot = wave_segsum(cnt, fl ? GR_KEY_SET(k[u]) : 0xffffffffu - lane, &tail);
-                    if (tail) h += tot;
-                }
-            }
-        }
-    });
-    if (h == 0x1234567887654321ull) sink[0] = h;     // (never true in practice: keeps the loads alive)
-}
-
 #define GA_SWEEP_MAX 2048  // sets of a workgroup's segment swept per piece (the LDS list of the accepted ones)
 #define GA_THREADS 256   // (the apply launch walks sets, not records: 256 threads, as measured -- 7.6 vs 10.3 ms per S4 step with 512)
 // PARTIAL (universe_p < 1).  With min(need[u], .) a pick lowers the gain of EVERY set of its universe
@@ -636,12 +524,9 @@ gr_probe_kernel(FlatArgs a, u32 round, u32 buf, unsigned long long *sink) {
 // so under uT the need of u stays at least c's count until c is the maximum (its gain is what it is now,
 // and u is not finished before), and under uM nothing in u is covered before c at all.  The set with the
 // largest key of all passes by uM everywhere, so every round makes a pick.
-// Round 6: uT by LEVELS.  What the argument needs of "smax" is only that it bounds what the CANDIDATE covers in u
-// (the higher keys' picks leave the need at least that, so the candidate's min(need, count) is still its count at
-// its turn -- and the candidate's own early pick leaves every higher set's term alone: need - bits(c) >= need - b >=
-// the bits in words owned by larger keys >= that set's count).  A candidate with c uncovered elements in u is
-// therefore tested against the threshold of the smallest bound b_j >= c out of {8, 16, ..., smax} (GR_UT_LEVELS of
-// them; one -- smax alone -- by default: see GR_UT_LEVELS for what six of them measured).
+// (Round 6 measured one threshold per LEVEL of what the candidate still covers in u -- bounds 8, 16, ..., smax -- on S4
+// at -c 0.9: exact, 1,316 -> 1,205 rounds, but six thresholds per universe in gr_usel and 450 instead of 379 ms per
+// solve.  One threshold, bound smax, is what is built.)
 // the universe test of candidate sa over the rows [r0, r1) of this device, rows first, first + stride, ...: per
 // (set, universe) segment -- the first row of a segment sums it
 __device__ __forceinline__ bool gr_passes(const FlatArgs &a, const u32 *acc, u32 sa, u32 r0, u32 r1, u32 first, u32 stride) {
@@ -652,7 +537,7 @@ __device__ __forceinline__ bool gr_passes(const FlatArgs &a, const u32 *acc, u32
         if (r > r0 && (u32)a.row_univ[r - 1] == u) continue;
         u32 c = 0;
         for (u32 j = r; j < r1 && (u32)a.row_univ[j] == u; ++j) c += range_popcount((const u64 *)a.bm, a.row_gs[j], a.row_ge[j]);
-        if (c && !(key >= a.uT[(size_t)u * GR_UT_LEVELS + gr_ut_level(c)] || key >= a.uM[u])) ok = false;
+        if (c && !(key >= a.uT[u] || key >= a.uM[u])) ok = false;
     }
     return ok;
 }
@@ -1008,71 +893,60 @@ gr_usel_kernel(FlatArgs a, u32 round) {
     const i32 nd = a.need[u];
     const u32 g0 = a.genome_off[u], g1 = a.genome_off[u + 1];
     if (nd <= 0 || g1 <= g0) {
-        if (tid < GR_UT_LEVELS) a.uT[(size_t)u * GR_UT_LEVELS + tid] = ~0ull;
-        if (tid == 0) a.uM[u] = ~0ull;
+        if (tid == 0) { a.uT[u] = ~0ull; a.uM[u] = ~0ull; }
         return;
     }
     const unsigned long long *owner = a.owner[round & 1];
     const u32 w0 = g0 >> 6, w1 = (g1 - 1) >> 6;
     const u32 smax = st->smax;
     unsigned long long mx = 0;
-    for (u32 level = 0; level < GR_UT_LEVELS; ++level) {
-        // (a bound that repeats the previous level's -- smax below 128 -- repeats its threshold)
-        if (level > 0 && gr_ut_bound(level, smax) == gr_ut_bound(level - 1, smax)) {
-            __syncthreads();
-            if (tid == 0) a.uT[(size_t)u * GR_UT_LEVELS + level] = a.uT[(size_t)u * GR_UT_LEVELS + level - 1];
-            continue;
-        }
-        const long long x0 = (long long)nd - (long long)gr_ut_bound(level, smax);
+    const long long x0 = (long long)nd - (long long)smax;
+    if (tid == 0) { s_prefix = 0; s_x = x0; s_n = 0; }
+    bool stop = false;
+    for (int byte = 7; byte >= 0; --byte) {
+        s_hist[tid] = 0;
         __syncthreads();
-        if (tid == 0) { s_prefix = 0; s_x = x0; if (level == 0) s_n = 0; }
-        bool stop = false;
-        for (int byte = 7; byte >= 0; --byte) {
-            s_hist[tid] = 0;
-            __syncthreads();
-            const unsigned long long prefix = s_prefix;
-            const long long x = s_x;
-            const u32 nl = s_n;
-            if ((level == 0 && byte == 7) || nl > GR_USEL_CAP) {
-                for (u32 w = w0 + tid; w <= w1; w += 256) {
-                    u64 m = ~0ull;
-                    if (w == w0) m &= ~0ull << (g0 & 63);
-                    if (w == w1) m &= ~0ull >> (63 - ((g1 - 1) & 63));
-                    const u32 wt = (u32)__popcll(a.bm[w] & m);
-                    if (!wt) continue;
-                    const unsigned long long k = owner[w];
-                    if (level == 0 && byte == 7) {
-                        mx = k > mx ? k : mx;
-                        const u32 at = atomicAdd(&s_n, 1u);
-                        if (at < GR_USEL_CAP) { s_k[at] = k; s_w[at] = wt; }
-                    }
-                    if (x0 >= 0 && (byte == 7 || (k >> (8 * (byte + 1))) == prefix)) atomicAdd(&s_hist[(k >> (8 * byte)) & 0xffu], (unsigned long long)wt);
+        const unsigned long long prefix = s_prefix;
+        const long long x = s_x;
+        const u32 nl = s_n;
+        if (byte == 7 || nl > GR_USEL_CAP) {
+            for (u32 w = w0 + tid; w <= w1; w += 256) {
+                u64 m = ~0ull;
+                if (w == w0) m &= ~0ull << (g0 & 63);
+                if (w == w1) m &= ~0ull >> (63 - ((g1 - 1) & 63));
+                const u32 wt = (u32)__popcll(a.bm[w] & m);
+                if (!wt) continue;
+                const unsigned long long k = owner[w];
+                if (byte == 7) {
+                    mx = k > mx ? k : mx;
+                    const u32 at = atomicAdd(&s_n, 1u);
+                    if (at < GR_USEL_CAP) { s_k[at] = k; s_w[at] = wt; }
                 }
-            } else {
-                for (u32 q = tid; q < nl; q += 256) {
-                    const unsigned long long k = s_k[q];
-                    if (byte == 7 || (k >> (8 * (byte + 1))) == prefix) atomicAdd(&s_hist[(k >> (8 * byte)) & 0xffu], (unsigned long long)s_w[q]);
-                }
+                if (x0 >= 0 && (byte == 7 || (k >> (8 * (byte + 1))) == prefix)) atomicAdd(&s_hist[(k >> (8 * byte)) & 0xffu], (unsigned long long)wt);
             }
-            __syncthreads();
-            if (x0 < 0) break;                       // (need below the bound: only the top set passes, uM is all that is used)
-            // the highest byte value d whose suffix sum (the weight of d and everything above) exceeds x
-            unsigned long long T = s_hist[tid];
-            for (int off = 1; off < 256; off <<= 1) {
-                s_scan[tid] = T;
-                __syncthreads();
-                if (tid + off < 256) T += s_scan[tid + off];
-                __syncthreads();
+        } else {
+            for (u32 q = tid; q < nl; q += 256) {
+                const unsigned long long k = s_k[q];
+                if (byte == 7 || (k >> (8 * (byte + 1))) == prefix) atomicAdd(&s_hist[(k >> (8 * byte)) & 0xffu], (unsigned long long)s_w[q]);
             }
-            const int over = (long long)T > x;         // (suffix sums do not increase with the byte value: a prefix of the threads)
-            const int cnt = __syncthreads_count(over);
-            if (cnt == 0) { stop = true; break; }     // everything in reach weighs at most x: no threshold
-            if ((int)tid == cnt - 1) { s_prefix = (prefix << 8) | (unsigned long long)tid; s_x = x - (long long)(T - s_hist[tid]); }
-            __syncthreads();
         }
         __syncthreads();
-        if (tid == 0) a.uT[(size_t)u * GR_UT_LEVELS + level] = x0 < 0 ? ~0ull : (stop ? 0ull : s_prefix);
+        if (x0 < 0) break;                       // (need below the bound: only the top set passes, uM is all that is used)
+        // the highest byte value d whose suffix sum (the weight of d and everything above) exceeds x
+        unsigned long long T = s_hist[tid];
+        for (int off = 1; off < 256; off <<= 1) {
+            s_scan[tid] = T;
+            __syncthreads();
+            if (tid + off < 256) T += s_scan[tid + off];
+            __syncthreads();
+        }
+        const int over = (long long)T > x;         // (suffix sums do not increase with the byte value: a prefix of the threads)
+        const int cnt = __syncthreads_count(over);
+        if (cnt == 0) { stop = true; break; }     // everything in reach weighs at most x: no threshold
+        if ((int)tid == cnt - 1) { s_prefix = (prefix << 8) | (unsigned long long)tid; s_x = x - (long long)(T - s_hist[tid]); }
+        __syncthreads();
     }
+    if (tid == 0) a.uT[u] = x0 < 0 ? ~0ull : (stop ? 0ull : s_prefix);
     mx = wave_max_u64(mx);
     if ((tid & 63) == 0) s_max[tid >> 6] = mx;
     __syncthreads();
@@ -1357,7 +1231,7 @@ struct FlatSolve {
         // workgroups per CU: the walk is persistent (for_each_step deals the steps out), so what is resident at once -- 4 x 8
         // wavefronts per CU -- is enough, and the ~20 short launches at the end of every solve start half as many (K2 rounds of
         // an S4 step one chain at a time: 12 per CU 41.8 ms, 8: 40.5 -- the value until round 6 --, 6: 40.3, 4: 40.1)
-        const i64 wg_per_cu = chip_test_env("CATCHHIP_FLAT_WG_PER_CU") ? std::max(1, atoi(chip_test_env("CATCHHIP_FLAT_WG_PER_CU"))) : 4;
+        const i64 wg_per_cu = std::max<i64>(1, chip_test_env_int("CATCHHIP_FLAT_WG_PER_CU", 4));
         gblocks = (unsigned)(std::max<i64>(8, std::min<i64>(div_up(nrows, GR_BCH), (i64)ctx->num_cus * wg_per_cu)) + 7) & ~7u;
         // Tiles.  A coordinate space whose bitmap + owner words (0.25 B per base) fit
         // the eight L2s together (<= 64 Mbases: 2 MB per XCD) is cut into 8 STRIPED
@@ -1369,21 +1243,21 @@ struct FlatSolve {
         // rounds of an S4 step), 16-32 of them so that every XCD sweeps several, at most 256 (one radix pass).
         int tile_shift = -1;
         u32 ntiles = 8;
-        if (((u64)R->total > ((u64)64 << 20) || chip_test_env("CATCHHIP_FLAT_TILE_SHIFT")) && !chip_test_env("CATCHHIP_FLAT_STRIPED")) {
+        const int forced_shift = (int)chip_test_env_int("CATCHHIP_FLAT_TILE_SHIFT", -1);
+        if (((u64)R->total > ((u64)64 << 20) || forced_shift >= 0) && !chip_test_env("CATCHHIP_FLAT_STRIPED")) {
             // (partial coverage: hundreds of rounds over the tenth of the rows that stays alive, in which what a
             // round moves is the per-set arrays once per tile -- 8 tiles of up to 32 Mbases: 198 -> 159 ms on
             // S4's largest group)
-            const int max_shift = chip_test_env("CATCHHIP_FLAT_MAX_TILE_SHIFT") ? atoi(chip_test_env("CATCHHIP_FLAT_MAX_TILE_SHIFT")) : (partial ? 25 : 24);
+            const int max_shift = partial ? 25 : 24;
             // (round 6, the kernels of rounds 4-6: 16 tiles of 16 Mbases beat 32 of 8 on S4's largest group -- 16.8 vs 17.8 ms
             // in the rounds; 8 of 32 Mbases: 16.9 -- so at least 8 tiles, one per XCD, whatever the coverage; 16 until then)
             // A union of independent groups (rows of a scan with group numbers) gets 16 tiles at least: its tiles differ
             // tenfold in rows, and 30 of them are dealt to 8 XCDs more evenly than 15 (S4's union instance: 24.1 M rows on the
             // fullest XCD with 15 tiles, for 21.8 M on average) -- worth more there than the longer runs of larger tiles.
-            const u64 min_tiles = chip_test_env("CATCHHIP_FLAT_MIN_TILES") ? (u64)std::max(1, atoi(chip_test_env("CATCHHIP_FLAT_MIN_TILES")))
-                                                                           : (R->grouped && !partial ? 16 : 8);
+            const u64 min_tiles = (u64)std::max<i64>(1, chip_test_env_int("CATCHHIP_FLAT_MIN_TILES", R->grouped && !partial ? 16 : 8));
             tile_shift = 16;
             while (tile_shift < max_shift && ((u64)R->total >> (tile_shift + 1)) >= min_tiles) ++tile_shift;
-            if (chip_test_env("CATCHHIP_FLAT_TILE_SHIFT")) tile_shift = atoi(chip_test_env("CATCHHIP_FLAT_TILE_SHIFT"));
+            if (forced_shift >= 0) tile_shift = forced_shift;
             while (((u64)R->total >> tile_shift) >= 256) ++tile_shift;
             ntiles = (u32)((u64)R->total >> tile_shift) + 1;
         }
@@ -1400,14 +1274,14 @@ struct FlatSolve {
         const size_t o_chg0 = take(4 * nchg), o_chg1 = take(4 * nchg);
         const size_t o_cflag = take(partial ? 4 * ((size_t)nsets + 1) : 0), o_ufinal = take(partial ? 4 * (size_t)nuniv + 4 : 0);
         const size_t zero_bytes = off;
-        const bool list_alive = !partial && !sharded && !chip_test_env("CATCHHIP_FLAT_NO_ALIVE_LIST");
+        const bool list_alive = !partial && !sharded;
         const u32 alive_seg = (u32)div_up((i64)std::max<u32>(nsets, 1), (i64)gblocks);
         const size_t o_al0 = take(list_alive ? 4 * (size_t)alive_seg * gblocks : 0), o_al1 = take(list_alive ? 4 * (size_t)alive_seg * gblocks : 0),
                      o_alc0 = take(list_alive ? 4 * (size_t)gblocks : 0), o_alc1 = take(list_alive ? 4 * (size_t)gblocks : 0);
         const size_t o_usize = take(4 * (size_t)std::max<u32>(nuniv, 1)), o_picks = take(4 * (size_t)nsets),
                      o_keys = take(8 * (size_t)nsets), o_tptr = take(4 * 258), o_sptr = take(4 * ((size_t)nsets + 1)),
                      o_xt = take(4 * 8 * GR_MAXTX), o_xn = take(4 * 8);
-        const size_t o_need = take(partial ? 4 * (size_t)nuniv + 4 : 0), o_uT = take(partial ? 8 * (size_t)nuniv * GR_UT_LEVELS + 8 : 0),
+        const size_t o_need = take(partial ? 4 * (size_t)nuniv + 4 : 0), o_uT = take(partial ? 8 * (size_t)nuniv + 8 : 0),
                      o_uM = take(partial ? 8 * (size_t)nuniv + 8 : 0), o_cpos = take(partial ? 4 * ((size_t)nsets + 1) : 0),
                      o_cset = take(partial ? 4 * ((size_t)nsets + 2) : 0);
         TRY(arena.alloc(off));
@@ -1494,20 +1368,17 @@ struct FlatSolve {
         // the sorted records are buffer 0, the sort's scratch is buffer 1
         fa.key[0] = (unsigned long long *)skey.p;
         fa.key[1] = (unsigned long long *)skey_alt.p;
-        // (measured on S4: the ORs cost 4.8 ms inside round 0's count launch against 5.9 ms as a pass of their own;
-        // opt-in, so that "set-up" and "rounds" keep meaning what they meant in earlier rounds' numbers)
-        fa.bm_in_round0 = (!partial && !sharded && chip_test_env("CATCHHIP_FLAT_BITMAP_IN_ROUND0")) ? 1u : 0u;
         // Full coverage on one device needs no universe bitmap at all: every position of a row is in the universe
         // (the union of the rows), so a row's uncovered positions are those of its own that are not COVERED yet --
         // the bitmap holds the covered positions and starts empty (round 3: gr_bitmap was 5.9 ms per S4 step).
         // Partial coverage needs |U_u| per genome and a shard the all-reduced needs: those keep the union.
-        fa.inv = (!partial && !sharded && !fa.bm_in_round0 && !chip_test_env("CATCHHIP_FLAT_UNIVERSE_BITMAP")) ? ~0ull : 0ull;
-        if (!fa.bm_in_round0 && !fa.inv) hipLaunchKernelGGL(gr_bitmap_kernel, dim3(gblocks), dim3(GR_THREADS), 0, s, fa);
+        fa.inv = (!partial && !sharded) ? ~0ull : 0ull;
+        if (!fa.inv) hipLaunchKernelGGL(gr_bitmap_kernel, dim3(gblocks), dim3(GR_THREADS), 0, s, fa);
         // Round 0 of a full-coverage solve counts nothing that is not known: every row is uncovered, a set's gain is
         // the total length of its rows -- which the row build summed on the way (catchhip_rows::gain0).  Then the
         // first count launch (a pass over every record: 0.9 of the 21 ms of S4's largest solve) is left out.
         fa.count0_done = 0;
-        if (!partial && !sharded && !fa.bm_in_round0 && !stats_dirty && R->gain0_n && nrows && !chip_test_env("CATCHHIP_FLAT_COUNT_ROUND0")) {
+        if (!partial && !sharded && !stats_dirty && R->gain0_n && nrows && !chip_test_env("CATCHHIP_FLAT_COUNT_ROUND0")) {
             const u32 ng = std::min<u32>(R->gain0_n, nsets);
             HIP_TRY(hipMemcpyAsync(fa.acc[0], R->gain0.p, sizeof(u32) * (size_t)ng, hipMemcpyDeviceToDevice, s));
             hipLaunchKernelGGL(gr_fill_one_kernel, dim3(1), dim3(1), 0, s, fa.acc[0] + nsets, 1u);
@@ -1537,15 +1408,6 @@ struct FlatSolve {
         } else hipLaunchKernelGGL(gr_count_kernel<false>, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
     }
     void launch_claim(u32 round) {
-        if (!partial && round < 2 && chip_test_env("CATCHHIP_FLAT_PROBE")) {
-            // (measurement only: the ingredients of this claim launch and of the count launch before it, replayed)
-            unsigned long long *sink = (unsigned long long *)fa.blkcnt;
-            hipLaunchKernelGGL((gr_probe_kernel<0, false>), dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round, round & 1, sink);
-            hipLaunchKernelGGL((gr_probe_kernel<1, false>), dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round, round & 1, sink);
-            hipLaunchKernelGGL((gr_probe_kernel<2, false>), dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round, round & 1, sink);
-            hipLaunchKernelGGL((gr_probe_kernel<2, true>), dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round, round & 1, sink);
-            hipLaunchKernelGGL((gr_probe_kernel<3, true>), dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round, round & 1, sink);
-        }
         hipLaunchKernelGGL(gr_claim_kernel, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
         if (partial && fa.nuniv) hipLaunchKernelGGL(gr_usel_kernel, dim3(fa.nuniv), dim3(256), 0, ctx->stream, fa, round);
     }
@@ -1613,20 +1475,6 @@ static int greedy_flat(catchhip_ctx *ctx, const catchhip_rows *R, u32 nsets, con
     TRY(F.setup(ctx, R, nsets, h_rank, nrank, false, &tm, h_p));
     const i64 max_rounds = (i64)nsets + nrank + 2;
     i64 rounds = 0;
-    if (chip_test_env("CATCHHIP_FLAT_TRACE") && atoi(chip_test_env("CATCHHIP_FLAT_TRACE")) > 1) {   // the rows of every XCD's tiles at the start
-        std::vector<u32> tc(F.fa.ntiles);
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(tc.data(), F.fa.tile_cnt[0], 4 * (size_t)F.fa.ntiles, hipMemcpyDeviceToHost));
-        unsigned long long xs[8] = {0}, tot = 0;
-        u32 xt[8 * GR_MAXTX], xn[8];
-        HIP_TRY(hipMemcpy(xt, F.fa.xcd_tile, sizeof(xt), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(xn, F.fa.xcd_ntiles, sizeof(xn), hipMemcpyDeviceToHost));
-        for (u32 x = 0; x < 8; ++x)
-            for (u32 j = 0; j < xn[x] && j < (u32)GR_MAXTX; ++j) { xs[x] += tc[xt[x * GR_MAXTX + j]]; tot += tc[xt[x * GR_MAXTX + j]]; }
-        fprintf(stderr, "[catchhip] flat solver: %llu rows in %u tiles (shift %d); per XCD:", tot, F.fa.ntiles, F.fa.tile_shift);
-        for (int x = 0; x < 8; ++x) fprintf(stderr, " %llu", xs[x]);
-        fprintf(stderr, "\n");
-    }
     int per_sync = 16;   // most instances finish in 13-21 rounds: one or two synchronisations
     u8 *H = (u8 *)ctx->h_big;
     GreedyState *h_st = (GreedyState *)H;
@@ -1656,29 +1504,6 @@ static int greedy_flat(catchhip_ctx *ctx, const catchhip_rows *R, u32 nsets, con
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ctx->evx[2 * r], ctx->evx[2 * r + 1]) == hipSuccess) ctx->phase_ms[PHASE_CLAIM] += ms;
             ctx->phase_launches[PHASE_CLAIM]++;
-        }
-        if (chip_test_env("CATCHHIP_FLAT_TRACE")) {
-            i64 vis = 0;
-            for (unsigned b = 0; b < F.gblocks; ++b) vis += (i64)h_blk[4 * b];
-            fprintf(stderr, "[catchhip] flat solver: %lld rounds queued, %u run, %u picks, %u universes in need, %lld records streamed so far\n",
-                    (long long)rounds, h_st->iters, h_st->npicks, h_st->n_need, (long long)vis);
-            if (atoi(chip_test_env("CATCHHIP_FLAT_TRACE")) > 1) {     // alive rows per tile and per XCD (tiles x, x + 8, ...)
-                std::vector<u32> tc(F.fa.ntiles);
-                HIP_TRY(hipMemcpy(tc.data(), F.fa.tile_cnt[(rounds & 1) ^ 1], 4 * (size_t)F.fa.ntiles, hipMemcpyDeviceToHost));
-                unsigned long long xs[8] = {0}, tot = 0;
-                u32 mx = 0;
-                u32 xt[8 * GR_MAXTX], xn[8];
-                HIP_TRY(hipMemcpy(xt, F.fa.xcd_tile, sizeof(xt), hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(xn, F.fa.xcd_ntiles, sizeof(xn), hipMemcpyDeviceToHost));
-                for (u32 x = 0; x < 8; ++x)
-                    for (u32 j = 0; j < xn[x] && j < (u32)GR_MAXTX; ++j) {
-                        const u32 c = tc[xt[x * GR_MAXTX + j]];
-                        xs[x] += c; tot += c; mx = std::max(mx, c);
-                    }
-                fprintf(stderr, "[catchhip]   alive %llu in %u tiles (largest %u); per XCD:", tot, F.fa.ntiles, mx);
-                for (int x = 0; x < 8; ++x) fprintf(stderr, " %llu", xs[x]);
-                fprintf(stderr, "\n");
-            }
         }
         if (h_st->done) break;
         if (rounds > max_rounds) { chip_set_error("setcover: round cap exceeded"); return CATCHHIP_EINVAL; }

@@ -248,8 +248,7 @@ class SetCoverFilter(BaseFilter):
         if (only is None and tables is None
                 and assume_unique and not self.identify and not self.avoided_genomes
                 and len(todo) >= int(_lib.test_env("CATCHHIP_UNION_MIN_GROUPS", "8"))
-                and sum(len(input_strs[gi]) for gi in todo) <= len(todo) * int(
-                    _lib.test_env("CATCHHIP_UNION_MAX_MEAN_CANDIDATES", "8192"))
+                and sum(len(input_strs[gi]) for gi in todo) <= len(todo) * 8192
                 and len({len(s) for gi in todo for s in input_strs[gi]}) == 1):
             self._filter_strs_union(input_strs, target_genomes_grouped, todo,
                                     selected, timings)
@@ -676,31 +675,21 @@ class SetCoverFilter(BaseFilter):
                 slots = threading.Semaphore(max(2, depth) * nl)
                 res_lock = threading.Lock()
 
-                # Builders: one (CATCHHIP_BUILDERS, a test hook, starts more when no random numbers are drawn while
-                # building; each takes the next item of the production order when it is free).  Measured in round 5 on S4
+                # ONE builder, which takes the items in production order (so the draws of a build that draws random
+                # numbers -- random anchors, a near-duplicate filter -- stay in that order).  Measured in round 5 on S4
                 # from host strings: two builders, or lanes balanced by cost instead of size, leave the pass at 0.128-0.133 s
                 # -- the three lanes' kernels share one device, and the pass is within ~10 % of the device work it holds
                 # (96 ms of scans and solves one chain at a time + ~20 ms of front-end kernels + 0.5 GB of uploads).
-                # (keep_input_order is set whenever building draws random numbers -- random anchors, a near-duplicate
-                # filter --: ONE builder then, whatever the hook says, so that the draws stay in production order)
-                nbuilders = 1 if keep_input_order else max(1, int(_lib.test_env("CATCHHIP_BUILDERS", "1")))
-                next_item = [0]
-                take_lock = threading.Lock()
-
-                def producer(worker=0):
-                    while True:
+                def producer():
+                    for gi in production:
                         slots.acquire()
-                        with take_lock:
-                            at_ = next_item[0]
-                            next_item[0] += 1
-                        if at_ >= len(production) or errors:
+                        if errors:
                             slots.release()
                             return
-                        gi = production[at_]
                         try:
                             # built on the upload context of the DEVICE whose lane will consume it: with CATCHHIP_DEVICES
                             # the lanes sit on several GPUs, and an object cannot change hands across devices
-                            res = build(gi, engine.upload_context(ctxs[lane_of[gi]].device, index=worker))
+                            res = build(gi, engine.upload_context(ctxs[lane_of[gi]].device))
                         except BaseException as exc:
                             with cv:
                                 errors.append(exc)
@@ -750,19 +739,16 @@ class SetCoverFilter(BaseFilter):
                         if errors:
                             return
 
-                prods = [threading.Thread(target=producer, args=(w,), name="catchhip-prefetch") for w in range(nbuilders)]
+                prod = threading.Thread(target=producer, name="catchhip-prefetch")
                 threads = [threading.Thread(target=lane, args=(li,), name="catchhip-lane") for li in range(1, nl)]
-                for t in prods:
-                    t.start()
+                prod.start()
                 for t in threads:
                     t.start()
                 lane(0)
                 for t in threads:
                     t.join()
-                for _ in range(len(production) + nbuilders + 1):
-                    slots.release()                  # let the builders run off the end of the list (or into the error flag)
-                for t in prods:
-                    t.join()
+                slots.release()                      # (after an error the builder may be waiting for a slot: into the error flag)
+                prod.join()
                 for res in built.values():           # built, never consumed (after an error)
                     discard(res)
                 if errors:
@@ -826,7 +812,6 @@ class SetCoverFilter(BaseFilter):
                        rows=0, scan_launches=0, greedy_launches=0,
                        candidates=0, unique_candidates=0)
         ctx = engine.default_context()
-        max_bases = int(float(_lib.test_env("CATCHHIP_UNION_MAX_MBASES", str(max_bases / 1e6))) * 1e6)     # (test hook)
         # the clusters of a clustered design may come as views of the genomes' storage (probe_designer.
         # ClusteredFragments: every member a single-sequence genome): sizes, targets and the selected probes' text
         # are then taken from the table, and no Genome / str is made per fragment

@@ -201,9 +201,8 @@ class World:
     def native_for(self, shards):
         """What sharded_solve's `native` should be for these shards: "rccl" when the ranks have a communicator (one
         process per GPU: the whole loop then runs under the C ABI, catchhip_shard_solve), None when the exchange goes
-        through the host (several ranks on one GPU, or the CATCHHIP_SHARD_PYTHON_LOOP test hook)."""
-        from catch_amd import _lib
-        if self.rccl and len(shards) == 1 and not _lib.test_env("CATCHHIP_SHARD_PYTHON_LOOP"):
+        through the host (several ranks on one GPU)."""
+        if self.rccl and len(shards) == 1:
             return "rccl"
         return None
 

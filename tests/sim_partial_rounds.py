@@ -10,7 +10,8 @@ A set c is accepted in a round iff
                below c's count in u, so neither min(need, count) nor its neighbours change c's gain before
                c is the maximum.  B = the largest (set, universe) count until round 5; since round 6 the
                smallest of the levels 8, 16, 32, 64, 128, CMAX that is >= c's own count in u when LEVELS=1
-               is set (gr_usel / gr_passes built with -DGR_UT_LEVELS=6; exact, measured, not the default).
+               is set.  LEVELS=1 is a MODEL ONLY: the library measured that rule in round 6 (exact, fewer
+               rounds, slower solves), rejected it and no longer builds it; it computes the one-level rule.
 Gains are exact: sum over universes of min(need[u], count).  Usage: python tests/sim_partial_rounds.py [scale] [groups]
 """
 import sys, time
@@ -22,7 +23,7 @@ from oracle import oracle as orc
 
 
 import os
-LEVELS = os.environ.get("LEVELS", "0") != "0"     # (the library builds with one level, GR_UT_LEVELS; LEVELS=1: six)
+LEVELS = os.environ.get("LEVELS", "0") != "0"     # (the library computes one level; LEVELS=1: six, a model only)
 
 
 def level_of(c, bounds):

@@ -657,3 +657,40 @@ def test_minhash_parameter_draws_in_bulk_equal_the_interpreter():
         random.seed(1000 + seed)
         assert _randint_pairs_like_random(5000, P) == want and random.getstate() == st
     assert _randint_pairs_like_random(10, 2 ** 31 - 2) is None       # (another modulus: not what this parses)
+
+
+def test_every_test_hook_has_a_user_and_the_readme_lists_real_ones():
+    """A test hook (chip_test_env / chip_test_env_int in csrc, _lib.test_env on the Python side) exists only
+    while something sets it: a file under tests/, bench.py, __graft_entry__.py or a script under tools/.  A
+    hook nobody sets is an untested branch, and goes with the code only it reaches.  And the hooks README.md's
+    paragraph names exist in the sources.  Reads files of the repository only."""
+    import glob
+
+    def read(path):
+        with open(path, encoding="utf-8") as f:
+            return f.read()
+
+    def files(*patterns):
+        return sorted(p for pat in patterns for p in glob.glob(os.path.join(REPO, pat), recursive=True)
+                      if os.path.isfile(p))
+
+    csrc = [p for p in files("catch_amd/csrc/*") if p.endswith((".hip", ".inc", ".h"))]
+    hooks = set()
+    for p in csrc:
+        hooks |= set(re.findall(r'\bchip_test_env(?:_int)?\(\s*"(CATCHHIP_[A-Z0-9_]+)"', read(p)))
+    for p in files("catch_amd/**/*.py"):
+        hooks |= set(re.findall(r'\btest_env\(\s*"(CATCHHIP_[A-Z0-9_]+)"', read(p)))
+    assert len(hooks) >= 20, hooks          # (the patterns still find them)
+    users = files("tests/**/*.py", "tools/**/*.py", "tools/**/*.sh", "bench.py", "__graft_entry__.py")
+    used = set()
+    for p in users:
+        used |= set(re.findall(r"\bCATCHHIP_[A-Z0-9_]+\b", read(p)))
+    assert sorted(hooks - used) == []
+
+    readme = read(os.path.join(REPO, "README.md"))
+    start = readme.index("Everything else that starts with `CATCHHIP_`")
+    paragraph = readme[start:readme.index("\n\n", start)]
+    listed = set(re.findall(r"\bCATCHHIP_[A-Z0-9_]+\b", paragraph))
+    assert len(listed) >= 10, listed
+    sources = "\n".join(read(p) for p in csrc + files("catch_amd/**/*.py", "include/*.h"))
+    assert sorted(n for n in listed if not re.search(r"\b%s\b" % n, sources)) == []
