@@ -107,6 +107,9 @@ PROTOTYPES = {
         ctypes.c_int32, ctypes.c_int32, c_i32p, ctypes.c_int64, c_i64p, c_f64p,
         ctypes.POINTER(c_i64p), c_i64p, c_i64p]),
     "catchhip_ctx_last_grid_counters": (ctypes.c_int, [c_vp, c_i64p]),
+    "catchhip_pool_solve": (ctypes.c_int, [
+        c_vp, ctypes.c_int64, c_i64p, c_i64p, c_f64p, ctypes.c_int64, c_i32p, c_i64p,
+        ctypes.POINTER(ctypes.c_double)]),
     "catchhip_comm_unique_id": (ctypes.c_int, [c_u8p]),
     "catchhip_comm_init": (ctypes.c_int, [
         c_vp, c_u8p, ctypes.c_int32, ctypes.c_int32]),

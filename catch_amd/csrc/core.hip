@@ -82,6 +82,8 @@ static size_t pool_soft_limit() {
     return soft_limit;
 }
 
+size_t chip_pool_soft_limit() { return pool_soft_limit(); }
+
 const void *chip_pool_set_owner(const void *owner) {
     const void *prev = g_pool_owner;
     g_pool_owner = owner;

@@ -81,6 +81,8 @@ struct PoolScope {
     ~PoolScope() { chip_pool_set_owner(prev); }
 };
 void chip_pool_free(void *p);
+// what the cache may hold (bytes): 0.87 of the device, or CATCHHIP_POOL_SOFT_LIMIT_GB
+size_t chip_pool_soft_limit();
 
 // Device buffer owning a pooled region (returned to the pool in the destructor).
 template <typename T> struct DevBuf {
@@ -115,7 +117,7 @@ template <typename T> struct DevBuf {
 };
 
 enum { PHASE_SCAN = 0, PHASE_ROWS = 1, PHASE_GREEDY = 2, PHASE_NDF = 3, PHASE_GREEDY_ROUNDS = 4, PHASE_VERIFY = 5,
-       PHASE_CLAIM = 6, PHASE_VCOUNT = 7, NPHASE = 8 };
+       PHASE_CLAIM = 6, PHASE_VCOUNT = 7, PHASE_POOL = 8, NPHASE = 9 };
 #define CHIP_EVX 16   // event pairs for per-launch timing inside a batch of solver rounds (PHASE_CLAIM)
 
 struct catchhip_ctx {

@@ -16,6 +16,7 @@ PHASE_SCAN, PHASE_ROWS, PHASE_GREEDY, PHASE_NDF, PHASE_GREEDY_ROUNDS = 0, 1, 2, 
 PHASE_VERIFY = 5
 PHASE_CLAIM = 6
 PHASE_VCOUNT = 7      # key-grouped join: the counting pass (PHASE_VERIFY: the writing pass)
+PHASE_POOL = 8        # catchhip_pool_solve: one launch per dataset + the walk back
 
 
 def _ptr(a, t):
@@ -1077,6 +1078,25 @@ def setcover_grid(ctx, probes, targets, mismatches, lcf_thres, island,
         None if up is None else _ptr(up, c_f64p), out_p,
         _ptr(n_out, c_i64p), _ptr(nrows, c_i64p)))
     return [(outs[i][:n_out[i]].tolist(), int(nrows[i])) for i in range(n)]
+
+
+def pool_solve(ctx, opt_off, counts, losses, budget):
+    """catchhip_pool_solve: the exact budgeted choice of one option per dataset.
+    opt_off[D + 1], counts / losses per option -> (option index per dataset,
+    total count, loss).  ValueError when the budget cannot be met."""
+    off = np.ascontiguousarray(opt_off, dtype=np.int64)
+    cn = np.ascontiguousarray(counts, dtype=np.int64)
+    ls = np.ascontiguousarray(losses, dtype=np.float64)
+    D = int(off.size) - 1
+    assert D >= 0 and cn.size == ls.size == int(off[-1])
+    if cn.size == 0:
+        cn, ls = np.zeros(1, np.int64), np.zeros(1, np.float64)
+    out = np.zeros(max(D, 1), dtype=np.int32)
+    total = ctypes.c_int64(0)
+    loss = ctypes.c_double(0.0)
+    check(ctx._L.catchhip_pool_solve(ctx._h, D, _ptr(off, c_i64p), _ptr(cn, c_i64p), _ptr(ls, c_f64p),
+                                     int(budget), _ptr(out, c_i32p), ctypes.byref(total), ctypes.byref(loss)))
+    return out[:D].astype(np.int64), int(total.value), float(loss.value)
 
 
 def collect_solution_checks(sink):

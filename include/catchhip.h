@@ -67,7 +67,10 @@ int catchhip_pool_trim(void);
  * (count+claim, check+apply) launch pairs of the frontier solver's rounds,
  * 5 = only the seed-verify launch of the seed scan (part of phase 0),
  * 6 = only the claim launches of the row-parallel solver (part of phase 4;
- * 0 launches when the last solve used the other kernels).
+ * 0 launches when the last solve used the other kernels), 7 = only the
+ * counting pass of the key-grouped join (part of phase 0; 5 is its writing
+ * pass), 8 = the launches of
+ * catchhip_pool_solve (one per dataset + the walk back).
  * *launches = kernel launches timed. */
 int catchhip_ctx_last_kernel_ms(catchhip_ctx *ctx, int phase, double *ms,
                                 int64_t *launches);
@@ -296,6 +299,31 @@ int catchhip_setcover_grid(catchhip_ctx *ctx, const catchhip_probes *probes,
 /* Work of the last catchhip_setcover_grid on this context, 4 values: cover
  * scans, derived row tables, solves, rows of the e = 0 scan. */
 int catchhip_ctx_last_grid_counters(catchhip_ctx *ctx, int64_t *out4);
+
+/* ---- pooling: one designed grid point per dataset within a probe budget ----
+ * Replaces param_search.standard_search / higher_dimensional_search +
+ * _round_params (catch/pool/param_search.py:547-658, :661-749, :362-520; the
+ * loss of :25-126 without its barrier term) as bin/pool.py calls them.  The
+ * reference interpolates probe counts between grid points, minimises loss +
+ * barrier from a random start and rounds; this is the exact minimum over the
+ * designed points themselves (a multiple-choice knapsack).  Dataset i has
+ * options opt_off[i] .. opt_off[i + 1] - 1 (opt_off[0] = 0) with counts[]
+ * (probes) and losses[] (float64, finite), both host arrays of opt_off[D]
+ * entries.  f_0[b] = 0 for 0 <= b <= budget; f_i[b] = min over options k with
+ * count <= b of f_{i-1}[b - count] + loss, in float64, +inf where none fits,
+ * the smallest k among equal values; the walk back from f_D[budget] gives
+ * out_choice[D] (option index within its dataset), *out_total (sum of the
+ * chosen counts) and *out_loss (= f_D[budget]: the chosen losses added in
+ * dataset order).  One kernel launch per dataset, one lane per budget cell; the
+ * D x (budget + 1) table of 16-bit choices stays on the device.
+ * CATCHHIP_EINVAL with a message: the budget is below the sum of each dataset's
+ * smallest count (the message names that sum), a dataset has no or more than
+ * 65,535 options, a negative count, a loss that is not finite, or a choice
+ * table larger than the device-memory cache may hold. */
+int catchhip_pool_solve(catchhip_ctx *ctx, int64_t D, const int64_t *opt_off,
+                        const int64_t *counts, const double *losses,
+                        int64_t budget, int32_t *out_choice, int64_t *out_total,
+                        double *out_loss);
 
 /* Multi-GPU, one process per GPU: an RCCL communicator attached to a context
  * (the reference has no counterpart: it forks a process pool,
