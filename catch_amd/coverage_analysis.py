@@ -8,8 +8,11 @@ sequence (:183-280) -- is one catchhip_cover_ranges call per strand over all
 genomes at once (every sequence its own universe); the statistics the
 reference derives from those ranges (:282-335) are reduced on the device too (catchhip_rows_stats: bases
 covered, summed range lengths, sequences per probe), so a report over thousands
-of genomes never brings the row table to the host; `target_covers` and
-`sliding_coverage` (:337-411) are fetched / computed on first use.
+of genomes never brings the row table to the host.  The sliding-window depth
+(:337-411) is computed on the device as well (catchhip_rows_window_depth, one
+scan per strand on first use of `sliding_coverage` or its writer): what comes
+back is one integer sum and one base count per window, never a range.
+`target_covers` is fetched on first use.
 Same constructor, attributes (`target_covers`, `bp_covered`,
 `average_coverage`, `sliding_coverage`, `probe_map_counts`) and writers.
 
@@ -20,6 +23,7 @@ import logging
 
 import numpy as np
 
+from catch_amd import _lib
 from catch_amd import engine
 from catch_amd import probe
 
@@ -54,12 +58,16 @@ class Analyzer:
         self.rc_too = rc_too
         self._covers = None
         self._sliding = None
+        self._windows = None
         self._window = (50, 25)
         self._scan_inputs = None
+        self._np_state = None
 
-    def _iter_target_genomes(self):
-        for i, genomes_from_group in enumerate(self.target_genomes):
-            for j, gnm in enumerate(genomes_from_group):
+    def _iter_target_genomes(self, groups=None):
+        """groups: only these groupings, in the order given (the rows of one
+        dataset of a report that several analyzers share; None = all)."""
+        for i in (range(len(self.target_genomes)) if groups is None else groups):
+            for j, gnm in enumerate(self.target_genomes[i]):
                 yield i, j, gnm, False
                 if self.rc_too:
                     yield i, j, gnm, True
@@ -97,8 +105,8 @@ class Analyzer:
           self.bp_covered[i][j][rc]   bases covered by at least one probe (:282-302)
           self._total_covered[i][j][rc]  sum of the ranges' lengths (:318-320)
           self.probe_map_counts[p]    sequences probe p maps to, forward strand (:255-258)
-        self.target_covers / self.sliding_coverage are fetched / computed on
-        first use (they need every range on the host)."""
+        self.target_covers is fetched on first use (it needs every range on the
+        host); self.sliding_coverage is computed on first use, on the device."""
         logger.info("Finding probe covers across target genomes")
         self.probe_map_counts = Counter()
         self.bp_covered, self._total_covered = {}, {}
@@ -106,12 +114,15 @@ class Analyzer:
             for d in (self.bp_covered, self._total_covered):
                 d.setdefault(i, {}).setdefault(j, {False: None, True: None})[rc] = 0
         self._covers = None
+        self._sliding = self._windows = None
         strs = [p.seq_str for p in self.probes]
         flat = self._flat_genomes()
         self._scan_inputs = None
         if not strs or not flat:
             return
         ctx = engine.default_context()
+        # (random anchors draw from np.random: _map_count_order replays the draws)
+        self._np_state = np.random.get_state()
         self._scan_inputs = probe.anchor_table(
             strs, self.mismatches, self.lcf_thres,
             min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k)
@@ -197,36 +208,108 @@ class Analyzer:
     def _compute_sliding_coverage_in_target_genomes(self, window_length,
                                                     window_stride):
         """:337-411: average depth in windows; keys are window middles.
-        Needs every range on the host: computed on first use of
-        self.sliding_coverage."""
+        Computed on first use of self.sliding_coverage or of its writer."""
         self._window = (window_length, window_stride)
-        self._sliding = None
+        self._sliding = self._windows = None
+
+    def _window_tables(self):
+        """Per strand (keys, values, win_off): the windows of flat genome g are
+        win_off[g]:win_off[g + 1], keys[w] the window's middle as the reference
+        reports it (:401-408) and values[w] its average depth.  One scan per
+        strand; the depth, its prefix sums and the window sums stay on the
+        device (Rows.window_depth), which returns an integer sum and a base
+        count per window: float(sum) / count is np.average of the reference's
+        uint16 slice (:409-410), whose sum is exact in float64."""
+        if self._windows is not None:
+            return self._windows
+        window_length, window_stride = self._window
+        flat = self._flat_genomes()
+        sizes = np.asarray([gnm.size(False) for _i, _j, gnm in flat], dtype=np.int64)
+        span_first = np.zeros(len(flat) + 1, dtype=np.int64)
+        np.cumsum([len(gnm.seqs) for _i, _j, gnm in flat], out=span_first[1:])
+        strands = (False, True) if self.rc_too else (False,)
+        device = {}
+        if self._scan_inputs is not None:
+            ctx = engine.default_context()
+            k, uniq, owner, ep, eo = self._scan_inputs
+            probes_dev = engine.Probes(ctx, uniq, owner, ep, eo, k)
+            try:
+                for rc in strands:
+                    targets, _owner, _off = self._strand_targets(ctx, flat, rc)
+                    try:
+                        rows = self._scan(ctx, probes_dev, targets)
+                        device[rc] = rows.window_depth(span_first, window_length,
+                                                       window_stride)
+                        rows.close()
+                    finally:
+                        targets.close()
+            finally:
+                probes_dev.close()
+        # the reported start of every window, for all genomes at once (:401-407)
+        per = -(-sizes // window_stride)
+        win_off = np.zeros(len(flat) + 1, dtype=np.int64)
+        np.cumsum(per, out=win_off[1:])
+        n = np.repeat(sizes, per)
+        start = (np.arange(win_off[-1], dtype=np.int64) - np.repeat(win_off[:-1], per)) * window_stride
+        start = np.where(start + window_length > n, n - window_length, start)
+        keys = start + (window_length / 2)
+        self._windows = {}
+        for rc in strands:
+            if rc in device:
+                sums, counts, off = device[rc]
+                assert np.array_equal(off, win_off)
+                values = sums.astype(np.float64) / counts
+            else:       # no probes: nothing is covered
+                values = np.zeros(keys.size, dtype=np.float64)
+            self._windows[rc] = (keys, values, win_off)
+        return self._windows
+
+    def _host_sliding_coverage(self):
+        """The same on the host from the fetched ranges, base by base and window
+        by window: the path the device computation is tested against
+        (CATCHHIP_ANALYSIS_HOST_WINDOWS=1, a test hook)."""
+        window_length, window_stride = self._window
+        sliding = {}
+        for i, j, gnm, rc in self._iter_target_genomes():
+            covers = self.target_covers[i][j][rc]
+            n = gnm.size(False)
+            diff = np.zeros(n + 1, dtype=np.int64)
+            if covers:
+                arr = np.asarray(covers, dtype=np.int64)
+                np.add.at(diff, arr[:, 0], 1)
+                np.add.at(diff, arr[:, 1], -1)
+            # the reference stores the depth as uint16
+            counts = np.cumsum(diff[:n]).astype(np.uint16)
+            out = {}
+            for window_start in np.arange(0, n, window_stride):
+                window_end = window_start + window_length
+                if window_end > n:
+                    window_end = n
+                    window_start = window_end - window_length
+                middle = window_start + (window_length / 2)
+                out[middle] = np.average(counts[window_start:window_end])
+            sliding.setdefault(i, {}).setdefault(
+                j, {False: None, True: None})[rc] = out
+        return sliding
+
+    @staticmethod
+    def _host_windows():
+        return _lib.test_env("CATCHHIP_ANALYSIS_HOST_WINDOWS", "0") not in ("", "0")
 
     @property
     def sliding_coverage(self):
         if self._sliding is None:
-            window_length, window_stride = self._window
+            if self._host_windows():
+                self._sliding = self._host_sliding_coverage()
+                return self._sliding
+            tables = self._window_tables()
             self._sliding = {}
-            for i, j, gnm, rc in self._iter_target_genomes():
-                covers = self.target_covers[i][j][rc]
-                n = gnm.size(False)
-                diff = np.zeros(n + 1, dtype=np.int64)
-                if covers:
-                    arr = np.asarray(covers, dtype=np.int64)
-                    np.add.at(diff, arr[:, 0], 1)
-                    np.add.at(diff, arr[:, 1], -1)
-                # the reference stores the depth as uint16
-                counts = np.cumsum(diff[:n]).astype(np.uint16)
-                out = {}
-                for window_start in np.arange(0, n, window_stride):
-                    window_end = window_start + window_length
-                    if window_end > n:
-                        window_end = n
-                        window_start = window_end - window_length
-                    middle = window_start + (window_length / 2)
-                    out[middle] = np.average(counts[window_start:window_end])
-                self._sliding.setdefault(i, {}).setdefault(
-                    j, {False: None, True: None})[rc] = out
+            for g, (i, j, _gnm) in enumerate(self._flat_genomes()):
+                for rc, (keys, values, win_off) in tables.items():
+                    lo, hi = win_off[g], win_off[g + 1]
+                    self._sliding.setdefault(i, {}).setdefault(
+                        j, {False: None, True: None})[rc] = dict(
+                            zip(keys[lo:hi].tolist(), values[lo:hi].tolist()))
         return self._sliding
 
     def run(self, window_length=50, window_stride=25):
@@ -241,25 +324,32 @@ class Analyzer:
         h = "%s, genome %d" % (self.target_genomes_names[i], j)
         return h + " (rc)" if rc else h
 
-    def write_data_matrix_as_tsv(self, fn):
-        data = [["Genome", "Num bases covered", "Frac bases covered",
-                 "Frac bases covered over unambig", "Average coverage/depth",
-                 "Average coverage/depth over unambig"]]
-        for i, j, gnm, rc in self._iter_target_genomes():
+    _TSV_HEADER = ["Genome", "Num bases covered", "Frac bases covered",
+                   "Frac bases covered over unambig", "Average coverage/depth",
+                   "Average coverage/depth over unambig"]
+
+    def _data_matrix_rows(self, groups=None):
+        data = []
+        for i, j, gnm, rc in self._iter_target_genomes(groups):
             bp_covered = self.bp_covered[i][j][rc]
             avg_all, avg_unambig = self.average_coverage[i][j][rc]
             data.append([self._row_header(i, j, rc), bp_covered,
                          float(bp_covered) / gnm.size(False),
                          float(bp_covered) / gnm.size(True),
                          avg_all, avg_unambig])
+        return data
+
+    def write_data_matrix_as_tsv(self, fn):
         with open(fn, "w") as f:
-            for row in data:
+            for row in [self._TSV_HEADER] + self._data_matrix_rows():
                 f.write("\t".join(str(entry) for entry in row) + "\n")
 
-    def _make_data_matrix_string(self):
-        data = [["Genome", "Num bases covered\n[over unambig]",
-                 "Average coverage/depth\n[over unambig]"]]
-        for i, j, gnm, rc in self._iter_target_genomes():
+    _TABLE_HEADER = ["Genome", "Num bases covered\n[over unambig]",
+                     "Average coverage/depth\n[over unambig]"]
+
+    def _make_data_matrix_string(self, groups=None):
+        data = [self._TABLE_HEADER] if groups is None else []
+        for i, j, gnm, rc in self._iter_target_genomes(groups):
             bp_covered = self.bp_covered[i][j][rc]
             frac_all = float(bp_covered) / gnm.size(False)
             frac_unambig = float(bp_covered) / gnm.size(True)
@@ -276,24 +366,96 @@ class Analyzer:
     def print_analysis(self):
         print("NUMBER OF PROBES: %d" % len(self.probes))
         print()
-        print(_table(self._make_data_matrix_string(),
-                     ["left", "right", "right"]))
+        print_table(self._make_data_matrix_string())
 
     def write_sliding_window_coverage(self, fn):
         with open(fn, "w") as f:
-            for i, j, _gnm, rc in self._iter_target_genomes():
+            self._write_sliding_rows(f)
+
+    def _write_sliding_rows(self, f, groups=None):
+        if self._host_windows():
+            for i, j, _gnm, rc in self._iter_target_genomes(groups):
                 header = self._row_header(i, j, rc)
                 cov = self.sliding_coverage[i][j][rc]
                 for pos in sorted(cov.keys()):
                     f.write("\t".join(str(x) for x in [header, pos, cov[pos]]) + "\n")
+            return
+        # Straight from the window tables, genome by genome.  A genome's keys
+        # ascend; the windows that stretch past its end share one key and one
+        # value (one dict entry in the reference): the last of a run is written.
+        tables = self._window_tables()
+        flat_index = {(i, j): g for g, (i, j, _gnm) in enumerate(self._flat_genomes())}
+        for i, j, _gnm, rc in self._iter_target_genomes(groups):
+            header = self._row_header(i, j, rc)
+            keys, values, win_off = tables[rc]
+            g = flat_index[(i, j)]
+            k, v = keys[win_off[g]:win_off[g + 1]], values[win_off[g]:win_off[g + 1]]
+            if not k.size:
+                continue
+            last = np.append(k[1:] != k[:-1], True)
+            f.write("".join("%s\t%s\t%s\n" % (header, pos, val) for pos, val in
+                            zip(k[last].tolist(), v[last].tolist())))
+
+    def _map_count_order(self):
+        """The probes that map somewhere (as indices into self.probes), in the
+        order the reference first meets them (:222-250: genomes and sequences
+        in order, inside a sequence by the position of the first accepted k-mer,
+        at one position in the order the k-mer map lists its entries) -- the
+        order of its probe_map_counts, which a Counter keeps.  One more scan of
+        the forward strand (catchhip_cover_scan_first_seen); per probe the
+        first sequence and the key inside it are picked on the device."""
+        if self._scan_inputs is None:
+            return []
+        strs = [p.seq_str for p in self.probes]
+        state = np.random.get_state()
+        np.random.set_state(self._np_state)
+        try:
+            k, uniq, owner, ep, eo, draws = probe.anchor_table(
+                strs, self.mismatches, self.lcf_thres, min_k=self.kmer_probe_map_k,
+                k=self.kmer_probe_map_k, with_draws=True)
+        finally:
+            np.random.set_state(state)
+        order = probe.anchor_order(self.probes, strs, uniq, ep, eo, draws, k)
+        ctx = engine.default_context()
+        probes_dev = engine.Probes(ctx, uniq, owner, ep, eo, k)
+        try:
+            targets, _owner, _off = self._strand_targets(ctx, self._flat_genomes(), False)
+            try:
+                rows = engine.Rows.scan_first_seen(
+                    ctx, probes_dev, targets, self.mismatches, self.lcf_thres,
+                    self.island_of_exact_match, 0, engine.SCAN_AUTO, order)
+                first_universe, first_key = rows.first_seen_per_set(len(strs))
+                rows.close()
+            finally:
+                targets.close()
+        finally:
+            probes_dev.close()
+        seen = np.flatnonzero(first_universe >= 0)
+        return seen[np.lexsort((first_key[seen], first_universe[seen]))].tolist()
+
+    def ordered_probe_map_counts(self):
+        """[(probe, sequences it maps to)] in the reference's order."""
+        return [(self.probes[pi], self.probe_map_counts[self.probes[pi]])
+                for pi in self._map_count_order()]
 
     def write_probe_map_counts(self, fn):
-        with open(fn, "w") as f:
-            f.write("\t".join(["Probe identifier", "Probe sequence",
-                               "Number sequences mapped to"]) + "\n")
-            for p, count in self.probe_map_counts.items():
-                ident = p.identifier() if hasattr(p, "identifier") else ""
-                f.write("\t".join(str(x) for x in [ident, p.seq_str, count]) + "\n")
+        write_probe_map_counts(self.ordered_probe_map_counts(), fn)
+
+
+def write_probe_map_counts(probe_map_counts, fn):
+    """probe_map_counts: (probe, count) pairs."""
+    with open(fn, "w") as f:
+        f.write("\t".join(["Probe identifier", "Probe sequence",
+                           "Number sequences mapped to"]) + "\n")
+        for p, count in probe_map_counts:
+            ident = p.identifier() if hasattr(p, "identifier") else ""
+            f.write("\t".join(str(x) for x in [ident, p.seq_str, count]) + "\n")
+
+
+def print_table(data):
+    """The report's table as the reference prints it (:531-533): its table
+    string ends in a newline, so print() leaves an empty line after it."""
+    print(_table(data, ["left", "right", "right"]) + "\n")
 
 
 def _table(data, col_justify):

@@ -636,6 +636,35 @@ class Rows:
             int(num_sets), _ptr(ps, c_i64p)))
         return tl[:ngenomes], ul[:ngenomes], ps[:num_sets]
 
+    def first_seen_per_set(self, num_sets):
+        """catchhip_rows_first_seen_per_set -> (first universe int32[num_sets] (-1: no rows), its first-seen
+        key uint64[num_sets]); rows from scan_first_seen."""
+        num_sets = int(num_sets)
+        un = np.full(max(num_sets, 1), -1, dtype=np.int32)
+        key = np.zeros(max(num_sets, 1), dtype=np.uint64)
+        check(self.ctx._L.catchhip_rows_first_seen_per_set(
+            self.ctx._h, self._h, num_sets, _ptr(un, c_i32p), _ptr(key, c_u64p)))
+        return un[:num_sets], key[:num_sets]
+
+    def window_depth(self, span_first, window_length, window_stride):
+        """catchhip_rows_window_depth: span s = universes [span_first[s], span_first[s + 1]) ->
+        (sums uint64[nwin], counts uint32[nwin], win_off int64[nspans + 1]): per window, in span order, the
+        sum of the 16-bit depth over its bases and their number; windows of span s are win_off[s]:win_off[s + 1]."""
+        sf = np.ascontiguousarray(span_first, dtype=np.int64)
+        nspans = max(int(sf.size) - 1, 0)
+        per_span = np.zeros(max(nspans, 1), dtype=np.int64)
+        fn = self.ctx._L.catchhip_rows_window_depth
+        check(fn(self.ctx._h, self._h, _ptr(sf, c_i64p) if sf.size else None, nspans, int(window_length),
+                 int(window_stride), _ptr(per_span, c_i64p), None, None, 0))
+        win_off = np.zeros(nspans + 1, dtype=np.int64)
+        np.cumsum(per_span[:nspans], out=win_off[1:])
+        nwin = int(win_off[-1])
+        sums = np.zeros(max(nwin, 1), dtype=np.uint64)
+        counts = np.zeros(max(nwin, 1), dtype=np.uint32)
+        check(fn(self.ctx._h, self._h, _ptr(sf, c_i64p) if sf.size else None, nspans, int(window_length),
+                 int(window_stride), _ptr(per_span, c_i64p), _ptr(sums, c_u64p), _ptr(counts, c_u32p), nwin))
+        return sums[:nwin], counts[:nwin], win_off
+
     def cover_check(self, num_sets, picks, universe_p=None):
         """catchhip_rows_cover_check: replays `picks` (set ids in pick order) over these rows with kernels that
         share nothing with the solvers -> dict(picks_without_gain, universes_short, bad_pick_ids, universe_bases,

@@ -75,21 +75,7 @@ class AdapterFilter(BaseFilter):
 
     # ------------------------------------------------------------------
     def _anchor_order(self, probes, strs, uniq, ep, eo, draws, k):
-        """For every anchor entry its rank among the entries of its k-mer, in
-        the order the reference's map lists them (probe.py:393-401 / :496-503
-        build a set of (Probe, pos) per k-mer; SharedKmerProbeMap.construct
-        :739-747 iterates it)."""
-        uidx = {s: i for i, s in enumerate(uniq)}
-        kmer_entries = {}
-        for i, pos in draws:
-            kmer_entries.setdefault(strs[i][pos:pos + k], set()).add(
-                (probes[i], pos))
-        rank = {}
-        for members in kmer_entries.values():
-            for r, (p, pos) in enumerate(members):
-                rank[(uidx[p.seq_str], pos)] = r
-        return np.fromiter((rank[e] for e in zip(ep.tolist(), eo.tolist())),
-                           dtype=np.uint32, count=len(ep))
+        return probe.anchor_order(probes, strs, uniq, ep, eo, draws, k)
 
     def _make_votes_across_target_genomes(self, probes, target_genomes):
         """[(A votes, B votes)] per input probe (:299-361)."""

@@ -103,6 +103,26 @@ def pigeonhole_kmer_length(probe_length, mismatches):
     return k
 
 
+def anchor_order(probes, strs, uniq, ep, eo, draws, k):
+    """For every anchor entry of anchor_table(..., with_draws=True) its rank
+    among the entries of its k-mer, in the order the reference's map lists
+    them (probe.py:393-401 / :496-503 build a set of (Probe, pos) per k-mer;
+    SharedKmerProbeMap.construct :739-747 iterates it): the same sets are
+    built from the caller's probe objects in the same insertion order, so the
+    interpreter yields the same order."""
+    uidx = {s: i for i, s in enumerate(uniq)}
+    kmer_entries = {}
+    for i, pos in draws:
+        kmer_entries.setdefault(strs[i][pos:pos + k], set()).add(
+            (probes[i], pos))
+    rank = {}
+    for members in kmer_entries.values():
+        for r, (p, pos) in enumerate(members):
+            rank[(uidx[p.seq_str], pos)] = r
+    return np.fromiter((rank[e] for e in zip(ep.tolist(), eo.tolist())),
+                       dtype=np.uint32, count=len(ep))
+
+
 def anchor_table(probe_strs, mismatches, lcf_thres, min_k=20, k=20,
                  num_kmers_per_probe=20, assume_unique=False,
                  with_draws=False):

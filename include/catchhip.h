@@ -729,6 +729,34 @@ int catchhip_rows_stats(catchhip_ctx *ctx, const catchhip_rows *rows,
                         int64_t *total_len, int64_t *union_len,
                         int64_t num_sets, int64_t *universes_per_set);
 
+/* Sliding-window depth of a row table without fetching it (csrc/analysis.hip; replaces the per-base loop and the
+ * per-window np.average of catch/coverage_analysis.py:336-413).  `rows` is a table from catchhip_cover_ranges (or any
+ * table that is not deferred) with one universe per sequence.  Span s is the run of universes [span_first[s],
+ * span_first[s + 1]): one genome, its chromosomes concatenated, so windows cross chromosome boundaries as in the
+ * reference.  span_first[0 .. nspans] must be non-decreasing within [0, universes of the table].
+ *   depth[pos] = rows whose [start, end) holds pos, modulo 2^16 (the reference stores it as uint16, :377)
+ *   windows of a span of n bases start at 0, stride, 2 stride, .. < n (:401); one with start + length > n becomes
+ *   [n - length, n) (:403-407), and when n < length numpy's slice rule makes that [max(0, 2n - length), n).
+ * span_windows[s] receives the number of windows of span s (ceil(n / stride); 0 for an empty span).  With sums ==
+ * counts == NULL that is all the call does (no device work): callers size their arrays with it.  Otherwise, for
+ * every window of every span in order, sums[] takes the integer sum of the depth over the window's bases and
+ * counts[] their number; capacity = room in both, in windows.  The windows past the end of a span repeat one
+ * window; all of them are written.  No float arithmetic happens on the device: the average is double(sum) / count
+ * on the host, which equals np.average of the uint16 slice (:409-410) because that sum is exact in float64.
+ * CATCHHIP_EINVAL: deferred rows, spans out of order or past the universes, window_length or window_stride < 1,
+ * capacity too small. */
+int catchhip_rows_window_depth(catchhip_ctx *ctx, const catchhip_rows *rows, const int64_t *span_first,
+                               int64_t nspans, int64_t window_length, int64_t window_stride,
+                               int64_t *span_windows, uint64_t *sums, uint32_t *counts, int64_t capacity);
+
+/* Where every set id < num_sets was seen first, on rows from catchhip_cover_scan_first_seen with one universe per
+ * sequence: first_universe[s] = the first universe set s has rows in (-1: none) and first_key[s] = the key of the
+ * first accepted seed there (catchhip_rows_fetch_first_seen).  Sorting the sets by (first_universe, first_key)
+ * gives the order in which catch/coverage_analysis.py:245-250 first meets each probe, i.e. the order of its
+ * probe_map_counts. */
+int catchhip_rows_first_seen_per_set(catchhip_ctx *ctx, const catchhip_rows *rows, int64_t num_sets,
+                                     int32_t *first_universe, uint64_t *first_key);
+
 /* Property checks of a set-cover solution by kernels independent of the solvers (csrc/check.hip), usable at any
  * scale: `picks` are set ids IN THE ORDER they were picked, `rows` the instance's row table (not a deferred one),
  * universe_p per universe or NULL (every universe fully covered).  out5[0] = picks that covered no new position
