@@ -322,6 +322,12 @@ extern "C" int catchhip_ctx_last_join_counters(catchhip_ctx *c, i64 *out4) {
     return 0;
 }
 
+extern "C" int catchhip_ctx_last_rows_direct(catchhip_ctx *c, i64 *out) {
+    ARG_CHECK(c != nullptr && out != nullptr);
+    *out = c->rows_direct;
+    return 0;
+}
+
 extern "C" int catchhip_ctx_last_seeds_dropped(catchhip_ctx *c, i64 *out) {
     ARG_CHECK(c != nullptr && out != nullptr);
     *out = c->seeds_dropped;

@@ -29,6 +29,9 @@ extern "C" int catchhip_setcover_filter(catchhip_ctx *ctx, const catchhip_probes
     if (universe_p)
         for (i32 u = 0; u < T->ngenomes && full; ++u) full = universe_p[u] == 1.0;
     const auto t_in = std::chrono::steady_clock::now();
+    ctx->rows_direct = 0;
+    // (tests: small instances through the synchronous branch below)
+    if (full && chip_test_env("CATCHHIP_FILTER_NO_DEFER")) full = false;
     if (full) {
         rc = chip_cover_scan_nosync(ctx, P, T, mismatches, lcf_thres, island, cover_extension, mode, &R);
         if (rc < 0) return rc;
@@ -50,11 +53,13 @@ extern "C" int catchhip_setcover_filter(catchhip_ctx *ctx, const catchhip_probes
     }
     const bool timing = getenv("CATCHHIP_TIMING") != nullptr;   // host wall time of the two halves (stderr)
     const auto t0 = std::chrono::steady_clock::now();
-    rc = catchhip_cover_scan(ctx, P, T, mismatches, lcf_thres, island, cover_extension, mode, &R, &nr);
+    // scan, then solve, and the rows never leave this call: they stay in the row build's bucketed form when the
+    // build allows it, and the solver that cannot read that form gets the SoA table made for it (chip_setcover_solve)
+    rc = chip_cover_scan_direct(ctx, P, T, mismatches, lcf_thres, island, cover_extension, mode, &R, &nr);
     if (rc) return rc;
     if (nrows) *nrows = nr;
     const auto t1 = std::chrono::steady_clock::now();
-    rc = catchhip_setcover_greedy(ctx, R, num_sets, ranks, universe_p, out_ids, n_out);
+    rc = chip_setcover_solve(ctx, R, num_sets, ranks, universe_p, out_ids, n_out);
     const auto t2 = std::chrono::steady_clock::now();
     (void)catchhip_rows_destroy(R);
     if (timing)

@@ -130,6 +130,7 @@ struct catchhip_ctx {
     i64 counters[8] = {};
     i64 ndf_counters[4] = {};      // last Hamming near-duplicate filter: probes, tables, pairs compared, edges
     i64 solver_counters[4] = {};   // row-parallel solver: records streamed, rows counted again, bitmap words read, owner words looked at
+    i64 rows_direct = 0;     // the last catchhip_setcover_filter solved from the bucketed records (catchhip_rows::rows4), no SoA table
     i64 seeds_dropped = 0;   // of counters[1]: work-list entries the seed look-up's anchor-pair filter left empty
     i64 join_counters[4] = {};     // last key-grouped join: hit positions, pairs verified, lane slots of wave-wide runs, tasks of cut runs
     i64 grid_counters[4] = {};     // last catchhip_setcover_grid: scans, derived tables, solves, rows of the e = 0 scan
@@ -158,6 +159,15 @@ int chip_cover_scan_nosync(catchhip_ctx *ctx, const catchhip_probes *P, const ca
 // deferred scan unusable (overflow, long rows): redo through the synchronous calls
 int chip_greedy_deferred(catchhip_ctx *ctx, catchhip_rows *R, i64 num_sets, const i64 *ranks, i64 *out_ids,
                          i64 *n_out, int *retry);
+// catchhip_cover_scan for a caller that solves at once (catchhip_setcover_filter): the rows may come back in
+// DIRECT form (catchhip_rows::rows4) -- the bucketed records of the row build, no SoA table
+int chip_cover_scan_direct(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, i32 mismatches,
+                           i32 lcf_thres, i32 island, i32 cover_extension, i32 mode, catchhip_rows **out, i64 *nrows);
+// direct rows -> the SoA table (set_id / univ / gs / ge), for the solvers that index four arrays; no-op on SoA rows
+int chip_rows_materialise(catchhip_ctx *ctx, catchhip_rows *R);
+// catchhip_setcover_greedy on rows of either form (materialises direct rows unless the row-parallel solver takes them)
+int chip_setcover_solve(catchhip_ctx *ctx, catchhip_rows *R, i64 num_sets, const i64 *ranks, const double *universe_p,
+                        i64 *out_ids, i64 *n_out);
 
 struct catchhip_targets {
     catchhip_ctx *ctx = nullptr;
@@ -261,6 +271,17 @@ struct catchhip_rows {
     // the first round's gains of a full-coverage solve, which then needs no count launch of its own; gain0_n = 0: not there
     DevBuf<u32> gain0;
     u32 gain0_n = 0;
+    // DIRECT form (chip_cover_scan_direct; rows4.p != null, the four SoA arrays are empty): the row build's bucket-grouped
+    // records {.x start, .y end, .z universe, .w bucket} as bucket_merge left them.  Bucket b owns the slots from
+    // bstart[b]; its mcnt[b] merged rows sit at the front of them, in start order, and the stale records behind them
+    // keep .w == b -- slot i is a row iff i - bstart[rows4[i].w] < mcnt[rows4[i].w].  slots = the slots to look at
+    // (== n when nothing merged: then every slot is a row and nobody tests).  rstart = exclusive scan of mcnt (the
+    // row numbers of the SoA form).  The set of bucket b is bucket_set[b], or b itself when bucket_set is null.
+    DevBuf<uint4> rows4;
+    DevBuf<u32> bstart, mcnt, rstart;
+    i64 slots = 0;
+    u32 nb = 0;
+    const i32 *bucket_set = nullptr;   // (the probes' array: they outlive the filter call the rows live in)
 };
 
 // ---- timing helpers -----------------------------------------------------

@@ -15,6 +15,16 @@
 // emit kernel produce the final table.  The whole build is stream-ordered; the
 // host synchronises once, to learn the number of rows.
 //
+// When the rows go straight to the row-parallel solver (catchhip_setcover_filter,
+// synchronous branch) the emit kernel is not launched: the bucket-grouped records ARE
+// the table ("direct rows", catchhip_rows::rows4 in internal.h).  What the solver relies
+// on: every producer files a record under its bucket's number (.w), the merge walk
+// writes a bucket's mcnt[b] merged rows to its FIRST slots in start order and leaves the
+// stale records behind them in place with .w == b -- so slot i is a row iff
+// i - bstart[S[i].w] < mcnt[S[i].w], and when nothing merged every slot is one.  The emit
+// kernel then only serves the callers that keep the table (catchhip_cover_scan) and the
+// solvers that index four arrays (chip_rows_materialise).
+//
 // Buckets larger than BK_SMALL go to a workgroup-wide instance of the same
 // code (BK_BIG); beyond that the caller falls back to the radix-sort build.
 

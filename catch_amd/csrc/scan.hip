@@ -2131,7 +2131,7 @@ first_seen_spread_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__
 static int cover_scan_impl(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T,
                            i32 mismatches, i32 lcf_thres, i32 island, i32 cover_extension, i32 mode, bool merge,
                            catchhip_rows **out, i64 *nrows, bool want_first = false,
-                           const u32 *anchor_order = nullptr) {
+                           const u32 *anchor_order = nullptr, bool allow_direct = false) {
     ARG_CHECK(ctx && P && T && out && cover_extension >= 0);
     PoolScope pool_scope(ctx);
     ARG_CHECK(P->ctx == ctx && T->ctx == ctx);
@@ -2186,16 +2186,30 @@ static int cover_scan_impl(catchhip_ctx *ctx, const catchhip_probes *P, const ca
         if (!O.overflow) {
             R->n = O.nrows;
             R->lmax = O.lmax;
-            if ((rc = R->set_id.alloc(R->n))) break;
-            if ((rc = R->univ.alloc(R->n))) break;
-            if ((rc = R->gs.alloc(R->n))) break;
-            if ((rc = R->ge.alloc(R->n))) break;
+            // Direct form: the caller solves at once and the row-parallel solver reads the bucketed records where they
+            // lie -- the buffers move over, nothing is copied per row.  Merged rows under a bucket -> set table keep the
+            // SoA form: kept conservative (a bucket is one set there too, so the slot rule would hold; not measured).
+            const bool direct = allow_direct && merge && !want_first && R->n &&
+                                (O.nhits == O.nrows || P->bucket_identity) && !chip_test_env("CATCHHIP_ROWS_SOA");
+            if (direct) {
+                R->rows4.swap(O.B.S); R->bstart.swap(O.B.bstart); R->mcnt.swap(O.B.mcnt); R->rstart.swap(O.B.rstart);
+                R->slots = O.nhits;
+                R->nb = O.B.nb;
+                R->bucket_set = P->bucket_identity ? (const i32 *)nullptr : (const i32 *)P->bucket_set.p;
+            } else {
+                if ((rc = R->set_id.alloc(R->n))) break;
+                if ((rc = R->univ.alloc(R->n))) break;
+                if ((rc = R->gs.alloc(R->n))) break;
+                if ((rc = R->ge.alloc(R->n))) break;
+            }
             if (R->n) {
-                hipLaunchKernelGGL(rows_emit_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream,
-                                   (const u32 *)O.B.rstart.p, O.B.nb, (const u32 *)O.B.bstart.p,
-                                   P->bucket_identity ? (const i32 *)nullptr : (const i32 *)P->bucket_set.p, (const uint4 *)O.B.S.p, (u32)R->n, (const u32 *)nullptr, R->set_id.p, R->univ.p,
-                                   R->gs.p, R->ge.p, (const u32 *)nullptr, O.nhits == O.nrows ? 1 : 0);
-                tm.launch();
+                if (!direct) {
+                    hipLaunchKernelGGL(rows_emit_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream,
+                                       (const u32 *)O.B.rstart.p, O.B.nb, (const u32 *)O.B.bstart.p,
+                                       P->bucket_identity ? (const i32 *)nullptr : (const i32 *)P->bucket_set.p, (const uint4 *)O.B.S.p, (u32)R->n, (const u32 *)nullptr, R->set_id.p, R->univ.p,
+                                       R->gs.p, R->ge.p, (const u32 *)nullptr, O.nhits == O.nrows ? 1 : 0);
+                    tm.launch();
+                }
                 if (merge && O.B.bsum.p && O.B.bsum.n >= (size_t)O.B.nb && P->max_set_id < ((i64)1 << 31)) {
                     // the sets' total row lengths: what the first round of a full-coverage solve would count
                     const u32 ng = (u32)std::max<i64>(P->max_set_id + 1, (i64)(P->bucket_identity ? O.B.nb : 0));
@@ -2280,6 +2294,39 @@ extern "C" int catchhip_cover_scan(catchhip_ctx *ctx, const catchhip_probes *P, 
                                    i32 mismatches, i32 lcf_thres, i32 island, i32 cover_extension, i32 mode,
                                    catchhip_rows **out, i64 *nrows) {
     return cover_scan_impl(ctx, P, T, mismatches, lcf_thres, island, cover_extension, mode, true, out, nrows);
+}
+
+int chip_cover_scan_direct(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, i32 mismatches,
+                           i32 lcf_thres, i32 island, i32 cover_extension, i32 mode, catchhip_rows **out, i64 *nrows) {
+    return cover_scan_impl(ctx, P, T, mismatches, lcf_thres, island, cover_extension, mode, true, out, nrows, false,
+                           nullptr, true);
+}
+
+// the SoA table from direct rows: what the row build's emit launch would have written
+int chip_rows_materialise(catchhip_ctx *ctx, catchhip_rows *R) {
+    if (!R->rows4.p) return 0;
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    TRY(R->set_id.alloc(R->n));
+    TRY(R->univ.alloc(R->n));
+    TRY(R->gs.alloc(R->n));
+    TRY(R->ge.alloc(R->n));
+    // (the emit launch belongs to the row build: PHASE_ROWS is extended on purpose, at the price of one event
+    // synchronisation on this fallback path)
+    PhaseTimer tm(ctx, PHASE_ROWS, true);
+    if (R->n) {
+        tm.launch();
+        hipLaunchKernelGGL(rows_emit_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream,
+                           (const u32 *)R->rstart.p, R->nb, (const u32 *)R->bstart.p, R->bucket_set,
+                           (const uint4 *)R->rows4.p, (u32)R->n, (const u32 *)nullptr, R->set_id.p, R->univ.p, R->gs.p,
+                           R->ge.p, (const u32 *)nullptr, R->slots == R->n ? 1 : 0);
+    }
+    HIP_TRY(hipGetLastError());
+    tm.finish_add();
+    // (the records go back to the pool: whatever takes them is ordered behind the launch on the context's stream)
+    R->rows4.release(); R->bstart.release(); R->mcnt.release(); R->rstart.release();
+    R->slots = 0; R->nb = 0; R->bucket_set = nullptr;
+    return 0;
 }
 
 extern "C" int catchhip_cover_scan_first_seen(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T,

@@ -977,6 +977,15 @@ int chip_greedy_deferred(catchhip_ctx *ctx, catchhip_rows *R, i64 num_sets, cons
 
 extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *R, i64 num_sets, const i64 *ranks,
                                         const double *universe_p, i64 *out_ids, i64 *n_out) {
+    // (rows a caller holds are always in SoA form: nothing of *R changes)
+    ARG_CHECK(R && !R->rows4.p);
+    return chip_setcover_solve(ctx, const_cast<catchhip_rows *>(R), num_sets, ranks, universe_p, out_ids, n_out);
+}
+
+// Chooses the solver.  Direct rows (catchhip_rows::rows4) go to the row-parallel solver as they are; every other
+// solver indexes the four SoA arrays, which are made from the records first.
+int chip_setcover_solve(catchhip_ctx *ctx, catchhip_rows *R, i64 num_sets, const i64 *ranks, const double *universe_p,
+                        i64 *out_ids, i64 *n_out) {
     ARG_CHECK(ctx && R && n_out && num_sets >= 0 && R->ctx == ctx);
     PoolScope pool_scope(ctx);
     *n_out = 0;
@@ -985,7 +994,7 @@ extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *
     if (num_sets == 0 || R->n == 0) return 0;  // no universe has anything to cover
     ARG_CHECK(out_ids != nullptr);
     if (num_sets >= (i64)ID_MASK) { chip_set_error("setcover: more than 2^32-2 sets not supported"); return CATCHHIP_EINVAL; }
-    if (R->n >= ((i64)1 << 31)) { chip_set_error("setcover: too many rows"); return CATCHHIP_EINVAL; }
+    if (R->n >= ((i64)1 << 31) || R->slots >= ((i64)1 << 31)) { chip_set_error("setcover: too many rows"); return CATCHHIP_EINVAL; }
     HIP_TRY(hipSetDevice(ctx->device));
     const u32 nrows = (u32)R->n, nsets = (u32)num_sets, nuniv = (u32)R->ngenomes;
     hipStream_t s = ctx->stream;
@@ -1016,15 +1025,22 @@ extern "C" int catchhip_setcover_greedy(catchhip_ctx *ctx, const catchhip_rows *
     // round).  So: 2^18 rows.  (Smaller instances never get here through the fused filter: below ~11 Mbases of
     // targets it queues scan and solve without a synchronisation, chip_greedy_deferred.)
     const i64 flat_min_rows = chip_test_env_int("CATCHHIP_FLAT_MIN_ROWS", (i64)1 << 18);
-    if (batched && R->lmax <= 257 && (i64)nrows >= flat_min_rows && nsets <= GR_MAX_SETS)
+    if (batched && R->lmax <= 257 && (i64)nrows >= flat_min_rows && nsets <= GR_MAX_SETS) {
+        if (R->rows4.p) ctx->rows_direct = 1;   // (reset by catchhip_setcover_filter alone: the figure is its last call's)
         return greedy_flat(ctx, R, nsets, ranks ? h_rank.data() : nullptr, nrank, out_ids, n_out);
+    }
+    const bool flat_partial = !batched && universe_p && R->lmax <= 257 && nsets <= GR_MAX_SETS && !sequential &&
+                              !chip_test_env("CATCHHIP_PARTIAL_SEQUENTIAL");
+    if (!flat_partial) TRY(chip_rows_materialise(ctx, R));   // long rows, a small or a huge instance, the sequential hooks
     if (batched) return greedy_frontier(ctx, R, nsets, ranks ? h_rank.data() : nullptr, nrank, out_ids, n_out, &no_retry);
     // Partial coverage (some universe_p < 1) with rows of at most 257 bases: frontier rounds of the
     // row-parallel kernels with the universe test (setcover_flat.inc, "PARTIAL") whatever the size --
     // the one-workgroup solvers below take 3.9 ms per pick on S4's largest group (54.6 s for S4 under
     // -c 0.9 against 0.17 s under -c 1.0)
-    if (universe_p && R->lmax <= 257 && nsets <= GR_MAX_SETS && !sequential && !chip_test_env("CATCHHIP_PARTIAL_SEQUENTIAL"))
+    if (flat_partial) {
+        if (R->rows4.p) ctx->rows_direct = 1;
         return greedy_flat(ctx, R, nsets, ranks ? h_rank.data() : nullptr, nrank, out_ids, n_out, universe_p);
+    }
 
     DevBuf<u32> set_ptr, flag, idx, tmp, seg_univ, seg_set, row_seg, set_seg_ptr, usize, can, left, rank,
         picked, picks;

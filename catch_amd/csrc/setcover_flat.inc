@@ -87,9 +87,12 @@ struct FlatArgs {
     // (S4's union instance: 27.8 M rows on the fullest XCD for 21.8 M on average).  Striped tiles: tile x to XCD x.
     const u32 *xcd_tile, *xcd_ntiles;
     u32 *tile_cnt[2];               // alive rows of every tile in buffer 0 / 1
-    const u32 *set_ptr;             // the row table in set order (as built by the scan): rows of set s =
-    const u32 *row_gs, *row_ge;     //   [set_ptr[s], set_ptr[s + 1]), their ranges and universes
+    // NOTE: always [set_ptr[s], set_end[s]) -- with direct rows set_ptr[s + 1] is NOT the end of set s (gaps, no sentinel)
+    const u32 *set_ptr, *set_end;   // the row table in set order (as built by the scan): rows of set s =
+    const u32 *row_gs, *row_ge;     //   [set_ptr[s], set_end[s]), their ranges and universes (SoA rows: set_end = set_ptr + 1)
     const i32 *row_univ;
+    const uint4 *rows4;             // direct rows (catchhip_rows::rows4): {start, end, universe, bucket} records instead of
+                                    //   the three arrays; row indices are slots, a set's rows lie at the front of its bucket
     const u32 *rank;
     u32 *usize;
     u32 *acc[2];                    // gains, accumulated by gr_count of round r in acc[r & 1]
@@ -136,6 +139,16 @@ struct FlatArgs {
     unsigned long long inv;         // ~0: bm holds the COVERED positions (starts all zero: nothing to build), 0: the uncovered ones
 };
 
+// where the set-up kernels (segment flags, the partition by tile) read the (set, start)-ordered rows
+struct GrRowSrc {
+    const i32 *set, *univ;          // SoA rows
+    const u32 *gs, *ge;
+    const uint4 *rows4;             // direct rows: {start, end, universe, bucket}; null: SoA
+    const u32 *bstart, *mcnt;       //   merged buckets: where a bucket's rows begin and how many there are; null: every slot is a row
+    const i32 *bucket_set;          //   set of a bucket; null: the bucket itself
+    u32 n;                          // rows (SoA) / slots (direct)
+};
+
 // inclusive sum over the 64 lanes by DPP moves (no LDS permutes): Kogge-Stone inside the 16-lane rows (row_shr 1, 2, 4, 8,
 // zero fill), then lane 15 of rows 0 / 2 added to rows 1 / 3 (row_bcast:15) and lane 31 to rows 2 and 3 (row_bcast:31)
 __device__ __forceinline__ u32 wave_incl_scan_dpp(u32 v) {
@@ -160,6 +173,18 @@ __device__ __forceinline__ u32 wave_segsum(u32 v, u32 key, bool *tail) {
     *tail = lane == 63 || ((heads >> (lane + 1)) & 1ull);
     const u32 incl = wave_incl_scan_dpp(v);
     return incl - (u32)__shfl((int)(incl - v), (int)start, WAVE);      // minus the sum of the lanes before the run
+}
+
+// row r of the set-ordered table, in either form (the branch is uniform over the launch)
+__device__ __forceinline__ void gr_row_range(const FlatArgs &a, u32 r, u32 &x, u32 &e) {
+    if (a.rows4) { const uint2 q = *(const uint2 *)(a.rows4 + r); x = q.x; e = q.y; }
+    else { x = a.row_gs[r]; e = a.row_ge[r]; }
+}
+__device__ __forceinline__ u32 gr_row_univ(const FlatArgs &a, u32 r) { return a.rows4 ? a.rows4[r].z : (u32)a.row_univ[r]; }
+__device__ __forceinline__ u32 gr_row_popcount(const FlatArgs &a, u32 r) {
+    u32 x, e;
+    gr_row_range(a, r, x, e);
+    return range_popcount((const u64 *)a.bm, x, e);
 }
 
 // global start of a record of tile t (contiguous tiles: t << shift; striped: 4-kbase stripes dealt round robin)
@@ -533,10 +558,10 @@ __device__ __forceinline__ bool gr_passes(const FlatArgs &a, const u32 *acc, u32
     const unsigned long long key = ((unsigned long long)acc[sa] << ID_BITS) | (unsigned long long)(ID_MASK - sa);
     bool ok = true;
     for (u32 r = r0 + first; r < r1; r += stride) {
-        const u32 u = (u32)a.row_univ[r];
-        if (r > r0 && (u32)a.row_univ[r - 1] == u) continue;
+        const u32 u = gr_row_univ(a, r);
+        if (r > r0 && gr_row_univ(a, r - 1) == u) continue;
         u32 c = 0;
-        for (u32 j = r; j < r1 && (u32)a.row_univ[j] == u; ++j) c += range_popcount((const u64 *)a.bm, a.row_gs[j], a.row_ge[j]);
+        for (u32 j = r; j < r1 && gr_row_univ(a, j) == u; ++j) c += gr_row_popcount(a, j);
         if (c && !(key >= a.uT[u] || key >= a.uM[u])) ok = false;
     }
     return ok;
@@ -559,7 +584,7 @@ gr_verdict_kernel(FlatArgs a, u32 round) {
         while (todo) {
             const u32 sa = base + (u32)__ffsll((long long)todo) - 1u;
             todo &= todo - 1ull;
-            const u32 r0 = a.set_ptr[sa], r1 = a.set_ptr[sa + 1];
+            const u32 r0 = a.set_ptr[sa], r1 = a.set_end[sa];
             if (__ballot(!gr_passes(a, acc, sa, r0, r1, lane, 64u)) && lane == 0) a.lost[sa] = tag;
         }
     }
@@ -714,7 +739,8 @@ gr_apply_kernel(FlatArgs a, u32 round) {
         // the rows of an accepted set leave the universe
         auto cover_rows = [&](u32 r0, u32 r1, u32 first, u32 stride) {
             for (u32 r = r0 + first; r < r1; r += stride) {
-                const u32 x = a.row_gs[r], e = a.row_ge[r];
+                u32 x, e;
+                gr_row_range(a, r, x, e);
                 const u32 w0 = x >> 6, nwd = ((e - 1) >> 6) - w0 + 1;
                 const u64 m0 = ~0ull << (x & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
                 // The accepted sets of a round share no word in which they hold uncovered bits, so a
@@ -736,7 +762,7 @@ gr_apply_kernel(FlatArgs a, u32 round) {
                         if (PARTIAL) cleared += (u32)__popcll(v[t] & m);      // (partial coverage keeps the uncovered positions)
                     }
                 }
-                if (PARTIAL && cleared) atomicSub(&a.need[a.row_univ[r]], (i32)cleared);
+                if (PARTIAL && cleared) atomicSub(&a.need[gr_row_univ(a, r)], (i32)cleared);
             }
         };
         if (PARTIAL) {
@@ -744,7 +770,7 @@ gr_apply_kernel(FlatArgs a, u32 round) {
             // candidates of up to 256 rows take one wavefront each (four at a time per workgroup) ...
             for (u32 q = threadIdx.x >> 6; q < nwon; q += GA_THREADS / 64) {
                 const u32 sa = s_won[q];
-                const u32 r0 = a.set_ptr[sa], r1 = a.set_ptr[sa + 1];
+                const u32 r0 = a.set_ptr[sa], r1 = a.set_end[sa];
                 if (r1 - r0 > 256u) continue;
                 if (__ballot(!passes(sa, r0, r1, lane, 64u))) continue;   // stays alive; another round
                 if (lane == 0) record_pick(sa);
@@ -755,7 +781,7 @@ gr_apply_kernel(FlatArgs a, u32 round) {
         // ... and the others (partial coverage: the long ones) the whole workgroup
         for (u32 q = 0; q < nwon; ++q) {
             const u32 sa = s_won[q];
-            const u32 r0 = a.set_ptr[sa], r1 = a.set_ptr[sa + 1];
+            const u32 r0 = a.set_ptr[sa], r1 = a.set_end[sa];
             if (PARTIAL) {
                 if (r1 - r0 <= 256u) continue;
                 if (threadIdx.x == 0) s_pass = 1u;
@@ -782,9 +808,10 @@ gr_cover_kernel(FlatArgs a, u32 round) {
     const u32 first = st->nwon, last = st->npicks, par = round & 1;      // the picks of this round
     for (u32 q = first + blockIdx.x; q < last; q += gridDim.x) {
         const u32 sa = a.picks[q];
-        const u32 r0 = a.set_ptr[sa], r1 = a.set_ptr[sa + 1];
+        const u32 r0 = a.set_ptr[sa], r1 = a.set_end[sa];
         for (u32 r = r0 + threadIdx.x; r < r1; r += GA_THREADS) {
-            const u32 x = a.row_gs[r], e = a.row_ge[r];
+            u32 x, e;
+            gr_row_range(a, r, x, e);
             const u32 w0 = x >> 6, nwd = ((e - 1) >> 6) - w0 + 1;
             const u64 m0 = ~0ull << (x & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
             // The accepted sets of a round share no word in which they hold uncovered bits, so a row's own bits are
@@ -811,12 +838,33 @@ gr_cover_kernel(FlatArgs a, u32 round) {
 // multi-row segments: largest (set, universe) element count -> st->smax, cflag[s] = 1 for a set that
 // holds several rows in one universe
 __global__ void __launch_bounds__(256)
-gr_seg_flag_kernel(const i32 *__restrict__ row_set, const i32 *__restrict__ row_univ, const u32 *__restrict__ gs,
-                   const u32 *__restrict__ ge, u32 nrows, u32 *__restrict__ cflag, GreedyState *__restrict__ st) {
+gr_seg_flag_kernel(GrRowSrc src, u32 *__restrict__ cflag, GreedyState *__restrict__ st) {
     __shared__ u32 s_max[4];
     u32 best = 0;
+    const i32 *__restrict__ row_set = src.set, *__restrict__ row_univ = src.univ;
+    const u32 *__restrict__ gs = src.gs, *__restrict__ ge = src.ge;
+    const u32 nrows = src.n;
     // (grid-stride: one atomic on the shared maximum per workgroup, not per wavefront of rows)
     for (u32 r = blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += gridDim.x * blockDim.x) {
+        if (src.rows4) {
+            // direct rows: a bucket is a set, and the slot before a row's is a row of its bucket or another bucket's slot
+            const uint4 q = src.rows4[r];
+            const u32 end = src.mcnt ? src.bstart[q.w] + src.mcnt[q.w] : nrows;
+            if (r >= end) continue;                     // a stale record behind the bucket's merged rows
+            bool head = r == 0;
+            if (!head) { const uint4 pq = src.rows4[r - 1]; head = pq.w != q.w || pq.z != q.z; }
+            if (head) {
+                u32 tot = 0, j = r;
+                for (; j < end; ++j) {
+                    const uint4 qj = src.rows4[j];
+                    if (qj.w != q.w || qj.z != q.z) break;
+                    tot += qj.y - qj.x;
+                }
+                if (j > r + 1) cflag[src.bucket_set ? (u32)src.bucket_set[q.w] : q.w] = 1u;
+                best = tot > best ? tot : best;
+            }
+            continue;
+        }
         if (r == 0 || row_set[r - 1] != row_set[r] || row_univ[r - 1] != row_univ[r]) {
             u32 tot = 0, j = r;
             for (; j < nrows && row_set[j] == row_set[r] && row_univ[j] == row_univ[r]; ++j) tot += ge[j] - gs[j];
@@ -861,13 +909,13 @@ gr_fixup_kernel(FlatArgs a, u32 round) {
     const u32 lane = threadIdx.x & 63;
     for (u32 i = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < ncs; i += (gridDim.x * blockDim.x) >> 6) {
         const u32 s = a.cset[i];
-        const u32 r0 = a.set_ptr[s], r1 = a.set_ptr[s + 1];
+        const u32 r0 = a.set_ptr[s], r1 = a.set_end[s];
         u32 tot = 0;
         for (u32 r = r0 + lane; r < r1; r += 64) {
-            const u32 u = (u32)a.row_univ[r];
-            if (r > r0 && (u32)a.row_univ[r - 1] == u) continue;
+            const u32 u = gr_row_univ(a, r);
+            if (r > r0 && gr_row_univ(a, r - 1) == u) continue;
             u32 c = 0;
-            for (u32 j = r; j < r1 && (u32)a.row_univ[j] == u; ++j) c += range_popcount((const u64 *)a.bm, a.row_gs[j], a.row_ge[j]);
+            for (u32 j = r; j < r1 && gr_row_univ(a, j) == u; ++j) c += gr_row_popcount(a, j);
             const i32 nd = a.need[u];
             if (nd > 0) tot += c < (u32)nd ? c : (u32)nd;
         }
@@ -1010,6 +1058,29 @@ gr_finish_kernel(FlatArgs a, u32 round) {
 // (set, start)-ordered row table by tile.  The record (see GR_KEY_*) is formed
 // on the way -- a separate key pass + a generic radix pass read and wrote every
 // row once more (S4: 1.9 + 1.2 ms of key and histogram traffic per step).
+//
+// The rows come in one of two forms (GrRowSrc): the SoA table of a catchhip_rows, or the row build's bucketed
+// 16-byte records where they lie (direct rows, catchhip_rows::rows4).  There the index space is the SLOTS of the
+// record array: when buckets merged, a bucket's rows sit at the front of its slots and the stale records behind
+// them are skipped (slot i of bucket b is a row iff i < bstart[b] + mcnt[b]); when nothing merged every slot is a
+// row, mcnt is null and nothing is tested.  Slot order is (set, start) order, so the partition stays stable.
+//
+// The histogram is [ntiles][blocks] words, tile-major (256 digit rows until round 7, whatever the tile count: with
+// S4's 16-30 tiles nine tenths of what was written and scanned were zeros).  The LDS arrays stay 256 wide.
+// row (slot) idx: false when there is none; its range, set and universe otherwise
+__device__ __forceinline__ bool gr_src_row(const GrRowSrc &src, u32 idx, u32 &x, u32 &e, u32 &sid, u32 &univ) {
+    if (idx >= src.n) return false;
+    if (src.rows4) {
+        const uint4 q = src.rows4[idx];
+        if (src.mcnt && idx >= src.bstart[q.w] + src.mcnt[q.w]) return false;
+        x = q.x; e = q.y; univ = q.z;
+        sid = src.bucket_set ? (u32)src.bucket_set[q.w] : q.w;
+        return true;
+    }
+    x = src.gs[idx]; e = src.ge[idx]; sid = (u32)src.set[idx];
+    univ = src.univ ? (u32)src.univ[idx] : 0u;
+    return true;
+}
 #define GT_THREADS 256
 #define GT_ROUNDS 16
 #define GT_TILE (GT_THREADS * GT_ROUNDS)
@@ -1017,7 +1088,7 @@ gr_finish_kernel(FlatArgs a, u32 round) {
 __device__ __forceinline__ u32 gr_tile_of(u32 x, int tile_shift) { return tile_shift < 0 ? (x >> 12) & 7u : x >> tile_shift; }
 
 __global__ void __launch_bounds__(GT_THREADS)
-gr_tile_hist_kernel(const u32 *__restrict__ gs, u32 nrows, int tile_shift, u32 *__restrict__ hist, u32 nblocks) {
+gr_tile_hist_kernel(GrRowSrc src, int tile_shift, u32 ntiles, u32 *__restrict__ hist, u32 nblocks) {
     __shared__ u32 h[256];
     h[threadIdx.x] = 0;
     __syncthreads();
@@ -1025,29 +1096,33 @@ gr_tile_hist_kernel(const u32 *__restrict__ gs, u32 nrows, int tile_shift, u32 *
 #pragma unroll 4
     for (int r = 0; r < GT_ROUNDS; ++r) {
         const u32 idx = base + r * GT_THREADS + threadIdx.x;
-        if (idx < nrows) atomicAdd(&h[gr_tile_of(gs[idx], tile_shift)], 1u);
+        if (idx >= src.n) continue;
+        if (!src.rows4) atomicAdd(&h[gr_tile_of(src.gs[idx], tile_shift)], 1u);
+        else if (!src.mcnt) atomicAdd(&h[gr_tile_of(src.rows4[idx].x, tile_shift)], 1u);
+        else {
+            const uint4 q = src.rows4[idx];
+            if (idx < src.bstart[q.w] + src.mcnt[q.w]) atomicAdd(&h[gr_tile_of(q.x, tile_shift)], 1u);
+        }
     }
     __syncthreads();
-    hist[(size_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
+    if (threadIdx.x < ntiles) hist[(size_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
 }
 
 __global__ void __launch_bounds__(GT_THREADS)
-gr_tile_scatter_kernel(const i32 *__restrict__ row_set, const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 nrows,
-                       int tile_shift, const u32 *__restrict__ hist_scanned, u32 nblocks,
-                       unsigned long long *__restrict__ keys,
-                       const i32 *__restrict__ row_univ, const u32 *__restrict__ cflag, u32 *__restrict__ unis) {
+gr_tile_scatter_kernel(GrRowSrc src, int tile_shift, u32 ntiles, const u32 *__restrict__ hist_scanned, u32 nblocks,
+                       unsigned long long *__restrict__ keys, const u32 *__restrict__ cflag, u32 *__restrict__ unis) {
     __shared__ u32 wave_cnt[GT_THREADS / 64][256];
     __shared__ u32 base[256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    base[tid] = hist_scanned[(size_t)tid * nblocks + blockIdx.x];
+    const u32 nrows = src.n;
+    base[tid] = (u32)tid < ntiles ? hist_scanned[(size_t)tid * nblocks + blockIdx.x] : 0u;
     const u32 tile0 = blockIdx.x * GT_TILE;
     const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     for (int r = 0; r < GT_ROUNDS; ++r) {
         if (tile0 + (u32)r * GT_THREADS >= nrows) break;   // uniform
         const u32 idx = tile0 + (u32)r * GT_THREADS + tid;
-        const bool valid = idx < nrows;
-        const u32 x = valid ? gs[idx] : 0u, e = valid ? ge[idx] : 1u;
-        const u32 sid = valid ? (u32)row_set[idx] : 0u;
+        u32 x = 0u, e = 1u, sid = 0u, univ = 0u;
+        const bool valid = gr_src_row(src, idx, x, e, sid, univ);
         const u32 digit = valid ? gr_tile_of(x, tile_shift) : 0u;
 #pragma unroll
         for (int w = 0; w < GT_THREADS / 64; ++w) wave_cnt[w][tid] = 0;
@@ -1078,13 +1153,13 @@ gr_tile_scatter_kernel(const i32 *__restrict__ row_set, const u32 *__restrict__ 
             const u32 pos = wave_cnt[wave][digit] + rank_in_wave;
             const u32 nwd = ((e - 1) >> 6) - (x >> 6) + 1;
             keys[pos] = GR_KEY_MAKE(gr_loc(x, tile_shift), e - x, (1u << nwd) - 1u, sid);
-            if (unis) unis[pos] = (u32)row_univ[idx] | (cflag[sid] ? 0x80000000u : 0u);   // partial coverage
+            if (unis) unis[pos] = univ | (cflag[sid] ? 0x80000000u : 0u);   // partial coverage
         }
         __syncthreads();
     }
 }
 
-// first record of every tile (the scanned histogram is digit-major: tile t starts where its first block does),
+// first record of every tile (the scanned histogram is tile-major: tile t starts where its first block does),
 // and the tiles' sizes
 __global__ void __launch_bounds__(256)
 gr_tile_ptr_kernel(const u32 *__restrict__ hist_scanned, u32 nblocks, u32 nrows, u32 ntiles, u32 *__restrict__ tile_ptr,
@@ -1206,6 +1281,17 @@ gr_bitmap_kernel(FlatArgs a) {
 // round.  FlatSolve holds the state so that the rounds can be driven from
 // outside (setcover_sharded.inc puts an all-reduce between the launches).
 __global__ void gr_fill_one_kernel(u32 *p, u32 v) { *p = v; }
+// direct rows: the slots of every set's rows from its bucket (set_ptr / set_end arrive zeroed: a set without a bucket is empty)
+__global__ void __launch_bounds__(256)
+gr_set_range_kernel(const u32 *__restrict__ bstart, const u32 *__restrict__ mcnt, const i32 *__restrict__ bucket_set, u32 nb,
+                    u32 nsets, u32 *__restrict__ set_ptr, u32 *__restrict__ set_end) {
+    const u32 b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nb) return;
+    const u32 s = bucket_set ? (u32)bucket_set[b] : b;
+    if (s >= nsets) return;
+    set_ptr[s] = bstart[b];
+    set_end[s] = bstart[b] + mcnt[b];
+}
 
 struct FlatSolve {
     catchhip_ctx *ctx = nullptr;
@@ -1227,6 +1313,17 @@ struct FlatSolve {
         hipStream_t s = ctx->stream;
         const u32 nrows = (u32)R->n, nuniv = (u32)R->ngenomes;
         const size_t nwords = (size_t)(R->total / 64 + 2);
+        // where the set-up kernels read the rows: the SoA table, or the row build's records in place (direct rows;
+        // the validity test of merged buckets only when something merged)
+        const bool direct = R->rows4.p != nullptr;
+        GrRowSrc src;
+        src.set = (const i32 *)R->set_id.p; src.univ = (const i32 *)R->univ.p;
+        src.gs = (const u32 *)R->gs.p; src.ge = (const u32 *)R->ge.p;
+        src.rows4 = (const uint4 *)R->rows4.p;
+        const bool gaps = direct && R->slots != R->n;
+        src.bstart = gaps ? (const u32 *)R->bstart.p : nullptr; src.mcnt = gaps ? (const u32 *)R->mcnt.p : nullptr;
+        src.bucket_set = direct ? R->bucket_set : nullptr;
+        src.n = direct ? (u32)R->slots : nrows;
         // a multiple of 8, at least 8: workgroup b serves the tiles of XCD b % 8
         // workgroups per CU: the walk is persistent (for_each_step deals the steps out), so what is resident at once -- 4 x 8
         // wavefronts per CU -- is enough, and the ~20 short launches at the end of every solve start half as many (K2 rounds of
@@ -1273,13 +1370,16 @@ struct FlatSolve {
         const size_t nchg = stats_dirty ? nwords / 32 + 4 : 0;
         const size_t o_chg0 = take(4 * nchg), o_chg1 = take(4 * nchg);
         const size_t o_cflag = take(partial ? 4 * ((size_t)nsets + 1) : 0), o_ufinal = take(partial ? 4 * (size_t)nuniv + 4 : 0);
+        // direct rows: set_ptr / set_end are filled from the buckets and must start zeroed (a set without a bucket is empty)
+        const size_t o_dsptr = take(direct ? 4 * ((size_t)nsets + 1) : 0), o_send = take(direct ? 4 * ((size_t)nsets + 1) : 0);
         const size_t zero_bytes = off;
         const bool list_alive = !partial && !sharded;
         const u32 alive_seg = (u32)div_up((i64)std::max<u32>(nsets, 1), (i64)gblocks);
         const size_t o_al0 = take(list_alive ? 4 * (size_t)alive_seg * gblocks : 0), o_al1 = take(list_alive ? 4 * (size_t)alive_seg * gblocks : 0),
                      o_alc0 = take(list_alive ? 4 * (size_t)gblocks : 0), o_alc1 = take(list_alive ? 4 * (size_t)gblocks : 0);
         const size_t o_usize = take(4 * (size_t)std::max<u32>(nuniv, 1)), o_picks = take(4 * (size_t)nsets),
-                     o_keys = take(8 * (size_t)nsets), o_tptr = take(4 * 258), o_sptr = take(4 * ((size_t)nsets + 1)),
+                     o_keys = take(8 * (size_t)nsets), o_tptr = take(4 * 258),
+                     o_sptr = direct ? o_dsptr : take(4 * ((size_t)nsets + 1)),
                      o_xt = take(4 * 8 * GR_MAXTX), o_xn = take(4 * 8);
         const size_t o_need = take(partial ? 4 * (size_t)nuniv + 4 : 0), o_uT = take(partial ? 8 * (size_t)nuniv + 8 : 0),
                      o_uM = take(partial ? 8 * (size_t)nuniv + 8 : 0), o_cpos = take(partial ? 4 * ((size_t)nsets + 1) : 0),
@@ -1315,9 +1415,8 @@ struct FlatSolve {
             HIP_TRY(hipMemcpyAsync(d_p.p, h_p, sizeof(double) * nuniv, hipMemcpyHostToDevice, s));
             // sets that hold several rows in one universe, and the largest (set, universe) count
             DevBuf<u32> tmp2;
-            hipLaunchKernelGGL(gr_seg_flag_kernel, dim3((unsigned)std::max<i64>(1, std::min<i64>(div_up((i64)nrows, 256), (i64)ctx->num_cus * 16))), dim3(256), 0, s,   // (a shard without rows still takes part)
-                               (const i32 *)R->set_id.p, (const i32 *)R->univ.p, (const u32 *)R->gs.p, (const u32 *)R->ge.p,
-                               nrows, (u32 *)(A + o_cflag), (GreedyState *)(A + o_st));
+            hipLaunchKernelGGL(gr_seg_flag_kernel, dim3((unsigned)std::max<i64>(1, std::min<i64>(div_up((i64)src.n, 256), (i64)ctx->num_cus * 16))), dim3(256), 0, s,   // (a shard without rows still takes part)
+                               src, (u32 *)(A + o_cflag), (GreedyState *)(A + o_st));
             TRY(chip_exclusive_scan_u32(ctx, (const u32 *)(A + o_cflag), (u32 *)(A + o_cpos), (i64)nsets, tmp2));
             hipLaunchKernelGGL(gr_cset_kernel, dim3((unsigned)div_up((i64)nsets, 256)), dim3(256), 0, s,
                                (const u32 *)(A + o_cflag), (const u32 *)(A + o_cpos), nsets, (u32 *)(A + o_cset));
@@ -1329,8 +1428,19 @@ struct FlatSolve {
         fa.xcd_tile = (const u32 *)(A + o_xt); fa.xcd_ntiles = (const u32 *)(A + o_xn);
         fa.set_ptr = (const u32 *)(A + o_sptr);
         fa.row_gs = (const u32 *)R->gs.p; fa.row_ge = (const u32 *)R->ge.p; fa.row_univ = (const i32 *)R->univ.p;
-        hipLaunchKernelGGL(set_ptr_kernel, dim3((unsigned)div_up((i64)nsets + 1, 256)), dim3(256), 0, s, (const i32 *)R->set_id.p,
-                           nrows, nsets, (u32 *)(A + o_sptr));
+        fa.rows4 = (const uint4 *)R->rows4.p;
+        if (direct) {
+            // the buckets know where their sets' rows lie: nothing is searched in the rows
+            fa.set_end = (const u32 *)(A + o_send);
+            if (R->nb)
+                hipLaunchKernelGGL(gr_set_range_kernel, dim3((unsigned)div_up((i64)R->nb, 256)), dim3(256), 0, s,
+                                   (const u32 *)R->bstart.p, (const u32 *)R->mcnt.p, R->bucket_set, R->nb, nsets,
+                                   (u32 *)(A + o_sptr), (u32 *)(A + o_send));
+        } else {
+            fa.set_end = fa.set_ptr + 1;
+            hipLaunchKernelGGL(set_ptr_kernel, dim3((unsigned)div_up((i64)nsets + 1, 256)), dim3(256), 0, s, (const i32 *)R->set_id.p,
+                               nrows, nsets, (u32 *)(A + o_sptr));
+        }
         fa.rank = (const u32 *)(A + o_rank); fa.usize = (u32 *)(A + o_usize);
         fa.acc[0] = (u32 *)(A + o_acc0); fa.acc[1] = (u32 *)(A + o_acc1);
         fa.claimed = (u32 *)(A + o_claimed); fa.lost = (u32 *)(A + o_lost);
@@ -1346,15 +1456,13 @@ struct FlatSolve {
         fa.nchg = (u32)nchg; fa.tile_shift = tile_shift;
         // rows into (tile, set, start) order: one stable partition by tile
         if (nrows) {
-            const u32 nblk = (u32)div_up(nrows, GT_TILE);
+            const u32 nblk = (u32)div_up(src.n, GT_TILE);
             DevBuf<u32> hist, tmp;
-            TRY(hist.alloc((size_t)256 * nblk));
-            hipLaunchKernelGGL(gr_tile_hist_kernel, dim3(nblk), dim3(GT_THREADS), 0, s, (const u32 *)R->gs.p, nrows, tile_shift,
-                               hist.p, nblk);
-            TRY(chip_exclusive_scan_u32(ctx, hist.p, hist.p, (i64)256 * nblk, tmp));
-            hipLaunchKernelGGL(gr_tile_scatter_kernel, dim3(nblk), dim3(GT_THREADS), 0, s, (const i32 *)R->set_id.p,
-                               (const u32 *)R->gs.p, (const u32 *)R->ge.p, nrows, tile_shift, (const u32 *)hist.p, nblk,
-                               (unsigned long long *)skey.p, (const i32 *)R->univ.p,
+            TRY(hist.alloc((size_t)ntiles * nblk));
+            hipLaunchKernelGGL(gr_tile_hist_kernel, dim3(nblk), dim3(GT_THREADS), 0, s, src, tile_shift, ntiles, hist.p, nblk);
+            TRY(chip_exclusive_scan_u32(ctx, hist.p, hist.p, (i64)ntiles * nblk, tmp));
+            hipLaunchKernelGGL(gr_tile_scatter_kernel, dim3(nblk), dim3(GT_THREADS), 0, s, src, tile_shift, ntiles,
+                               (const u32 *)hist.p, nblk, (unsigned long long *)skey.p,
                                partial ? (const u32 *)(A + o_cflag) : (const u32 *)nullptr, partial ? suni.p : (u32 *)nullptr);
             hipLaunchKernelGGL(gr_tile_ptr_kernel, dim3(1), dim3(256), 0, s, (const u32 *)hist.p, nblk, nrows, ntiles,
                                (u32 *)(A + o_tptr), fa.tile_cnt[0]);

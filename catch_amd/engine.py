@@ -212,6 +212,8 @@ class Context:
         dropped = np.zeros(1, dtype=np.int64)
         check(self._L.catchhip_ctx_last_seeds_dropped(self._h, _ptr(dropped, c_i64p)))
         d["seeds_dropped"] = int(dropped[0])   # of seed_hits: left without a seed by the look-up's filter
+        check(self._L.catchhip_ctx_last_rows_direct(self._h, _ptr(dropped, c_i64p)))
+        d["rows_direct"] = int(dropped[0])     # 1: the last setcover_filter solved from the bucketed records
         jc = np.zeros(4, dtype=np.int64)
         check(self._L.catchhip_ctx_last_join_counters(self._h, _ptr(jc, c_i64p)))
         d.update(zip(("join_hit_positions", "join_pairs", "join_lane_slots", "join_cut_tasks"), (int(x) for x in jc)))

@@ -94,6 +94,9 @@ int catchhip_ctx_last_join_counters(catchhip_ctx *ctx, int64_t *out4);
  * seed), or no second anchor of the probe matches (more than m mismatches).
  * They cost the verification 4 bytes each and none of its gathers. */
 int catchhip_ctx_last_seeds_dropped(catchhip_ctx *ctx, int64_t *out);
+/* 1 when the last catchhip_setcover_filter on this context solved from the row
+ * build's bucketed records (no SoA row table was written), 0 otherwise. */
+int catchhip_ctx_last_rows_direct(catchhip_ctx *ctx, int64_t *out);
 /* Work of the row-parallel frontier solver in the last solve that used it (zeros
  * otherwise), 4 values: row records streamed by the count launches (alive rows,
  * summed over the rounds); of those, rows whose bitmap words were read again
