@@ -32,19 +32,6 @@
 
 #include "internal.h"
 
-struct catchhip_candidates {
-    catchhip_ctx *ctx = nullptr;
-    const catchhip_targets *T = nullptr;   // borrowed: must outlive this object
-    i32 L = 0;
-    i64 ncand = 0, nuniq = 0;
-    DevBuf<u32> upos;   // global start of every unique candidate, first-occurrence order
-    DevBuf<u32> mult;   // how many candidates equal each unique one (valid until a near-duplicate filter ran)
-    bool grouped = false;   // the targets carry groups: duplicates are only removed inside a group
-    i32 ngroups = 0;
-    DevBuf<u32> ugrp;   // group of every unique candidate (non-decreasing)
-    bool filtered = false;   // a near-duplicate filter replaced the list (multiplicity order, kept ones only)
-};
-
 #define CAND_NONE 0xffffffffu
 
 __device__ __forceinline__ u32 cand_find_segment(const u32 *__restrict__ off, u32 n, u32 x) {
@@ -424,6 +411,38 @@ extern "C" int catchhip_candidates_fetch(catchhip_ctx *ctx, const catchhip_candi
         if (id < 0 || id >= C->nuniq) { chip_set_error("candidates_fetch: id out of range"); return CATCHHIP_ERANK; }
         global_start[i] = h[(size_t)id];
     }
+    return 0;
+}
+
+// a filter that is a function of the candidate alone (prefilter.hip): the flagged candidates stay, in their order,
+// with their multiplicities and groups -- what the filter would have left had it run before the de-duplication
+int chip_candidates_keep_flagged(catchhip_ctx *ctx, catchhip_candidates *C, DevBuf<u32> &flag, i64 *nkept) {
+    hipStream_t s = ctx->stream;
+    const u32 n = (u32)C->nuniq;
+    DevBuf<u32> at, tmp, pos, mult, grp;
+    HIP_TRY(hipMemsetAsync(flag.p + n, 0, sizeof(u32), s));
+    TRY(cand_scan(ctx, flag, at, (i64)n + 1, tmp));
+    u32 nk = 0;
+    TRY(cand_read_u32(ctx, at.p + n, &nk));
+    const dim3 grid((unsigned)div_up((i64)n, 256)), block(256);
+    TRY(pos.alloc((size_t)nk + 1));
+    TRY(mult.alloc((size_t)nk + 1));
+    hipLaunchKernelGGL(cand_compact_kernel, grid, block, 0, s, (const u32 *)C->upos.p, (const u32 *)flag.p,
+                       (const u32 *)at.p, n, pos.p);
+    hipLaunchKernelGGL(cand_compact_kernel, grid, block, 0, s, (const u32 *)C->mult.p, (const u32 *)flag.p,
+                       (const u32 *)at.p, n, mult.p);
+    if (C->grouped) {
+        TRY(grp.alloc((size_t)nk + 1));
+        hipLaunchKernelGGL(cand_compact_kernel, grid, block, 0, s, (const u32 *)C->ugrp.p, (const u32 *)flag.p,
+                           (const u32 *)at.p, n, grp.p);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));     // (the old lists go back to the pool below)
+    C->upos.swap(pos);
+    C->mult.swap(mult);
+    if (C->grouped) C->ugrp.swap(grp);
+    C->nuniq = nk;
+    if (nkept) *nkept = nk;
     return 0;
 }
 

@@ -284,6 +284,23 @@ struct catchhip_rows {
     const i32 *bucket_set = nullptr;   // (the probes' array: they outlive the filter call the rows live in)
 };
 
+// unique candidate probes of a targets object (candidates.hip; the poly(A) pre-filter of prefilter.hip edits the list)
+struct catchhip_candidates {
+    catchhip_ctx *ctx = nullptr;
+    const catchhip_targets *T = nullptr;   // borrowed: must outlive this object
+    i32 L = 0;
+    i64 ncand = 0, nuniq = 0;
+    DevBuf<u32> upos;   // global start of every unique candidate, first-occurrence order
+    DevBuf<u32> mult;   // how many candidates equal each unique one (valid until a near-duplicate filter ran)
+    bool grouped = false;   // the targets carry groups: duplicates are only removed inside a group
+    i32 ngroups = 0;
+    DevBuf<u32> ugrp;   // group of every unique candidate (non-decreasing)
+    bool filtered = false;   // a near-duplicate filter replaced the list (multiplicity order, kept ones only)
+};
+// flag[0..n) (device, 0 / 1; n + 1 words allocated): the unique list becomes the flagged candidates, order kept --
+// upos, mult and (grouped) ugrp compacted, nuniq updated (candidates.hip: cand_scan + cand_compact_kernel)
+int chip_candidates_keep_flagged(catchhip_ctx *ctx, catchhip_candidates *C, DevBuf<u32> &flag, i64 *nkept);
+
 // ---- timing helpers -----------------------------------------------------
 struct PhaseTimer {
     catchhip_ctx *c;

@@ -7,15 +7,19 @@ group of target genomes (bin/design.py:91-99), one Genome per record.  Filter
 list as bin/design.py:296-340 builds it: exact duplicate filter (or a
 near-duplicate filter with --filter-with-lsh-hamming / --filter-with-lsh-
 minhash), then the set cover filter; --cluster-and-design-separately clusters
-the input sequences first and designs per cluster (:387-411); --add-adapters
-appends the adapter filter (:345-365).  Options outside the accelerated path
-(reverse complements, N expansion, poly-A / FASTA filters, custom hybridization
-functions) are not offered.  --print-analysis and the three --write-...
+the input sequences first and designs per cluster (:387-411).  The optional
+filters stand where bin/design.py:255-385 puts them: --filter-from-fasta and
+--filter-polya before the duplicate filter, --add-adapters, --expand-n and
+--add-reverse-complements after the set cover, which --skip-set-cover leaves
+out; --limit-target-genomes[-randomly-with-replacement] cut the input down
+right after it is read (:101-112).  Custom hybridization functions and
+download: labels are not offered.  --print-analysis and the three --write-...
 options run the coverage analysis of the designed probes (bin/design.py:417-442).
 """
 import argparse
 import logging
 import os
+import random
 import sys
 
 from catch_amd.filter import duplicate_filter, near_duplicate_filter
@@ -93,6 +97,28 @@ def parse_args(argv=None, args_type="basic"):
                    default=prof["fragments"],
                    help="cluster fragments of this length instead of whole "
                         "sequences")
+    # bin/design.py:660-742
+    p.add_argument("--filter-from-fasta",
+                   help="keep only the candidate probes that are a sequence of "
+                        "this FASTA file (records whose header contains "
+                        "'reverse complement' do not count), in the file's order")
+    p.add_argument("--skip-set-cover", dest="skip_set_cover", action="store_true",
+                   help="leave the set cover filter out")
+    p.add_argument("--filter-polya", nargs=2, type=int,
+                   help="<X> <Y>: drop candidate probes with a stretch of X or "
+                        "more 'A' bases, tolerating up to Y mismatches (likewise 'T')")
+    p.add_argument("--add-reverse-complements", dest="add_reverse_complements",
+                   action="store_true",
+                   help="add the reverse complement of each probe to the output")
+    p.add_argument("--expand-n", nargs="?", type=int, default=None, const=3,
+                   help="replace 'N' bases by real bases, combinatorially; with "
+                        "INT, expand at most INT randomly chosen N per probe and "
+                        "replace the others by random bases")
+    p.add_argument("--limit-target-genomes", type=int,
+                   help="use only the first LIMIT_TARGET_GENOMES genomes of "
+                        "every dataset")
+    p.add_argument("--limit-target-genomes-randomly-with-replacement", type=int,
+                   help="draw this many genomes of every dataset, with replacement")
     p.add_argument("--add-adapters", action="store_true",
                    help="add PCR adapters to both ends of every probe")
     p.add_argument("--adapter-a", nargs=2,
@@ -137,6 +163,19 @@ def main(args):
                          "and --adapter-b, but --add-adapters is required to "
                          "add adapter sequences onto the ends of probes"))
     genomes_grouped = [seq_io.read_genomes_from_fasta(fn) for fn in args.dataset]
+    # bin/design.py:101-112: before anything else draws from `random`
+    if (args.limit_target_genomes and
+            args.limit_target_genomes_randomly_with_replacement):
+        raise Exception(("Cannot --limit-target-genomes and "
+                         "--limit-target-genomes-randomly-with-replacement at "
+                         "the same time"))
+    elif args.limit_target_genomes:
+        genomes_grouped = [genomes[:args.limit_target_genomes]
+                           for genomes in genomes_grouped]
+    elif args.limit_target_genomes_randomly_with_replacement:
+        k = args.limit_target_genomes_randomly_with_replacement
+        genomes_grouped = [random.choices(genomes, k=k)
+                           for genomes in genomes_grouped]
 
     # bin/design.py:180-205, :232: argument checks and the k-mer length each
     # consumer of the probe map uses (20 / 20 / 10 unless given)
@@ -154,6 +193,27 @@ def main(args):
                            "--kmer-probe-map-k below it", args.probe_length)
         k_scf, k_af, k_analyzer = 20, 20, 10
     filters = []
+    if args.filter_from_fasta:      # bin/design.py:261-264
+        from catch_amd.filter import fasta_filter
+        filters.append(fasta_filter.FastaFilter(args.filter_from_fasta,
+                                                skip_reverse_complements=True))
+    if args.filter_polya:           # bin/design.py:268-284
+        from catch_amd.filter import polya_filter
+        polya_length, polya_mismatches = args.filter_polya
+        if polya_length > args.probe_length:
+            logger.warning(("Length of poly(A) stretch to filter (%d) is "
+                            "greater than PROBE_LENGTH (%d), which is usually "
+                            "undesirable"), polya_length, args.probe_length)
+        if polya_length < 10:
+            logger.warning(("Length of poly(A) stretch to filter (%d) is "
+                            "short, and may lead to many probes being "
+                            "filtered"), polya_length)
+        if polya_mismatches > 10:
+            logger.warning(("Number of mismatches to tolerate when searching "
+                            "for poly(A) stretches (%d) is high, and may "
+                            "lead to many probes being filtered"),
+                           polya_mismatches)
+        filters.append(polya_filter.PolyAFilter(polya_length, polya_mismatches))
     if (args.filter_with_lsh_hamming is not None and
             args.filter_with_lsh_minhash is not None):
         raise Exception("Cannot use both --filter-with-lsh-hamming "
@@ -195,13 +255,24 @@ def main(args):
             mismatches=args.mismatches, lcf_thres=lcf_thres,
             island_of_exact_match=args.island_of_exact_match,
             kmer_probe_map_k=k_af))
+    if args.expand_n is not None:           # bin/design.py:370-373
+        from catch_amd.filter import n_expansion_filter
+        filters.append(n_expansion_filter.NExpansionFilter(
+            limit_n_expansion_randomly=args.expand_n))
+    if args.add_reverse_complements:        # bin/design.py:378-380
+        from catch_amd.filter import reverse_complement_filter
+        filters.append(reverse_complement_filter.ReverseComplementFilter())
+    merge_after = scf
+    if args.skip_set_cover:                 # bin/design.py:383-393
+        merge_after = filters[filters.index(scf) - 1]
+        filters.remove(scf)
 
     pb = probe_designer.ProbeDesigner(
         genomes_grouped, filters, probe_length=args.probe_length,
         probe_stride=args.probe_stride, allow_small_seqs=args.small_seq_min,
         seq_length_to_skip=args.small_seq_skip,
         cluster_threshold=args.cluster_and_design_separately,
-        cluster_merge_after=(scf if args.cluster_and_design_separately
+        cluster_merge_after=(merge_after if args.cluster_and_design_separately
                              else None),
         cluster_method=(args.cluster_and_design_separately_method
                         if args.cluster_and_design_separately else None),
@@ -214,9 +285,8 @@ def main(args):
     if (args.print_analysis or args.write_analysis_to_tsv or
             args.write_sliding_window_coverage or
             args.write_probe_map_counts_to_tsv):
-        # bin/design.py:417-442; no reverse-complement probes are added by this
-        # CLI, so the reverse strands are not analysed (rc_too follows
-        # --add-reverse-complements there)
+        # bin/design.py:417-442; the reverse strands are analysed when reverse-
+        # complement probes were added (rc_too follows --add-reverse-complements)
         from catch_amd import coverage_analysis
         analyzer = coverage_analysis.Analyzer(
             pb.final_probes, args.mismatches, lcf_thres, genomes_grouped,
@@ -224,7 +294,7 @@ def main(args):
             island_of_exact_match=args.island_of_exact_match,
             cover_extension=args.cover_extension,
             kmer_probe_map_k=k_analyzer,
-            rc_too=False)
+            rc_too=args.add_reverse_complements)
         analyzer.run()
         if args.write_analysis_to_tsv:
             analyzer.write_data_matrix_as_tsv(args.write_analysis_to_tsv)

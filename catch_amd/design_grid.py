@@ -24,7 +24,9 @@ logger = logging.getLogger("catch_amd.design_grid")
 
 # catch_amd.design options that a pooled design does not take: they couple the
 # datasets (identification, avoided genomes, clustering), need a second probe
-# model (the tolerant options), or belong after pooling (adapters, analyses)
+# model (the tolerant options), belong after pooling (adapters, analyses, N
+# expansion, reverse complements), or are not part of a grid (a FASTA filter,
+# no set cover, limited input)
 _REFUSED = (
     ("identify", "-i/--identify"),
     ("avoid_genomes", "--avoid-genomes"),
@@ -41,6 +43,13 @@ _REFUSED = (
     ("write_analysis_to_tsv", "--write-analysis-to-tsv"),
     ("write_sliding_window_coverage", "--write-sliding-window-coverage"),
     ("write_probe_map_counts_to_tsv", "--write-probe-map-counts-to-tsv"),
+    ("expand_n", "--expand-n"),
+    ("add_reverse_complements", "--add-reverse-complements"),
+    ("filter_from_fasta", "--filter-from-fasta"),
+    ("skip_set_cover", "--skip-set-cover"),
+    ("limit_target_genomes", "--limit-target-genomes"),
+    ("limit_target_genomes_randomly_with_replacement",
+     "--limit-target-genomes-randomly-with-replacement"),
 )
 
 
@@ -69,6 +78,9 @@ def parse_args(argv=None):
     p.add_argument("--filter-with-lsh-minhash", type=float,
                    help="Jaccard-distance threshold of the MinHash "
                         "near-duplicate filter")
+    p.add_argument("--filter-polya", nargs=2, type=int,
+                   help="<X> <Y>: drop candidate probes with a stretch of X or "
+                        "more 'A' bases, tolerating up to Y mismatches (likewise 'T')")
     p.add_argument("--small-seq-skip", type=int)
     p.add_argument("--small-seq-min", type=int)
     p.add_argument("--kmer-probe-map-k", type=int)
@@ -90,6 +102,12 @@ def parse_args(argv=None):
     p.add_argument("--write-analysis-to-tsv", help=S)
     p.add_argument("--write-sliding-window-coverage", help=S)
     p.add_argument("--write-probe-map-counts-to-tsv", help=S)
+    p.add_argument("--expand-n", nargs="?", type=int, default=None, const=3, help=S)
+    p.add_argument("--add-reverse-complements", action="store_true", help=S)
+    p.add_argument("--filter-from-fasta", help=S)
+    p.add_argument("--skip-set-cover", action="store_true", help=S)
+    p.add_argument("--limit-target-genomes", type=int, help=S)
+    p.add_argument("--limit-target-genomes-randomly-with-replacement", type=int, help=S)
     # the grid values are given with --grid-*: the single-value options are refused
     p.add_argument("-m", "--mismatches", type=int, help=S)
     p.add_argument("-e", "--cover-extension", type=int, help=S)
@@ -101,7 +119,8 @@ def parse_args(argv=None):
 def check_args(args, error):
     """Refuses what a grid does not take; checks names and grid values."""
     for attr, flag in _REFUSED:
-        if getattr(args, attr, None):
+        value = getattr(args, attr, None)
+        if value or (attr == "expand_n" and value is not None):     # (--expand-n 0 is given, too)
             error("%s is not supported by a grid design: a pooled design designs "
                   "each dataset on its own, and this option either couples the "
                   "datasets or belongs after pooling" % flag)
@@ -138,7 +157,7 @@ def main(args):
         coverage=args.coverage, filter_with_lsh_hamming=args.filter_with_lsh_hamming,
         filter_with_lsh_minhash=args.filter_with_lsh_minhash,
         small_seq_skip=args.small_seq_skip, small_seq_min=args.small_seq_min,
-        kmer_probe_map_k=args.kmer_probe_map_k)
+        kmer_probe_map_k=args.kmer_probe_map_k, filter_polya=args.filter_polya)
     os.makedirs(args.output_dir, exist_ok=True)
     counts = []
     for di, name in enumerate(args.names):

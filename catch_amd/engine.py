@@ -481,6 +481,22 @@ class Candidates:
             self.ctx._h, self._h, idp, n, _ptr(out, c_i64p)))
         return out[:n]
 
+    def drop_polya(self, length, mismatches, min_exact=6):
+        """catchhip_candidates_drop_polya: the unique candidates without those
+        the poly(A) filter drops, order, multiplicities and groups kept."""
+        nk = ctypes.c_int64(0)
+        check(self.ctx._L.catchhip_candidates_drop_polya(
+            self.ctx._h, self._h, int(length), int(mismatches), int(min_exact),
+            ctypes.byref(nk)))
+        self.n = nk.value
+
+    def multiplicities(self):
+        """How many candidates equal every unique one (before a near-duplicate filter)."""
+        out = np.zeros(max(self.n, 1), dtype=np.uint32)
+        check(self.ctx._L.catchhip_candidates_multiplicities(
+            self.ctx._h, self._h, _ptr(out, c_u32p)))
+        return out[:self.n]
+
     def ndf_hamming(self, positions, dist_thres):
         """catchhip_candidates_ndf_hamming: the list becomes the candidates the
         Hamming near-duplicate filter keeps, in its priority order."""

@@ -13,8 +13,10 @@ from catch_amd import genome
 from catch_amd import probe
 from catch_amd.filter import candidate_probes
 from catch_amd.filter.duplicate_filter import DuplicateFilter
+from catch_amd.filter.fasta_filter import FastaFilter
 from catch_amd.filter.near_duplicate_filter import (
     NearDuplicateFilterWithHammingDistance, NearDuplicateFilterWithMinHash)
+from catch_amd.filter.polya_filter import PolyAFilter
 from catch_amd.filter.set_cover_filter import SetCoverFilter
 from catch_amd.utils import cluster
 
@@ -207,14 +209,15 @@ class ProbeDesigner:
         return candidates, self._pass_through_filters(candidates, genomes, filters)
 
     def _design_on_strings(self, genomes, filters):
-        """[DuplicateFilter | near-duplicate filter, SetCoverFilter] -- the
-        filter lists bin/design.py:296-340 builds -- on plain strings:
-        candidates are sliced, de-duplicated (dict, or the LSH filter on the
-        device) and handed to the set cover filter without a Probe object per
-        candidate (a design over 8,000 genomes spent 0.85 of its 1.0 s building
-        them); only the selected probes become objects."""
-        first, scf = filters
-        mode = self._device_front_end_mode(genomes, first, scf)
+        """[pre-filters ..., DuplicateFilter | near-duplicate filter,
+        SetCoverFilter] -- the filter lists bin/design.py:255-340 builds, the
+        pre-filters being FastaFilter and PolyAFilter -- on plain strings:
+        candidates are sliced, filtered, de-duplicated (dict, or the LSH filter
+        on the device) and handed to the set cover filter without a Probe object
+        per candidate (a design over 8,000 genomes spent 0.85 of its 1.0 s
+        building them); only the selected probes become objects."""
+        *pre_filters, first, scf = filters
+        mode = self._device_front_end_mode(genomes, first, scf, pre_filters)
         if mode is not None:
             self._candidate_strs = None
             self._candidate_genomes = genomes
@@ -222,7 +225,8 @@ class ProbeDesigner:
                    else scf._filter_genomes_device_union)
             chosen = run(genomes, self.probe_length, self.probe_stride,
                          self.seq_length_to_skip,
-                         None if type(first) is DuplicateFilter else first)
+                         None if type(first) is DuplicateFilter else first,
+                         pre_filters=tuple(pre_filters))
             return [[probe.Probe.from_str(s) for s in grp] for grp in chosen]
         cand = []
         for grp in genomes:
@@ -234,7 +238,9 @@ class ProbeDesigner:
                 logger.warning("There are no candidate probes for a grouping "
                                "of genomes")
             cand.append(c)
-        self._candidate_strs = cand
+        self._candidate_strs = cand      # (candidate_probes: the unfiltered ones, as in the reference)
+        for f in pre_filters:            # filter after filter, each over the groups in order (BaseFilter.filter)
+            cand = [f._filter_strs(c) for c in cand]
         if type(first) is DuplicateFilter:
             uniq = [list(dict.fromkeys(c)) for c in cand]
         elif hasattr(first, "_filter_strs_many"):
@@ -245,14 +251,18 @@ class ProbeDesigner:
         chosen = [[u[i] for i in sel] for u, sel in zip(uniq, ids)]
         return [[probe.Probe.from_str(s) for s in grp] for grp in chosen]
 
-    def _device_front_end_mode(self, genomes, first, scf):
+    def _device_front_end_mode(self, genomes, first, scf, pre_filters=()):
         """Candidates and the duplicate (or near-duplicate) filter on the device:
         one of the usual filter pairs without ranks, no --small-seq-min, every
-        sequence a str at least a probe long (or skipped).  "per group": few or
-        large groups, each its own instance; "union": many small groups
-        (clusters) as one instance with group numbers; None: host front end."""
+        sequence a str at least a probe long (or skipped), and no pre-filter but
+        the poly(A) filter (a kernel; the FASTA filter is a look-up on the host).
+        "per group": few or large groups, each its own instance; "union": many
+        small groups (clusters) as one instance with group numbers; None: host
+        front end."""
         import os
         if os.environ.get("CATCHHIP_HOST_FRONT_END"):
+            return None
+        if any(type(f) is not PolyAFilter for f in pre_filters):
             return None
         if self.allow_small_seqs:
             return None
@@ -306,11 +316,22 @@ class ProbeDesigner:
         return "union"
 
     @staticmethod
+    def _strings_prefix(filters):
+        """Length of the leading [FastaFilter | PolyAFilter ..., DuplicateFilter |
+        near-duplicate filter, SetCoverFilter] the strings path runs; 0: none."""
+        n = 0
+        while n < len(filters) and type(filters[n]) in (FastaFilter, PolyAFilter):
+            n += 1
+        if (len(filters) >= n + 2 and type(filters[n]) in (
+                DuplicateFilter, NearDuplicateFilterWithHammingDistance,
+                NearDuplicateFilterWithMinHash)
+                and type(filters[n + 1]) is SetCoverFilter):
+            return n + 2
+        return 0
+
+    @staticmethod
     def _strings_path_ok(filters):
-        return (len(filters) >= 2 and type(filters[0]) in (
-            DuplicateFilter, NearDuplicateFilterWithHammingDistance,
-            NearDuplicateFilterWithMinHash)
-            and type(filters[1]) is SetCoverFilter)
+        return ProbeDesigner._strings_prefix(filters) > 0
 
     @property
     def candidate_probes(self):
@@ -344,8 +365,9 @@ class ProbeDesigner:
         if self._strings_path_ok(before):
             # the two expensive filters on strings, any later ones (adapters)
             # on the few selected probes as objects
-            grouped = self._design_on_strings(genomes, before[:2])
-            grouped = self._pass_through_filters(grouped, genomes, before[2:])
+            n = self._strings_prefix(before)
+            grouped = self._design_on_strings(genomes, before[:n])
+            grouped = self._pass_through_filters(grouped, genomes, before[n:])
             probes = list(dict.fromkeys(itertools.chain(*grouped)))
         else:
             candidates, grouped = self._design_for_genomes(genomes, before)

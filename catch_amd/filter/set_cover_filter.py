@@ -464,7 +464,8 @@ class SetCoverFilter(BaseFilter):
 
     def _filter_genomes_device(self, target_genomes_grouped, probe_length,
                                probe_stride, seq_length_to_skip=None,
-                               near_duplicate_filter=None, return_ids=False):
+                               near_duplicate_filter=None, return_ids=False,
+                               pre_filters=()):
         """[DuplicateFilter | near-duplicate filter, SetCoverFilter] with the
         front end on the device (near_duplicate_filter: an LSH filter object to
         apply to the unique candidates, in their multiplicity order, before the
@@ -559,6 +560,8 @@ class SetCoverFilter(BaseFilter):
                                           probe_stride, seq_length_to_skip)
                 made.append(cands)
                 ncand, nuniq = cands.ncandidates, cands.n
+                for f in pre_filters:     # functions of the candidate alone (poly(A)): before the near-duplicate filter
+                    f._apply_to_candidates(cands)
                 if near_duplicate_filter is not None:
                     if len(items[gi]) > 1:
                         near_duplicate_filter._apply_to_grouped_candidates(cands, len(items[gi]))
@@ -793,7 +796,7 @@ class SetCoverFilter(BaseFilter):
     def _filter_genomes_device_union(self, target_genomes_grouped, probe_length,
                                      probe_stride, seq_length_to_skip=None,
                                      near_duplicate_filter=None,
-                                     max_bases=300_000_000):
+                                     max_bases=300_000_000, pre_filters=()):
         """_filter_genomes_device for many small groups (the clusters of a
         clustered design): the groups of a chunk share one targets / candidates
         / probes triple that carries group numbers -- duplicates are removed
@@ -879,6 +882,8 @@ class SetCoverFilter(BaseFilter):
                 t1 = _time.perf_counter()
                 cands = engine.Candidates(bctx, targets, probe_length, probe_stride, seq_length_to_skip)
                 ncand, nuniq = cands.ncandidates, cands.n
+                for f in pre_filters:     # (as in _filter_genomes_device; grouped candidates alike)
+                    f._apply_to_candidates(cands)
                 t2 = _time.perf_counter()
                 if near_duplicate_filter is not None:
                     if chunk_no[id(chunk)] in drawn_ndf:

@@ -19,7 +19,7 @@ import numpy as np
 
 from catch_amd import engine
 from catch_amd.filter import candidate_probes, duplicate_filter
-from catch_amd.filter import near_duplicate_filter, probe_designer
+from catch_amd.filter import near_duplicate_filter, polya_filter, probe_designer
 from catch_amd.filter import set_cover_filter
 
 logger = logging.getLogger(__name__)
@@ -131,12 +131,14 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
                 coverage=1.0, filter_with_lsh_hamming=None,
                 filter_with_lsh_minhash=None, small_seq_skip=None,
                 small_seq_min=None, kmer_probe_map_k=None,
-                scan_mode=engine.SCAN_AUTO, stats=None):
+                scan_mode=engine.SCAN_AUTO, stats=None, filter_polya=None):
     """Probes for every (dataset, m, e) point.
 
     datasets: list of datasets, each a list of Genome objects (one FASTA file =
     one dataset).  mismatches, cover_extensions: the grid values.  The other
-    options are catch_amd.design's.  Returns {(dataset index, m, e): probe
+    options are catch_amd.design's (filter_polya: the (length, mismatches)
+    of --filter-polya -- per dataset and a function of the candidate alone,
+    so it is part of the front end every grid point shares).  Returns {(dataset index, m, e): probe
     sequences in the order the set cover picked them}.  stats (a dict, may be
     None) receives the number of grid calls (scans of a (dataset, m)), derived
     row tables and solves."""
@@ -176,6 +178,24 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
             coverage=coverage, cover_extension=0, kmer_probe_map_k=k_scf)
         scfs[m].scan_mode = scan_mode
     _first_filter(probe_length, filter_with_lsh_hamming, filter_with_lsh_minhash)   # (argument checks)
+    pre_filters = []
+    if filter_polya:
+        # the warnings catch_amd.design gives
+        polya_length, polya_mismatches = filter_polya
+        if polya_length > probe_length:
+            logger.warning(("Length of poly(A) stretch to filter (%d) is "
+                            "greater than PROBE_LENGTH (%d), which is usually "
+                            "undesirable"), polya_length, probe_length)
+        if polya_length < 10:
+            logger.warning(("Length of poly(A) stretch to filter (%d) is "
+                            "short, and may lead to many probes being "
+                            "filtered"), polya_length)
+        if polya_mismatches > 10:
+            logger.warning(("Number of mismatches to tolerate when searching "
+                            "for poly(A) stretches (%d) is high, and may "
+                            "lead to many probes being filtered"),
+                           polya_mismatches)
+        pre_filters.append(polya_filter.PolyAFilter(polya_length, polya_mismatches))
 
     np_state0, py_state0 = np.random.get_state(), random.getstate()
     out = {}
@@ -202,6 +222,8 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
                 # catch/filter/set_cover_filter.py's _filter_genomes_device, one group
                 P.targets = engine.Targets(ctx, [g.seqs for g in genomes])
                 P.cands = engine.Candidates(ctx, P.targets, probe_length, probe_stride, small_seq_skip)
+                for f in pre_filters:
+                    f._apply_to_candidates(P.cands)
                 if ndf is not None:
                     ndf._apply_to_candidates(P.cands)
                 if P.cands.n == 0:
@@ -214,6 +236,8 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
                         list(g.seqs), probe_length, probe_stride, **pd._window_options())
                 if len(cand) == 0:
                     logger.warning("There are no candidate probes for a grouping of genomes")
+                for f in pre_filters:
+                    cand = f._filter_strs(cand)
                 if ndf is None:
                     P.uniq = list(dict.fromkeys(cand))
                 elif hasattr(ndf, "_filter_strs_many"):

@@ -77,12 +77,12 @@ def iterate_fasta(fn, replace_degenerate=True):
 
 
 def write_probe_fasta(probes, out_fn):
-    """catch/utils/seq_io.py:235-252 (header = probe.header or the last 10
-    hex digits of sha224(sequence), catch/probe.py:303-322)."""
+    """catch/utils/seq_io.py:235-252 (header = probe.header, or "probe_" + the
+    last 10 hex digits of sha224(sequence), catch/probe.py:303-322)."""
     with open(out_fn, "w") as f:
         for p in probes:
             header = p.header
-            if header is None:
-                header = hashlib.sha224(p.seq_str.encode()).hexdigest()[-10:]
+            if not header:
+                header = "probe_" + hashlib.sha224(p.seq_str.encode()).hexdigest()[-10:]
             f.write(">" + header + "\n")
             f.write(p.seq_str + "\n")

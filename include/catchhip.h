@@ -705,6 +705,24 @@ int catchhip_candidates_ndf_minhash_many(catchhip_ctx *ctx, catchhip_candidates 
                                          double dist_thres, int64_t *nkept);
 int catchhip_candidates_groups(catchhip_ctx *ctx, const catchhip_candidates *cands,
                                int32_t *group_of_candidate);
+/* PolyAFilter._filter on the candidates (catch/filter/polya_filter.py:43-71, which
+ * costs a k_lcf call of O(L^2) per candidate): unique candidates with a stretch of
+ * >= length 'A' (or 'T') under `mismatches` mismatches are dropped -- but only
+ * those that hold an exact run of >= min_exact 'A' or 'T', the reference's gate
+ * (min_exact_length_to_consider, 6 by default; 0 = no gate).  Every character but
+ * the stretch's own is a mismatch, N included; length > probe_length drops nothing.
+ * The rule is a function of the candidate alone, so the list left -- order,
+ * multiplicities and groups kept, ncandidates untouched -- is what the reference's
+ * [PolyAFilter, DuplicateFilter] leaves.  Before any catchhip_candidates_ndf_* call
+ * (EINVAL after one); grouped and ungrouped candidates alike; *nkept = candidates
+ * left (0 is valid). */
+int catchhip_candidates_drop_polya(catchhip_ctx *ctx, catchhip_candidates *cands,
+                                   int32_t length, int32_t mismatches,
+                                   int32_t min_exact, int64_t *nkept);
+/* multiplicity[i] = how many candidates equal unique candidate i (the priority of
+ * near_duplicate_filter.py:60-66); EINVAL once a catchhip_candidates_ndf_* call ran */
+int catchhip_candidates_multiplicities(catchhip_ctx *ctx, const catchhip_candidates *cands,
+                                       uint32_t *multiplicity);
 /* A probes object of the unique candidates (set id = candidate index), as
  * catchhip_probes_create would build from their strings.  Anchors: sorted by
  * (probe, position) without duplicates, or ent_probe = ent_pos = NULL for the
