@@ -111,6 +111,12 @@ PROTOTYPES = {
     "catchhip_pool_solve": (ctypes.c_int, [
         c_vp, ctypes.c_int64, c_i64p, c_i64p, c_f64p, ctypes.c_int64, c_i32p, c_i64p,
         ctypes.POINTER(ctypes.c_double)]),
+    "catchhip_redundancy_graph": (ctypes.c_int, [
+        c_vp, c_u8p, c_i64p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vpp, c_i64p]),
+    "catchhip_redundancy_fetch": (ctypes.c_int, [c_vp, c_vp, c_i64p, c_u32p]),
+    "catchhip_redundancy_destroy": (ctypes.c_int, [c_vp]),
+    "catchhip_redundancy_naive": (ctypes.c_int, [c_vp, c_vp, c_u8p]),
+    "catchhip_redundancy_rows": (ctypes.c_int, [c_vp, c_vp, c_vpp, c_i64p]),
     "catchhip_comm_unique_id": (ctypes.c_int, [c_u8p]),
     "catchhip_comm_init": (ctypes.c_int, [
         c_vp, c_u8p, ctypes.c_int32, ctypes.c_int32]),

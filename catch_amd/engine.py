@@ -782,6 +782,62 @@ class Rows:
             pass
 
 
+REDUNDANT_SHIFT, REDUNDANT_LCF = 0, 1
+REDUNDANT_MAX_LENGTH = 256     # bases per probe the pair kernel is compiled for (csrc/redundant.hip)
+
+
+class RedundancyGraph:
+    """Device-resident redundancy graph of a probe list (catchhip_redgraph):
+    probes i and j are neighbours iff the predicate of `kind` with parameters
+    (p0, p1) holds for them -- REDUNDANT_SHIFT: (shift, mismatch_thres);
+    REDUNDANT_LCF: (mismatches, lcf_thres >= 1)."""
+
+    def __init__(self, ctx, probe_strs, kind, p0, p1):
+        self.ctx = ctx
+        self._h = ctypes.c_void_p()
+        self.n = len(probe_strs)
+        buf, off = _concat(list(probe_strs))
+        ne = ctypes.c_int64(0)
+        check(ctx._L.catchhip_redundancy_graph(
+            ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), self.n, int(kind), int(p0), int(p1),
+            ctypes.byref(self._h), ctypes.byref(ne)))
+        self.nedges = ne.value
+
+    def fetch(self):
+        """(ptr int64[n + 1], idx uint32[nedges]): the neighbours of i are
+        idx[ptr[i]:ptr[i + 1]], ascending."""
+        ptr = np.zeros(self.n + 1, dtype=np.int64)
+        idx = np.zeros(max(self.nedges, 1), dtype=np.uint32)
+        check(self.ctx._L.catchhip_redundancy_fetch(self.ctx._h, self._h, _ptr(ptr, c_i64p), _ptr(idx, c_u32p)))
+        return ptr, idx[:self.nedges]
+
+    def naive(self):
+        """catchhip_redundancy_naive -> bool[n]: the probes the reference's
+        double loop keeps."""
+        keep = np.zeros(max(self.n, 1), dtype=np.uint8)
+        check(self.ctx._L.catchhip_redundancy_naive(self.ctx._h, self._h, _ptr(keep, c_u8p)))
+        return keep[:self.n].astype(bool)
+
+    def rows(self):
+        """catchhip_redundancy_rows -> Rows of the sets {i} + N(i) for
+        Rows.greedy(num_sets=n)."""
+        h = ctypes.c_void_p()
+        n = ctypes.c_int64(0)
+        check(self.ctx._L.catchhip_redundancy_rows(self.ctx._h, self._h, ctypes.byref(h), ctypes.byref(n)))
+        return Rows(self.ctx, h, n.value)
+
+    def close(self):
+        if self._h and self.ctx._h:      # (see Context.close)
+            self.ctx._L.catchhip_redundancy_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Shard:
     """One rank's part of a universe-sharded set cover instance
     (catchhip_shard): the frontier solver's state over this rank's cover

@@ -45,6 +45,31 @@ class Probe:
         b = np.frombuffer(other.seq_str.encode("latin-1"), dtype=np.uint8)
         return int(np.count_nonzero(a != b))
 
+    def mismatches_at_offset(self, other, offset):
+        """catch/probe.py:66-88: mismatches with `other` shifted right by
+        `offset` (left when negative), over the overlapping part."""
+        n = len(self.seq_str)
+        if n != len(other.seq_str):
+            raise ValueError("Sequences must be of same length")
+        if abs(offset) >= n:
+            raise ValueError("Invalid offset value " + str(offset))
+        a = np.frombuffer(self.seq_str.encode("utf-32-le"), dtype=np.uint32)
+        b = np.frombuffer(other.seq_str.encode("utf-32-le"), dtype=np.uint32)
+        if offset < 0:
+            return int(np.count_nonzero(a[:n + offset] != b[-offset:]))
+        return int(np.count_nonzero(a[offset:] != b[:n - offset]))
+
+    def min_mismatches_within_shift(self, other, max_shift):
+        """catch/probe.py:90-104."""
+        return min(self.mismatches_at_offset(other, offset)
+                   for offset in range(-max_shift, max_shift + 1))
+
+    def longest_common_substring_length(self, other, k):
+        """catch/probe.py:106-119: length of the longest common substring with
+        at most k mismatches (catch_amd.utils.longest_common_substring.k_lcf)."""
+        from catch_amd.utils import longest_common_substring
+        return longest_common_substring.k_lcf(self.seq_str, other.seq_str, k)[0]
+
     def reverse_complement(self):
         rc_map = {"A": "T", "T": "A", "C": "G", "G": "C"}
         return Probe("".join(rc_map.get(b, b) for b in self.seq_str[::-1]))

@@ -328,6 +328,61 @@ int catchhip_pool_solve(catchhip_ctx *ctx, int64_t D, const int64_t *opt_off,
                         int64_t budget, int32_t *out_choice, int64_t *out_total,
                         double *out_loss);
 
+/* ---- design_naively: redundancy graph, naive pass, dominating set ----------
+ * The reference's two legacy filters evaluate a pairwise predicate
+ * are_redundant(a, b) over all n (n - 1) / 2 pairs of a probe list in Python
+ * (catch/filter/naive_redundant_filter.py:46-77, catch/filter/
+ * dominating_set_filter.py:62-91).  catchhip_redundancy_graph evaluates the
+ * predicate for every pair on the device (csrc/redundant.hip) and keeps the
+ * result as an opaque device-resident graph in CSR form: symmetric, no self
+ * loops, every neighbour list ascending; *nedges (64-bit, may be NULL) counts
+ * the directed edges, two per redundant pair.  n probes at bytes / off[n + 1]
+ * (duplicates allowed; letters ACGTN; at most 256 bases each -- CATCHHIP_EINVAL
+ * names the limit otherwise).
+ *   kind 0: naive_redundant_filter.redundant_shift_and_mismatch_count(shift =
+ *           p0, mismatch_thres = p1) (:80-143): redundant iff for some offset s
+ *           in [-p0, p0] the overlapping parts differ in at most p1 places; an
+ *           empty overlap has 0 mismatches (the quick loop, :112-137).
+ *   kind 1: naive_redundant_filter.redundant_longest_common_substring(
+ *           mismatches = p0, lcf_thres = p1, prune_with_heuristic_and_anchor =
+ *           False) (:146-215): redundant iff longest_common_substring.k_lcf(a, b,
+ *           p0)[0] >= p1 (catch/utils/longest_common_substring.py:11-56), i.e.
+ *           on some diagonal a window of p1 positions has at most p0 mismatches.
+ *           Characters compare by plain inequality: N equals N.  p1 <= 0 makes
+ *           every pair redundant and is refused with CATCHHIP_EINVAL (the caller
+ *           knows the answer).  The reference's randomised heuristic (the True
+ *           branch) is not reproduced: the exact predicate runs for every pair.
+ * catchhip_redundancy_fetch copies the graph out: ptr[n + 1], idx[nedges]. */
+typedef struct catchhip_redgraph catchhip_redgraph;
+int catchhip_redundancy_graph(catchhip_ctx *ctx, const uint8_t *bytes,
+                              const int64_t *off, int64_t n, int32_t kind,
+                              int32_t p0, int32_t p1, catchhip_redgraph **out,
+                              int64_t *nedges);
+int catchhip_redundancy_fetch(catchhip_ctx *ctx, const catchhip_redgraph *graph,
+                              int64_t *ptr, uint32_t *idx);
+int catchhip_redundancy_destroy(catchhip_redgraph *graph);
+/* Replaces NaiveRedundantFilter._filter's double loop (catch/filter/
+ * naive_redundant_filter.py:46-77): keep[i] (host, n bytes) = 1 iff no kept
+ * probe with a smaller index is redundant to probe i -- the lexicographically
+ * first maximal independent set of the graph.  Frontier rounds on the device (a
+ * vertex is dropped once a smaller neighbour is kept, kept once all smaller
+ * neighbours are dropped; one read-back per 8 rounds) and, when a round decides
+ * few vertices (a chain of dependencies), one single-workgroup launch that walks
+ * the rest in order.  The graph never leaves the device. */
+int catchhip_redundancy_naive(catchhip_ctx *ctx, const catchhip_redgraph *graph,
+                              uint8_t *keep);
+/* The set cover instance DominatingSetFilter._filter hands to set_cover.approx
+ * (catch/filter/dominating_set_filter.py:62-91, catch/utils/set_cover.py:14-144,
+ * cost 1 and p = 1): set i = {i} + neighbours of i, as a rows object for
+ * catchhip_setcover_greedy with num_sets = n and one universe in which element
+ * u is the row [2 u, 2 u + 1).  approx picks the largest gain and, of equal
+ * gains, the lowest id (it iterates a set of small dense ints), which is the
+ * solver's order.  The probes of the graph must be distinct: approx's universe
+ * holds Probe objects that hash by sequence, so the caller builds the graph on
+ * first occurrences.  *nrows = nedges + n (fewer than 2^31, else EINVAL). */
+int catchhip_redundancy_rows(catchhip_ctx *ctx, const catchhip_redgraph *graph,
+                             catchhip_rows **out, int64_t *nrows);
+
 /* Multi-GPU, one process per GPU: an RCCL communicator attached to a context
  * (the reference has no counterpart: it forks a process pool,
  * catch/probe.py:727-743, catch/filter/set_cover_filter.py:848-900).  The
