@@ -349,14 +349,49 @@ def _sequences_with_unique_windows(rng, L, stride, nuniq):
     return seqs
 
 
+# the kernel's workgroup by candidate length (csrc/prefilter.hip): rows copied into LDS at an odd pitch of
+# 4 * ceil((L + 15) / 16) + 1 dwords, as many of 256 / 128 / 64 rows as fit 64 KB, and read from global memory when 64 do not
+POLYA_TIER_EDGES = [(225, 40), (226, 40), (481, 97), (482, 97), (993, 200), (994, 200)]
+
+
+def _polya_workgroup(L):
+    """(rows per workgroup, bytes of dynamic LDS) of the poly(A) kernel's launch; (256, 0): unstaged."""
+    pitch = 4 * ((L + 30) // 16) + 1
+    for rows in (256, 128, 64):
+        if rows * pitch * 4 <= 65536:
+            return rows, rows * pitch * 4
+    return 256, 0
+
+
+def _polya_sizes(L):
+    """Unique-candidate counts around one and two workgroups of every size the kernel uses."""
+    if any(L == edge for edge, _ in POLYA_TIER_EDGES):
+        return [1, 63, 64, 65, 127, 128, 129, 257]
+    return [0, 1, 255, 256, 257] + ([3000] if L in (65, 100) else [])
+
+
+def test_polya_tier_edges_sit_on_the_workgroup_sizes_claimed():
+    """No GPU: the lengths added to the kernel test are the last of one workgroup size and the first of the next --
+    256 rows up to 225 bases (62,464 bytes of LDS, the largest launch), 128 rows for 226..481, 64 rows for 482..993,
+    unstaged from 994 -- and the lengths tested before all take 256 rows within 48 KB."""
+    assert [_polya_workgroup(L) for L, _ in POLYA_TIER_EDGES] == [
+        (256, 62464), (128, 33280), (128, 64000), (64, 33024), (64, 64768), (256, 0)]
+    assert all(_polya_workgroup(L)[0] == 256 and 0 < _polya_workgroup(L)[1] <= 48 * 1024 for L in (8, 63, 64, 65, 100, 130))
+    assert _polya_workgroup(130) == (256, 41984)
+    for L, stride in POLYA_TIER_EDGES:
+        sizes, rows = _polya_sizes(L), _polya_workgroup(L)[0]
+        assert {63, 64, 65, 127, 128, 129} <= set(sizes) and max(sizes) > rows and stride < L
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("L,stride", [(8, 3), (63, 20), (64, 32), (65, 17), (100, 50), (130, 50)])
+@pytest.mark.parametrize("L,stride", [(8, 3), (63, 20), (64, 32), (65, 17), (100, 50), (130, 50)] + POLYA_TIER_EDGES)
 def test_drop_polya_kernel_equals_numpy(ctx, L, stride):
     """catchhip_candidates_drop_polya against the NumPy rule: the surviving positions, multiplicities and groups are
-    the unfiltered list's, masked; 0, 1 and 255..257 unique candidates (a block is 256 rows) and ~3,000."""
+    the unfiltered list's, masked; 0, 1 and 255..257 unique candidates (a block is 256 rows) and ~3,000.  At the
+    lengths of POLYA_TIER_EDGES, where a block is 256, 128 or 64 rows: 1, 63..65, 127..129 and 257."""
     from catch_amd import engine
     rng = np.random.default_rng(1000 + L)
-    sizes = [0, 1, 255, 256, 257] + ([3000] if L in (65, 100) else [])
+    sizes = _polya_sizes(L)
     for nuniq in sizes:
         seqs = ["N" * (L + 40)] if nuniq == 0 else _sequences_with_unique_windows(rng, L, stride, nuniq)
         concat = "".join(seqs)

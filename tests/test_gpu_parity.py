@@ -2247,7 +2247,8 @@ def _first_seen_device(ctx, uniq, entries, k, seqs, m, thres, island, ent_rank, 
 
 
 @pytest.mark.parametrize("L,m,thres,island,min_k", [(100, 2, 100, 0, 20), (75, 2, 75, 0, 20), (100, 5, 100, 0, 20),
-                                                     (100, 3, 80, 0, 20), (75, 2, 60, 25, 10), (60, 1, 60, 0, 20)])
+                                                     (100, 3, 80, 0, 20), (75, 2, 60, 25, 10), (60, 1, 60, 0, 20),
+                                                     (224, 2, 224, 0, 20)])
 def test_first_seen_keys_match_oracle(ctx, oracle, L, m, thres, island, min_k):
     """catchhip_cover_scan_first_seen: merged rows as catchhip_cover_scan, and
     for every (probe, sequence) the first accepted seed (position, caller's

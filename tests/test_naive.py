@@ -9,6 +9,7 @@ counts.  The GPU tests compare the device graph with a NumPy restatement of the
 two predicates (every diagonal, windows of exactly lcf_thres) that is itself
 checked against the golden pairs without a GPU.
 """
+import functools
 import os
 import re
 
@@ -36,20 +37,17 @@ def _encode(strs):
     return arr, np.array([len(s) for s in strs], dtype=np.int64)
 
 
-def _redundant(A, la, B, lb, kind, p0, p1):
-    """The predicate for every pair of the broadcast of A (..., LA) against B (..., LB): kind "lcf": on some diagonal
-    a window of exactly p1 positions inside the overlap has at most p0 mismatches (everything when p1 <= 0); kind
-    "shift": for some offset in [-p0, p0] the overlap (possibly empty) has at most p1 mismatches."""
+_NEVER = 1 << 12          # what a position outside the overlap adds to a window: more than any mismatch budget asked for
+
+
+def _fewest(A, la, B, lb, kind, p):
+    """For every pair of the broadcast of A (..., LA) against B (..., LB).  kind "lcf": the fewest mismatches in a window
+    of exactly p >= 1 positions inside the overlap, over every diagonal (>= _NEVER where no diagonal holds such a
+    window); kind "shift": the fewest mismatches of the overlap (possibly empty: 0) over the offsets in [-p, p]."""
     LA, LB = A.shape[-1], B.shape[-1]
     shape = np.broadcast_shapes(A.shape[:-1], B.shape[:-1])
-    out = np.zeros(shape, dtype=bool)
-    if kind == "lcf":
-        if p1 <= 0:
-            return ~out
-        diagonals = range(-(LB - 1), LA)
-    else:
-        diagonals = range(-p0, p0 + 1)
-    for d in diagonals:
+    best = np.full(shape, _NEVER * (LA + LB + 1), dtype=np.int64)
+    for d in (range(-(LB - 1), LA) if kind == "lcf" else range(-p, p + 1)):
         i0, j0 = max(d, 0), max(-d, 0)
         size = min(LA - i0, LB - j0)
         overlap = np.minimum(la - i0, lb - j0)
@@ -59,22 +57,48 @@ def _redundant(A, la, B, lb, kind, p0, p1):
             else:
                 neq = A[..., i0:i0 + size] != B[..., j0:j0 + size]
                 count = (neq & (np.arange(size) < overlap[..., None])).sum(axis=-1)
-            out |= count <= p1
+            best = np.minimum(best, count)
             continue
-        if size < p1:
+        if size < p:
             continue
-        neq = (A[..., i0:i0 + size] != B[..., j0:j0 + size]).astype(np.int32)
-        neq = np.where(np.arange(size) >= overlap[..., None], size + 1, neq)     # (a window leaves the overlap: never)
-        cs = np.concatenate([np.zeros(shape + (1,), dtype=np.int64), np.cumsum(neq, axis=-1)], axis=-1)
-        out |= ((cs[..., p1:] - cs[..., :-p1]) <= p0).any(axis=-1)
-    return out
+        neq = np.where(np.arange(size) < overlap[..., None], A[..., i0:i0 + size] != B[..., j0:j0 + size], _NEVER)
+        cs = np.cumsum(neq, axis=-1, dtype=np.int32)             # (a window that leaves the overlap: >= _NEVER)
+        win = cs[..., p - 1:].copy()
+        win[..., 1:] -= cs[..., :size - p]
+        best = np.minimum(best, win.min(axis=-1))
+    return best
+
+
+def _redundant(A, la, B, lb, kind, p0, p1):
+    """The predicate for every pair of the broadcast of A (..., LA) against B (..., LB): kind "lcf": on some diagonal
+    a window of exactly p1 positions inside the overlap has at most p0 mismatches (everything when p1 <= 0); kind
+    "shift": for some offset in [-p0, p0] the overlap (possibly empty) has at most p1 mismatches."""
+    assert p0 < _NEVER and p1 < _NEVER
+    if kind == "lcf":
+        if p1 <= 0:
+            return np.ones(np.broadcast_shapes(A.shape[:-1], B.shape[:-1]), dtype=bool)
+        return _fewest(A, la, B, lb, "lcf", p1) <= p0
+    return _fewest(A, la, B, lb, "shift", p0) <= p1
+
+
+@functools.lru_cache(maxsize=4)
+def _fewest_of_pairs(strs, kind, p):
+    """_fewest for the pairs i < j of a probe set: computed once for every mismatch budget a test asks about."""
+    arr, lens = _encode(strs)
+    i, j = np.triu_indices(len(strs), 1)
+    return i, j, _fewest(arr[i], lens[i], arr[j], lens[j], kind, p)
 
 
 def restate_graph(strs, kind, p0, p1):
     """Adjacency matrix (symmetric, no self loops) of the redundancy graph; pair (i, j), i < j, is (a, b)."""
-    arr, lens = _encode(strs)
-    adj = _redundant(arr[:, None, :], lens[:, None], arr[None, :, :], lens[None, :], kind, p0, p1)
-    adj = np.triu(adj, 1)
+    n = len(strs)
+    adj = np.zeros((n, n), dtype=bool)
+    if kind == "lcf" and p1 <= 0:
+        adj[np.triu_indices(n, 1)] = True
+    else:
+        assert p0 < _NEVER and p1 < _NEVER
+        i, j, fewest = _fewest_of_pairs(tuple(strs), kind, p1 if kind == "lcf" else p0)
+        adj[i, j] = fewest <= (p0 if kind == "lcf" else p1)
     return adj | adj.T
 
 
@@ -232,14 +256,15 @@ def test_redundancy_symbols_declared_bound_and_built():
 
 
 # ------------------------------------------------------------------ GPU
-def _probe_set(rng, n, length, n_rate=0.0):
-    """n probes in families: windows of a few roots with 0-3 substitutions; length None: lengths 1-150 mixed."""
-    roots = ["".join(rng.choice(list("ACGT"), size=230)) for _ in range(max(1, n // 6))]
+def _probe_set(rng, n, length, n_rate=0.0, root_length=230, max_length=150):
+    """n probes in families: windows of a few roots of root_length bases with 0-3 substitutions; length None: lengths
+    1-max_length mixed."""
+    roots = ["".join(rng.choice(list("ACGT"), size=root_length)) for _ in range(max(1, n // 6))]
     out = []
     for _ in range(n):
-        L = int(rng.integers(1, 151)) if length is None else length
+        L = int(rng.integers(1, max_length + 1)) if length is None else length
         root = roots[int(rng.integers(len(roots)))]
-        at = int(rng.integers(0, min(12, 230 - L) + 1))
+        at = int(rng.integers(0, min(12, root_length - L) + 1))
         s = list(root[at:at + L])
         for j in rng.choice(L, size=min(L, int(rng.integers(0, 4))), replace=False):
             s[j] = "ACGT"[int(rng.integers(4))]
@@ -274,17 +299,50 @@ def _check_graph(ctx, strs, kind, p0, p1):
         g.close()
 
 
-# (n, probe length or None = mixed, share of N): 63 / 64 / 65 and 130 straddle the 64-probe pair tile
+# (n, probe length or None = lengths 1-150 mixed or (1, M) = lengths 1-M mixed, share of N): 63 / 64 / 65 and 130 straddle
+# the 64-probe pair tile; from 129 bases a plane is four 64-base words, all four in use from 193, full at 256
 GRAPH_SETS = [(1, 40, 0.0), (2, 128, 0.0), (63, 65, 0.02), (64, 64, 0.0), (65, 1, 0.1), (65, 40, 0.03), (40, 100, 0.02),
-              (130, 40, 0.0), (36, 128, 0.02), (36, 129, 0.0), (40, None, 0.03)]
+              (130, 40, 0.0), (36, 128, 0.02), (36, 129, 0.0), (40, None, 0.03),
+              (40, 192, 0.0), (40, 193, 0.02), (36, 255, 0.02), (36, 256, 0.0), (65, 256, 0.01), (40, (1, 256), 0.03)]
+LONG_ROOT = 280           # root length of the sets longer than 150 bases (a window of 256 at offsets 0-12)
+
+
+def _graph_set(n, length, n_rate):
+    """The probes of one GRAPH_SETS entry and the length its thresholds and shifts are taken around."""
+    if isinstance(length, tuple):
+        rng = np.random.default_rng(1000 + n * 7 + length[1])
+        return _probe_set(rng, n, None, n_rate, root_length=LONG_ROOT, max_length=length[1]), 200
+    rng = np.random.default_rng(1000 + n * 7 + (length or 0))
+    if length is not None and length > 150:
+        return _probe_set(rng, n, length, n_rate, root_length=LONG_ROOT), length
+    return _probe_set(rng, n, length, n_rate), length if length is not None else 100
+
+
+def test_long_graph_sets_fill_the_words_they_are_there_for():
+    """No GPU: the sets above 128 bases use the plane words claimed -- 192 fills word 2 exactly, 193 puts one base into
+    word 3, 255 / 256 leave one bit / nothing of word 3 free -- and the mixed set holds lengths on both sides of every
+    word boundary, 256 itself not required."""
+    for n, length, n_rate in GRAPH_SETS:
+        strs, around = _graph_set(n, length, n_rate)
+        assert len(strs) == n and set("".join(strs)) <= set("ACGTN")
+        if isinstance(length, tuple):
+            lens = sorted(len(s) for s in strs)
+            assert around == 200 and lens[0] >= 1 and lens[-1] <= 256
+            for lo, hi in ((1, 64), (65, 128), (129, 192), (193, 256)):
+                assert sum(lo <= x <= hi for x in lens) >= 4, (lo, hi, lens)
+        elif length is not None:
+            assert around == length and all(len(s) == length for s in strs)
+        if n_rate > 0 and n * (around if length is None or isinstance(length, tuple) else length) >= 1000:
+            assert any("N" in s for s in strs)
+    # today's sets are the sets of before the generalisation (same seeds, same draws)
+    assert _graph_set(36, 129, 0.0)[0] == _probe_set(np.random.default_rng(1000 + 36 * 7 + 129), 36, 129, 0.0)
+    assert _graph_set(40, None, 0.03)[0] == _probe_set(np.random.default_rng(1000 + 40 * 7), 40, None, 0.03)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,length,n_rate", GRAPH_SETS)
 def test_graph_equals_restatement_both_kinds_and_naive_pass_equals_the_loop(ctx, n, length, n_rate):
-    rng = np.random.default_rng(1000 + n * 7 + (length or 0))
-    strs = _probe_set(rng, n, length, n_rate)
-    L = length if length is not None else 100
+    strs, L = _graph_set(n, length, n_rate)
     edges = 0
     for lcf_thres in sorted({1, max(L // 2, 1), L, L + 1}):
         for mismatches in (0, 2, 5):
@@ -293,6 +351,18 @@ def test_graph_equals_restatement_both_kinds_and_naive_pass_equals_the_loop(ctx,
         for thres in (0, 3):
             edges += _check_graph(ctx, strs, "shift", shift, thres)
     assert n < 2 or edges > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,length,n_rate,shift", [(64, 64, 0.0, 70), (63, 65, 0.02, 129), (36, 256, 0.0, 300),
+                                                   (36, 256, 0.0, 257), (40, (1, 256), 0.03, 300)])
+def test_graph_shift_beyond_the_packed_width(ctx, n, length, n_rate, shift):
+    """A shift above the 64 W bases the planes hold (W = 1 up to 64 bases, 2 up to 128, 4 up to 256): the kernel
+    clamps the diagonals it walks to 64 W, where every overlap is empty and so without a mismatch -- all pairs, as
+    the restatement says, whatever the mismatch threshold."""
+    strs, _ = _graph_set(n, length, n_rate)
+    for thres in (0, 3):
+        assert _check_graph(ctx, strs, "shift", shift, thres) == n * (n - 1)
 
 
 @pytest.mark.gpu
@@ -311,6 +381,10 @@ def test_graph_refuses_what_it_cannot_pack(ctx):
         engine.RedundancyGraph(ctx, ["ACGT", "ACGU"], engine.REDUNDANT_LCF, 0, 2)
     with pytest.raises(ValueError, match="every pair"):
         engine.RedundancyGraph(ctx, ["ACGT", "ACGA"], engine.REDUNDANT_LCF, 0, 0)
+    with pytest.raises(ValueError, match="mismatches must not be negative"):
+        engine.RedundancyGraph(ctx, ["ACGT", "ACGA"], engine.REDUNDANT_LCF, -1, 2)
+    with pytest.raises(ValueError, match="shift must not be negative"):
+        engine.RedundancyGraph(ctx, ["ACGT", "ACGA"], engine.REDUNDANT_SHIFT, -1, 0)
     g = engine.RedundancyGraph(ctx, [], engine.REDUNDANT_SHIFT, 0, 0)
     assert g.nedges == 0 and g.naive().size == 0 and g.fetch()[0].tolist() == [0]
     g.close()
@@ -342,6 +416,32 @@ def test_naive_pass_on_a_path_an_empty_and_a_complete_graph(ctx, n):
         assert g.nedges == n * (n - 1)
         assert g.naive().tolist() == [True] + [False] * (n - 1)
         g.close()
+
+
+@pytest.mark.gpu
+def test_naive_pass_on_a_path_of_256_base_probes(ctx):
+    """Windows of 256 bases at stride 100: neighbours share 156 bases, second neighbours 56, so under LCF (0, 120) the
+    graph is a path of 300 vertices whose every comparison runs over all four words of a plane.  lcf_thres = 257: no
+    edges.  shift = 256: complete."""
+    from catch_amd import engine
+    n = 300
+    rng = np.random.default_rng(256)
+    seq = "".join(rng.choice(list("ACGT"), size=100 * n + 156))
+    strs = [seq[100 * i:100 * i + 256] for i in range(n)]
+    g = engine.RedundancyGraph(ctx, strs, engine.REDUNDANT_LCF, 0, 120)
+    ptr, idx = g.fetch()
+    assert g.nedges == 2 * (n - 1)
+    assert all(idx[ptr[i]:ptr[i + 1]].tolist() == [j for j in (i - 1, i + 1) if 0 <= j < n] for i in range(n))
+    keep = g.naive()
+    assert (keep == naive_loop(ptr, idx)).all() and keep.tolist() == [i % 2 == 0 for i in range(n)]
+    g.close()
+    g = engine.RedundancyGraph(ctx, strs, engine.REDUNDANT_LCF, 0, 257)
+    assert g.nedges == 0 and g.naive().all()
+    g.close()
+    g = engine.RedundancyGraph(ctx, strs, engine.REDUNDANT_SHIFT, 256, 0)
+    assert g.nedges == n * (n - 1)
+    assert g.naive().tolist() == [True] + [False] * (n - 1)
+    g.close()
 
 
 def _predicate(case):
