@@ -152,6 +152,10 @@ PROTOTYPES = {
     "catchhip_sigs_common_row": (ctypes.c_int, [
         c_vp, c_vp, ctypes.c_uint32, c_u16p]),
     "catchhip_sigs_condensed": (ctypes.c_int, [c_vp, c_vp, c_f32p, c_f32p]),
+    "catchhip_sigs_linkage_average": (ctypes.c_int, [c_vp, c_vp, c_f32p, ctypes.c_double, c_i32p, c_f64p]),
+    "catchhip_linkage_average": (ctypes.c_int, [c_vp, ctypes.c_int64, c_f32p, ctypes.c_double, c_i32p, c_f64p]),
+    "catchhip_linkage_labels": (ctypes.c_int, [ctypes.c_int64, c_f64p, ctypes.c_double, c_i32p, c_f64p]),
+    "catchhip_linkage_fits": (ctypes.c_int, [c_vp, ctypes.c_int64, c_i32p]),
     "catchhip_sigs_neighbors": (ctypes.c_int, [
         c_vp, c_vp, ctypes.c_uint32, ctypes.c_uint32, c_u64p, ctypes.c_int64, c_i64p]),
     "catchhip_sigs_neighbors_many": (ctypes.c_int, [

@@ -301,6 +301,39 @@ struct catchhip_candidates {
 // upos, mult and (grouped) ugrp compacted, nuniq updated (candidates.hip: cand_scan + cand_compact_kernel)
 int chip_candidates_keep_flagged(catchhip_ctx *ctx, catchhip_candidates *C, DevBuf<u32> &flag, i64 *nkept);
 
+// MinHash signatures of sequences on the device (cluster.hip; linkage.hip reads them)
+struct catchhip_sigs {
+    catchhip_ctx *ctx = nullptr;
+    u32 nseq = 0, N = 0;
+    DevBuf<u32> sig;    // [nseq][N], ascending
+    DevBuf<u32> sigT;   // [N][nseq]
+    DevBuf<u64> fpT;    // 4,096-bit fingerprints of the signatures, [word][nseq] (catchhip_sigs_neighbors_many, on first use)
+    DevBuf<u32> fp_excess;
+    bool fp_ready = false;
+    // the neighbour graph (catchhip_sigs_graph): rows of g_idx / g_com delimited by g_ptr
+    DevBuf<u64> g_ptr;
+    DevBuf<u32> g_idx, g_com;
+    u64 g_edges = 0;
+    bool g_ready = false;
+};
+
+// common values met by the N-step merge walk of two ascending N-value lists.
+// Branch-free: the three-way comparison of a divergent wavefront would run all
+// three paths every step (measured: 28-33 us per row of 6,000 walks, one
+// wavefront per CU, whether the values came from L2 or from LDS).
+template <typename FA, typename FB> __device__ __forceinline__ u32 walk_common(u32 N, FA a_at, FB b_at) {
+    u32 ia = 0, ib = 0, common = 0;
+    for (u32 step = 0; step < N; ++step) {
+        const u32 act = (ia < N) & (ib < N);           // the reference's loop condition
+        const u32 a = a_at(min(ia, N - 1)), b = b_at(min(ib, N - 1));
+        const u32 lt = act & (a < b), gt = act & (a > b), eq = act & (a == b);
+        ia += lt | eq;
+        ib += gt | eq;
+        common += eq;
+    }
+    return common;
+}
+
 // ---- timing helpers -----------------------------------------------------
 struct PhaseTimer {
     catchhip_ctx *c;

@@ -1087,6 +1087,29 @@ class Signatures:
             self.ctx._h, self._h, _ptr(lut, c_f32p), _ptr(out, c_f32p)))
         return out[:npairs]
 
+    def linkage_fits(self):
+        """Whether the float64 square matrix of linkage_clusters (8 n^2 bytes) takes at most half of the device
+        memory that is free now."""
+        fits = ctypes.c_int32(0)
+        check(self.ctx._L.catchhip_linkage_fits(self.ctx._h, self.n, ctypes.byref(fits)))
+        return bool(fits.value)
+
+    def linkage_clusters(self, lut, threshold, return_merges=False):
+        """catchhip_sigs_linkage_average: SciPy's average linkage + fcluster(criterion="distance") of the
+        distances lut[common] on the device -> clusters as lists of indices, largest first (what
+        cluster.cluster_hierarchically_from_dist_matrix returns for self.condensed(lut)); return_merges: also the
+        linkage matrix, float64 (n - 1, 4)."""
+        from catch_amd.utils import cluster
+        lut = np.ascontiguousarray(lut, dtype=np.float32)
+        assert lut.size == self.N + 1
+        labels = np.zeros(max(self.n, 1), dtype=np.int32)
+        merges = np.zeros((max(self.n - 1, 1), 4), dtype=np.float64) if return_merges else None
+        check(self.ctx._L.catchhip_sigs_linkage_average(
+            self.ctx._h, self._h, _ptr(lut, c_f32p), float(threshold), _ptr(labels, c_i32p),
+            _ptr(merges, c_f64p) if return_merges else None))
+        clusters = cluster._clusters_from_labels(labels[:self.n])
+        return (clusters, merges[:max(self.n - 1, 0)]) if return_merges else clusters
+
 
 def tolerant_bp(ctx, probes, targets, mismatches, lcf_thres, island, out):
     """catchhip_tolerant_bp: out (int64, one per unique probe) += bp."""

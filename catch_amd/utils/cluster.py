@@ -1,14 +1,19 @@
 """Clustering of sequences before design (mirrors catch/utils/cluster.py; used
 by `--cluster-and-design-separately`).
 
-On the device (catch_amd/csrc/cluster.hip): the MinHash signatures of all
-sequences (md5 of every k-mer, N smallest per sequence) and the signature
-distances -- one row at a time for the connected-components search, or the
-whole condensed matrix for hierarchical clustering.  On the host: the
-depth-first search itself (sequential by nature: which vertices get explored
-depends on what earlier explorations absorbed, cluster.py:235-355) and
-SciPy's average linkage (:197-232), the same third-party routine the
-reference calls.
+On the device (catch_amd/csrc/cluster.hip, linkage.hip): the MinHash signatures
+of all sequences (md5 of every k-mer, N smallest per sequence), the signature
+distances -- the whole neighbour graph for the connected-components search --
+and, for the hierarchical method, SciPy's average linkage itself: the float64
+distance matrix is filled on the device and one persistent workgroup runs the
+nearest-neighbour chain with SciPy's tie rules (cluster_hierarchically_on_device,
+engine.Signatures.linkage_clusters).  On the host: the depth-first search
+(sequential by nature: which vertices get explored depends on what earlier
+explorations absorbed, cluster.py:235-355), the sort / relabelling / flat
+clusters of the n - 1 merges (native, no SciPy), and -- only when the matrix of
+8 n^2 bytes does not fit in half of the free device memory --
+cluster_hierarchically_from_dist_matrix: SciPy's average linkage (:197-232),
+the same third-party routine the reference calls.
 """
 from collections import defaultdict
 import logging
@@ -70,6 +75,45 @@ def cluster_hierarchically_from_dist_matrix(dist_matrix, threshold):
     numbers = list(range(min(members), max(members) + 1))
     numbers.sort(key=lambda c: len(members[c]), reverse=True)   # stable
     return [members[c] for c in numbers]
+
+
+def _clusters_from_labels(labels):
+    """Flat cluster numbers (fcluster's, 1-based) -> member lists in ascending
+    index, largest cluster first, ties in cluster number (what
+    cluster_hierarchically_from_dist_matrix makes of them)."""
+    labels = np.asarray(labels, dtype=np.int64)
+    by_label = np.argsort(labels, kind="stable")
+    counts = np.bincount(labels)[1:]
+    assert counts.size and counts.min() > 0           # (fcluster numbers its clusters 1 .. k without gaps)
+    ends = np.cumsum(counts)
+    members = [by_label[a:b].tolist() for a, b in zip((ends - counts).tolist(), ends.tolist())]
+    members.sort(key=len, reverse=True)   # stable
+    return members
+
+
+def cluster_hierarchically_on_device(dist_matrix, threshold, ctx=None, return_merges=False):
+    """cluster_hierarchically_from_dist_matrix for an arbitrary float32
+    condensed matrix, computed on the device (catch_amd/csrc/linkage.hip): the
+    same clusters in the same order.  ValueError when the length is not
+    n (n - 1) / 2 or an entry is not finite, as SciPy raises.  return_merges:
+    also the linkage matrix, float64 (n - 1, 4), bit for bit SciPy's."""
+    import ctypes
+    from catch_amd import engine
+    dm = np.ascontiguousarray(dist_matrix, dtype=np.float32)
+    if dm.ndim != 1:
+        raise ValueError("the condensed distance matrix must be one-dimensional")
+    n = int(round((1.0 + np.sqrt(1.0 + 8.0 * dm.size)) / 2.0))
+    if n * (n - 1) // 2 != dm.size:
+        raise ValueError("the length of the condensed distance matrix (%d) is not n (n - 1) / 2" % dm.size)
+    if ctx is None:
+        ctx = engine.default_context()
+    labels = np.zeros(n, dtype=np.int32)
+    merges = np.zeros((max(n - 1, 1), 4), dtype=np.float64)
+    _lib.check(ctx._L.catchhip_linkage_average(
+        ctx._h, n, dm.ctypes.data_as(_lib.c_f32p) if dm.size else None, float(threshold),
+        labels.ctypes.data_as(_lib.c_i32p), merges.ctypes.data_as(_lib.c_f64p)))
+    clusters = _clusters_from_labels(labels)
+    return (clusters, merges[:n - 1]) if return_merges else clusters
 
 
 def _table_size_after_inserts(m):
@@ -502,8 +546,21 @@ def cluster_with_minhash_signatures(seqs, k=12, N=100, threshold=0.1,
                         num_seqs, jaccard_dist_threshold)
             # what the reference's c_float matrix holds: float32(1.0 - c / N)
             lut = (1.0 - np.arange(N + 1, dtype=np.float64) / float(N)).astype(np.float32)
-            clusters = cluster_hierarchically_from_dist_matrix(
-                sigs.condensed(lut), jaccard_dist_threshold)
+            t1 = _time.perf_counter()
+            max_n = _lib.test_env("CATCHHIP_LINKAGE_MAX_N")
+            if _lib.test_env("CATCHHIP_CLUSTER_HOST_LINKAGE") or (max_n is not None and num_seqs > int(max_n)) \
+                    or not sigs.linkage_fits():
+                # the float64 square matrix would take more than half of the free device memory (or a test
+                # asks for this path): the float32 condensed matrix and SciPy on the host
+                logger.info("Average linkage of %d sequences on the host", num_seqs)
+                dist_matrix = sigs.condensed(lut)
+                last_timings["condensed_s"] = _time.perf_counter() - t1
+                clusters = cluster_hierarchically_from_dist_matrix(dist_matrix, jaccard_dist_threshold)
+                last_timings["linkage"] = "host"
+            else:
+                clusters = sigs.linkage_clusters(lut, jaccard_dist_threshold)
+                last_timings["linkage"] = "device"
+            last_timings["linkage_s"] = _time.perf_counter() - t1
     finally:
         sigs.close()
     last_timings["total_s"] = _time.perf_counter() - t0

@@ -640,6 +640,23 @@ int catchhip_pyintset_list(catchhip_pyintset *s, int32_t which, const uint32_t *
  * roundings of 1.0 - c / N, which is what the reference's c_float array holds). */
 int catchhip_sigs_condensed(catchhip_ctx *ctx, const catchhip_sigs *sigs,
                             const float *lut, float *out);
+/* cluster.cluster_hierarchically_from_dist_matrix (catch/utils/cluster.py:197-232) on the device: SciPy's
+ * linkage(method="average") -- the nearest-neighbour chain in float64 with its tie rules, one persistent workgroup --
+ * and fcluster(criterion="distance") at `threshold`.  The distances are those of catchhip_sigs_condensed
+ * ((double)lut[common(i, j)]; the float32 matrix is never written), or a caller's float32 condensed matrix of n points,
+ * n (n - 1) / 2 entries, all finite (CATCHHIP_EINVAL otherwise, as SciPy raises ValueError).  labels[n]: SciPy's
+ * 1-based flat cluster numbers.  merges[(n - 1) * 4] (may be null): the linkage matrix as SciPy returns it -- sorted
+ * by height (stable), relabelled so that merge k creates node n + k.  Needs 8 n^2 bytes of device memory. */
+int catchhip_sigs_linkage_average(catchhip_ctx *ctx, const catchhip_sigs *sigs, const float *lut,
+                                  double threshold, int32_t *labels, double *merges);
+int catchhip_linkage_average(catchhip_ctx *ctx, int64_t n, const float *condensed, double threshold,
+                             int32_t *labels, double *merges);
+/* The host part of the two by itself (no device): merges[(n - 1) * 4] = (x, y, height, size) per merge in the order
+ * the chain made them, x and y the points that stand for the two clusters -> labels[n] and sorted[(n - 1) * 4]
+ * (may be null) as above. */
+int catchhip_linkage_labels(int64_t n, const double *merges, double threshold, int32_t *labels, double *sorted);
+/* *fits = 1 when the float64 square matrix of n points takes at most half of the device memory that is free now. */
+int catchhip_linkage_fits(catchhip_ctx *ctx, int64_t n, int32_t *fits);
 
 /* ---- scan with first-discovery keys (next row: catch/filter/adapter_filter.py)
  * catchhip_cover_scan, plus for every row the key that orders probes the way

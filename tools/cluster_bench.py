@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Timing of the clustering pre-step (catch_amd/csrc/cluster.hip) on a synthetic
 input: signatures, one distance row, the condensed matrix, and the whole
-cluster_with_minhash_signatures for both methods.
+cluster_with_minhash_signatures for both methods -- the hierarchical one with
+the average linkage on the device and on the host (CATCHHIP_CLUSTER_HOST_LINKAGE),
+and the linkage stage alone for both.
 
     python tools/cluster_bench.py [--workload S4] [--scale 0.25] [--fragment 50000]
 """
@@ -31,6 +33,9 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=200000,
                     help="bases hashed by a hashlib loop for comparison (0 = skip)")
     ap.add_argument("--hierarchical-max", type=int, default=12000)
+    ap.add_argument("--max-sequences", type=int, default=0,
+                    help="cluster only the first so many fragments (0 = all): a chosen n for the linkage timings")
+    ap.add_argument("--repeat", type=int, default=3, help="runs of every clustering; the best is reported")
     a = ap.parse_args()
     groups = synthetic.dataset(a.workload, scale=a.scale)
     seqs = []
@@ -71,15 +76,46 @@ def main():
         out["pairs_per_s"] = dm.size / (out["condensed_kernel_ms"] * 1e-3)
     sigs.close()
     named = dict(enumerate(seqs))
-    for method in ("simple", "hierarchical"):
-        if method == "hierarchical" and len(seqs) > a.hierarchical_max:
-            continue
-        random.seed(1)
-        t0 = time.perf_counter()
-        cl = cluster.cluster_with_minhash_signatures(named, threshold=0.15, cluster_method=method)
-        out[method + "_wall_s"] = time.perf_counter() - t0
-        out[method + "_clusters"] = len(cl)
-        out[method + "_largest"] = [len(c) for c in cl[:5]]
+    if a.max_sequences and len(seqs) > a.max_sequences:
+        named = dict(enumerate(seqs[:a.max_sequences]))
+    out["clustered_sequences"] = len(named)
+    # (method, key prefix, environment): the hierarchical method with the linkage on the device and, under the
+    # CATCHHIP_CLUSTER_HOST_LINKAGE test hook, on the host (condensed float32 matrix + SciPy: the path until now)
+    runs = [("simple", "simple", {})]
+    if len(named) <= a.hierarchical_max:
+        runs += [("hierarchical", "hierarchical", {}),
+                 ("hierarchical", "hierarchical_host", {"CATCHHIP_CLUSTER_HOST_LINKAGE": "1"})]
+    os.environ["CATCHHIP_TEST_HOOKS"] = "1"
+    for method, key, env in runs:
+        walls, stages = [], []
+        for _ in range(max(1, a.repeat)):
+            for k, v in env.items():
+                os.environ[k] = v
+            try:
+                random.seed(1)
+                t0 = time.perf_counter()
+                cl = cluster.cluster_with_minhash_signatures(named, threshold=0.15, cluster_method=method)
+                walls.append(time.perf_counter() - t0)
+            finally:
+                for k in env:
+                    os.environ.pop(k, None)
+            stages.append(dict(cluster.last_timings, kernel_ms=ctx.kernel_ms(PHASE_NDF)[0]))
+        out[key + "_wall_s"] = min(walls)                      # best of --repeat (the first run is the cold one)
+        out[key + "_wall_s_all"] = walls
+        out[key + "_clusters"] = len(cl)
+        out[key + "_largest"] = [len(c) for c in cl[:5]]
+        if method == "hierarchical":
+            # the linkage stage alone: distances + linkage + flat clusters (everything after the signatures)
+            out[key + "_linkage"] = stages[-1]["linkage"]
+            out[key + "_linkage_s"] = min(s["linkage_s"] for s in stages)
+            if stages[-1]["linkage"] == "device":       # matrix fill + chain, by the device's events
+                out[key + "_linkage_kernel_ms"] = min(s["kernel_ms"] for s in stages)
+            if "condensed_s" in stages[-1]:
+                out[key + "_condensed_s"] = min(s["condensed_s"] for s in stages)
+            out[key + "_result"] = [len(c) for c in cl]
+    if "hierarchical_result" in out:
+        out["hierarchical_paths_agree"] = out.pop("hierarchical_result") == out.pop("hierarchical_host_result")
+        out["linkage_host_over_device"] = out["hierarchical_host_linkage_s"] / out["hierarchical_linkage_s"]
     if a.cpu_sample:
         import hashlib
         import heapq
