@@ -239,13 +239,6 @@ static int cand_scan(catchhip_ctx *ctx, DevBuf<u32> &flag, DevBuf<u32> &out, i64
     return chip_exclusive_scan_u32(ctx, flag.p, out.p, n_plus_1, tmp);
 }
 
-static int cand_read_u32(catchhip_ctx *ctx, const u32 *d, u32 *out) {
-    HIP_TRY(hipMemcpyAsync(ctx->h_pin, d, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *out = *(volatile u32 *)ctx->h_pin;
-    return 0;
-}
-
 static int candidates_build(catchhip_ctx *ctx, const catchhip_targets *T, u32 L, u32 stride, i64 skip_len,
                             catchhip_candidates *C) {
     hipStream_t s = ctx->stream;
@@ -265,8 +258,8 @@ static int candidates_build(catchhip_ctx *ctx, const catchhip_targets *T, u32 L,
     TRY(cand_scan(ctx, nwin, win_off, (i64)nseq + 1, tmp));
     TRY(cand_scan(ctx, nslot, slot_off, (i64)nseq + 1, tmp));
     u32 nwin_total = 0, nslot_total = 0;
-    TRY(cand_read_u32(ctx, win_off.p + nseq, &nwin_total));
-    TRY(cand_read_u32(ctx, slot_off.p + nseq, &nslot_total));
+    TRY(read_count(ctx, win_off.p + nseq, &nwin_total));
+    TRY(read_count(ctx, slot_off.p + nseq, &nslot_total));
     tm.launch(12);
     C->ncand = 0;
     C->nuniq = 0;
@@ -285,7 +278,7 @@ static int candidates_build(catchhip_ctx *ctx, const catchhip_targets *T, u32 L,
                        (const u32 *)slots.p, nslot_total, flag.p);
     TRY(cand_scan(ctx, flag, at, (i64)nslot_total + 1, tmp));
     u32 ncand = 0;
-    TRY(cand_read_u32(ctx, at.p + nslot_total, &ncand));
+    TRY(read_count(ctx, at.p + nslot_total, &ncand));
     tm.launch(6);
     C->ncand = ncand;
     if (ncand == 0) { tm.finish(); return 0; }
@@ -328,7 +321,7 @@ static int candidates_build(catchhip_ctx *ctx, const catchhip_targets *T, u32 L,
                        (const u32 *)runid.p, (const u32 *)head.p, ncand, L, keep.p, cmult.p, cg);
     TRY(cand_scan(ctx, keep, kat, (i64)ncand + 1, tmp));
     u32 nuniq = 0;
-    TRY(cand_read_u32(ctx, kat.p + ncand, &nuniq));
+    TRY(read_count(ctx, kat.p + ncand, &nuniq));
     C->nuniq = nuniq;
     TRY(C->upos.alloc((size_t)nuniq + 1));
     TRY(C->mult.alloc((size_t)nuniq + 1));
@@ -366,17 +359,16 @@ extern "C" int catchhip_candidates_create(catchhip_ctx *ctx, const catchhip_targ
             return CATCHHIP_EINVAL;
         }
     }
-    catchhip_candidates *C = new catchhip_candidates();
+    std::unique_ptr<catchhip_candidates> C(new catchhip_candidates());
     C->ctx = ctx;
     C->T = T;
     C->L = probe_length;
     C->grouped = T->has_groups;
     C->ngroups = T->ngroups_set;
-    int rc = T->total ? candidates_build(ctx, T, (u32)probe_length, (u32)probe_stride, seq_length_to_skip, C) : 0;
-    if (rc) { delete C; return rc; }
+    if (T->total) TRY(candidates_build(ctx, T, (u32)probe_length, (u32)probe_stride, seq_length_to_skip, C.get()));
     if (ncandidates) *ncandidates = C->ncand;
     if (nunique) *nunique = C->nuniq;
-    *out = C;
+    *out = C.release();
     return 0;
 }
 
@@ -423,7 +415,7 @@ int chip_candidates_keep_flagged(catchhip_ctx *ctx, catchhip_candidates *C, DevB
     HIP_TRY(hipMemsetAsync(flag.p + n, 0, sizeof(u32), s));
     TRY(cand_scan(ctx, flag, at, (i64)n + 1, tmp));
     u32 nk = 0;
-    TRY(cand_read_u32(ctx, at.p + n, &nk));
+    TRY(read_count(ctx, at.p + n, &nk));
     const dim3 grid((unsigned)div_up((i64)n, 256)), block(256);
     TRY(pos.alloc((size_t)nk + 1));
     TRY(mult.alloc((size_t)nk + 1));
@@ -703,7 +695,7 @@ static int cand_apply_keep(catchhip_ctx *ctx, catchhip_candidates *C, DevBuf<u32
     HIP_TRY(hipMemsetAsync(flag.p + n, 0, sizeof(u32), s));
     TRY(cand_scan(ctx, flag, at, (i64)n + 1, tmp));
     u32 nk = 0;
-    TRY(cand_read_u32(ctx, at.p + n, &nk));
+    TRY(read_count(ctx, at.p + n, &nk));
     TRY(out.alloc((size_t)nk + 1));
     hipLaunchKernelGGL(cand_compact_kernel, dim3((unsigned)div_up((i64)n, 256)), dim3(256), 0, s,
                        (const u32 *)opos.p, (const u32 *)flag.p, (const u32 *)at.p, n, out.p);
@@ -874,7 +866,7 @@ static int probes_from_candidates_impl(catchhip_ctx *ctx, const catchhip_candida
                            (const u8 *)d_draws.p, (u32)n, (u32)m, d_cnt.p);
         TRY(cand_scan(ctx, d_cnt, d_ptr, n + 1, d_tmp));
         u32 total_ent = 0;
-        TRY(cand_read_u32(ctx, d_ptr.p + n, &total_ent));
+        TRY(read_count(ctx, d_ptr.p + n, &total_ent));
         nent = total_ent;
     } else if (pigeon) {
         ARG_CHECK(L % k == 0);
@@ -890,7 +882,7 @@ static int probes_from_candidates_impl(catchhip_ctx *ctx, const catchhip_candida
             }
         }
     }
-    catchhip_probes *p = new catchhip_probes();
+    std::unique_ptr<catchhip_probes> p(new catchhip_probes());
     p->ctx = ctx;
     p->nprobes = n;
     p->total = n * L;
@@ -903,78 +895,65 @@ static int probes_from_candidates_impl(catchhip_ctx *ctx, const catchhip_candida
     p->has_n = C->T->has_n;
     p->sorted_unique = true;
     hipStream_t s = ctx->stream;
-    int rc = 0;
-    do {
-        if ((rc = p->bytes.alloc((size_t)p->total + 256)) || (rc = p->probe_off.alloc((size_t)n + 1)) ||
-            (rc = p->set_id.alloc((size_t)n + 1)) || (rc = p->bucket_of.alloc((size_t)n + 1)) ||
-            (rc = p->bucket_set.alloc((size_t)n + 1)) || (rc = p->ent_probe.alloc((size_t)nent + 1)) ||
-            (rc = p->ent_pos.alloc((size_t)nent + 1)) || (rc = p->sent_probe.alloc((size_t)nent + 1)) ||
-            (rc = p->sent_pos.alloc((size_t)nent + 1)) || (rc = p->ent_ptr.alloc((size_t)n + 1)))
-            break;
-        if (hipMemsetAsync(p->bytes.p, 0, (size_t)p->total + 256, s) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-        hipLaunchKernelGGL(cand_gather_kernel, dim3((unsigned)div_up(std::max<i64>(p->total, n + 1), 256)), dim3(256), 0,
-                           s, (const u8 *)C->T->bytes.p, (const u32 *)C->upos.p, (u32)n, (u32)L, p->bytes.p,
-                           p->probe_off.p, p->set_id.p, p->bucket_of.p, p->bucket_set.p);
-        p->bucket_identity = true;
-        if (draws) {
-            p->pigeonhole = false;
-            if (n) {
-                hipLaunchKernelGGL(cand_draws_fill_kernel, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, (const u8 *)d_draws.p,
-                                   (u32)n, (u32)m, (const u32 *)d_ptr.p, p->ent_probe.p, p->ent_pos.p, p->sent_probe.p, p->sent_pos.p);
-            }
-            if (hipMemcpyAsync(p->ent_ptr.p, d_ptr.p, sizeof(u32) * ((size_t)n + 1), hipMemcpyDeviceToDevice, s) != hipSuccess) {
-                rc = CATCHHIP_EHIP;
-                break;
-            }
-        } else if (pigeon) {
-            const u32 nanch = (u32)(L / k);
-            p->pigeonhole = n > 0;
-            hipLaunchKernelGGL(cand_pigeon_kernel, dim3((unsigned)div_up(std::max<i64>(nent, n + 1), 256)), dim3(256), 0,
-                               s, (u32)n, nanch, (u32)k, p->ent_probe.p, p->ent_pos.p, p->sent_probe.p, p->sent_pos.p,
-                               p->ent_ptr.p);
-        } else {
-            // given sorted by (probe, position): the sorted table is the table
-            std::vector<u32> ptr((size_t)n + 1, 0);
-            bool pg = n > 0 && L % k == 0 && nent == n * (L / k);
-            for (i64 e = 0; e < nent; ++e) {
-                ptr[(size_t)ent_probe[e] + 1]++;
-                if (pg && ent_pos[e] != (i32)((e % (L / k)) * k)) pg = false;
-            }
-            for (i64 i = 0; i < n; ++i) {
-                if (pg && ptr[(size_t)i + 1] != (u32)(L / k)) pg = false;
-                ptr[(size_t)i + 1] += ptr[(size_t)i];
-            }
-            p->pigeonhole = pg;
-            if (nent && (hipMemcpyAsync(p->ent_probe.p, ent_probe, sizeof(i32) * nent, hipMemcpyHostToDevice, s) != hipSuccess ||
-                         hipMemcpyAsync(p->ent_pos.p, ent_pos, sizeof(i32) * nent, hipMemcpyHostToDevice, s) != hipSuccess ||
-                         hipMemcpyAsync(p->sent_probe.p, ent_probe, sizeof(i32) * nent, hipMemcpyHostToDevice, s) != hipSuccess ||
-                         hipMemcpyAsync(p->sent_pos.p, ent_pos, sizeof(i32) * nent, hipMemcpyHostToDevice, s) != hipSuccess)) {
-                rc = CATCHHIP_EHIP;
-                break;
-            }
-            if (hipMemcpyAsync(p->ent_ptr.p, ptr.data(), sizeof(u32) * ((size_t)n + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess) {
-                rc = CATCHHIP_EHIP;
-                break;
-            }
+    TRY(p->bytes.alloc((size_t)p->total + 256));
+    TRY(p->probe_off.alloc((size_t)n + 1));
+    TRY(p->set_id.alloc((size_t)n + 1));
+    TRY(p->bucket_of.alloc((size_t)n + 1));
+    TRY(p->bucket_set.alloc((size_t)n + 1));
+    TRY(p->ent_probe.alloc((size_t)nent + 1));
+    TRY(p->ent_pos.alloc((size_t)nent + 1));
+    TRY(p->sent_probe.alloc((size_t)nent + 1));
+    TRY(p->sent_pos.alloc((size_t)nent + 1));
+    TRY(p->ent_ptr.alloc((size_t)n + 1));
+    HIP_TRY(hipMemsetAsync(p->bytes.p, 0, (size_t)p->total + 256, s));
+    hipLaunchKernelGGL(cand_gather_kernel, dim3((unsigned)div_up(std::max<i64>(p->total, n + 1), 256)), dim3(256), 0,
+                       s, (const u8 *)C->T->bytes.p, (const u32 *)C->upos.p, (u32)n, (u32)L, p->bytes.p,
+                       p->probe_off.p, p->set_id.p, p->bucket_of.p, p->bucket_set.p);
+    p->bucket_identity = true;
+    if (draws) {
+        p->pigeonhole = false;
+        if (n) {
+            hipLaunchKernelGGL(cand_draws_fill_kernel, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, (const u8 *)d_draws.p,
+                               (u32)n, (u32)m, (const u32 *)d_ptr.p, p->ent_probe.p, p->ent_pos.p, p->sent_probe.p, p->sent_pos.p);
         }
-        if (C->grouped) {   // the scans pair a probe only with its own group's genomes
-            if ((rc = p->group.alloc((size_t)n + 1))) break;
-            if (n && hipMemcpyAsync(p->group.p, C->ugrp.p, sizeof(u32) * (size_t)n, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-                rc = CATCHHIP_EHIP;
-                break;
-            }
-            p->has_groups = true;
+        HIP_TRY(hipMemcpyAsync(p->ent_ptr.p, d_ptr.p, sizeof(u32) * ((size_t)n + 1), hipMemcpyDeviceToDevice, s));
+    } else if (pigeon) {
+        const u32 nanch = (u32)(L / k);
+        p->pigeonhole = n > 0;
+        hipLaunchKernelGGL(cand_pigeon_kernel, dim3((unsigned)div_up(std::max<i64>(nent, n + 1), 256)), dim3(256), 0,
+                           s, (u32)n, nanch, (u32)k, p->ent_probe.p, p->ent_pos.p, p->sent_probe.p, p->sent_pos.p,
+                           p->ent_ptr.p);
+    } else {
+        // given sorted by (probe, position): the sorted table is the table
+        std::vector<u32> ptr((size_t)n + 1, 0);
+        bool pg = n > 0 && L % k == 0 && nent == n * (L / k);
+        for (i64 e = 0; e < nent; ++e) {
+            ptr[(size_t)ent_probe[e] + 1]++;
+            if (pg && ent_pos[e] != (i32)((e % (L / k)) * k)) pg = false;
         }
-        if ((rc = chip_probes_pack_planes(p))) break;
-        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-            chip_set_error("probes_from_candidates failed: %s", hipGetErrorString(hipGetLastError()));
-            rc = CATCHHIP_EHIP;
-            break;
+        for (i64 i = 0; i < n; ++i) {
+            if (pg && ptr[(size_t)i + 1] != (u32)(L / k)) pg = false;
+            ptr[(size_t)i + 1] += ptr[(size_t)i];
         }
-    } while (0);
-    if (rc) { delete p; return rc; }
-    *out = p;
+        p->pigeonhole = pg;
+        if (nent) {
+            HIP_TRY(hipMemcpyAsync(p->ent_probe.p, ent_probe, sizeof(i32) * nent, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(p->ent_pos.p, ent_pos, sizeof(i32) * nent, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(p->sent_probe.p, ent_probe, sizeof(i32) * nent, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(p->sent_pos.p, ent_pos, sizeof(i32) * nent, hipMemcpyHostToDevice, s));
+        }
+        HIP_TRY(hipMemcpyAsync(p->ent_ptr.p, ptr.data(), sizeof(u32) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (C->grouped) {   // the scans pair a probe only with its own group's genomes
+        TRY(p->group.alloc((size_t)n + 1));
+        if (n) HIP_TRY(hipMemcpyAsync(p->group.p, C->ugrp.p, sizeof(u32) * (size_t)n, hipMemcpyDeviceToDevice, s));
+        p->has_groups = true;
+    }
+    TRY(chip_probes_pack_planes(p.get()));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    *out = p.release();
     return 0;
 }
 

@@ -181,9 +181,7 @@ extern "C" int catchhip_rows_cover_check(catchhip_ctx *ctx, const catchhip_rows 
                            (const u32 *)R->gs.p, (const u32 *)R->ge.p, nrows, (const u32 *)prank.p, nsets, U.p, flag.p, bad.p);
         HIP_TRY(hipMemsetAsync(flag.p + nrows, 0, sizeof(u32), s));
         TRY(chip_exclusive_scan_u32(ctx, flag.p, pos.p, (i64)nrows + 1, tmp));
-        HIP_TRY(hipMemcpyAsync(ctx->h_pin, pos.p + nrows, sizeof(u32), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        nkeys = *(volatile u32 *)ctx->h_pin;
+        TRY(read_count(ctx, pos.p + nrows, &nkeys));
     }
     TRY(keys.alloc(std::max<u32>(nkeys, 1)));
     TRY(vals.alloc(std::max<u32>(nkeys, 1)));

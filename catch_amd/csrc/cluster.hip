@@ -541,61 +541,49 @@ static int sigs_create_impl(catchhip_ctx *ctx, const u8 *bytes, const u64 *offse
     ARG_CHECK(a >= 1 && a <= MD5_P && b <= MD5_P);
     PoolScope pool_scope(ctx);
     *out = nullptr;
-    catchhip_sigs *S = new catchhip_sigs();
+    std::unique_ptr<catchhip_sigs> S(new catchhip_sigs());
     S->ctx = ctx;
     S->nseq = nseq;
     S->N = N;
-    if (nseq == 0) { *out = S; return 0; }
+    if (nseq == 0) { *out = S.release(); return 0; }
     const bool own_upload = std::is_same<Upload, SigsNoUpload>::value;
-    if (!((bytes || !own_upload) && offsets && offsets[0] == 0)) {
-        delete S;
-        ARG_CHECK((bytes || !own_upload) && offsets && offsets[0] == 0);
-    }
+    ARG_CHECK((bytes || !own_upload) && offsets && offsets[0] == 0);
     for (u32 s = 0; s < nseq; ++s) {
         // lsh.py:113 asserts kmer_size <= len(s)
         if (offsets[s + 1] < offsets[s] || offsets[s + 1] - offsets[s] < (u64)k) {
-            delete S;
             chip_set_error("signatures: sequence %u is shorter than the k-mer size %d", s, (int)k);
             return CATCHHIP_EINVAL;
         }
     }
     const u64 total = offsets[nseq];
-    int rc = 0;
-    do {
-        if ((rc = hipSetDevice(ctx->device) == hipSuccess ? 0 : CATCHHIP_EHIP)) break;
-        if ((rc = md5_table_upload(ctx))) break;
-        hipStream_t st = ctx->stream;
-        const u64 ntiles = (total + KM_TILE - 1) / KM_TILE;
-        DevBuf<u32> d_words, H;
-        DevBuf<u64> d_off;
-        const size_t padded = (size_t)ntiles * KM_TILE + 64;
-        if ((rc = d_words.alloc(padded / 4)) || (rc = H.alloc((size_t)total)) || (rc = d_off.alloc((size_t)nseq + 1)) ||
-            (rc = S->sig.alloc((size_t)nseq * N)) || (rc = S->sigT.alloc((size_t)nseq * N)))
-            break;
-#define CL_HIP(expr)                                                                        \
-    if ((expr) != hipSuccess) {                                                             \
-        chip_set_error("%s:%d: %s failed: %s", __FILE__, __LINE__, #expr, hipGetErrorString(hipGetLastError())); \
-        rc = CATCHHIP_EHIP;                                                                 \
-        break;                                                                              \
-    }
-        CL_HIP(hipMemsetAsync((u8 *)d_words.p + (total & ~(u64)3), 0, padded - (total & ~(u64)3), st));
-        if (own_upload) { CL_HIP(hipMemcpyAsync(d_words.p, bytes, total, hipMemcpyHostToDevice, st)); }
-        else if ((rc = upload((u8 *)d_words.p, st))) break;
-        CL_HIP(hipMemcpyAsync(d_off.p, offsets, sizeof(u64) * ((size_t)nseq + 1), hipMemcpyHostToDevice, st));
-        PhaseTimer tm(ctx, PHASE_NDF);
-        hipLaunchKernelGGL(kmer_md5_kernel, dim3((unsigned)ntiles), dim3(KM_THREADS), 0, st, (const u32 *)d_words.p,
-                           total, (int)k, (u32)(a % MD5_P), b, H.p);
-        hipLaunchKernelGGL(sig_select_kernel, dim3((unsigned)std::min<u64>(nseq, (u64)ctx->num_cus * 32)),
-                           dim3(SS_THREADS), 0, st, (const u32 *)H.p, (const u64 *)d_off.p, nseq, (int)k, N, S->sig.p);
-        hipLaunchKernelGGL(sig_transpose_kernel, dim3((nseq + 31) / 32, (N + 31) / 32), dim3(32, 8), 0, st,
-                           (const u32 *)S->sig.p, nseq, N, S->sigT.p);
-        tm.launch(3);
-        CL_HIP(hipGetLastError());
-        CL_HIP(hipStreamSynchronize(st));
-        tm.finish();
-    } while (0);
-    if (rc) { delete S; return rc; }
-    *out = S;
+    HIP_TRY(hipSetDevice(ctx->device));
+    TRY(md5_table_upload(ctx));
+    hipStream_t st = ctx->stream;
+    const u64 ntiles = (total + KM_TILE - 1) / KM_TILE;
+    DevBuf<u32> d_words, H;
+    DevBuf<u64> d_off;
+    const size_t padded = (size_t)ntiles * KM_TILE + 64;
+    TRY(d_words.alloc(padded / 4));
+    TRY(H.alloc((size_t)total));
+    TRY(d_off.alloc((size_t)nseq + 1));
+    TRY(S->sig.alloc((size_t)nseq * N));
+    TRY(S->sigT.alloc((size_t)nseq * N));
+    HIP_TRY(hipMemsetAsync((u8 *)d_words.p + (total & ~(u64)3), 0, padded - (total & ~(u64)3), st));
+    if (own_upload) HIP_TRY(hipMemcpyAsync(d_words.p, bytes, total, hipMemcpyHostToDevice, st));
+    else TRY(upload((u8 *)d_words.p, st));
+    HIP_TRY(hipMemcpyAsync(d_off.p, offsets, sizeof(u64) * ((size_t)nseq + 1), hipMemcpyHostToDevice, st));
+    PhaseTimer tm(ctx, PHASE_NDF);
+    hipLaunchKernelGGL(kmer_md5_kernel, dim3((unsigned)ntiles), dim3(KM_THREADS), 0, st, (const u32 *)d_words.p,
+                       total, (int)k, (u32)(a % MD5_P), b, H.p);
+    hipLaunchKernelGGL(sig_select_kernel, dim3((unsigned)std::min<u64>(nseq, (u64)ctx->num_cus * 32)),
+                       dim3(SS_THREADS), 0, st, (const u32 *)H.p, (const u64 *)d_off.p, nseq, (int)k, N, S->sig.p);
+    hipLaunchKernelGGL(sig_transpose_kernel, dim3((nseq + 31) / 32, (N + 31) / 32), dim3(32, 8), 0, st,
+                       (const u32 *)S->sig.p, nseq, N, S->sigT.p);
+    tm.launch(3);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    tm.finish();
+    *out = S.release();
     return 0;
 }
 
@@ -640,12 +628,11 @@ extern "C" int catchhip_sigs_create_ptrs(catchhip_ctx *ctx, const u8 *const *seq
         hipEvent_t ev[2] = {nullptr, nullptr};
         HIP_TRY(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
-        int rc = 0;
         const int nthreads = (int)std::max<u64>(1, std::min<u64>(8, total >> 21));
-        for (u64 c = 0, lo = 0; lo < total && !rc; ++c, lo += CH) {
+        auto chunk = [&](u64 c, u64 lo) -> int {
             const u64 hi = std::min<u64>(total, lo + CH);
             u8 *buf = pin + (c & 1) * CH;
-            if (c >= 2 && hipEventSynchronize(ev[c & 1]) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
+            if (c >= 2) HIP_TRY(hipEventSynchronize(ev[c & 1]));
             auto work = [&](int tix) {
                 const u64 a0 = lo + (hi - lo) * (u64)tix / (u64)nthreads, a1 = lo + (hi - lo) * (u64)(tix + 1) / (u64)nthreads;
                 if (a0 >= a1) return;
@@ -661,12 +648,14 @@ extern "C" int catchhip_sigs_create_ptrs(catchhip_ctx *ctx, const u8 *const *seq
                 for (int tix = 0; tix < nthreads; ++tix) th.emplace_back(work, tix);
                 for (auto &t : th) t.join();
             }
-            if (hipMemcpyAsync(dst + lo, buf, (size_t)(hi - lo), hipMemcpyHostToDevice, st) != hipSuccess ||
-                hipEventRecord(ev[c & 1], st) != hipSuccess) rc = CATCHHIP_EHIP;
-        }
-        if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = CATCHHIP_EHIP;      // (the pinned buffers are reused by others)
+            HIP_TRY(hipMemcpyAsync(dst + lo, buf, (size_t)(hi - lo), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipEventRecord(ev[c & 1], st));
+            return 0;
+        };
+        int rc = 0;
+        for (u64 c = 0, lo = 0; lo < total && !rc; ++c, lo += CH) rc = chunk(c, lo);
+        if (!rc) rc = catchhip_ctx_sync(ctx);      // (the pinned buffers are reused by others)
         (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-        if (rc) chip_set_error("signatures: upload failed");
         return rc;
     };
     return sigs_create_impl(ctx, nullptr, off.data(), nseq, k, N, a, b, out, upload);
@@ -824,9 +813,7 @@ extern "C" int catchhip_sigs_graph(catchhip_ctx *ctx, catchhip_sigs *S, u32 min_
                            (unsigned long long)cap, (unsigned long long *)d_n.p);
         tm.launch(1);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(ctx->h_pin, d_n.p, sizeof(u64), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        n = *(volatile u64 *)ctx->h_pin;
+        TRY(chip_read_back(ctx, d_n.p, sizeof(u64), &n));
         if (n + 1 < cap || n == 0) break;
         if (max_edges && n > (u64)max_edges) { tm.finish(); *nedges = (i64)n; return 0; }   // too many: the caller asks list by list
         if (attempt == 1) { chip_set_error("sigs_graph: edge count changed between two passes"); return CATCHHIP_EINVAL; }

@@ -70,11 +70,11 @@ static bool diff_iterates_ascending(u64 n, i64 m, i64 q) {
 extern "C" int catchhip_dfs_create(u32 n, const i64 *ptr, const u32 *idx, const u32 *com, u32 near_common,
                                    catchhip_dfs **out) {
     ARG_CHECK(out && ptr && n >= 1 && (ptr[n] == 0 || (idx && com)));
-    catchhip_dfs *d = new (std::nothrow) catchhip_dfs();
-    if (!d) return CATCHHIP_ENOMEM;
+    std::unique_ptr<catchhip_dfs> d(new (std::nothrow) catchhip_dfs());
+    if (!d) { chip_set_error("dfs_create: out of host memory"); return CATCHHIP_ENOMEM; }
     d->n = n; d->ptr = ptr; d->idx = idx; d->com = com; d->near_common = near_common;
     d->avail.assign(n, 1);
-    *out = d;
+    *out = d.release();
     return 0;
 }
 
@@ -299,11 +299,11 @@ struct catchhip_pyintset { PyIntSet s; u32 n = 0; std::vector<u32> out; };
 
 extern "C" int catchhip_pyintset_create(u32 n, catchhip_pyintset **out) {
     ARG_CHECK(out && n < PyIntSet::DUMMY);
-    catchhip_pyintset *h = new (std::nothrow) catchhip_pyintset();
-    if (!h) return CATCHHIP_ENOMEM;
+    std::unique_ptr<catchhip_pyintset> h(new (std::nothrow) catchhip_pyintset());
+    if (!h) { chip_set_error("pyintset_create: out of host memory"); return CATCHHIP_ENOMEM; }
     h->n = n;
     h->s.init_range(n);
-    *out = h;
+    *out = h.release();
     return 0;
 }
 extern "C" void catchhip_pyintset_destroy(catchhip_pyintset *h) { delete h; }

@@ -2,6 +2,7 @@
 #include <stdarg.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "internal.h"
@@ -73,6 +74,7 @@ static size_t pool_soft_limit() {
         // their peaks, and at 207 GB every step returned blocks to the driver and asked for them again -- 547 instead of ~400
         // hipMalloc calls in a three-step run and a step of 3.95-4.25 s instead of 3.3-3.45; a request that the driver cannot
         // serve still trims the cache and tries again, chip_pool_alloc below)
+        // (a failing query is an answer: no limit)
         soft_limit = (hipMemGetInfo(&fr, &tot) == hipSuccess && tot) ? (size_t)((double)tot * 0.87) : ~(size_t)0 >> 1;
         if (const char *e = getenv("CATCHHIP_POOL_SOFT_LIMIT_GB")) {
             const double gb = atof(e);
@@ -138,7 +140,7 @@ void *chip_pool_alloc(size_t bytes) {
     void *p = nullptr;
     hipError_t e = hipMalloc(&p, cls);
     g_pool_stats[0]++;
-    if (e != hipSuccess) {
+    if (e != hipSuccess) {   // not yet an error: the retry below decides
         g_pool_stats[3]++;
         // give this owner's cached blocks back to the driver and retry once
         // (other owners' blocks may still be referenced by queued work)
@@ -154,7 +156,7 @@ void *chip_pool_alloc(size_t bytes) {
             }
         }
         e = hipMalloc(&p, cls);
-        if (e != hipSuccess) {
+        if (e != hipSuccess) {   // returns a null pointer, not a code: DevBuf::alloc makes it CATCHHIP_ENOMEM
             chip_set_error("hipMalloc(%zu bytes) failed: %s", cls, hipGetErrorString(e));
             return nullptr;
         }
@@ -215,7 +217,7 @@ extern "C" int catchhip_device_count(int *count) {
     ARG_CHECK(count != nullptr);
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) {
+    if (e != hipSuccess) {   // also an answer: the caller gets a count of 0 with the code
         *count = 0;
         chip_set_error("hipGetDeviceCount: %s", hipGetErrorString(e));
         return CATCHHIP_EHIP;
@@ -224,33 +226,37 @@ extern "C" int catchhip_device_count(int *count) {
     return 0;
 }
 
+// pinned host memory; a refusal is CATCHHIP_ENOMEM, as for device memory
+static int chip_host_alloc(void **p, size_t bytes) {
+    const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) {   // the code differs from HIP_TRY's
+        chip_set_error("hipHostMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        return CATCHHIP_ENOMEM;
+    }
+    return 0;
+}
+
 extern "C" int catchhip_ctx_create(int device, catchhip_ctx **out) {
     ARG_CHECK(out != nullptr);
     *out = nullptr;
     HIP_TRY(hipSetDevice(device));
-    catchhip_ctx *c = new catchhip_ctx();
+    std::unique_ptr<catchhip_ctx> c(new catchhip_ctx());
     c->device = device;
     hipDeviceProp_t prop;
+    // (a failing query is an answer: the default CU count stays)
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->num_cus = prop.multiProcessorCount;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        chip_set_error("hipStreamCreate failed");
-        return CATCHHIP_EHIP;
-    }
+    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (int i = 0; i < 2 * NPHASE; ++i) (void)hipEventCreate(&c->ev[i]);
     for (int i = 0; i < 2 * CHIP_EVX; ++i) (void)hipEventCreate(&c->evx[i]);
-    if (hipHostMalloc((void **)&c->h_pin, 64 * sizeof(u64), hipHostMallocDefault) != hipSuccess) {
-        chip_set_error("hipHostMalloc failed");
-        delete c;
-        return CATCHHIP_ENOMEM;
-    }
-    *out = c;
+    TRY(chip_host_alloc((void **)&c->h_pin, 64 * sizeof(u64)));
+    *out = c.release();
     return 0;
 }
 
 void chip_phase_collect(catchhip_ctx *c, int phase) {
     float ms = 0.f;
     (void)hipEventSynchronize(c->ev[2 * phase + 1]);
+    // (timing is best effort: a failing query leaves the phase's time as it was)
     if (hipEventElapsedTime(&ms, c->ev[2 * phase], c->ev[2 * phase + 1]) == hipSuccess) c->phase_ms[phase] = ms;
 }
 
@@ -259,10 +265,7 @@ int chip_pinned_reserve(catchhip_ctx *c, size_t bytes) {
     size_t want = std::max<size_t>(bytes, (size_t)1 << 20);
     want = (want + 4095) & ~(size_t)4095;
     if (c->h_big) { (void)hipStreamSynchronize(c->stream); (void)hipHostFree(c->h_big); c->h_big = nullptr; c->h_big_bytes = 0; }
-    if (hipHostMalloc(&c->h_big, want, hipHostMallocDefault) != hipSuccess) {
-        chip_set_error("hipHostMalloc(%zu) failed", want);
-        return CATCHHIP_ENOMEM;
-    }
+    TRY(chip_host_alloc(&c->h_big, want));
     c->h_big_bytes = want;
     return 0;
 }
@@ -431,7 +434,7 @@ static int targets_create_impl(catchhip_ctx *ctx, const u8 *bytes, const i64 *se
         chip_set_error("targets larger than 2^32 bases per group are not supported");
         return CATCHHIP_EINVAL;
     }
-    catchhip_targets *t = new catchhip_targets();
+    std::unique_ptr<catchhip_targets> t(new catchhip_targets());
     t->ctx = ctx;
     t->total = total;
     t->nseq = nseq;
@@ -447,7 +450,6 @@ static int targets_create_impl(catchhip_ctx *ctx, const u8 *bytes, const i64 *se
         i64 len = seq_off[i + 1] - seq_off[i];
         i32 g = seq_genome[i];
         if (len < 0 || g < prev || g < 0 || g >= ngenomes) {
-            delete t;
             chip_set_error("targets: bad seq_off / seq_genome (must be non-decreasing)");
             return CATCHHIP_EINVAL;
         }
@@ -464,44 +466,33 @@ static int targets_create_impl(catchhip_ctx *ctx, const u8 *bytes, const i64 *se
     if (alpha) { t->dna5 = alpha[0]; t->has_n = alpha[1]; }
     else alphabet_scan(bytes, total, &t->dna5, &t->has_n);
 
-    int rc = 0;
-    do {
-        if ((rc = t->bytes.alloc((size_t)total + 256))) break;
-        if ((rc = t->seq_off.alloc((size_t)nseq + 1))) break;
-        if ((rc = t->seq_genome.alloc((size_t)nseq))) break;
-        if ((rc = t->genome_off.alloc((size_t)ngenomes + 1))) break;
-        hipStream_t s = ctx->stream;
-        if (hipMemsetAsync(t->bytes.p, 0, (size_t)total + 256, s) != hipSuccess ||
-            (total && hipMemcpyAsync(t->bytes.p, bytes, (size_t)total, hipMemcpyHostToDevice, s) != hipSuccess) ||
-            hipMemcpyAsync(t->seq_off.p, so32.data(), sizeof(u32) * (nseq + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
-            (nseq && hipMemcpyAsync(t->seq_genome.p, seq_genome, sizeof(i32) * nseq, hipMemcpyHostToDevice, s) != hipSuccess) ||
-            hipMemcpyAsync(t->genome_off.p, go32.data(), sizeof(u32) * (ngenomes + 1), hipMemcpyHostToDevice, s) != hipSuccess) {
-            chip_set_error("targets upload failed");
-            rc = CATCHHIP_EHIP;
-            break;
+    TRY(t->bytes.alloc((size_t)total + 256));
+    TRY(t->seq_off.alloc((size_t)nseq + 1));
+    TRY(t->seq_genome.alloc((size_t)nseq));
+    TRY(t->genome_off.alloc((size_t)ngenomes + 1));
+    hipStream_t s = ctx->stream;
+    HIP_TRY(hipMemsetAsync(t->bytes.p, 0, (size_t)total + 256, s));
+    if (total) HIP_TRY(hipMemcpyAsync(t->bytes.p, bytes, (size_t)total, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(t->seq_off.p, so32.data(), sizeof(u32) * (nseq + 1), hipMemcpyHostToDevice, s));
+    if (nseq) HIP_TRY(hipMemcpyAsync(t->seq_genome.p, seq_genome, sizeof(i32) * nseq, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(t->genome_off.p, go32.data(), sizeof(u32) * (ngenomes + 1), hipMemcpyHostToDevice, s));
+    if (t->dna5) {
+        // room for a whole scan tile of overhang beyond the last base
+        t->nwords = (total + 8192) / 32 + 64;
+        TRY(t->planes.alloc((size_t)t->nwords * 3));
+        HIP_TRY(hipMemsetAsync(t->planes.p, 0, sizeof(u32) * t->nwords * 3, s));
+        TRY(t->tq.alloc((size_t)t->nwords));
+        HIP_TRY(hipMemsetAsync(t->tq.p, 0, sizeof(uint4) * t->nwords, s));
+        if (total) {
+            i64 chunks = (total + 63) / 64;
+            unsigned blocks = (unsigned)(chunks < 4 * 2048 ? div_up(chunks, 4) : 2048);
+            hipLaunchKernelGGL(pack_targets_kernel, dim3(blocks), dim3(256), 0, s, t->bytes.p, total,
+                               t->planes.p, t->nwords, t->tq.p);
         }
-        if (t->dna5) {
-            // room for a whole scan tile of overhang beyond the last base
-            t->nwords = (total + 8192) / 32 + 64;
-            if ((rc = t->planes.alloc((size_t)t->nwords * 3))) break;
-            if (hipMemsetAsync(t->planes.p, 0, sizeof(u32) * t->nwords * 3, s) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-            if ((rc = t->tq.alloc((size_t)t->nwords))) break;
-            if (hipMemsetAsync(t->tq.p, 0, sizeof(uint4) * t->nwords, s) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-            if (total) {
-                i64 chunks = (total + 63) / 64;
-                unsigned blocks = (unsigned)(chunks < 4 * 2048 ? div_up(chunks, 4) : 2048);
-                hipLaunchKernelGGL(pack_targets_kernel, dim3(blocks), dim3(256), 0, s, t->bytes.p, total,
-                                   t->planes.p, t->nwords, t->tq.p);
-            }
-        }
-        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-            chip_set_error("targets pack failed");
-            rc = CATCHHIP_EHIP;
-            break;
-        }
-    } while (0);
-    if (rc) { delete t; return rc; }
-    *out = t;
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    *out = t.release();
     return 0;
 }
 
@@ -646,7 +637,7 @@ extern "C" int catchhip_probes_create(catchhip_ctx *ctx, const u8 *bytes, const 
     HIP_TRY(hipSetDevice(ctx->device));
     i64 total = probe_off[nprobes];
     ARG_CHECK(probe_off[0] == 0 && total >= 0 && total < ((i64)1 << 31));
-    catchhip_probes *p = new catchhip_probes();
+    std::unique_ptr<catchhip_probes> p(new catchhip_probes());
     p->ctx = ctx;
     p->nprobes = nprobes;
     p->total = total;
@@ -657,9 +648,9 @@ extern "C" int catchhip_probes_create(catchhip_ctx *ctx, const u8 *bytes, const 
     for (i64 i = 0; i <= nprobes; ++i) po32[i] = (u32)probe_off[i];
     for (i64 i = 0; i < nprobes; ++i) {
         i64 len = probe_off[i + 1] - probe_off[i];
-        if (set_id[i] < 0) { delete p; chip_set_error("probes: negative set id"); return CATCHHIP_EINVAL; }
+        if (set_id[i] < 0) { chip_set_error("probes: negative set id"); return CATCHHIP_EINVAL; }
         if (set_id[i] > p->max_set_id) p->max_set_id = set_id[i];
-        if (len <= 0) { delete p; chip_set_error("probes: empty probe"); return CATCHHIP_EINVAL; }
+        if (len <= 0) { chip_set_error("probes: empty probe"); return CATCHHIP_EINVAL; }
         if (len != p->L) p->L = -1;
     }
     // anchors must lie inside their probe
@@ -668,7 +659,6 @@ extern "C" int catchhip_probes_create(catchhip_ctx *ctx, const u8 *bytes, const 
     for (i64 e = 0; e < nent; ++e) {
         i32 q = ent_probe[e], a = ent_pos[e];
         if (q < 0 || q >= nprobes || a < 0 || a + k > probe_off[q + 1] - probe_off[q]) {
-            delete p;
             chip_set_error("probes: anchor %lld out of range", (long long)e);
             return CATCHHIP_EINVAL;
         }
@@ -691,70 +681,55 @@ extern "C" int catchhip_probes_create(catchhip_ctx *ctx, const u8 *bytes, const 
             p->sorted_unique = false;
     alphabet_scan(bytes, total, &p->dna5, &p->has_n);
 
-    int rc = 0;
-    do {
-        hipStream_t s = ctx->stream;
-        if ((rc = p->bytes.alloc((size_t)total + 256))) break;
-        if ((rc = p->probe_off.alloc((size_t)nprobes + 1))) break;
-        if ((rc = p->set_id.alloc((size_t)nprobes))) break;
-        if ((rc = p->ent_probe.alloc((size_t)nent))) break;
-        if ((rc = p->ent_pos.alloc((size_t)nent))) break;
-        if (hipMemsetAsync(p->bytes.p, 0, (size_t)total + 256, s) != hipSuccess ||
-            (total && hipMemcpyAsync(p->bytes.p, bytes, (size_t)total, hipMemcpyHostToDevice, s) != hipSuccess) ||
-            hipMemcpyAsync(p->probe_off.p, po32.data(), sizeof(u32) * (nprobes + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
-            (nprobes && hipMemcpyAsync(p->set_id.p, set_id, sizeof(i32) * nprobes, hipMemcpyHostToDevice, s) != hipSuccess) ||
-            (nent && hipMemcpyAsync(p->ent_probe.p, ent_probe, sizeof(i32) * nent, hipMemcpyHostToDevice, s) != hipSuccess) ||
-            (nent && hipMemcpyAsync(p->ent_pos.p, ent_pos, sizeof(i32) * nent, hipMemcpyHostToDevice, s) != hipSuccess)) {
-            chip_set_error("probes upload failed");
-            rc = CATCHHIP_EHIP;
-            break;
+    hipStream_t s = ctx->stream;
+    TRY(p->bytes.alloc((size_t)total + 256));
+    TRY(p->probe_off.alloc((size_t)nprobes + 1));
+    TRY(p->set_id.alloc((size_t)nprobes));
+    TRY(p->ent_probe.alloc((size_t)nent));
+    TRY(p->ent_pos.alloc((size_t)nent));
+    HIP_TRY(hipMemsetAsync(p->bytes.p, 0, (size_t)total + 256, s));
+    if (total) HIP_TRY(hipMemcpyAsync(p->bytes.p, bytes, (size_t)total, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(p->probe_off.p, po32.data(), sizeof(u32) * (nprobes + 1), hipMemcpyHostToDevice, s));
+    if (nprobes) HIP_TRY(hipMemcpyAsync(p->set_id.p, set_id, sizeof(i32) * nprobes, hipMemcpyHostToDevice, s));
+    if (nent) {
+        HIP_TRY(hipMemcpyAsync(p->ent_probe.p, ent_probe, sizeof(i32) * nent, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->ent_pos.p, ent_pos, sizeof(i32) * nent, hipMemcpyHostToDevice, s));
+    }
+    {   // buckets of the row build: unique probes grouped by set id, in set-id order
+        std::vector<i32> ids(set_id, set_id + nprobes);
+        std::sort(ids.begin(), ids.end());
+        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        p->nbuckets = (i64)ids.size();
+        std::vector<u32> bo((size_t)nprobes);
+        for (i64 i = 0; i < nprobes; ++i)
+            bo[i] = (u32)(std::lower_bound(ids.begin(), ids.end(), set_id[i]) - ids.begin());
+        TRY(p->bucket_of.alloc((size_t)nprobes + 1));
+        TRY(p->bucket_set.alloc(ids.size() + 1));
+        if (nprobes) {
+            HIP_TRY(hipMemcpyAsync(p->bucket_of.p, bo.data(), sizeof(u32) * nprobes, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(p->bucket_set.p, ids.data(), sizeof(i32) * ids.size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));
         }
-        {   // buckets of the row build: unique probes grouped by set id, in set-id order
-            std::vector<i32> ids(set_id, set_id + nprobes);
-            std::sort(ids.begin(), ids.end());
-            ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-            p->nbuckets = (i64)ids.size();
-            std::vector<u32> bo((size_t)nprobes);
-            for (i64 i = 0; i < nprobes; ++i)
-                bo[i] = (u32)(std::lower_bound(ids.begin(), ids.end(), set_id[i]) - ids.begin());
-            if ((rc = p->bucket_of.alloc((size_t)nprobes + 1))) break;
-            if ((rc = p->bucket_set.alloc(ids.size() + 1))) break;
-            if (nprobes && (hipMemcpyAsync(p->bucket_of.p, bo.data(), sizeof(u32) * nprobes, hipMemcpyHostToDevice, s) != hipSuccess ||
-                            hipMemcpyAsync(p->bucket_set.p, ids.data(), sizeof(i32) * ids.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
-                            hipStreamSynchronize(s) != hipSuccess)) {
-                chip_set_error("probes upload failed");
-                rc = CATCHHIP_EHIP;
-                break;
-            }
-        }
-        if (nent) {   // anchors grouped by probe, ascending position
-            std::vector<u64> key((size_t)nent);
-            for (i64 e = 0; e < nent; ++e) key[e] = ((u64)(u32)ent_probe[e] << 32) | (u32)ent_pos[e];
-            std::sort(key.begin(), key.end());
-            std::vector<u32> sp((size_t)nent), so((size_t)nent), ptr((size_t)nprobes + 1, 0);
-            for (i64 e = 0; e < nent; ++e) { sp[e] = (u32)(key[e] >> 32); so[e] = (u32)key[e]; ptr[sp[e] + 1]++; }
-            for (i64 i = 0; i < nprobes; ++i) ptr[i + 1] += ptr[i];
-            if ((rc = p->sent_probe.alloc((size_t)nent))) break;
-            if ((rc = p->sent_pos.alloc((size_t)nent))) break;
-            if ((rc = p->ent_ptr.alloc((size_t)nprobes + 1))) break;
-            if (hipMemcpyAsync(p->sent_probe.p, sp.data(), sizeof(u32) * nent, hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(p->sent_pos.p, so.data(), sizeof(u32) * nent, hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(p->ent_ptr.p, ptr.data(), sizeof(u32) * (nprobes + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess) {
-                chip_set_error("probes upload failed");
-                rc = CATCHHIP_EHIP;
-                break;
-            }
-        }
-        if ((rc = chip_probes_pack_planes(p))) break;
-        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-            chip_set_error("probes pack failed");
-            rc = CATCHHIP_EHIP;
-            break;
-        }
-    } while (0);
-    if (rc) { delete p; return rc; }
-    *out = p;
+    }
+    if (nent) {   // anchors grouped by probe, ascending position
+        std::vector<u64> key((size_t)nent);
+        for (i64 e = 0; e < nent; ++e) key[e] = ((u64)(u32)ent_probe[e] << 32) | (u32)ent_pos[e];
+        std::sort(key.begin(), key.end());
+        std::vector<u32> sp((size_t)nent), so((size_t)nent), ptr((size_t)nprobes + 1, 0);
+        for (i64 e = 0; e < nent; ++e) { sp[e] = (u32)(key[e] >> 32); so[e] = (u32)key[e]; ptr[sp[e] + 1]++; }
+        for (i64 i = 0; i < nprobes; ++i) ptr[i + 1] += ptr[i];
+        TRY(p->sent_probe.alloc((size_t)nent));
+        TRY(p->sent_pos.alloc((size_t)nent));
+        TRY(p->ent_ptr.alloc((size_t)nprobes + 1));
+        HIP_TRY(hipMemcpyAsync(p->sent_probe.p, sp.data(), sizeof(u32) * nent, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->sent_pos.p, so.data(), sizeof(u32) * nent, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->ent_ptr.p, ptr.data(), sizeof(u32) * (nprobes + 1), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    TRY(chip_probes_pack_planes(p.get()));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    *out = p.release();
     return 0;
 }
 

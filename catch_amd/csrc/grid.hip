@@ -111,50 +111,37 @@ grid_len_kernel(const i32 *__restrict__ o_set, const u32 *__restrict__ o_gs, con
 static int grid_derive_one(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_targets *T, const u32 *thr,
                            u32 e, u32 ng, DevBuf<u32> &flag, DevBuf<u32> &pos, DevBuf<u32> &scan_tmp,
                            DevBuf<u32> &info, catchhip_rows **out) {
-    catchhip_rows *R = new catchhip_rows();
-    R->ctx = ctx;
-    R->total = R0->total;
-    R->ngenomes = R0->ngenomes;
-    R->h_genome_off = R0->h_genome_off;
+    std::unique_ptr<catchhip_rows> R;
+    TRY(chip_rows_new(ctx, R0->total, R0->ngenomes, R0->h_genome_off, R0->genome_off.p, false, R));
     R->ext = (i32)e;
     const u32 n0 = (u32)R0->n;
     hipStream_t s = ctx->stream;
-    int rc = 0;
-    do {
-        if ((rc = R->genome_off.alloc((size_t)R0->ngenomes + 1))) break;
-        if (hipMemcpyAsync(R->genome_off.p, R0->genome_off.p, sizeof(u32) * ((size_t)R0->ngenomes + 1),
-                           hipMemcpyDeviceToDevice, s) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-        if (n0 == 0) break;
-        // (capacity n0: an extension never makes more rows, and no count has to come back before the emit)
-        if ((rc = R->set_id.alloc(n0)) || (rc = R->univ.alloc(n0)) || (rc = R->gs.alloc(n0)) || (rc = R->ge.alloc(n0)))
-            break;
-        if (ng) {
-            if ((rc = R->gain0.alloc(ng))) break;
-            if (hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)ng, s) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-            R->gain0_n = ng;
-        }
-        if (hipMemsetAsync(info.p, 0, sizeof(u32) * 2, s) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-        const dim3 grid((unsigned)div_up(n0, 256)), blk(256);
-        hipLaunchKernelGGL(grid_flags_kernel, grid, blk, 0, s, thr, n0, e, flag.p);
-        if ((rc = chip_exclusive_scan_u32(ctx, flag.p, pos.p, n0, scan_tmp))) break;
-        hipLaunchKernelGGL(grid_emit_kernel, grid, blk, 0, s, (const i32 *)R0->set_id.p, (const i32 *)R0->univ.p,
-                           (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, thr, (const u32 *)pos.p, n0, e,
-                           (const u32 *)T->seq_off.p, (u32)T->nseq, R->set_id.p, R->univ.p, R->gs.p, R->ge.p, info.p);
-        hipLaunchKernelGGL(grid_len_kernel, grid, blk, 0, s, (const i32 *)R->set_id.p, (const u32 *)R->gs.p,
-                           (const u32 *)R->ge.p, n0, ng ? R->gain0.p : (u32 *)nullptr, ng, info.p);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(ctx->h_pin, info.p, sizeof(u32) * 2, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            chip_set_error("rows_extend: %s", hipGetErrorString(hipGetLastError()));
-            rc = CATCHHIP_EHIP;
-            break;
-        }
-        const volatile u32 *h = (const volatile u32 *)ctx->h_pin;
-        R->n = h[0];
-        R->lmax = h[1];
-    } while (0);
-    if (rc) { delete R; return rc; }
-    *out = R;
+    if (n0 == 0) {   // no rows to extend
+        *out = R.release();
+        return 0;
+    }
+    // (capacity n0: an extension never makes more rows, and no count has to come back before the emit)
+    TRY(chip_rows_alloc_soa(R.get(), n0));
+    if (ng) {
+        TRY(R->gain0.alloc(ng));
+        HIP_TRY(hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)ng, s));
+        R->gain0_n = ng;
+    }
+    HIP_TRY(hipMemsetAsync(info.p, 0, sizeof(u32) * 2, s));
+    const dim3 grid((unsigned)div_up(n0, 256)), blk(256);
+    hipLaunchKernelGGL(grid_flags_kernel, grid, blk, 0, s, thr, n0, e, flag.p);
+    TRY(chip_exclusive_scan_u32(ctx, flag.p, pos.p, n0, scan_tmp));
+    hipLaunchKernelGGL(grid_emit_kernel, grid, blk, 0, s, (const i32 *)R0->set_id.p, (const i32 *)R0->univ.p,
+                       (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, thr, (const u32 *)pos.p, n0, e,
+                       (const u32 *)T->seq_off.p, (u32)T->nseq, R->set_id.p, R->univ.p, R->gs.p, R->ge.p, info.p);
+    hipLaunchKernelGGL(grid_len_kernel, grid, blk, 0, s, (const i32 *)R->set_id.p, (const u32 *)R->gs.p,
+                       (const u32 *)R->ge.p, n0, ng ? R->gain0.p : (u32 *)nullptr, ng, info.p);
+    HIP_TRY(hipGetLastError());
+    u32 h[2];   // {rows, longest row}
+    TRY(chip_read_back(ctx, info.p, sizeof(h), h));
+    R->n = h[0];
+    R->lmax = h[1];
+    *out = R.release();
     return 0;
 }
 
@@ -189,6 +176,16 @@ static int grid_thresholds(catchhip_ctx *ctx, const catchhip_rows *R0, const cat
     return 0;
 }
 
+// what every derived table of R0 shares: the thresholds and the scratch of the flag scan
+static int grid_prepare(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_targets *T, DevBuf<u32> &thr,
+                        DevBuf<u32> &flag, DevBuf<u32> &pos) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    TRY(grid_thresholds(ctx, R0, T, thr));
+    TRY(flag.alloc((size_t)R0->n));
+    TRY(pos.alloc((size_t)R0->n));
+    return 0;
+}
+
 extern "C" int catchhip_rows_extend(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_targets *T,
                                     i32 n_ext, const i32 *ext, catchhip_rows **out, i64 *nrows) {
     ARG_CHECK(ctx && R0 && T && out && n_ext >= 0 && (n_ext == 0 || ext));
@@ -199,11 +196,8 @@ extern "C" int catchhip_rows_extend(catchhip_ctx *ctx, const catchhip_rows *R0, 
     }
     TRY(grid_check_rows0(R0, T));
     PoolScope pool_scope(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
     DevBuf<u32> thr, flag, pos, scan_tmp, info;
-    TRY(grid_thresholds(ctx, R0, T, thr));
-    TRY(flag.alloc((size_t)R0->n));
-    TRY(pos.alloc((size_t)R0->n));
+    TRY(grid_prepare(ctx, R0, T, thr, flag, pos));
     TRY(info.alloc(2));
     for (i32 i = 0; i < n_ext; ++i) {
         const int rc = grid_derive_one(ctx, R0, T, thr.p, (u32)ext[i], R0->gain0_n, flag, pos, scan_tmp, info, &out[i]);
@@ -269,12 +263,7 @@ extern "C" int catchhip_setcover_grid(catchhip_ctx *ctx, const catchhip_probes *
     {
         PoolScope pool_scope(ctx);
         DevBuf<u32> thr, flag, pos, scan_tmp, info;
-        if (!rescan && R0->n) {
-            if (hipSetDevice(ctx->device) != hipSuccess) rc = CATCHHIP_EHIP;
-            if (!rc) rc = grid_thresholds(ctx, R0, T, thr);
-            if (!rc) rc = flag.alloc((size_t)R0->n);
-            if (!rc) rc = pos.alloc((size_t)R0->n);
-        }
+        if (!rescan && R0->n) rc = grid_prepare(ctx, R0, T, thr, flag, pos);
         if (!rc && !rescan) rc = info.alloc(2);
         // the derived tables fill gain0 for every set the solver asks about (the scan's own gain0 may be missing)
         const u32 ng = (u32)std::min<i64>(std::max<i64>(num_sets, R0 ? (i64)R0->gain0_n : 0), (i64)0xfffffffe);

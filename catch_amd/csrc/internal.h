@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -149,6 +150,15 @@ struct catchhip_ctx {
 // pinned host scratch of at least `bytes` (contents not preserved on growth)
 int chip_pinned_reserve(catchhip_ctx *ctx, size_t bytes);
 
+// small synchronous read-back: `bytes` (at most the 512 of h_pin) from the device to *out, through the pinned words
+static inline int chip_read_back(catchhip_ctx *ctx, const void *d, size_t bytes, void *out) {
+    HIP_TRY(hipMemcpyAsync(ctx->h_pin, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(out, ctx->h_pin, bytes);
+    return 0;
+}
+static inline int read_count(catchhip_ctx *ctx, const u32 *d, u32 *out) { return chip_read_back(ctx, d, sizeof(u32), out); }
+
 // elapsed time of a phase whose start/stop events were recorded earlier
 void chip_phase_collect(catchhip_ctx *ctx, int phase);
 // scan + row build with no host synchronisation (seed path only); returns 1
@@ -284,6 +294,30 @@ struct catchhip_rows {
     const i32 *bucket_set = nullptr;   // (the probes' array: they outlive the filter call the rows live in)
 };
 
+// the four SoA arrays of n rows
+static inline int chip_rows_alloc_soa(catchhip_rows *R, size_t n) {
+    TRY(R->set_id.alloc(n));
+    TRY(R->univ.alloc(n));
+    TRY(R->gs.alloc(n));
+    TRY(R->ge.alloc(n));
+    return 0;
+}
+// an empty rows object over a coordinate space that is on the device already (a targets object's, or other rows'):
+// the host facts, and genome_off copied on the context's stream.  Call under the caller's PoolScope, device set.
+static inline int chip_rows_new(catchhip_ctx *ctx, i64 total, i32 ngenomes, const std::vector<i64> &h_genome_off,
+                                const u32 *d_genome_off, bool grouped, std::unique_ptr<catchhip_rows> &R) {
+    R.reset(new catchhip_rows());
+    R->ctx = ctx;
+    R->total = total;
+    R->ngenomes = ngenomes;
+    R->h_genome_off = h_genome_off;
+    R->grouped = grouped;
+    TRY(R->genome_off.alloc((size_t)ngenomes + 1));
+    HIP_TRY(hipMemcpyAsync(R->genome_off.p, d_genome_off, sizeof(u32) * ((size_t)ngenomes + 1), hipMemcpyDeviceToDevice,
+                           ctx->stream));
+    return 0;
+}
+
 // unique candidate probes of a targets object (candidates.hip; the poly(A) pre-filter of prefilter.hip edits the list)
 struct catchhip_candidates {
     catchhip_ctx *ctx = nullptr;
@@ -362,6 +396,7 @@ struct PhaseTimer {
         float ms = 0.f;
         stop();
         (void)hipEventSynchronize(c->ev[2 * phase + 1]);
+        // (timing is best effort: a failing query leaves the phase's time as it was)
         if (hipEventElapsedTime(&ms, c->ev[2 * phase], c->ev[2 * phase + 1]) == hipSuccess)
             c->phase_ms[phase] = ms;
     }

@@ -742,9 +742,9 @@ static int ndf_keep_out(catchhip_ctx *ctx, u32 nn, const u32 *d_status, NdfKeep 
         TRY(bad.alloc(1));
         HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(u32), s));
         hipLaunchKernelGGL(ndf_flags_kernel, dim3((unsigned)div_up(nn, 256)), dim3(256), 0, s, d_status, nn, keep.d_flags, bad.p);
-        HIP_TRY(hipMemcpyAsync(ctx->h_pin, bad.p, sizeof(u32), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (*(volatile u32 *)ctx->h_pin) { chip_set_error("ndf: unresolved probe"); return CATCHHIP_EINVAL; }
+        u32 nbad;
+        TRY(read_count(ctx, bad.p, &nbad));
+        if (nbad) { chip_set_error("ndf: unresolved probe"); return CATCHHIP_EINVAL; }
         return 0;
     }
     std::vector<u32> h_status(nn);
@@ -839,9 +839,8 @@ static int ndf_lazy_rounds(catchhip_ctx *ctx, u32 nn, size_t tn, DevBuf<u32> &co
             hipLaunchKernelGGL(ndf_cflag_kernel, dim3((unsigned)div_up((i64)tcur + 1, 256)), dim3(256), 0, s, (const u32 *)svals_buf.p,
                                (const u32 *)status.p, tcur, cflag.p, (const u32 *)st2.p);
             TRY(chip_exclusive_scan_u32(ctx, cflag.p, cpos.p, (i64)tcur + 1, ctmp));
-            HIP_TRY(hipMemcpyAsync(ctx->h_pin, cpos.p + tcur, sizeof(u32), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            const u32 total = *(volatile u32 *)ctx->h_pin;
+            u32 total;
+            TRY(read_count(ctx, cpos.p + tcur, &total));
             if (total % ntables != 0) { chip_set_error("ndf: tables disagree on the surviving probes"); return CATCHHIP_EINVAL; }
             const u32 nslot2 = total / ntables;
             if ((u64)nslot2 * 4 <= (u64)nslot * 3) {
@@ -873,26 +872,26 @@ static int ndf_lazy_rounds(catchhip_ctx *ctx, u32 nn, size_t tn, DevBuf<u32> &co
         if (wake) hipLaunchKernelGGL(ndf_wake_kernel, dim3((unsigned)div_up(nn, 1024)), dim3(1024), 0, s, status.p, flags.p, nn, lists[(round & 1) ^ 1].p, undecided, trace ? 1 : 0, st2.p);
         else hipLaunchKernelGGL(ndf_node_round_kernel, dim3(nb), dim3(256), 0, s, status.p, flags.p, nn, undecided);
         tm.launch(2);
-        HIP_TRY(hipMemcpyAsync(ctx->h_pin, undecided, 3 * sizeof(u32), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        u32 h_und[3];
+        TRY(chip_read_back(ctx, undecided, sizeof(h_und), h_und));
         if (trace) {
             const auto t1 = std::chrono::steady_clock::now();
             u64 hp[2 * ES_SHARDS], cmp = 0;
             (void)hipMemcpy(hp, pairs.p, sizeof(hp), hipMemcpyDeviceToHost);
             for (int sh = 0; sh < ES_SHARDS; ++sh) cmp += hp[sh];
             fprintf(stderr, "[catchhip]     lazy round %u: %u entries -> %u undecided probes, %u entries next; %.2f ms, %llu pairs compared so far\n",
-                    round, nlist, ((volatile u32 *)ctx->h_pin)[0], ((volatile u32 *)ctx->h_pin)[1],
+                    round, nlist, h_und[0], h_und[1],
                     std::chrono::duration<double, std::milli>(t1 - t_round).count(), (unsigned long long)cmp);
             t_round = std::chrono::steady_clock::now();
         }
         const bool idle = wake && !nlist;             // (no pass in this round)
-        left = ((volatile u32 *)ctx->h_pin)[0];       // (wake-ups: a flag unless the rounds are traced)
-        nlist = ((volatile u32 *)ctx->h_pin)[1];
+        left = h_und[0];       // (wake-ups: a flag unless the rounds are traced)
+        nlist = h_und[1];
         // A round without a pass in which the wake-up launch neither woke nor dropped anybody: whoever is undecided now
         // neither waits nor walks (a broken invariant).  (A round that only DROPS is progress: a chain of probes each
         // parked on the next resolves one link per wake-up launch -- the first form of this check stopped there: fuzz
         // seed 31188, 4,720 of 5,608 probes of near-identical small groups undecided after round 0.)
-        if (idle && left && !nlist && !((volatile u32 *)ctx->h_pin)[2]) {
+        if (idle && left && !nlist && !h_und[2]) {
             chip_set_error("ndf: undecided probes that nobody will wake");
             return CATCHHIP_EINVAL;
         }
@@ -947,9 +946,9 @@ static int ndf_resolve(catchhip_ctx *ctx, u32 nn, u32 segused, u32 segcap, DevBu
                                s, e_i.p, e_j.p, segcap, (const u32 *)count.p, status.p, flags.p);
         hipLaunchKernelGGL(ndf_node_round_kernel, dim3(nb), dim3(256), 0, s, status.p, flags.p, nn, undecided);
         tm.launch(2);
-        HIP_TRY(hipMemcpyAsync(ctx->h_pin, undecided, sizeof(u32), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (*(volatile u32 *)ctx->h_pin == 0) break;
+        u32 left;
+        TRY(read_count(ctx, undecided, &left));
+        if (left == 0) break;
     }
     tm.stop();
     HIP_TRY(hipStreamSynchronize(s));
@@ -1787,9 +1786,9 @@ static int ndf_minhash_impl(catchhip_ctx *ctx, const u8 *bytes, const i64 *probe
     if (!want_ids) {
         HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(u32), s));
         hipLaunchKernelGGL(mh_other_chars_kernel, dim3(2048), dim3(256), 0, s, (const u8 *)d_bytes.p, (u64)total, count.p);
-        HIP_TRY(hipMemcpyAsync(ctx->h_pin, count.p, sizeof(u32), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        want_ids = *(volatile u32 *)ctx->h_pin != 0u;
+        u32 ncollide;
+        TRY(read_count(ctx, count.p, &ncollide));
+        want_ids = ncollide != 0u;
         HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(u32), s));
     }
     if (want_ids) { TRY(id_hi.alloc(nkm)); TRY(id_lo.alloc(nkm)); }

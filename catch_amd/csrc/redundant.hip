@@ -387,72 +387,62 @@ extern "C" int catchhip_redundancy_graph(catchhip_ctx *ctx, const u8 *bytes, con
     }
     PoolScope pool_scope(ctx);
     hipStream_t s = ctx->stream;
-    catchhip_redgraph *G = new catchhip_redgraph();
+    std::unique_ptr<catchhip_redgraph> G(new catchhip_redgraph());
     G->ctx = ctx;
     G->n = n;
-    int rc = 0;
-    do {
-        if ((rc = G->ptr.alloc((size_t)n + 1))) break;
-        if (n == 0) {
-            if (hipMemsetAsync(G->ptr.p, 0, sizeof(i64), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) rc = CATCHHIP_EHIP;
-            if (!rc) rc = G->idx.alloc(1);
-            break;
-        }
-        const int W = maxlen <= 64 ? 1 : maxlen <= 128 ? 2 : 4;
-        const i64 total = off[n] - off[0];
-        DevBuf<u8> d_bytes;
-        DevBuf<i64> d_off;
-        DevBuf<u64> planes;
-        DevBuf<u32> lens, deg;
-        DevBuf<unsigned long long> bitmap;
-        if ((rc = d_bytes.alloc((size_t)total + 1))) break;
-        if ((rc = d_off.alloc((size_t)n + 1))) break;
-        if ((rc = planes.alloc((size_t)3 * W * npad))) break;
-        if ((rc = lens.alloc((size_t)npad))) break;
-        if ((rc = deg.alloc((size_t)n))) break;
-        if ((rc = bitmap.alloc((size_t)n * tiles))) break;
-        // (offsets relative to the first byte handed over)
-        std::vector<i64> rel((size_t)n + 1);
-        for (i64 i = 0; i <= n; ++i) rel[i] = off[i] - off[0];
-        rc = CATCHHIP_EHIP;
-        if (total && hipMemcpyAsync(d_bytes.p, bytes + off[0], (size_t)total, hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (hipMemcpyAsync(d_off.p, rel.data(), sizeof(i64) * ((size_t)n + 1), hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (hipMemsetAsync(planes.p, 0, sizeof(u64) * (size_t)3 * W * npad, s) != hipSuccess) break;
-        if (hipMemsetAsync(lens.p, 0, sizeof(u32) * (size_t)npad, s) != hipSuccess) break;
-        if (hipMemsetAsync(bitmap.p, 0, sizeof(u64) * (size_t)n * tiles, s) != hipSuccess) break;
-        PhaseTimer timer(ctx, PHASE_NDF);
-        hipLaunchKernelGGL(rg_pack_kernel, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, (const u8 *)d_bytes.p,
-                           (const i64 *)d_off.p, (u32)n, (u32)npad, W, planes.p, lens.p);
-        const dim3 grid((unsigned)tiles, (unsigned)tiles);
-        if (W == 1) rg_launch_pairs<1>(s, grid, kind, planes.p, lens.p, (u32)n, (u32)npad, p0, p1, bitmap.p, (u32)tiles);
-        else if (W == 2) rg_launch_pairs<2>(s, grid, kind, planes.p, lens.p, (u32)n, (u32)npad, p0, p1, bitmap.p, (u32)tiles);
-        else rg_launch_pairs<4>(s, grid, kind, planes.p, lens.p, (u32)n, (u32)npad, p0, p1, bitmap.p, (u32)tiles);
-        hipLaunchKernelGGL(rg_degree_kernel, dim3((unsigned)div_up(n, 4)), dim3(256), 0, s,
-                           (const unsigned long long *)bitmap.p, (u32)n, (u32)tiles, deg.p);
-        hipLaunchKernelGGL(rg_scan_kernel, dim3(1), dim3(RN_BLOCK), 0, s, (const u32 *)deg.p, (u32)n, G->ptr.p);
-        timer.launch(4);
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipMemcpyAsync(ctx->h_pin, G->ptr.p + n, sizeof(i64), hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;      // (rel[] and the caller's bytes are free again)
-        G->nedges = (i64) * (volatile u64 *)ctx->h_pin;
-        if ((rc = G->idx.alloc((size_t)std::max<i64>(G->nedges, 1)))) break;
-        rc = CATCHHIP_EHIP;
-        hipLaunchKernelGGL(rg_fill_kernel, dim3((unsigned)div_up(n, 4)), dim3(256), 0, s,
-                           (const unsigned long long *)bitmap.p, (u32)n, (u32)tiles, (const i64 *)G->ptr.p, G->idx.p);
-        timer.launch(1);
-        timer.stop();
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;
-        timer.finish();
-        rc = 0;
-    } while (0);
-    if (rc) {
-        if (rc == CATCHHIP_EHIP) chip_set_error("redundancy_graph: HIP error: %s", hipGetErrorString(hipGetLastError()));
-        delete G;
-        return rc;
+    TRY(G->ptr.alloc((size_t)n + 1));
+    if (n == 0) {   // the empty graph
+        HIP_TRY(hipMemsetAsync(G->ptr.p, 0, sizeof(i64), s));
+        HIP_TRY(hipStreamSynchronize(s));
+        TRY(G->idx.alloc(1));
+        if (nedges) *nedges = 0;
+        *out = G.release();
+        return 0;
     }
+    const int W = maxlen <= 64 ? 1 : maxlen <= 128 ? 2 : 4;
+    const i64 total = off[n] - off[0];
+    DevBuf<u8> d_bytes;
+    DevBuf<i64> d_off;
+    DevBuf<u64> planes;
+    DevBuf<u32> lens, deg;
+    DevBuf<unsigned long long> bitmap;
+    TRY(d_bytes.alloc((size_t)total + 1));
+    TRY(d_off.alloc((size_t)n + 1));
+    TRY(planes.alloc((size_t)3 * W * npad));
+    TRY(lens.alloc((size_t)npad));
+    TRY(deg.alloc((size_t)n));
+    TRY(bitmap.alloc((size_t)n * tiles));
+    // (offsets relative to the first byte handed over)
+    std::vector<i64> rel((size_t)n + 1);
+    for (i64 i = 0; i <= n; ++i) rel[i] = off[i] - off[0];
+    if (total) HIP_TRY(hipMemcpyAsync(d_bytes.p, bytes + off[0], (size_t)total, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_off.p, rel.data(), sizeof(i64) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(planes.p, 0, sizeof(u64) * (size_t)3 * W * npad, s));
+    HIP_TRY(hipMemsetAsync(lens.p, 0, sizeof(u32) * (size_t)npad, s));
+    HIP_TRY(hipMemsetAsync(bitmap.p, 0, sizeof(u64) * (size_t)n * tiles, s));
+    PhaseTimer timer(ctx, PHASE_NDF);
+    hipLaunchKernelGGL(rg_pack_kernel, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, (const u8 *)d_bytes.p,
+                       (const i64 *)d_off.p, (u32)n, (u32)npad, W, planes.p, lens.p);
+    const dim3 grid((unsigned)tiles, (unsigned)tiles);
+    if (W == 1) rg_launch_pairs<1>(s, grid, kind, planes.p, lens.p, (u32)n, (u32)npad, p0, p1, bitmap.p, (u32)tiles);
+    else if (W == 2) rg_launch_pairs<2>(s, grid, kind, planes.p, lens.p, (u32)n, (u32)npad, p0, p1, bitmap.p, (u32)tiles);
+    else rg_launch_pairs<4>(s, grid, kind, planes.p, lens.p, (u32)n, (u32)npad, p0, p1, bitmap.p, (u32)tiles);
+    hipLaunchKernelGGL(rg_degree_kernel, dim3((unsigned)div_up(n, 4)), dim3(256), 0, s,
+                       (const unsigned long long *)bitmap.p, (u32)n, (u32)tiles, deg.p);
+    hipLaunchKernelGGL(rg_scan_kernel, dim3(1), dim3(RN_BLOCK), 0, s, (const u32 *)deg.p, (u32)n, G->ptr.p);
+    timer.launch(4);
+    HIP_TRY(hipGetLastError());
+    TRY(chip_read_back(ctx, G->ptr.p + n, sizeof(i64), &G->nedges));   // (rel[] and the caller's bytes are free again)
+    TRY(G->idx.alloc((size_t)std::max<i64>(G->nedges, 1)));
+    hipLaunchKernelGGL(rg_fill_kernel, dim3((unsigned)div_up(n, 4)), dim3(256), 0, s,
+                       (const unsigned long long *)bitmap.p, (u32)n, (u32)tiles, (const i64 *)G->ptr.p, G->idx.p);
+    timer.launch(1);
+    timer.stop();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    timer.finish();
     if (nedges) *nedges = G->nedges;
-    *out = G;
+    *out = G.release();
     return 0;
 }
 
@@ -533,7 +523,7 @@ extern "C" int catchhip_redundancy_rows(catchhip_ctx *ctx, const catchhip_redgra
     HIP_TRY(hipSetDevice(ctx->device));
     PoolScope pool_scope(ctx);
     hipStream_t s = ctx->stream;
-    catchhip_rows *R = new catchhip_rows();
+    std::unique_ptr<catchhip_rows> R(new catchhip_rows());
     R->ctx = ctx;
     R->n = rows;
     R->ngenomes = 1;
@@ -541,28 +531,15 @@ extern "C" int catchhip_redundancy_rows(catchhip_ctx *ctx, const catchhip_redgra
     R->lmax = rows ? 1 : 0;
     R->h_genome_off = {0, 2 * n};
     const u32 go[2] = {0u, (u32)(2 * n)};
-    int rc = 0;
-    do {
-        if ((rc = R->set_id.alloc((size_t)rows))) break;
-        if ((rc = R->univ.alloc((size_t)rows))) break;
-        if ((rc = R->gs.alloc((size_t)rows))) break;
-        if ((rc = R->ge.alloc((size_t)rows))) break;
-        if ((rc = R->genome_off.alloc(2))) break;
-        rc = CATCHHIP_EHIP;
-        if (hipMemcpyAsync(R->genome_off.p, go, sizeof(go), hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (n)
-            hipLaunchKernelGGL(rr_rows_kernel, dim3((unsigned)div_up(n, 4)), dim3(256), 0, s, (const i64 *)G->ptr.p,
-                               (const u32 *)G->idx.p, (u32)n, R->set_id.p, R->univ.p, R->gs.p, R->ge.p);
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;
-        rc = 0;
-    } while (0);
-    if (rc) {
-        if (rc == CATCHHIP_EHIP) chip_set_error("redundancy_rows: HIP error: %s", hipGetErrorString(hipGetLastError()));
-        delete R;
-        return rc;
-    }
+    TRY(chip_rows_alloc_soa(R.get(), (size_t)rows));
+    TRY(R->genome_off.alloc(2));
+    HIP_TRY(hipMemcpyAsync(R->genome_off.p, go, sizeof(go), hipMemcpyHostToDevice, s));
+    if (n)
+        hipLaunchKernelGGL(rr_rows_kernel, dim3((unsigned)div_up(n, 4)), dim3(256), 0, s, (const i64 *)G->ptr.p,
+                           (const u32 *)G->idx.p, (u32)n, R->set_id.p, R->univ.p, R->gs.p, R->ge.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
     if (nrows) *nrows = rows;
-    *out = R;
+    *out = R.release();
     return 0;
 }

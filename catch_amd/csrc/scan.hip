@@ -1184,12 +1184,8 @@ struct RawHits {
     bool has_end = false;
 };
 
-static int read_count(catchhip_ctx *ctx, const u32 *d, u32 *out) {
-    HIP_TRY(hipMemcpyAsync(ctx->h_pin, d, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *out = *(volatile u32 *)ctx->h_pin;
-    return 0;
-}
+// the bits of a probe's last 32-base word that hold bases
+static u32 probe_tail_mask(int L) { return (L & 31) ? ((1u << (L & 31)) - 1u) : 0xffffffffu; }
 
 // seed scan: equal-length DNA probes with anchors, full-length cover threshold,
 // no island, every sequence at least one probe long (SURVEY.md App. A.8 without
@@ -1214,7 +1210,7 @@ static bool fast_path_ok(const catchhip_probes *P, const catchhip_targets *T, in
 static int run_fast(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, int mm,
                     RawHits &H, PhaseTimer &tm) {
     const bool use_n = P->has_n || T->has_n;
-    const u32 tailmask = (P->L & 31) ? ((1u << (P->L & 31)) - 1u) : 0xffffffffu;
+    const u32 tailmask = probe_tail_mask(P->L);
     u32 cap = (u32)std::max<i64>((i64)1 << 20, std::min<i64>(P->nprobes * 64, (i64)1 << 28));
     TRY(H.count.alloc(1));
     // enough workgroups to fill 256 CUs several times over
@@ -1361,7 +1357,7 @@ static int run_seed_async(catchhip_ctx *ctx, const catchhip_probes *P, const cat
     TRY(seed_table_lookup_async(ctx, P, T, pos_limit, mm, verify4 != nullptr && sink.wcnt != nullptr, S, sink.bcnt, nb, res,
                                 tm));
     if (S.nranges) HIP_TRY(hipMemsetAsync(sink.wcnt, 0, sizeof(u32) * ((size_t)S.scap / 64 + 1), ctx->stream));
-    const u32 tailmask = (P->L & 31) ? ((1u << (P->L & 31)) - 1u) : 0xffffffffu;
+    const u32 tailmask = probe_tail_mask(P->L);
     // the verify launch alone is phase 5 (read lazily by catchhip_ctx_last_kernel_ms)
     (void)hipEventRecord(ctx->ev[2 * PHASE_VERIFY], ctx->stream);
     if (verify4)
@@ -1466,7 +1462,7 @@ static int run_general(catchhip_ctx *ctx, const catchhip_probes *P, const catchh
         // packed images: the window's mismatch mask in a few words, bit scans around the anchor
         TRY(cut.alloc((size_t)cut_cap + 1));
         HIP_TRY(hipMemsetAsync(cut.p, 0, sizeof(u32), ctx->stream));
-        const u32 tailmask = (P->L & 31) ? ((1u << (P->L & 31)) - 1u) : 0xffffffffu;
+        const u32 tailmask = probe_tail_mask(P->L);
         hipLaunchKernelGGL(planes, dim3((unsigned)div_up(nseeds, 256 * SE_PPT)), dim3(256), 0, ctx->stream,
                            (const u32 *)T->planes.p, T->nwords, (const u8 *)T->bytes.p, (const u32 *)T->seq_off.p,
                            (const uint4 *)P->planes.p, (const u8 *)P->bytes.p, (const u32 *)P->probe_off.p, e_probe,
@@ -1700,7 +1696,7 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
     A.tq = (const uint4 *)T->tq.p; A.seq_off = (const u32 *)T->seq_off.p; A.pplanes = (const uint4 *)P->planes.p;
     A.nanch = nanch; A.ntab = ntab; A.L = (int)P->L; A.k = k; A.mm = mm;
     A.div_magic = (((unsigned long long)1 << 34) + (unsigned long long)nanch - 1ull) / (unsigned long long)nanch;
-    A.tailmask = (P->L & 31) ? ((1u << (P->L & 31)) - 1u) : 0xffffffffu;
+    A.tailmask = probe_tail_mask(P->L);
     A.nhit = J.nhit;
     A.slot = (const uint4 *)S.slot.p; A.ents = (const u32 *)S.ents.p;
     A.ecnt = J.ecnt.p; A.ebase = (const u32 *)J.ebase.p; A.S = nullptr;
@@ -2003,6 +1999,14 @@ __global__ void rows_info_kernel(const u32 *__restrict__ res, const u32 *__restr
     else if (t == 12) info[t] = scap;
 }
 
+// the emit launch of the row build: R->n slots of bucketed records -> R's SoA arrays (nrows_dev / nhits_dev: the
+// device's counts of a deferred scan, or null; all_rows as the kernel takes it)
+static void rows_emit(catchhip_ctx *ctx, catchhip_rows *R, const u32 *rstart, u32 nb, const u32 *bstart,
+                      const i32 *bucket_set, const uint4 *rec, const u32 *nrows_dev, const u32 *nhits_dev, int all_rows) {
+    hipLaunchKernelGGL(rows_emit_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream, rstart, nb, bstart,
+                       bucket_set, rec, (u32)R->n, nrows_dev, R->set_id.p, R->univ.p, R->gs.p, R->ge.p, nhits_dev, all_rows);
+}
+
 int chip_cover_scan_nosync(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, i32 mismatches,
                            i32 lcf_thres, i32 island, i32 cover_extension, i32 mode, catchhip_rows **out) {
     *out = nullptr;
@@ -2027,45 +2031,27 @@ int chip_cover_scan_nosync(catchhip_ctx *ctx, const catchhip_probes *P, const ca
     sink.rec = O.B.rec.p; sink.rank = O.B.rank.p; sink.bcnt = O.B.bcnt.p;
     O.B.compact = true;
     sink.wcnt = O.B.wcnt.p;
-    catchhip_rows *R = new catchhip_rows();
-    R->ctx = ctx;
-    R->total = T->total;
-    R->ngenomes = T->ngenomes;
-    R->h_genome_off = T->h_genome_off;
-    R->grouped = P->has_groups && T->has_groups;
+    std::unique_ptr<catchhip_rows> R;   // (declared after O: on a failure the rows go back to the pool first, as ever)
+    TRY(chip_rows_new(ctx, T->total, T->ngenomes, T->h_genome_off, T->genome_off.p, P->has_groups && T->has_groups, R));
     R->deferred = true;
     R->n = O.S.scap;   // capacity; the row count is info[4]
-    int rc = 0;
-    do {
-        if ((rc = R->genome_off.alloc((size_t)T->ngenomes + 1))) break;
-        if ((rc = R->info.alloc(16))) break;
-        if ((rc = R->set_id.alloc(R->n))) break;
-        if ((rc = R->univ.alloc(R->n))) break;
-        if ((rc = R->gs.alloc(R->n))) break;
-        if ((rc = R->ge.alloc(R->n))) break;
-        if (hipMemcpyAsync(R->genome_off.p, T->genome_off.p, sizeof(u32) * (T->ngenomes + 1),
-                           hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-        PhaseTimer ts(ctx, PHASE_SCAN);
-        if ((rc = run_seed_async(ctx, P, T, mismatches, O.S, sink, nb, O.B.res.p, ts))) break;
-        ts.stop();
-        PhaseTimer tr(ctx, PHASE_ROWS);
-        if ((rc = bucket_finish_async(ctx, O.B, O.S.scap, O.S.ctr.p + 1, false, tr))) break;
-        hipLaunchKernelGGL(rows_emit_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream,
-                           (const u32 *)O.B.rstart.p, O.B.nb, (const u32 *)O.B.bstart.p,
-                           P->bucket_identity ? (const i32 *)nullptr : (const i32 *)P->bucket_set.p,
-                           (const uint4 *)O.B.S.p, (u32)R->n,
-                           (const u32 *)(O.B.res.p + 4), R->set_id.p, R->univ.p, R->gs.p, R->ge.p,
-                           (const u32 *)(O.B.res.p + 2), -1);
-        hipLaunchKernelGGL(rows_info_kernel, dim3(1), dim3(64), 0, ctx->stream, (const u32 *)O.B.res.p,
-                           (const u32 *)O.S.ctr.p, O.S.scap, R->info.p);
-        tr.launch(2);
-        tr.stop();
-        if (hipGetLastError() != hipSuccess) { chip_set_error("cover scan: launch failed"); rc = CATCHHIP_EHIP; break; }
-    } while (0);
-    if (rc) { delete R; return rc; }
+    TRY(R->info.alloc(16));
+    TRY(chip_rows_alloc_soa(R.get(), R->n));
+    PhaseTimer ts(ctx, PHASE_SCAN);
+    TRY(run_seed_async(ctx, P, T, mismatches, O.S, sink, nb, O.B.res.p, ts));
+    ts.stop();
+    PhaseTimer tr(ctx, PHASE_ROWS);
+    TRY(bucket_finish_async(ctx, O.B, O.S.scap, O.S.ctr.p + 1, false, tr));
+    rows_emit(ctx, R.get(), O.B.rstart.p, O.B.nb, O.B.bstart.p, P->bucket_identity ? nullptr : P->bucket_set.p, O.B.S.p,
+              O.B.res.p + 4, O.B.res.p + 2, -1);
+    hipLaunchKernelGGL(rows_info_kernel, dim3(1), dim3(64), 0, ctx->stream, (const u32 *)O.B.res.p,
+                       (const u32 *)O.S.ctr.p, O.S.scap, R->info.p);
+    tr.launch(2);
+    tr.stop();
+    HIP_TRY(hipGetLastError());
     // O's scratch goes back to this context's cache here; whatever reuses it is
     // ordered behind the kernels above on the context's stream
-    *out = R;
+    *out = R.release();
     return 0;
 }
 
@@ -2161,132 +2147,107 @@ static int cover_scan_impl(catchhip_ctx *ctx, const catchhip_probes *P, const ca
     // seed scan (O(G + seeds)) is used, whatever the anchor table;
     // CATCHHIP_SCAN_FAST forces the tiled O(P*G) scan (pigeonhole anchors only),
     // CATCHHIP_SCAN_GENERAL the byte-exact seed join.
-    catchhip_rows *R = new catchhip_rows();
-    R->ctx = ctx;
-    R->total = T->total;
-    R->ngenomes = T->ngenomes;
-    R->h_genome_off = T->h_genome_off;
-    R->grouped = P->has_groups && T->has_groups;
+    std::unique_ptr<catchhip_rows> R;
+    TRY(chip_rows_new(ctx, T->total, T->ngenomes, T->h_genome_off, T->genome_off.p, P->has_groups && T->has_groups, R));
     R->ext = merge ? cover_extension : -1;
-    int rc = 0;
-    do {
-        if ((rc = R->genome_off.alloc((size_t)T->ngenomes + 1))) break;
-        if (hipMemcpyAsync(R->genome_off.p, T->genome_off.p, sizeof(u32) * (T->ngenomes + 1),
-                           hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-        if (P->nprobes == 0 || T->total == 0) break;   // no rows
-        ScanOut O;
-        if ((rc = scan_and_group(ctx, P, T, mismatches, lcf_thres, island, (u32)cover_extension, false, mode, O,
-                                 !merge, want_first))) break;
-        if (!merge && O.overflow) {
-            chip_set_error("cover_ranges: a probe has more than %d cover ranges", BK_BIG);
-            rc = CATCHHIP_EINVAL;
-            break;
-        }
-        PhaseTimer tm(ctx, PHASE_ROWS, true);   // continues the row-build phase (adds to its time)
-        if (!O.overflow) {
-            R->n = O.nrows;
-            R->lmax = O.lmax;
-            // Direct form: the caller solves at once and the row-parallel solver reads the bucketed records where they
-            // lie -- the buffers move over, nothing is copied per row.  Merged rows under a bucket -> set table keep the
-            // SoA form: kept conservative (a bucket is one set there too, so the slot rule would hold; not measured).
-            const bool direct = allow_direct && merge && !want_first && R->n &&
-                                (O.nhits == O.nrows || P->bucket_identity) && !chip_test_env("CATCHHIP_ROWS_SOA");
-            if (direct) {
-                R->rows4.swap(O.B.S); R->bstart.swap(O.B.bstart); R->mcnt.swap(O.B.mcnt); R->rstart.swap(O.B.rstart);
-                R->slots = O.nhits;
-                R->nb = O.B.nb;
-                R->bucket_set = P->bucket_identity ? (const i32 *)nullptr : (const i32 *)P->bucket_set.p;
-            } else {
-                if ((rc = R->set_id.alloc(R->n))) break;
-                if ((rc = R->univ.alloc(R->n))) break;
-                if ((rc = R->gs.alloc(R->n))) break;
-                if ((rc = R->ge.alloc(R->n))) break;
-            }
-            if (R->n) {
-                if (!direct) {
-                    hipLaunchKernelGGL(rows_emit_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream,
-                                       (const u32 *)O.B.rstart.p, O.B.nb, (const u32 *)O.B.bstart.p,
-                                       P->bucket_identity ? (const i32 *)nullptr : (const i32 *)P->bucket_set.p, (const uint4 *)O.B.S.p, (u32)R->n, (const u32 *)nullptr, R->set_id.p, R->univ.p,
-                                       R->gs.p, R->ge.p, (const u32 *)nullptr, O.nhits == O.nrows ? 1 : 0);
-                    tm.launch();
-                }
-                if (merge && O.B.bsum.p && O.B.bsum.n >= (size_t)O.B.nb && P->max_set_id < ((i64)1 << 31)) {
-                    // the sets' total row lengths: what the first round of a full-coverage solve would count
-                    const u32 ng = (u32)std::max<i64>(P->max_set_id + 1, (i64)(P->bucket_identity ? O.B.nb : 0));
-                    if ((rc = R->gain0.alloc(ng))) break;
-                    if (hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)ng, ctx->stream) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-                    hipLaunchKernelGGL(rows_gain0_kernel, dim3((unsigned)div_up((i64)O.B.nb, 256)), dim3(256), 0, ctx->stream,
-                                       (const unsigned long long *)O.B.bsum.p, O.B.nb,
-                                       P->bucket_identity ? (const i32 *)nullptr : (const i32 *)P->bucket_set.p, ng, R->gain0.p);
-                    R->gain0_n = ng;
-                    tm.launch();
-                }
-            }
+    if (P->nprobes == 0 || T->total == 0) {   // no rows (*nrows is 0 already)
+        *out = R.release();
+        return 0;
+    }
+    ScanOut O;
+    TRY(scan_and_group(ctx, P, T, mismatches, lcf_thres, island, (u32)cover_extension, false, mode, O, !merge, want_first));
+    if (!merge && O.overflow) {
+        chip_set_error("cover_ranges: a probe has more than %d cover ranges", BK_BIG);
+        return CATCHHIP_EINVAL;
+    }
+    PhaseTimer tm(ctx, PHASE_ROWS, true);   // continues the row-build phase (adds to its time)
+    if (!O.overflow) {
+        R->n = O.nrows;
+        R->lmax = O.lmax;
+        const i32 *bucket_set = P->bucket_identity ? (const i32 *)nullptr : (const i32 *)P->bucket_set.p;
+        // Direct form: the caller solves at once and the row-parallel solver reads the bucketed records where they
+        // lie -- the buffers move over, nothing is copied per row.  Merged rows under a bucket -> set table keep the
+        // SoA form: kept conservative (a bucket is one set there too, so the slot rule would hold; not measured).
+        const bool direct = allow_direct && merge && !want_first && R->n &&
+                            (O.nhits == O.nrows || P->bucket_identity) && !chip_test_env("CATCHHIP_ROWS_SOA");
+        if (direct) {
+            R->rows4.swap(O.B.S); R->bstart.swap(O.B.bstart); R->mcnt.swap(O.B.mcnt); R->rstart.swap(O.B.rstart);
+            R->slots = O.nhits;
+            R->nb = O.B.nb;
+            R->bucket_set = bucket_set;
         } else {
-            MergedRows M;
-            if ((rc = build_rows_radix(ctx, O.B, O.nrec, O.nrec_dev, O.nhits, P->bucket_set.p, T->genome_off.p,
-                                       (u32)T->ngenomes, P->max_set_id, M, tm, O.from_join ? &O.J : nullptr))) break;
-            R->n = M.nmerged;
-            if ((rc = R->set_id.alloc(R->n))) break;
-            if ((rc = R->univ.alloc(R->n))) break;
-            if ((rc = R->gs.alloc(R->n))) break;
-            if ((rc = R->ge.alloc(R->n))) break;
-            if (M.n) {
-                DevBuf<u32> d_lmax;
-                if ((rc = d_lmax.alloc(1))) break;
-                if (hipMemsetAsync(d_lmax.p, 0, sizeof(u32), ctx->stream) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-                hipLaunchKernelGGL(rows_compact_kernel, dim3((unsigned)div_up(M.n, 256)), dim3(256), 0, ctx->stream,
-                                   M.keys.p, M.head.p, M.mend.p, M.seg.p, M.idx.p, M.n, R->set_id.p, R->univ.p,
-                                   R->gs.p, R->ge.p, d_lmax.p);
+            TRY(chip_rows_alloc_soa(R.get(), R->n));
+        }
+        if (R->n) {
+            if (!direct) {
+                rows_emit(ctx, R.get(), O.B.rstart.p, O.B.nb, O.B.bstart.p, bucket_set, O.B.S.p, nullptr, nullptr,
+                          O.nhits == O.nrows ? 1 : 0);
                 tm.launch();
-                if (hipMemcpyAsync(ctx->h_pin, d_lmax.p, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                    hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-                R->lmax = *(volatile u32 *)ctx->h_pin;
+            }
+            if (merge && O.B.bsum.p && O.B.bsum.n >= (size_t)O.B.nb && P->max_set_id < ((i64)1 << 31)) {
+                // the sets' total row lengths: what the first round of a full-coverage solve would count
+                const u32 ng = (u32)std::max<i64>(P->max_set_id + 1, (i64)(P->bucket_identity ? O.B.nb : 0));
+                TRY(R->gain0.alloc(ng));
+                HIP_TRY(hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)ng, ctx->stream));
+                hipLaunchKernelGGL(rows_gain0_kernel, dim3((unsigned)div_up((i64)O.B.nb, 256)), dim3(256), 0, ctx->stream,
+                                   (const unsigned long long *)O.B.bsum.p, O.B.nb, bucket_set, ng, R->gain0.p);
+                R->gain0_n = ng;
+                tm.launch();
             }
         }
-        if (want_first && R->n) {
-            DevBuf<unsigned long long> first;
-            DevBuf<u32> d_order;
-            if ((rc = first.alloc(R->n)) || (rc = R->first_key.alloc(R->n))) break;
-            if (anchor_order) {
-                if ((rc = d_order.alloc((size_t)P->nent))) break;
-                if (hipMemcpyAsync(d_order.p, anchor_order, sizeof(u32) * (size_t)P->nent, hipMemcpyHostToDevice,
-                                   ctx->stream) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
-            }
-            if (hipMemsetAsync(first.p, 0xff, sizeof(unsigned long long) * (size_t)R->n, ctx->stream) != hipSuccess) {
-                rc = CATCHHIP_EHIP;
-                break;
-            }
-            const u32 nsrc = O.from_seeds ? O.nrec : O.H.n;
-            if (nsrc)
-                hipLaunchKernelGGL(first_seen_kernel, dim3((unsigned)div_up((i64)nsrc, 256)), dim3(256), 0, ctx->stream,
-                                   O.from_seeds ? 1 : 0, (const uint4 *)O.B.rec.p, (const u32 *)O.B.rank.p,
-                                   (const u32 *)O.S.spos.p, (const u32 *)O.S.sent.p, O.nrec_dev, nsrc,
-                                   (const u32 *)O.H.a.p, (const u32 *)O.H.d.p, (const u32 *)O.H.e.p,
-                                   (const u32 *)P->bucket_of.p, (const i32 *)P->bucket_set.p,
-                                   anchor_order ? (const u32 *)d_order.p : (const u32 *)nullptr, (const i32 *)R->set_id.p,
-                                   (const i32 *)R->univ.p, (const u32 *)R->gs.p, (const u32 *)R->ge.p,
-                                   (const u32 *)R->genome_off.p, (u32)R->n, first.p);
-            hipLaunchKernelGGL(first_seen_spread_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream,
-                               (const i32 *)R->set_id.p, (const i32 *)R->univ.p, (const u32 *)R->gs.p,
-                               (const u32 *)R->genome_off.p, (u32)R->n, (const unsigned long long *)first.p,
-                               R->first_key.p);
-            tm.launch(2);
-            // `first` and the order table go back to the pool after the synchronisation below
-            if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = CATCHHIP_EHIP; break; }
+    } else {
+        MergedRows M;
+        TRY(build_rows_radix(ctx, O.B, O.nrec, O.nrec_dev, O.nhits, P->bucket_set.p, T->genome_off.p,
+                             (u32)T->ngenomes, P->max_set_id, M, tm, O.from_join ? &O.J : nullptr));
+        R->n = M.nmerged;
+        TRY(chip_rows_alloc_soa(R.get(), R->n));
+        if (M.n) {
+            DevBuf<u32> d_lmax;
+            TRY(d_lmax.alloc(1));
+            HIP_TRY(hipMemsetAsync(d_lmax.p, 0, sizeof(u32), ctx->stream));
+            hipLaunchKernelGGL(rows_compact_kernel, dim3((unsigned)div_up(M.n, 256)), dim3(256), 0, ctx->stream,
+                               M.keys.p, M.head.p, M.mend.p, M.seg.p, M.idx.p, M.n, R->set_id.p, R->univ.p,
+                               R->gs.p, R->ge.p, d_lmax.p);
+            tm.launch();
+            TRY(read_count(ctx, d_lmax.p, &R->lmax));
         }
-        tm.stop();
-        // the scratch buffers of the build are released when O goes out of scope
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-            chip_set_error("cover_scan: row build failed: %s", hipGetErrorString(hipGetLastError()));
-            rc = CATCHHIP_EHIP;
-            break;
+    }
+    if (want_first && R->n) {
+        DevBuf<unsigned long long> first;
+        DevBuf<u32> d_order;
+        TRY(first.alloc(R->n));
+        TRY(R->first_key.alloc(R->n));
+        if (anchor_order) {
+            TRY(d_order.alloc((size_t)P->nent));
+            HIP_TRY(hipMemcpyAsync(d_order.p, anchor_order, sizeof(u32) * (size_t)P->nent, hipMemcpyHostToDevice,
+                                   ctx->stream));
         }
-        tm.finish_add();
-    } while (0);
-    if (rc) { delete R; return rc; }
-    *out = R;
+        HIP_TRY(hipMemsetAsync(first.p, 0xff, sizeof(unsigned long long) * (size_t)R->n, ctx->stream));
+        const u32 nsrc = O.from_seeds ? O.nrec : O.H.n;
+        if (nsrc)
+            hipLaunchKernelGGL(first_seen_kernel, dim3((unsigned)div_up((i64)nsrc, 256)), dim3(256), 0, ctx->stream,
+                               O.from_seeds ? 1 : 0, (const uint4 *)O.B.rec.p, (const u32 *)O.B.rank.p,
+                               (const u32 *)O.S.spos.p, (const u32 *)O.S.sent.p, O.nrec_dev, nsrc,
+                               (const u32 *)O.H.a.p, (const u32 *)O.H.d.p, (const u32 *)O.H.e.p,
+                               (const u32 *)P->bucket_of.p, (const i32 *)P->bucket_set.p,
+                               anchor_order ? (const u32 *)d_order.p : (const u32 *)nullptr, (const i32 *)R->set_id.p,
+                               (const i32 *)R->univ.p, (const u32 *)R->gs.p, (const u32 *)R->ge.p,
+                               (const u32 *)R->genome_off.p, (u32)R->n, first.p);
+        hipLaunchKernelGGL(first_seen_spread_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream,
+                           (const i32 *)R->set_id.p, (const i32 *)R->univ.p, (const u32 *)R->gs.p,
+                           (const u32 *)R->genome_off.p, (u32)R->n, (const unsigned long long *)first.p,
+                           R->first_key.p);
+        tm.launch(2);
+        // `first` and the order table go back to the pool after this synchronisation
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    tm.stop();
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipGetLastError());
+    tm.finish_add();
+    // the scratch buffers of the build are released when O goes out of scope
     if (nrows) *nrows = R->n;
+    *out = R.release();
     return 0;
 }
 
@@ -2307,19 +2268,14 @@ int chip_rows_materialise(catchhip_ctx *ctx, catchhip_rows *R) {
     if (!R->rows4.p) return 0;
     PoolScope pool_scope(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
-    TRY(R->set_id.alloc(R->n));
-    TRY(R->univ.alloc(R->n));
-    TRY(R->gs.alloc(R->n));
-    TRY(R->ge.alloc(R->n));
+    TRY(chip_rows_alloc_soa(R, R->n));
     // (the emit launch belongs to the row build: PHASE_ROWS is extended on purpose, at the price of one event
     // synchronisation on this fallback path)
     PhaseTimer tm(ctx, PHASE_ROWS, true);
     if (R->n) {
         tm.launch();
-        hipLaunchKernelGGL(rows_emit_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream,
-                           (const u32 *)R->rstart.p, R->nb, (const u32 *)R->bstart.p, R->bucket_set,
-                           (const uint4 *)R->rows4.p, (u32)R->n, (const u32 *)nullptr, R->set_id.p, R->univ.p, R->gs.p,
-                           R->ge.p, (const u32 *)nullptr, R->slots == R->n ? 1 : 0);
+        rows_emit(ctx, R, R->rstart.p, R->nb, R->bstart.p, R->bucket_set, R->rows4.p, nullptr, nullptr,
+                  R->slots == R->n ? 1 : 0);
     }
     HIP_TRY(hipGetLastError());
     tm.finish_add();
@@ -2664,9 +2620,8 @@ extern "C" int catchhip_adapter_votes(catchhip_ctx *ctx, const catchhip_rows *R,
     hipLaunchKernelGGL(av_heads_kernel, dim3((unsigned)div_up((i64)n + 1, 256)), dim3(256), 0, s, (const i32 *)R->set_id.p,
                        (const i32 *)R->univ.p, n, flag.p);
     TRY(chip_exclusive_scan_u32(ctx, flag.p, at.p, (i64)n + 1, tmp));
-    HIP_TRY(hipMemcpyAsync(ctx->h_pin, at.p + n, sizeof(u32), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const u32 nheads = *(volatile u32 *)ctx->h_pin;
+    u32 nheads;
+    TRY(read_count(ctx, at.p + n, &nheads));
     TRY(hkeys.alloc(nheads));
     TRY(heads.alloc(nheads));
     hipLaunchKernelGGL(av_headkeys_kernel, dim3(nb), dim3(256), 0, s, (const u32 *)flag.p, (const u32 *)at.p,
@@ -2691,17 +2646,17 @@ extern "C" int catchhip_rows_from_host(catchhip_ctx *ctx, const i32 *set_id, con
     ARG_CHECK(nrows == 0 || (set_id && universe && start && end));
     *out = nullptr;
     HIP_TRY(hipSetDevice(ctx->device));
-    catchhip_rows *R = new catchhip_rows();
+    std::unique_ptr<catchhip_rows> R(new catchhip_rows());
     R->ctx = ctx;
     R->ngenomes = ngenomes;
     R->n = nrows;
     R->h_genome_off.assign((size_t)ngenomes + 1, 0);
     for (i32 g = 0; g < ngenomes; ++g) {
-        if (genome_len[g] < 0) { delete R; chip_set_error("rows_from_host: negative genome length"); return CATCHHIP_EINVAL; }
+        if (genome_len[g] < 0) { chip_set_error("rows_from_host: negative genome length"); return CATCHHIP_EINVAL; }
         R->h_genome_off[g + 1] = R->h_genome_off[g] + genome_len[g];
     }
     R->total = R->h_genome_off[ngenomes];
-    if (R->total >= ((i64)1 << 32) - 4096) { delete R; chip_set_error("rows_from_host: coordinate space too large"); return CATCHHIP_EINVAL; }
+    if (R->total >= ((i64)1 << 32) - 4096) { chip_set_error("rows_from_host: coordinate space too large"); return CATCHHIP_EINVAL; }
     std::vector<u32> gs((size_t)nrows), ge((size_t)nrows), go((size_t)ngenomes + 1);
     for (i32 g = 0; g <= ngenomes; ++g) go[g] = (u32)R->h_genome_off[g];
     for (i64 i = 0; i < nrows; ++i) {
@@ -2714,30 +2669,22 @@ extern "C" int catchhip_rows_from_host(catchhip_ctx *ctx, const i32 *set_id, con
                 else if (u == universe[i - 1] && start[i] <= end[i - 1]) ok = false;  // must be disjoint, non-touching
             }
         }
-        if (!ok) { delete R; chip_set_error("rows_from_host: row %lld is invalid or out of order", (long long)i); return CATCHHIP_EINVAL; }
+        if (!ok) { chip_set_error("rows_from_host: row %lld is invalid or out of order", (long long)i); return CATCHHIP_EINVAL; }
         gs[i] = (u32)(R->h_genome_off[u] + start[i]);
         ge[i] = (u32)(R->h_genome_off[u] + end[i]);
         R->lmax = std::max(R->lmax, ge[i] - gs[i]);
     }
-    int rc = 0;
-    do {
-        if ((rc = R->set_id.alloc(nrows))) break;
-        if ((rc = R->univ.alloc(nrows))) break;
-        if ((rc = R->gs.alloc(nrows))) break;
-        if ((rc = R->ge.alloc(nrows))) break;
-        if ((rc = R->genome_off.alloc((size_t)ngenomes + 1))) break;
-        hipStream_t s = ctx->stream;
-        if ((nrows && (hipMemcpyAsync(R->set_id.p, set_id, sizeof(i32) * nrows, hipMemcpyHostToDevice, s) != hipSuccess ||
-                       hipMemcpyAsync(R->univ.p, universe, sizeof(i32) * nrows, hipMemcpyHostToDevice, s) != hipSuccess ||
-                       hipMemcpyAsync(R->gs.p, gs.data(), sizeof(u32) * nrows, hipMemcpyHostToDevice, s) != hipSuccess ||
-                       hipMemcpyAsync(R->ge.p, ge.data(), sizeof(u32) * nrows, hipMemcpyHostToDevice, s) != hipSuccess)) ||
-            hipMemcpyAsync(R->genome_off.p, go.data(), sizeof(u32) * (ngenomes + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            chip_set_error("rows_from_host: upload failed");
-            rc = CATCHHIP_EHIP;
-        }
-    } while (0);
-    if (rc) { delete R; return rc; }
-    *out = R;
+    TRY(chip_rows_alloc_soa(R.get(), nrows));
+    TRY(R->genome_off.alloc((size_t)ngenomes + 1));
+    hipStream_t s = ctx->stream;
+    if (nrows) {
+        HIP_TRY(hipMemcpyAsync(R->set_id.p, set_id, sizeof(i32) * nrows, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(R->univ.p, universe, sizeof(i32) * nrows, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(R->gs.p, gs.data(), sizeof(u32) * nrows, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(R->ge.p, ge.data(), sizeof(u32) * nrows, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemcpyAsync(R->genome_off.p, go.data(), sizeof(u32) * (ngenomes + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = R.release();
     return 0;
 }

@@ -1610,6 +1610,7 @@ static int greedy_flat(catchhip_ctx *ctx, const catchhip_rows *R, u32 nsets, con
         HIP_TRY(hipStreamSynchronize(s));
         for (int r = 0; r < timed; ++r) {
             float ms = 0.f;
+            // (timing is best effort: a pair that cannot be read adds nothing)
             if (hipEventElapsedTime(&ms, ctx->evx[2 * r], ctx->evx[2 * r + 1]) == hipSuccess) ctx->phase_ms[PHASE_CLAIM] += ms;
             ctx->phase_launches[PHASE_CLAIM]++;
         }

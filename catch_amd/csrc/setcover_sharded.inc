@@ -172,7 +172,7 @@ extern "C" int catchhip_shard_create_pi(catchhip_ctx *ctx, const catchhip_rows *
     if (R->n >= ((i64)1 << 31)) { chip_set_error("shard: too many rows"); return CATCHHIP_EINVAL; }
     HIP_TRY(hipSetDevice(ctx->device));
     PoolScope pool_scope(ctx);
-    catchhip_shard *S = new catchhip_shard();
+    std::unique_ptr<catchhip_shard> S(new catchhip_shard());
     S->ctx = ctx;
     const u32 nsets = (u32)num_sets;
     const u32 nrank = dense_ranks(ranks, nsets, S->h_rank);
@@ -180,18 +180,17 @@ extern "C" int catchhip_shard_create_pi(catchhip_ctx *ctx, const catchhip_rows *
     S->partial = partial;
     S->nsets = S->cap = nsets;
     // everything a round or a batch needs is allocated here: nothing can fail to allocate between two collectives
-    int rc = S->F.setup(ctx, R, nsets, S->has_ranks ? S->h_rank.data() : nullptr, nrank, true, nullptr,
-                        partial ? universe_p : nullptr);
-    if (!rc) rc = S->xg.alloc((size_t)nsets + 2);
-    if (!rc) rc = S->xl.alloc((size_t)nsets + 16);
-    if (!rc) rc = S->xlist[0].alloc(nsets);
-    if (!rc) rc = S->xlist[1].alloc(nsets);
-    if (!rc) rc = S->xflag.alloc((size_t)nsets + 1);
-    if (!rc) rc = S->xpos.alloc((size_t)nsets + 1);
-    if (!rc) rc = chip_exclusive_scan_reserve(S->xtmp, (i64)nsets + 1);
-    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = CATCHHIP_EHIP;
-    if (rc) { delete S; return rc; }
-    *out = S;
+    TRY(S->F.setup(ctx, R, nsets, S->has_ranks ? S->h_rank.data() : nullptr, nrank, true, nullptr,
+                   partial ? universe_p : nullptr));
+    TRY(S->xg.alloc((size_t)nsets + 2));
+    TRY(S->xl.alloc((size_t)nsets + 16));
+    TRY(S->xlist[0].alloc(nsets));
+    TRY(S->xlist[1].alloc(nsets));
+    TRY(S->xflag.alloc((size_t)nsets + 1));
+    TRY(S->xpos.alloc((size_t)nsets + 1));
+    TRY(chip_exclusive_scan_reserve(S->xtmp, (i64)nsets + 1));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *out = S.release();
     return 0;
 }
 

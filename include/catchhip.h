@@ -43,6 +43,14 @@ typedef struct catchhip_probes catchhip_probes;
 typedef struct catchhip_rows catchhip_rows;
 
 int catchhip_abi_version(void);
+/* The message of the calling thread's last failing call.  It is thread-local;
+ * EVERY call that returns a non-zero code sets it before it returns, so the
+ * text read right after a failure belongs to that failure and never to an
+ * earlier call (a successful call leaves it alone: read it only after a
+ * non-zero return).  For CATCHHIP_EHIP it names the failing HIP call with its
+ * source line and hipGetErrorString of the error that call returned; for
+ * CATCHHIP_EINVAL it says which argument or input was refused.  A call that
+ * fails hands out no object and has returned every device block it took. */
 const char *catchhip_last_error(void);
 
 /* ---- context: one HIP device + one stream ----------------------------- */
