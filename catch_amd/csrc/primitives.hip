@@ -278,3 +278,45 @@ int chip_radix_sort_pairs_segments(catchhip_ctx *ctx, DevBuf<u64> &keys, DevBuf<
     HIP_TRY(hipGetLastError());
     return 0;
 }
+
+// ------------------------------------------------------------------------
+// Test entry points (tests/test_primitives.py): host data in, one call of the primitive, its result out.
+// No logic of their own beyond the copies.
+// ------------------------------------------------------------------------
+extern "C" int catchhip_selftest_scan_u32(catchhip_ctx *ctx, const u32 *in, i64 n, i32 in_place, u32 *out) {
+    ARG_CHECK(ctx && n >= 0 && n < ((i64)1 << 32) && (n == 0 || (in && out)));
+    PoolScope pool_scope(ctx);
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevBuf<u32> d_in, d_out, tmp;
+    TRY(d_in.alloc((size_t)n));
+    if (!in_place) TRY(d_out.alloc((size_t)n));
+    HIP_TRY(hipMemcpyAsync(d_in.p, in, sizeof(u32) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    u32 *res = in_place ? d_in.p : d_out.p;
+    TRY(chip_exclusive_scan_u32(ctx, d_in.p, res, n, tmp));
+    HIP_TRY(hipMemcpyAsync(out, res, sizeof(u32) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int catchhip_selftest_sort_pairs(catchhip_ctx *ctx, u64 *keys, u32 *vals, i64 n, i64 nseg, i32 key_bits,
+                                            i32 first_bit) {
+    ARG_CHECK(ctx && n >= 0 && nseg >= 0 && nseg < ((i64)1 << 31) && n < ((i64)1 << 32));
+    const i64 total = n * (nseg > 0 ? nseg : 1);
+    ARG_CHECK(total < ((i64)1 << 32) && (total == 0 || (keys && vals)));
+    PoolScope pool_scope(ctx);
+    if (total == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevBuf<u64> d_keys, d_keys_alt;
+    DevBuf<u32> d_vals, d_vals_alt;
+    TRY(d_keys.alloc((size_t)total));
+    TRY(d_vals.alloc((size_t)total));
+    HIP_TRY(hipMemcpyAsync(d_keys.p, keys, sizeof(u64) * (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_vals.p, vals, sizeof(u32) * (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+    if (nseg == 0) TRY(chip_radix_sort_pairs(ctx, d_keys, d_keys_alt, d_vals, d_vals_alt, n, key_bits, first_bit));
+    else TRY(chip_radix_sort_pairs_segments(ctx, d_keys, d_keys_alt, d_vals, d_vals_alt, n, nseg, key_bits, first_bit));
+    HIP_TRY(hipMemcpyAsync(keys, d_keys.p, sizeof(u64) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(vals, d_vals.p, sizeof(u32) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}

@@ -282,6 +282,27 @@ class Context:
         """catchhip_comm_selftest: a checked SUM all-reduce on this context's communicator (collective)."""
         check(self._L.catchhip_comm_selftest(self._h, int(nelem)))
 
+    # -- test entry points of the device-wide primitives (tests/test_primitives.py) ---
+    def selftest_scan_u32(self, values, in_place=False):
+        """catchhip_selftest_scan_u32: the device's exclusive prefix sum (mod 2^32) of uint32 values."""
+        x = np.ascontiguousarray(values, dtype=np.uint32)
+        out = np.zeros(max(x.size, 1), dtype=np.uint32)
+        check(self._L.catchhip_selftest_scan_u32(self._h, _ptr(x, c_u32p), int(x.size), int(bool(in_place)),
+                                                 _ptr(out, c_u32p)))
+        return out[:x.size]
+
+    def selftest_sort_pairs(self, keys, vals, key_bits, first_bit=0, nseg=0):
+        """catchhip_selftest_sort_pairs: (keys, vals) as the device's radix sort leaves them.  nseg = 0: one sort
+        of all pairs; nseg >= 1: keys / vals are nseg segments of equal length, each sorted on its own."""
+        k = np.array(keys, dtype=np.uint64, order="C").reshape(-1)
+        v = np.array(vals, dtype=np.uint32, order="C").reshape(-1)
+        if k.size != v.size or (nseg > 0 and k.size % nseg):
+            raise ValueError("selftest_sort_pairs: keys and vals must be nseg segments of one length")
+        n = k.size // nseg if nseg > 0 else k.size
+        check(self._L.catchhip_selftest_sort_pairs(self._h, _ptr(k, c_u64p), _ptr(v, c_u32p), int(n), int(nseg),
+                                                   int(key_bits), int(first_bit)))
+        return k, v
+
     # -- near-duplicate filter --------------------------------------------
     def ndf_hamming(self, probe_strs, L, positions, dist_thres):
         n = len(probe_strs)

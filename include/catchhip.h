@@ -407,6 +407,21 @@ int catchhip_comm_destroy(catchhip_ctx *ctx);
  * elements.  catch_amd.parallel.init_from_env runs it once after catchhip_comm_init and
  * falls back to the host exchange, by agreement of all ranks, if any rank fails. */
 int catchhip_comm_selftest(catchhip_ctx *ctx, int64_t nelem);
+/* Test entry points of the two device-wide primitives every kernel family builds
+ * on (csrc/primitives.hip); tests/test_primitives.py compares them with NumPy.
+ * No reference counterpart.
+ * _scan_u32: out[i] = in[0] + .. + in[i-1] (mod 2^32) for n values; in_place != 0
+ * scans the uploaded buffer onto itself, otherwise into a second buffer.
+ * _sort_pairs: keys / vals hold n * max(nseg, 1) pairs and come back as the device
+ * buffers stand after the call.  nseg == 0: one stable sort of n pairs on
+ * max(1, ceil(key_bits / 8)) 8-bit digits from first_bit upwards; nseg >= 1:
+ * nseg segments of n pairs side by side, each sorted on its own.  The sort's own
+ * refusals (CATCHHIP_EINVAL) come back unchanged. */
+int catchhip_selftest_scan_u32(catchhip_ctx *ctx, const uint32_t *in, int64_t n,
+                               int32_t in_place, uint32_t *out);
+int catchhip_selftest_sort_pairs(catchhip_ctx *ctx, uint64_t *keys, uint32_t *vals,
+                                 int64_t n, int64_t nseg, int32_t key_bits,
+                                 int32_t first_bit);
 /* Which RCCL the communicators of this library go through: "RCCL version code V
  * from <file> (<how it was chosen>)".  The library opens ONE copy by path
  * (CATCHHIP_RCCL_PATH, else /opt/rocm/lib/librccl.so) instead of whatever file of

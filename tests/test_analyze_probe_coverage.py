@@ -5,6 +5,7 @@ The reference results are recorded by tests/golden/make_analysis_golden.py from 
 (tests/golden/analysis_cli.json.gz): per case the inputs, the cover ranges, `sliding_coverage`, the three written
 files and the printed report.  The window rule is restated here in NumPy (restate_windows); the restatement is
 pinned to the recorded reference results without a GPU, and the kernel is then tested against the restatement."""
+import functools
 import gzip
 import json
 import logging
@@ -41,6 +42,27 @@ def restate_windows(starts, ends, n, length, stride):
         piece = depth[ws:we]
         out.append((ws, int(piece.sum(dtype=np.uint64)), int(piece.size)))
     return out
+
+
+def restate_windows_vectorised(starts, ends, n, length, stride):
+    """restate_windows without the Python loop over the windows (a table of millions of positions has hundreds of
+    thousands): the depth as uint16, its prefix sums in 64 bits, and the slice rule written out -- a window that
+    passes the end becomes depth[n - length : n], whose negative start counts from the end and stops at 0.  Same
+    result, the reported start (negative when n < length) included."""
+    diff = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(diff, np.asarray(starts, dtype=np.int64), 1)
+    np.add.at(diff, np.asarray(ends, dtype=np.int64), -1)
+    depth = np.cumsum(diff[:n]).astype(np.uint16)
+    prefix = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(depth, dtype=np.uint64, out=prefix[1:])
+    ws = np.arange(0, n, stride, dtype=np.int64)
+    we = ws + length
+    over = we > n
+    we = np.where(over, n, we)
+    ws = np.where(over, we - length, ws)
+    lo = np.where(ws < 0, np.maximum(ws + n, 0), ws)            # the slice's own start
+    sums = prefix[we] - prefix[lo]
+    return list(zip(ws.tolist(), sums.tolist(), (we - lo).tolist()))
 
 
 def restated_dict(starts, ends, n, length, stride):
@@ -180,29 +202,24 @@ def _random_table(rng, lengths, nsets, max_intervals):
     return (np.asarray(si, np.int32), np.asarray(un, np.int32), np.asarray(st, np.int64), np.asarray(en, np.int64))
 
 
-def _expect_windows(un, st, en, lengths, span_first, length, stride):
+def _expect_windows(un, st, en, lengths, span_first, length, stride, restate=restate_windows):
     off = np.concatenate(([0], np.cumsum(lengths)))
     sums, counts, per_span = [], [], []
     for u0, u1 in zip(span_first[:-1], span_first[1:]):
         inside = (un >= u0) & (un < u1)
         base = off[un[inside]] - off[u0]
-        w = restate_windows(st[inside] + base, en[inside] + base, int(off[u1] - off[u0]), length, stride)
+        w = restate(st[inside] + base, en[inside] + base, int(off[u1] - off[u0]), length, stride)
         sums += [x[1] for x in w]
         counts += [x[2] for x in w]
         per_span.append(len(w))
     return sums, counts, np.concatenate(([0], np.cumsum(per_span))).tolist()
 
 
-@pytest.mark.gpu
-def test_window_depth_kernel_equals_the_restatement(ctx):
-    """catchhip_rows_window_depth on tables built with catchhip_rows_from_host: random spans of several universes
-    (empty universes and empty spans among them, spans that start after universe 0, tiles of 2048 positions
-    crossed), window / stride pairs with the window longer than every span among them."""
-    from catch_amd import engine
+def _kernel_test_shapes():
+    """The table, the span sets and the (window, stride) pairs of test_window_depth_kernel_equals_the_restatement."""
     rng = np.random.default_rng(5)
     lengths = np.asarray([700, 0, 1300, 37, 2048, 1, 24, 5000, 0, 0, 90, 4096, 333, 49, 50, 51], dtype=np.int64)
-    si, un, st, en = _random_table(rng, lengths, nsets=40, max_intervals=3)
-    rows = engine.Rows.from_host(ctx, si, un, st, en, lengths)
+    table = _random_table(rng, lengths, nsets=40, max_intervals=3)
     nu = len(lengths)
     span_sets = [
         np.arange(nu + 1),                                    # every universe a span
@@ -211,9 +228,59 @@ def test_window_depth_kernel_equals_the_restatement(ctx):
         np.asarray([0, nu]),                                  # everything one genome
         np.asarray([4, 4]),                                   # one empty span
     ]
+    return lengths, table, span_sets, ((50, 25), (1, 1), (7, 3), (3, 7), (20000, 1000), (4000, 1), (2048, 2048))
+
+
+def test_vectorised_window_rule_equals_the_looped_one_and_the_recorded_reference():
+    """No GPU: restate_windows_vectorised == restate_windows, window by window (reported start, sum, bases), on every
+    span and (window, stride) pair of the kernel test -- spans shorter than the window and than half of it, empty
+    ones and windows longer than every span among them -- and on the recorded cover ranges, where it therefore gives
+    the recorded sliding_coverage as restate_windows does."""
+    lengths, (_si, un, st, en), span_sets, shapes = _kernel_test_shapes()
+    off = np.concatenate(([0], np.cumsum(lengths)))
+    seen = set()
+    for span_first in span_sets:
+        for u0, u1 in zip(span_first[:-1], span_first[1:]):
+            inside = (un >= u0) & (un < u1)
+            base = off[un[inside]] - off[u0]
+            n = int(off[u1] - off[u0])
+            for length, stride in shapes:
+                args = (st[inside] + base, en[inside] + base, n, length, stride)
+                assert restate_windows_vectorised(*args) == restate_windows(*args), (u0, u1, length, stride)
+                seen.add("empty" if n == 0 else "half" if 2 * n < length else "window" if n < length else "long")
+    assert seen == {"empty", "half", "window", "long"}
+    for length, stride in shapes:
+        want = _expect_windows(un, st, en, lengths, span_sets[1], length, stride)
+        assert _expect_windows(un, st, en, lengths, span_sets[1], length, stride, restate=restate_windows_vectorised) == want
+    assert restate_windows_vectorised([0], [30], 40, 50, 25) == [(-10, 0, 10), (-10, 0, 10)]
+    assert restate_windows_vectorised([0], [15], 20, 50, 25) == [(-30, 15, 20)]
+    assert restate_windows_vectorised([], [], 0, 50, 25) == []
+    ngenomes = 0
+    for c in golden_cases():
+        for i, grp in enumerate(c["genome_lengths"]):
+            for j, n in enumerate(grp):
+                for r in range(2):
+                    cov = c["target_covers"][i][j][r]
+                    args = ([a for a, _ in cov], [b for _, b in cov], n, 50, 25)
+                    got = restate_windows_vectorised(*args)
+                    assert got == restate_windows(*args), (c["name"], i, j, r)
+                    assert {ws + 50 / 2: float(s) / k for ws, s, k in got} == \
+                        {k: v for k, v in c["sliding_coverage"][i][j][r]}, (c["name"], i, j, r)
+                    ngenomes += 1
+    assert ngenomes >= 60
+
+
+@pytest.mark.gpu
+def test_window_depth_kernel_equals_the_restatement(ctx):
+    """catchhip_rows_window_depth on tables built with catchhip_rows_from_host: random spans of several universes
+    (empty universes and empty spans among them, spans that start after universe 0, tiles of 2048 positions
+    crossed), window / stride pairs with the window longer than every span among them."""
+    from catch_amd import engine
+    lengths, (si, un, st, en), span_sets, shapes = _kernel_test_shapes()
+    rows = engine.Rows.from_host(ctx, si, un, st, en, lengths)
     covered = 0
     for span_first in span_sets:
-        for length, stride in ((50, 25), (1, 1), (7, 3), (3, 7), (20000, 1000), (4000, 1), (2048, 2048)):
+        for length, stride in shapes:
             sums, counts, win_off = rows.window_depth(span_first, length, stride)
             want = _expect_windows(un, st, en, lengths, span_first, length, stride)
             assert win_off.tolist() == want[2], (span_first, length, stride)
@@ -267,6 +334,103 @@ def test_window_depth_wraps_at_65536_and_refuses_bad_arguments(ctx):
                                            out_c.ctypes.data_as(c_u32p), 4)
     assert rc == -1 and per[0] == 12
     rows.close()
+
+
+# ------------------------------------------------------------------ the second turns: more than 1,024 tiles, more windows than threads
+WD_TILE = 2048                     # positions per tile of wd_tile_kernel; wd_tilescan_kernel scans 1,024 tile sums per turn
+CARRY_AT = 1024 * WD_TILE          # = 2,097,152: the first position whose prefix needs the carry of the second turn
+BIG_LENGTHS = (777, 0, 2_200_123)  # a short universe, an empty one, one of a little more than 2,200,000 bases
+
+
+@functools.lru_cache(maxsize=1)
+def _big_table():
+    """A few thousand rows over 7 sets by _random_table's rules; set 6 is written by hand around CARRY_AT (global
+    coordinates: the long universe starts at 777)."""
+    rng = np.random.default_rng(2097152)
+    lengths = np.asarray(BIG_LENGTHS, dtype=np.int64)
+    si, un, st, en = _random_table(rng, lengths, nsets=6, max_intervals=600)
+    x = CARRY_AT - int(lengths[0])               # the long universe's own coordinate of CARRY_AT
+    by_hand = [(5, 90), (x - 70000, x - 3), (x - 2, x + 1), (x + 2, x + 2049), (x + 5000, x + 90000),
+               (int(lengths[2]) - 4000, int(lengths[2]))]
+    si = np.concatenate((si, np.full(len(by_hand), 6, np.int32)))
+    un = np.concatenate((un, np.full(len(by_hand), 2, np.int32)))
+    st = np.concatenate((st, np.asarray([a for a, _ in by_hand], np.int64)))
+    en = np.concatenate((en, np.asarray([b for _, b in by_hand], np.int64)))
+    return lengths, si, un, st, en
+
+
+def test_big_window_table_is_what_it_claims():
+    """No GPU: the table obeys _random_table's rules, has more than 1,024 tiles, rows on both sides of CARRY_AT and
+    rows that straddle it."""
+    lengths, si, un, st, en = _big_table()
+    assert 2000 <= si.size <= 9000 and np.unique(si).size == 7
+    order = np.lexsort((st, un, si))
+    assert (order == np.arange(si.size)).all()                              # sorted by (set, universe, start)
+    assert (st < en).all() and (st >= 0).all() and (en <= lengths[un]).all()
+    same = (si[1:] == si[:-1]) & (un[1:] == un[:-1])
+    assert (st[1:][same] > en[:-1][same]).all()                             # disjoint and not touching
+    total = int(lengths.sum())
+    assert 2_200_000 < total and (total >> 11) + 1 > 1024                   # the kernel's tile count
+    off = np.concatenate(([0], np.cumsum(lengths)))
+    gs, ge = st + off[un], en + off[un]
+    assert ((gs < CARRY_AT) & (ge > CARRY_AT)).sum() >= 3                   # straddling rows
+    assert (gs == CARRY_AT - 2).any() and (gs == CARRY_AT + 2).any()
+    assert (gs > CARRY_AT).sum() >= 50 and (ge < CARRY_AT).sum() >= 1000
+    assert set(un.tolist()) == {0, 2}
+
+
+def _compute_units(ctx):
+    """Compute units of the context's device, asked of the HIP runtime the library is linked to."""
+    import ctypes
+    path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
+    count = ctypes.c_int(0)
+    hip_device_attribute_multiprocessor_count = 63
+    rc = ctypes.CDLL(path).hipDeviceGetAttribute(ctypes.byref(count), hip_device_attribute_multiprocessor_count,
+                                                 int(ctx.device))
+    assert rc == 0 and 1 <= count.value <= 4096, (rc, count.value)
+    return count.value
+
+
+@pytest.mark.gpu
+def test_window_depth_beyond_1024_tiles_and_beyond_one_window_per_thread(ctx):
+    """wd_tilescan_kernel's second turn (the carry over 1,024 tile sums) and wd_window_kernel's second turn (more
+    windows than the 8 x CUs workgroups of 256 it is launched with), against the vectorised restatement.  Reached on
+    an MI355X: 1,075 tiles; 550,225 windows of (4, 4) over the table as one span against 524,288 threads at 256
+    compute units (with more compute units the stride shrinks until the windows outnumber the threads)."""
+    from catch_amd import engine
+    lengths, si, un, st, en = _big_table()
+    total = int(lengths.sum())
+    threads = 8 * 256 * _compute_units(ctx)
+    stride = 4
+    while stride > 1 and (total - 1) // stride + 1 <= threads:
+        stride -= 1
+    nwin = (total - 1) // stride + 1
+    assert nwin > threads, (nwin, threads)
+    rows = engine.Rows.from_host(ctx, si, un, st, en, lengths)
+    try:
+        for span_first in (np.asarray([0, 3]), np.asarray([0, 1, 2, 3]), np.asarray([2, 3])):
+            for length, step in ((4, stride), (100000, 50000), (3_000_000, 1_000_000)):
+                sums, counts, win_off = rows.window_depth(span_first, length, step)
+                want = _expect_windows(un, st, en, lengths, span_first, length, step, restate=restate_windows_vectorised)
+                assert win_off.tolist() == want[2], (span_first, length, step)
+                want_sums, want_counts = np.asarray(want[0], np.uint64), np.asarray(want[1], np.uint32)
+                bad = np.nonzero(sums != want_sums)[0]
+                assert bad.size == 0, (span_first.tolist(), length, step, bad[:5].tolist(), sums[bad[:5]].tolist(),
+                                       want_sums[bad[:5]].tolist())
+                assert np.array_equal(counts, want_counts), (span_first.tolist(), length, step)
+                if span_first.tolist() == [0, 3] and length == 4:
+                    assert sums.size == nwin
+                    past_carry = sums[CARRY_AT // step + 1:]             # windows that start beyond CARRY_AT
+                    past_threads = sums[threads:]                         # windows of a thread's second turn
+                    assert int(past_carry.sum()) > 0 and int(past_threads.sum()) > 0
+                    print("window depth: %d positions, %d tiles (> 1024); windows (%d, %d): %d > %d threads launched; "
+                          "sum of the depth beyond position %d: %d, over the windows past the first turn: %d"
+                          % (total, (total >> 11) + 1, length, step, nwin, threads, CARRY_AT, int(past_carry.sum()),
+                             int(past_threads.sum())))
+                if length == 3_000_000:
+                    assert (counts < length).all()                       # the window is longer than every span
+    finally:
+        rows.close()
 
 
 def _write_fasta(path, records):

@@ -2765,6 +2765,71 @@ def test_neighbour_graph_edge_cases(ctx):
 
 
 @pytest.mark.gpu
+def test_neighbour_lists_and_graph_of_a_large_clique(ctx, monkeypatch):
+    """4,200 identical sequences and 30 unrelated ones behind them.  Every clique vertex has 4,200 entries in its
+    neighbour list (itself included): more than the 4,096 that catchhip_sigs_neighbors copies back with the count,
+    so the second copy runs; 32 lists in one call are 134,400 entries, more than the 16,384 of
+    catchhip_sigs_neighbors_many's first copy (and more than the wrapper's first buffer: it grows and asks again);
+    the graph has 4,200 x 4,199 = 17,635,800 ordered pairs, more than the 2^24 slots of catchhip_sigs_graph's first
+    pass, so it counts, allocates n + 2 and runs again.  Every row is checked, not a sample."""
+    from catch_amd import engine
+    from catch_amd.utils import lsh
+    rng = np.random.RandomState(4200)
+
+    def rand(n):
+        return "".join("ACGT"[x] for x in rng.randint(0, 4, size=n))
+    nc, nu = 4200, 30
+    seqs = [rand(400)] * nc + [rand(400) for _ in range(nu)]
+    n = nc + nu
+    edges = nc * (nc - 1)
+    assert edges > 1 << 24 and edges > 1024 * n and nc > 4096 and 32 * nc > 16384
+    random.seed(9)
+    sigs = lsh.MinHashFamily(12, N=100).signatures(seqs)
+    try:
+        ptr, gidx, gcom = sigs.graph(9)
+        assert ptr.shape == (n + 1,) and gidx.size == gcom.size == edges
+        assert np.array_equal(ptr, np.minimum(np.arange(n + 1), nc) * (nc - 1))        # the unrelated rows are empty
+        others = np.arange(nc - 1, dtype=np.uint32)[None, :]
+        want = others + (others >= np.arange(nc, dtype=np.uint32)[:, None])            # row j: 0 .. nc - 1 without j
+        assert np.array_equal(gidx.reshape(nc, nc - 1), want)
+        assert (gcom == 100).all()
+        del want
+        ends = (1, nc // 2, nc - 2)
+        single = {}
+        for j in ends:
+            row = sigs.common_row(j).astype(np.int64)
+            assert (row[:nc] == 100).all() and (row[nc:] < 9).all()
+            idx, com = sigs.neighbors(j, 9)
+            assert idx.size == nc > 4096 and np.array_equal(idx, np.arange(nc)) and (com == 100).all()
+            single[j] = (idx, com)
+        for j in (nc, n - 1):                                    # an unrelated vertex: itself
+            idx, com = sigs.neighbors(j, 9)
+            assert idx.tolist() == [j] and com.tolist() == [100]
+        js = np.asarray(list(ends) + [5, nc - 1, 0] + list(range(100, 100 + 26 * 150, 150)))
+        assert js.size == 32 == engine.Signatures.NEIGHBORS_MANY_MAX and js.max() < nc
+        many = sigs.neighbors_many(js, 9)
+        assert sum(idx.size for idx, _ in many) == 32 * nc > 16384
+        for j, (idx, com) in zip(js.tolist(), many):
+            assert np.array_equal(idx, np.arange(nc)) and (com == 100).all(), j
+            if j in single:
+                assert np.array_equal(idx, single[j][0]) and np.array_equal(com, single[j][1])
+        mixed = sigs.neighbors_many([nc + 3, 7], 9)              # a short list in front of a long one
+        assert mixed[0][0].tolist() == [nc + 3] and np.array_equal(mixed[1][0], np.arange(nc))
+        print("clique of %d + %d unrelated: %d ordered pairs > 2^24 = %d (second graph pass); neighbour lists of %d "
+              "entries > 4096; %d entries from one call for 32 vertices > 16384"
+              % (nc, nu, gidx.size, 1 << 24, nc, 32 * nc))
+        # more pairs than the caller lets the graph hold: no graph, below and above the first pass's room
+        for limit in (1 << 20, edges - 1):
+            monkeypatch.setattr(engine.Signatures, "GRAPH_MAX_EDGES", limit)
+            assert sigs.graph(9) is None
+        monkeypatch.setattr(engine.Signatures, "GRAPH_MAX_EDGES", edges)
+        ptr2, gidx2, gcom2 = sigs.graph(9)
+        assert np.array_equal(ptr2, ptr) and np.array_equal(gidx2, gidx) and np.array_equal(gcom2, gcom)
+    finally:
+        sigs.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("first", ["hamming", "minhash"])
 def test_union_chunks_in_pipeline_stages_select_what_chunks_one_by_one_select(ctx, monkeypatch, first):
     """The clustered design's union instances (several clusters per chunk, several chunks): the three-stage

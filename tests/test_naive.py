@@ -444,6 +444,118 @@ def test_naive_pass_on_a_path_of_256_base_probes(ctx):
     g.close()
 
 
+# ------------------------------------------------------------------ more than 4,096 probes: a second turn of 64 bitmap words
+BIG_N, BIG_FAMILIES, BIG_LENGTH = 4200, 600, 24
+
+
+@functools.lru_cache(maxsize=1)
+def _big_family_set():
+    """4,200 probes of 24 bases: member k of family f sits at index f + 600 k and is the family's root with 0-2
+    substitutions out of ACGT and, now and then, N.  A family's members lie 600 indices apart, so rows below 4,096
+    have neighbours in the bitmap words 64 and 65 (columns 4,096-4,199) and the other way round."""
+    rng = np.random.default_rng(4200)
+    roots = rng.choice(list("ACGT"), size=(BIG_FAMILIES, BIG_LENGTH))
+    out = []
+    for i in range(BIG_N):
+        s = roots[i % BIG_FAMILIES].copy()
+        for j in rng.choice(BIG_LENGTH, size=int(rng.integers(0, 3)), replace=False):
+            s[j] = "N" if rng.random() < 0.1 else "ACGT"[int(rng.integers(4))]
+        out.append("".join(s))
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=1)
+def _big_mismatches():
+    """Hamming distance of every pair of _big_family_set, N a letter of its own: 24 minus the product of the one-hot
+    encodings (position x letter).  The product is taken in float32, whose sums of at most 24 ones are exact."""
+    strs = _big_family_set()
+    arr, lens = _encode(list(strs))
+    assert (lens == BIG_LENGTH).all()
+    onehot = (arr[:, :, None] == np.frombuffer(b"ACGTN", dtype=np.uint8)[None, None, :])
+    assert (onehot.sum(axis=2) == 1).all()
+    flat = onehot.reshape(BIG_N, BIG_LENGTH * 5).astype(np.float32)
+    same = flat @ flat.T
+    assert same.max() == BIG_LENGTH and (same == np.rint(same)).all()
+    return BIG_LENGTH - same.astype(np.int64)
+
+
+def _big_adjacency(thres):
+    adj = _big_mismatches() <= thres
+    np.fill_diagonal(adj, False)
+    return adj
+
+
+def test_hamming_adjacency_of_the_big_set_is_the_restatement_on_a_slice():
+    """No GPU: kind "shift" with shift 0 is the Hamming predicate, so restate_graph(..., "shift", 0, t) of 200 probes
+    of the big set -- 29 whole families, members on both sides of column 4,096 among them -- is that block of the
+    one-hot adjacency, at both thresholds, with edges at both; and the set is what it claims."""
+    strs = _big_family_set()
+    assert len(strs) == BIG_N and all(len(s) == BIG_LENGTH for s in strs) and set("".join(strs)) == set("ACGTN")
+    assert -(-BIG_N // 64) == 66                             # bitmap words per row: a second turn of the 64-word walk
+    pick = np.asarray([f + BIG_FAMILIES * k for f in range(540, 569) for k in range(7)][:200])
+    assert (pick < 4096).any() and (pick >= 4096).any() and (pick >= 4160).any()
+    sub = [strs[i] for i in pick]
+    for thres in (0, 4):
+        adj = _big_adjacency(thres)
+        want = restate_graph(sub, "shift", 0, thres)
+        assert want.any() and (adj[np.ix_(pick, pick)] == want).all(), thres
+        assert (adj == adj.T).all() and not adj.diagonal().any()
+        # some family has members on both sides of column 4,096, joined by an edge; both ways round, word 65 included
+        assert adj[500, 500 + 6 * BIG_FAMILIES] or thres == 0
+        assert adj[:4096, 4096:].any() and adj[4096:, :4096].any() and adj[:4096, 4160:].any() and adj[4160:, :4096].any()
+        in_family = adj[np.arange(BIG_N)[:, None] % BIG_FAMILIES == np.arange(BIG_N)[None, :] % BIG_FAMILIES].sum()
+        assert in_family >= (1000 if thres == 0 else 25000) and (thres == 0 or in_family == BIG_N * 6)
+    assert _big_adjacency(4).sum() > _big_adjacency(0).sum()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("thres", [0, 4])
+def test_graph_naive_pass_and_rows_above_4096_probes(ctx, thres):
+    """66 bitmap words per row: rg_degree_kernel and rg_fill_kernel take a second turn (and carry the count of the
+    first 64 words into it), rg_pairs_kernel runs on a 66 x 66 tile grid.  The fetched CSR graph is compared whole
+    with the one-hot adjacency, the naive pass with the reference's loop, the dominating-set rows with
+    {i} + N(i) in order."""
+    from catch_amd import engine
+    strs = list(_big_family_set())
+    adj = _big_adjacency(thres)
+    g = engine.RedundancyGraph(ctx, strs, engine.REDUNDANT_SHIFT, 0, thres)
+    try:
+        ptr, idx = g.fetch()
+        want_ptr = np.concatenate(([0], np.cumsum(adj.sum(axis=1))))
+        want_row, want_idx = np.nonzero(adj)                             # row-major: every row ascending
+        assert want_idx.size > 0 and g.nedges == idx.size
+        assert np.array_equal(ptr, want_ptr), np.nonzero(ptr != want_ptr)[0][:5].tolist()
+        assert np.array_equal(idx, want_idx), np.nonzero(idx != want_idx)[0][:5].tolist()
+        # (said by the equality, and cheap to say on its own:) symmetric, every row ascending, no loops
+        got = np.zeros((BIG_N, BIG_N), dtype=bool)
+        row = np.repeat(np.arange(BIG_N), np.diff(ptr))
+        got[row, idx] = True
+        assert (got == got.T).all() and not got.diagonal().any()
+        inner = np.ones(idx.size, dtype=bool)
+        inner[ptr[:-1][np.diff(ptr) > 0]] = False
+        assert (np.diff(idx.astype(np.int64))[inner[1:]] > 0).all()
+        keep = g.naive()
+        assert np.array_equal(keep, naive_loop(ptr, idx)) and 0 < keep.sum() < BIG_N
+        rows = g.rows()
+        try:
+            assert rows.n == g.nedges + BIG_N
+            set_id, univ, start, end = rows.fetch()
+            with_self = adj.copy()
+            np.fill_diagonal(with_self, True)
+            want_set, want_elem = np.nonzero(with_self)
+            assert np.array_equal(set_id, want_set) and np.array_equal(start, 2 * want_elem)
+            assert np.array_equal(end, start + 1) and not univ.any()
+        finally:
+            rows.close()
+        high = int((want_idx[want_row < 4096] >= 4096).sum()), int((want_idx[want_row >= 4096] < 4096).sum())
+        assert high[0] > 0 and high[1] > 0 and (want_idx[want_row < 4096] >= 4160).any()
+        print("redundancy graph of %d probes, mismatches <= %d: rowwords %d, %d directed edges, %d from rows below 4096 "
+              "to columns from 4096, %d the other way, longest row %d, naive pass keeps %d"
+              % (BIG_N, thres, -(-BIG_N // 64), idx.size, high[0], high[1], int(np.diff(ptr).max()), int(keep.sum())))
+    finally:
+        g.close()
+
+
 def _predicate(case):
     from catch_amd.filter import naive_redundant_filter as nrf
     if case["kind"] == "default":
