@@ -15,6 +15,7 @@
 //
 // Everything is integer arithmetic; the host divides sum by count.
 #include "internal.h"
+#include "wave.h"
 
 #include <algorithm>
 
@@ -45,13 +46,9 @@ wd_tile_kernel(u32 *__restrict__ d, u64 total, u64 *__restrict__ tile_sum) {
         v[j] = (base + j < total) ? (d[base + j + 1] & 0xffffu) : 0u;
         s += v[j];
     }
+    // (block_excl_scan_u32 of wave.h written out below the wave scan: through that helper this kernel takes 34 VGPRs, not 33)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 inc = s;
-#pragma unroll
-    for (int k = 1; k < WAVE; k <<= 1) {
-        const u32 t = __shfl_up(inc, k, WAVE);
-        if (lane >= k) inc += t;
-    }
+    const u32 inc = wave_incl_scan(s, lane);
     if (lane == 63) lds[wave] = inc;
     __syncthreads();
     u32 woff = 0, tot = 0;
@@ -81,12 +78,7 @@ wd_tilescan_kernel(u64 *__restrict__ t, u64 n) {
     for (u64 base = 0; base < n; base += 1024) {
         const u64 i = base + threadIdx.x;
         const u64 v = i < n ? t[i] : 0;
-        u64 inc = v;
-#pragma unroll
-        for (int k = 1; k < WAVE; k <<= 1) {
-            const u64 x = __shfl_up(inc, k, WAVE);
-            if (lane >= k) inc += x;
-        }
+        const u64 inc = wave_incl_scan(v, lane);
         if (lane == 63) lds[wave] = inc;
         __syncthreads();
         u64 woff = 0, tot = 0;

@@ -31,18 +31,9 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "wave.h"
 
 #define CAND_NONE 0xffffffffu
-
-__device__ __forceinline__ u32 cand_find_segment(const u32 *__restrict__ off, u32 n, u32 x) {
-    u32 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u32 mid = (lo + hi) >> 1;
-        if (off[mid] <= x) lo = mid; else hi = mid;
-    }
-    while (lo + 1 < n && off[lo + 1] <= x) ++lo;
-    return lo;
-}
 
 __global__ void __launch_bounds__(256)
 cand_flags_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ seq_off, u32 nseq, u32 total,
@@ -51,7 +42,7 @@ cand_flags_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ seq_off,
     if (g > total) return;
     u32 pr = 0, rs = 0;
     if (g < total && bytes[g] == 'N') {
-        const u32 sq = cand_find_segment(seq_off, nseq, g);
+        const u32 sq = find_segment(seq_off, nseq, g);
         const u32 lo = seq_off[sq], hi = seq_off[sq + 1];
         pr = (g + 1 < hi && bytes[g + 1] == 'N') ? 1u : 0u;
         rs = (pr && (g == lo || bytes[g - 1] != 'N')) ? 1u : 0u;
@@ -88,7 +79,7 @@ cand_regular_kernel(const u32 *__restrict__ seq_off, u32 nseq, u32 L, u32 stride
                     u32 *__restrict__ slots) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nwin_total) return;
-    const u32 q = cand_find_segment(win_off, nseq, t);
+    const u32 q = find_segment(win_off, nseq, t);
     const u32 w = t - win_off[q], nw = win_off[q + 1] - win_off[q];
     const u32 lo = seq_off[q], hi = seq_off[q + 1], n = hi - lo;
     u32 s = CAND_NONE;
@@ -105,7 +96,7 @@ cand_flank_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ seq_off,
                   const u32 *__restrict__ pairs_before, u32 *__restrict__ slots) {
     const u32 a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= total || !rstart[a]) return;
-    const u32 q = cand_find_segment(seq_off, nseq, a);
+    const u32 q = find_segment(seq_off, nseq, a);
     const u32 nw = win_off[q + 1] - win_off[q];
     if (nw == 0) return;                                        // skipped sequence
     const u32 lo = seq_off[q], hi = seq_off[q + 1];
@@ -142,7 +133,7 @@ cand_hash_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ cpos, u32
     const u8 *p = bytes + cpos[c];
     u64 h = 0x9e3779b97f4a7c15ull ^ (u64)L;
     if (seq_group) {   // independent groups: equal windows of different groups are different candidates
-        const u32 g = (u32)seq_group[cand_find_segment(seq_off, nseq, cpos[c])];
+        const u32 g = (u32)seq_group[find_segment(seq_off, nseq, cpos[c])];
         cgrp[c] = g;
         h = (h ^ (u64)g) * 0xff51afd7ed558ccdull;
     }

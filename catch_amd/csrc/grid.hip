@@ -21,19 +21,9 @@
 #include <chrono>
 
 #include "internal.h"
+#include "wave.h"
 
 #define GRID_NEVER 0xffffffffu
-
-// the sequence holding base x (empty sequences skipped), as the scan files hits
-__device__ __forceinline__ u32 grid_segment(const u32 *__restrict__ off, u32 n, u32 x) {
-    u32 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u32 mid = (lo + hi) >> 1;
-        if (off[mid] <= x) lo = mid; else hi = mid;
-    }
-    while (lo + 1 < n && off[lo + 1] <= x) ++lo;
-    return lo;
-}
 
 // thr[r] = the smallest e at which row r merges with its predecessor (GRID_NEVER:
 // first row of its (set, universe), or a whole sequence lies between the two)
@@ -45,7 +35,7 @@ grid_thresh_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__ univ,
     u32 v = GRID_NEVER;
     if (r > 0 && set_id[r] == set_id[r - 1] && univ[r] == univ[r - 1]) {
         const u32 s = gs[r], t = ge[r - 1];
-        const u32 a = grid_segment(seq_off, nseq, t - 1u), b = grid_segment(seq_off, nseq, s);
+        const u32 a = find_segment(seq_off, nseq, t - 1u), b = find_segment(seq_off, nseq, s);
         if (a == b) {
             v = (s - t + 1u) >> 1;                       // ceil(g / 2), g >= 1
         } else if (seq_off[a + 1] == seq_off[b]) {       // adjacent (only empty sequences between)
@@ -77,14 +67,14 @@ grid_emit_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__ univ, c
     const u32 o = head ? pos[r] : pos[r] - 1u;   // (pos is exclusive; row 0 is always a head)
     if (head) {
         const u32 s = gs[r];
-        const u32 lo = seq_off[grid_segment(seq_off, nseq, s)];
+        const u32 lo = seq_off[find_segment(seq_off, nseq, s)];
         o_set[o] = set_id[r];
         o_univ[o] = univ[r];
         o_gs[o] = (s - lo > e) ? s - e : lo;
     }
     if (last) {
         const u32 t = ge[r];
-        const u32 hi = seq_off[grid_segment(seq_off, nseq, t - 1u) + 1];
+        const u32 hi = seq_off[find_segment(seq_off, nseq, t - 1u) + 1];
         o_ge[o] = (hi - t > e) ? t + e : hi;
         if (r + 1 == n) info[0] = o + 1u;
     }
@@ -103,7 +93,7 @@ grid_len_kernel(const i32 *__restrict__ o_set, const u32 *__restrict__ o_gs, con
         const u32 sid = (u32)o_set[o];
         if (gain0 && sid < ng) atomicAdd(&gain0[sid], len);
     }
-    for (int d = 32; d > 0; d >>= 1) len = max(len, __shfl_down(len, d));
+    len = wave_max(len);
     if ((threadIdx.x & 63u) == 0 && len) atomicMax(&info[1], len);
 }
 

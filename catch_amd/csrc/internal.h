@@ -464,6 +464,18 @@ __host__ __device__ static inline long long chip_pyhash_seed0(const u8 *src, int
 // after they were added in index order (core.hip)
 void chip_pyset_order(const i64 *hash, i64 n, i64 *order);
 
+// Body of a function that picks the instance of a kernel template for a probe of nw 32-base words (host side):
+// returns KERNEL<nw, further template arguments...> for nw in 1..MAX (MAX is 7 or 8), nullptr for any other nw.
+#define PICK_NW_CASES_7(KERNEL, ...)                                                                          \
+    case 1: return KERNEL<1, ##__VA_ARGS__>; case 2: return KERNEL<2, ##__VA_ARGS__>;                         \
+    case 3: return KERNEL<3, ##__VA_ARGS__>; case 4: return KERNEL<4, ##__VA_ARGS__>;                         \
+    case 5: return KERNEL<5, ##__VA_ARGS__>; case 6: return KERNEL<6, ##__VA_ARGS__>;                         \
+    case 7: return KERNEL<7, ##__VA_ARGS__>;
+#define PICK_NW_CASES_8(KERNEL, ...) PICK_NW_CASES_7(KERNEL, ##__VA_ARGS__) case 8: return KERNEL<8, ##__VA_ARGS__>;
+#define PICK_NW(MAX, nw, KERNEL, ...)                                                                         \
+    switch (nw) { PICK_NW_CASES_##MAX(KERNEL, ##__VA_ARGS__) }                                                \
+    return nullptr
+
 static inline int ceil_log2_u64(u64 x) {
     int b = 0;
     while (b < 64 && ((u64)1 << b) < x) ++b;

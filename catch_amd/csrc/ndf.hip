@@ -22,6 +22,7 @@
 #include <chrono>
 
 #include "internal.h"
+#include "wave.h"
 
 // The edge list is written through ONE counter per shard: a single counter is a
 // single address (~10 ns per atomic, however the compiler aggregates them), and
@@ -116,7 +117,7 @@ ndf_edge_kernel(const u64 *__restrict__ padded, u32 n, int W, int d, const i32 *
         }
     }
     // pairs compared (SURVEY 8(d) K3's C): one 64-bit add per wavefront, beside its shard's edge counter
-    for (int o = 32; o > 0; o >>= 1) npairs += __shfl_down(npairs, o, WAVE);
+    npairs = wave_sum(npairs);
     if ((threadIdx.x & 63) == 0 && npairs)
         atomicAdd((unsigned long long *)(count + ((x >> 6) & (ES_SHARDS - 1)) * ES_STRIDE + 2), (unsigned long long)npairs);
 }
@@ -462,6 +463,7 @@ ndf_lazy_kernel(Family fam, u32 n, const u64 *__restrict__ keys_all, const u32 *
         if (WAKE && verdict == 1 && atomicSub(&left[i], 1u) == 1u && atomicCAS(&status[i], 0u, 1u) == 0u) ndf_mark(Q.st2, i, 1u);
     }
     if (__ballot(compared != 0u)) {                  // (one atomic per wavefront and counter)
+        // (wave_sum_all_n of wave.h, written out: through the helper the MinHash instance of this kernel spills more registers)
         for (int o = 32; o > 0; o >>= 1) { compared += __shfl_xor(compared, o, WAVE); found += __shfl_xor(found, o, WAVE); }
         if (lane == 0) {
             atomicAdd(&pairs[wave_id & (ES_SHARDS - 1)], (unsigned long long)compared);
@@ -607,6 +609,7 @@ ndf_probe_kernel(Family fam, u32 n, const u64 *__restrict__ keys_all, const u32 
         }
     }
     if (__ballot(compared != 0u)) {
+        // (wave_sum_all_n of wave.h, written out: through the helper the MinHash instance of this kernel spills more registers)
         for (int o = 32; o > 0; o >>= 1) { compared += __shfl_xor(compared, o, WAVE); found += __shfl_xor(found, o, WAVE); }
         if (lane == 0) {
             atomicAdd(&pairs[wave_id & (ES_SHARDS - 1)], (unsigned long long)compared);
@@ -1261,7 +1264,7 @@ mh_kmer_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ probe_off, 
         __syncthreads();
         if (lane < MH_FPW) fp[(size_t)i * MH_FPW + lane] = s_fp[lane];
         u32 set = lane < MH_FPW ? (u32)__popcll(s_fp[lane]) : 0u;
-        for (int d = 32; d > 0; d >>= 1) set += __shfl_xor(set, d, WAVE);
+        set = wave_sum_all(set);
         if (lane == 0) { nuniq[i] = out; fp_excess[i] = out - set; }
     }
 }
@@ -1544,6 +1547,8 @@ struct MinHashFamily {       // same signature in table t (the key only groups),
     // i near j, by the whole wavefront (i, j wave-uniform): B's k-mers staged in LDS, every lane looks its share of
     // A's up by binary search, the matches are summed -- |A and B| >= need is what mh_near's walk decides (its early
     // exits only shorten the walk), `need` from a table of the reference's own two IEEE operations made on the host
+    // (The three wave sums are wave_sum_all of wave.h, written out: through the helper ndf_lazy_kernel's dense MinHash
+    // instance spills two more registers.)
     __device__ __forceinline__ bool near_wave(u32 i, u32 j, Scratch &S, u32 lane) const {
         const u32 na = nuniq[i], nb = nuniq[j];
         const u32 most = min(na, nb);

@@ -3,6 +3,7 @@
 // value) pairs.  Hand-written for gfx950: 64-lane wavefronts, wave-level
 // multi-split through __ballot, LDS for the per-workgroup digit tables.
 #include "internal.h"
+#include "wave.h"
 
 // ------------------------------------------------------------------------
 // exclusive scan (u32): tile reduce -> recursive scan of tile sums -> tile scan
@@ -11,33 +12,7 @@
 #define SCAN_ITEMS 8
 #define SCAN_TILE (SCAN_THREADS * SCAN_ITEMS)
 
-__device__ __forceinline__ u32 wave_incl_scan_u32(u32 v, int lane) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        u32 t = __shfl_up(v, d, WAVE);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// block-wide exclusive scan of one value per thread; returns exclusive prefix,
-// *block_total = sum over the block.  lds: 4+1 words.
-__device__ __forceinline__ u32 block_excl_scan_u32(u32 v, u32 *lds, u32 *block_total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 inc = wave_incl_scan_u32(v, lane);
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    u32 woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN_THREADS / WAVE; ++w) {
-        u32 t = lds[w];
-        if (w < wave) woff += t;
-        tot += t;
-    }
-    __syncthreads();
-    *block_total = tot;
-    return woff + inc - v;
-}
+static_assert(SCAN_THREADS == 256, "block_excl_scan_u32 scans a workgroup of 256");
 
 __global__ void __launch_bounds__(SCAN_THREADS)
 scan_tile_reduce(const u32 *__restrict__ in, u32 *__restrict__ tile_sums, i64 n) {
@@ -191,7 +166,7 @@ radix_scatter(const u64 *__restrict__ keys_in, const u32 *__restrict__ vals_in,
         u32 tot = 0;
 #pragma unroll
         for (int w = 0; w < RS_WAVES; ++w) { const u32 c = wave_cnt[w][tid]; wave_cnt[w][tid] = tot; tot += c; }
-        u32 inc = wave_incl_scan_u32(tot, lane);
+        u32 inc = wave_incl_scan(tot, lane);
         if (lane == 63) s_scan[wave] = inc;
         __syncthreads();
         u32 woff = 0;
@@ -280,8 +255,8 @@ int chip_radix_sort_pairs_segments(catchhip_ctx *ctx, DevBuf<u64> &keys, DevBuf<
 }
 
 // ------------------------------------------------------------------------
-// Test entry points (tests/test_primitives.py): host data in, one call of the primitive, its result out.
-// No logic of their own beyond the copies.
+// Test entry points (tests/test_primitives.py): host data in, one call of the primitive (for the helpers of wave.h:
+// one kernel that calls each of them), its result out.  No logic of their own beyond the copies.
 // ------------------------------------------------------------------------
 extern "C" int catchhip_selftest_scan_u32(catchhip_ctx *ctx, const u32 *in, i64 n, i32 in_place, u32 *out) {
     ARG_CHECK(ctx && n >= 0 && n < ((i64)1 << 32) && (n == 0 || (in && out)));
@@ -317,6 +292,69 @@ extern "C" int catchhip_selftest_sort_pairs(catchhip_ctx *ctx, u64 *keys, u32 *v
     else TRY(chip_radix_sort_pairs_segments(ctx, d_keys, d_keys_alt, d_vals, d_vals_alt, n, nseg, key_bits, first_bit));
     HIP_TRY(hipMemcpyAsync(keys, d_keys.p, sizeof(u64) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(vals, d_vals.p, sizeof(u32) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// every helper of wave.h on one value per thread: out32[k * n + i] = result k of thread i, out64 likewise.  n is a
+// multiple of 256, so every lane of every wavefront is at work.
+#define WT_OUT32 10
+#define WT_OUT64 2
+__global__ void __launch_bounds__(256)
+selftest_wave_kernel(const u32 *__restrict__ in, u32 n, u32 *__restrict__ out32, u64 *__restrict__ out64) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const u32 v = in[i];
+    const u64 v64 = ((u64)(v & 0xffffu) << 32) | v;
+    u32 total;
+    const u32 excl = wave_excl_scan(v, &total);
+    const u32 r[WT_OUT32] = {wave_sum(v), wave_max(v), wave_sum_all(v), wave_max_all(v), wave_incl_scan(v, lane), excl, total,
+                             wave_incl_scan_dpp(v), quad_sum(v), row8_sum(v)};
+#pragma unroll
+    for (int k = 0; k < WT_OUT32; ++k) out32[(size_t)k * n + i] = r[k];
+    out64[i] = wave_max(v64);
+    out64[(size_t)n + i] = wave_incl_scan(v64, lane);
+}
+
+__global__ void __launch_bounds__(256)
+selftest_find_segment_kernel(const u32 *__restrict__ off, u32 n, const u32 *__restrict__ x, u32 nx, u32 *__restrict__ out) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i < nx) out[i] = find_segment(off, n, x[i]);
+}
+
+extern "C" int catchhip_selftest_wave(catchhip_ctx *ctx, const u32 *in, i64 n, u32 *out32, u64 *out64) {
+    ARG_CHECK(ctx && in && out32 && out64 && n > 0 && n % 256 == 0 && n <= ((i64)1 << 24));
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevBuf<u32> d_in, d_out32;
+    DevBuf<u64> d_out64;
+    TRY(d_in.alloc((size_t)n));
+    TRY(d_out32.alloc((size_t)n * WT_OUT32));
+    TRY(d_out64.alloc((size_t)n * WT_OUT64));
+    HIP_TRY(hipMemcpyAsync(d_in.p, in, sizeof(u32) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(selftest_wave_kernel, dim3((unsigned)(n / 256)), dim3(256), 0, ctx->stream, (const u32 *)d_in.p,
+                       (u32)n, d_out32.p, d_out64.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out32, d_out32.p, sizeof(u32) * (size_t)n * WT_OUT32, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out64, d_out64.p, sizeof(u64) * (size_t)n * WT_OUT64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int catchhip_selftest_find_segment(catchhip_ctx *ctx, const u32 *off, i64 n, const u32 *x, i64 nx, u32 *out) {
+    ARG_CHECK(ctx && off && x && out && n >= 1 && n < ((i64)1 << 31) && nx >= 1 && nx < ((i64)1 << 31));
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevBuf<u32> d_off, d_x, d_out;
+    TRY(d_off.alloc((size_t)n + 1));
+    TRY(d_x.alloc((size_t)nx));
+    TRY(d_out.alloc((size_t)nx));
+    HIP_TRY(hipMemcpyAsync(d_off.p, off, sizeof(u32) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_x.p, x, sizeof(u32) * (size_t)nx, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(selftest_find_segment_kernel, dim3((unsigned)div_up(nx, 256)), dim3(256), 0, ctx->stream,
+                       (const u32 *)d_off.p, (u32)n, (const u32 *)d_x.p, (u32)nx, d_out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(u32) * (size_t)nx, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -32,6 +32,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "wave.h"
 
 #define RG_TILE 64
 #define RG_BLOCK 256
@@ -185,7 +186,7 @@ rg_degree_kernel(const unsigned long long *__restrict__ bitmap, u32 n, u32 rowwo
     if (row >= n) return;
     u32 c = 0;
     for (u32 w = lane; w < rowwords; w += 64) c += (u32)__popcll(bitmap[(size_t)row * rowwords + w]);
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    c = wave_sum_all(c);
     if (lane == 0) deg[row] = c;
 }
 
@@ -221,11 +222,7 @@ rg_fill_kernel(const unsigned long long *__restrict__ bitmap, u32 n, u32 rowword
         const u32 w = w0 + lane;
         u64 word = w < rowwords ? bitmap[(size_t)row * rowwords + w] : 0ull;
         const u32 c = (u32)__popcll(word);
-        u32 incl = c;
-        for (int o = 1; o < 64; o <<= 1) {
-            const u32 v = __shfl_up(incl, o);
-            if ((int)lane >= o) incl += v;
-        }
+        const u32 incl = wave_incl_scan(c, (int)lane);
         i64 at = base + (incl - c);
         while (word) {
             const int b = __ffsll((long long)word) - 1;

@@ -122,10 +122,8 @@ scan1_kernel(const u32 *in, u32 *__restrict__ out, u32 n, u32 *__restrict__ tota
             if (i0 == lo) keep[j] = (i0 + j < hi) ? v[j] : 0u;
         }
     }
-    u32 inc = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const u32 t = __shfl_up(inc, d); if ((int)lane >= d) inc += t; }
-    for (int d = 32; d > 0; d >>= 1) { mx = max(mx, __shfl_down(mx, d)); amx = max(amx, __shfl_down(amx, d)); }
+    const u32 inc = wave_incl_scan(sum, (int)lane);
+    wave_max_n(mx, amx);
     if (lane == 63) s_part[wave] = inc;
     if (lane == 0) { s_mx[wave] = mx; s_amx[wave] = amx; }
     __syncthreads();
@@ -181,7 +179,7 @@ scan_tiles_reduce_kernel(const u32 *in, u32 n, const u32 *__restrict__ aux, u32 
             if (aux) amx = max(amx, aux[i]);
         }
     }
-    for (int d = 32; d > 0; d >>= 1) { sum += __shfl_down(sum, d); amx = max(amx, __shfl_down(amx, d)); }
+    wave_sum_max(sum, amx);
     if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = sum; s_amx[threadIdx.x >> 6] = amx; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -205,7 +203,7 @@ scan_tiles_apply_kernel(const u32 *in, u32 *__restrict__ out, u32 n, const u32 *
         if (i < blockIdx.x) before += tsum[i];
         amx = max(amx, tamax[i]);
     }
-    for (int d = 32; d > 0; d >>= 1) { before += __shfl_down(before, d); amx = max(amx, __shfl_down(amx, d)); }
+    wave_sum_max(before, amx);
     if (lane == 0) { s_red[wave] = before; s_red2[wave] = amx; }
     __syncthreads();
     before = 0; amx = 0;
@@ -218,9 +216,7 @@ scan_tiles_apply_kernel(const u32 *in, u32 *__restrict__ out, u32 n, const u32 *
         v[j] = (t0 + j < n) ? in[t0 + j] : 0u;
         sum += v[j];
     }
-    u32 inc = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const u32 t = __shfl_up(inc, d); if ((int)lane >= d) inc += t; }
+    const u32 inc = wave_incl_scan(sum, (int)lane);
     if (lane == 63) s_wsum[wave] = inc;
     __syncthreads();
     u32 woff = 0, tile_total = 0;
@@ -282,6 +278,8 @@ __device__ __forceinline__ void bucket_merge_walk(const u32 *s_es, const u32 *s_
             }
             out += (u32)__popcll(hb);
         }
+        // (wave_sum_max of wave.h, written out here and at the end of the walk: through the helper bucket_merge_big_kernel's
+        // register count moves, 40 -> 39 VGPRs)
         for (int d = 32; d > 0; d >>= 1) { lmax = max(lmax, __shfl_down(lmax, d)); total_len += __shfl_down(total_len, d); }
         if (lane == 0) { mcnt[b] = out; blmax[b] = lmax; if (bsum) bsum[b] = total_len; }
         return;

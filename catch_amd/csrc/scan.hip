@@ -22,22 +22,11 @@
 #include <chrono>
 
 #include "internal.h"
+#include "wave.h"
 
 // ------------------------------------------------------------------------
 // helpers
 // ------------------------------------------------------------------------
-// index s with off[s] <= x < off[s+1]  (off has n+1 entries, off[0] = 0)
-__device__ __forceinline__ u32 find_segment(const u32 *__restrict__ off, u32 n, u32 x) {
-    u32 lo = 0, hi = n;  // answer in [lo, hi)
-    while (hi - lo > 1) {
-        u32 mid = (lo + hi) >> 1;
-        if (off[mid] <= x) lo = mid; else hi = mid;
-    }
-    // skip empty segments: off[lo] <= x and we need x < off[lo+1]
-    while (lo + 1 < n && off[lo + 1] <= x) ++lo;
-    return lo;
-}
-
 struct HitBuf {
     u32 *a;      // probe (unique index)
     u32 *b;      // global start
@@ -139,19 +128,6 @@ __device__ __forceinline__ u32 seed_hash(unsigned long long k) {
 __device__ __forceinline__ u32 seed_hash2(unsigned long long k) {
     k ^= k >> 31; k *= 0x94d049bb133111ebull; k ^= k >> 29;
     return (u32)k;
-}
-
-// exclusive prefix sum over the 64 lanes of a wave; *total = wave sum
-__device__ __forceinline__ u32 wave_excl_scan(u32 v, u32 *total) {
-    const int lane = __lane_id();
-    u32 incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    *total = __shfl(incl, 63);
-    return incl - v;
 }
 
 // 2-plane key of kb bases starting at base offset `o` of a plane pair
@@ -562,14 +538,6 @@ seed_verify_kernel(const u32 *__restrict__ tplanes, i64 nwords, const u32 *__res
 // a time and files the hits with all 64 lanes.  NW <= 7 (the window needs
 // NW + 1 <= 8 words).  (A first version with 8 lanes per seed and the masks
 // computed per seed was issue-bound: 99 -> 65 ms, ~24 instructions per seed.)
-__device__ __forceinline__ u32 dpp_row_shl1(u32 v) {   // lane i <- lane i + 1 (inside a row of 16)
-    return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, true);
-}
-__device__ __forceinline__ u32 quad_sum(u32 v) {       // sum over the 4 lanes of a quad, in every lane
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);    // quad_perm [1,0,3,2]
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);    // quad_perm [2,3,0,1]
-    return v;
-}
 // bits [pos, pos+len) of a (NW x 32)-bit string restricted to word t
 __device__ __forceinline__ u32 word_range_mask(int t, int pos, int len) {
     const int lo = max(pos - 32 * t, 0), hi = min(pos + len - 32 * t, 32);
@@ -714,35 +682,12 @@ seed_verify4_kernel(const uint4 *__restrict__ tq, const u32 *__restrict__ seq_of
 typedef void (*seed_verify_fn)(const u32 *, i64, const u32 *, const uint4 *, const u32 *, const u32 *, const u32 *,
                                int, int, int, int, u32, int, const u32 *, const u32 *, const u32 *, const u32 *, u32,
                                HitSink);
-static seed_verify_fn pick_seed_verify(int nw) {
-    switch (nw) {
-    case 1: return seed_verify_kernel<1>;
-    case 2: return seed_verify_kernel<2>;
-    case 3: return seed_verify_kernel<3>;
-    case 4: return seed_verify_kernel<4>;
-    case 5: return seed_verify_kernel<5>;
-    case 6: return seed_verify_kernel<6>;
-    case 7: return seed_verify_kernel<7>;
-    case 8: return seed_verify_kernel<8>;
-    }
-    return nullptr;
-}
+static seed_verify_fn pick_seed_verify(int nw) { PICK_NW(8, nw, seed_verify_kernel); }
 
 typedef void (*seed_verify4_fn)(const uint4 *, const u32 *, const uint4 *, const u32 *, const u32 *, const u32 *, int, int,
                                 int, int, int, u32, int, const u32 *, const u32 *, const u32 *, const u32 *, u32,
                                 HitSink, const uint2 *);
-static seed_verify4_fn pick_seed_verify4(int nw) {
-    switch (nw) {
-    case 1: return seed_verify4_kernel<1>;
-    case 2: return seed_verify4_kernel<2>;
-    case 3: return seed_verify4_kernel<3>;
-    case 4: return seed_verify4_kernel<4>;
-    case 5: return seed_verify4_kernel<5>;
-    case 6: return seed_verify4_kernel<6>;
-    case 7: return seed_verify4_kernel<7>;
-    }
-    return nullptr;
-}
+static seed_verify4_fn pick_seed_verify4(int nw) { PICK_NW(7, nw, seed_verify4_kernel); }
 
 #include "scan_join.inc"
 
@@ -1087,19 +1032,7 @@ extend_cut_kernel(const u32 *__restrict__ cut, u32 cut_cap, const u8 *__restrict
 typedef void (*extend_planes_fn)(const u32 *, i64, const u8 *, const u32 *, const uint4 *, const u8 *, const u32 *,
                                  const i32 *, const i32 *, int, int, int, int, int, u32, int, const u32 *, const u32 *,
                                  const u32 *, u32, HitBuf, u32 *, u32);
-static extend_planes_fn pick_extend_planes(int nw) {
-    switch (nw) {
-    case 1: return extend_planes_kernel<1>;
-    case 2: return extend_planes_kernel<2>;
-    case 3: return extend_planes_kernel<3>;
-    case 4: return extend_planes_kernel<4>;
-    case 5: return extend_planes_kernel<5>;
-    case 6: return extend_planes_kernel<6>;
-    case 7: return extend_planes_kernel<7>;
-    case 8: return extend_planes_kernel<8>;
-    }
-    return nullptr;
-}
+static extend_planes_fn pick_extend_planes(int nw) { PICK_NW(8, nw, extend_planes_kernel); }
 
 // ------------------------------------------------------------------------
 // rows: extension / clip / sort / merge
@@ -1161,7 +1094,7 @@ rows_compact_kernel(const u64 *__restrict__ keys, const u32 *__restrict__ head,
         len = mend[t] - (u32)keys[t];
     }
     // longest row of the table: one atomic per wavefront
-    for (int d = 32; d > 0; d >>= 1) { u32 o = __shfl_down(len, d, 64); len = o > len ? o : len; }
+    len = wave_max(len);
     if ((threadIdx.x & 63) == 0 && len) atomicMax(lmax, len);
 }
 
@@ -2417,7 +2350,7 @@ rows_union_kernel(const unsigned long long *__restrict__ bm, const u32 *__restri
             c += (u32)__popcll(bm[w] & m);
         }
     }
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, WAVE);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) union_len[u] = (unsigned long long)part[0] + part[1] + part[2] + part[3];
@@ -2552,7 +2485,7 @@ av_tally_kernel(const u64 *__restrict__ hkeys, const u32 *__restrict__ heads, u3
             plain += w * (m1 - base);
             swp += w * (m2 - base);
         }
-        for (int d = 32; d > 0; d >>= 1) { plain += __shfl_down(plain, d, WAVE); swp += __shfl_down(swp, d, WAVE); }
+        wave_sum_n(plain, swp);
         if (lane == 0) { s_plain[wave] = plain; s_swap[wave] = swp; }
         __syncthreads();
         if (tid == 0) {

@@ -410,7 +410,7 @@ __device__ __forceinline__ void kj_lanes(const JoinArgs &A, bool active, u32 idx
         if (A.seq_group) sgrp = A.seq_group[sq];
     }
     u32 maxq = active ? nq : 0u;
-    for (int d = 32; d > 0; d >>= 1) maxq = max(maxq, (u32)__shfl_xor((int)maxq, d));
+    maxq = wave_max_all(maxq);
     for (u32 j = 0; j < maxq; ++j) {
         const bool on = active && j < nq;
         u32 e = 0, p = 0, a = 0;
@@ -488,7 +488,7 @@ kj_verify_kernel(JoinArgs A) {
     if (!WRITE) {   // statistics: pairs verified, and the lane slots the wave-wide runs occupy (64 per chunk and entry)
         unsigned long long pr = (unsigned long long)W * Q;
         unsigned long long sl = (head && !small) ? (unsigned long long)((W + 63u) / 64u) * 64ull * Q : 0ull;
-        for (int d = 32; d > 0; d >>= 1) { pr += __shfl_down(pr, d); sl += __shfl_down(sl, d); }
+        wave_sum_n(pr, sl);
         // (64 shards each: an atomic on ONE address costs ~10 ns however it is issued, and a hit list of 10^8 records is 2 M wavefronts)
         if (lane == 0 && pr) { atomicAdd(&A.pairs[(c64 >> 6) & 63u], pr); if (sl) atomicAdd(&A.pairs[64u + ((c64 >> 6) & 63u)], sl); }
     }
@@ -606,29 +606,5 @@ kj_bases_kernel(const u32 *__restrict__ ecnt, u32 nprobes, int nanch, int ntab, 
 }
 
 typedef void (*kj_kernel_fn)(JoinArgs);
-template <bool WRITE> static kj_kernel_fn pick_kj_verify(int nw) {
-    switch (nw) {
-    case 1: return kj_verify_kernel<1, WRITE>;
-    case 2: return kj_verify_kernel<2, WRITE>;
-    case 3: return kj_verify_kernel<3, WRITE>;
-    case 4: return kj_verify_kernel<4, WRITE>;
-    case 5: return kj_verify_kernel<5, WRITE>;
-    case 6: return kj_verify_kernel<6, WRITE>;
-    case 7: return kj_verify_kernel<7, WRITE>;
-    case 8: return kj_verify_kernel<8, WRITE>;
-    }
-    return nullptr;
-}
-template <bool WRITE> static kj_kernel_fn pick_kj_giant(int nw) {
-    switch (nw) {
-    case 1: return kj_giant_kernel<1, WRITE>;
-    case 2: return kj_giant_kernel<2, WRITE>;
-    case 3: return kj_giant_kernel<3, WRITE>;
-    case 4: return kj_giant_kernel<4, WRITE>;
-    case 5: return kj_giant_kernel<5, WRITE>;
-    case 6: return kj_giant_kernel<6, WRITE>;
-    case 7: return kj_giant_kernel<7, WRITE>;
-    case 8: return kj_giant_kernel<8, WRITE>;
-    }
-    return nullptr;
-}
+template <bool WRITE> static kj_kernel_fn pick_kj_verify(int nw) { PICK_NW(8, nw, kj_verify_kernel, WRITE); }
+template <bool WRITE> static kj_kernel_fn pick_kj_giant(int nw) { PICK_NW(8, nw, kj_giant_kernel, WRITE); }

@@ -38,6 +38,7 @@
 #include <string>
 
 #include "internal.h"
+#include "wave.h"
 
 struct GreedyState {
     unsigned long long best_key;
@@ -202,7 +203,7 @@ universe_size_kernel(const u64 *__restrict__ bm, const u32 *__restrict__ genome_
             c += (u32)__popcll(bm[w] & m);
         }
     }
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, WAVE);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) usize[u] = part[0] + part[1] + part[2] + part[3];
@@ -256,7 +257,7 @@ seg_init_kernel(const u32 *__restrict__ segcnt, const u32 *__restrict__ seg_univ
     }
     // largest segment count (bounds when min(left, count) can bind): one
     // atomic per wavefront instead of one contended atomic per segment
-    for (int d = 32; d > 0; d >>= 1) { u32 o = __shfl_down(c, d, WAVE); c = o > c ? o : c; }
+    c = wave_max(c);
     if ((threadIdx.x & 63) == 0 && c) atomicMax(&st->smax, c);
 }
 
@@ -356,15 +357,6 @@ struct GreedyArgs {
 #define GW_CAND 4          // candidate rows fetched per lane per step
 #define BUCKET_SHIFT 5
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        unsigned long long o = __shfl_down(v, d, WAVE);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // contribution min(left, count) of segment q changed? patch the set's gain.
 __device__ __forceinline__ void patch_segment(const GreedyArgs &a, u32 q, u32 *s_cdirty) {
     const u32 ss = a.seg_set[q];
@@ -435,13 +427,13 @@ greedy_wg_kernel(GreedyArgs a) {
             ckey = k;
         }
         {
-            unsigned long long k = wave_max_u64(ckey);
+            unsigned long long k = wave_max(ckey);
             if (lane == 0) s_red[wave] = k;
         }
         __syncthreads();
         // every wave folds the 16 partial maxima itself: no second barrier and no
         // global access between the scan and the apply phase
-        unsigned long long key = wave_max_u64(lane < GW_WAVES ? s_red[lane] : 0ull);
+        unsigned long long key = wave_max(lane < GW_WAVES ? s_red[lane] : 0ull);
         key = __shfl(key, 0, WAVE);
         if ((key >> ID_BITS) == 0) {
             // no set of this rank covers anything still needed: next rank

@@ -79,13 +79,6 @@ struct FrontArgs {
 };
 #define GF_LIST_TILE 4096   // sets per workgroup step of the list build: one cursor atomic each
 
-template <int G>
-__device__ __forceinline__ u32 group_sum(u32 v) {
-#pragma unroll
-    for (int d = 1; d < G; d <<= 1) v += __shfl_xor(v, d, WAVE);
-    return v;
-}
-
 // No same-address atomics in the round kernels: ~10 ns each on MI355X, a
 // per-wavefront counter update alone cost 75 us per launch.  Dead sets are
 // skipped by their stored gain instead of being compacted away, the "some set
@@ -180,7 +173,7 @@ gf_count_claim_kernel(FrontArgs a, u32 round) {
         if (lost) a.lost[s] = round + 1;
         if (sub == 0) a.claimed[s] = round + 1;
     }
-    for (int d = 32; d > 0; d >>= 1) { cnt_rows += __shfl_down(cnt_rows, d, WAVE); cnt_words += __shfl_down(cnt_words, d, WAVE); }
+    wave_sum_n(cnt_rows, cnt_words);
     if ((threadIdx.x & 63) == 0) { atomicAdd(&s_rows, cnt_rows); atomicAdd(&s_words, cnt_words); }
     if (any_claim && sub == 0) s_claim = 1;
     __syncthreads();
@@ -228,10 +221,8 @@ gf_check_apply_kernel(FrontArgs a, u32 round) {
                 mask |= lv ? (1u << q) : 0u;
                 mine += lv ? 1u : 0u;
             }
-            u32 inc = mine;
             const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const u32 t = __shfl_up(inc, d, WAVE); if ((int)lane >= d) inc += t; }
+            const u32 inc = wave_incl_scan(mine, (int)lane);
             __syncthreads();
             if (lane == 63) s_cnt[wave] = inc;
             __syncthreads();
@@ -309,12 +300,6 @@ gf_check_apply_kernel(FrontArgs a, u32 round) {
 // skipped by their stored gain instead of being compacted away, the "some set
 // of this rank claimed" signal is a plain store, work counters are per
 // workgroup.
-__device__ __forceinline__ u32 row8_sum(u32 v) {   // sum over the 8 lanes of a row, in every lane
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);    // quad_perm [1,0,3,2]
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);    // quad_perm [2,3,0,1]
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true);   // row_half_mirror
-    return v;
-}
 // mask of the bits of [x, e) inside bitmap word w0 + t
 __device__ __forceinline__ u64 row_word_mask(u32 x, u32 e, u32 t, u32 nwd) {
     u64 m = ~0ull;
@@ -445,7 +430,7 @@ gfl_count_claim_kernel(FrontArgs a, u32 round) {
         }
         if (lig == 0) a.claimed[s] = round + 1;
     }
-    for (int d = 32; d > 0; d >>= 1) { cnt_rows += __shfl_down(cnt_rows, d, WAVE); cnt_words += __shfl_down(cnt_words, d, WAVE); }
+    wave_sum_n(cnt_rows, cnt_words);
     if ((threadIdx.x & 63) == 0) { atomicAdd(&s_rows, cnt_rows); atomicAdd(&s_words, cnt_words); }
     if (any_claim && lig == 0) s_claim = 1;
     __syncthreads();
@@ -496,10 +481,8 @@ gfl_check_apply_kernel(FrontArgs a, u32 round) {
                 mask |= lv ? (1u << q) : 0u;
                 mine += lv ? 1u : 0u;
             }
-            u32 inc = mine;
             const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const u32 t = __shfl_up(inc, d, WAVE); if ((int)lane >= d) inc += t; }
+            const u32 inc = wave_incl_scan(mine, (int)lane);
             __syncthreads();
             if (lane == 63) s_cnt[wave] = inc;
             __syncthreads();
@@ -652,7 +635,7 @@ gf_universe_kernel(const unsigned long long *bm, const u32 *__restrict__ genome_
             c += (u32)__popcll(bm[w] & m);
         }
     }
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, WAVE);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -149,32 +149,6 @@ struct GrRowSrc {
     u32 n;                          // rows (SoA) / slots (direct)
 };
 
-// inclusive sum over the 64 lanes by DPP moves (no LDS permutes): Kogge-Stone inside the 16-lane rows (row_shr 1, 2, 4, 8,
-// zero fill), then lane 15 of rows 0 / 2 added to rows 1 / 3 (row_bcast:15) and lane 31 to rows 2 and 3 (row_bcast:31)
-__device__ __forceinline__ u32 wave_incl_scan_dpp(u32 v) {
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return v;
-}
-
-// inclusive sum over runs of equal keys in adjacent lanes; *tail = this lane ends its run.  Round 6: the wave's plain
-// prefix sum by DPP moves minus its value just before the run's first lane -- one LDS permute instead of six (the six-step
-// segmented scan through ds_bpermute was ~30 of the count launch's 190 VALU instructions per 64 rows).
-__device__ __forceinline__ u32 wave_segsum(u32 v, u32 key, bool *tail) {
-    const u32 lane = threadIdx.x & 63;
-    const u32 kprev = (u32)__builtin_amdgcn_update_dpp((int)key, (int)key, 0x138, 0xf, 0xf, false);   // wave_shr:1 (lane 0: its own key, unused)
-    const unsigned long long heads = __ballot(lane == 0 || kprev != key);
-    // first lane of this lane's run: highest head at or below it
-    const u32 start = 63u - (u32)__clzll(heads & (~0ull >> (63 - lane)));
-    *tail = lane == 63 || ((heads >> (lane + 1)) & 1ull);
-    const u32 incl = wave_incl_scan_dpp(v);
-    return incl - (u32)__shfl((int)(incl - v), (int)start, WAVE);      // minus the sum of the lanes before the run
-}
-
 // row r of the set-ordered table, in either form (the branch is uniform over the launch)
 __device__ __forceinline__ void gr_row_range(const FlatArgs &a, u32 r, u32 &x, u32 &e) {
     if (a.rows4) { const uint2 q = *(const uint2 *)(a.rows4 + r); x = q.x; e = q.y; }
@@ -387,12 +361,7 @@ gr_count_kernel(FlatArgs a, u32 round) {
             o += (u32)__popcll(alive[u]);
         }
     });
-    for (int d = 32; d > 0; d >>= 1) {
-        cnt_rows += __shfl_down(cnt_rows, d, WAVE);
-        cnt_dirty += __shfl_down(cnt_dirty, d, WAVE);
-        cnt_words += __shfl_down(cnt_words, d, WAVE);
-        cnt_own += __shfl_down(cnt_own, d, WAVE);
-    }
+    wave_sum_n(cnt_rows, cnt_dirty, cnt_words, cnt_own);
     if (lane == 0) {
         atomicAdd(&s_rows[0], (unsigned long long)cnt_rows);
         atomicAdd(&s_rows[1], (unsigned long long)cnt_dirty);
@@ -527,7 +496,7 @@ gr_claim_kernel(FlatArgs a, u32 round) {
     });
     if (any) s_claim = 1;
     if (count_here) {
-        for (int d = 32; d > 0; d >>= 1) { c_rows += __shfl_down(c_rows, d, WAVE); c_own += __shfl_down(c_own, d, WAVE); }
+        wave_sum_n(c_rows, c_own);
         if ((threadIdx.x & 63) == 0) { atomicAdd(&s_cnt[0], (unsigned long long)c_rows); atomicAdd(&s_cnt[1], (unsigned long long)c_own); }
     }
     __syncthreads();
@@ -872,7 +841,7 @@ gr_seg_flag_kernel(GrRowSrc src, u32 *__restrict__ cflag, GreedyState *__restric
             best = tot > best ? tot : best;
         }
     }
-    for (int d = 32; d > 0; d >>= 1) { const u32 o = __shfl_down(best, d, WAVE); best = o > best ? o : best; }
+    best = wave_max(best);
     if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = best;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -919,7 +888,7 @@ gr_fixup_kernel(FlatArgs a, u32 round) {
             const i32 nd = a.need[u];
             if (nd > 0) tot += c < (u32)nd ? c : (u32)nd;
         }
-        for (int d = 32; d > 0; d >>= 1) tot += __shfl_down(tot, d, WAVE);
+        tot = wave_sum(tot);
         if (lane == 0) acc[s] = a.picked[s] ? 0u : tot;
     }
 }
@@ -995,7 +964,7 @@ gr_usel_kernel(FlatArgs a, u32 round) {
         __syncthreads();
     }
     if (tid == 0) a.uT[u] = x0 < 0 ? ~0ull : (stop ? 0ull : s_prefix);
-    mx = wave_max_u64(mx);
+    mx = wave_max(mx);
     if ((tid & 63) == 0) s_max[tid >> 6] = mx;
     __syncthreads();
     if (tid == 0) {

@@ -303,6 +303,31 @@ class Context:
                                                    int(key_bits), int(first_bit)))
         return k, v
 
+    WAVE_RESULTS_32 = ("wave_sum", "wave_max", "wave_sum_all", "wave_max_all", "wave_incl_scan", "wave_excl_scan",
+                       "wave_excl_scan_total", "wave_incl_scan_dpp", "quad_sum", "row8_sum")
+    WAVE_RESULTS_64 = ("wave_max_u64", "wave_incl_scan_u64")
+
+    def selftest_wave(self, values):
+        """catchhip_selftest_wave: what every helper of csrc/wave.h returned to every thread, by name; one uint32
+        value per thread, a multiple of 256 of them."""
+        x = np.ascontiguousarray(values, dtype=np.uint32)
+        o32 = np.zeros((len(self.WAVE_RESULTS_32), x.size), dtype=np.uint32)
+        o64 = np.zeros((len(self.WAVE_RESULTS_64), x.size), dtype=np.uint64)
+        check(self._L.catchhip_selftest_wave(self._h, _ptr(x, c_u32p), int(x.size), _ptr(o32, c_u32p),
+                                             _ptr(o64, c_u64p)))
+        out = dict(zip(self.WAVE_RESULTS_32, o32))
+        out.update(zip(self.WAVE_RESULTS_64, o64))
+        return out
+
+    def selftest_find_segment(self, off, x):
+        """catchhip_selftest_find_segment: the device's find_segment(off, len(off) - 1, x[j]) for every j."""
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        x = np.ascontiguousarray(x, dtype=np.uint32)
+        out = np.zeros(max(x.size, 1), dtype=np.uint32)
+        check(self._L.catchhip_selftest_find_segment(self._h, _ptr(off, c_u32p), int(off.size) - 1, _ptr(x, c_u32p),
+                                                     int(x.size), _ptr(out, c_u32p)))
+        return out[:x.size]
+
     # -- near-duplicate filter --------------------------------------------
     def ndf_hamming(self, probe_strs, L, positions, dist_thres):
         n = len(probe_strs)

@@ -422,6 +422,19 @@ int catchhip_selftest_scan_u32(catchhip_ctx *ctx, const uint32_t *in, int64_t n,
 int catchhip_selftest_sort_pairs(catchhip_ctx *ctx, uint64_t *keys, uint32_t *vals,
                                  int64_t n, int64_t nseg, int32_t key_bits,
                                  int32_t first_bit);
+/* Test entry points of the wavefront-level helpers the kernels share (csrc/wave.h).
+ * _wave: n words (a multiple of 256, at most 2^24), one 256-thread workgroup per 256,
+ * one word per thread.  out32 holds 10 arrays of n words, [k * n + i] = what helper k
+ * returned to thread i: 0 wave_sum, 1 wave_max, 2 wave_sum_all, 3 wave_max_all,
+ * 4 wave_incl_scan, 5 wave_excl_scan, 6 its total, 7 wave_incl_scan_dpp, 8 quad_sum,
+ * 9 row8_sum.  out64 holds 2 arrays of n: 0 wave_max, 1 wave_incl_scan of the 64-bit
+ * value ((in[i] & 0xffff) << 32) | in[i].
+ * _find_segment: out[j] = find_segment(off, n, x[j]) for nx values; off has n + 1
+ * entries, off[0] = 0, non-decreasing; x[j] < off[n] is the caller's business. */
+int catchhip_selftest_wave(catchhip_ctx *ctx, const uint32_t *in, int64_t n,
+                           uint32_t *out32, uint64_t *out64);
+int catchhip_selftest_find_segment(catchhip_ctx *ctx, const uint32_t *off, int64_t n,
+                                   const uint32_t *x, int64_t nx, uint32_t *out);
 /* Which RCCL the communicators of this library go through: "RCCL version code V
  * from <file> (<how it was chosen>)".  The library opens ONE copy by path
  * (CATCHHIP_RCCL_PATH, else /opt/rocm/lib/librccl.so) instead of whatever file of

@@ -13,6 +13,10 @@ np.cumsum in 64 bits masked to 32, the sort against np.argsort(kind="stable") of
 Not covered here: the third scan level inside ONE sort (a histogram of more than 2048^2 counters: about 67 M keys; the
 65,535 two-key segments of the refusal test do scan 16.8 M counters, but one tile per segment) and the n * nseg
 arithmetic of the segmented sort near 2^32.  The full-size digests of bench.py remain the check for both.
+
+The wavefront-level helpers of csrc/wave.h (reductions, scans, DPP sums, find_segment) are below the two, through
+catchhip_selftest_wave and catchhip_selftest_find_segment: one kernel that calls every helper on one value per thread
+and hands back what every thread got.
 """
 import os
 import re
@@ -86,11 +90,13 @@ def test_selftest_symbols_declared_bound_and_wrapped():
     from catch_amd import _lib, engine
     hdr = open(os.path.join(REPO, "include", "catchhip.h")).read()
     src = open(os.path.join(REPO, "catch_amd", "csrc", "primitives.hip")).read()
-    for name in ("catchhip_selftest_scan_u32", "catchhip_selftest_sort_pairs"):
+    for name in ("catchhip_selftest_scan_u32", "catchhip_selftest_sort_pairs", "catchhip_selftest_wave",
+                 "catchhip_selftest_find_segment"):
         assert re.search(r"\b%s\s*\(" % name, hdr), name
         assert re.search(r'extern "C" int %s\s*\(' % name, src), name
         assert name in _lib.PROTOTYPES, name
     assert callable(engine.Context.selftest_scan_u32) and callable(engine.Context.selftest_sort_pairs)
+    assert callable(engine.Context.selftest_wave) and callable(engine.Context.selftest_find_segment)
     # the structural sizes this file is written around
     assert re.search(r"#define SCAN_THREADS 256\b", src) and re.search(r"#define SCAN_ITEMS 8\b", src)
     assert re.search(r"#define RS_THREADS 256\b", src) and re.search(r"#define RS_ROUNDS 16\b", src)
@@ -266,3 +272,121 @@ def test_segmented_sort_refuses_65536_segments(ctx):
     got_k, got_v = ctx.selftest_sort_pairs(keys, np.arange(keys.size, dtype=np.uint32), 32, 0, nseg=65535)
     assert np.array_equal(got_k, keys.reshape(-1, 2)[:, ::-1].reshape(-1))
     assert np.array_equal(got_v, np.arange(keys.size).reshape(-1, 2)[:, ::-1].reshape(-1))
+
+
+# ------------------------------------------------------------------ wave.h
+WAVE_PATTERNS = ("zeros", "all_ones", "ramp", "lane0", "lane63", "lane15", "lane16", "lanes15_16", "lane31", "lane32",
+                 "lanes31_32", "random")
+WAVE_SIZES = (256, 512)     # one workgroup of four wavefronts, and two
+
+
+def _wave_input(pattern, n):
+    """One value per thread.  The single-lane patterns put a value that differs from wavefront to wavefront (and has
+    its top bit set: two of them wrap) into the named lanes of every wavefront: lane 0 and lane 63 are the ends of the
+    shuffles, 15|16 and 31|32 the borders of the DPP rows and of the row broadcasts."""
+    x = np.zeros(n, dtype=np.uint32)
+    lanes = {"lane0": (0,), "lane63": (63,), "lane15": (15,), "lane16": (16,), "lanes15_16": (15, 16), "lane31": (31,),
+             "lane32": (32,), "lanes31_32": (31, 32)}
+    if pattern == "zeros":
+        pass
+    elif pattern == "all_ones":
+        x[:] = 0xffffffff
+    elif pattern == "ramp":
+        x[:] = np.arange(n, dtype=np.uint32) * np.uint32(3) + np.uint32(1)
+    elif pattern == "random":
+        x[:] = np.random.default_rng(n).integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
+    else:
+        for lane in lanes[pattern]:
+            x[lane::64] = np.uint32(0x80000001) + np.arange(n // 64, dtype=np.uint32) * np.uint32(0x01010101) + np.uint32(lane)
+    return x
+
+
+def _wave_expected(x):
+    """NumPy's answers, per thread; None where a helper promises nothing (every lane but 0 of a lane-0 form)."""
+    m32 = np.uint64(0xffffffff)
+    w = x.reshape(-1, 64).astype(np.uint64)
+    inc = np.cumsum(w, axis=1) & m32
+    tot = (w.sum(axis=1) & m32)[:, None]
+    ones = np.ones_like(w)
+    w64 = ((w & np.uint64(0xffff)) << np.uint64(32)) | w
+    exp = {
+        "wave_sum": tot[:, 0], "wave_max": w.max(axis=1),                    # lane 0 of every wavefront only
+        "wave_sum_all": tot * ones, "wave_max_all": w.max(axis=1)[:, None] * ones,
+        "wave_incl_scan": inc, "wave_excl_scan": (inc - w) & m32, "wave_excl_scan_total": tot * ones,
+        "wave_incl_scan_dpp": inc,
+        "quad_sum": np.repeat(x.reshape(-1, 4).astype(np.uint64).sum(axis=1) & m32, 4),
+        "row8_sum": np.repeat(x.reshape(-1, 8).astype(np.uint64).sum(axis=1) & m32, 8),
+        "wave_max_u64": w64.max(axis=1),                                       # lane 0 only
+        "wave_incl_scan_u64": np.cumsum(w64, axis=1),
+    }
+    return {k: v.reshape(-1) for k, v in exp.items()}
+
+
+LANE0_FORMS = ("wave_sum", "wave_max", "wave_max_u64")
+
+
+def test_wave_references_on_a_case_written_down():
+    x = np.zeros(256, dtype=np.uint32)
+    x[0], x[1], x[63], x[64] = 0xffffffff, 2, 5, 7
+    e = _wave_expected(x)
+    assert e["wave_sum"].tolist() == [6, 7, 0, 0] and e["wave_max"].tolist() == [0xffffffff, 7, 0, 0]
+    assert e["wave_incl_scan"][:3].tolist() == [0xffffffff, 1, 1] and int(e["wave_incl_scan"][63]) == 6
+    assert e["wave_excl_scan"][:3].tolist() == [0, 0xffffffff, 1] and set(e["wave_excl_scan_total"][:64].tolist()) == {6}
+    assert e["quad_sum"][:5].tolist() == [1, 1, 1, 1, 0] and e["row8_sum"][56:65].tolist() == [5] * 8 + [7]
+    assert int(e["wave_max_u64"][0]) == (0xffff << 32) | 0xffffffff and int(e["wave_incl_scan_u64"][1]) == (0xffff << 32) + 0xffffffff + (2 << 32) + 2
+    for pattern in WAVE_PATTERNS:
+        for n in WAVE_SIZES:
+            v = _wave_input(pattern, n)
+            assert v.size == n and (pattern == "zeros") == (not v.any())
+    assert np.count_nonzero(_wave_input("lanes15_16", 256)) == 8 and np.count_nonzero(_wave_input("lane63", 512)) == 8
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pattern", WAVE_PATTERNS)
+def test_wave_helpers_equal_numpy(ctx, pattern):
+    """Lane-0 forms are asserted in lane 0 of each wavefront, everything else in every lane."""
+    for n in WAVE_SIZES:
+        x = _wave_input(pattern, n)
+        got, want = ctx.selftest_wave(x), _wave_expected(x)
+        assert set(got) == set(want)
+        for name in got:
+            g = got[name][::64] if name in LANE0_FORMS else got[name]
+            assert g.shape == want[name].shape, (pattern, n, name)
+            bad = np.nonzero(g.astype(np.uint64) != want[name])[0]
+            assert bad.size == 0, (pattern, n, name, bad[:5].tolist(), g[bad[:5]].tolist(), want[name][bad[:5]].tolist())
+
+
+def _segment_tables():
+    rng = np.random.default_rng(300)
+    lens300 = rng.integers(0, 40, size=300)
+    lens300[rng.integers(0, 300, size=60)] = 0
+    tables = {
+        "n1": [5], "n2": [3, 4], "n300": lens300,
+        "empty_front": [0, 0, 0, 4, 5], "empty_middle": [3, 0, 2, 0, 0, 0, 0, 6, 0, 0, 1, 9], "empty_end": [4, 5, 0, 0, 0],
+    }
+    return {k: np.concatenate(([0], np.cumsum(v))).astype(np.uint32) for k, v in tables.items()}
+
+
+def test_segment_tables_are_what_they_claim():
+    t = _segment_tables()
+    assert t["n1"].tolist() == [0, 5] and t["n2"].tolist() == [0, 3, 7] and t["n300"].size == 301
+    assert t["empty_front"][:4].tolist() == [0, 0, 0, 0] and t["empty_end"][-4:].tolist() == [9, 9, 9, 9]
+    d = np.diff(t["empty_middle"].astype(np.int64))
+    assert d[0] > 0 and d[-1] > 0 and (d[3:7] == 0).all()
+    d = np.diff(t["n300"].astype(np.int64))
+    assert (d == 0).sum() >= 40 and ((d[1:] == 0) & (d[:-1] == 0)).any() and all(int(v[-1]) > 0 for v in t.values())
+    # the reference on a table small enough to write down: off = [0, 0, 0, 0, 4, 9]
+    assert np.searchsorted(t["empty_front"][1:], np.arange(9), side="right").tolist() == [3] * 4 + [4] * 5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("table", ["n1", "n2", "n300", "empty_front", "empty_middle", "empty_end"])
+def test_find_segment_equals_searchsorted(ctx, table):
+    off = _segment_tables()[table]
+    n = off.size - 1
+    x = np.arange(int(off[n]), dtype=np.uint32)           # every x of the contract: [0, off[n])
+    got = ctx.selftest_find_segment(off, x)
+    want = np.searchsorted(off[1:n + 1], x, side="right")
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, (table, bad[:5].tolist(), got[bad[:5]].tolist(), want[bad[:5]].tolist())
+    assert (off[got] <= x).all() and (x < off[got + 1]).all()
