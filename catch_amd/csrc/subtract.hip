@@ -1,0 +1,283 @@
+// Rows minus the bases another table covers (catchhip_rows_subtract): the reduced set cover instance behind
+// SetCoverFilter(fixed_probes=...).
+//
+// The reference's greedy loop (catch/utils/set_cover.py:362-550) has no notion of sets picked beforehand; picking
+// them first is the same as removing their elements from every universe and every other set before the first
+// round.  Here that state is a row table: every row [s, t) of `rows` is cut into its maximal runs of bases that no
+// row of `covered` touches.  Pieces of one row are at least one covered base apart and stay inside their row, so the
+// output keeps the order and the normal form (disjoint, non-touching inside a (set, universe)) of the input and goes
+// to catchhip_setcover_greedy as it is.
+//
+// covered -> bitmap (one bit per base) -> pieces per row (word-parallel) -> exclusive scan -> emit.
+#include <algorithm>
+
+#include "internal.h"
+#include "wave.h"
+
+#define SUB_MAXW 5   // rows of at most 5 words (<= 257 bases) load all their words before the first use (RP_MAXW of setcover.hip)
+
+// bit b of bm = base b lies in some row of `covered` (rows of several sets overlap: most words are complete already)
+__global__ void __launch_bounds__(256)
+sub_bitmap_kernel(const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n, unsigned long long *__restrict__ bm) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const u32 s = gs[r], e = ge[r];
+    if (e <= s) return;
+    const u32 w0 = s >> 6, w1 = (e - 1) >> 6;
+    for (u32 w = w0; w <= w1; ++w) {
+        u64 m = ~0ull;
+        if (w == w0) m &= ~0ull << (s & 63);
+        if (w == w1) m &= ~0ull >> (63 - ((e - 1) & 63));
+        if ((bm[w] & m) != m) atomicOr(&bm[w], m);
+    }
+}
+
+// the uncovered bases of word j (of nw) of a row: v = the bitmap word, m0 / m1 = the masks of the row's two ends
+__device__ __forceinline__ u64 sub_free(u64 v, u32 j, u32 nw, u64 m0, u64 m1) {
+    u64 m = ~0ull;
+    if (j == 0) m &= m0;
+    if (j == nw - 1) m &= m1;
+    return ~v & m;
+}
+// pieces that START in a word: an uncovered base whose predecessor is covered or lies before the row
+// (prev = the word before, 0 for the first)
+__device__ __forceinline__ u32 sub_starts(u64 f, u64 prev) { return (u32)__popcll(f & ~((f << 1) | (prev >> 63))); }
+
+// cnt[r] = pieces of row r; info[0] += their number
+__global__ void __launch_bounds__(256)
+sub_count_kernel(const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n,
+                 const unsigned long long *__restrict__ bm, u32 *__restrict__ cnt,
+                 unsigned long long *__restrict__ info) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    u32 c = 0;
+    if (r < n) {
+        const u32 s = gs[r], e = ge[r];
+        if (e > s) {
+            const u32 w0 = s >> 6, nw = ((e - 1) >> 6) - w0 + 1;
+            const u64 m0 = ~0ull << (s & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
+            u64 prev = 0;
+            if (nw <= SUB_MAXW) {
+                u64 v[SUB_MAXW];
+#pragma unroll
+                for (u32 j = 0; j < SUB_MAXW; ++j) v[j] = (j < nw) ? bm[w0 + j] : ~0ull;
+#pragma unroll
+                for (u32 j = 0; j < SUB_MAXW; ++j) {
+                    const u64 f = (j < nw) ? sub_free(v[j], j, nw, m0, m1) : 0ull;
+                    c += sub_starts(f, prev);
+                    prev = f;
+                }
+            } else {
+                for (u32 j = 0; j < nw; ++j) {
+                    const u64 f = sub_free(bm[w0 + j], j, nw, m0, m1);
+                    c += sub_starts(f, prev);
+                    prev = f;
+                }
+            }
+        }
+        cnt[r] = c;
+    }
+    const unsigned long long t = wave_sum((unsigned long long)c);
+    if ((threadIdx.x & 63u) == 0 && t) atomicAdd(&info[0], t);
+}
+
+// One row's walk over its words, lowest first: word() takes the uncovered bases of a word and the base of its bit 0,
+// finish() closes a piece that runs to the row's end.
+struct SubWalk {
+    i32 *o_set, *o_univ;
+    u32 *o_gs, *o_ge;
+    u32 o, cap;          // next output row, rows allocated
+    i32 sid, un;
+    u32 start;           // first base of the open piece
+    bool open;
+    u32 sum, longest;    // of the pieces written so far
+    __device__ __forceinline__ void put(u32 a, u32 b) {
+        if (o < cap) { o_set[o] = sid; o_univ[o] = un; o_gs[o] = a; o_ge[o] = b; }
+        ++o;
+        sum += b - a;
+        longest = max(longest, b - a);
+    }
+    __device__ __forceinline__ void word(u64 f, u32 base) {
+        if (open) {
+            if (f == ~0ull) return;
+            const u32 t = (u32)__builtin_ctzll(~f);
+            put(start, base + t);
+            open = false;
+            f &= ~0ull << t;
+        }
+        while (f) {
+            const u32 b = (u32)__builtin_ctzll(f);
+            const u64 x = ~(f >> b);                             // (the b bits shifted in end the run at the word's end)
+            const u32 len = x ? (u32)__builtin_ctzll(x) : 64u;
+            if (b + len >= 64u) { open = true; start = base + b; return; }
+            put(base + b, base + b + len);
+            f &= ~0ull << (b + len);
+        }
+    }
+    __device__ __forceinline__ void finish(u32 e) {
+        if (open) put(start, e);
+        open = false;
+    }
+};
+
+// the pieces of row r to rows pos[r] .. of the output; their lengths into gain0[set] (the first round's gains of a
+// full-coverage solve) and the longest piece into info[1]
+__global__ void __launch_bounds__(256)
+sub_emit_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__ univ, const u32 *__restrict__ gs,
+                const u32 *__restrict__ ge, u32 n, const unsigned long long *__restrict__ bm,
+                const u32 *__restrict__ pos, u32 cap, i32 *__restrict__ o_set, i32 *__restrict__ o_univ,
+                u32 *__restrict__ o_gs, u32 *__restrict__ o_ge, u32 *__restrict__ gain0, u32 ng,
+                unsigned long long *__restrict__ info) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    u32 longest = 0;
+    if (r < n) {
+        const u32 s = gs[r], e = ge[r];
+        SubWalk w;
+        w.o_set = o_set; w.o_univ = o_univ; w.o_gs = o_gs; w.o_ge = o_ge;
+        w.o = pos[r]; w.cap = cap;
+        w.sid = set_id[r]; w.un = univ[r];
+        w.start = 0; w.open = false; w.sum = 0; w.longest = 0;
+        if (e > s) {
+            const u32 w0 = s >> 6, nw = ((e - 1) >> 6) - w0 + 1;
+            const u64 m0 = ~0ull << (s & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
+            if (nw <= SUB_MAXW) {
+                u64 v[SUB_MAXW];
+#pragma unroll
+                for (u32 j = 0; j < SUB_MAXW; ++j) v[j] = (j < nw) ? bm[w0 + j] : ~0ull;
+#pragma unroll
+                for (u32 j = 0; j < SUB_MAXW; ++j)
+                    if (j < nw) w.word(sub_free(v[j], j, nw, m0, m1), (w0 + j) << 6);
+            } else {
+                for (u32 j = 0; j < nw; ++j) w.word(sub_free(bm[w0 + j], j, nw, m0, m1), (w0 + j) << 6);
+            }
+            w.finish(e);
+        }
+        if (gain0 && w.sum && (u32)w.sid < ng) atomicAdd(&gain0[(u32)w.sid], w.sum);
+        longest = w.longest;
+    }
+    longest = wave_max(longest);
+    if ((threadIdx.x & 63u) == 0 && longest) atomicMax(&info[1], (unsigned long long)longest);
+}
+
+static int sub_check_table(const catchhip_rows *R, const char *which) {
+    if (R->deferred) {
+        chip_set_error("rows_subtract: %s are deferred rows (a fused scan that was never synchronised)", which);
+        return CATCHHIP_EINVAL;
+    }
+    if (R->rows4.p) {
+        chip_set_error("rows_subtract: %s are in the direct form of the fused filter, not a row table", which);
+        return CATCHHIP_EINVAL;
+    }
+    if (R->grouped) {
+        chip_set_error("rows_subtract: %s come from a scan with group numbers (a union of instances), which is not supported", which);
+        return CATCHHIP_EINVAL;
+    }
+    return 0;
+}
+
+// a copy of R0 (nothing is covered)
+static int sub_copy(catchhip_ctx *ctx, const catchhip_rows *R0, catchhip_rows *R) {
+    const size_t n = (size_t)R0->n;
+    hipStream_t s = ctx->stream;
+    TRY(chip_rows_alloc_soa(R, n));
+    HIP_TRY(hipMemcpyAsync(R->set_id.p, R0->set_id.p, sizeof(i32) * n, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(R->univ.p, R0->univ.p, sizeof(i32) * n, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(R->gs.p, R0->gs.p, sizeof(u32) * n, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(R->ge.p, R0->ge.p, sizeof(u32) * n, hipMemcpyDeviceToDevice, s));
+    if (R0->gain0_n) {
+        TRY(R->gain0.alloc(R0->gain0_n));
+        HIP_TRY(hipMemcpyAsync(R->gain0.p, R0->gain0.p, sizeof(u32) * (size_t)R0->gain0_n, hipMemcpyDeviceToDevice, s));
+        R->gain0_n = R0->gain0_n;
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    R->n = R0->n;
+    R->lmax = R0->lmax;
+    return 0;
+}
+
+extern "C" int catchhip_rows_subtract(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_rows *C,
+                                      catchhip_rows **out, i64 *nrows) {
+    ARG_CHECK(ctx && R0 && C && out);
+    ARG_CHECK(R0->ctx == ctx && C->ctx == ctx);
+    *out = nullptr;
+    if (nrows) *nrows = 0;
+    TRY(sub_check_table(R0, "the rows"));
+    TRY(sub_check_table(C, "the covered rows"));
+    if (R0->total != C->total || R0->ngenomes != C->ngenomes || R0->h_genome_off != C->h_genome_off) {
+        chip_set_error("rows_subtract: the covered rows are not over the coordinate space of the rows "
+                       "(%lld bases in %d universes against %lld in %d)",
+                       (long long)C->total, (int)C->ngenomes, (long long)R0->total, (int)R0->ngenomes);
+        return CATCHHIP_EINVAL;
+    }
+    if (R0->total >= ((i64)1 << 32) - 1) {
+        chip_set_error("rows_subtract: more than 2^32 - 2 target bases");
+        return CATCHHIP_EINVAL;
+    }
+    if (R0->n >= ((i64)1 << 31) || C->n >= ((i64)1 << 31)) {
+        chip_set_error("rows_subtract: too many rows");
+        return CATCHHIP_EINVAL;
+    }
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    std::unique_ptr<catchhip_rows> R;
+    TRY(chip_rows_new(ctx, R0->total, R0->ngenomes, R0->h_genome_off, R0->genome_off.p, false, R));
+    R->ext = -1;
+    PhaseTimer tm(ctx, PHASE_ROWS);
+    if (R0->n == 0 || C->n == 0) {
+        if (R0->n) TRY(sub_copy(ctx, R0, R.get()));
+        else HIP_TRY(hipStreamSynchronize(s));   // (genome_off is on its way)
+        tm.finish();
+        if (nrows) *nrows = R->n;
+        *out = R.release();
+        return 0;
+    }
+    const u32 n0 = (u32)R0->n, nc = (u32)C->n;
+    const size_t nwords = (size_t)(R0->total / 64 + 2) + 8;
+    DevBuf<unsigned long long> bm, info;
+    DevBuf<u32> cnt, pos, scan_tmp;
+    TRY(bm.alloc(nwords));
+    TRY(info.alloc(2));
+    TRY(cnt.alloc(n0));
+    TRY(pos.alloc(n0));
+    HIP_TRY(hipMemsetAsync(bm.p, 0, sizeof(unsigned long long) * nwords, s));
+    HIP_TRY(hipMemsetAsync(info.p, 0, sizeof(unsigned long long) * 2, s));
+    const dim3 grid((unsigned)div_up(n0, 256)), blk(256);
+    hipLaunchKernelGGL(sub_bitmap_kernel, dim3((unsigned)div_up(nc, 256)), blk, 0, s, (const u32 *)C->gs.p,
+                       (const u32 *)C->ge.p, nc, bm.p);
+    hipLaunchKernelGGL(sub_count_kernel, grid, blk, 0, s, (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, n0,
+                       (const unsigned long long *)bm.p, cnt.p, info.p);
+    TRY(chip_exclusive_scan_u32(ctx, cnt.p, pos.p, n0, scan_tmp));
+    tm.launch(3);
+    HIP_TRY(hipGetLastError());
+    // the number of pieces sizes the output (a row may fall into many): it has to come back before the emit
+    unsigned long long npieces = 0;
+    TRY(chip_read_back(ctx, info.p, sizeof(npieces), &npieces));
+    if (npieces >= (1ull << 31)) {
+        chip_set_error("rows_subtract: the rows fall into %llu pieces; a row table holds fewer than 2^31", npieces);
+        return CATCHHIP_EINVAL;
+    }
+    if (npieces) {
+        const u32 cap = (u32)npieces, ng = R0->gain0_n;
+        TRY(chip_rows_alloc_soa(R.get(), cap));
+        if (ng) {
+            TRY(R->gain0.alloc(ng));
+            HIP_TRY(hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)ng, s));
+            R->gain0_n = ng;
+        }
+        hipLaunchKernelGGL(sub_emit_kernel, grid, blk, 0, s, (const i32 *)R0->set_id.p, (const i32 *)R0->univ.p,
+                           (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, n0, (const unsigned long long *)bm.p,
+                           (const u32 *)pos.p, cap, R->set_id.p, R->univ.p, R->gs.p, R->ge.p,
+                           ng ? R->gain0.p : (u32 *)nullptr, ng, info.p);
+        tm.launch(1);
+        HIP_TRY(hipGetLastError());
+        unsigned long long longest = 0;
+        tm.stop();
+        TRY(chip_read_back(ctx, info.p + 1, sizeof(longest), &longest));
+        R->n = (i64)cap;
+        R->lmax = (u32)longest;
+    }
+    tm.finish();
+    if (nrows) *nrows = R->n;
+    *out = R.release();
+    return 0;
+}

@@ -13,8 +13,11 @@ filters stand where bin/design.py:255-385 puts them: --filter-from-fasta and
 --add-reverse-complements after the set cover, which --skip-set-cover leaves
 out; --limit-target-genomes[-randomly-with-replacement] cut the input down
 right after it is read (:101-112).  Custom hybridization functions and
-download: labels are not offered.  --print-analysis and the three --write-...
-options run the coverage analysis of the designed probes (bin/design.py:417-442).
+download: labels are not offered.  --extend-probes (no counterpart in the
+reference) keeps an existing probe set and designs only the probes that bring
+the targets up to the required coverage next to it.  --print-analysis and the
+three --write-... options run the coverage analysis of the designed probes
+(bin/design.py:417-442).
 """
 import argparse
 import logging
@@ -81,6 +84,8 @@ def parse_args(argv=None, args_type="basic"):
     p.add_argument("--write-probe-map-counts-to-tsv")
     def dissimilarity(val):
         fval = float(val)
+        if fval == 0:
+            return None      # no clustering: the way to switch design_large.py's default off (--extend-probes needs it)
         if 0 < fval <= 0.5:
             return fval
         raise argparse.ArgumentTypeError(
@@ -89,7 +94,7 @@ def parse_args(argv=None, args_type="basic"):
                    default=prof["cluster"],
                    help="cluster all input sequences by MinHash signature "
                         "(threshold in 1-ANI, (0, 0.5]), design per cluster "
-                        "and merge")
+                        "and merge; 0: do not cluster")
     p.add_argument("--cluster-and-design-separately-method",
                    choices=["choose", "simple", "hierarchical"],
                    default="choose")
@@ -119,6 +124,13 @@ def parse_args(argv=None, args_type="basic"):
                         "every dataset")
     p.add_argument("--limit-target-genomes-randomly-with-replacement", type=int,
                    help="draw this many genomes of every dataset, with replacement")
+    p.add_argument("--extend-probes", metavar="FASTA",
+                   help="probes that exist already (adapter-free sequences, "
+                        "every record one probe): design only the additional "
+                        "probes that bring the targets up to the required "
+                        "coverage beside them; the output holds the new "
+                        "probes, an analysis covers the existing and the new "
+                        "ones together")
     p.add_argument("--add-adapters", action="store_true",
                    help="add PCR adapters to both ends of every probe")
     p.add_argument("--adapter-a", nargs=2,
@@ -150,6 +162,28 @@ def main(args):
         raise Exception(("Cannot use --cluster-and-design-separately with "
                          "--identify, because clustering collapses genome "
                          "groupings into one"))
+    existing_probes = []
+    if args.extend_probes:
+        if args.skip_set_cover:
+            raise Exception(("Cannot use --extend-probes with --skip-set-cover: "
+                             "the set cover is what decides which probes the "
+                             "existing ones leave to be designed"))
+        if args.cluster_and_design_separately:
+            raise Exception(("Cannot use --extend-probes with "
+                             "--cluster-and-design-separately (a default of "
+                             "design_large.py): the existing probes are set "
+                             "against each dataset as a whole; set "
+                             "--cluster-and-design-separately to 0 (and, where "
+                             "it is set, --cluster-from-fragments to 0 too)"))
+        if args.cluster_from_fragments:
+            raise Exception(("Cannot use --extend-probes with "
+                             "--cluster-from-fragments (a default of "
+                             "design_large.py): nothing is clustered; set "
+                             "--cluster-from-fragments to 0 as well"))
+        existing_probes = list(seq_io.iterate_fasta(args.extend_probes))
+        if len(existing_probes) == 0:
+            raise Exception("--extend-probes: %s holds no sequence"
+                            % args.extend_probes)
     if args.cluster_from_fragments and not args.cluster_and_design_separately:
         raise Exception(("Cannot use --cluster-from-fragments without also "
                          "setting --cluster-and-design-separately"))
@@ -243,7 +277,7 @@ def main(args):
         island_of_exact_match_tolerant=args.island_of_exact_match_tolerant,
         identify=args.identify, avoided_genomes=args.avoid_genomes,
         coverage=args.coverage, cover_extension=args.cover_extension,
-        kmer_probe_map_k=k_scf)
+        kmer_probe_map_k=k_scf, fixed_probes=existing_probes)
     filters.append(scf)
     if args.add_adapters:      # bin/design.py:345-365 (default sequences :350, :354)
         from catch_amd.filter import adapter_filter
@@ -288,8 +322,12 @@ def main(args):
         # bin/design.py:417-442; the reverse strands are analysed when reverse-
         # complement probes were added (rc_too follows --add-reverse-complements)
         from catch_amd import coverage_analysis
+        analyzed = pb.final_probes
+        if existing_probes:      # what the user will order against: the probes they own, then the new ones
+            from catch_amd import probe
+            analyzed = [probe.Probe.from_str(s) for s in existing_probes] + list(analyzed)
         analyzer = coverage_analysis.Analyzer(
-            pb.final_probes, args.mismatches, lcf_thres, genomes_grouped,
+            analyzed, args.mismatches, lcf_thres, genomes_grouped,
             target_genomes_names=[os.path.basename(fn) for fn in args.dataset],
             island_of_exact_match=args.island_of_exact_match,
             cover_extension=args.cover_extension,
@@ -306,7 +344,8 @@ def main(args):
         if args.print_analysis:
             analyzer.print_analysis()
     else:
-        print(len(pb.final_probes))      # bin/design.py:443-445: only without an analysis
+        # bin/design.py:443-445: only without an analysis (with --extend-probes: the number of NEW probes)
+        print(len(pb.final_probes))
     return pb
 
 

@@ -782,6 +782,16 @@ class Rows:
             _ptr(ext, c_i32p) if n else None, hs, _ptr(nr, c_i64p)))
         return [Rows(self.ctx, ctypes.c_void_p(hs[i]), nr[i]) for i in range(n)]
 
+    def subtract(self, covered):
+        """catchhip_rows_subtract: these rows without the bases that `covered`
+        (Rows over the same universes, any set ids) covers -- every row cut
+        into its uncovered runs, set, universe and order kept."""
+        h = ctypes.c_void_p()
+        n = ctypes.c_int64(0)
+        check(self.ctx._L.catchhip_rows_subtract(
+            self.ctx._h, self._h, covered._h, ctypes.byref(h), ctypes.byref(n)))
+        return Rows(self.ctx, h, n.value)
+
     def fetch_gain0(self, num_sets):
         """catchhip_rows_fetch_gain0 -> uint32[min(num_sets, held)] (None: the rows hold no gain0)."""
         out = np.zeros(max(int(num_sets), 1), dtype=np.uint32)

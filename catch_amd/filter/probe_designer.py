@@ -276,6 +276,8 @@ class ProbeDesigner:
             return None
         if scf.identify or scf.avoided_genomes:
             return None
+        if getattr(scf, "fixed_probes", None):
+            return None                  # extending a probe set: the host front end (SetCoverFilter._filter_strs_extend)
         skip, L = self.seq_length_to_skip, self.probe_length
         total, ngroups = 0, 0
         if isinstance(genomes, ClusteredFragments):

@@ -7,6 +7,10 @@ Same constructor and `BaseFilter.filter()` contract as the reference class
 the HIP kernels of libcatchhip.so through `catch_amd.engine`.  There is no
 CPU fallback: without the library or a GPU the filter raises.
 
+Beyond the reference: `fixed_probes` (a trailing keyword) names probes the user
+owns already; the filter then selects only what they leave uncovered
+(_filter_strs_extend).
+
 Not supported (raises NotImplementedError): custom hybridization functions
 loaded from a Python file (`custom_cover_range_fn`, :288-299) -- an arbitrary
 Python callable cannot run inside a kernel.
@@ -59,7 +63,8 @@ class SetCoverFilter(BaseFilter):
                  coverage=1.0,
                  cover_extension=0,
                  kmer_probe_map_k=20,
-                 kmer_probe_map_use_native_dict=False):
+                 kmer_probe_map_use_native_dict=False,
+                 fixed_probes=None):
         if (custom_cover_range_fn is not None
                 or custom_cover_range_tolerant_fn is not None):
             raise NotImplementedError(
@@ -104,6 +109,10 @@ class SetCoverFilter(BaseFilter):
         self._force_num_processes = None   # accepted, unused (:355-357)
         self.scan_mode = engine.SCAN_AUTO
         self.last_timings = {}
+        # probes the user owns already (strings or Probe objects; not an argument of the reference's class): the
+        # filter then selects only what they leave uncovered (_filter_strs_extend)
+        self.fixed_probes = [q if isinstance(q, str) else q.seq_str
+                             for q in (fixed_probes if fixed_probes is not None else ())]
 
     # ------------------------------------------------------------------
     def _context(self):
@@ -230,6 +239,9 @@ class SetCoverFilter(BaseFilter):
         the ranks and every rank returns the complete selection."""
         import os
         from catch_amd import parallel
+        if self.fixed_probes:
+            return self._filter_strs_extend(input_strs, target_genomes_grouped,
+                                            assume_unique)
         if only is None and parallel.world().size > 1:
             return self._filter_strs_multirank(input_strs, target_genomes_grouped,
                                                assume_unique, parallel.world())
@@ -322,6 +334,102 @@ class SetCoverFilter(BaseFilter):
         self.last_timings = timings
         return selected
 
+
+    def _filter_strs_extend(self, input_strs, target_genomes_grouped,
+                            assume_unique=False):
+        """_filter_strs with fixed probes: per group the candidates that bring
+        its genomes up to the required coverage GIVEN the fixed probes, in pick
+        order.  The fixed probes count as sets picked before the first round of
+        the greedy loop (catch/utils/set_cover.py:362-550): their coverage C0_u
+        (the filter's own hybridization model, strands as given) leaves every
+        universe and every candidate's rows, and as many bases may stay
+        uncovered as in U_u = (union of the candidates' rows) + C0_u
+        (extension_fraction).  The solvers run unchanged on the reduced
+        instance.  One group after the other on one context, in input order; the
+        fixed probes' anchors are drawn first."""
+        from catch_amd import parallel
+        if parallel.world().size > 1:
+            raise NotImplementedError(
+                "fixed probes (extending an existing probe set) run on one rank")
+        ctx = self._context()
+        selected = [[] for _ in input_strs]
+        timings = dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0, rows=0,
+                       scan_launches=0, greedy_launches=0, fixed_scan_ms=0.0,
+                       subtract_ms=0.0, rows_fixed=0, rows_reduced=0)
+
+        def add_phases(names):
+            for name, ph in names:
+                ms, nl = ctx.kernel_ms(ph)
+                timings[name] = timings.get(name, 0.0) + ms
+                ln = name.replace("_ms", "_launches")
+                timings[ln] = timings.get(ln, 0) + nl
+
+        fk, funiq, _fowner, fep, feo = probe.anchor_table(
+            self.fixed_probes, self.mismatches, self.lcf_thres,
+            min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k)
+        fowner = np.zeros(len(funiq), dtype=np.int32)     # one set: only their union matters
+        scan_args = (self.mismatches, self.lcf_thres, self.island_of_exact_match,
+                     self.cover_extension, self.scan_mode)
+        for gi, strs in enumerate(input_strs):
+            if len(strs) == 0:
+                continue
+            target_genomes = target_genomes_grouped[gi]
+            ng = len(target_genomes)
+            logger.info("Building set cover sets input (group %d of %d), %d fixed probes",
+                        gi + 1, len(input_strs), len(funiq))
+            k, uniq, owner, ep, eo = probe.anchor_table(
+                strs, self.mismatches, self.lcf_thres,
+                min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
+                assume_unique=assume_unique)
+            held = []
+            try:
+                targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
+                held.append(targets)
+                probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
+                held.append(probes)
+                rows = engine.Rows.scan(ctx, probes, targets, *scan_args)
+                held.append(rows)
+                add_phases((("scan_ms", engine.PHASE_SCAN), ("verify_ms", engine.PHASE_VERIFY),
+                            ("rows_ms", engine.PHASE_ROWS)))
+                fprobes = engine.Probes(ctx, funiq, fowner, fep, feo, fk)
+                held.append(fprobes)
+                frows = engine.Rows.scan(ctx, fprobes, targets, *scan_args)
+                held.append(frows)
+                timings["fixed_scan_ms"] += sum(ctx.kernel_ms(ph)[0] for ph in (
+                    engine.PHASE_SCAN, engine.PHASE_ROWS))     # (the verify phase lies inside the scan phase)
+                reduced = rows.subtract(frows)
+                held.append(reduced)
+                timings["subtract_ms"] += ctx.kernel_ms(engine.PHASE_ROWS)[0]
+                n2 = reduced.stats(ng)[1]
+                c0 = frows.stats(ng)[1]
+                universe_p = [extension_fraction(int(a), int(b), p) for a, b, p in
+                              zip(n2, c0, self._make_universe_p(target_genomes))]
+                ranks = self._make_ranks_strs(strs, target_genomes_grouped, ctx)
+                logger.info("Solving the set cover instance of group %d of %d",
+                            gi + 1, len(input_strs))
+                ids = reduced.greedy(
+                    len(strs), ranks if ranks.any() else None,
+                    None if all(p == 1.0 for p in universe_p) else universe_p)
+                add_phases((("greedy_ms", engine.PHASE_GREEDY),
+                            ("rounds_ms", engine.PHASE_GREEDY_ROUNDS),
+                            ("claim_ms", engine.PHASE_CLAIM)))
+                timings["rows"] += rows.n
+                timings["rows_fixed"] += frows.n
+                timings["rows_reduced"] += reduced.n
+                timings["picks"] += len(ids)
+            finally:
+                for h in reversed(held):
+                    h.close()
+            num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
+            if num_bad > 0:
+                logger.warning(("Group %d: forced to choose %d less-than-ideal "
+                                "probe%s (i.e., probes that 'hit' more than "
+                                "one grouping during identification or probes "
+                                "that cover an avoided genome)"), gi + 1,
+                               num_bad, "" if num_bad == 1 else "s")
+            selected[gi] = list(ids)
+        self.last_timings = timings
+        return selected
 
     def _anchor_tables_in_input_order(self, input_strs, nonempty, assume_unique):
         """{group: anchor table} for all non-empty groups, drawn in input order,
@@ -1069,6 +1177,26 @@ class SetCoverFilter(BaseFilter):
             for j, gi in enumerate(chunk):
                 selected[gi] = (ids[grp == j] - offsets[j]).tolist()
             _accumulate(timings, ctx, nrows, len(ids))
+
+
+def extension_fraction(n2, covered, p):
+    """The coverage fraction to ask of a universe of the REDUCED instance
+    (SetCoverFilter._filter_strs_extend): n2 elements are left of a universe of
+    n2 + covered after the fixed probes took theirs, and of the whole universe
+    the fraction p was to be covered.  catch/utils/set_cover.py:366-367 lets
+    can = int(|U| - p |U|) elements (IEEE double) stay uncovered; the solver
+    derives that number from a fraction of ITS universe, so the fraction
+    returned makes int(n2 - p' n2) == min(can, n2): exactly 1.0 when nothing may
+    stay uncovered, 0.0 when everything left may, else the middle of the
+    interval of fractions that give `can` (its ends are half an element away:
+    no rounding of a double below 2^32 reaches them)."""
+    n = n2 + covered
+    can = int(n - p * n)
+    if can == 0:
+        return 1.0
+    if can >= n2:
+        return 0.0
+    return (n2 - can - 0.5) / n2
 
 
 def _lpt(costs, nbins):

@@ -293,6 +293,23 @@ int catchhip_rows_extend(catchhip_ctx *ctx, const catchhip_rows *rows0,
  * No reference counterpart (the reference counts every round). */
 int catchhip_rows_fetch_gain0(catchhip_ctx *ctx, const catchhip_rows *rows,
                               int64_t n, uint32_t *gain0, int64_t *n_out);
+/* ---- extending an existing probe set: rows minus what is covered already ---
+ * out = every maximal run of bases of every row of `rows` that no row of
+ * `covered` touches, with the row's set and universe, in the order of `rows`:
+ * the reduced set cover instance in which the sets behind `covered` count as
+ * picked before the first round of catch/utils/set_cover.py:362-550 (their
+ * elements leave every universe and every other set).  The reference has no
+ * counterpart.  `rows`: a row table in the solver's form (a merged cover scan,
+ * rows_from_host, rows_extend); `covered`: any row table over the same
+ * coordinate space (equal universe lengths), any set ids, rows may overlap
+ * across sets.  The result is sorted and normalised like `rows` (pieces of a
+ * row are at least one covered base apart) and carries gain0 when `rows`
+ * does; *nrows (may be NULL) = its row count.  An empty `covered` gives a copy
+ * of `rows`.  CATCHHIP_EINVAL for deferred, direct or grouped rows (either
+ * table), another coordinate space, or 2^32 - 1 target bases and more. */
+int catchhip_rows_subtract(catchhip_ctx *ctx, const catchhip_rows *rows,
+                           const catchhip_rows *covered,
+                           catchhip_rows **out, int64_t *nrows);
 /* One (probes, targets, mismatches) instance over n_ext cover extensions: the
  * reference's design.py run once per e (set_cover_filter.py:816-846 each time).
  * Scans once at e = 0, derives the rows at each ext[i] (catchhip_rows_extend,
