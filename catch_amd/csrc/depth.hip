@@ -1,0 +1,213 @@
+// Rows below a coverage depth (catchhip_rows_below_depth): the reduced set cover instance of one layer of
+// SetCoverFilter(coverage_depth=D).
+//
+// Layer k of the layered greedy asks for every base to lie in k picked sets.  The sets picked by the layers before
+// it are out of the running, and a base that k of them hold already needs nothing more: the layer's instance is the
+// rows of the unpicked sets, each cut into its maximal runs of bases at depth < k, where depth(b) = the number of
+// picked sets with a row over b.  The rows of one set never overlap, so that is the number of picked ROWS over b.
+//
+//   1. dp_mark_kernel       picked[set] = 1; a set named twice or out of range raises a flag
+//   2. dp_diff_kernel       over the picked rows: d[gs] += 1, d[ge] -= 1 (u32, wrapping; integer atomics, so the
+//                           result does not depend on the order of the rows) -- total + 1 entries, a row may end at total
+//   3. chip_exclusive_scan_u32 in place: depth[b] = d[b + 1].  A row never leaves its universe, so the depth falls
+//                           to 0 at every universe boundary and one scan serves the whole coordinate space.
+//   4. dp_threshold_kernel  a lane per base: __ballot(depth >= k) is one 64-bit word of the bitmap of bases that need
+//                           nothing more; lane 0 stores it and adds its bits to reached[universe]
+//   5. chip_rows_cut        subtract.hip's count, scan and emit over that bitmap, the picked sets left out whole
+//
+// Everything is integer arithmetic.
+#include "internal.h"
+#include "wave.h"
+
+#define DP_WORDS 32   // bitmap words (of 64 bases) per wavefront of dp_threshold_kernel: one atomic per wave and universe
+
+// flag[0] |= 1: an id outside [0, num_sets); |= 2: an id given twice
+__global__ void __launch_bounds__(256)
+dp_mark_kernel(const i64 *__restrict__ picks, u32 npicks, i64 num_sets, u32 *__restrict__ picked32,
+               u32 *__restrict__ flag) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npicks) return;
+    const i64 s = picks[i];
+    if (s < 0 || s >= num_sets) { atomicOr(&flag[0], 1u); return; }
+    if (atomicExch(&picked32[s], 1u)) atomicOr(&flag[0], 2u);
+}
+
+// the marks as bytes (what chip_rows_cut's kernels index per row)
+__global__ void __launch_bounds__(256)
+dp_pack_kernel(const u32 *__restrict__ picked32, u32 num_sets, u8 *__restrict__ picked) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < num_sets) picked[i] = (u8)picked32[i];
+}
+
+__global__ void __launch_bounds__(256)
+dp_diff_kernel(const i32 *__restrict__ set_id, const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n,
+               const u8 *__restrict__ picked, u32 num_sets, u32 *__restrict__ d) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const u32 s = (u32)set_id[r];
+    if (s >= num_sets || !picked[s]) return;
+    const u32 a = gs[r], b = ge[r];
+    if (b <= a) return;
+    atomicAdd(&d[a], 1u);
+    atomicAdd(&d[b], 0xffffffffu);
+}
+
+// d[b + 1] = depth of base b.  Wavefront v takes the words [v * DP_WORDS, (v + 1) * DP_WORDS) of the bitmap, lowest
+// first: bit b of bm = depth(b) >= k.  Lane 0 keeps the universe the walk is in and the bits it counted there, and
+// adds them to reached[] when the walk leaves the universe (boundaries are not word-aligned) and at the end.
+__global__ void __launch_bounds__(256)
+dp_threshold_kernel(const u32 *__restrict__ d, u32 total, u32 k, const u32 *__restrict__ genome_off, u32 ng,
+                    unsigned long long *__restrict__ bm, unsigned long long *__restrict__ reached) {
+    const u32 lane = threadIdx.x & 63u;
+    const u32 nw = (u32)(((u64)total + 63) >> 6);
+    const u32 w0 = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * DP_WORDS;
+    if (w0 >= nw) return;                                   // (the whole wavefront)
+    const u32 w1 = min(w0 + DP_WORDS, nw);
+    u32 u = 0;
+    u64 uend = 0;
+    unsigned long long acc = 0;
+    if (lane == 0) {
+        u = find_segment(genome_off, ng, w0 << 6);
+        uend = genome_off[u + 1];
+    }
+    for (u32 w = w0; w < w1; ++w) {
+        const u64 pos = ((u64)w << 6) + lane;
+        const bool in = pos < total && d[pos + 1] >= k;
+        const unsigned long long bits = __ballot(in);
+        if (lane == 0) {
+            bm[w] = bits;
+            const u64 base = (u64)w << 6;
+            u64 rest = bits;
+            while (rest) {
+                if (uend >= base + 64 || u + 1 >= ng) {     // the rest of the word lies in universe u
+                    acc += (u32)__popcll(rest);
+                    break;
+                }
+                const u32 nb = uend > base ? (u32)(uend - base) : 0u;    // bits [0, nb) are universe u's: nb <= 63
+                const u64 m = nb ? ~0ull >> (64 - nb) : 0ull;
+                acc += (u32)__popcll(rest & m);
+                rest &= ~m;
+                if (rest) {                                 // on to the next universe
+                    if (acc) atomicAdd(&reached[u], acc);
+                    acc = 0;
+                    ++u;
+                    uend = genome_off[u + 1];
+                }
+            }
+        }
+    }
+    if (lane == 0 && acc) atomicAdd(&reached[u], acc);
+}
+
+extern "C" int catchhip_rows_below_depth(catchhip_ctx *ctx, const catchhip_rows *R0, i64 num_sets, const i64 *picks,
+                                         i64 npicks, i32 depth, catchhip_rows **out, i64 *nrows, i64 *reached) {
+    ARG_CHECK(ctx && R0 && out);
+    ARG_CHECK(R0->ctx == ctx);
+    *out = nullptr;
+    if (nrows) *nrows = 0;
+    ARG_CHECK(num_sets >= 0 && num_sets < ((i64)1 << 31) && npicks >= 0 && (npicks == 0 || picks));
+    if (depth < 1) {
+        chip_set_error("rows_below_depth: depth %d; the smallest depth is 1", (int)depth);
+        return CATCHHIP_EINVAL;
+    }
+    TRY(chip_rows_cut_check(R0, "rows_below_depth", "the rows"));
+    if (R0->total >= ((i64)1 << 32) - 1) {
+        chip_set_error("rows_below_depth: more than 2^32 - 2 target bases");
+        return CATCHHIP_EINVAL;
+    }
+    if (R0->n >= ((i64)1 << 31)) {
+        chip_set_error("rows_below_depth: too many rows");
+        return CATCHHIP_EINVAL;
+    }
+    if (npicks > num_sets) {
+        chip_set_error("rows_below_depth: %lld picks of %lld sets (an id is repeated or out of range)",
+                       (long long)npicks, (long long)num_sets);
+        return CATCHHIP_EINVAL;
+    }
+    const i32 ng = R0->ngenomes;
+    if (reached) for (i32 u = 0; u < ng; ++u) reached[u] = 0;
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    std::unique_ptr<catchhip_rows> R;
+    TRY(chip_rows_new(ctx, R0->total, ng, R0->h_genome_off, R0->genome_off.p, false, R));
+    R->ext = -1;
+    PhaseTimer tm(ctx, PHASE_ROWS);
+    if (npicks == 0) {                                       // depth 0 everywhere: a copy, nothing reached
+        if (R0->n) TRY(chip_rows_copy(ctx, R0, R.get()));
+        else HIP_TRY(hipStreamSynchronize(s));               // (genome_off is on its way)
+        tm.finish();
+        if (nrows) *nrows = R->n;
+        *out = R.release();
+        return 0;
+    }
+    // the picked sets
+    DevBuf<i64> d_picks;
+    DevBuf<u32> picked32, flag;
+    DevBuf<u8> picked;
+    TRY(d_picks.alloc((size_t)npicks));
+    TRY(picked32.alloc((size_t)num_sets));
+    TRY(picked.alloc((size_t)num_sets));
+    TRY(flag.alloc(1));
+    HIP_TRY(hipMemcpyAsync(d_picks.p, picks, sizeof(i64) * (size_t)npicks, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(picked32.p, 0, sizeof(u32) * (size_t)num_sets, s));
+    HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(u32), s));
+    hipLaunchKernelGGL(dp_mark_kernel, dim3((unsigned)div_up(npicks, 256)), dim3(256), 0, s, (const i64 *)d_picks.p,
+                       (u32)npicks, num_sets, picked32.p, flag.p);
+    hipLaunchKernelGGL(dp_pack_kernel, dim3((unsigned)div_up(num_sets, 256)), dim3(256), 0, s,
+                       (const u32 *)picked32.p, (u32)num_sets, picked.p);
+    tm.launch(2);
+    HIP_TRY(hipGetLastError());
+    u32 h_flag = 0;
+    TRY(read_count(ctx, flag.p, &h_flag));                   // (also: the pageable picks[] has been read)
+    if (h_flag) {
+        chip_set_error("rows_below_depth: a pick %s", (h_flag & 1u) ? "lies outside the set ids" : "is given twice");
+        return CATCHHIP_EINVAL;
+    }
+    // depth per base -> the bitmap of bases at depth >= `depth`, and their number per universe
+    const u64 total = (u64)R0->total;
+    const size_t nwords = (size_t)(total / 64 + 2) + 8;
+    DevBuf<unsigned long long> bm, d_reached;
+    TRY(bm.alloc(nwords));
+    TRY(d_reached.alloc((size_t)ng));
+    HIP_TRY(hipMemsetAsync(bm.p, 0, sizeof(unsigned long long) * nwords, s));
+    HIP_TRY(hipMemsetAsync(d_reached.p, 0, sizeof(unsigned long long) * (size_t)(ng ? ng : 1), s));
+    if (R0->n && total && ng > 0) {
+        DevBuf<u32> d, tmp;
+        TRY(d.alloc(total + 2));
+        TRY(chip_exclusive_scan_reserve(tmp, (i64)total + 1));
+        HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(u32) * (total + 2), s));
+        hipLaunchKernelGGL(dp_diff_kernel, dim3((unsigned)div_up(R0->n, 256)), dim3(256), 0, s,
+                           (const i32 *)R0->set_id.p, (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, (u32)R0->n,
+                           (const u8 *)picked.p, (u32)num_sets, d.p);
+        TRY(chip_exclusive_scan_u32(ctx, d.p, d.p, (i64)total + 1, tmp));
+        const u64 nwaves = div_up((i64)div_up((i64)total, 64), DP_WORDS);
+        hipLaunchKernelGGL(dp_threshold_kernel, dim3((unsigned)div_up((i64)nwaves, 256 / WAVE)), dim3(256), 0, s,
+                           (const u32 *)d.p, (u32)total, (u32)depth, (const u32 *)R0->genome_off.p, (u32)ng, bm.p,
+                           d_reached.p);
+        tm.launch(3);
+        HIP_TRY(hipGetLastError());
+        TRY(chip_rows_cut(ctx, R0, (const unsigned long long *)bm.p, (const u8 *)picked.p, (u32)num_sets, R.get(), tm,
+                          "rows_below_depth"));
+    }
+    if (R->n == 0 && R0->gain0_n) {                          // nothing left of any set: gain0 is carried all the same
+        TRY(R->gain0.alloc(R0->gain0_n));
+        HIP_TRY(hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)R0->gain0_n, s));
+        R->gain0_n = R0->gain0_n;
+    }
+    tm.stop();
+    if (reached && ng > 0) {
+        TRY(chip_pinned_reserve(ctx, sizeof(unsigned long long) * (size_t)ng));
+        HIP_TRY(hipMemcpyAsync(ctx->h_big, d_reached.p, sizeof(unsigned long long) * (size_t)ng,
+                               hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const unsigned long long *h = (const unsigned long long *)ctx->h_big;
+        for (i32 u = 0; u < ng; ++u) reached[u] = (i64)h[u];
+    } else {
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    tm.finish();
+    if (nrows) *nrows = R->n;
+    *out = R.release();
+    return 0;
+}

@@ -407,6 +407,18 @@ struct PhaseTimer {
     }
 };
 
+// ---- rows cut by a bitmap of bases (subtract.hip; catchhip_rows_subtract and catchhip_rows_below_depth) --------
+// CATCHHIP_EINVAL (message "<who>: <which> are ...") for deferred, direct or grouped rows
+int chip_rows_cut_check(const catchhip_rows *R, const char *who, const char *which);
+// a copy of the SoA table R0 (with its gain0 and lmax) into R, made by chip_rows_new over the same coordinate space
+int chip_rows_copy(catchhip_ctx *ctx, const catchhip_rows *R0, catchhip_rows *R);
+// every row of R0 (non-empty, fewer than 2^31 rows) cut into its maximal runs of bases whose bit in bm is clear
+// (total / 64 + 1 words at least); the rows of the sets with skip[set] != 0 (set < nskip; skip may be null) are left
+// out whole.  Order and normal form of R0 are kept; R gets n, lmax and, when R0 has it, gain0.  tm: the caller's
+// running timer (its launches are counted and its stop event recorded here).
+int chip_rows_cut(catchhip_ctx *ctx, const catchhip_rows *R0, const unsigned long long *bm, const u8 *skip, u32 nskip,
+                  catchhip_rows *R, PhaseTimer &tm, const char *who);
+
 // ---- device primitives (primitives.hip) ---------------------------------
 // exclusive prefix sum of n u32 values (in place allowed: out may equal in);
 // if total != nullptr, *total (device u64) receives the grand total.

@@ -9,6 +9,8 @@
 // to catchhip_setcover_greedy as it is.
 //
 // covered -> bitmap (one bit per base) -> pieces per row (word-parallel) -> exclusive scan -> emit.
+// Everything behind the bitmap is chip_rows_cut, which catchhip_rows_below_depth (depth.hip) calls with a bitmap of its
+// own and the sets that leave the table whole.
 #include <algorithm>
 
 #include "internal.h"
@@ -43,16 +45,21 @@ __device__ __forceinline__ u64 sub_free(u64 v, u32 j, u32 nw, u64 m0, u64 m1) {
 // (prev = the word before, 0 for the first)
 __device__ __forceinline__ u32 sub_starts(u64 f, u64 prev) { return (u32)__popcll(f & ~((f << 1) | (prev >> 63))); }
 
+// skip[s] != 0 (s < nskip; skip may be null): the rows of set s leave the table whole (catchhip_rows_below_depth)
+__device__ __forceinline__ bool sub_skipped(const u8 *__restrict__ skip, u32 nskip, i32 sid) {
+    return skip && (u32)sid < nskip && skip[(u32)sid];
+}
+
 // cnt[r] = pieces of row r; info[0] += their number
 __global__ void __launch_bounds__(256)
-sub_count_kernel(const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n,
-                 const unsigned long long *__restrict__ bm, u32 *__restrict__ cnt,
-                 unsigned long long *__restrict__ info) {
+sub_count_kernel(const i32 *__restrict__ set_id, const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n,
+                 const unsigned long long *__restrict__ bm, const u8 *__restrict__ skip, u32 nskip,
+                 u32 *__restrict__ cnt, unsigned long long *__restrict__ info) {
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
     u32 c = 0;
     if (r < n) {
         const u32 s = gs[r], e = ge[r];
-        if (e > s) {
+        if (e > s && !sub_skipped(skip, nskip, set_id[r])) {
             const u32 w0 = s >> 6, nw = ((e - 1) >> 6) - w0 + 1;
             const u64 m0 = ~0ull << (s & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
             u64 prev = 0;
@@ -124,7 +131,7 @@ struct SubWalk {
 __global__ void __launch_bounds__(256)
 sub_emit_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__ univ, const u32 *__restrict__ gs,
                 const u32 *__restrict__ ge, u32 n, const unsigned long long *__restrict__ bm,
-                const u32 *__restrict__ pos, u32 cap, i32 *__restrict__ o_set, i32 *__restrict__ o_univ,
+                const u8 *__restrict__ skip, u32 nskip, const u32 *__restrict__ pos, u32 cap, i32 *__restrict__ o_set, i32 *__restrict__ o_univ,
                 u32 *__restrict__ o_gs, u32 *__restrict__ o_ge, u32 *__restrict__ gain0, u32 ng,
                 unsigned long long *__restrict__ info) {
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,7 +143,7 @@ sub_emit_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__ univ, co
         w.o = pos[r]; w.cap = cap;
         w.sid = set_id[r]; w.un = univ[r];
         w.start = 0; w.open = false; w.sum = 0; w.longest = 0;
-        if (e > s) {
+        if (e > s && !sub_skipped(skip, nskip, w.sid)) {
             const u32 w0 = s >> 6, nw = ((e - 1) >> 6) - w0 + 1;
             const u64 m0 = ~0ull << (s & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
             if (nw <= SUB_MAXW) {
@@ -158,24 +165,24 @@ sub_emit_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__ univ, co
     if ((threadIdx.x & 63u) == 0 && longest) atomicMax(&info[1], (unsigned long long)longest);
 }
 
-static int sub_check_table(const catchhip_rows *R, const char *which) {
+int chip_rows_cut_check(const catchhip_rows *R, const char *who, const char *which) {
     if (R->deferred) {
-        chip_set_error("rows_subtract: %s are deferred rows (a fused scan that was never synchronised)", which);
+        chip_set_error("%s: %s are deferred rows (a fused scan that was never synchronised)", who, which);
         return CATCHHIP_EINVAL;
     }
     if (R->rows4.p) {
-        chip_set_error("rows_subtract: %s are in the direct form of the fused filter, not a row table", which);
+        chip_set_error("%s: %s are in the direct form of the fused filter, not a row table", who, which);
         return CATCHHIP_EINVAL;
     }
     if (R->grouped) {
-        chip_set_error("rows_subtract: %s come from a scan with group numbers (a union of instances), which is not supported", which);
+        chip_set_error("%s: %s come from a scan with group numbers (a union of instances), which is not supported", who, which);
         return CATCHHIP_EINVAL;
     }
     return 0;
 }
 
 // a copy of R0 (nothing is covered)
-static int sub_copy(catchhip_ctx *ctx, const catchhip_rows *R0, catchhip_rows *R) {
+int chip_rows_copy(catchhip_ctx *ctx, const catchhip_rows *R0, catchhip_rows *R) {
     const size_t n = (size_t)R0->n;
     hipStream_t s = ctx->stream;
     TRY(chip_rows_alloc_soa(R, n));
@@ -194,14 +201,64 @@ static int sub_copy(catchhip_ctx *ctx, const catchhip_rows *R0, catchhip_rows *R
     return 0;
 }
 
+// The rows of R0 (a non-empty table that passed chip_rows_cut_check, fewer than 2^31 rows) cut into their maximal
+// runs of bases whose bit in bm is clear, into R (made by chip_rows_new over R0's coordinate space); the rows of the
+// sets with skip[set] != 0 (set < nskip; skip may be null) are left out whole.  count -> exclusive scan -> read-back
+// of the number of pieces -> emit; R gets n, lmax and, when R0 has it, gain0.  tm is the caller's running timer: its
+// stop event is recorded behind the emit.
+int chip_rows_cut(catchhip_ctx *ctx, const catchhip_rows *R0, const unsigned long long *bm, const u8 *skip, u32 nskip,
+                  catchhip_rows *R, PhaseTimer &tm, const char *who) {
+    hipStream_t s = ctx->stream;
+    const u32 n0 = (u32)R0->n;
+    DevBuf<unsigned long long> info;
+    DevBuf<u32> cnt, pos, scan_tmp;
+    TRY(info.alloc(2));
+    TRY(cnt.alloc(n0));
+    TRY(pos.alloc(n0));
+    HIP_TRY(hipMemsetAsync(info.p, 0, sizeof(unsigned long long) * 2, s));
+    const dim3 grid((unsigned)div_up(n0, 256)), blk(256);
+    hipLaunchKernelGGL(sub_count_kernel, grid, blk, 0, s, (const i32 *)R0->set_id.p, (const u32 *)R0->gs.p,
+                       (const u32 *)R0->ge.p, n0, bm, skip, nskip, cnt.p, info.p);
+    TRY(chip_exclusive_scan_u32(ctx, cnt.p, pos.p, n0, scan_tmp));
+    tm.launch(2);
+    HIP_TRY(hipGetLastError());
+    // the number of pieces sizes the output (a row may fall into many): it has to come back before the emit
+    unsigned long long npieces = 0;
+    TRY(chip_read_back(ctx, info.p, sizeof(npieces), &npieces));
+    if (npieces >= (1ull << 31)) {
+        chip_set_error("%s: the rows fall into %llu pieces; a row table holds fewer than 2^31", who, npieces);
+        return CATCHHIP_EINVAL;
+    }
+    if (npieces) {
+        const u32 cap = (u32)npieces, ng = R0->gain0_n;
+        TRY(chip_rows_alloc_soa(R, cap));
+        if (ng) {
+            TRY(R->gain0.alloc(ng));
+            HIP_TRY(hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)ng, s));
+            R->gain0_n = ng;
+        }
+        hipLaunchKernelGGL(sub_emit_kernel, grid, blk, 0, s, (const i32 *)R0->set_id.p, (const i32 *)R0->univ.p,
+                           (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, n0, bm, skip, nskip, (const u32 *)pos.p, cap,
+                           R->set_id.p, R->univ.p, R->gs.p, R->ge.p, ng ? R->gain0.p : (u32 *)nullptr, ng, info.p);
+        tm.launch(1);
+        HIP_TRY(hipGetLastError());
+        unsigned long long longest = 0;
+        tm.stop();
+        TRY(chip_read_back(ctx, info.p + 1, sizeof(longest), &longest));
+        R->n = (i64)cap;
+        R->lmax = (u32)longest;
+    }
+    return 0;
+}
+
 extern "C" int catchhip_rows_subtract(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_rows *C,
                                       catchhip_rows **out, i64 *nrows) {
     ARG_CHECK(ctx && R0 && C && out);
     ARG_CHECK(R0->ctx == ctx && C->ctx == ctx);
     *out = nullptr;
     if (nrows) *nrows = 0;
-    TRY(sub_check_table(R0, "the rows"));
-    TRY(sub_check_table(C, "the covered rows"));
+    TRY(chip_rows_cut_check(R0, "rows_subtract", "the rows"));
+    TRY(chip_rows_cut_check(C, "rows_subtract", "the covered rows"));
     if (R0->total != C->total || R0->ngenomes != C->ngenomes || R0->h_genome_off != C->h_genome_off) {
         chip_set_error("rows_subtract: the covered rows are not over the coordinate space of the rows "
                        "(%lld bases in %d universes against %lld in %d)",
@@ -224,58 +281,22 @@ extern "C" int catchhip_rows_subtract(catchhip_ctx *ctx, const catchhip_rows *R0
     R->ext = -1;
     PhaseTimer tm(ctx, PHASE_ROWS);
     if (R0->n == 0 || C->n == 0) {
-        if (R0->n) TRY(sub_copy(ctx, R0, R.get()));
+        if (R0->n) TRY(chip_rows_copy(ctx, R0, R.get()));
         else HIP_TRY(hipStreamSynchronize(s));   // (genome_off is on its way)
         tm.finish();
         if (nrows) *nrows = R->n;
         *out = R.release();
         return 0;
     }
-    const u32 n0 = (u32)R0->n, nc = (u32)C->n;
+    const u32 nc = (u32)C->n;
     const size_t nwords = (size_t)(R0->total / 64 + 2) + 8;
-    DevBuf<unsigned long long> bm, info;
-    DevBuf<u32> cnt, pos, scan_tmp;
+    DevBuf<unsigned long long> bm;
     TRY(bm.alloc(nwords));
-    TRY(info.alloc(2));
-    TRY(cnt.alloc(n0));
-    TRY(pos.alloc(n0));
     HIP_TRY(hipMemsetAsync(bm.p, 0, sizeof(unsigned long long) * nwords, s));
-    HIP_TRY(hipMemsetAsync(info.p, 0, sizeof(unsigned long long) * 2, s));
-    const dim3 grid((unsigned)div_up(n0, 256)), blk(256);
-    hipLaunchKernelGGL(sub_bitmap_kernel, dim3((unsigned)div_up(nc, 256)), blk, 0, s, (const u32 *)C->gs.p,
+    hipLaunchKernelGGL(sub_bitmap_kernel, dim3((unsigned)div_up(nc, 256)), dim3(256), 0, s, (const u32 *)C->gs.p,
                        (const u32 *)C->ge.p, nc, bm.p);
-    hipLaunchKernelGGL(sub_count_kernel, grid, blk, 0, s, (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, n0,
-                       (const unsigned long long *)bm.p, cnt.p, info.p);
-    TRY(chip_exclusive_scan_u32(ctx, cnt.p, pos.p, n0, scan_tmp));
-    tm.launch(3);
-    HIP_TRY(hipGetLastError());
-    // the number of pieces sizes the output (a row may fall into many): it has to come back before the emit
-    unsigned long long npieces = 0;
-    TRY(chip_read_back(ctx, info.p, sizeof(npieces), &npieces));
-    if (npieces >= (1ull << 31)) {
-        chip_set_error("rows_subtract: the rows fall into %llu pieces; a row table holds fewer than 2^31", npieces);
-        return CATCHHIP_EINVAL;
-    }
-    if (npieces) {
-        const u32 cap = (u32)npieces, ng = R0->gain0_n;
-        TRY(chip_rows_alloc_soa(R.get(), cap));
-        if (ng) {
-            TRY(R->gain0.alloc(ng));
-            HIP_TRY(hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)ng, s));
-            R->gain0_n = ng;
-        }
-        hipLaunchKernelGGL(sub_emit_kernel, grid, blk, 0, s, (const i32 *)R0->set_id.p, (const i32 *)R0->univ.p,
-                           (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, n0, (const unsigned long long *)bm.p,
-                           (const u32 *)pos.p, cap, R->set_id.p, R->univ.p, R->gs.p, R->ge.p,
-                           ng ? R->gain0.p : (u32 *)nullptr, ng, info.p);
-        tm.launch(1);
-        HIP_TRY(hipGetLastError());
-        unsigned long long longest = 0;
-        tm.stop();
-        TRY(chip_read_back(ctx, info.p + 1, sizeof(longest), &longest));
-        R->n = (i64)cap;
-        R->lmax = (u32)longest;
-    }
+    tm.launch(1);
+    TRY(chip_rows_cut(ctx, R0, (const unsigned long long *)bm.p, nullptr, 0, R.get(), tm, "rows_subtract"));
     tm.finish();
     if (nrows) *nrows = R->n;
     *out = R.release();

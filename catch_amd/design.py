@@ -15,7 +15,9 @@ out; --limit-target-genomes[-randomly-with-replacement] cut the input down
 right after it is read (:101-112).  Custom hybridization functions and
 download: labels are not offered.  --extend-probes (no counterpart in the
 reference) keeps an existing probe set and designs only the probes that bring
-the targets up to the required coverage next to it.  --print-analysis and the
+the targets up to the required coverage next to it; --coverage-depth D (no
+counterpart either) designs a set in which D probes cover every base, one
+greedy layer per unit of depth.  --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
 """
@@ -131,6 +133,13 @@ def parse_args(argv=None, args_type="basic"):
                         "coverage beside them; the output holds the new "
                         "probes, an analysis covers the existing and the new "
                         "ones together")
+    p.add_argument("--coverage-depth", type=int, default=1, metavar="D",
+                   help="design a probe set in which D selected probes cover "
+                        "every base that D candidates can cover (default 1: "
+                        "the ordinary set cover): D greedy layers, each over "
+                        "what the layers before it leave below its depth; the "
+                        "output lists the probes layer by layer, and its "
+                        "first k layers are the design at depth k")
     p.add_argument("--add-adapters", action="store_true",
                    help="add PCR adapters to both ends of every probe")
     p.add_argument("--adapter-a", nargs=2,
@@ -184,6 +193,30 @@ def main(args):
         if len(existing_probes) == 0:
             raise Exception("--extend-probes: %s holds no sequence"
                             % args.extend_probes)
+    if args.coverage_depth < 1:
+        raise Exception("--coverage-depth must be at least 1, not %d"
+                        % args.coverage_depth)
+    if args.coverage_depth > 1:
+        if args.extend_probes:
+            raise Exception(("Cannot use --coverage-depth above 1 with "
+                             "--extend-probes: the depth that existing probes "
+                             "reach already is not taken into account"))
+        if args.skip_set_cover:
+            raise Exception(("Cannot use --coverage-depth above 1 with "
+                             "--skip-set-cover: the depth is what the set "
+                             "cover's layers design for"))
+        if args.cluster_and_design_separately:
+            raise Exception(("Cannot use --coverage-depth above 1 with "
+                             "--cluster-and-design-separately (a default of "
+                             "design_large.py): the layers are designed "
+                             "against each dataset as a whole; set "
+                             "--cluster-and-design-separately to 0 (and, where "
+                             "it is set, --cluster-from-fragments to 0 too)"))
+        if args.cluster_from_fragments:
+            raise Exception(("Cannot use --coverage-depth above 1 with "
+                             "--cluster-from-fragments (a default of "
+                             "design_large.py): nothing is clustered; set "
+                             "--cluster-from-fragments to 0 as well"))
     if args.cluster_from_fragments and not args.cluster_and_design_separately:
         raise Exception(("Cannot use --cluster-from-fragments without also "
                          "setting --cluster-and-design-separately"))
@@ -277,7 +310,8 @@ def main(args):
         island_of_exact_match_tolerant=args.island_of_exact_match_tolerant,
         identify=args.identify, avoided_genomes=args.avoid_genomes,
         coverage=args.coverage, cover_extension=args.cover_extension,
-        kmer_probe_map_k=k_scf, fixed_probes=existing_probes)
+        kmer_probe_map_k=k_scf, fixed_probes=existing_probes,
+        coverage_depth=args.coverage_depth)
     filters.append(scf)
     if args.add_adapters:      # bin/design.py:345-365 (default sequences :350, :354)
         from catch_amd.filter import adapter_filter
@@ -314,6 +348,11 @@ def main(args):
                                  if args.cluster_and_design_separately
                                  else None))
     pb.design()
+    if args.coverage_depth > 1:
+        for fn, sizes in zip(args.dataset, scf.last_layer_sizes):
+            logger.info("%s: %s probes in the layers of depth 1 to %d",
+                        os.path.basename(fn), " / ".join(str(x) for x in sizes),
+                        len(sizes))
     if args.write_probe_fasta:
         seq_io.write_probe_fasta(pb.final_probes, args.write_probe_fasta)
     if (args.print_analysis or args.write_analysis_to_tsv or

@@ -642,10 +642,11 @@ class Candidates:
 class Rows:
     """Device-resident cover rows (catchhip_rows)."""
 
-    def __init__(self, ctx, handle, n):
+    def __init__(self, ctx, handle, n, ngenomes=None):
         self.ctx = ctx
         self._h = handle
         self.n = int(n)
+        self.ngenomes = ngenomes      # universes of the coordinate space (None: the maker did not say)
 
     @staticmethod
     def scan(ctx, probes, targets, mismatches, lcf_thres, island=0,
@@ -659,7 +660,7 @@ class Rows:
             ctx._h, probes._h, targets._h, int(mismatches), int(lcf_thres),
             int(island), int(cover_extension), int(mode), ctypes.byref(h),
             ctypes.byref(n)))
-        return Rows(ctx, h, n.value)
+        return Rows(ctx, h, n.value, getattr(targets, "ngenomes", None))
 
     @staticmethod
     def scan_first_seen(ctx, probes, targets, mismatches, lcf_thres, island=0,
@@ -676,7 +677,7 @@ class Rows:
             int(island), int(cover_extension), int(mode),
             None if order is None else _ptr(order, c_u32p),
             ctypes.byref(h), ctypes.byref(n)))
-        return Rows(ctx, h, n.value)
+        return Rows(ctx, h, n.value, getattr(targets, "ngenomes", None))
 
     def adapter_votes(self, multiplicity):
         """catchhip_adapter_votes -> (A votes, B votes) per set id."""
@@ -767,7 +768,7 @@ class Rows:
         check(ctx._L.catchhip_rows_from_host(
             ctx._h, _ptr(si, c_i32p), _ptr(un, c_i32p), _ptr(st, c_i64p),
             _ptr(en, c_i64p), n, _ptr(gl, c_i64p), ng, ctypes.byref(h)))
-        return Rows(ctx, h, n)
+        return Rows(ctx, h, n, int(np.asarray(genome_len).size))
 
     def extend(self, targets, cover_extensions):
         """catchhip_rows_extend: these rows (a cover scan at cover_extension 0)
@@ -780,7 +781,7 @@ class Rows:
         check(self.ctx._L.catchhip_rows_extend(
             self.ctx._h, self._h, targets._h, n,
             _ptr(ext, c_i32p) if n else None, hs, _ptr(nr, c_i64p)))
-        return [Rows(self.ctx, ctypes.c_void_p(hs[i]), nr[i]) for i in range(n)]
+        return [Rows(self.ctx, ctypes.c_void_p(hs[i]), nr[i], self.ngenomes) for i in range(n)]
 
     def subtract(self, covered):
         """catchhip_rows_subtract: these rows without the bases that `covered`
@@ -790,7 +791,24 @@ class Rows:
         n = ctypes.c_int64(0)
         check(self.ctx._L.catchhip_rows_subtract(
             self.ctx._h, self._h, covered._h, ctypes.byref(h), ctypes.byref(n)))
-        return Rows(self.ctx, h, n.value)
+        return Rows(self.ctx, h, n.value, self.ngenomes)
+
+    def below_depth(self, num_sets, picks, depth):
+        """catchhip_rows_below_depth -> (Rows, reached int64[ngenomes]): the rows
+        of the sets not in `picks`, cut into their runs of bases that fewer than
+        `depth` picked sets cover; reached[u] = the bases of universe u that
+        `depth` or more of them cover."""
+        if self.ngenomes is None:
+            raise ValueError("below_depth: rows of an unknown number of universes")
+        pk = np.ascontiguousarray(picks, dtype=np.int64)
+        ng = int(self.ngenomes)
+        reached = np.zeros(max(ng, 1), dtype=np.int64)
+        h = ctypes.c_void_p()
+        n = ctypes.c_int64(0)
+        check(self.ctx._L.catchhip_rows_below_depth(
+            self.ctx._h, self._h, int(num_sets), _ptr(pk, c_i64p) if pk.size else None,
+            int(pk.size), int(depth), ctypes.byref(h), ctypes.byref(n), _ptr(reached, c_i64p)))
+        return Rows(self.ctx, h, n.value, ng), reached[:ng]
 
     def fetch_gain0(self, num_sets):
         """catchhip_rows_fetch_gain0 -> uint32[min(num_sets, held)] (None: the rows hold no gain0)."""

@@ -278,6 +278,8 @@ class ProbeDesigner:
             return None
         if getattr(scf, "fixed_probes", None):
             return None                  # extending a probe set: the host front end (SetCoverFilter._filter_strs_extend)
+        if getattr(scf, "coverage_depth", 1) > 1:
+            return None                  # layers of a coverage depth: the host front end (SetCoverFilter._filter_strs_depth)
         skip, L = self.seq_length_to_skip, self.probe_length
         total, ngroups = 0, 0
         if isinstance(genomes, ClusteredFragments):

@@ -9,7 +9,9 @@ CPU fallback: without the library or a GPU the filter raises.
 
 Beyond the reference: `fixed_probes` (a trailing keyword) names probes the user
 owns already; the filter then selects only what they leave uncovered
-(_filter_strs_extend).
+(_filter_strs_extend).  `coverage_depth` (after it) asks for every base to be
+covered by that many selected probes, one greedy layer per unit of depth
+(_filter_strs_depth).
 
 Not supported (raises NotImplementedError): custom hybridization functions
 loaded from a Python file (`custom_cover_range_fn`, :288-299) -- an arbitrary
@@ -46,7 +48,20 @@ def _reverse_complement(s):
     return s[::-1].translate(_RC)
 
 
-class SetCoverFilter(BaseFilter):
+class _KeywordsBeyondInit(type):
+    """SetCoverFilter(..., fixed_probes=None, coverage_depth=1): `coverage_depth`
+    is a keyword of the CALL of the class, taken here and handed to the new
+    object after __init__ ran.  __init__ itself stays the reference's argument
+    list followed by `fixed_probes`, the form its callers and the signature
+    checks of the extension know; `coverage_depth` can only be given by name."""
+
+    def __call__(cls, *args, coverage_depth=1, **kwargs):
+        obj = super().__call__(*args, **kwargs)
+        obj._set_coverage_depth(coverage_depth)
+        return obj
+
+
+class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
     """Selects candidate probes with the greedy multi-universe set cover."""
 
     def __init__(self,
@@ -113,6 +128,20 @@ class SetCoverFilter(BaseFilter):
         # filter then selects only what they leave uncovered (_filter_strs_extend)
         self.fixed_probes = [q if isinstance(q, str) else q.seq_str
                              for q in (fixed_probes if fixed_probes is not None else ())]
+        self.coverage_depth = 1     # (SetCoverFilter(..., coverage_depth=D) sets it: _KeywordsBeyondInit)
+        self.last_layer_sizes = []
+
+    def _set_coverage_depth(self, coverage_depth):
+        """How many selected probes are to cover every base (not an argument of
+        the reference's class): 1 is the reference's set cover, more runs one
+        greedy layer per unit of depth (_filter_strs_depth)."""
+        if (isinstance(coverage_depth, bool) or not isinstance(coverage_depth, (int, np.integer))
+                or coverage_depth < 1):
+            raise ValueError("coverage_depth must be an integer >= 1, not %r" % (coverage_depth,))
+        if coverage_depth > 1 and self.fixed_probes:
+            raise NotImplementedError(
+                "coverage_depth > 1 cannot be combined with fixed_probes")
+        self.coverage_depth = int(coverage_depth)
 
     # ------------------------------------------------------------------
     def _context(self):
@@ -242,6 +271,9 @@ class SetCoverFilter(BaseFilter):
         if self.fixed_probes:
             return self._filter_strs_extend(input_strs, target_genomes_grouped,
                                             assume_unique)
+        if self.coverage_depth > 1:
+            return self._filter_strs_depth(input_strs, target_genomes_grouped,
+                                           assume_unique)
         if only is None and parallel.world().size > 1:
             return self._filter_strs_multirank(input_strs, target_genomes_grouped,
                                                assume_unique, parallel.world())
@@ -428,6 +460,118 @@ class SetCoverFilter(BaseFilter):
                                 "that cover an avoided genome)"), gi + 1,
                                num_bad, "" if num_bad == 1 else "s")
             selected[gi] = list(ids)
+        self.last_timings = timings
+        return selected
+
+    def _filter_strs_depth(self, input_strs, target_genomes_grouped,
+                           assume_unique=False):
+        """_filter_strs with coverage_depth = D > 1: per group the candidates of
+        D greedy layers, in layer order and then pick order.  depth(b) = the
+        number of candidates picked so far with a cover row over base b.  Layer
+        1 is the ordinary instance (the scanned rows, the user's fractions).
+        Layer k > 1 is the rows of the unpicked candidates cut into their runs
+        of bases with depth < k (Rows.below_depth); its universe u is those
+        n2[u] bases together with the reached[u] bases at depth >= k, of which
+        int(|U| - p |U|) may stay below k (extension_fraction restates p for the
+        n2[u] bases the solver sees).  The solvers run unchanged, with the same
+        ranks in every layer; the first k layers are the design at depth k.  A
+        layer with no row left is empty and logged.  One group after the other
+        on one context, in input order, one scan per group."""
+        from catch_amd import parallel
+        if parallel.world().size > 1:
+            raise NotImplementedError("coverage_depth > 1 runs on one rank")
+        ctx = self._context()
+        selected = [[] for _ in input_strs]
+        self.last_layer_sizes = [[] for _ in input_strs]
+        timings = dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0, rows=0,
+                       scan_launches=0, greedy_launches=0, depth_ms=0.0,
+                       rows_reduced=0)
+
+        def add_phases(names):
+            for name, ph in names:
+                ms, nl = ctx.kernel_ms(ph)
+                timings[name] = timings.get(name, 0.0) + ms
+                ln = name.replace("_ms", "_launches")
+                timings[ln] = timings.get(ln, 0) + nl
+
+        greedy_phases = (("greedy_ms", engine.PHASE_GREEDY),
+                         ("rounds_ms", engine.PHASE_GREEDY_ROUNDS),
+                         ("claim_ms", engine.PHASE_CLAIM))
+        for gi, strs in enumerate(input_strs):
+            if len(strs) == 0:
+                continue
+            target_genomes = target_genomes_grouped[gi]
+            ng = len(target_genomes)
+            logger.info("Building set cover sets input (group %d of %d), coverage depth %d",
+                        gi + 1, len(input_strs), self.coverage_depth)
+            k, uniq, owner, ep, eo = probe.anchor_table(
+                strs, self.mismatches, self.lcf_thres,
+                min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
+                assume_unique=assume_unique)
+            held = []
+            try:
+                targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
+                held.append(targets)
+                probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
+                held.append(probes)
+                rows = engine.Rows.scan(ctx, probes, targets, self.mismatches, self.lcf_thres,
+                                        self.island_of_exact_match, self.cover_extension,
+                                        self.scan_mode)
+                held.append(rows)
+                add_phases((("scan_ms", engine.PHASE_SCAN), ("verify_ms", engine.PHASE_VERIFY),
+                            ("rows_ms", engine.PHASE_ROWS)))
+                timings["rows"] += rows.n
+                p = self._make_universe_p(target_genomes)
+                ranks = self._make_ranks_strs(strs, target_genomes_grouped, ctx)
+                rk = ranks if ranks.any() else None
+                ids, sizes = [], []
+                for layer in range(1, self.coverage_depth + 1):
+                    if layer == 1:
+                        table, universe_p = rows, p
+                    else:
+                        table, reached = rows.below_depth(len(strs), ids, layer)
+                        held.append(table)
+                        ms, nl = ctx.kernel_ms(engine.PHASE_ROWS)
+                        timings["depth_ms"] += ms
+                        timings["depth_launches"] = timings.get("depth_launches", 0) + nl
+                        timings["rows_reduced"] += table.n
+                        if table.n == 0:
+                            # (not the end: a base that `layer` picks hold lies below the next layer's depth)
+                            logger.info("Group %d of %d: no candidate is left to raise any base to "
+                                        "depth %d; layer %d is empty", gi + 1, len(input_strs),
+                                        layer, layer)
+                            held.remove(table)
+                            table.close()
+                            sizes.append(0)
+                            continue
+                        n2 = table.stats(ng)[1]
+                        universe_p = [extension_fraction(int(a), int(b), q)
+                                      for a, b, q in zip(n2, reached, p)]
+                    logger.info("Solving the set cover instance of group %d of %d, layer %d of %d",
+                                gi + 1, len(input_strs), layer, self.coverage_depth)
+                    got = table.greedy(len(strs), rk,
+                                       None if all(q == 1.0 for q in universe_p) else universe_p)
+                    add_phases(greedy_phases)
+                    if table is not rows:
+                        held.remove(table)
+                        table.close()
+                    ids += got
+                    sizes.append(len(got))
+                timings["picks"] += len(ids)
+            finally:
+                for h in reversed(held):
+                    h.close()
+            logger.info("Group %d of %d: picks per layer %s", gi + 1, len(input_strs),
+                        " / ".join(str(x) for x in sizes))
+            num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
+            if num_bad > 0:
+                logger.warning(("Group %d: forced to choose %d less-than-ideal "
+                                "probe%s (i.e., probes that 'hit' more than "
+                                "one grouping during identification or probes "
+                                "that cover an avoided genome)"), gi + 1,
+                               num_bad, "" if num_bad == 1 else "s")
+            selected[gi] = list(ids)
+            self.last_layer_sizes[gi] = sizes
         self.last_timings = timings
         return selected
 

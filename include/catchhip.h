@@ -11,6 +11,10 @@
  * unless the comment says "device".  All functions return 0 on success and a
  * negative CATCHHIP_E* code on failure; catchhip_last_error() gives the
  * message for the calling thread.  One host thread per context.
+ * Two entry points build set cover instances the reference cannot state
+ * (catchhip_rows_subtract: beside probes owned already;
+ * catchhip_rows_below_depth: one layer of a design that covers every base
+ * several times); the solvers they feed are the reference's.
  *
  * Coordinates.  A `targets` object is a list of sequences, concatenated in
  * the order given; consecutive sequences with the same genome index form one
@@ -310,6 +314,30 @@ int catchhip_rows_fetch_gain0(catchhip_ctx *ctx, const catchhip_rows *rows,
 int catchhip_rows_subtract(catchhip_ctx *ctx, const catchhip_rows *rows,
                            const catchhip_rows *covered,
                            catchhip_rows **out, int64_t *nrows);
+/* ---- coverage depth: rows below depth k under the picks so far --------------
+ * out = every row of `rows` whose set is not in picks[0..npicks), cut into its
+ * maximal runs of bases b with depth(b) < depth, where depth(b) = the number of
+ * picked sets with a row over b (distinct sets: the rows of a set do not
+ * overlap); set, universe and order kept.  It is the instance of layer `depth`
+ * of a layered greedy that covers every base `depth` times: the sets picked by
+ * the earlier layers are absent, and a base they cover `depth` times already has
+ * left every universe and every other set.  The reference has no counterpart.
+ * `rows`: a row table in the solver's form with set ids in [0, num_sets) (a
+ * merged cover scan, rows_from_host, rows_extend).  The result is sorted and
+ * normalised like `rows` (pieces of a row are at least one base apart),
+ * carries gain0 when `rows` does and its exact longest row: it goes to
+ * catchhip_setcover_greedy as it is.  *nrows (may be NULL) = its row count;
+ * reached[u] (ngenomes values, may be NULL) = the bases of universe u with
+ * depth(b) >= depth.  npicks == 0 gives a copy of `rows`, every set picked an
+ * empty table.  CATCHHIP_EINVAL for depth < 1, a pick outside [0, num_sets) or
+ * given twice, deferred, direct or grouped rows, 2^32 - 1 target bases and
+ * more, 2^31 rows or pieces and more.  Scratch: 4 bytes + 1 bit per target
+ * base.  Timed as phase 1. */
+int catchhip_rows_below_depth(catchhip_ctx *ctx, const catchhip_rows *rows,
+                              int64_t num_sets, const int64_t *picks,
+                              int64_t npicks, int32_t depth,
+                              catchhip_rows **out, int64_t *nrows,
+                              int64_t *reached);
 /* One (probes, targets, mismatches) instance over n_ext cover extensions: the
  * reference's design.py run once per e (set_cover_filter.py:816-846 each time).
  * Scans once at e = 0, derives the rows at each ext[i] (catchhip_rows_extend,
