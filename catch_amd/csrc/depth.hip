@@ -15,7 +15,8 @@
 //                           nothing more; lane 0 stores it and adds its bits to reached[universe]
 //   5. chip_rows_cut        subtract.hip's count, scan and emit over that bitmap, the picked sets left out whole
 //
-// Everything is integer arithmetic.
+// Everything is integer arithmetic.  Steps 1 to 4 are also host calls of their own (chip_depth_marks, chip_depth_array,
+// chip_depth_bitmap; internal.h): catchhip_rows_prune (prune.hip) starts from the same depth array and bitmap.
 #include "internal.h"
 #include "wave.h"
 
@@ -45,7 +46,7 @@ dp_diff_kernel(const i32 *__restrict__ set_id, const u32 *__restrict__ gs, const
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const u32 s = (u32)set_id[r];
-    if (s >= num_sets || !picked[s]) return;
+    if (picked && (s >= num_sets || !picked[s])) return;     // (picked == null: every row counts)
     const u32 a = gs[r], b = ge[r];
     if (b <= a) return;
     atomicAdd(&d[a], 1u);
@@ -54,7 +55,8 @@ dp_diff_kernel(const i32 *__restrict__ set_id, const u32 *__restrict__ gs, const
 
 // d[b + 1] = depth of base b.  Wavefront v takes the words [v * DP_WORDS, (v + 1) * DP_WORDS) of the bitmap, lowest
 // first: bit b of bm = depth(b) >= k.  Lane 0 keeps the universe the walk is in and the bits it counted there, and
-// adds them to reached[] when the walk leaves the universe (boundaries are not word-aligned) and at the end.
+// adds them to reached[] (may be null: nobody counts) when the walk leaves the universe (boundaries are not
+// word-aligned) and at the end.
 __global__ void __launch_bounds__(256)
 dp_threshold_kernel(const u32 *__restrict__ d, u32 total, u32 k, const u32 *__restrict__ genome_off, u32 ng,
                     unsigned long long *__restrict__ bm, unsigned long long *__restrict__ reached) {
@@ -88,7 +90,7 @@ dp_threshold_kernel(const u32 *__restrict__ d, u32 total, u32 k, const u32 *__re
                 acc += (u32)__popcll(rest & m);
                 rest &= ~m;
                 if (rest) {                                 // on to the next universe
-                    if (acc) atomicAdd(&reached[u], acc);
+                    if (acc && reached) atomicAdd(&reached[u], acc);
                     acc = 0;
                     ++u;
                     uend = genome_off[u + 1];
@@ -96,7 +98,96 @@ dp_threshold_kernel(const u32 *__restrict__ d, u32 total, u32 k, const u32 *__re
             }
         }
     }
-    if (lane == 0 && acc) atomicAdd(&reached[u], acc);
+    if (lane == 0 && acc && reached) atomicAdd(&reached[u], acc);
+}
+
+// ---- the three steps above as host calls (internal.h), for catchhip_rows_below_depth and catchhip_rows_prune ----------
+// picked[set] = 1 for the sets of picks[0..npicks) (npicks > 0), as bytes; d_picks = the picks on the device
+int chip_depth_marks(catchhip_ctx *ctx, const i64 *picks, i64 npicks, i64 num_sets, DevBuf<i64> &d_picks,
+                     DevBuf<u8> &picked, PhaseTimer &tm, const char *who) {
+    hipStream_t s = ctx->stream;
+    DevBuf<u32> picked32, flag;
+    TRY(d_picks.alloc((size_t)npicks));
+    TRY(picked32.alloc((size_t)num_sets));
+    TRY(picked.alloc((size_t)num_sets));
+    TRY(flag.alloc(1));
+    HIP_TRY(hipMemcpyAsync(d_picks.p, picks, sizeof(i64) * (size_t)npicks, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(picked32.p, 0, sizeof(u32) * (size_t)num_sets, s));
+    HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(u32), s));
+    hipLaunchKernelGGL(dp_mark_kernel, dim3((unsigned)div_up(npicks, 256)), dim3(256), 0, s, (const i64 *)d_picks.p,
+                       (u32)npicks, num_sets, picked32.p, flag.p);
+    hipLaunchKernelGGL(dp_pack_kernel, dim3((unsigned)div_up(num_sets, 256)), dim3(256), 0, s,
+                       (const u32 *)picked32.p, (u32)num_sets, picked.p);
+    tm.launch(2);
+    HIP_TRY(hipGetLastError());
+    u32 h_flag = 0;
+    TRY(read_count(ctx, flag.p, &h_flag));                   // (also: the pageable picks[] has been read)
+    if (h_flag) {
+        chip_set_error("%s: a pick %s", who, (h_flag & 1u) ? "lies outside the set ids" : "is given twice");
+        return CATCHHIP_EINVAL;
+    }
+    return 0;
+}
+
+// d[b + 1] = the picked rows of R0 over base b, plus the rows of F (may be null: none) over it; total + 2 entries
+int chip_depth_array(catchhip_ctx *ctx, const catchhip_rows *R0, const u8 *picked, u32 num_sets, const catchhip_rows *F,
+                     DevBuf<u32> &d, DevBuf<u32> &tmp, PhaseTimer &tm) {
+    hipStream_t s = ctx->stream;
+    const u64 total = (u64)R0->total;
+    TRY(d.alloc(total + 2));
+    TRY(chip_exclusive_scan_reserve(tmp, (i64)total + 1));
+    HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(u32) * (total + 2), s));
+    if (R0->n) {
+        hipLaunchKernelGGL(dp_diff_kernel, dim3((unsigned)div_up(R0->n, 256)), dim3(256), 0, s,
+                           (const i32 *)R0->set_id.p, (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, (u32)R0->n, picked,
+                           num_sets, d.p);
+        tm.launch(1);
+    }
+    if (F && F->n) {
+        hipLaunchKernelGGL(dp_diff_kernel, dim3((unsigned)div_up(F->n, 256)), dim3(256), 0, s,
+                           (const i32 *)F->set_id.p, (const u32 *)F->gs.p, (const u32 *)F->ge.p, (u32)F->n,
+                           (const u8 *)nullptr, 0u, d.p);
+        tm.launch(1);
+    }
+    TRY(chip_exclusive_scan_u32(ctx, d.p, d.p, (i64)total + 1, tmp));
+    tm.launch(1);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// bit b of bm (zeroed by the caller) = d[b + 1] >= k; reached[u] (device, zeroed by the caller; may be null) += the
+// bits of universe u
+int chip_depth_bitmap(catchhip_ctx *ctx, const u32 *d, u64 total, u32 k, const u32 *genome_off, u32 ng,
+                      unsigned long long *bm, unsigned long long *reached, PhaseTimer &tm) {
+    const u64 nwaves = div_up((i64)div_up((i64)total, 64), DP_WORDS);
+    hipLaunchKernelGGL(dp_threshold_kernel, dim3((unsigned)div_up((i64)nwaves, 256 / WAVE)), dim3(256), 0, ctx->stream,
+                       d, (u32)total, k, genome_off, ng, bm, reached);
+    tm.launch(1);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the refusals catchhip_rows_below_depth and catchhip_rows_prune share (R0 passed ARG_CHECK)
+int chip_depth_check(const catchhip_rows *R0, i64 num_sets, i64 npicks, i32 depth, const char *who) {
+    if (depth < 1) {
+        chip_set_error("%s: depth %d; the smallest depth is 1", who, (int)depth);
+        return CATCHHIP_EINVAL;
+    }
+    TRY(chip_rows_cut_check(R0, who, "the rows"));
+    if (R0->total >= ((i64)1 << 32) - 1) {
+        chip_set_error("%s: more than 2^32 - 2 target bases", who);
+        return CATCHHIP_EINVAL;
+    }
+    if (R0->n >= ((i64)1 << 31)) {
+        chip_set_error("%s: too many rows", who);
+        return CATCHHIP_EINVAL;
+    }
+    if (npicks > num_sets) {
+        chip_set_error("%s: %lld picks of %lld sets (an id is repeated or out of range)", who,
+                       (long long)npicks, (long long)num_sets);
+        return CATCHHIP_EINVAL;
+    }
+    return 0;
 }
 
 extern "C" int catchhip_rows_below_depth(catchhip_ctx *ctx, const catchhip_rows *R0, i64 num_sets, const i64 *picks,
@@ -106,24 +197,7 @@ extern "C" int catchhip_rows_below_depth(catchhip_ctx *ctx, const catchhip_rows 
     *out = nullptr;
     if (nrows) *nrows = 0;
     ARG_CHECK(num_sets >= 0 && num_sets < ((i64)1 << 31) && npicks >= 0 && (npicks == 0 || picks));
-    if (depth < 1) {
-        chip_set_error("rows_below_depth: depth %d; the smallest depth is 1", (int)depth);
-        return CATCHHIP_EINVAL;
-    }
-    TRY(chip_rows_cut_check(R0, "rows_below_depth", "the rows"));
-    if (R0->total >= ((i64)1 << 32) - 1) {
-        chip_set_error("rows_below_depth: more than 2^32 - 2 target bases");
-        return CATCHHIP_EINVAL;
-    }
-    if (R0->n >= ((i64)1 << 31)) {
-        chip_set_error("rows_below_depth: too many rows");
-        return CATCHHIP_EINVAL;
-    }
-    if (npicks > num_sets) {
-        chip_set_error("rows_below_depth: %lld picks of %lld sets (an id is repeated or out of range)",
-                       (long long)npicks, (long long)num_sets);
-        return CATCHHIP_EINVAL;
-    }
+    TRY(chip_depth_check(R0, num_sets, npicks, depth, "rows_below_depth"));
     const i32 ng = R0->ngenomes;
     if (reached) for (i32 u = 0; u < ng; ++u) reached[u] = 0;
     PoolScope pool_scope(ctx);
@@ -143,27 +217,8 @@ extern "C" int catchhip_rows_below_depth(catchhip_ctx *ctx, const catchhip_rows 
     }
     // the picked sets
     DevBuf<i64> d_picks;
-    DevBuf<u32> picked32, flag;
     DevBuf<u8> picked;
-    TRY(d_picks.alloc((size_t)npicks));
-    TRY(picked32.alloc((size_t)num_sets));
-    TRY(picked.alloc((size_t)num_sets));
-    TRY(flag.alloc(1));
-    HIP_TRY(hipMemcpyAsync(d_picks.p, picks, sizeof(i64) * (size_t)npicks, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(picked32.p, 0, sizeof(u32) * (size_t)num_sets, s));
-    HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(u32), s));
-    hipLaunchKernelGGL(dp_mark_kernel, dim3((unsigned)div_up(npicks, 256)), dim3(256), 0, s, (const i64 *)d_picks.p,
-                       (u32)npicks, num_sets, picked32.p, flag.p);
-    hipLaunchKernelGGL(dp_pack_kernel, dim3((unsigned)div_up(num_sets, 256)), dim3(256), 0, s,
-                       (const u32 *)picked32.p, (u32)num_sets, picked.p);
-    tm.launch(2);
-    HIP_TRY(hipGetLastError());
-    u32 h_flag = 0;
-    TRY(read_count(ctx, flag.p, &h_flag));                   // (also: the pageable picks[] has been read)
-    if (h_flag) {
-        chip_set_error("rows_below_depth: a pick %s", (h_flag & 1u) ? "lies outside the set ids" : "is given twice");
-        return CATCHHIP_EINVAL;
-    }
+    TRY(chip_depth_marks(ctx, picks, npicks, num_sets, d_picks, picked, tm, "rows_below_depth"));
     // depth per base -> the bitmap of bases at depth >= `depth`, and their number per universe
     const u64 total = (u64)R0->total;
     const size_t nwords = (size_t)(total / 64 + 2) + 8;
@@ -174,19 +229,9 @@ extern "C" int catchhip_rows_below_depth(catchhip_ctx *ctx, const catchhip_rows 
     HIP_TRY(hipMemsetAsync(d_reached.p, 0, sizeof(unsigned long long) * (size_t)(ng ? ng : 1), s));
     if (R0->n && total && ng > 0) {
         DevBuf<u32> d, tmp;
-        TRY(d.alloc(total + 2));
-        TRY(chip_exclusive_scan_reserve(tmp, (i64)total + 1));
-        HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(u32) * (total + 2), s));
-        hipLaunchKernelGGL(dp_diff_kernel, dim3((unsigned)div_up(R0->n, 256)), dim3(256), 0, s,
-                           (const i32 *)R0->set_id.p, (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, (u32)R0->n,
-                           (const u8 *)picked.p, (u32)num_sets, d.p);
-        TRY(chip_exclusive_scan_u32(ctx, d.p, d.p, (i64)total + 1, tmp));
-        const u64 nwaves = div_up((i64)div_up((i64)total, 64), DP_WORDS);
-        hipLaunchKernelGGL(dp_threshold_kernel, dim3((unsigned)div_up((i64)nwaves, 256 / WAVE)), dim3(256), 0, s,
-                           (const u32 *)d.p, (u32)total, (u32)depth, (const u32 *)R0->genome_off.p, (u32)ng, bm.p,
-                           d_reached.p);
-        tm.launch(3);
-        HIP_TRY(hipGetLastError());
+        TRY(chip_depth_array(ctx, R0, (const u8 *)picked.p, (u32)num_sets, nullptr, d, tmp, tm));
+        TRY(chip_depth_bitmap(ctx, (const u32 *)d.p, total, (u32)depth, (const u32 *)R0->genome_off.p, (u32)ng, bm.p,
+                              d_reached.p, tm));
         TRY(chip_rows_cut(ctx, R0, (const unsigned long long *)bm.p, (const u8 *)picked.p, (u32)num_sets, R.get(), tm,
                           "rows_below_depth"));
     }

@@ -419,6 +419,23 @@ int chip_rows_copy(catchhip_ctx *ctx, const catchhip_rows *R0, catchhip_rows *R)
 int chip_rows_cut(catchhip_ctx *ctx, const catchhip_rows *R0, const unsigned long long *bm, const u8 *skip, u32 nskip,
                   catchhip_rows *R, PhaseTimer &tm, const char *who);
 
+// ---- depth per base from a pick list (depth.hip; catchhip_rows_below_depth and catchhip_rows_prune) -------------
+// the refusals the two share: depth < 1, rows chip_rows_cut_check refuses, 2^32 - 1 bases and more, 2^31 rows and
+// more, more picks than sets
+int chip_depth_check(const catchhip_rows *R0, i64 num_sets, i64 npicks, i32 depth, const char *who);
+// picked[set] = 1 (bytes, num_sets of them) for the sets of the host array picks[0..npicks), npicks > 0; d_picks = the
+// picks on the device.  CATCHHIP_EINVAL ("<who>: a pick ...") for an id outside [0, num_sets) or given twice.
+int chip_depth_marks(catchhip_ctx *ctx, const i64 *picks, i64 npicks, i64 num_sets, DevBuf<i64> &d_picks,
+                     DevBuf<u8> &picked, PhaseTimer &tm, const char *who);
+// d[b + 1] = depth of base b = the rows of R0's picked sets over it, plus the rows of F over it (F may be null;
+// otherwise any table over R0's coordinate space, every row counts).  d gets total + 2 entries; tmp = the scan's scratch.
+int chip_depth_array(catchhip_ctx *ctx, const catchhip_rows *R0, const u8 *picked, u32 num_sets, const catchhip_rows *F,
+                     DevBuf<u32> &d, DevBuf<u32> &tmp, PhaseTimer &tm);
+// bit b of bm = d[b + 1] >= k (bm: total / 64 + 1 words at least, zeroed by the caller); reached[u] (device, zeroed
+// by the caller; may be null) += the bits of universe u
+int chip_depth_bitmap(catchhip_ctx *ctx, const u32 *d, u64 total, u32 k, const u32 *genome_off, u32 ng,
+                      unsigned long long *bm, unsigned long long *reached, PhaseTimer &tm);
+
 // ---- device primitives (primitives.hip) ---------------------------------
 // exclusive prefix sum of n u32 values (in place allowed: out may equal in);
 // if total != nullptr, *total (device u64) receives the grand total.

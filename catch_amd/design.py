@@ -17,7 +17,8 @@ download: labels are not offered.  --extend-probes (no counterpart in the
 reference) keeps an existing probe set and designs only the probes that bring
 the targets up to the required coverage next to it; --coverage-depth D (no
 counterpart either) designs a set in which D probes cover every base, one
-greedy layer per unit of depth.  --print-analysis and the
+greedy layer per unit of depth; --prune-redundant (nor this) drops the selected
+probes that cover nothing alone.  --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
 """
@@ -140,6 +141,16 @@ def parse_args(argv=None, args_type="basic"):
                         "what the layers before it leave below its depth; the "
                         "output lists the probes layer by layer, and its "
                         "first k layers are the design at depth k")
+    p.add_argument("--prune-redundant", action="store_true",
+                   help="look back at the selected probes once the set cover "
+                        "is complete, from the last pick to the first, and "
+                        "drop each one whose bases are all covered often "
+                        "enough without it (more than --coverage-depth times "
+                        "with it); the bases covered stay the same, the output "
+                        "holds the probes kept; with --extend-probes the "
+                        "existing probes count and stay; with --coverage-depth "
+                        "above 1 the first k layers are no longer the design "
+                        "at depth k")
     p.add_argument("--add-adapters", action="store_true",
                    help="add PCR adapters to both ends of every probe")
     p.add_argument("--adapter-a", nargs=2,
@@ -214,6 +225,23 @@ def main(args):
                              "it is set, --cluster-from-fragments to 0 too)"))
         if args.cluster_from_fragments:
             raise Exception(("Cannot use --coverage-depth above 1 with "
+                             "--cluster-from-fragments (a default of "
+                             "design_large.py): nothing is clustered; set "
+                             "--cluster-from-fragments to 0 as well"))
+    if args.prune_redundant:
+        if args.skip_set_cover:
+            raise Exception(("Cannot use --prune-redundant with "
+                             "--skip-set-cover: it is the set cover's picks "
+                             "that are looked at again"))
+        if args.cluster_and_design_separately:
+            raise Exception(("Cannot use --prune-redundant with "
+                             "--cluster-and-design-separately (a default of "
+                             "design_large.py): the picks are set against each "
+                             "dataset as a whole; set "
+                             "--cluster-and-design-separately to 0 (and, where "
+                             "it is set, --cluster-from-fragments to 0 too)"))
+        if args.cluster_from_fragments:
+            raise Exception(("Cannot use --prune-redundant with "
                              "--cluster-from-fragments (a default of "
                              "design_large.py): nothing is clustered; set "
                              "--cluster-from-fragments to 0 as well"))
@@ -311,7 +339,8 @@ def main(args):
         identify=args.identify, avoided_genomes=args.avoid_genomes,
         coverage=args.coverage, cover_extension=args.cover_extension,
         kmer_probe_map_k=k_scf, fixed_probes=existing_probes,
-        coverage_depth=args.coverage_depth)
+        coverage_depth=args.coverage_depth,
+        prune_redundant=args.prune_redundant)
     filters.append(scf)
     if args.add_adapters:      # bin/design.py:345-365 (default sequences :350, :354)
         from catch_amd.filter import adapter_filter
@@ -353,6 +382,9 @@ def main(args):
             logger.info("%s: %s probes in the layers of depth 1 to %d",
                         os.path.basename(fn), " / ".join(str(x) for x in sizes),
                         len(sizes))
+    if args.prune_redundant:
+        for fn, sizes, gone in zip(args.dataset, scf.last_layer_sizes, scf.last_pruned):
+            logger.info("%s: %d picked, %d redundant", os.path.basename(fn), sum(sizes), len(gone))
     if args.write_probe_fasta:
         seq_io.write_probe_fasta(pb.final_probes, args.write_probe_fasta)
     if (args.print_analysis or args.write_analysis_to_tsv or

@@ -647,6 +647,7 @@ class Rows:
         self._h = handle
         self.n = int(n)
         self.ngenomes = ngenomes      # universes of the coordinate space (None: the maker did not say)
+        self.last_prune_rounds = 0    # rounds the device took in the last prune() of these rows
 
     @staticmethod
     def scan(ctx, probes, targets, mismatches, lcf_thres, island=0,
@@ -809,6 +810,26 @@ class Rows:
             self.ctx._h, self._h, int(num_sets), _ptr(pk, c_i64p) if pk.size else None,
             int(pk.size), int(depth), ctypes.byref(h), ctypes.byref(n), _ptr(reached, c_i64p)))
         return Rows(self.ctx, h, n.value, ng), reached[:ng]
+
+    def prune(self, num_sets, picks, depth=1, fixed=None):
+        """catchhip_rows_prune -> (kept, removed): the picks (set ids in pick
+        order) examined from the last to the first, one removed whenever every
+        base of its rows is covered by more than `depth` of the remaining picks
+        and the rows of `fixed` (Rows over the same universes, or None).  kept
+        is in pick order, removed in examination order.  The rounds the device
+        took are left in `last_prune_rounds`."""
+        pk = np.ascontiguousarray(picks, dtype=np.int64)
+        flags = np.zeros(max(int(pk.size), 1), dtype=np.uint8)
+        nrem = ctypes.c_int64(0)
+        rounds = ctypes.c_int64(0)
+        check(self.ctx._L.catchhip_rows_prune(
+            self.ctx._h, self._h, None if fixed is None else fixed._h, int(num_sets),
+            _ptr(pk, c_i64p) if pk.size else None, int(pk.size), int(depth),
+            _ptr(flags, c_u8p), ctypes.byref(nrem), ctypes.byref(rounds)))
+        gone = flags[:pk.size] != 0
+        assert int(gone.sum()) == nrem.value
+        self.last_prune_rounds = int(rounds.value)
+        return pk[~gone].tolist(), pk[gone][::-1].tolist()
 
     def fetch_gain0(self, num_sets):
         """catchhip_rows_fetch_gain0 -> uint32[min(num_sets, held)] (None: the rows hold no gain0)."""

@@ -280,6 +280,8 @@ class ProbeDesigner:
             return None                  # extending a probe set: the host front end (SetCoverFilter._filter_strs_extend)
         if getattr(scf, "coverage_depth", 1) > 1:
             return None                  # layers of a coverage depth: the host front end (SetCoverFilter._filter_strs_depth)
+        if getattr(scf, "prune_redundant", False):
+            return None                  # pruning needs the group's rows: the host front end, as for a coverage depth
         skip, L = self.seq_length_to_skip, self.probe_length
         total, ngroups = 0, 0
         if isinstance(genomes, ClusteredFragments):

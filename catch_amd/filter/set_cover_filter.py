@@ -11,7 +11,9 @@ Beyond the reference: `fixed_probes` (a trailing keyword) names probes the user
 owns already; the filter then selects only what they leave uncovered
 (_filter_strs_extend).  `coverage_depth` (after it) asks for every base to be
 covered by that many selected probes, one greedy layer per unit of depth
-(_filter_strs_depth).
+(_filter_strs_depth).  `prune_redundant` (a keyword too) looks back at the picks
+once the design is complete and drops those that cover nothing alone
+(engine.Rows.prune).
 
 Not supported (raises NotImplementedError): custom hybridization functions
 loaded from a Python file (`custom_cover_range_fn`, :288-299) -- an arbitrary
@@ -49,15 +51,17 @@ def _reverse_complement(s):
 
 
 class _KeywordsBeyondInit(type):
-    """SetCoverFilter(..., fixed_probes=None, coverage_depth=1): `coverage_depth`
-    is a keyword of the CALL of the class, taken here and handed to the new
-    object after __init__ ran.  __init__ itself stays the reference's argument
-    list followed by `fixed_probes`, the form its callers and the signature
-    checks of the extension know; `coverage_depth` can only be given by name."""
+    """SetCoverFilter(..., fixed_probes=None, coverage_depth=1,
+    prune_redundant=False): `coverage_depth` and `prune_redundant` are keywords
+    of the CALL of the class, taken here and handed to the new object after
+    __init__ ran.  __init__ itself stays the reference's argument list followed
+    by `fixed_probes`, the form its callers and the signature checks of the
+    extension know; the two can only be given by name."""
 
-    def __call__(cls, *args, coverage_depth=1, **kwargs):
+    def __call__(cls, *args, coverage_depth=1, prune_redundant=False, **kwargs):
         obj = super().__call__(*args, **kwargs)
         obj._set_coverage_depth(coverage_depth)
+        obj._set_prune_redundant(prune_redundant)
         return obj
 
 
@@ -130,6 +134,19 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                              for q in (fixed_probes if fixed_probes is not None else ())]
         self.coverage_depth = 1     # (SetCoverFilter(..., coverage_depth=D) sets it: _KeywordsBeyondInit)
         self.last_layer_sizes = []
+        self.prune_redundant = False   # (SetCoverFilter(..., prune_redundant=True) sets it: _KeywordsBeyondInit)
+        self.last_pruned = []
+
+    def _set_prune_redundant(self, prune_redundant):
+        """Whether the picks are looked at again once the design is complete (not
+        an argument of the reference's class): from the last pick to the first,
+        one is dropped when every base it covers is covered more than
+        coverage_depth times without it (by the other picks and the fixed
+        probes).  The bases covered stay the same; last_pruned[group] holds the
+        dropped candidates in the order they were dropped."""
+        if not isinstance(prune_redundant, (bool, np.bool_)):
+            raise ValueError("prune_redundant must be True or False, not %r" % (prune_redundant,))
+        self.prune_redundant = bool(prune_redundant)
 
     def _set_coverage_depth(self, coverage_depth):
         """How many selected probes are to cover every base (not an argument of
@@ -271,7 +288,8 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         if self.fixed_probes:
             return self._filter_strs_extend(input_strs, target_genomes_grouped,
                                             assume_unique)
-        if self.coverage_depth > 1:
+        if self.coverage_depth > 1 or self.prune_redundant:
+            # (pruning needs the group's rows: the layered path keeps them, at depth 1 too)
             return self._filter_strs_depth(input_strs, target_genomes_grouped,
                                            assume_unique)
         if only is None and parallel.world().size > 1:
@@ -385,9 +403,14 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                 "fixed probes (extending an existing probe set) run on one rank")
         ctx = self._context()
         selected = [[] for _ in input_strs]
+        self.last_pruned = [[] for _ in input_strs]
+        if self.prune_redundant:
+            self.last_layer_sizes = [[] for _ in input_strs]     # (one layer: what the extension's solve picked)
         timings = dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0, rows=0,
                        scan_launches=0, greedy_launches=0, fixed_scan_ms=0.0,
                        subtract_ms=0.0, rows_fixed=0, rows_reduced=0)
+        if self.prune_redundant:
+            timings.update(prune_ms=0.0, prune_launches=0, prune_rounds=0, pruned=0)
 
         def add_phases(names):
             for name, ph in names:
@@ -448,6 +471,10 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                 timings["rows"] += rows.n
                 timings["rows_fixed"] += frows.n
                 timings["rows_reduced"] += reduced.n
+                if self.prune_redundant:
+                    # the new probes beside the fixed ones, which stay whatever happens
+                    self.last_layer_sizes[gi] = [len(ids)]
+                    ids, self.last_pruned[gi] = _prune(ctx, rows, len(strs), ids, 1, frows, timings)
                 timings["picks"] += len(ids)
             finally:
                 for h in reversed(held):
@@ -465,7 +492,8 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
 
     def _filter_strs_depth(self, input_strs, target_genomes_grouped,
                            assume_unique=False):
-        """_filter_strs with coverage_depth = D > 1: per group the candidates of
+        """_filter_strs with coverage_depth = D > 1 (or D = 1 with
+        prune_redundant, which needs the rows): per group the candidates of
         D greedy layers, in layer order and then pick order.  depth(b) = the
         number of candidates picked so far with a cover row over base b.  Layer
         1 is the ordinary instance (the scanned rows, the user's fractions).
@@ -476,16 +504,23 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         n2[u] bases the solver sees).  The solvers run unchanged, with the same
         ranks in every layer; the first k layers are the design at depth k.  A
         layer with no row left is empty and logged.  One group after the other
-        on one context, in input order, one scan per group."""
+        on one context, in input order, one scan per group.  With
+        prune_redundant the picks of all layers go through Rows.prune at depth D
+        after the last layer (the nesting of the layers is lost: a pick of layer
+        1 may be dropped for picks of layer 2); last_layer_sizes stays what the
+        layers picked, last_pruned[group] the dropped ones."""
         from catch_amd import parallel
         if parallel.world().size > 1:
-            raise NotImplementedError("coverage_depth > 1 runs on one rank")
+            raise NotImplementedError("coverage_depth > 1 and prune_redundant run on one rank")
         ctx = self._context()
         selected = [[] for _ in input_strs]
         self.last_layer_sizes = [[] for _ in input_strs]
+        self.last_pruned = [[] for _ in input_strs]
         timings = dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0, rows=0,
                        scan_launches=0, greedy_launches=0, depth_ms=0.0,
                        rows_reduced=0)
+        if self.prune_redundant:
+            timings.update(prune_ms=0.0, prune_launches=0, prune_rounds=0, pruned=0)
 
         def add_phases(names):
             for name, ph in names:
@@ -557,12 +592,18 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                         table.close()
                     ids += got
                     sizes.append(len(got))
+                if self.prune_redundant:
+                    ids, self.last_pruned[gi] = _prune(ctx, rows, len(strs), ids, self.coverage_depth, None,
+                                                       timings)
                 timings["picks"] += len(ids)
             finally:
                 for h in reversed(held):
                     h.close()
             logger.info("Group %d of %d: picks per layer %s", gi + 1, len(input_strs),
                         " / ".join(str(x) for x in sizes))
+            if self.prune_redundant:
+                logger.info("Group %d of %d: %d picked, %d redundant", gi + 1, len(input_strs),
+                            sum(sizes), len(self.last_pruned[gi]))
             num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
             if num_bad > 0:
                 logger.warning(("Group %d: forced to choose %d less-than-ideal "
@@ -574,6 +615,51 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
             self.last_layer_sizes[gi] = sizes
         self.last_timings = timings
         return selected
+
+    def prune_probe_strs(self, probe_strs, target_genomes):
+        """Which probes of an existing list can go without uncovering a base?
+        Every string is a set of its own (equal strings too) and every one is
+        picked, in the order given; one scan against `target_genomes` (one
+        universe each) under this filter's hybridization model and cover
+        extension, then Rows.prune at coverage_depth.  Returns (indices kept, in
+        the order given; indices dropped, last examined last): the last strings
+        are examined first.  `coverage` plays no part: no base that the list
+        covers coverage_depth times (or as often as it can) is lost."""
+        from catch_amd import parallel
+        if parallel.world().size > 1:
+            raise NotImplementedError("pruning a probe list runs on one rank")
+        probe_strs = list(probe_strs)
+        timings = dict(scan_ms=0.0, rows_ms=0.0, rows=0, picks=0, prune_ms=0.0,
+                       prune_launches=0, prune_rounds=0, pruned=0)
+        if not probe_strs:
+            self.last_timings = timings
+            return [], []
+        ctx = self._context()
+        k, uniq, owner, ep, eo = probe.anchor_table(
+            probe_strs, self.mismatches, self.lcf_thres,
+            min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
+            assume_unique=True)
+        held = []
+        try:
+            targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
+            held.append(targets)
+            probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
+            held.append(probes)
+            rows = engine.Rows.scan(ctx, probes, targets, self.mismatches, self.lcf_thres,
+                                    self.island_of_exact_match, self.cover_extension,
+                                    self.scan_mode)
+            held.append(rows)
+            timings["scan_ms"] = ctx.kernel_ms(engine.PHASE_SCAN)[0]
+            timings["rows_ms"] = ctx.kernel_ms(engine.PHASE_ROWS)[0]
+            timings["rows"] = rows.n
+            kept, removed = _prune(ctx, rows, len(probe_strs), list(range(len(probe_strs))),
+                                   self.coverage_depth, None, timings)
+            timings["picks"] = len(kept)
+        finally:
+            for h in reversed(held):
+                h.close()
+        self.last_timings = timings
+        return kept, removed
 
     def _anchor_tables_in_input_order(self, input_strs, nonempty, assume_unique):
         """{group: anchor table} for all non-empty groups, drawn in input order,
@@ -1341,6 +1427,19 @@ def extension_fraction(n2, covered, p):
     if can >= n2:
         return 0.0
     return (n2 - can - 0.5) / n2
+
+
+def _prune(ctx, rows, num_sets, ids, depth, fixed_rows, timings):
+    """Rows.prune of a group's picks (SetCoverFilter(prune_redundant=True)) ->
+    (the picks kept, the picks dropped); its device time, launches and rounds
+    and the number dropped are added to `timings`."""
+    kept, removed = rows.prune(num_sets, ids, depth, fixed_rows)
+    ms, nl = ctx.kernel_ms(engine.PHASE_ROWS) if len(ids) else (0.0, 0)
+    timings["prune_ms"] = timings.get("prune_ms", 0.0) + ms
+    timings["prune_launches"] = timings.get("prune_launches", 0) + nl
+    timings["prune_rounds"] = timings.get("prune_rounds", 0) + rows.last_prune_rounds
+    timings["pruned"] = timings.get("pruned", 0) + len(removed)
+    return kept, removed
 
 
 def _lpt(costs, nbins):

@@ -14,7 +14,8 @@
  * Two entry points build set cover instances the reference cannot state
  * (catchhip_rows_subtract: beside probes owned already;
  * catchhip_rows_below_depth: one layer of a design that covers every base
- * several times); the solvers they feed are the reference's.
+ * several times); the solvers they feed are the reference's.  A third,
+ * catchhip_rows_prune, takes picks away again: those that cover nothing alone.
  *
  * Coordinates.  A `targets` object is a list of sequences, concatenated in
  * the order given; consecutive sequences with the same genome index form one
@@ -338,6 +339,33 @@ int catchhip_rows_below_depth(catchhip_ctx *ctx, const catchhip_rows *rows,
                               int64_t npicks, int32_t depth,
                               catchhip_rows **out, int64_t *nrows,
                               int64_t *reached);
+/* ---- pruning: the picks that cover nothing alone ---------------------------
+ * Which of picks[0..npicks) (set ids in pick order) can leave without any base
+ * falling below `depth`?  depth(b) = the picked sets with a row of `rows` over
+ * b plus the rows of `fixed` over b (`fixed`: NULL, or any row table over the
+ * same coordinate space -- probes that stay whatever happens; every one of its
+ * rows counts).  The picks are examined from the last picked to the first; a
+ * pick is removed if at its turn every base of every one of its rows has
+ * depth >= depth + 1, and its removal lowers the depth of its bases by 1
+ * before the next pick is examined.  min(depth(b), depth) is the same before
+ * and after for every base, and no pick that stays is removable afterwards.
+ * The device reproduces this walk exactly, in parallel rounds, with integer
+ * arithmetic only: the result does not depend on launch geometry or on the
+ * order of atomics.  removed_flags[i] (npicks bytes) = 1 if picks[i] was
+ * removed; *nremoved their number; *rounds the rounds the device took (a
+ * final one-workgroup walk counts as one).  The latter two may be NULL.  A
+ * pick without rows is removed.  The reference has no counterpart.  `rows`: a
+ * row table in the solver's form with set ids in [0, num_sets).  npicks == 0
+ * returns at once.  CATCHHIP_EINVAL as catchhip_rows_below_depth: depth < 1, a
+ * pick outside [0, num_sets) or given twice, deferred, direct or grouped rows
+ * (either table), 2^32 - 1 target bases and more; and for a `fixed` table of
+ * another context or coordinate space.  Scratch: 12 bytes + 1 bit per target
+ * base.  Timed as phase 1. */
+int catchhip_rows_prune(catchhip_ctx *ctx, const catchhip_rows *rows,
+                        const catchhip_rows *fixed, int64_t num_sets,
+                        const int64_t *picks, int64_t npicks, int32_t depth,
+                        uint8_t *removed_flags, int64_t *nremoved,
+                        int64_t *rounds);
 /* One (probes, targets, mismatches) instance over n_ext cover extensions: the
  * reference's design.py run once per e (set_cover_filter.py:816-846 each time).
  * Scans once at e = 0, derives the rows at each ext[i] (catchhip_rows_extend,
