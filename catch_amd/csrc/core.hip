@@ -313,6 +313,12 @@ extern "C" int catchhip_ctx_last_solver_counters(catchhip_ctx *c, i64 *out4) {
     return 0;
 }
 
+extern "C" int catchhip_ctx_last_solver_levels(catchhip_ctx *c, i64 *out2) {
+    ARG_CHECK(c != nullptr && out2 != nullptr);
+    for (int i = 0; i < 2; ++i) out2[i] = c->solver_levels[i];
+    return 0;
+}
+
 extern "C" int catchhip_ctx_last_ndf_counters(catchhip_ctx *c, i64 *out4) {
     ARG_CHECK(c != nullptr && out4 != nullptr);
     for (int i = 0; i < 4; ++i) out4[i] = c->ndf_counters[i];

@@ -130,6 +130,7 @@ struct catchhip_ctx {
     i64 phase_launches[NPHASE] = {};
     i64 counters[8] = {};
     i64 ndf_counters[4] = {};      // last Hamming near-duplicate filter: probes, tables, pairs compared, edges
+    i64 solver_levels[2] = {};     // row-parallel solver: gain levels gone through, bands (setcover_flat.inc)
     i64 solver_counters[4] = {};   // row-parallel solver: records streamed, rows counted again, bitmap words read, owner words looked at
     i64 rows_direct = 0;     // the last catchhip_setcover_filter solved from the bucketed records (catchhip_rows::rows4), no SoA table
     i64 seeds_dropped = 0;   // of counters[1]: work-list entries the seed look-up's anchor-pair filter left empty

@@ -2616,6 +2616,16 @@ extern "C" int catchhip_rows_from_host(catchhip_ctx *ctx, const i32 *set_id, con
         HIP_TRY(hipMemcpyAsync(R->gs.p, gs.data(), sizeof(u32) * nrows, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(R->ge.p, ge.data(), sizeof(u32) * nrows, hipMemcpyHostToDevice, s));
     }
+    // the sets' total row lengths, as a scan's row build leaves them (a set's rows are disjoint): the first round's gains
+    // of a full-coverage solve, and what the row-parallel solver cuts its gain bands by
+    std::vector<u32> g0;
+    if (nrows) {
+        g0.assign((size_t)set_id[nrows - 1] + 1, 0u);
+        for (i64 i = 0; i < nrows; ++i) g0[(size_t)set_id[i]] += ge[i] - gs[i];
+        TRY(R->gain0.alloc(g0.size()));
+        HIP_TRY(hipMemcpyAsync(R->gain0.p, g0.data(), sizeof(u32) * g0.size(), hipMemcpyHostToDevice, s));
+        R->gain0_n = (u32)g0.size();
+    }
     HIP_TRY(hipMemcpyAsync(R->genome_off.p, go.data(), sizeof(u32) * (ngenomes + 1), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
     *out = R.release();

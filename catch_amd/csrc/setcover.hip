@@ -55,6 +55,8 @@ struct GreedyState {
     unsigned long long n_wrows, n_recount, n_words;  // work counters
     u32 need_live, ticket;   // row-parallel solver, partial coverage: universes still in need (being counted) / workgroups done
     u32 nwon;                // row-parallel solver, full coverage: npicks when this round began -- the sets accepted in it are picks[nwon .. npicks)
+    u32 level[2];            // row-parallel solver, gain bands: the level of a round, by round parity (written by the apply launch before)
+    u32 gmax;                // row-parallel solver, gain bands: the largest round-0 gain
 };
 
 // packed key = (gain << 32) | (0xFFFFFFFF - set id): gains are < 2^32 (a group's
@@ -958,6 +960,7 @@ int chip_greedy_deferred(catchhip_ctx *ctx, catchhip_rows *R, i64 num_sets, cons
     *n_out = 0;
     ctx->phase_ms[PHASE_CLAIM] = 0.0; ctx->phase_launches[PHASE_CLAIM] = 0;   // (only the row-parallel solver fills it)
     memset(ctx->solver_counters, 0, sizeof(ctx->solver_counters));
+    memset(ctx->solver_levels, 0, sizeof(ctx->solver_levels));
     if (num_sets <= 0 || num_sets >= (i64)ID_MASK || !R->deferred) { *retry = 1; return 0; }
     HIP_TRY(hipSetDevice(ctx->device));
     PoolScope pool_scope(ctx);
@@ -983,6 +986,7 @@ int chip_setcover_solve(catchhip_ctx *ctx, catchhip_rows *R, i64 num_sets, const
     *n_out = 0;
     ctx->phase_ms[PHASE_CLAIM] = 0.0; ctx->phase_launches[PHASE_CLAIM] = 0;   // (only the row-parallel solver fills it)
     memset(ctx->solver_counters, 0, sizeof(ctx->solver_counters));
+    memset(ctx->solver_levels, 0, sizeof(ctx->solver_levels));
     if (num_sets == 0 || R->n == 0) return 0;  // no universe has anything to cover
     ARG_CHECK(out_ids != nullptr);
     if (num_sets >= (i64)ID_MASK) { chip_set_error("setcover: more than 2^32-2 sets not supported"); return CATCHHIP_EINVAL; }

@@ -137,6 +137,16 @@ struct FlatArgs {
     u32 pretested;                  // partial coverage, sharded: the universe test of the candidates ran in gr_verdict_kernel
                                     // on every rank and failures travelled with the lost marks -- gr_apply accepts what is left
     unsigned long long inv;         // ~0: bm holds the COVERED positions (starts all zero: nothing to build), 0: the uncovered ones
+    // Gain bands (full coverage on one device, no ranks; DESIGN.md section 4 K2).  Gains only fall, so a set's round-0
+    // gain bounds its gain for ever: the sets are cut into nbands bands by it (band 0 the highest; band_thr[b] = the
+    // lower boundary T_b of band b, the last one's is 1) and every coordinate tile into nbands SUB-TILES, tile * nbands +
+    // band -- what tile_ptr, tile_cnt, xcd_tile and ntiles speak of.  A round of level L = st->level[round & 1]
+    // streams the sub-tiles of the bands <= L only, and a set claims only with a gain >= T_L: every set that does not
+    // claim -- asleep, or counted below T_L -- has a smaller key than every claimant, which is all the acceptance
+    // rule needs.  A round without a claimant raises the level.  nbands == 1, T_0 = 1: the rounds as they were.
+    const u32 *band_thr;
+    const u8 *band;                 // band of every set (null: one band)
+    u32 nbands;
 };
 
 // where the set-up kernels (segment flags, the partition by tile) read the (set, start)-ordered rows
@@ -190,23 +200,36 @@ __device__ __forceinline__ void load_records(const FlatArgs &a, u32 buf, u32 bba
 // that all workgroups of the XCD sweep the tiles front to back together and
 // stay busy when the tiles have shrunk to a few steps each.  Trip counts are
 // uniform inside a workgroup.
-#define GR_MAXTX 32                      // tiles per XCD (256 tiles / 8)
+#define GR_MAXTX 32                      // (sub-)tiles per XCD (256 tiles / 8)
+#define GR_BANDS 2                       // gain bands (as far as the tiles allow: FlatSolve::setup) and the ratio of two neighbouring
+#define GR_BAND_RATIO 650                //   boundaries in 1/1000.  S4 step, ms: 1 band 74.8-76.6; 2 bands at 0.60 / 0.65 / 0.70: 71.4 / 71.4 /
+                                         //   70.1-71.0, at 0.50: 78.5, at 0.75-0.85: 76.9-78.3; 3 at 0.6 / 0.7: 75.7 / 75.9; 4 at 0.7 / 0.8: 80.3 / 73.5;
+                                         //   8 at 0.75: 110.8 (every level ends with a round that claims nothing: DESIGN.md section 4 K2)
 struct GrNoTileHook { __device__ __forceinline__ void operator()(u32, u32) const {} };
+// Which sub-tiles a walk takes (gain bands): those of the bands <= level; the sub-tiles of band `wake` (none: ~0)
+// are streamed for the first time -- all their records, where the partition put them (buffer 0).
+struct GrWalk { u32 level = 0xffffffffu, wake = 0xffffffffu; };
+// f(sub-tile, bbase, end, tile start, k, x, fresh): fresh = a step of a band that wakes (uniform over the workgroup)
 // on_tile(tile, steps of this XCD in all): called by the whole workgroup before its first step in a tile
 template <class F, class G = GrNoTileHook>
-__device__ __forceinline__ void for_each_step(const FlatArgs &a, u32 buf, F f, G on_tile = G()) {
+__device__ __forceinline__ void for_each_step(const FlatArgs &a, u32 buf, F f, G on_tile = G(), GrWalk wk = GrWalk()) {
     __shared__ u32 s_first[GR_MAXTX + 1];   // first step number of the XCD's j-th tile
     __shared__ u32 s_tstart[GR_MAXTX], s_tcnt[GR_MAXTX];
-    __shared__ u32 s_tile[GR_MAXTX];
+    __shared__ u32 s_tile[GR_MAXTX], s_ctile[GR_MAXTX], s_fresh[GR_MAXTX];
     const u32 xcd = blockIdx.x & 7;
     const u32 nbx = (gridDim.x + 7 - xcd) >> 3;        // workgroups on this XCD
     const u32 ntx = min(a.xcd_ntiles[xcd], (u32)GR_MAXTX);
     // the tiles' ranges: loaded side by side, kept in LDS for the walk
     if (threadIdx.x < ntx) {
         const u32 tl = a.xcd_tile[xcd * GR_MAXTX + threadIdx.x];
+        const u32 band = a.nbands > 1 ? tl % a.nbands : 0u;
+        const bool fresh = a.nbands > 1 && band == wk.wake;
         s_tile[threadIdx.x] = tl;
+        s_ctile[threadIdx.x] = a.nbands > 1 ? tl / a.nbands : tl;
+        s_fresh[threadIdx.x] = fresh ? 1u : 0u;
         s_tstart[threadIdx.x] = a.tile_ptr[tl];
-        s_tcnt[threadIdx.x] = a.tile_cnt[buf][tl];
+        // (a sleeping band's sub-tiles count as empty: nothing of theirs is read)
+        s_tcnt[threadIdx.x] = band > wk.level ? 0u : fresh ? a.tile_ptr[tl + 1] - a.tile_ptr[tl] : a.tile_cnt[buf][tl];
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -225,7 +248,7 @@ __device__ __forceinline__ void for_each_step(const FlatArgs &a, u32 buf, F f, G
         while (s_first[j + 1] <= g) ++j;              // steps only move forward
         bbase = s_tstart[j] + (g - s_first[j]) * GR_BCH;
         end = s_tstart[j] + s_tcnt[j];
-        load_records(a, buf, bbase, end, s_tile[j], kc, xc);
+        load_records(a, s_fresh[j] ? 0u : buf, bbase, end, s_ctile[j], kc, xc);
     }
     u32 jprev = 0xffffffffu;
     while (g < total) {
@@ -236,9 +259,9 @@ __device__ __forceinline__ void for_each_step(const FlatArgs &a, u32 buf, F f, G
             while (s_first[j + 1] <= gn) ++j;
             bbase = s_tstart[j] + (gn - s_first[j]) * GR_BCH;
             end = s_tstart[j] + s_tcnt[j];
-            load_records(a, buf, bbase, end, s_tile[j], kn, xn);
+            load_records(a, s_fresh[j] ? 0u : buf, bbase, end, s_ctile[j], kn, xn);
         }
-        f(s_tile[jc], bc, ec, s_tstart[jc], kc, xc);
+        f(s_tile[jc], bc, ec, s_tstart[jc], kc, xc, s_fresh[jc] != 0u);
 #pragma unroll
         for (int u = 0; u < GR_UNR; ++u) { kc[u] = kn[u]; xc[u] = xn[u]; }
         g = gn;
@@ -265,7 +288,17 @@ gr_count_kernel(FlatArgs a, u32 round) {
     u32 cnt_rows = 0, cnt_dirty = 0, cnt_words = 0, cnt_own = 0, step_par = 0;
     // statistics (off in timed runs): words that changed in the previous round's apply launch
     const u32 *chg = a.changed[0] ? a.changed[ob ^ 1] : nullptr;
-    for_each_step(a, ib, [&](u32 t, u32 bbase, u32 end, u32 tstart, unsigned long long (&k)[GR_UNR], u32 (&x)[GR_UNR]) {
+    // gain bands: the level of this round; a level other than the last round's means that its band wakes now
+    GrWalk wk;
+    if (a.nbands > 1) {
+        wk.level = st->level[ob];
+        if (round && st->level[ob ^ 1] != wk.level) wk.wake = wk.level;
+    }
+    for_each_step(a, ib, [&](u32 t, u32 bbase, u32 end, u32 tstart, unsigned long long (&k)[GR_UNR], u32 (&x)[GR_UNR], bool fresh) {
+        // A band that wakes is read from buffer 0.  In an even round that is the buffer being written as well: its
+        // records then stay where they are, the dead ones without flags (they claim nothing, and the next count
+        // launch drops them), and the step adds its slots to the sub-tile's counter
+        const bool inplace = fresh && ob == 0;
         unsigned long long v[GR_UNR][RP_MAXW];
 #pragma unroll
         for (int u = 0; u < GR_UNR; ++u)
@@ -334,6 +367,7 @@ gr_count_kernel(FlatArgs a, u32 round) {
             if (threadIdx.x == 0) {
                 u32 tot = 0;
                 for (int w = 0; w < GR_WAVES; ++w) tot += s_wcnt[sp][w];
+                if (inplace) tot = min((u32)GR_BCH, end - bbase);
                 base_got = tot ? atomicAdd(&a.tile_cnt[ob][t], tot) : 0u;
             }
         }
@@ -351,6 +385,14 @@ gr_count_kernel(FlatArgs a, u32 round) {
         __syncthreads();
         u32 o = tstart + s_base[sp];
         for (u32 w = 0; w < wave; ++w) o += s_wcnt[sp][w];
+        if (inplace) {
+#pragma unroll
+            for (int u = 0; u < GR_UNR; ++u) {
+                const u32 r = bbase + wave * GR_WCH + lane + u * 64;
+                if (r < end) a.key[0][r] = GR_KEY_NOFLAGS(k[u]) | ((unsigned long long)nf[u] << GR_SET_BITS);
+            }
+            return;
+        }
 #pragma unroll
         for (int u = 0; u < GR_UNR; ++u) {
             if (nf[u]) {
@@ -360,7 +402,7 @@ gr_count_kernel(FlatArgs a, u32 round) {
             }
             o += (u32)__popcll(alive[u]);
         }
-    });
+    }, GrNoTileHook(), wk);
     wave_sum_n(cnt_rows, cnt_dirty, cnt_words, cnt_own);
     if (lane == 0) {
         atomicAdd(&s_rows[0], (unsigned long long)cnt_rows);
@@ -399,14 +441,20 @@ gr_claim_kernel(FlatArgs a, u32 round) {
     // No row anywhere (sharded: on any rank -- acc[] holds the all-reduced values) holds an uncovered
     // element: every universe is covered, finished (all gains are zero then, so nothing is claimed
     // by the workgroups that do not see the flag yet)
-    if (acc[a.nsets] == 0) { if (blockIdx.x == 0 && threadIdx.x == 0) st->done = 1; return; }
+    // (gain bands: only at the last level -- before it the sleeping bands may hold such rows, nothing claims, and
+    // the apply launch raises the level)
+    const u32 level = a.nbands > 1 ? st->level[par] : 0u;
+    if (acc[a.nsets] == 0) { if (blockIdx.x == 0 && threadIdx.x == 0 && level + 1 >= a.nbands) st->done = 1; return; }
+    const u32 gain_min = a.band_thr[level];     // T_L: what a set must gain to claim in this round (one band: 1)
+    GrWalk wk;
+    wk.level = a.nbands > 1 ? level : 0xffffffffu;
     if (a.sharded) {
         // the claimants are decided by the global gains, the same on every rank --
         // also for sets without an alive row here
         for (u32 s = blockIdx.x * GR_THREADS + threadIdx.x; s < a.nsets; s += gridDim.x * GR_THREADS)
             if (acc[s] && a.rank[s] == cur_rank) { any = true; a.claimed[s] = round + 1; }
     }
-    for_each_step(a, par, [&](u32, u32 bbase, u32 end, u32, unsigned long long (&k)[GR_UNR], u32 (&x)[GR_UNR]) {
+    for_each_step(a, par, [&](u32, u32 bbase, u32 end, u32, unsigned long long (&k)[GR_UNR], u32 (&x)[GR_UNR], bool) {
         // the set's gain / rank and the owner words depend only on the record:
         // all requested together.  Round 6: the gain (and rank) of a set is fetched by the FIRST lane of its run
         // only and handed to the others by a lane permute -- the launch is bound by the vector memory pipeline's
@@ -437,7 +485,7 @@ gr_claim_kernel(FlatArgs a, u32 round) {
         // group (the replayed loads of the same launch take 1.2 ms, tools/pmc_rounds.sh).  So:
         // every raise of the step is issued first, the answers are looked at afterwards.
         u32 gg[GR_UNR];
-        bool claims[GR_UNR];
+        bool claims[GR_UNR], set_claims[GR_UNR];
 #pragma unroll
         for (int u = 0; u < GR_UNR; ++u) {
             // (an alive row belongs to a set that was not chosen: the rows of an
@@ -448,7 +496,10 @@ gr_claim_kernel(FlatArgs a, u32 round) {
             const u32 rr = one_rank ? 0u : __shfl(rk[u], (int)hl[u], WAVE);
             // (decided per set, so the lanes of a run agree; the first lane of a run
             // stores the marks for all of them)
-            claims[u] = fl && gg[u] != 0 && rr == cur_rank;
+            // (a band that woke in place leaves dead records, without flags, among its alive ones: such a record may
+            // be the first of its set's run, so what the run's first lane stores goes by the set, not by its own record)
+            set_claims[u] = gg[u] >= gain_min && rr == cur_rank;
+            claims[u] = fl && set_claims[u];
         }
 #pragma unroll
         for (int u = 0; u < GR_UNR; ++u) {
@@ -487,13 +538,13 @@ gr_claim_kernel(FlatArgs a, u32 round) {
             const unsigned long long after = heads[u] & ~((2ull << lane) - 1ull);           // run heads beyond this lane (lane 63: none)
             const unsigned long long upto = after ? ((1ull << (__ffsll((long long)after) - 1)) - 1ull) : ~0ull;
             const bool head = ((heads[u] >> lane) & 1ull) != 0;
-            if (head && claims[u]) {
+            if (head && set_claims[u]) {
                 if (lb & upto & ~((1ull << lane) - 1ull)) a.lost[s] = round + 1;
                 // (without ranks a set claims iff its gain is not zero: gr_apply looks at the gain instead of a mark)
                 if (!one_rank || a.sharded) a.claimed[s] = round + 1;
             }
         }
-    });
+    }, GrNoTileHook(), wk);
     if (any) s_claim = 1;
     if (count_here) {
         wave_sum_n(c_rows, c_own);
@@ -580,18 +631,27 @@ gr_apply_kernel(FlatArgs a, u32 round) {
     else if (gtid < 2) a.acc[par ^ 1][a.nsets + gtid] = 0u;
     for (u32 i = gtid; i < a.ntiles; i += gsize) a.tile_cnt[par ^ 1][i] = 0u;
     if (a.changed[0]) for (u32 i = gtid; i < a.nchg; i += gsize) a.changed[par ^ 1][i] = 0u;   // (statistics; marked by the next round's apply)
+    // gain bands: the level of this round (the next round's is written below, into the other cell: no workgroup of
+    // this launch reads what thread 0 writes)
+    const u32 level = a.nbands > 1 ? st->level[par] : 0u;
+    const u32 gain_min = a.band_thr[level];
     if (gtid == 0) {
         const u32 claimed = st->fr_claim[par];
         st->fr_claim[par ^ 1] = 0;
         st->fr_claim[par] = 0;
+        u32 next_level = level;
         // nothing claimed although rows with uncovered elements exist (or the claim launch
         // would have set the finished flag)
         if (claimed == 0) {
-            // no set of this rank covers anything still needed: next rank
-            const u32 nr = st->cur_rank + 1;
-            st->cur_rank = nr;
-            if (nr >= st->nrank) st->done = 2;
+            if (level + 1 < a.nbands) next_level = level + 1;     // no awake set gains T_L any more: the next band wakes
+            else {
+                // no set of this rank covers anything still needed: next rank
+                const u32 nr = st->cur_rank + 1;
+                st->cur_rank = nr;
+                if (nr >= st->nrank) st->done = 2;
+            }
         }
+        if (a.nbands > 1) st->level[par ^ 1] = next_level;
     }
     const u32 lane = threadIdx.x & 63;
     const bool gain_claims = st->nrank <= 1 && !a.sharded;   // (see gr_claim_kernel: no claim marks then)
@@ -621,7 +681,8 @@ gr_apply_kernel(FlatArgs a, u32 round) {
                 const bool valid = idx < pend;
                 const u32 s = valid ? (in_list ? in_list[seg0 + idx] : seg0 + idx) : 0u;
                 const u32 g = valid ? acc[s] : 0u;
-                const bool won = valid && (gain_claims ? g != 0u : a.claimed[s] == round + 1) && a.lost[s] != round + 1;
+                // (a set claimed iff it gained T_L: a sleeping set's round-0 gain, which round 0 finds here, is below it)
+                const bool won = valid && (gain_claims ? g >= gain_min : a.claimed[s] == round + 1) && a.lost[s] != round + 1;
                 if (in_list && valid) a.acc[par ^ 1][s] = 0u;
                 const unsigned long long wb = __ballot(won);
                 if (wb) {
@@ -639,7 +700,8 @@ gr_apply_kernel(FlatArgs a, u32 round) {
                 }
                 if (out_list) {
                     // (the segment being read and the one being written are different buffers)
-                    const bool still = valid && g != 0u && !won;
+                    // (a set of a sleeping band stays listed: its gain is zero only because nothing counted it)
+                    const bool still = valid && !won && (g != 0u || (a.band && a.band[s] > level));
                     const unsigned long long sb = __ballot(still);
                     if (sb) {
                         u32 o0 = 0;
@@ -1056,12 +1118,56 @@ __device__ __forceinline__ bool gr_src_row(const GrRowSrc &src, u32 idx, u32 &x,
 // tile_shift < 0: 8 striped tiles (4-kbase stripes dealt round robin)
 __device__ __forceinline__ u32 gr_tile_of(u32 x, int tile_shift) { return tile_shift < 0 ? (x >> 12) & 7u : x >> tile_shift; }
 
+// Gain bands.  The boundaries: T_b = ratio^(b + 1) x the largest round-0 gain (ratio in 1/1000), the last one 1.
+__global__ void __launch_bounds__(256)
+gr_gain_max_kernel(const u32 *__restrict__ gain0, u32 n, GreedyState *__restrict__ st) {
+    __shared__ u32 s_max[4];
+    u32 best = 0;
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) best = max(best, gain0[i]);
+    best = wave_max(best);
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < 4; ++i) best = max(best, s_max[i]);
+        if (best) atomicMax(&st->gmax, best);
+    }
+}
+__device__ __forceinline__ u32 gr_band_boundary(u32 prev, u32 ratio_pm) {
+    return max(1u, (u32)(((unsigned long long)prev * ratio_pm) / 1000ull));
+}
+// band of every set: the first whose boundary its round-0 gain reaches (sets beyond the gains held: the last)
+__global__ void __launch_bounds__(256)
+gr_band_kernel(const u32 *__restrict__ gain0, u32 ng, u32 nsets, const GreedyState *__restrict__ st, u32 nbands, u32 ratio_pm,
+               u32 *__restrict__ band_thr, u8 *__restrict__ band) {
+    const u32 s = blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 g = s < ng ? gain0[s] : 0u;
+    u32 t = st->gmax, b = 0, mine = nbands - 1;
+    for (; b + 1 < nbands; ++b) {
+        t = gr_band_boundary(t, ratio_pm);
+        if (s == 0) band_thr[b] = t;
+        if (g >= t && mine == nbands - 1) mine = b;
+    }
+    if (s == 0) band_thr[nbands - 1] = 1u;
+    if (s < nsets) band[s] = (u8)mine;
+}
+
+// (band: the band of every set, null with one band -- the partition's digit is the sub-tile, tile * nbands + band)
 __global__ void __launch_bounds__(GT_THREADS)
-gr_tile_hist_kernel(GrRowSrc src, int tile_shift, u32 ntiles, u32 *__restrict__ hist, u32 nblocks) {
+gr_tile_hist_kernel(GrRowSrc src, int tile_shift, u32 ntiles, u32 *__restrict__ hist, u32 nblocks, const u8 *__restrict__ band, u32 nbands) {
     __shared__ u32 h[256];
     h[threadIdx.x] = 0;
     __syncthreads();
     const u32 base = blockIdx.x * GT_TILE;
+    if (band) {
+        for (int r = 0; r < GT_ROUNDS; ++r) {
+            u32 x = 0u, e = 1u, sid = 0u, univ = 0u;
+            if (gr_src_row(src, base + r * GT_THREADS + threadIdx.x, x, e, sid, univ))
+                atomicAdd(&h[gr_tile_of(x, tile_shift) * nbands + band[sid]], 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x < ntiles) hist[(size_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
+        return;
+    }
 #pragma unroll 4
     for (int r = 0; r < GT_ROUNDS; ++r) {
         const u32 idx = base + r * GT_THREADS + threadIdx.x;
@@ -1079,7 +1185,8 @@ gr_tile_hist_kernel(GrRowSrc src, int tile_shift, u32 ntiles, u32 *__restrict__ 
 
 __global__ void __launch_bounds__(GT_THREADS)
 gr_tile_scatter_kernel(GrRowSrc src, int tile_shift, u32 ntiles, const u32 *__restrict__ hist_scanned, u32 nblocks,
-                       unsigned long long *__restrict__ keys, const u32 *__restrict__ cflag, u32 *__restrict__ unis) {
+                       unsigned long long *__restrict__ keys, const u32 *__restrict__ cflag, u32 *__restrict__ unis,
+                       const u8 *__restrict__ band, u32 nbands) {
     __shared__ u32 wave_cnt[GT_THREADS / 64][256];
     __shared__ u32 base[256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1092,7 +1199,7 @@ gr_tile_scatter_kernel(GrRowSrc src, int tile_shift, u32 ntiles, const u32 *__re
         const u32 idx = tile0 + (u32)r * GT_THREADS + tid;
         u32 x = 0u, e = 1u, sid = 0u, univ = 0u;
         const bool valid = gr_src_row(src, idx, x, e, sid, univ);
-        const u32 digit = valid ? gr_tile_of(x, tile_shift) : 0u;
+        const u32 digit = valid ? (band ? gr_tile_of(x, tile_shift) * nbands + band[sid] : gr_tile_of(x, tile_shift)) : 0u;
 #pragma unroll
         for (int w = 0; w < GT_THREADS / 64; ++w) wave_cnt[w][tid] = 0;
         __syncthreads();
@@ -1147,15 +1254,24 @@ gr_tile_ptr_kernel(const u32 *__restrict__ hist_scanned, u32 nblocks, u32 nrows,
 // the tiles of every XCD (FlatArgs::xcd_tile): by_rows = largest tile first, each to the XCD that holds the fewest rows so far
 // (at most GR_MAXTX tiles per XCD; 8 x GR_MAXTX >= ntiles); otherwise tile t to XCD t % 8 as until round 6
 __global__ void __launch_bounds__(256)
-gr_tile_assign_kernel(const u32 *__restrict__ tile_cnt, u32 ntiles, int by_rows, u32 *__restrict__ xcd_tile, u32 *__restrict__ xcd_ntiles) {
+// Gain bands: ntiles COORDINATE tiles of nbands sub-tiles each (tile_cnt is per sub-tile).  Coordinate tiles are
+// dealt, by their rows of all bands, and the lists then name every tile's sub-tiles side by side, band 0 first: they
+// stay on one XCD (8 x (GR_MAXTX / nbands) >= ntiles).
+gr_tile_assign_kernel(const u32 *__restrict__ tile_cnt, u32 ntiles, u32 nbands, int by_rows, u32 *__restrict__ xcd_tile, u32 *__restrict__ xcd_ntiles) {
     __shared__ u32 s_cnt[256], s_order[256];
     const u32 t = threadIdx.x;
+    const u32 max_held = (u32)GR_MAXTX / nbands;
     if (!by_rows) {
-        if (t < ntiles) xcd_tile[(t & 7u) * GR_MAXTX + (t >> 3)] = t;
-        if (t < 8) xcd_ntiles[t] = ntiles > t ? (ntiles - t + 7u) >> 3 : 0u;
+        if (t < ntiles)
+            for (u32 b = 0; b < nbands; ++b) xcd_tile[(t & 7u) * GR_MAXTX + (t >> 3) * nbands + b] = t * nbands + b;
+        if (t < 8) xcd_ntiles[t] = ntiles > t ? ((ntiles - t + 7u) >> 3) * nbands : 0u;
         return;
     }
-    s_cnt[t] = t < ntiles ? tile_cnt[t] : 0u;
+    {
+        u32 c = 0;
+        if (t < ntiles) for (u32 b = 0; b < nbands; ++b) c += tile_cnt[t * nbands + b];
+        s_cnt[t] = c;
+    }
     __syncthreads();
     if (t < ntiles) {
         u32 rk = 0;
@@ -1170,7 +1286,7 @@ gr_tile_assign_kernel(const u32 *__restrict__ tile_cnt, u32 ntiles, int by_rows,
             const u32 tl = s_order[r];
             u32 best = 8;
             for (u32 x = 0; x < 8; ++x)
-                if (held[x] < (u32)GR_MAXTX && (best == 8 || load[x] < load[best])) best = x;
+                if (held[x] < max_held && (best == 8 || load[x] < load[best])) best = x;
             xcd_tile[best * GR_MAXTX + held[best]] = tl;
             ++held[best];
             load[best] += s_cnt[tl];
@@ -1186,7 +1302,7 @@ gr_tile_assign_kernel(const u32 *__restrict__ tile_cnt, u32 ntiles, int by_rows,
             int bi = -1, bj = -1;                         // tile slots: bj < 0 = a move of bi
             for (u32 i = 0; i < held[xa]; ++i) {
                 const unsigned long long ca = s_cnt[xcd_tile[xa * GR_MAXTX + i]];
-                if (held[xb] < (u32)GR_MAXTX) {
+                if (held[xb] < max_held) {
                     const unsigned long long m = la - ca > lb + ca ? la - ca : lb + ca;
                     if (m < best) { best = m; bi = (int)i; bj = -1; }
                 }
@@ -1218,7 +1334,13 @@ gr_tile_assign_kernel(const u32 *__restrict__ tile_cnt, u32 ntiles, int by_rows,
                 while (j > 0 && lst[j - 1] > v) { lst[j] = lst[j - 1]; --j; }
                 lst[j] = v;
             }
-            xcd_ntiles[x] = held[x];
+            // coordinate tiles -> their sub-tiles (from the back: slot i * nbands + b lies at or behind slot i)
+            if (nbands > 1)
+                for (u32 i = held[x]; i-- > 0;) {
+                    const u32 ct = lst[i];
+                    for (u32 b = nbands; b-- > 0;) lst[i * nbands + b] = ct * nbands + b;
+                }
+            xcd_ntiles[x] = held[x] * nbands;
         }
     }
 }
@@ -1227,7 +1349,7 @@ gr_tile_assign_kernel(const u32 *__restrict__ tile_cnt, u32 ntiles, int by_rows,
 // tile-ordered records (the tile's words are L2-resident while it is built)
 __global__ void __launch_bounds__(GR_THREADS)
 gr_bitmap_kernel(FlatArgs a) {
-    for_each_step(a, 0, [&](u32, u32 bbase, u32 end, u32, unsigned long long (&k)[GR_UNR], u32 (&x)[GR_UNR]) {
+    for_each_step(a, 0, [&](u32, u32 bbase, u32 end, u32, unsigned long long (&k)[GR_UNR], u32 (&x)[GR_UNR], bool) {
 #pragma unroll
         for (int u = 0; u < GR_UNR; ++u) {
             if (!GR_KEY_FLAGS(k[u])) continue;
@@ -1327,6 +1449,20 @@ struct FlatSolve {
             while (((u64)R->total >> tile_shift) >= 256) ++tile_shift;
             ntiles = (u32)((u64)R->total >> tile_shift) + 1;
         }
+        // Gain bands: full coverage on one device without ranks, when the rows came with their sets' round-0 gains.
+        // As many as asked for (CATCHHIP_FLAT_BANDS; 1: none) and as the tiles allow: every XCD lists at most GR_MAXTX
+        // sub-tiles, and the coordinate tiles are dealt to the XCDs whole.
+        const bool stats_dirty = chip_test_env("CATCHHIP_FLAT_COUNT_DIRTY") != nullptr;   // E_dirty beside the rows counted (bench: one untimed step)
+        u32 nbands = 1;
+        if (!partial && !sharded && !h_rank && nrank <= 1 && !stats_dirty && R->gain0_n && nrows) {
+            const u32 max_bands = (u32)GR_MAXTX / (u32)div_up((i64)ntiles, 8);
+            // (a union of unlike groups keeps one band unless asked: the boundaries go by the instance's largest gain, and the
+            // smaller groups lie below all of them -- they would wait for the last level and then run as without bands)
+            const i64 want = R->grouped ? chip_test_env_int("CATCHHIP_FLAT_BANDS_GROUPED", 1) : chip_test_env_int("CATCHHIP_FLAT_BANDS", GR_BANDS);
+            nbands = (u32)std::max<i64>(1, std::min<i64>(want, (i64)max_bands));
+        }
+        const u32 band_ratio = (u32)std::max<i64>(1, std::min<i64>(chip_test_env_int("CATCHHIP_FLAT_BAND_RATIO", GR_BAND_RATIO), 999));
+        const u32 nsub = ntiles * nbands;                                  // sub-tiles: what the records are partitioned by
         size_t off = 0;
         auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
         const size_t o_bm = take(8 * (nwords + 8)), o_ow0 = take(8 * (nwords + 8)), o_ow1 = take(8 * (nwords + 8)),
@@ -1335,7 +1471,6 @@ struct FlatSolve {
                      o_lost = take(4 * (size_t)nsets), o_rank = take(4 * (size_t)nsets),
                      o_acc0 = take(4 * ((size_t)nsets + 2)), o_acc1 = take(4 * ((size_t)nsets + 2)),
                      o_tc0 = take(4 * 258), o_tc1 = take(4 * 258);
-        const bool stats_dirty = chip_test_env("CATCHHIP_FLAT_COUNT_DIRTY") != nullptr;   // E_dirty beside the rows counted (bench: one untimed step)
         const size_t nchg = stats_dirty ? nwords / 32 + 4 : 0;
         const size_t o_chg0 = take(4 * nchg), o_chg1 = take(4 * nchg);
         const size_t o_cflag = take(partial ? 4 * ((size_t)nsets + 1) : 0), o_ufinal = take(partial ? 4 * (size_t)nuniv + 4 : 0);
@@ -1349,7 +1484,8 @@ struct FlatSolve {
         const size_t o_usize = take(4 * (size_t)std::max<u32>(nuniv, 1)), o_picks = take(4 * (size_t)nsets),
                      o_keys = take(8 * (size_t)nsets), o_tptr = take(4 * 258),
                      o_sptr = direct ? o_dsptr : take(4 * ((size_t)nsets + 1)),
-                     o_xt = take(4 * 8 * GR_MAXTX), o_xn = take(4 * 8);
+                     o_xt = take(4 * 8 * GR_MAXTX), o_xn = take(4 * 8),
+                     o_thr = take(4 * GR_MAXTX), o_band = take(nbands > 1 ? (size_t)nsets : 0);
         const size_t o_need = take(partial ? 4 * (size_t)nuniv + 4 : 0), o_uT = take(partial ? 8 * (size_t)nuniv + 8 : 0),
                      o_uM = take(partial ? 8 * (size_t)nuniv + 8 : 0), o_cpos = take(partial ? 4 * ((size_t)nsets + 1) : 0),
                      o_cset = take(partial ? 4 * ((size_t)nsets + 2) : 0);
@@ -1418,7 +1554,15 @@ struct FlatSolve {
         fa.alive_cnt[0] = (u32 *)(A + o_alc0); fa.alive_cnt[1] = (u32 *)(A + o_alc1); fa.alive_seg = alive_seg;
         fa.pick_key = (unsigned long long *)(A + o_keys);
         fa.blkcnt = (unsigned long long *)(A + o_blk); fa.st = (GreedyState *)(A + o_st);
-        fa.nsets = nsets; fa.nwords = (u32)nwords; fa.ntiles = ntiles; fa.nuniv = nuniv;
+        fa.nsets = nsets; fa.nwords = (u32)nwords; fa.ntiles = nsub; fa.nuniv = nuniv;
+        fa.nbands = nbands; fa.band_thr = (const u32 *)(A + o_thr); fa.band = nbands > 1 ? (const u8 *)(A + o_band) : nullptr;
+        if (nbands > 1) {
+            const u32 ng = std::min<u32>(R->gain0_n, nsets);
+            hipLaunchKernelGGL(gr_gain_max_kernel, dim3((unsigned)std::max<i64>(1, std::min<i64>(div_up((i64)ng, 1024), (i64)ctx->num_cus))), dim3(256), 0, s,
+                               (const u32 *)R->gain0.p, ng, (GreedyState *)(A + o_st));
+            hipLaunchKernelGGL(gr_band_kernel, dim3((unsigned)div_up((i64)nsets, 256)), dim3(256), 0, s, (const u32 *)R->gain0.p, ng, nsets,
+                               (const GreedyState *)(A + o_st), nbands, band_ratio, (u32 *)(A + o_thr), (u8 *)(A + o_band));
+        } else hipLaunchKernelGGL(gr_fill_one_kernel, dim3(1), dim3(1), 0, s, (u32 *)(A + o_thr), 1u);
         fa.sharded = sharded ? 1u : 0u;
         fa.pretested = (sharded && partial) ? 1u : 0u;
         fa.changed[0] = stats_dirty ? (u32 *)(A + o_chg0) : nullptr; fa.changed[1] = stats_dirty ? (u32 *)(A + o_chg1) : nullptr;
@@ -1427,20 +1571,21 @@ struct FlatSolve {
         if (nrows) {
             const u32 nblk = (u32)div_up(src.n, GT_TILE);
             DevBuf<u32> hist, tmp;
-            TRY(hist.alloc((size_t)ntiles * nblk));
-            hipLaunchKernelGGL(gr_tile_hist_kernel, dim3(nblk), dim3(GT_THREADS), 0, s, src, tile_shift, ntiles, hist.p, nblk);
-            TRY(chip_exclusive_scan_u32(ctx, hist.p, hist.p, (i64)ntiles * nblk, tmp));
-            hipLaunchKernelGGL(gr_tile_scatter_kernel, dim3(nblk), dim3(GT_THREADS), 0, s, src, tile_shift, ntiles,
+            TRY(hist.alloc((size_t)nsub * nblk));
+            hipLaunchKernelGGL(gr_tile_hist_kernel, dim3(nblk), dim3(GT_THREADS), 0, s, src, tile_shift, nsub, hist.p, nblk, fa.band, nbands);
+            TRY(chip_exclusive_scan_u32(ctx, hist.p, hist.p, (i64)nsub * nblk, tmp));
+            hipLaunchKernelGGL(gr_tile_scatter_kernel, dim3(nblk), dim3(GT_THREADS), 0, s, src, tile_shift, nsub,
                                (const u32 *)hist.p, nblk, (unsigned long long *)skey.p,
-                               partial ? (const u32 *)(A + o_cflag) : (const u32 *)nullptr, partial ? suni.p : (u32 *)nullptr);
-            hipLaunchKernelGGL(gr_tile_ptr_kernel, dim3(1), dim3(256), 0, s, (const u32 *)hist.p, nblk, nrows, ntiles,
+                               partial ? (const u32 *)(A + o_cflag) : (const u32 *)nullptr, partial ? suni.p : (u32 *)nullptr,
+                               fa.band, nbands);
+            hipLaunchKernelGGL(gr_tile_ptr_kernel, dim3(1), dim3(256), 0, s, (const u32 *)hist.p, nblk, nrows, nsub,
                                (u32 *)(A + o_tptr), fa.tile_cnt[0]);
             // (hist / tmp go back to the pool; their reuse is ordered by the stream)
         } else {
-            hipLaunchKernelGGL(gr_tile_ptr_kernel, dim3(1), dim3(256), 0, s, (const u32 *)nullptr, 0u, 0u, ntiles,
+            hipLaunchKernelGGL(gr_tile_ptr_kernel, dim3(1), dim3(256), 0, s, (const u32 *)nullptr, 0u, 0u, nsub,
                                (u32 *)(A + o_tptr), fa.tile_cnt[0]);
         }
-        hipLaunchKernelGGL(gr_tile_assign_kernel, dim3(1), dim3(256), 0, s, (const u32 *)fa.tile_cnt[0], ntiles,
+        hipLaunchKernelGGL(gr_tile_assign_kernel, dim3(1), dim3(256), 0, s, (const u32 *)fa.tile_cnt[0], ntiles, nbands,
                            (tile_shift >= 0 && !chip_test_env("CATCHHIP_FLAT_TILES_ROUND_ROBIN")) ? 1 : 0, (u32 *)(A + o_xt), (u32 *)(A + o_xn));
         // the sorted records are buffer 0, the sort's scratch is buffer 1
         fa.key[0] = (unsigned long long *)skey.p;
@@ -1550,7 +1695,7 @@ static int greedy_flat(catchhip_ctx *ctx, const catchhip_rows *R, u32 nsets, con
     FlatSolve F;
     PhaseTimer tm(ctx, PHASE_GREEDY);
     TRY(F.setup(ctx, R, nsets, h_rank, nrank, false, &tm, h_p));
-    const i64 max_rounds = (i64)nsets + nrank + 2;
+    const i64 max_rounds = (i64)nsets + nrank + 2 + F.fa.nbands;
     i64 rounds = 0;
     int per_sync = 16;   // most instances finish in 13-21 rounds: one or two synchronisations
     u8 *H = (u8 *)ctx->h_big;
@@ -1602,6 +1747,7 @@ static int greedy_flat(catchhip_ctx *ctx, const catchhip_rows *R, u32 nsets, con
     ctx->phase_launches[PHASE_GREEDY] = iters;
     ctx->counters[2] = iters; ctx->counters[3] = np; ctx->counters[4] = n_vis;
     ctx->counters[5] = n_rec; ctx->counters[6] = n_wrd;
+    ctx->solver_levels[0] = F.fa.nbands > 1 ? (i64)std::max(h_st->level[0], h_st->level[1]) + 1 : 1; ctx->solver_levels[1] = F.fa.nbands;
     if (done == 2) {
         chip_set_error("setcover: ranks exhausted while coverage is still required");
         return CATCHHIP_ERANK;

@@ -221,6 +221,9 @@ class Context:
         check(self._L.catchhip_ctx_last_solver_counters(self._h, _ptr(sc, c_i64p)))
         d.update(zip(("flat_rows_streamed", "flat_rows_recounted", "flat_bitmap_words",
                       "flat_owner_words"), (int(x) for x in sc)))
+        lv = np.zeros(2, dtype=np.int64)
+        check(self._L.catchhip_ctx_last_solver_levels(self._h, _ptr(lv, c_i64p)))
+        d["flat_levels"], d["flat_bands"] = int(lv[0]), int(lv[1])   # gain bands of the last row-parallel solve
         return d
 
     def grid_counters(self):

@@ -117,6 +117,10 @@ int catchhip_ctx_last_rows_direct(catchhip_ctx *ctx, int64_t *out);
  * memo invalidation by overlap, catch/utils/set_cover.py:552-613, is the same
  * idea); bitmap words read for them; owner words the claim launches looked at. */
 int catchhip_ctx_last_solver_counters(catchhip_ctx *ctx, int64_t *out4);
+/* Gain bands of the last solve by the row-parallel solver (zeros otherwise), 2
+ * values: the levels it went through (1: every row was awake from the first
+ * round on) and the bands its sets were cut into. */
+int catchhip_ctx_last_solver_levels(catchhip_ctx *ctx, int64_t *out2);
 /* Work of the last Hamming near-duplicate filter on this context (SURVEY 8(d)
  * K3's quantities; catch/filter/near_duplicate_filter.py:47-142 does the same
  * look-ups probe by probe): probes N, tables T, pairs sharing a bucket that were
