@@ -2218,6 +2218,147 @@ int chip_rows_materialise(catchhip_ctx *ctx, catchhip_rows *R) {
     return 0;
 }
 
+// ------------------------------------------------------------------------
+// Test entry point of the row build (tests/test_row_build.py): hit records in, as a producer would have filed them;
+// bucket_prepare + bucket_finish_async + rows_emit -- or build_rows_radix + rows_compact_kernel -- exactly as
+// cover_scan_impl / chip_cover_scan_nosync call them; everything the build left behind out.  No logic of its own
+// beyond the copies, the lay-out and a look at the caller's indices (a rank or a bucket out of range would send the
+// scatter outside its buffers).
+// ------------------------------------------------------------------------
+extern "C" int catchhip_selftest_row_build(catchhip_ctx *ctx, const u32 *rec, const u32 *rank, const u32 *wcnt, i64 nrec,
+                                           const u32 *bcnt, const u32 *bstart_in, i64 nb, const i32 *bucket_set,
+                                           const u32 *run_cnt, i32 run_stride, i32 nruns, const u32 *bounds,
+                                           i64 nbounds, const i32 *opt, i32 *o_set, i32 *o_seg, u32 *o_start,
+                                           u32 *o_end, u32 *o_mcnt, u32 *o_blmax, u64 *o_bsum, u32 *o_S, u32 *o_bstart,
+                                           i64 *scalars) {
+    ARG_CHECK(ctx && opt && scalars && nrec >= 0 && nrec < ((i64)1 << 26) && nb >= 1 && nb < ((i64)1 << 24));
+    ARG_CHECK((nrec == 0 || rec) && o_mcnt && o_blmax && o_bsum && o_bstart);
+    const bool dedupe = opt[0] != 0, want_sum = opt[1] != 0, grouped = bstart_in != nullptr;
+    const int build = opt[2], emit_form = opt[3];
+    ARG_CHECK(build >= 0 && build <= 2 && (emit_form == 0 || emit_form == 1));
+    ARG_CHECK(grouped ? !rank && !wcnt && !bcnt && build == 0 : (nrec == 0 || rank) && bcnt && !run_cnt);
+    // the caller's indices
+    u32 nhits = 0;
+    if (grouped) {
+        ARG_CHECK(bstart_in[0] == 0 && (i64)bstart_in[nb] == nrec);
+        for (i64 b = 0; b < nb; ++b) ARG_CHECK(bstart_in[b] <= bstart_in[b + 1]);
+        for (i64 i = 0; i < nrec; ++i) ARG_CHECK((i64)rec[4 * i + 3] < nb);
+        if (run_cnt) {
+            ARG_CHECK(nruns >= 0 && nruns <= BK_RUNS_MAX && run_stride >= nruns && run_stride <= 64);
+            for (i64 i = 0; i < nb * run_stride; ++i) ARG_CHECK(run_cnt[i] <= (1u << 20));
+        }
+        nhits = (u32)nrec;
+    } else {
+        std::vector<u32> seen((size_t)nb, 0u);
+        for (i64 d = 0; d < nrec; ++d) {
+            if (wcnt && (u32)(d & 63) >= wcnt[d >> 6]) continue;
+            if (rank[d] == BK_NONE) continue;
+            const u32 b = rec[4 * d + 3];
+            ARG_CHECK((i64)b < nb && rank[d] < bcnt[b]);
+            if (build != 0) ARG_CHECK(bounds && nbounds >= 1 && rec[4 * d] < bounds[nbounds]);
+            ++seen[b];
+        }
+        for (i64 b = 0; b < nb; ++b) { ARG_CHECK(seen[(size_t)b] == bcnt[b]); nhits += bcnt[b]; }
+    }
+    i64 max_set_id = nb - 1;
+    if (bucket_set) {
+        max_set_id = 0;
+        for (i64 b = 0; b < nb; ++b) { ARG_CHECK(bucket_set[b] >= 0); max_set_id = std::max<i64>(max_set_id, bucket_set[b]); }
+    }
+    if (build != 0) {
+        ARG_CHECK(bounds && nbounds >= 1 && nbounds < ((i64)1 << 24) && bounds[0] == 0);
+        for (i64 g = 0; g < nbounds; ++g) ARG_CHECK(bounds[g] <= bounds[g + 1]);
+    }
+    ARG_CHECK(nhits == 0 || (o_set && o_seg && o_start && o_end && o_S));
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    BucketBuild B;
+    DevBuf<i32> d_bucket_set;
+    DevBuf<u32> d_run_cnt, d_bounds;
+    TRY(bucket_prepare(B, (u32)nb, (u32)std::max<i64>(nrec, 1), want_sum));
+    if (bucket_set) {
+        TRY(d_bucket_set.alloc((size_t)nb));
+        HIP_TRY(hipMemcpyAsync(d_bucket_set.p, bucket_set, sizeof(i32) * (size_t)nb, hipMemcpyHostToDevice, s));
+    }
+    u32 h_res[8] = {0, 0, grouped ? nhits : 0u, 0, 0, 0, 0, 0};   // (a grouped producer leaves the hits in res[2])
+    HIP_TRY(hipMemcpyAsync(B.res.p, h_res, sizeof(h_res), hipMemcpyHostToDevice, s));
+    PhaseTimer tm(ctx, PHASE_ROWS);
+    if (grouped) {
+        if (nrec) HIP_TRY(hipMemcpyAsync(B.S.p, rec, sizeof(uint4) * (size_t)nrec, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(B.bstart.p, bstart_in, sizeof(u32) * ((size_t)nb + 1), hipMemcpyHostToDevice, s));
+        if (run_cnt) {
+            TRY(d_run_cnt.alloc((size_t)nb * run_stride));
+            HIP_TRY(hipMemcpyAsync(d_run_cnt.p, run_cnt, sizeof(u32) * (size_t)nb * run_stride, hipMemcpyHostToDevice, s));
+        }
+        TRY(bucket_finish_async(ctx, B, 0, nullptr, want_sum, tm, dedupe, true, (const u32 *)d_run_cnt.p, run_stride, nruns));
+    } else {
+        if (nrec) {
+            HIP_TRY(hipMemcpyAsync(B.rec.p, rec, sizeof(uint4) * (size_t)nrec, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(B.rank.p, rank, sizeof(u32) * (size_t)nrec, hipMemcpyHostToDevice, s));
+            if (wcnt) {
+                HIP_TRY(hipMemcpyAsync(B.wcnt.p, wcnt, sizeof(u32) * (size_t)div_up(nrec, 64), hipMemcpyHostToDevice, s));
+                B.compact = true;
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(B.bcnt.p, bcnt, sizeof(u32) * (size_t)nb, hipMemcpyHostToDevice, s));
+        TRY(bucket_finish_async(ctx, B, (u32)nrec, nullptr, want_sum, tm, dedupe));
+    }
+    HIP_TRY(hipGetLastError());
+    TRY(chip_read_back(ctx, B.res.p, sizeof(h_res), h_res));
+    const bool overflow = h_res[1] != 0;
+    const bool radix = build == 1 || (build == 2 && overflow);
+    ARG_CHECK(h_res[2] == nhits && h_res[4] <= nhits);
+    u32 nrows = h_res[4], lmax = h_res[5];
+    catchhip_rows R;
+    R.ctx = ctx;
+    if (!radix) {
+        // emit_form 0: the host knows the counts (cover_scan_impl); 1: one slot per hit, the counts stay on the
+        // device (chip_cover_scan_nosync)
+        R.n = emit_form ? nhits : nrows;
+        TRY(chip_rows_alloc_soa(&R, (size_t)R.n));
+        if (R.n) {
+            if (emit_form)
+                rows_emit(ctx, &R, B.rstart.p, B.nb, B.bstart.p, d_bucket_set.p, B.S.p, B.res.p + 4, B.res.p + 2, -1);
+            else
+                rows_emit(ctx, &R, B.rstart.p, B.nb, B.bstart.p, d_bucket_set.p, B.S.p, nullptr, nullptr,
+                          nhits == nrows ? 1 : 0);
+        }
+    } else {
+        MergedRows M;
+        TRY(d_bounds.alloc((size_t)nbounds + 1));
+        HIP_TRY(hipMemcpyAsync(d_bounds.p, bounds, sizeof(u32) * ((size_t)nbounds + 1), hipMemcpyHostToDevice, s));
+        TRY(build_rows_radix(ctx, B, (u32)nrec, nullptr, nhits, d_bucket_set.p, d_bounds.p, (u32)nbounds, max_set_id, M, tm));
+        R.n = M.nmerged;
+        nrows = M.nmerged; lmax = 0;
+        TRY(chip_rows_alloc_soa(&R, (size_t)R.n));
+        if (M.n) {
+            DevBuf<u32> d_lmax;
+            TRY(d_lmax.alloc(1));
+            HIP_TRY(hipMemsetAsync(d_lmax.p, 0, sizeof(u32), s));
+            hipLaunchKernelGGL(rows_compact_kernel, dim3((unsigned)div_up(M.n, 256)), dim3(256), 0, s, M.keys.p,
+                               M.head.p, M.mend.p, M.seg.p, M.idx.p, M.n, R.set_id.p, R.univ.p, R.gs.p, R.ge.p, d_lmax.p);
+            TRY(read_count(ctx, d_lmax.p, &lmax));
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    if (nrows) {
+        HIP_TRY(hipMemcpyAsync(o_set, R.set_id.p, sizeof(i32) * nrows, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(o_seg, R.univ.p, sizeof(i32) * nrows, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(o_start, R.gs.p, sizeof(u32) * nrows, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(o_end, R.ge.p, sizeof(u32) * nrows, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipMemcpyAsync(o_mcnt, B.mcnt.p, sizeof(u32) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(o_blmax, B.blmax.p, sizeof(u32) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    if (want_sum) HIP_TRY(hipMemcpyAsync(o_bsum, B.bsum.p, sizeof(u64) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(o_bstart, B.bstart.p, sizeof(u32) * ((size_t)nb + 1), hipMemcpyDeviceToHost, s));
+    if (nhits) HIP_TRY(hipMemcpyAsync(o_S, B.S.p, sizeof(uint4) * (size_t)nhits, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    tm.finish();
+    scalars[0] = nhits; scalars[1] = nrows; scalars[2] = lmax; scalars[3] = overflow ? 1 : 0; scalars[4] = radix ? 1 : 0;
+    return 0;
+}
+
 extern "C" int catchhip_cover_scan_first_seen(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T,
                                               i32 mismatches, i32 lcf_thres, i32 island, i32 cover_extension,
                                               i32 mode, const u32 *anchor_order, catchhip_rows **out, i64 *nrows) {

@@ -331,6 +331,98 @@ class Context:
                                                      int(x.size), _ptr(out, c_u32p)))
         return out[:x.size]
 
+    # -- test entry point of the row build (tests/test_row_build.py) -------
+    ROW_BUILDS = {"bucketed": 0, "radix": 1, "radix_if_overflow": 2}
+    BK_NONE = 0xffffffff
+
+    def selftest_row_build(self, hits, nb, form="scattered", hit_slots=None, wave_hits=None, bucket_set=None,
+                           run_cnt=None, nruns=0, bounds=None, dedupe=False, want_sum=True, build="bucketed",
+                           emit="host"):
+        """catchhip_selftest_row_build: the row build's own functions on hit records filed the way a producer files
+        them.  hits: (n, 4) uint32 {start, end, segment, bucket} in ARRIVAL order; a hit's rank is its arrival index
+        inside its bucket.  form:
+          "scattered"  record d = a work item; hit_slots (ascending slot numbers, one per hit; default 0..n-1) says
+                       which work items hit, the others are misses (rank BK_NONE, record left as garbage);
+          "compact"    the same with compact filing: wave_hits[w] hits stand at the front of slots 64 w ..;
+          "grouped"    the records stand at bstart[bucket] + rank already; run_cnt (nb, stride) / nruns as the
+                       key-grouped join leaves its anchor runs.
+        Returns a dict: set / seg / start / end (the emitted table), mcnt / blmax / bsum per bucket, bstart, S (the
+        grouped records after the merge, (hits, 4)), hits, rows, lmax, overflow, radix."""
+        h = np.ascontiguousarray(hits, dtype=np.uint32).reshape(-1, 4)
+        n, nb = h.shape[0], int(nb)
+        bucket = h[:, 3].astype(np.int64)
+        if n and int(bucket.max()) >= nb:
+            raise ValueError("selftest_row_build: a hit names a bucket past nb")
+        bcnt = np.bincount(bucket, minlength=nb).astype(np.uint32)
+        bstart = np.zeros(nb + 1, dtype=np.uint32)
+        np.cumsum(bcnt, out=bstart[1:])
+        order = np.argsort(bucket, kind="stable")           # arrival order kept inside a bucket
+        rank_of = np.zeros(n, dtype=np.uint32)
+        rank_of[order] = (np.arange(n, dtype=np.int64) - bstart[bucket[order]].astype(np.int64)).astype(np.uint32)
+        rec = rank = wcnt = d_bcnt = d_bstart = d_runs = None
+        stride = 0
+        if form == "grouped":
+            rec = np.ascontiguousarray(h[order])
+            d_bstart = bstart
+            n_rec = n
+            if run_cnt is not None:
+                d_runs = np.ascontiguousarray(run_cnt, dtype=np.uint32).reshape(nb, -1)
+                stride = d_runs.shape[1]
+        else:
+            if form == "compact":
+                wave_hits = np.asarray(wave_hits, dtype=np.int64)
+                if wave_hits.sum() != n or (wave_hits.size and (wave_hits.min() < 0 or wave_hits.max() > 64)):
+                    raise ValueError("selftest_row_build: wave_hits must hold n hits, at most 64 per wave")
+                first = np.repeat(64 * np.arange(wave_hits.size, dtype=np.int64) - (np.cumsum(wave_hits) - wave_hits),
+                                  wave_hits)
+                hit_slots = first + np.arange(n, dtype=np.int64)
+                nslots = 64 * wave_hits.size
+                wcnt = np.ascontiguousarray(np.append(wave_hits, 0), dtype=np.uint32)
+            elif form == "scattered":
+                hit_slots = np.arange(n, dtype=np.int64) if hit_slots is None else np.asarray(hit_slots, dtype=np.int64)
+                if hit_slots.size != n or (n > 1 and (np.diff(hit_slots) <= 0).any()) or (n and hit_slots[0] < 0):
+                    raise ValueError("selftest_row_build: hit_slots must be n ascending slot numbers")
+                nslots = int(hit_slots[-1]) + 1 if n else 0
+            else:
+                raise ValueError("selftest_row_build: form %r" % (form,))
+            # slots without a hit: a record that would do damage if anybody read it, and no rank
+            rec = np.full((max(nslots, 1), 4), 0xdeadbeef, dtype=np.uint32)
+            rank = np.full(max(nslots, 1), self.BK_NONE, dtype=np.uint32)
+            rec[hit_slots] = h
+            rank[hit_slots] = rank_of
+            if form == "compact":                            # (compact filing never looks at the ranks past the hits)
+                rank[np.setdiff1d(np.arange(nslots), hit_slots)] = 0
+            d_bcnt = bcnt
+            n_rec = nslots
+        bs = None if bucket_set is None else np.ascontiguousarray(bucket_set, dtype=np.int32)
+        if bs is not None and bs.size != nb:
+            raise ValueError("selftest_row_build: bucket_set must have nb entries")
+        bd = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.uint32)
+        opt = np.array([int(bool(dedupe)), int(bool(want_sum)), self.ROW_BUILDS[build],
+                        {"host": 0, "device": 1}[emit]], dtype=np.int32)
+        cap = max(n, 1)
+        o_set, o_seg = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        o_start, o_end = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        o_mcnt, o_blmax = np.zeros(nb, dtype=np.uint32), np.zeros(nb, dtype=np.uint32)
+        o_bsum = np.zeros(nb, dtype=np.uint64)
+        o_S = np.zeros((cap, 4), dtype=np.uint32)
+        o_bstart = np.zeros(nb + 1, dtype=np.uint32)
+        scalars = np.zeros(5, dtype=np.int64)
+
+        def p(a, t):
+            return None if a is None else _ptr(a, t)
+        check(self._L.catchhip_selftest_row_build(
+            self._h, p(rec, c_u32p), p(rank, c_u32p), p(wcnt, c_u32p), int(n_rec), p(d_bcnt, c_u32p),
+            p(d_bstart, c_u32p), nb, p(bs, c_i32p), p(d_runs, c_u32p), int(stride), int(nruns), p(bd, c_u32p),
+            0 if bd is None else int(bd.size) - 1, _ptr(opt, c_i32p), _ptr(o_set, c_i32p), _ptr(o_seg, c_i32p),
+            _ptr(o_start, c_u32p), _ptr(o_end, c_u32p), _ptr(o_mcnt, c_u32p), _ptr(o_blmax, c_u32p),
+            _ptr(o_bsum, c_u64p), _ptr(o_S, c_u32p), _ptr(o_bstart, c_u32p), _ptr(scalars, c_i64p)))
+        rows = int(scalars[1])
+        return {"set": o_set[:rows], "seg": o_seg[:rows], "start": o_start[:rows], "end": o_end[:rows],
+                "mcnt": o_mcnt, "blmax": o_blmax, "bsum": o_bsum if want_sum else None, "bstart": o_bstart,
+                "S": o_S[:n], "hits": int(scalars[0]), "rows": rows, "lmax": int(scalars[2]),
+                "overflow": bool(scalars[3]), "radix": bool(scalars[4])}
+
     # -- near-duplicate filter --------------------------------------------
     def ndf_hamming(self, probe_strs, L, positions, dist_thres):
         n = len(probe_strs)

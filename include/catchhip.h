@@ -512,6 +512,36 @@ int catchhip_selftest_wave(catchhip_ctx *ctx, const uint32_t *in, int64_t n,
                            uint32_t *out32, uint64_t *out64);
 int catchhip_selftest_find_segment(catchhip_ctx *ctx, const uint32_t *off, int64_t n,
                                    const uint32_t *x, int64_t nx, uint32_t *out);
+/* Test entry point of the bucketed row build (csrc/rows_bucket.inc and its host side
+ * in csrc/scan.hip); tests/test_row_build.py compares it with a sequential merge in
+ * NumPy.  No reference counterpart.  Hit records go in as a producer files them, the
+ * build's own functions run as the scans call them, everything they leave comes out.
+ * rec: nrec records of 4 words {start, end, segment, bucket}, nb buckets.  Producer:
+ *  - scattered (bstart_in == NULL): rank[d] = arrival index of record d inside its
+ *    bucket or 0xffffffff for a miss, bcnt[b] = hits of bucket b; with wcnt (one word
+ *    per 64 records) only the first wcnt[d / 64] records of every 64 are looked at;
+ *  - grouped (bstart_in: nb + 1 offsets): record i already stands at its place;
+ *    run_cnt (or NULL) [b * run_stride + a] = length of sorted run a < nruns of bucket b.
+ * bucket_set (or NULL): bucket -> set id.  bounds: nbounds + 1 segment offsets of the
+ * start coordinates, needed by the radix build only.
+ * opt: [0] dedupe (equal ranges collapse, nothing merges), [1] per-bucket sums wanted,
+ * [2] 0 = bucketed build, 1 = radix build, 2 = radix build iff a bucket overflowed,
+ * [3] emit 0 = with the counts known to the host, 1 = one slot per hit, counts read
+ * on the device.  Scattered records only for [2] != 0.
+ * Out: the table (o_set / o_seg / o_start / o_end, room for one row per hit), per
+ * bucket o_mcnt / o_blmax / o_bsum (nb each; o_bsum only with opt[1]), o_bstart
+ * (nb + 1), o_S = the grouped records after the merge (4 words per hit), scalars[5] =
+ * hits, rows, longest row, overflow flag, radix build used.
+ * CATCHHIP_EINVAL when a rank, a bucket or an offset would point outside its array. */
+int catchhip_selftest_row_build(catchhip_ctx *ctx, const uint32_t *rec, const uint32_t *rank,
+                                const uint32_t *wcnt, int64_t nrec, const uint32_t *bcnt,
+                                const uint32_t *bstart_in, int64_t nb, const int32_t *bucket_set,
+                                const uint32_t *run_cnt, int32_t run_stride, int32_t nruns,
+                                const uint32_t *bounds, int64_t nbounds, const int32_t *opt,
+                                int32_t *o_set, int32_t *o_seg, uint32_t *o_start,
+                                uint32_t *o_end, uint32_t *o_mcnt, uint32_t *o_blmax,
+                                uint64_t *o_bsum, uint32_t *o_S, uint32_t *o_bstart,
+                                int64_t *scalars);
 /* Which RCCL the communicators of this library go through: "RCCL version code V
  * from <file> (<how it was chosen>)".  The library opens ONE copy by path
  * (CATCHHIP_RCCL_PATH, else /opt/rocm/lib/librccl.so) instead of whatever file of
