@@ -107,6 +107,9 @@ PROTOTYPES = {
         c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int64, ctypes.c_int32, c_vpp, c_i64p, c_i64p]),
     "catchhip_rows_prune": (ctypes.c_int, [
         c_vp, c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int64, ctypes.c_int32, c_u8p, c_i64p, c_i64p]),
+    "catchhip_rows_pick_gains": (ctypes.c_int, [
+        c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int64, c_u32p, c_i64p, ctypes.c_int64, c_i64p, c_i64p,
+        c_u64p, c_i32p, c_i64p]),
     "catchhip_rows_fetch_gain0": (ctypes.c_int, [
         c_vp, c_vp, ctypes.c_int64, c_u32p, c_i64p]),
     "catchhip_setcover_grid": (ctypes.c_int, [

@@ -18,7 +18,10 @@ reference) keeps an existing probe set and designs only the probes that bring
 the targets up to the required coverage next to it; --coverage-depth D (no
 counterpart either) designs a set in which D probes cover every base, one
 greedy layer per unit of depth; --prune-redundant (nor this) drops the selected
-probes that cover nothing alone.  --print-analysis and the
+probes that cover nothing alone; --max-probes N (nor this) keeps, over all
+datasets, the N set cover picks that added the most coverage when they were
+taken, and --write-coverage-curve writes how coverage grows with the number
+of probes.  --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
 """
@@ -151,6 +154,32 @@ def parse_args(argv=None, args_type="basic"):
                         "existing probes count and stay; with --coverage-depth "
                         "above 1 the first k layers are no longer the design "
                         "at depth k")
+    p.add_argument("--max-probes", type=int, default=None, metavar="N",
+                   help="a probe budget: after the set cover, keep only N of "
+                        "its picks over all datasets -- the picks are merged "
+                        "by the number of bases each covered first when it was "
+                        "taken (ties to the earlier dataset), so every dataset "
+                        "keeps the first picks of its own order; with -c 1.0 "
+                        "and neither --identify nor --avoid-genomes this is "
+                        "the greedy choice of N probes for maximum coverage "
+                        "over all datasets together, otherwise a prefix rule; "
+                        "N counts set cover picks, a probe picked for several "
+                        "datasets once (--expand-n and "
+                        "--add-reverse-complements change the final count)")
+    p.add_argument("--write-coverage-curve", metavar="FILE",
+                   help="write a TSV of the coverage reached by the first k "
+                        "picks of every dataset (columns dataset, probes, "
+                        "bases_covered, bases_coverable, fraction, "
+                        "worst_genome, worst_genome_fraction); with several "
+                        "datasets a block '*' follows for the picks merged by "
+                        "gain, totals only; the probes column counts set cover "
+                        "PICKS in every block -- in '*' a probe picked for two "
+                        "datasets is two picks, so row k there can stand for "
+                        "fewer than k probes written, and --max-probes N may "
+                        "cut at a row beyond N")
+    p.add_argument("--coverage-curve-points", type=int, default=100, metavar="P",
+                   help="about how many pick counts per dataset the coverage "
+                        "curve is measured at (the last pick always is)")
     p.add_argument("--add-adapters", action="store_true",
                    help="add PCR adapters to both ends of every probe")
     p.add_argument("--adapter-a", nargs=2,
@@ -161,6 +190,44 @@ def parse_args(argv=None, args_type="basic"):
     args = p.parse_args(argv)
     args.args_type = args_type
     return args
+
+
+def write_coverage_curve(path, names, scf):
+    """--write-coverage-curve: per dataset the rows of scf.last_coverage_curve
+    (measured on the device at the dataset's checkpoints); with several
+    datasets a block '*' for the picks of all datasets merged by gain
+    (set_cover_filter.allocate_budget's order), totals only: the cumulative sum
+    of the merged gains on top of what was covered before the first pick.
+    The `probes` column counts PICKS in every block.  In '*' a probe picked
+    for two datasets counts twice, while the designer writes it once and
+    --max-probes counts it once: the cut of a budget N is the row
+    sum(scf.last_budget_kept) of '*', which can lie beyond N."""
+    def frac(a, b):
+        return "%.6f" % (a / b) if b else "NA"
+    with open(path, "w") as f:
+        f.write("\t".join(("dataset", "probes", "bases_covered", "bases_coverable", "fraction",
+                           "worst_genome", "worst_genome_fraction")) + "\n")
+        for name, curve in zip(names, scf.last_coverage_curve):
+            for k, cov, coverable, wu, wc, wd in curve:
+                f.write("%s\t%d\t%d\t%d\t%s\t%s\t%s\n" % (
+                    name, k, cov, coverable, frac(cov, coverable),
+                    "NA" if wu < 0 else str(wu), "NA" if wu < 0 else frac(wc, wd)))
+        if len(names) > 1:
+            gains = [[int(x) for x in g] for g in scf.last_pick_gains]
+            total = sum(len(g) for g in gains)
+            coverable = before = 0
+            for g, curve in zip(gains, scf.last_coverage_curve):
+                if curve:
+                    coverable += curve[-1][2]
+                    before += curve[-1][1] - sum(g[:curve[-1][0]])
+            cov, taken = before, [0] * len(gains)
+            for k in range(1, total + 1):
+                # the next pick of the merge: the largest next gain, the earlier dataset among equals
+                gi = max((i for i in range(len(gains)) if taken[i] < len(gains[i])),
+                         key=lambda i: (gains[i][taken[i]], -i))
+                cov += gains[gi][taken[gi]]
+                taken[gi] += 1
+                f.write("*\t%d\t%d\t%d\t%s\tNA\tNA\n" % (k, cov, coverable, frac(cov, coverable)))
 
 
 def main(args):
@@ -245,6 +312,33 @@ def main(args):
                              "--cluster-from-fragments (a default of "
                              "design_large.py): nothing is clustered; set "
                              "--cluster-from-fragments to 0 as well"))
+    want_gains = args.max_probes is not None or bool(args.write_coverage_curve)
+    if args.coverage_curve_points < 1:
+        raise Exception("--coverage-curve-points must be at least 1, not %d"
+                        % args.coverage_curve_points)
+    if args.max_probes is not None and args.max_probes < 1:
+        raise Exception("--max-probes must be at least 1, not %d" % args.max_probes)
+    if want_gains:
+        opt = "--max-probes" if args.max_probes is not None else "--write-coverage-curve"
+        if args.skip_set_cover:
+            raise Exception(("Cannot use %s with --skip-set-cover: it is the "
+                             "set cover's picks whose gains are measured") % opt)
+        if args.cluster_and_design_separately:
+            raise Exception(("Cannot use %s with "
+                             "--cluster-and-design-separately (a default of "
+                             "design_large.py): the gains are measured against "
+                             "each dataset as a whole; set "
+                             "--cluster-and-design-separately to 0 (and, where "
+                             "it is set, --cluster-from-fragments to 0 too)") % opt)
+        if args.cluster_from_fragments:
+            raise Exception(("Cannot use %s with "
+                             "--cluster-from-fragments (a default of "
+                             "design_large.py): nothing is clustered; set "
+                             "--cluster-from-fragments to 0 as well") % opt)
+        if args.coverage_depth > 1:
+            raise Exception(("Cannot use %s with --coverage-depth above 1: "
+                             "what a pick adds is then no longer the bases it "
+                             "covers first") % opt)
     if args.cluster_from_fragments and not args.cluster_and_design_separately:
         raise Exception(("Cannot use --cluster-from-fragments without also "
                          "setting --cluster-and-design-separately"))
@@ -340,7 +434,9 @@ def main(args):
         coverage=args.coverage, cover_extension=args.cover_extension,
         kmer_probe_map_k=k_scf, fixed_probes=existing_probes,
         coverage_depth=args.coverage_depth,
-        prune_redundant=args.prune_redundant)
+        prune_redundant=args.prune_redundant,
+        max_probes=args.max_probes, pick_gains=want_gains,
+        curve_points=args.coverage_curve_points)
     filters.append(scf)
     if args.add_adapters:      # bin/design.py:345-365 (default sequences :350, :354)
         from catch_amd.filter import adapter_filter
@@ -385,6 +481,22 @@ def main(args):
     if args.prune_redundant:
         for fn, sizes, gone in zip(args.dataset, scf.last_layer_sizes, scf.last_pruned):
             logger.info("%s: %d picked, %d redundant", os.path.basename(fn), sum(sizes), len(gone))
+    if want_gains:
+        names = [os.path.basename(fn) for fn in args.dataset]
+        for name, gains, kept, curve in zip(names, scf.last_pick_gains, scf.last_budget_kept,
+                                            scf.last_coverage_curve):
+            at = [row for row in curve if row[0] == kept]
+            if at:
+                _k, cov, coverable, wu, wc, wd = at[0]
+                logger.info("%s: kept %d of %d picks, %d of %d coverable bases, worst genome %d at %.6f",
+                            name, kept, len(gains), cov, coverable, wu, wc / wd if wd else 1.0)
+            else:
+                logger.info("%s: kept %d of %d picks", name, kept, len(gains))
+        if args.max_probes is not None:
+            logger.info("--max-probes %d: %d set cover picks kept, %d probes in the output",
+                        args.max_probes, sum(scf.last_budget_kept), len(pb.final_probes))
+        if args.write_coverage_curve:
+            write_coverage_curve(args.write_coverage_curve, names, scf)
     if args.write_probe_fasta:
         seq_io.write_probe_fasta(pb.final_probes, args.write_probe_fasta)
     if (args.print_analysis or args.write_analysis_to_tsv or

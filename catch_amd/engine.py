@@ -743,6 +743,8 @@ class Rows:
         self.n = int(n)
         self.ngenomes = ngenomes      # universes of the coordinate space (None: the maker did not say)
         self.last_prune_rounds = 0    # rounds the device took in the last prune() of these rows
+        self.last_gains_ms = 0.0      # device time and launches of the last pick_gains() of these rows, summed over
+        self.last_gains_launches = 0  # the library calls it was split into
 
     @staticmethod
     def scan(ctx, probes, targets, mismatches, lcf_thres, island=0,
@@ -925,6 +927,67 @@ class Rows:
         assert int(gone.sum()) == nrem.value
         self.last_prune_rounds = int(rounds.value)
         return pk[~gone].tolist(), pk[gone][::-1].tolist()
+
+    # checkpoints x universes of one catchhip_rows_pick_gains call stay below this (the library refuses 2^31 and more)
+    PICK_GAINS_TABLE_LIMIT = 1 << 31
+
+    def pick_gains(self, num_sets, picks, checkpoints=None, denom=None, covered0=None):
+        """catchhip_rows_pick_gains -> (gains uint32[npicks], covered_total
+        uint64[ncheck], worst_universe int32[ncheck], worst_covered
+        int64[ncheck]); the last three are None without checkpoints.  gains[i] =
+        the bases that picks[i] (set ids in pick order) covered first.
+        checkpoints: pick counts in [1, npicks], strictly ascending; per
+        checkpoint k the bases the first k picks cover (plus covered0[u], per
+        universe; None: zeros), in total and in the universe with the smallest
+        share of denom[u] (-1: no universe has a positive denom).  A checkpoint
+        list whose table would not fit one call is split over several calls;
+        the device time and the launches of all of them are left in
+        `last_gains_ms` / `last_gains_launches`."""
+        pk = np.ascontiguousarray(picks, dtype=np.int64)
+        npk = int(pk.size)
+        gains = np.zeros(max(npk, 1), dtype=np.uint32)
+        self.last_gains_ms, self.last_gains_launches = 0.0, 0
+
+        def fn(*args):
+            rc = self.ctx._L.catchhip_rows_pick_gains(*args)
+            if rc == 0 and npk:                  # (no picks: the library returns at once, nothing is timed)
+                ms, nl = self.ctx.kernel_ms(PHASE_ROWS)
+                self.last_gains_ms += ms
+                self.last_gains_launches += nl
+            return rc
+        if checkpoints is None or len(checkpoints) == 0:
+            check(fn(self.ctx._h, self._h, int(num_sets), _ptr(pk, c_i64p) if npk else None, npk,
+                     _ptr(gains, c_u32p), None, 0, None, None, None, None, None))
+            return gains[:npk], None, None, None
+        if self.ngenomes is None:
+            raise ValueError("pick_gains: rows of an unknown number of universes")
+        if denom is None:
+            raise ValueError("pick_gains: checkpoints need denom")
+        ng = int(self.ngenomes)
+        ck = np.ascontiguousarray(checkpoints, dtype=np.int64)
+        dn = np.ascontiguousarray(denom, dtype=np.int64)
+        c0 = None if covered0 is None else np.ascontiguousarray(covered0, dtype=np.int64)
+        if dn.size != ng or (c0 is not None and c0.size != ng):
+            raise ValueError("pick_gains: denom / covered0 must hold one value per universe (%d)" % ng)
+        if ng == 0:
+            dn = np.zeros(1, np.int64)
+            c0 = None
+        nc = int(ck.size)
+        tot = np.zeros(nc, dtype=np.uint64)
+        wu = np.zeros(nc, dtype=np.int32)
+        wc = np.zeros(nc, dtype=np.int64)
+        per_call = max(1, (self.PICK_GAINS_TABLE_LIMIT - 1) // max(ng, 1))
+        for lo in range(0, nc, per_call):
+            hi = min(nc, lo + per_call)
+            part = np.ascontiguousarray(ck[lo:hi])
+            t = np.zeros(hi - lo, dtype=np.uint64)
+            u = np.zeros(hi - lo, dtype=np.int32)
+            c = np.zeros(hi - lo, dtype=np.int64)
+            check(fn(self.ctx._h, self._h, int(num_sets), _ptr(pk, c_i64p) if npk else None, npk,
+                     _ptr(gains, c_u32p), _ptr(part, c_i64p), hi - lo, _ptr(dn, c_i64p),
+                     None if c0 is None else _ptr(c0, c_i64p), _ptr(t, c_u64p), _ptr(u, c_i32p), _ptr(c, c_i64p)))
+            tot[lo:hi], wu[lo:hi], wc[lo:hi] = t, u, c
+        return gains[:npk], tot, wu, wc
 
     def fetch_gain0(self, num_sets):
         """catchhip_rows_fetch_gain0 -> uint32[min(num_sets, held)] (None: the rows hold no gain0)."""

@@ -282,6 +282,8 @@ class ProbeDesigner:
             return None                  # layers of a coverage depth: the host front end (SetCoverFilter._filter_strs_depth)
         if getattr(scf, "prune_redundant", False):
             return None                  # pruning needs the group's rows: the host front end, as for a coverage depth
+        if getattr(scf, "pick_gains", False):
+            return None                  # so do the gains per pick (and the probe budget that rests on them)
         skip, L = self.seq_length_to_skip, self.probe_length
         total, ngroups = 0, 0
         if isinstance(genomes, ClusteredFragments):

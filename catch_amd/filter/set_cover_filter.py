@@ -13,7 +13,10 @@ owns already; the filter then selects only what they leave uncovered
 covered by that many selected probes, one greedy layer per unit of depth
 (_filter_strs_depth).  `prune_redundant` (a keyword too) looks back at the picks
 once the design is complete and drops those that cover nothing alone
-(engine.Rows.prune).
+(engine.Rows.prune).  `pick_gains` (a keyword) reports what every pick added
+when it was taken and the coverage after the first k picks
+(engine.Rows.pick_gains); `max_probes` (a keyword) keeps, over all groups, only
+the N picks with the largest such gains (allocate_budget).
 
 Not supported (raises NotImplementedError): custom hybridization functions
 loaded from a Python file (`custom_cover_range_fn`, :288-299) -- an arbitrary
@@ -52,16 +55,19 @@ def _reverse_complement(s):
 
 class _KeywordsBeyondInit(type):
     """SetCoverFilter(..., fixed_probes=None, coverage_depth=1,
-    prune_redundant=False): `coverage_depth` and `prune_redundant` are keywords
-    of the CALL of the class, taken here and handed to the new object after
-    __init__ ran.  __init__ itself stays the reference's argument list followed
-    by `fixed_probes`, the form its callers and the signature checks of the
-    extension know; the two can only be given by name."""
+    prune_redundant=False, max_probes=None, pick_gains=False,
+    curve_points=100): everything after `fixed_probes` is a keyword of the CALL
+    of the class, taken here and handed to the new object after __init__ ran.
+    __init__ itself stays the reference's argument list followed by
+    `fixed_probes`, the form its callers and the signature checks of the
+    extension know; the others can only be given by name."""
 
-    def __call__(cls, *args, coverage_depth=1, prune_redundant=False, **kwargs):
+    def __call__(cls, *args, coverage_depth=1, prune_redundant=False, max_probes=None, pick_gains=False,
+                 curve_points=100, **kwargs):
         obj = super().__call__(*args, **kwargs)
         obj._set_coverage_depth(coverage_depth)
         obj._set_prune_redundant(prune_redundant)
+        obj._set_budget(max_probes, pick_gains, curve_points)
         return obj
 
 
@@ -136,6 +142,43 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         self.last_layer_sizes = []
         self.prune_redundant = False   # (SetCoverFilter(..., prune_redundant=True) sets it: _KeywordsBeyondInit)
         self.last_pruned = []
+        self.max_probes = None      # (SetCoverFilter(..., max_probes=N / pick_gains=True / curve_points=P): _KeywordsBeyondInit)
+        self.pick_gains = False
+        self.curve_points = 100
+        self.last_pick_gains = []
+        self.last_budget_kept = []
+        self.last_coverage_curve = []
+
+    def _set_budget(self, max_probes, pick_gains, curve_points):
+        """The probe budget and what it rests on (not arguments of the
+        reference's class).  pick_gains: after the solve (and the pruning) of a
+        group, last_pick_gains[group][i] = the bases its i-th pick covered first
+        and last_coverage_curve[group] = rows (k, covered, coverable, worst
+        universe, its covered, its denominator) at about curve_points pick
+        counts k, the last one included.  max_probes = N (implies pick_gains):
+        over all groups only the N picks that a merge of the groups' pick
+        sequences by gain takes first are kept (allocate_budget); a probe picked
+        for several groups counts once, as the designer writes it once; every group
+        keeps a prefix of its picks, last_budget_kept[group] its length.  Only
+        at coverage 1.0 without ranks is that the greedy for maximum coverage
+        over all groups together."""
+        if max_probes is not None:
+            if (isinstance(max_probes, bool) or not isinstance(max_probes, (int, np.integer))
+                    or max_probes < 1):
+                raise ValueError("max_probes must be an integer >= 1 (or None), not %r" % (max_probes,))
+            max_probes = int(max_probes)
+        if not isinstance(pick_gains, (bool, np.bool_)):
+            raise ValueError("pick_gains must be True or False, not %r" % (pick_gains,))
+        if (isinstance(curve_points, bool) or not isinstance(curve_points, (int, np.integer))
+                or curve_points < 1):
+            raise ValueError("curve_points must be an integer >= 1, not %r" % (curve_points,))
+        self.max_probes = max_probes
+        self.pick_gains = bool(pick_gains) or max_probes is not None
+        self.curve_points = int(curve_points)
+        if self.pick_gains and self.coverage_depth > 1:
+            raise NotImplementedError(
+                "pick_gains / max_probes cannot be combined with coverage_depth > 1: "
+                "a gain is then no longer the bases covered first")
 
     def _set_prune_redundant(self, prune_redundant):
         """Whether the picks are looked at again once the design is complete (not
@@ -288,8 +331,8 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         if self.fixed_probes:
             return self._filter_strs_extend(input_strs, target_genomes_grouped,
                                             assume_unique)
-        if self.coverage_depth > 1 or self.prune_redundant:
-            # (pruning needs the group's rows: the layered path keeps them, at depth 1 too)
+        if self.coverage_depth > 1 or self.prune_redundant or self.pick_gains:
+            # (pruning and the gains need the group's rows: the layered path keeps them, at depth 1 too)
             return self._filter_strs_depth(input_strs, target_genomes_grouped,
                                            assume_unique)
         if only is None and parallel.world().size > 1:
@@ -411,6 +454,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                        subtract_ms=0.0, rows_fixed=0, rows_reduced=0)
         if self.prune_redundant:
             timings.update(prune_ms=0.0, prune_launches=0, prune_rounds=0, pruned=0)
+        budget = _Budget(self, ctx, len(input_strs), timings)
 
         def add_phases(names):
             for name, ph in names:
@@ -425,68 +469,76 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         fowner = np.zeros(len(funiq), dtype=np.int32)     # one set: only their union matters
         scan_args = (self.mismatches, self.lcf_thres, self.island_of_exact_match,
                      self.cover_extension, self.scan_mode)
-        for gi, strs in enumerate(input_strs):
-            if len(strs) == 0:
-                continue
-            target_genomes = target_genomes_grouped[gi]
-            ng = len(target_genomes)
-            logger.info("Building set cover sets input (group %d of %d), %d fixed probes",
-                        gi + 1, len(input_strs), len(funiq))
-            k, uniq, owner, ep, eo = probe.anchor_table(
-                strs, self.mismatches, self.lcf_thres,
-                min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
-                assume_unique=assume_unique)
-            held = []
-            try:
-                targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
-                held.append(targets)
-                probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
-                held.append(probes)
-                rows = engine.Rows.scan(ctx, probes, targets, *scan_args)
-                held.append(rows)
-                add_phases((("scan_ms", engine.PHASE_SCAN), ("verify_ms", engine.PHASE_VERIFY),
-                            ("rows_ms", engine.PHASE_ROWS)))
-                fprobes = engine.Probes(ctx, funiq, fowner, fep, feo, fk)
-                held.append(fprobes)
-                frows = engine.Rows.scan(ctx, fprobes, targets, *scan_args)
-                held.append(frows)
-                timings["fixed_scan_ms"] += sum(ctx.kernel_ms(ph)[0] for ph in (
-                    engine.PHASE_SCAN, engine.PHASE_ROWS))     # (the verify phase lies inside the scan phase)
-                reduced = rows.subtract(frows)
-                held.append(reduced)
-                timings["subtract_ms"] += ctx.kernel_ms(engine.PHASE_ROWS)[0]
-                n2 = reduced.stats(ng)[1]
-                c0 = frows.stats(ng)[1]
-                universe_p = [extension_fraction(int(a), int(b), p) for a, b, p in
-                              zip(n2, c0, self._make_universe_p(target_genomes))]
-                ranks = self._make_ranks_strs(strs, target_genomes_grouped, ctx)
-                logger.info("Solving the set cover instance of group %d of %d",
-                            gi + 1, len(input_strs))
-                ids = reduced.greedy(
-                    len(strs), ranks if ranks.any() else None,
-                    None if all(p == 1.0 for p in universe_p) else universe_p)
-                add_phases((("greedy_ms", engine.PHASE_GREEDY),
-                            ("rounds_ms", engine.PHASE_GREEDY_ROUNDS),
-                            ("claim_ms", engine.PHASE_CLAIM)))
-                timings["rows"] += rows.n
-                timings["rows_fixed"] += frows.n
-                timings["rows_reduced"] += reduced.n
-                if self.prune_redundant:
-                    # the new probes beside the fixed ones, which stay whatever happens
-                    self.last_layer_sizes[gi] = [len(ids)]
-                    ids, self.last_pruned[gi] = _prune(ctx, rows, len(strs), ids, 1, frows, timings)
-                timings["picks"] += len(ids)
-            finally:
-                for h in reversed(held):
-                    h.close()
-            num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
-            if num_bad > 0:
-                logger.warning(("Group %d: forced to choose %d less-than-ideal "
-                                "probe%s (i.e., probes that 'hit' more than "
-                                "one grouping during identification or probes "
-                                "that cover an avoided genome)"), gi + 1,
-                               num_bad, "" if num_bad == 1 else "s")
-            selected[gi] = list(ids)
+        try:
+            for gi, strs in enumerate(input_strs):
+                if len(strs) == 0:
+                    continue
+                target_genomes = target_genomes_grouped[gi]
+                ng = len(target_genomes)
+                logger.info("Building set cover sets input (group %d of %d), %d fixed probes",
+                            gi + 1, len(input_strs), len(funiq))
+                k, uniq, owner, ep, eo = probe.anchor_table(
+                    strs, self.mismatches, self.lcf_thres,
+                    min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
+                    assume_unique=assume_unique)
+                held = []
+                try:
+                    targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
+                    held.append(targets)
+                    probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
+                    held.append(probes)
+                    rows = engine.Rows.scan(ctx, probes, targets, *scan_args)
+                    held.append(rows)
+                    add_phases((("scan_ms", engine.PHASE_SCAN), ("verify_ms", engine.PHASE_VERIFY),
+                                ("rows_ms", engine.PHASE_ROWS)))
+                    fprobes = engine.Probes(ctx, funiq, fowner, fep, feo, fk)
+                    held.append(fprobes)
+                    frows = engine.Rows.scan(ctx, fprobes, targets, *scan_args)
+                    held.append(frows)
+                    timings["fixed_scan_ms"] += sum(ctx.kernel_ms(ph)[0] for ph in (
+                        engine.PHASE_SCAN, engine.PHASE_ROWS))     # (the verify phase lies inside the scan phase)
+                    reduced = rows.subtract(frows)
+                    held.append(reduced)
+                    timings["subtract_ms"] += ctx.kernel_ms(engine.PHASE_ROWS)[0]
+                    n2 = reduced.stats(ng)[1]
+                    c0 = frows.stats(ng)[1]
+                    universe_p = [extension_fraction(int(a), int(b), p) for a, b, p in
+                                  zip(n2, c0, self._make_universe_p(target_genomes))]
+                    ranks = self._make_ranks_strs(strs, target_genomes_grouped, ctx)
+                    logger.info("Solving the set cover instance of group %d of %d",
+                                gi + 1, len(input_strs))
+                    ids = reduced.greedy(
+                        len(strs), ranks if ranks.any() else None,
+                        None if all(p == 1.0 for p in universe_p) else universe_p)
+                    add_phases((("greedy_ms", engine.PHASE_GREEDY),
+                                ("rounds_ms", engine.PHASE_GREEDY_ROUNDS),
+                                ("claim_ms", engine.PHASE_CLAIM)))
+                    timings["rows"] += rows.n
+                    timings["rows_fixed"] += frows.n
+                    timings["rows_reduced"] += reduced.n
+                    if self.prune_redundant:
+                        # the new probes beside the fixed ones, which stay whatever happens
+                        self.last_layer_sizes[gi] = [len(ids)]
+                        ids, self.last_pruned[gi] = _prune(ctx, rows, len(strs), ids, 1, frows, timings)
+                    timings["picks"] += len(ids)
+                    if self.pick_gains:
+                        # the table that went to the solver; beside it the bases the fixed probes cover
+                        budget.group(gi, reduced, len(strs), ids, n2 + c0, c0)
+                finally:
+                    for h in reversed(held):
+                        if not budget.holds(h):
+                            h.close()
+                num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
+                if num_bad > 0:
+                    logger.warning(("Group %d: forced to choose %d less-than-ideal "
+                                    "probe%s (i.e., probes that 'hit' more than "
+                                    "one grouping during identification or probes "
+                                    "that cover an avoided genome)"), gi + 1,
+                                   num_bad, "" if num_bad == 1 else "s")
+                selected[gi] = list(ids)
+            budget.finish(selected, input_strs)
+        finally:
+            budget.release()         # (a group that raised: the tables kept for the cut)
         self.last_timings = timings
         return selected
 
@@ -511,7 +563,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         layers picked, last_pruned[group] the dropped ones."""
         from catch_amd import parallel
         if parallel.world().size > 1:
-            raise NotImplementedError("coverage_depth > 1 and prune_redundant run on one rank")
+            raise NotImplementedError("coverage_depth > 1, prune_redundant, pick_gains and max_probes run on one rank")
         ctx = self._context()
         selected = [[] for _ in input_strs]
         self.last_layer_sizes = [[] for _ in input_strs]
@@ -521,6 +573,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                        rows_reduced=0)
         if self.prune_redundant:
             timings.update(prune_ms=0.0, prune_launches=0, prune_rounds=0, pruned=0)
+        budget = _Budget(self, ctx, len(input_strs), timings)
 
         def add_phases(names):
             for name, ph in names:
@@ -532,87 +585,94 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         greedy_phases = (("greedy_ms", engine.PHASE_GREEDY),
                          ("rounds_ms", engine.PHASE_GREEDY_ROUNDS),
                          ("claim_ms", engine.PHASE_CLAIM))
-        for gi, strs in enumerate(input_strs):
-            if len(strs) == 0:
-                continue
-            target_genomes = target_genomes_grouped[gi]
-            ng = len(target_genomes)
-            logger.info("Building set cover sets input (group %d of %d), coverage depth %d",
-                        gi + 1, len(input_strs), self.coverage_depth)
-            k, uniq, owner, ep, eo = probe.anchor_table(
-                strs, self.mismatches, self.lcf_thres,
-                min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
-                assume_unique=assume_unique)
-            held = []
-            try:
-                targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
-                held.append(targets)
-                probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
-                held.append(probes)
-                rows = engine.Rows.scan(ctx, probes, targets, self.mismatches, self.lcf_thres,
-                                        self.island_of_exact_match, self.cover_extension,
-                                        self.scan_mode)
-                held.append(rows)
-                add_phases((("scan_ms", engine.PHASE_SCAN), ("verify_ms", engine.PHASE_VERIFY),
-                            ("rows_ms", engine.PHASE_ROWS)))
-                timings["rows"] += rows.n
-                p = self._make_universe_p(target_genomes)
-                ranks = self._make_ranks_strs(strs, target_genomes_grouped, ctx)
-                rk = ranks if ranks.any() else None
-                ids, sizes = [], []
-                for layer in range(1, self.coverage_depth + 1):
-                    if layer == 1:
-                        table, universe_p = rows, p
-                    else:
-                        table, reached = rows.below_depth(len(strs), ids, layer)
-                        held.append(table)
-                        ms, nl = ctx.kernel_ms(engine.PHASE_ROWS)
-                        timings["depth_ms"] += ms
-                        timings["depth_launches"] = timings.get("depth_launches", 0) + nl
-                        timings["rows_reduced"] += table.n
-                        if table.n == 0:
-                            # (not the end: a base that `layer` picks hold lies below the next layer's depth)
-                            logger.info("Group %d of %d: no candidate is left to raise any base to "
-                                        "depth %d; layer %d is empty", gi + 1, len(input_strs),
-                                        layer, layer)
+        try:
+            for gi, strs in enumerate(input_strs):
+                if len(strs) == 0:
+                    continue
+                target_genomes = target_genomes_grouped[gi]
+                ng = len(target_genomes)
+                logger.info("Building set cover sets input (group %d of %d), coverage depth %d",
+                            gi + 1, len(input_strs), self.coverage_depth)
+                k, uniq, owner, ep, eo = probe.anchor_table(
+                    strs, self.mismatches, self.lcf_thres,
+                    min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
+                    assume_unique=assume_unique)
+                held = []
+                try:
+                    targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
+                    held.append(targets)
+                    probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
+                    held.append(probes)
+                    rows = engine.Rows.scan(ctx, probes, targets, self.mismatches, self.lcf_thres,
+                                            self.island_of_exact_match, self.cover_extension,
+                                            self.scan_mode)
+                    held.append(rows)
+                    add_phases((("scan_ms", engine.PHASE_SCAN), ("verify_ms", engine.PHASE_VERIFY),
+                                ("rows_ms", engine.PHASE_ROWS)))
+                    timings["rows"] += rows.n
+                    p = self._make_universe_p(target_genomes)
+                    ranks = self._make_ranks_strs(strs, target_genomes_grouped, ctx)
+                    rk = ranks if ranks.any() else None
+                    ids, sizes = [], []
+                    for layer in range(1, self.coverage_depth + 1):
+                        if layer == 1:
+                            table, universe_p = rows, p
+                        else:
+                            table, reached = rows.below_depth(len(strs), ids, layer)
+                            held.append(table)
+                            ms, nl = ctx.kernel_ms(engine.PHASE_ROWS)
+                            timings["depth_ms"] += ms
+                            timings["depth_launches"] = timings.get("depth_launches", 0) + nl
+                            timings["rows_reduced"] += table.n
+                            if table.n == 0:
+                                # (not the end: a base that `layer` picks hold lies below the next layer's depth)
+                                logger.info("Group %d of %d: no candidate is left to raise any base to "
+                                            "depth %d; layer %d is empty", gi + 1, len(input_strs),
+                                            layer, layer)
+                                held.remove(table)
+                                table.close()
+                                sizes.append(0)
+                                continue
+                            n2 = table.stats(ng)[1]
+                            universe_p = [extension_fraction(int(a), int(b), q)
+                                          for a, b, q in zip(n2, reached, p)]
+                        logger.info("Solving the set cover instance of group %d of %d, layer %d of %d",
+                                    gi + 1, len(input_strs), layer, self.coverage_depth)
+                        got = table.greedy(len(strs), rk,
+                                           None if all(q == 1.0 for q in universe_p) else universe_p)
+                        add_phases(greedy_phases)
+                        if table is not rows:
                             held.remove(table)
                             table.close()
-                            sizes.append(0)
-                            continue
-                        n2 = table.stats(ng)[1]
-                        universe_p = [extension_fraction(int(a), int(b), q)
-                                      for a, b, q in zip(n2, reached, p)]
-                    logger.info("Solving the set cover instance of group %d of %d, layer %d of %d",
-                                gi + 1, len(input_strs), layer, self.coverage_depth)
-                    got = table.greedy(len(strs), rk,
-                                       None if all(q == 1.0 for q in universe_p) else universe_p)
-                    add_phases(greedy_phases)
-                    if table is not rows:
-                        held.remove(table)
-                        table.close()
-                    ids += got
-                    sizes.append(len(got))
+                        ids += got
+                        sizes.append(len(got))
+                    if self.prune_redundant:
+                        ids, self.last_pruned[gi] = _prune(ctx, rows, len(strs), ids, self.coverage_depth, None,
+                                                           timings)
+                    timings["picks"] += len(ids)
+                    if self.pick_gains:
+                        budget.group(gi, rows, len(strs), ids, rows.stats(ng)[1], None)
+                finally:
+                    for h in reversed(held):
+                        if not budget.holds(h):
+                            h.close()
+                logger.info("Group %d of %d: picks per layer %s", gi + 1, len(input_strs),
+                            " / ".join(str(x) for x in sizes))
                 if self.prune_redundant:
-                    ids, self.last_pruned[gi] = _prune(ctx, rows, len(strs), ids, self.coverage_depth, None,
-                                                       timings)
-                timings["picks"] += len(ids)
-            finally:
-                for h in reversed(held):
-                    h.close()
-            logger.info("Group %d of %d: picks per layer %s", gi + 1, len(input_strs),
-                        " / ".join(str(x) for x in sizes))
-            if self.prune_redundant:
-                logger.info("Group %d of %d: %d picked, %d redundant", gi + 1, len(input_strs),
-                            sum(sizes), len(self.last_pruned[gi]))
-            num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
-            if num_bad > 0:
-                logger.warning(("Group %d: forced to choose %d less-than-ideal "
-                                "probe%s (i.e., probes that 'hit' more than "
-                                "one grouping during identification or probes "
-                                "that cover an avoided genome)"), gi + 1,
-                               num_bad, "" if num_bad == 1 else "s")
-            selected[gi] = list(ids)
-            self.last_layer_sizes[gi] = sizes
+                    logger.info("Group %d of %d: %d picked, %d redundant", gi + 1, len(input_strs),
+                                sum(sizes), len(self.last_pruned[gi]))
+                num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
+                if num_bad > 0:
+                    logger.warning(("Group %d: forced to choose %d less-than-ideal "
+                                    "probe%s (i.e., probes that 'hit' more than "
+                                    "one grouping during identification or probes "
+                                    "that cover an avoided genome)"), gi + 1,
+                                   num_bad, "" if num_bad == 1 else "s")
+                selected[gi] = list(ids)
+                self.last_layer_sizes[gi] = sizes
+            budget.finish(selected, input_strs)
+        finally:
+            budget.release()         # (a group that raised: the tables kept for the cut)
         self.last_timings = timings
         return selected
 
@@ -1427,6 +1487,120 @@ def extension_fraction(n2, covered, p):
     if can >= n2:
         return 0.0
     return (n2 - can - 0.5) / n2
+
+
+def allocate_budget(gains_per_group, N, keys_per_group=None):
+    """How many picks every group keeps when N picks may be kept in all:
+    gains_per_group[g][i] = the bases the i-th pick of group g covered first
+    (Rows.pick_gains).  A k-way merge: the group whose next pick has the largest
+    gain gives that pick, among equal gains the earlier group, until N picks
+    are taken or every group is exhausted.  Every group keeps a PREFIX of its
+    pick order, whatever the gains look like (partial coverage, ranks and a
+    pruned list give sequences that are not monotone).  Only where every
+    group's gains are the greedy's own (coverage 1.0, no ranks: they never
+    increase) is the merged order the greedy for maximum coverage over all
+    groups together, up to ties between groups.  Trailing picks with gain 0 are
+    kept only if the budget reaches them.  keys_per_group[g][i] (optional) names
+    the i-th pick of group g: a pick whose name the merge has taken already
+    (the same probe picked for two datasets, written once) is kept without
+    counting towards N, so that N counts distinct names.  Returns the kept
+    count per group."""
+    import heapq
+    if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or N < 1:
+        raise ValueError("the probe budget must be an integer >= 1, not %r" % (N,))
+    gains = [[int(x) for x in g] for g in gains_per_group]
+    kept = [0] * len(gains)
+    heap = [(-g[0], gi) for gi, g in enumerate(gains) if g]
+    heapq.heapify(heap)
+    taken, seen = 0, set()
+    while heap and taken < N:
+        _neg, gi = heapq.heappop(heap)
+        key = (gi, kept[gi]) if keys_per_group is None else keys_per_group[gi][kept[gi]]
+        taken += key not in seen
+        seen.add(key)
+        kept[gi] += 1
+        if kept[gi] < len(gains[gi]):
+            heapq.heappush(heap, (-gains[gi][kept[gi]], gi))
+    return kept
+
+
+def curve_checkpoints(n, points, extra=()):
+    """The pick counts at which a group of n picks is measured: ceil(j n /
+    points) for j = 1..points, made distinct, n always among them, and those of
+    `extra` that lie in 1..n."""
+    ks = {-(-j * n // points) for j in range(1, points + 1)} | {n} | {int(k) for k in extra}
+    return sorted(k for k in ks if 1 <= k <= n)
+
+
+class _Budget:
+    """The pick_gains / max_probes part of a _filter_strs_* run over all its
+    groups: one Rows.pick_gains call per group on the table that went to the
+    solver, and with max_probes the cut over all groups once the last one is
+    solved -- until then every group's table stays on the device (a second
+    small call measures the coverage at the group's cut)."""
+
+    def __init__(self, flt, ctx, ngroups, timings):
+        self.flt, self.ctx, self.timings = flt, ctx, timings
+        self.kept_tables = {}       # group -> (table, num_sets, ids, denom, covered0)
+        flt.last_pick_gains = [np.zeros(0, dtype=np.uint32) for _ in range(ngroups)]
+        flt.last_coverage_curve = [[] for _ in range(ngroups)]
+        flt.last_budget_kept = [0] * ngroups
+        if flt.pick_gains:
+            timings.update(gains_ms=0.0, gains_launches=0)
+
+    def holds(self, h):
+        return any(h is t[0] for t in self.kept_tables.values())
+
+    def _call(self, table, num_sets, ids, checkpoints, denom, covered0):
+        gains, tot, wu, wc = table.pick_gains(num_sets, ids, checkpoints, denom, covered0)
+        self.timings["gains_ms"] += table.last_gains_ms              # (summed over the calls of a split list)
+        self.timings["gains_launches"] += table.last_gains_launches
+        coverable = int(np.sum(denom))
+        rows = [(int(k), int(t), coverable, int(u), int(c), int(denom[u]) if u >= 0 else 0)
+                for k, t, u, c in zip(checkpoints, tot, wu, wc)]
+        return gains, rows
+
+    def group(self, gi, table, num_sets, ids, denom, covered0):
+        flt = self.flt
+        flt.last_budget_kept[gi] = len(ids)
+        if len(ids) == 0:
+            return
+        denom = np.asarray(denom, dtype=np.int64)
+        covered0 = None if covered0 is None else np.asarray(covered0, dtype=np.int64)
+        flt.last_pick_gains[gi], flt.last_coverage_curve[gi] = self._call(
+            table, num_sets, ids, curve_checkpoints(len(ids), flt.curve_points), denom, covered0)
+        if flt.max_probes is not None:
+            self.kept_tables[gi] = (table, num_sets, list(ids), denom, covered0)
+
+    def release(self):
+        """Closes the tables held for the cut; the filter calls it whether its
+        groups went through or one of them raised."""
+        for t in self.kept_tables.values():
+            t[0].close()
+        self.kept_tables = {}
+
+    def finish(self, selected, input_strs):
+        """The cut (max_probes): selected[group] becomes the prefix kept.  The
+        budget counts distinct probe sequences: the designer writes a probe
+        picked for two groups once, so sum(last_budget_kept), which counts
+        picks, can exceed max_probes."""
+        flt = self.flt
+        try:
+            if flt.max_probes is None:
+                return
+            kept = allocate_budget(flt.last_pick_gains, flt.max_probes,
+                                   [[strs[i] for i in ids] for strs, ids in zip(input_strs, selected)])
+            for gi, k in enumerate(kept):
+                curve = flt.last_coverage_curve[gi]
+                if gi in self.kept_tables and k >= 1 and all(row[0] != k for row in curve):
+                    table, num_sets, ids, denom, covered0 = self.kept_tables[gi]
+                    _g, rows = self._call(table, num_sets, ids, [k], denom, covered0)
+                    flt.last_coverage_curve[gi] = sorted(curve + rows)
+                self.timings["picks"] -= len(selected[gi]) - k
+                selected[gi] = selected[gi][:k]
+            flt.last_budget_kept = kept
+        finally:
+            self.release()
 
 
 def _prune(ctx, rows, num_sets, ids, depth, fixed_rows, timings):

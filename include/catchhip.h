@@ -16,6 +16,8 @@
  * catchhip_rows_below_depth: one layer of a design that covers every base
  * several times); the solvers they feed are the reference's.  A third,
  * catchhip_rows_prune, takes picks away again: those that cover nothing alone.
+ * A fourth, catchhip_rows_pick_gains, reports what each pick added when it was
+ * taken and the coverage after the first k picks (designs under a probe budget).
  *
  * Coordinates.  A `targets` object is a list of sequences, concatenated in
  * the order given; consecutive sequences with the same genome index form one
@@ -370,6 +372,39 @@ int catchhip_rows_prune(catchhip_ctx *ctx, const catchhip_rows *rows,
                         const int64_t *picks, int64_t npicks, int32_t depth,
                         uint8_t *removed_flags, int64_t *nremoved,
                         int64_t *rounds);
+/* ---- gain per pick: the bases each pick covered first ------------------------
+ * picks[0..npicks) are set ids in pick order; rank(i) = i.  first(b) = the
+ * smallest rank among the picks whose set has a row of `rows` over base b
+ * (none if no pick covers b).  gains[i] (npicks values) = the number of bases b
+ * with first(b) == i: what the pick added when it was taken.  A pick without
+ * rows, or one wholly shadowed by earlier picks, gets 0.  At full coverage
+ * without ranks these are the gains the greedy solver chose by, which it keeps
+ * on the device.  checkpoints[0..ncheck) are pick counts k in [1, npicks],
+ * strictly ascending.  For checkpoint k and universe u, cov_u(k) = covered0[u]
+ * + the bases b of u with first(b) < k (covered0 == NULL: zeros).
+ * covered_total[j] = the sum of cov_u(k_j) over the universes;
+ * worst_universe[j] = the universe with denom[u] > 0 whose cov_u / denom[u] is
+ * smallest, compared exactly by 64-bit cross-multiplication, ties to the lower
+ * universe, -1 if no universe has a positive denominator; worst_covered[j] =
+ * its cov_u (0 with -1).  With ncheck == 0 the six checkpoint and universe
+ * arguments may be NULL.  All arithmetic is integer; the result depends neither
+ * on launch geometry nor on the order of atomics.  The reference has no
+ * counterpart.  `rows`: a row table in the solver's form with set ids in
+ * [0, num_sets).  npicks == 0 returns at once and requires ncheck == 0.
+ * CATCHHIP_EINVAL for a pick outside [0, num_sets) or given twice, deferred,
+ * direct or grouped rows, 2^32 - 1 target bases and more, checkpoints out of
+ * range or not strictly ascending, a denom[u] or covered0[u] + universe length
+ * outside 32 bits, and ncheck x universes >= 2^31 (the caller splits the
+ * checkpoints).  Any table below 2^31 rows is served: the kernels that take a
+ * wavefront per row compute the row number in 64 bits.  Scratch: 4 bytes per
+ * target base + 4 bytes x ncheck x universes.  Timed as phase 1. */
+int catchhip_rows_pick_gains(catchhip_ctx *ctx, const catchhip_rows *rows,
+                             int64_t num_sets, const int64_t *picks,
+                             int64_t npicks, uint32_t *gains,
+                             const int64_t *checkpoints, int64_t ncheck,
+                             const int64_t *denom, const int64_t *covered0,
+                             uint64_t *covered_total, int32_t *worst_universe,
+                             int64_t *worst_covered);
 /* One (probes, targets, mismatches) instance over n_ext cover extensions: the
  * reference's design.py run once per e (set_cover_filter.py:816-846 each time).
  * Scans once at e = 0, derives the rows at each ext[i] (catchhip_rows_extend,
