@@ -50,6 +50,7 @@ PROTOTYPES = {
     "catchhip_ctx_last_join_counters": (ctypes.c_int, [c_vp, c_i64p]),
     "catchhip_ctx_last_solver_counters": (ctypes.c_int, [c_vp, c_i64p]),
     "catchhip_ctx_last_solver_levels": (ctypes.c_int, [c_vp, c_i64p]),
+    "catchhip_ctx_last_solver_band_groups": (ctypes.c_int, [c_vp, c_i64p]),
     "catchhip_ctx_last_ndf_counters": (ctypes.c_int, [c_vp, c_i64p]),
     "catchhip_targets_create": (ctypes.c_int, [
         c_vp, c_u8p, c_i64p, c_i32p, ctypes.c_int64, ctypes.c_int32, c_vpp]),

@@ -319,6 +319,12 @@ extern "C" int catchhip_ctx_last_solver_levels(catchhip_ctx *c, i64 *out2) {
     return 0;
 }
 
+extern "C" int catchhip_ctx_last_solver_band_groups(catchhip_ctx *c, i64 *out1) {
+    ARG_CHECK(c != nullptr && out1 != nullptr);
+    *out1 = c->solver_band_groups;
+    return 0;
+}
+
 extern "C" int catchhip_ctx_last_ndf_counters(catchhip_ctx *c, i64 *out4) {
     ARG_CHECK(c != nullptr && out4 != nullptr);
     for (int i = 0; i < 4; ++i) out4[i] = c->ndf_counters[i];
@@ -842,6 +848,14 @@ extern "C" int catchhip_targets_set_groups(catchhip_ctx *ctx, catchhip_targets *
     TRY(T->seq_group.alloc((size_t)T->nseq + 1));
     HIP_TRY(hipMemcpyAsync(T->seq_group.p, sg.data(), sizeof(i32) * ((size_t)T->nseq + 1), hipMemcpyHostToDevice,
                            ctx->stream));
+    // the distinct group numbers, ascending: dense group numbers for the solver's per-group band boundaries
+    T->h_group_ids.assign(group_of_genome, group_of_genome + T->ngenomes);
+    std::sort(T->h_group_ids.begin(), T->h_group_ids.end());
+    T->h_group_ids.erase(std::unique(T->h_group_ids.begin(), T->h_group_ids.end()), T->h_group_ids.end());
+    TRY(T->group_ids.alloc(T->h_group_ids.size() + 1));
+    if (!T->h_group_ids.empty())
+        HIP_TRY(hipMemcpyAsync(T->group_ids.p, T->h_group_ids.data(), sizeof(i32) * T->h_group_ids.size(), hipMemcpyHostToDevice,
+                               ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     T->has_groups = true;
     return 0;

@@ -131,6 +131,7 @@ struct catchhip_ctx {
     i64 counters[8] = {};
     i64 ndf_counters[4] = {};      // last Hamming near-duplicate filter: probes, tables, pairs compared, edges
     i64 solver_levels[2] = {};     // row-parallel solver: gain levels gone through, bands (setcover_flat.inc)
+    i64 solver_band_groups = 0;    // row-parallel solver: groups that got band boundaries of their own (1: one row of boundaries)
     i64 solver_counters[4] = {};   // row-parallel solver: records streamed, rows counted again, bitmap words read, owner words looked at
     i64 rows_direct = 0;     // the last catchhip_setcover_filter solved from the bucketed records (catchhip_rows::rows4), no SoA table
     i64 seeds_dropped = 0;   // of counters[1]: work-list entries the seed look-up's anchor-pair filter left empty
@@ -194,6 +195,10 @@ struct catchhip_targets {
     bool has_groups = false;
     DevBuf<i32> seq_group;   // nseq: instance of the sequence's genome (catchhip_targets_set_groups)
     i32 ngroups_set = 0;     // 1 + the largest group number
+    // the distinct group numbers, ascending (host and device): a group's place in it is its DENSE number, which the
+    // row-parallel solver's per-group band boundaries go by (catchhip_rows::set_group)
+    std::vector<i32> h_group_ids;
+    DevBuf<i32> group_ids;
     DevBuf<u32> genome_off;  // ngenomes+1 global offset of each genome's first base
     i64 nwords = 0;          // 32-base words per plane (+ padding)
     DevBuf<u32> planes;      // 3 planes, SoA: plane b at planes + b*nwords
@@ -266,6 +271,12 @@ struct catchhip_rows {
     // the scan's probes / targets carried group numbers (a union of independent instances, catchhip_*_set_groups): its
     // coordinate space is a row of unlike groups, which the row-parallel solver cuts into more, smaller tiles
     bool grouped = false;
+    // grouped rows of a merged scan that carry gain0: set_group[s] = dense number (0 .. ngroups - 1: the place of the
+    // group number among the targets' distinct ones) of the group of set s, ~0 for a set none of whose probes belongs
+    // to a group of the targets (it has no rows); set_group[set_group_n] != 0: some set has probes in several groups
+    // (the solver then cuts all sets by one row of boundaries).  set_group_n = 0: not there
+    DevBuf<u32> set_group;
+    u32 set_group_n = 0, ngroups = 0;
     // cover extension of the merged rows of a cover scan (or of catchhip_rows_extend); -1: anything else (host rows,
     // unmerged ranges, deferred rows) -- catchhip_rows_extend derives only from rows made at 0
     i32 ext = -1;

@@ -1549,6 +1549,29 @@ rows_gain0_kernel(const unsigned long long *__restrict__ bsum, u32 nb, const i32
     if (v && s < ng) atomicAdd(&gain0[s], v);
 }
 
+// Rows of a scan with group numbers: the dense group number of every set (catchhip_rows::set_group, which arrives
+// all ~0, its flag word zero) from its probes' group numbers -- the place of the number in gids (ascending, distinct:
+// the targets' groups).  A probe of a group the targets do not hold pairs with nothing and says nothing about its
+// set; a set whose probes name two groups raises the flag word set_group[ng].
+__global__ void __launch_bounds__(256)
+rows_set_group_kernel(const i32 *__restrict__ probe_group, const i32 *__restrict__ set_id, u32 nprobes,
+                      const i32 *__restrict__ gids, u32 ngroups, u32 ng, u32 *__restrict__ set_group) {
+    const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nprobes) return;
+    const i32 g = probe_group[p];
+    u32 lo = 0, hi = ngroups;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (gids[mid] < g) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= ngroups || gids[lo] != g) return;
+    const i32 s = set_id[p];
+    if (s < 0 || (u32)s >= ng) return;
+    const u32 old = atomicCAS(&set_group[(u32)s], 0xffffffffu, lo);
+    if (old != 0xffffffffu && old != lo) set_group[ng] = 1u;
+}
+
 static bool join_path_ok(const catchhip_probes *P, int mm) {
     if (!P->pigeonhole || P->k <= 0 || P->pwords < 1 || P->pwords > 8) return false;
     const int nanch = (int)(P->L / P->k);
@@ -2126,6 +2149,18 @@ static int cover_scan_impl(catchhip_ctx *ctx, const catchhip_probes *P, const ca
                                    (const unsigned long long *)O.B.bsum.p, O.B.nb, bucket_set, ng, R->gain0.p);
                 R->gain0_n = ng;
                 tm.launch();
+                if (R->grouped && !T->h_group_ids.empty()) {
+                    // ... and the group of every set: the solver cuts each group's sets by that group's largest gain
+                    TRY(R->set_group.alloc((size_t)ng + 1));
+                    HIP_TRY(hipMemsetAsync(R->set_group.p, 0xff, sizeof(u32) * (size_t)ng, ctx->stream));
+                    HIP_TRY(hipMemsetAsync(R->set_group.p + ng, 0, sizeof(u32), ctx->stream));
+                    hipLaunchKernelGGL(rows_set_group_kernel, dim3((unsigned)div_up(P->nprobes, 256)), dim3(256), 0, ctx->stream,
+                                       (const i32 *)P->group.p, (const i32 *)P->set_id.p, (u32)P->nprobes,
+                                       (const i32 *)T->group_ids.p, (u32)T->h_group_ids.size(), ng, R->set_group.p);
+                    R->set_group_n = ng;
+                    R->ngroups = (u32)T->h_group_ids.size();
+                    tm.launch();
+                }
             }
         }
     } else {

@@ -57,6 +57,7 @@ struct GreedyState {
     u32 nwon;                // row-parallel solver, full coverage: npicks when this round began -- the sets accepted in it are picks[nwon .. npicks)
     u32 level[2];            // row-parallel solver, gain bands: the level of a round, by round parity (written by the apply launch before)
     u32 gmax;                // row-parallel solver, gain bands: the largest round-0 gain
+    u32 band_groups;         // row-parallel solver, gain bands: groups with boundaries of their own (gr_band_kernel)
 };
 
 // packed key = (gain << 32) | (0xFFFFFFFF - set id): gains are < 2^32 (a group's
@@ -961,6 +962,7 @@ int chip_greedy_deferred(catchhip_ctx *ctx, catchhip_rows *R, i64 num_sets, cons
     ctx->phase_ms[PHASE_CLAIM] = 0.0; ctx->phase_launches[PHASE_CLAIM] = 0;   // (only the row-parallel solver fills it)
     memset(ctx->solver_counters, 0, sizeof(ctx->solver_counters));
     memset(ctx->solver_levels, 0, sizeof(ctx->solver_levels));
+    ctx->solver_band_groups = 0;
     if (num_sets <= 0 || num_sets >= (i64)ID_MASK || !R->deferred) { *retry = 1; return 0; }
     HIP_TRY(hipSetDevice(ctx->device));
     PoolScope pool_scope(ctx);
@@ -987,6 +989,7 @@ int chip_setcover_solve(catchhip_ctx *ctx, catchhip_rows *R, i64 num_sets, const
     ctx->phase_ms[PHASE_CLAIM] = 0.0; ctx->phase_launches[PHASE_CLAIM] = 0;   // (only the row-parallel solver fills it)
     memset(ctx->solver_counters, 0, sizeof(ctx->solver_counters));
     memset(ctx->solver_levels, 0, sizeof(ctx->solver_levels));
+    ctx->solver_band_groups = 0;
     if (num_sets == 0 || R->n == 0) return 0;  // no universe has anything to cover
     ARG_CHECK(out_ids != nullptr);
     if (num_sets >= (i64)ID_MASK) { chip_set_error("setcover: more than 2^32-2 sets not supported"); return CATCHHIP_EINVAL; }
@@ -1020,7 +1023,7 @@ int chip_setcover_solve(catchhip_ctx *ctx, catchhip_rows *R, i64 num_sets, const
     // 1.68 (11.1 vs 8.0); 3.4 M (configs[2]): 5.96 vs 3.12 (20.1 vs 13.5 -- the fused family also reads back every
     // round).  So: 2^18 rows.  (Smaller instances never get here through the fused filter: below ~11 Mbases of
     // targets it queues scan and solve without a synchronisation, chip_greedy_deferred.)
-    const i64 flat_min_rows = chip_test_env_int("CATCHHIP_FLAT_MIN_ROWS", (i64)1 << 18);
+    const i64 flat_min_rows = chip_test_env_int("CATCHHIP_FLAT_MIN_ROWS", GR_MIN_ROWS);
     if (batched && R->lmax <= 257 && (i64)nrows >= flat_min_rows && nsets <= GR_MAX_SETS) {
         if (R->rows4.p) ctx->rows_direct = 1;   // (reset by catchhip_setcover_filter alone: the figure is its last call's)
         return greedy_flat(ctx, R, nsets, ranks ? h_rank.data() : nullptr, nrank, out_ids, n_out);

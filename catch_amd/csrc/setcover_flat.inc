@@ -144,7 +144,27 @@ struct FlatArgs {
     // streams the sub-tiles of the bands <= L only, and a set claims only with a gain >= T_L: every set that does not
     // claim -- asleep, or counted below T_L -- has a smaller key than every claimant, which is all the acceptance
     // rule needs.  A round without a claimant raises the level.  nbands == 1, T_0 = 1: the rounds as they were.
+    //
+    // Boundaries per group (rows of a scan with group numbers: a union of independent instances side by side, whose
+    // gains differ tenfold -- cut by the instance's largest gain every smaller group would lie below all boundaries,
+    // sleep to the last level and then run as without bands).  Group g is cut by ITS largest round-0 gain into the row
+    // band_thr[g * nbands + b] = T_b[g]; set_thr[s] = group(s) (null: one row, as above).  The level stays one
+    // number for the instance: a round of level L streams the sub-tiles of the bands <= L, and a set claims iff its
+    // exact gain reaches T_L[group(s)].  Why that is exact:
+    //  * two sets share an uncovered element only inside one group (a probe pairs with its own group's genomes only);
+    //  * inside group g every set that does not claim is asleep (round-0 gain, hence gain, below T_L[g]) or counted
+    //    below T_L[g]: its gain, hence its key, is smaller than that of every claimant of g;
+    //  * so a claimant that holds the largest key on all its words beats every alive set it shares an element with --
+    //    all the proof sketch in setcover_batched.inc needs;
+    //  * a bitmap word shared by two groups at a group border may make a claimant lose to a set of the other group it
+    //    shares no element with: acceptance only becomes more conservative there, as with one row of boundaries;
+    //  * late acceptance is harmless -- the set's gain is unchanged until it is accepted -- and the picks are ordered
+    //    by their accept-time keys.
+    // A group that has emptied its level waits the few rounds the slowest group still needs: one level, so every
+    // cross-launch hand-off (level[], wake, fresh, fr_claim) is what it was.
     const u32 *band_thr;
+    const u32 *set_thr;
+    u32 ngroups;                    // rows of band_thr
     const u8 *band;                 // band of every set (null: one band)
     u32 nbands;
 };
@@ -205,6 +225,13 @@ __device__ __forceinline__ void load_records(const FlatArgs &a, u32 buf, u32 bba
 #define GR_BAND_RATIO 650                //   boundaries in 1/1000.  S4 step, ms: 1 band 74.8-76.6; 2 bands at 0.60 / 0.65 / 0.70: 71.4 / 71.4 /
                                          //   70.1-71.0, at 0.50: 78.5, at 0.75-0.85: 76.9-78.3; 3 at 0.6 / 0.7: 75.7 / 75.9; 4 at 0.7 / 0.8: 80.3 / 73.5;
                                          //   8 at 0.75: 110.8 (every level ends with a round that claims nothing: DESIGN.md section 4 K2)
+#define GR_BAND_RATIO_GROUPED 700        // the same for a union cut group by group.  S4 step, ms, three runs each, interleaved: the union with one
+                                         //   band 70.6 / 70.5 / 70.3; 2 bands per group at 0.70: 66.9 / 67.0 / 66.7, at 0.65: 70.3 / 70.4 / 70.6 (against
+                                         //   71.0 / 70.9 / 71.8), at 0.675 / 0.725: 67.4 / 67.6, at 0.60 (5 steps): 75.9, at 0.75: 71.8; 3 bands at 0.65:
+                                         //   74.7 (the large groups, solved alone, at 0.70 beside a union with one band: 70.3 / 70.7 / 70.9 -- they do
+                                         //   not care)
+#define GR_THR_LDS 1024                 // boundaries per group: the groups whose threshold of the round's level a workgroup keeps in LDS
+#define GR_MIN_ROWS ((i64)1 << 18)       // rows from which an instance takes this solver (setcover.hip), and grouped rows their bands
 struct GrNoTileHook { __device__ __forceinline__ void operator()(u32, u32) const {} };
 // Which sub-tiles a walk takes (gain bands): those of the bands <= level; the sub-tiles of band `wake` (none: ~0)
 // are streamed for the first time -- all their records, where the partition put them (buffer 0).
@@ -420,6 +447,8 @@ gr_count_kernel(FlatArgs a, u32 round) {
     if (threadIdx.x == 0 && s_rows[3]) atomicOr(&acc[a.nsets], 1u);
 }
 
+// BYGROUP: boundaries per group (FlatArgs::set_thr) -- the threshold of a set is fetched where its gain is
+template <bool BYGROUP>
 __global__ void __launch_bounds__(GR_THREADS)
 gr_claim_kernel(FlatArgs a, u32 round) {
     __shared__ u32 s_done, s_claim;
@@ -446,6 +475,12 @@ gr_claim_kernel(FlatArgs a, u32 round) {
     const u32 level = a.nbands > 1 ? st->level[par] : 0u;
     if (acc[a.nsets] == 0) { if (blockIdx.x == 0 && threadIdx.x == 0 && level + 1 >= a.nbands) st->done = 1; return; }
     const u32 gain_min = a.band_thr[level];     // T_L: what a set must gain to claim in this round (one band: 1)
+    // per group: T_L of every group, side by side in LDS (a set's threshold is then one gather, of its group, and an LDS read)
+    __shared__ u32 s_thr[BYGROUP ? GR_THR_LDS : 1];
+    if (BYGROUP) {
+        for (u32 q = threadIdx.x; q < min(a.ngroups, (u32)GR_THR_LDS); q += GR_THREADS) s_thr[q] = a.band_thr[q * a.nbands + level];
+        __syncthreads();
+    }
     GrWalk wk;
     wk.level = a.nbands > 1 ? level : 0xffffffffu;
     if (a.sharded) {
@@ -461,7 +496,7 @@ gr_claim_kernel(FlatArgs a, u32 round) {
         // address rate (~1 lane access per CU and cycle, profiles/r06_pmc_rounds_group0.txt), a run is ~20 rows
         // of one set in a tile, and a gather costs what its ACTIVE lanes cost
         const u32 lane = threadIdx.x & 63;
-        u32 g[GR_UNR], rk[GR_UNR], hl[GR_UNR];
+        u32 g[GR_UNR], rk[GR_UNR], hl[GR_UNR];     // (rk: per group the set's threshold -- bands are not cut under ranks)
         unsigned long long heads[GR_UNR];
         unsigned long long seen[GR_UNR][RP_MAXW];
 #pragma unroll
@@ -474,7 +509,8 @@ gr_claim_kernel(FlatArgs a, u32 round) {
             g[u] = 0; rk[u] = 0;
             if (run_head) {
                 g[u] = acc[s];
-                rk[u] = one_rank ? 0u : a.rank[s];
+                if (BYGROUP) { const u32 q = a.set_thr[s]; rk[u] = q < GR_THR_LDS ? s_thr[q] : a.band_thr[q * a.nbands + level]; }
+                else rk[u] = one_rank ? 0u : a.rank[s];
             }
             if (GR_KEY_FLAGS(k[u]))
                 load_words5(owner + (x[u] >> 6), seen[u], GR_KEY_FLAGS(k[u]));   // owner has slack words; a stale view only costs an atomic
@@ -493,12 +529,14 @@ gr_claim_kernel(FlatArgs a, u32 round) {
             const u32 fl = GR_KEY_FLAGS(k[u]);
             if (count_here && fl) { ++c_rows; c_own += (u32)__popc(fl); }
             gg[u] = __shfl(g[u], (int)hl[u], WAVE);
-            const u32 rr = one_rank ? 0u : __shfl(rk[u], (int)hl[u], WAVE);
+            const u32 rr = BYGROUP ? cur_rank : one_rank ? 0u : __shfl(rk[u], (int)hl[u], WAVE);
             // (decided per set, so the lanes of a run agree; the first lane of a run
             // stores the marks for all of them)
             // (a band that woke in place leaves dead records, without flags, among its alive ones: such a record may
             // be the first of its set's run, so what the run's first lane stores goes by the set, not by its own record)
-            set_claims[u] = gg[u] >= gain_min && rr == cur_rank;
+            // (per group: the run's first lane compared the gain with its set's threshold -- its bit of the ballot)
+            const bool reaches = BYGROUP ? ((__ballot(g[u] >= rk[u]) >> hl[u]) & 1ull) != 0 : gg[u] >= gain_min;
+            set_claims[u] = reaches && rr == cur_rank;
             claims[u] = fl && set_claims[u];
         }
 #pragma unroll
@@ -610,7 +648,7 @@ gr_verdict_kernel(FlatArgs a, u32 round) {
     }
 }
 
-template <bool PARTIAL>
+template <bool PARTIAL, bool BYGROUP = false>
 __global__ void __launch_bounds__(GA_THREADS)
 gr_apply_kernel(FlatArgs a, u32 round) {
     __shared__ u32 s_done;
@@ -669,6 +707,9 @@ gr_apply_kernel(FlatArgs a, u32 round) {
         const u32 seg0 = blockIdx.x * seg;
         const u32 nin = in_list ? a.alive_cnt[par ^ 1][blockIdx.x] : (seg0 < a.nsets ? min(seg, a.nsets - seg0) : 0u);
         u32 *out_list = listed ? a.alive[par] + seg0 : nullptr;
+        __shared__ u32 s_thr[BYGROUP ? GR_THR_LDS : 1];     // T_L of every group (see gr_claim_kernel)
+        if (BYGROUP)
+            for (u32 q = threadIdx.x; q < min(a.ngroups, (u32)GR_THR_LDS); q += GA_THREADS) s_thr[q] = a.band_thr[q * a.nbands + level];
         if (threadIdx.x == 0) { s_out = 0; s_nwin = 0; }
         __syncthreads();
         // The accepted sets of the segment are gathered in LDS and get their places among the picks by ONE atomic per
@@ -682,7 +723,9 @@ gr_apply_kernel(FlatArgs a, u32 round) {
                 const u32 s = valid ? (in_list ? in_list[seg0 + idx] : seg0 + idx) : 0u;
                 const u32 g = valid ? acc[s] : 0u;
                 // (a set claimed iff it gained T_L: a sleeping set's round-0 gain, which round 0 finds here, is below it)
-                const bool won = valid && (gain_claims ? g >= gain_min : a.claimed[s] == round + 1) && a.lost[s] != round + 1;
+                u32 g_min = gain_min;
+                if (BYGROUP) { const u32 q = a.set_thr[s]; g_min = q < GR_THR_LDS ? s_thr[q] : a.band_thr[q * a.nbands + level]; }   // (T_L of the set's own group)
+                const bool won = valid && (gain_claims ? g >= g_min : a.claimed[s] == round + 1) && a.lost[s] != round + 1;
                 if (in_list && valid) a.acc[par ^ 1][s] = 0u;
                 const unsigned long long wb = __ballot(won);
                 if (wb) {
@@ -1132,23 +1175,67 @@ gr_gain_max_kernel(const u32 *__restrict__ gain0, u32 n, GreedyState *__restrict
         if (best) atomicMax(&st->gmax, best);
     }
 }
+// the group the boundaries of set s go by (catchhip_rows::set_group; a set without a group has no rows: any will do);
+// a set with probes in two groups (the flag word behind the sets): every set goes by group 0
+__device__ __forceinline__ u32 gr_group_of(const u32 *__restrict__ set_group, u32 nsg, u32 s) {
+    if (set_group[nsg] || s >= nsg) return 0u;
+    const u32 g = set_group[s];
+    return g == 0xffffffffu ? 0u : g;
+}
+// the same per group: gmax[g] (zeroed) = the largest round-0 gain of group g's sets.  Sets come group after group, so
+// every wavefront takes a run of consecutive sets and carries the maximum of the group it is in: an atomic when the
+// group changes and one at the end (one per wavefront step was 24,000 atomics on 17 addresses, 0.64 ms, on S4's union;
+// 64 sets of several groups in one step: an atomic per lane)
+__global__ void __launch_bounds__(256)
+gr_group_gain_max_kernel(const u32 *__restrict__ gain0, u32 n, const u32 *__restrict__ set_group, u32 nsg, u32 *__restrict__ gmax) {
+    const u32 lane = threadIdx.x & 63;
+    const u32 wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+    const u32 per = ((n + nwaves - 1) / nwaves + 63u) & ~63u;
+    const u32 i1 = min(n, (wave + 1) * per);
+    u32 cur = 0xffffffffu, best = 0;
+    for (u32 i0 = wave * per; i0 < i1; i0 += 64) {
+        const u32 i = i0 + lane;
+        const u32 v = i < i1 ? gain0[i] : 0u;
+        const u32 grp = gr_group_of(set_group, nsg, i < i1 ? i : i1 - 1);
+        const u32 grp0 = __shfl(grp, 0, WAVE);
+        if (__ballot(grp != grp0) == 0ull) {
+            if (grp0 != cur) {
+                if (lane == 0 && best) atomicMax(&gmax[cur], best);
+                cur = grp0; best = 0;
+            }
+            best = max(best, wave_max(v));
+        } else if (v) atomicMax(&gmax[grp], v);
+    }
+    if (lane == 0 && best) atomicMax(&gmax[cur], best);
+}
 __device__ __forceinline__ u32 gr_band_boundary(u32 prev, u32 ratio_pm) {
     return max(1u, (u32)(((unsigned long long)prev * ratio_pm) / 1000ull));
 }
-// band of every set: the first whose boundary its round-0 gain reaches (sets beyond the gains held: the last)
+// band of every set: the first whose boundary its round-0 gain reaches (sets beyond the gains held: the last).
+// gmax[ngroups] / set_group: the groups' largest gains and the sets' groups (one group, set_group null: the instance's
+// largest gain) -- thread g < ngroups writes the boundaries of group g, band_thr[g * nbands + b] (a group without
+// rows: all 1), and set_thr[s] = the group of set s
 __global__ void __launch_bounds__(256)
-gr_band_kernel(const u32 *__restrict__ gain0, u32 ng, u32 nsets, const GreedyState *__restrict__ st, u32 nbands, u32 ratio_pm,
-               u32 *__restrict__ band_thr, u8 *__restrict__ band) {
+gr_band_kernel(const u32 *__restrict__ gain0, u32 ng, u32 nsets, GreedyState *__restrict__ st, u32 nbands, u32 ratio_pm,
+               u32 *__restrict__ band_thr, u8 *__restrict__ band, const u32 *__restrict__ gmax, u32 ngroups,
+               const u32 *__restrict__ set_group, u32 nsg, u32 *__restrict__ set_thr) {
     const u32 s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < ngroups) {
+        u32 t = gmax[s];
+        for (u32 b = 0; b + 1 < nbands; ++b) { t = gr_band_boundary(t, ratio_pm); band_thr[s * nbands + b] = t; }
+        band_thr[s * nbands + nbands - 1] = 1u;
+    }
+    if (s == 0) st->band_groups = (set_group && set_group[nsg]) ? 1u : ngroups;
+    if (s >= nsets) return;
+    const u32 grp = set_group ? gr_group_of(set_group, nsg, s) : 0u;
     const u32 g = s < ng ? gain0[s] : 0u;
-    u32 t = st->gmax, b = 0, mine = nbands - 1;
-    for (; b + 1 < nbands; ++b) {
+    u32 t = gmax[grp], mine = nbands - 1;
+    for (u32 b = 0; b + 1 < nbands; ++b) {
         t = gr_band_boundary(t, ratio_pm);
-        if (s == 0) band_thr[b] = t;
         if (g >= t && mine == nbands - 1) mine = b;
     }
-    if (s == 0) band_thr[nbands - 1] = 1u;
-    if (s < nsets) band[s] = (u8)mine;
+    band[s] = (u8)mine;
+    if (set_thr) set_thr[s] = grp;
 }
 
 // (band: the band of every set, null with one band -- the partition's digit is the sub-tile, tile * nbands + band)
@@ -1456,12 +1543,17 @@ struct FlatSolve {
         u32 nbands = 1;
         if (!partial && !sharded && !h_rank && nrank <= 1 && !stats_dirty && R->gain0_n && nrows) {
             const u32 max_bands = (u32)GR_MAXTX / (u32)div_up((i64)ntiles, 8);
-            // (a union of unlike groups keeps one band unless asked: the boundaries go by the instance's largest gain, and the
-            // smaller groups lie below all of them -- they would wait for the last level and then run as without bands)
-            const i64 want = R->grouped ? chip_test_env_int("CATCHHIP_FLAT_BANDS_GROUPED", 1) : chip_test_env_int("CATCHHIP_FLAT_BANDS", GR_BANDS);
+            // (a union of unlike groups is cut group by group, FlatArgs::set_thr, when it is large enough to get here by its
+            // own size; a smaller one -- here through CATCHHIP_FLAT_MIN_ROWS -- or one whose rows do not name their sets'
+            // groups keeps one band unless asked)
+            const i64 grouped_default = (R->set_group_n && (i64)nrows >= GR_MIN_ROWS) ? GR_BANDS : 1;
+            const i64 want = R->grouped ? chip_test_env_int("CATCHHIP_FLAT_BANDS_GROUPED", grouped_default) : chip_test_env_int("CATCHHIP_FLAT_BANDS", GR_BANDS);
             nbands = (u32)std::max<i64>(1, std::min<i64>(want, (i64)max_bands));
         }
-        const u32 band_ratio = (u32)std::max<i64>(1, std::min<i64>(chip_test_env_int("CATCHHIP_FLAT_BAND_RATIO", GR_BAND_RATIO), 999));
+        // boundaries per group: grouped rows that name the group of every set, more than one band
+        const u32 ngroups = (nbands > 1 && R->grouped && R->set_group_n && R->ngroups) ? R->ngroups : 1u;
+        const bool by_group = nbands > 1 && R->grouped && R->set_group_n && R->ngroups;
+        const u32 band_ratio = (u32)std::max<i64>(1, std::min<i64>(chip_test_env_int("CATCHHIP_FLAT_BAND_RATIO", R->grouped && R->set_group_n ? GR_BAND_RATIO_GROUPED : GR_BAND_RATIO), 999));
         const u32 nsub = ntiles * nbands;                                  // sub-tiles: what the records are partitioned by
         size_t off = 0;
         auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
@@ -1470,7 +1562,7 @@ struct FlatSolve {
                      o_picked = take(4 * (size_t)nsets), o_claimed = take(4 * (size_t)nsets),
                      o_lost = take(4 * (size_t)nsets), o_rank = take(4 * (size_t)nsets),
                      o_acc0 = take(4 * ((size_t)nsets + 2)), o_acc1 = take(4 * ((size_t)nsets + 2)),
-                     o_tc0 = take(4 * 258), o_tc1 = take(4 * 258);
+                     o_tc0 = take(4 * 258), o_tc1 = take(4 * 258), o_gmax = take(by_group ? 4 * (size_t)ngroups : 0);
         const size_t nchg = stats_dirty ? nwords / 32 + 4 : 0;
         const size_t o_chg0 = take(4 * nchg), o_chg1 = take(4 * nchg);
         const size_t o_cflag = take(partial ? 4 * ((size_t)nsets + 1) : 0), o_ufinal = take(partial ? 4 * (size_t)nuniv + 4 : 0);
@@ -1485,7 +1577,8 @@ struct FlatSolve {
                      o_keys = take(8 * (size_t)nsets), o_tptr = take(4 * 258),
                      o_sptr = direct ? o_dsptr : take(4 * ((size_t)nsets + 1)),
                      o_xt = take(4 * 8 * GR_MAXTX), o_xn = take(4 * 8),
-                     o_thr = take(4 * GR_MAXTX), o_band = take(nbands > 1 ? (size_t)nsets : 0);
+                     o_thr = take(4 * std::max<size_t>(GR_MAXTX, (size_t)ngroups * nbands)), o_band = take(nbands > 1 ? (size_t)nsets : 0),
+                     o_sthr = take(by_group ? 4 * (size_t)nsets : 0);
         const size_t o_need = take(partial ? 4 * (size_t)nuniv + 4 : 0), o_uT = take(partial ? 8 * (size_t)nuniv + 8 : 0),
                      o_uM = take(partial ? 8 * (size_t)nuniv + 8 : 0), o_cpos = take(partial ? 4 * ((size_t)nsets + 1) : 0),
                      o_cset = take(partial ? 4 * ((size_t)nsets + 2) : 0);
@@ -1556,12 +1649,20 @@ struct FlatSolve {
         fa.blkcnt = (unsigned long long *)(A + o_blk); fa.st = (GreedyState *)(A + o_st);
         fa.nsets = nsets; fa.nwords = (u32)nwords; fa.ntiles = nsub; fa.nuniv = nuniv;
         fa.nbands = nbands; fa.band_thr = (const u32 *)(A + o_thr); fa.band = nbands > 1 ? (const u8 *)(A + o_band) : nullptr;
+        fa.set_thr = by_group ? (const u32 *)(A + o_sthr) : nullptr; fa.ngroups = ngroups;
         if (nbands > 1) {
             const u32 ng = std::min<u32>(R->gain0_n, nsets);
-            hipLaunchKernelGGL(gr_gain_max_kernel, dim3((unsigned)std::max<i64>(1, std::min<i64>(div_up((i64)ng, 1024), (i64)ctx->num_cus))), dim3(256), 0, s,
-                               (const u32 *)R->gain0.p, ng, (GreedyState *)(A + o_st));
-            hipLaunchKernelGGL(gr_band_kernel, dim3((unsigned)div_up((i64)nsets, 256)), dim3(256), 0, s, (const u32 *)R->gain0.p, ng, nsets,
-                               (const GreedyState *)(A + o_st), nbands, band_ratio, (u32 *)(A + o_thr), (u8 *)(A + o_band));
+            const dim3 gmax_grid((unsigned)std::max<i64>(1, std::min<i64>(div_up((i64)ng, 1024), (i64)ctx->num_cus)));
+            if (by_group)
+                hipLaunchKernelGGL(gr_group_gain_max_kernel, gmax_grid, dim3(256), 0, s, (const u32 *)R->gain0.p, ng,
+                                   (const u32 *)R->set_group.p, R->set_group_n, (u32 *)(A + o_gmax));
+            else
+                hipLaunchKernelGGL(gr_gain_max_kernel, gmax_grid, dim3(256), 0, s, (const u32 *)R->gain0.p, ng, (GreedyState *)(A + o_st));
+            hipLaunchKernelGGL(gr_band_kernel, dim3((unsigned)div_up((i64)std::max(nsets, ngroups), 256)), dim3(256), 0, s,
+                               (const u32 *)R->gain0.p, ng, nsets, (GreedyState *)(A + o_st), nbands, band_ratio, (u32 *)(A + o_thr),
+                               (u8 *)(A + o_band), by_group ? (const u32 *)(A + o_gmax) : (const u32 *)(A + o_st + offsetof(GreedyState, gmax)),
+                               ngroups, by_group ? (const u32 *)R->set_group.p : (const u32 *)nullptr, R->set_group_n,
+                               by_group ? (u32 *)(A + o_sthr) : (u32 *)nullptr);
         } else hipLaunchKernelGGL(gr_fill_one_kernel, dim3(1), dim3(1), 0, s, (u32 *)(A + o_thr), 1u);
         fa.sharded = sharded ? 1u : 0u;
         fa.pretested = (sharded && partial) ? 1u : 0u;
@@ -1630,7 +1731,8 @@ struct FlatSolve {
         } else hipLaunchKernelGGL(gr_count_kernel<false>, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
     }
     void launch_claim(u32 round) {
-        hipLaunchKernelGGL(gr_claim_kernel, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
+        if (fa.set_thr) hipLaunchKernelGGL(gr_claim_kernel<true>, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
+        else hipLaunchKernelGGL(gr_claim_kernel<false>, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
         if (partial && fa.nuniv) hipLaunchKernelGGL(gr_usel_kernel, dim3(fa.nuniv), dim3(256), 0, ctx->stream, fa, round);
     }
     void launch_verdict(u32 round) {
@@ -1644,7 +1746,8 @@ struct FlatSolve {
             hipLaunchKernelGGL(gr_apply_kernel<true>, dim3(gblocks), dim3(GA_THREADS), 0, ctx->stream, fa, round);
             if (fa.nuniv) launch_finish(round);
         } else {
-            hipLaunchKernelGGL(gr_apply_kernel<false>, dim3(gblocks), dim3(GA_THREADS), 0, ctx->stream, fa, round);
+            if (fa.set_thr) hipLaunchKernelGGL((gr_apply_kernel<false, true>), dim3(gblocks), dim3(GA_THREADS), 0, ctx->stream, fa, round);
+            else hipLaunchKernelGGL(gr_apply_kernel<false>, dim3(gblocks), dim3(GA_THREADS), 0, ctx->stream, fa, round);
             hipLaunchKernelGGL(gr_cover_kernel, dim3(gblocks), dim3(GA_THREADS), 0, ctx->stream, fa, round);
         }
     }
@@ -1748,6 +1851,7 @@ static int greedy_flat(catchhip_ctx *ctx, const catchhip_rows *R, u32 nsets, con
     ctx->counters[2] = iters; ctx->counters[3] = np; ctx->counters[4] = n_vis;
     ctx->counters[5] = n_rec; ctx->counters[6] = n_wrd;
     ctx->solver_levels[0] = F.fa.nbands > 1 ? (i64)std::max(h_st->level[0], h_st->level[1]) + 1 : 1; ctx->solver_levels[1] = F.fa.nbands;
+    ctx->solver_band_groups = F.fa.nbands > 1 ? (i64)std::max<u32>(h_st->band_groups, 1u) : 1;
     if (done == 2) {
         chip_set_error("setcover: ranks exhausted while coverage is still required");
         return CATCHHIP_ERANK;

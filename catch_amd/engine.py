@@ -224,6 +224,8 @@ class Context:
         lv = np.zeros(2, dtype=np.int64)
         check(self._L.catchhip_ctx_last_solver_levels(self._h, _ptr(lv, c_i64p)))
         d["flat_levels"], d["flat_bands"] = int(lv[0]), int(lv[1])   # gain bands of the last row-parallel solve
+        check(self._L.catchhip_ctx_last_solver_band_groups(self._h, _ptr(lv, c_i64p)))
+        d["flat_band_groups"] = int(lv[0])   # groups with band boundaries of their own (1: one row of boundaries)
         return d
 
     def grid_counters(self):

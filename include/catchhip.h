@@ -123,6 +123,10 @@ int catchhip_ctx_last_solver_counters(catchhip_ctx *ctx, int64_t *out4);
  * values: the levels it went through (1: every row was awake from the first
  * round on) and the bands its sets were cut into. */
 int catchhip_ctx_last_solver_levels(catchhip_ctx *ctx, int64_t *out2);
+/* Of the same solve: the groups whose sets were cut into bands by boundaries of
+ * their own (rows of a scan with group numbers, more than one band); 1 when
+ * one row of boundaries served every set, 0 when the solver did not run. */
+int catchhip_ctx_last_solver_band_groups(catchhip_ctx *ctx, int64_t *out1);
 /* Work of the last Hamming near-duplicate filter on this context (SURVEY 8(d)
  * K3's quantities; catch/filter/near_duplicate_filter.py:47-142 does the same
  * look-ups probe by probe): probes N, tables T, pairs sharing a bucket that were
