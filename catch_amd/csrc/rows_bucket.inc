@@ -359,6 +359,103 @@ __device__ __forceinline__ void bucket_rank_sort(u32 *s_es, u32 *s_ee, u32 *s_sg
     }
 }
 
+// The no-touch path of bucket_merge_kernel<.., RUNS = true> (the comment there says what it relies on): one
+// wavefront, bucket of n <= 64 * NQ records given as runs rs[a] .. rs[a + 1], lane l holds records l, l + 64, ..
+// in registers.  Fills s_es / s_ee, ranks every record and tests it for a touch.  Clean bucket: stores the records
+// that are not at their place, the bucket's counts, and returns true.  Otherwise nothing is stored, s_sg is filled
+// too and the caller takes the general path.
+// BK_NT_SLOTS: the most register slots the path is built with.  With 8 (every wave bucket) the first version needed
+// 133 VGPRs, 3 wavefronts per SIMD; with 4 the kernel needs 82 and runs 5 (the general path alone: 71 and 7).
+// Buckets of more than 256 records take the general path; S4 has none (profiles/r10_bucket_distribution_S4.json).
+#define BK_RUNS_MAX 5
+#define BK_NT_SLOTS 4
+// inclusive maximum over the 64 lanes, the steps of wave_incl_scan_dpp (wave.h): lanes a step does not reach see 0
+__device__ __forceinline__ u32 bucket_incl_max_dpp(u32 v) {
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true));
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true));
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true));
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));
+    return v;
+}
+template <int NQ>
+__device__ __forceinline__ bool bucket_no_touch(u32 *s_es, u32 *s_ee, u32 *s_sg, const u32 (&rs)[BK_RUNS_MAX + 1], u32 n,
+                                                u32 base, u32 b, u32 lane, uint4 *__restrict__ S, u32 *__restrict__ mcnt,
+                                                u32 *__restrict__ blmax, unsigned long long *__restrict__ bsum) {
+    u32 es[NQ], ee[NQ], sg[NQ], rk[NQ];
+    __syncthreads();   // previous bucket's merge is done with the LDS arrays
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const u32 i = lane + q * 64u;
+        es[q] = ee[q] = sg[q] = 0;
+        if (i < n) { const uint4 r = S[base + i]; es[q] = r.x; ee[q] = r.y; sg[q] = r.z; s_es[i] = r.x; s_ee[i] = r.y; }
+    }
+    __syncthreads();
+    // Per run, the records that start at or before mine (`<=` on the 32-bit starts), by a search whose trip count
+    // depends on the run's length alone: the loop is the wavefront's, a lane only moves its position, and the slots
+    // of a lane share the steps.  My own run counts me in, so over all runs the count is my rank + 1 in a clean
+    // bucket.  The last record found in a run, stepping over myself, is the one of that run that could reach me.
+    bool touched = false;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) rk[q] = 0;
+#pragma unroll
+    for (int a = 0; a < BK_RUNS_MAX; ++a) {
+        if (rs[a + 1] == rs[a]) continue;
+        u32 pos[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) pos[q] = rs[a];
+        for (u32 len = rs[a + 1] - rs[a]; len > 1;) {
+            const u32 half = len >> 1;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) pos[q] = s_es[pos[q] + half] <= es[q] ? pos[q] + half : pos[q];
+            len -= half;
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int i = (int)(lane + q * 64u);
+            const u32 lo = pos[q] + (s_es[pos[q]] <= es[q] ? 1u : 0u);
+            rk[q] += lo - rs[a];
+            int j = (int)lo - 1;
+            j -= j == i ? 1 : 0;
+            const u32 near_end = s_ee[max(j, (int)rs[a])];
+            if (j >= (int)rs[a] && near_end >= es[q] && (u32)i < n) touched = true;
+        }
+    }
+    u32 lmax = 0, len_lo = 0, len_hi = 0;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const u32 i = lane + q * 64u;
+        rk[q] = i < n ? rk[q] - 1u : i;
+        const u32 len = ee[q] - es[q];        // (the slots past the bucket hold zeros)
+        lmax = max(lmax, len);
+        len_lo += len & 0xffffu;
+        len_hi += len >> 16;
+    }
+    if (__ballot(touched) != 0ull) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const u32 i = lane + q * 64u;
+            if (i < n) s_sg[i] = sg[q];
+        }
+        return false;
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const u32 i = lane + q * 64u;
+        if (i < n && rk[q] != i) S[base + rk[q]] = make_uint4(es[q], ee[q], sg[q], b);
+    }
+    // the bucket's longest row and total length by DPP moves instead of 18 LDS permutes; the total as two sums of
+    // 16-bit halves (at most 256 values each): LANE 63 holds the results
+    lmax = bucket_incl_max_dpp(lmax);
+    const u32 sum_lo = wave_incl_scan_dpp(len_lo), sum_hi = wave_incl_scan_dpp(len_hi);
+    if (lane == 63) {
+        mcnt[b] = n; blmax[b] = lmax;
+        if (bsum) bsum[b] = ((unsigned long long)sum_hi << 16) + sum_lo;
+    }
+    return true;
+}
+
 // Sort one bucket by start, merge per segment, write the merged rows back at
 // the bucket's first slots.  Instantiated with THREADS = 64: one wavefront
 // per bucket (the barriers are wave-wide no-ops), rank sort of up to CAP items;
@@ -368,14 +465,32 @@ __device__ __forceinline__ void bucket_rank_sort(u32 *s_es, u32 *s_ee, u32 *s_sg
 // item's place in the merged order is its index in its own run + the number of smaller items in the other runs,
 // found by binary search in LDS: O(log n) per item where the rank sort needs O(n) (the concatenation is never
 // nearly sorted, so the odd-even rounds always gave up: 20 ms per S4 step in the first version of the join).
-#define BK_RUNS_MAX 5
-template <int THREADS, int CAP>
+//
+// RUNS (the instance launched with run_cnt and without dedupe: the join's, hence every bucket of S4): a bucket in
+// which NOTHING TOUCHES leaves the kernel as it came, only in start order -- every record is a row of its own -- so
+// the permute through LDS, the walk and the write-back of records that already stand at their place are work whose
+// result is known once the bucket is known to be clean.  Per item, in registers: the searches that rank it (on the
+// 32-bit starts alone, `<=`) also find, in every other run, the last record that starts at or before it; the item is
+// TOUCHED iff the end of one of those, or of its predecessor in its own run, is >= its start (segments ignored: a
+// touch across two genomes only sends the bucket down the general path, which is exact).  Equal starts count as a
+// touch (the record found has end >= its start = mine), so a clean bucket never needs a tie order.
+// Why the nearest records are enough: let y start at or before x and reach it (end_y >= start_x).  y's successor y'
+// in y's own run starts at or before x's place too (it is x, or the run's last record before x, or one before that),
+// so start_y <= start_y' <= start_x <= end_y: y' is touched by its own predecessor and the bucket is not clean.
+// Hence if no item is touched, no record reaches a later one: every prefix maximum of the ends is the predecessor's
+// own end, below the next start, and the walk would open a row at every item -- mcnt = n, rows = records.
+// A clean bucket stores only the records whose rank is not their place (one non-empty run: nothing); no store to S
+// is issued before the verdict of the whole bucket is known, and a touched bucket then takes the general path below
+// as every bucket did before (64-bit rank, ties to the earlier run, permute, walk), the stale records behind the
+// merged rows included.
+template <int THREADS, int CAP, bool RUNS = false>
 __global__ void __launch_bounds__(THREADS)
 bucket_merge_kernel(const u32 *__restrict__ bstart, u32 nb, uint4 *__restrict__ S, u32 *__restrict__ mcnt,
                     u32 *__restrict__ blmax,
                     unsigned long long *__restrict__ bsum, int dedupe, const u32 *__restrict__ run_cnt, int run_stride,
                     int nruns) {
     constexpr int IPT = CAP / THREADS;
+    static_assert(!RUNS || THREADS == 64, "the no-touch path takes its verdict from one wavefront's ballot");
     __shared__ u32 s_es[CAP], s_ee[CAP], s_sg[CAP];
     const u32 tid = threadIdx.x, lane = tid & 63;
     for (u32 b = blockIdx.x; b < nb; b += gridDim.x) {
@@ -385,8 +500,31 @@ bucket_merge_kernel(const u32 *__restrict__ bstart, u32 nb, uint4 *__restrict__ 
             if (tid == 0) { mcnt[b] = 0; blmax[b] = 0; if (bsum) bsum[b] = 0; }
             continue;
         }
-        __syncthreads();   // previous bucket's merge is done with the LDS arrays
-        for (u32 i = tid; i < n; i += THREADS) { const uint4 r = S[base + i]; s_es[i] = r.x; s_ee[i] = r.y; s_sg[i] = r.z; }
+        bool filled = false;   // the LDS arrays hold the bucket already
+        if constexpr (RUNS) {
+            if (n == 1) {   // one record: a row as it stands (a sixth of S4's buckets)
+                if (lane == 0) { const uint4 r = S[base]; mcnt[b] = 1; blmax[b] = r.y - r.x; if (bsum) bsum[b] = r.y - r.x; }
+                continue;
+            }
+            u32 rs[BK_RUNS_MAX + 1];
+            rs[0] = 0;
+#pragma unroll
+            for (int a = 0; a < BK_RUNS_MAX; ++a) rs[a + 1] = rs[a] + (a < nruns ? run_cnt[(size_t)b * run_stride + a] : 0u);
+            if (rs[BK_RUNS_MAX] == n && !dedupe && n <= 64u * BK_NT_SLOTS) {
+                // as many register slots per lane as the bucket needs: 1 up to 64 records, 2 up to 128, 4 up to 256
+                const bool clean =
+                    n <= 64u ? bucket_no_touch<1>(s_es, s_ee, s_sg, rs, n, base, b, lane, S, mcnt, blmax, bsum)
+                    : n <= 128u ? bucket_no_touch<2>(s_es, s_ee, s_sg, rs, n, base, b, lane, S, mcnt, blmax, bsum)
+                                : bucket_no_touch<BK_NT_SLOTS>(s_es, s_ee, s_sg, rs, n, base, b, lane, S, mcnt, blmax, bsum);
+                if (clean) continue;
+                // something touches: the general path below, on the bucket as it stands in LDS
+                filled = true;
+            }
+        }
+        if (!filled) {
+            __syncthreads();   // previous bucket's merge is done with the LDS arrays
+            for (u32 i = tid; i < n; i += THREADS) { const uint4 r = S[base + i]; s_es[i] = r.x; s_ee[i] = r.y; s_sg[i] = r.z; }
+        }
         __syncthreads();
         // rank sort by (start, end, index), with as many items per thread as the
         // bucket needs: the comparison loop is n x (items per thread) and was the

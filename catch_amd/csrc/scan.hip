@@ -1495,7 +1495,9 @@ static int bucket_finish_async(catchhip_ctx *ctx, BucketBuild &B, u32 nrec, cons
                            (const uint4 *)B.rec.p, (const u32 *)B.rank.p, nrec, nrec_dev, (const u32 *)B.bstart.p,
                            B.S.p, B.compact ? (const u32 *)B.wcnt.p : (const u32 *)nullptr);
     unsigned long long *bsum = want_sum ? B.bsum.p : nullptr;
-    hipLaunchKernelGGL((bucket_merge_kernel<64, BK_SMALL>), dim3((unsigned)std::min<i64>(B.nb, (i64)1 << 20)), dim3(64),
+    // buckets given as anchor runs (the join; not cover_ranges' dedupe walk) take the instance with the no-touch path
+    const auto merge = run_cnt && !dedupe ? bucket_merge_kernel<64, BK_SMALL, true> : bucket_merge_kernel<64, BK_SMALL>;
+    hipLaunchKernelGGL(merge, dim3((unsigned)std::min<i64>(B.nb, (i64)1 << 20)), dim3(64),
                        0, s, (const u32 *)B.bstart.p, B.nb, B.S.p, B.mcnt.p, B.blmax.p, bsum,
                        dedupe ? 1 : 0, run_cnt, run_stride, nruns);
     static bool big_attr_set = false;
