@@ -232,6 +232,8 @@ PROTOTYPES = {
     "catchhip_rows_window_depth": (ctypes.c_int, [
         c_vp, c_vp, c_i64p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
         c_i64p, c_u64p, c_u32p, ctypes.c_int64]),
+    "catchhip_rows_uncovered": (ctypes.c_int, [
+        c_vp, c_vp, c_vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, c_vpp, c_i64p, c_i64p]),
     "catchhip_rows_first_seen_per_set": (ctypes.c_int, [
         c_vp, c_vp, ctypes.c_int64, c_i32p, c_u64p]),
     "catchhip_rows_cover_check": (ctypes.c_int, [

@@ -58,6 +58,7 @@ def parse_args(argv=None):
     p.add_argument("--write-probe-map-counts-to-tsv",
                    help="sequences each probe maps to, not counting reverse "
                         "complements")
+    coverage_analysis.add_uncovered_arguments(p)
 
     def check_max_num_processes(val):
         ival = int(val)
@@ -168,6 +169,7 @@ def main(args):
             a.write_probe_map_counts(args.write_probe_map_counts_to_tsv)
         if args.print_analysis:
             a.print_analysis()
+        coverage_analysis.write_uncovered(a, args)
         return analyzers
 
     if args.write_analysis_to_tsv:
@@ -194,7 +196,27 @@ def main(args):
         print("NUMBER OF PROBES: %d" % len(probes))
         print()
         coverage_analysis.print_table(data)
+    _write_uncovered(args, [(a, [local]) for a, local in order])
     return analyzers
+
+
+def _write_uncovered(args, order):
+    """--write-uncovered-regions / --write-uncovered-fasta: every (analyzer,
+    its groupings to write; None = all) in turn, one shared file each."""
+    if not (args.write_uncovered_regions or args.write_uncovered_fasta):
+        return
+    filters = coverage_analysis.uncovered_filters(args)
+    if args.write_uncovered_regions:
+        with open(args.write_uncovered_regions, "w") as f:
+            f.write("\t".join(coverage_analysis.Analyzer._UNCOVERED_HEADER) + "\n")
+            for a, groups in order:
+                a._write_uncovered_rows(f, groups, *filters)
+    if args.write_uncovered_fasta:
+        with open(args.write_uncovered_fasta, "w") as f:
+            for a, groups in order:
+                a._write_uncovered_fasta_rows(f, groups, *filters)
+    for a in dict.fromkeys(a for a, _groups in order):
+        a.log_uncovered_summary("", *filters)
 
 
 def _cli(argv):

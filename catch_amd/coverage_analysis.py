@@ -12,7 +12,9 @@ of genomes never brings the row table to the host.  The sliding-window depth
 (:337-411) is computed on the device as well (catchhip_rows_window_depth, one
 scan per strand on first use of `sliding_coverage` or its writer): what comes
 back is one integer sum and one base count per window, never a range.
-`target_covers` is fetched on first use.
+`target_covers` is fetched on first use.  Where the probes do not reach is read
+out on the device too (`uncovered_regions` and its writers,
+catchhip_rows_uncovered: one scan per strand, only the regions come back).
 Same constructor, attributes (`target_covers`, `bp_covered`,
 `average_coverage`, `sliding_coverage`, `probe_map_counts`) and writers.
 
@@ -62,6 +64,9 @@ class Analyzer:
         self._window = (50, 25)
         self._scan_inputs = None
         self._np_state = None
+        self._uncovered = {}
+        self.uncovered_summary = {}
+        self.last_uncovered_ms = 0.0      # device time of the last uncovered_regions() that went to the device, both strands
 
     def _iter_target_genomes(self, groups=None):
         """groups: only these groupings, in the order given (the rows of one
@@ -115,6 +120,7 @@ class Analyzer:
                 d.setdefault(i, {}).setdefault(j, {False: None, True: None})[rc] = 0
         self._covers = None
         self._sliding = self._windows = None
+        self._uncovered = {}
         strs = [p.seq_str for p in self.probes]
         flat = self._flat_genomes()
         self._scan_inputs = None
@@ -320,6 +326,115 @@ class Analyzer:
                                                          window_stride)
 
     # ------------------------------------------------------------------
+    def uncovered_regions(self, min_depth=1, min_length=1, min_unambig=1):
+        """{i: {j: {rc: [(seq_index, start, end, unambig), ...]}}}: the maximal
+        runs of bases, inside one sequence, that fewer than min_depth cover
+        ranges hold, by (sequence, start); start and end are 0-based, half-open,
+        within the sequence as scanned (for rc: the reverse-complemented
+        sequence, as in the sliding-window file), unambig = the run's bases that
+        are A, C, G or T.  Reported are the runs of min_length bases and more
+        with at least min_unambig unambiguous ones.  Also fills
+        self.uncovered_summary[i][j][rc] = (regions, bases, longest).  After
+        run(); one scan per strand, the row table stays on the device
+        (Rows.uncovered) and only the regions come back.  With no probes every
+        sequence that passes the filters is one region."""
+        key = (int(min_depth), int(min_length), int(min_unambig))
+        if key not in self._uncovered:
+            self._uncovered[key] = self._find_uncovered(*key)
+        regions, self.uncovered_summary = self._uncovered[key]
+        return regions
+
+    def _find_uncovered(self, min_depth, min_length, min_unambig):
+        regions, summary = {}, {}
+        for i, j, _gnm, rc in self._iter_target_genomes():
+            regions.setdefault(i, {}).setdefault(j, {False: None, True: None})[rc] = []
+            summary.setdefault(i, {}).setdefault(j, {False: None, True: None})[rc] = (0, 0, 0)
+        flat = self._flat_genomes()
+        if not flat:
+            return regions, summary
+        ctx = engine.default_context()
+        first_seq = np.zeros(len(flat) + 1, dtype=np.int64)
+        np.cumsum([len(gnm.seqs) for _i, _j, gnm in flat], out=first_seq[1:])
+        probes_dev = None
+        if self._scan_inputs is not None:
+            k, uniq, owner, ep, eo = self._scan_inputs
+            probes_dev = engine.Probes(ctx, uniq, owner, ep, eo, k)
+        self.last_uncovered_ms = 0.0
+        try:
+            for rc in ((False, True) if self.rc_too else (False,)):
+                # (the targets stay until the regions are back: the kernel counts their A, C, G, T)
+                targets, owner_of_seq, _off = self._strand_targets(ctx, flat, rc)
+                try:
+                    if probes_dev is not None:
+                        rows = self._scan(ctx, probes_dev, targets)
+                    else:       # no probes: a table without rows over the same sequences
+                        rows = engine.Rows.from_host(ctx, [], [], [], [], np.diff(targets.seq_off))
+                    try:
+                        univ, st, en, ua, per = rows.uncovered(targets, min_depth, min_length, min_unambig)
+                        self.last_uncovered_ms += rows.last_uncovered_ms
+                    finally:
+                        rows.close()
+                finally:
+                    targets.close()
+                bounds = np.searchsorted(univ, first_seq)       # (the regions come by (sequence, start))
+                seq = univ.astype(np.int64) - (first_seq[owner_of_seq[univ]] if univ.size else 0)
+                for g, (i, j, _gnm) in enumerate(flat):
+                    lo, hi = bounds[g], bounds[g + 1]
+                    regions[i][j][rc] = list(zip(seq[lo:hi].tolist(), st[lo:hi].tolist(), en[lo:hi].tolist(),
+                                                 ua[lo:hi].tolist()))
+                    p = per[first_seq[g]:first_seq[g + 1]]
+                    summary[i][j][rc] = ((int(p[:, 0].sum()), int(p[:, 1].sum()), int(p[:, 2].max()))
+                                         if p.size else (0, 0, 0))
+        finally:
+            if probes_dev is not None:
+                probes_dev.close()
+        return regions, summary
+
+    _UNCOVERED_HEADER = ["Genome", "Sequence", "Start", "End", "Length", "Unambig bases"]
+
+    @staticmethod
+    def _sequence_name(gnm, seq_index):
+        """The sequence's name in gnm.chrs when it has one, else its index."""
+        return list(gnm.chrs.keys())[seq_index] if gnm.chrs else seq_index
+
+    def write_uncovered_regions(self, fn, min_depth=1, min_length=1, min_unambig=1):
+        with open(fn, "w") as f:
+            f.write("\t".join(self._UNCOVERED_HEADER) + "\n")
+            self._write_uncovered_rows(f, None, min_depth, min_length, min_unambig)
+
+    def _write_uncovered_rows(self, f, groups=None, min_depth=1, min_length=1, min_unambig=1):
+        regions = self.uncovered_regions(min_depth, min_length, min_unambig)
+        for i, j, gnm, rc in self._iter_target_genomes(groups):
+            header = self._row_header(i, j, rc)
+            names = list(gnm.chrs.keys()) if gnm.chrs else None
+            f.write("".join("%s\t%s\t%d\t%d\t%d\t%d\n" % (header, names[s] if names else s, a, b, b - a, u)
+                            for s, a, b, u in regions[i][j][rc]))
+
+    def write_uncovered_fasta(self, fn, min_depth=1, min_length=1, min_unambig=1):
+        """The uncovered regions of the forward strand as FASTA records:
+        >{row header}|{sequence}|{start}-{end}, then that slice of the sequence."""
+        with open(fn, "w") as f:
+            self._write_uncovered_fasta_rows(f, None, min_depth, min_length, min_unambig)
+
+    def _write_uncovered_fasta_rows(self, f, groups=None, min_depth=1, min_length=1, min_unambig=1):
+        regions = self.uncovered_regions(min_depth, min_length, min_unambig)
+        for i, j, gnm, rc in self._iter_target_genomes(groups):
+            if rc:
+                continue
+            header = self._row_header(i, j, rc)
+            for s, a, b, _u in regions[i][j][rc]:
+                f.write(">%s|%s|%d-%d\n%s\n" % (header, self._sequence_name(gnm, s), a, b, gnm.seqs[s][a:b]))
+
+    def log_uncovered_summary(self, label="", min_depth=1, min_length=1, min_unambig=1):
+        """One line per dataset under --verbose: regions, uncovered bases, longest (over every genome and strand)."""
+        self.uncovered_regions(min_depth, min_length, min_unambig)
+        for i in range(len(self.target_genomes)):
+            triples = [t for j in self.uncovered_summary.get(i, {}).values() for t in j.values() if t is not None]
+            logger.info("%s%s: %d uncovered regions, %d uncovered bases, longest %d", label,
+                        self.target_genomes_names[i], sum(t[0] for t in triples), sum(t[1] for t in triples),
+                        max([t[2] for t in triples] + [0]))
+
+    # ------------------------------------------------------------------
     def _row_header(self, i, j, rc):
         h = "%s, genome %d" % (self.target_genomes_names[i], j)
         return h + " (rc)" if rc else h
@@ -440,6 +555,40 @@ class Analyzer:
 
     def write_probe_map_counts(self, fn):
         write_probe_map_counts(self.ordered_probe_map_counts(), fn)
+
+
+def add_uncovered_arguments(parser):
+    """The options of the uncovered-region read-out, shared by the command lines."""
+    parser.add_argument("--write-uncovered-regions",
+                        help="TSV of the regions the probes leave uncovered: maximal runs of "
+                             "bases, inside one sequence, below --uncovered-min-depth")
+    parser.add_argument("--write-uncovered-fasta",
+                        help="the uncovered regions of the forward strand as FASTA records")
+    parser.add_argument("--uncovered-min-depth", type=int, default=1,
+                        help="a base is uncovered when fewer than this many cover ranges hold it (default 1)")
+    parser.add_argument("--uncovered-min-length", type=int, default=1,
+                        help="report only regions of at least this many bases (default 1)")
+    parser.add_argument("--uncovered-keep-ambiguous", action="store_true",
+                        help="also report regions without a single A, C, G or T")
+
+
+def uncovered_filters(args):
+    """(min_depth, min_length, min_unambig) of the parsed options."""
+    if args.uncovered_min_depth < 1 or args.uncovered_min_length < 1:
+        raise ValueError("--uncovered-min-depth and --uncovered-min-length must be at least 1")
+    return (args.uncovered_min_depth, args.uncovered_min_length, 0 if args.uncovered_keep_ambiguous else 1)
+
+
+def write_uncovered(analyzer, args):
+    """--write-uncovered-regions / --write-uncovered-fasta of one analyzer that has run."""
+    if not (args.write_uncovered_regions or args.write_uncovered_fasta):
+        return
+    filters = uncovered_filters(args)
+    if args.write_uncovered_regions:
+        analyzer.write_uncovered_regions(args.write_uncovered_regions, *filters)
+    if args.write_uncovered_fasta:
+        analyzer.write_uncovered_fasta(args.write_uncovered_fasta, *filters)
+    analyzer.log_uncovered_summary("", *filters)
 
 
 def write_probe_map_counts(probe_map_counts, fn):

@@ -88,6 +88,8 @@ def parse_args(argv=None, args_type="basic"):
     p.add_argument("--write-analysis-to-tsv")
     p.add_argument("--write-sliding-window-coverage")
     p.add_argument("--write-probe-map-counts-to-tsv")
+    from catch_amd import coverage_analysis
+    coverage_analysis.add_uncovered_arguments(p)
     def dissimilarity(val):
         fval = float(val)
         if fval == 0:
@@ -501,7 +503,8 @@ def main(args):
         seq_io.write_probe_fasta(pb.final_probes, args.write_probe_fasta)
     if (args.print_analysis or args.write_analysis_to_tsv or
             args.write_sliding_window_coverage or
-            args.write_probe_map_counts_to_tsv):
+            args.write_probe_map_counts_to_tsv or
+            args.write_uncovered_regions or args.write_uncovered_fasta):
         # bin/design.py:417-442; the reverse strands are analysed when reverse-
         # complement probes were added (rc_too follows --add-reverse-complements)
         from catch_amd import coverage_analysis
@@ -526,6 +529,7 @@ def main(args):
             analyzer.write_probe_map_counts(args.write_probe_map_counts_to_tsv)
         if args.print_analysis:
             analyzer.print_analysis()
+        coverage_analysis.write_uncovered(analyzer, args)
     else:
         # bin/design.py:443-445: only without an analysis (with --extend-probes: the number of NEW probes)
         print(len(pb.final_probes))

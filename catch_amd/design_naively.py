@@ -57,6 +57,8 @@ def parse_args(argv=None):
                    help="(Optional) Randomly select N target genomes in the dataset with replacement")
     p.add_argument("--print-analysis", dest="print_analysis", action="store_true",
                    help="Print analysis of the probe set's coverage")
+    from catch_amd import coverage_analysis
+    coverage_analysis.add_uncovered_arguments(p)
     p.add_argument("--debug", dest="log_level", action="store_const", const=logging.DEBUG,
                    default=logging.WARNING, help="Debug output")
     p.add_argument("--verbose", dest="log_level", action="store_const", const=logging.INFO,
@@ -107,12 +109,14 @@ def main(args):
     pb.design()
     if getattr(args, "write_probe_fasta", None):
         seq_io.write_probe_fasta(pb.final_probes, args.write_probe_fasta)
-    if args.print_analysis:
+    if args.print_analysis or args.write_uncovered_regions or args.write_uncovered_fasta:
         from catch_amd import coverage_analysis
         analyzer = coverage_analysis.Analyzer(pb.final_probes, mismatches, args.probe_length, seqs,
                                               [args.dataset])
         analyzer.run()
-        analyzer.print_analysis()
+        if args.print_analysis:
+            analyzer.print_analysis()
+        coverage_analysis.write_uncovered(analyzer, args)
     else:
         print(len(pb.final_probes))
     return pb

@@ -747,6 +747,8 @@ class Rows:
         self.last_prune_rounds = 0    # rounds the device took in the last prune() of these rows
         self.last_gains_ms = 0.0      # device time and launches of the last pick_gains() of these rows, summed over
         self.last_gains_launches = 0  # the library calls it was split into
+        self.last_uncovered_ms = 0.0  # device time and launches of the last uncovered() of these rows
+        self.last_uncovered_launches = 0
 
     @staticmethod
     def scan(ctx, probes, targets, mismatches, lcf_thres, island=0,
@@ -829,6 +831,32 @@ class Rows:
         check(fn(self.ctx._h, self._h, _ptr(sf, c_i64p) if sf.size else None, nspans, int(window_length),
                  int(window_stride), _ptr(per_span, c_i64p), _ptr(sums, c_u64p), _ptr(counts, c_u32p), nwin))
         return sums[:nwin], counts[:nwin], win_off
+
+    def uncovered(self, targets=None, min_depth=1, min_length=1, min_unambig=1):
+        """catchhip_rows_uncovered -> (universe int32[n], start int64[n], end int64[n], unambig int64[n],
+        per_universe int64[ngenomes, 3]): the maximal runs of bases, inside one universe, that fewer than
+        `min_depth` rows cover, in (universe, start) order, start and end local to the universe; reported are the
+        runs of `min_length` bases and more of which at least `min_unambig` are A, C, G or T in `targets` (Targets
+        with one genome per sequence over these universes; None: every base counts).  per_universe[u] = (regions,
+        bases, longest) over the reported runs of universe u.  The device time and the launches are left in
+        `last_uncovered_ms` / `last_uncovered_launches`."""
+        if self.ngenomes is None:
+            raise ValueError("uncovered: rows of an unknown number of universes")
+        ng = int(self.ngenomes)
+        per = np.zeros((max(ng, 1), 3), dtype=np.int64)
+        h = ctypes.c_void_p()
+        n = ctypes.c_int64(0)
+        check(self.ctx._L.catchhip_rows_uncovered(
+            self.ctx._h, self._h, None if targets is None else targets._h, int(min_depth), int(min_length),
+            int(min_unambig), ctypes.byref(h), ctypes.byref(n), _ptr(per, c_i64p)))
+        self.last_uncovered_ms, self.last_uncovered_launches = self.ctx.kernel_ms(PHASE_ROWS)
+        regions = Rows(self.ctx, h, n.value, ng)
+        try:
+            ua, un, st, en = regions.fetch()
+        finally:
+            regions.close()
+        # (the count travels in the 32 bits of the set id column)
+        return un, st, en, ua.view(np.uint32).astype(np.int64), per[:ng]
 
     def cover_check(self, num_sets, picks, universe_p=None):
         """catchhip_rows_cover_check: replays `picks` (set ids in pick order) over these rows with kernels that

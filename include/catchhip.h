@@ -1024,6 +1024,32 @@ int catchhip_rows_window_depth(catchhip_ctx *ctx, const catchhip_rows *rows, con
                                int64_t nspans, int64_t window_length, int64_t window_stride,
                                int64_t *span_windows, uint64_t *sums, uint32_t *counts, int64_t capacity);
 
+/* The uncovered regions of a row table without fetching it (csrc/gaps.hip): where a probe set does not reach.
+ * `rows` is a table that is neither deferred nor in the direct form (both: CATCHHIP_EINVAL), with one universe per
+ * sequence and fewer than 2^32 - 4096 bases, as for catchhip_rows_window_depth.  Rows of different or equal sets may
+ * overlap.
+ *   depth of a base = the number of rows whose [start, end) holds it, exact in 32 bits (not the uint16 of the
+ *   sliding-window report)
+ *   region = a maximal run of bases at depth < min_depth inside one universe: two uncovered bases on either side of
+ *   a universe boundary belong to two regions, and a universe of length 0 has none
+ *   unambiguous count of a region = with `targets`, the number of its bases that are one of A, C, G, T (the rule of
+ *   Genome.size(True): N, every other letter and lower case are ambiguous); `targets` must hold one genome per
+ *   sequence and have the genome offsets of `rows`, anything else is CATCHHIP_EINVAL.  With targets == NULL the
+ *   count is the region's length.
+ * A region is reported when its length is >= min_length and its unambiguous count >= min_unambig (0 keeps regions
+ * without an unambiguous base).  *out receives a row table of the reported regions in (universe, start) order,
+ * to be read with catchhip_rows_fetch -- universe, start and end local to the universe -- whose set_id column
+ * carries the unambiguous count (its 32 bits read as unsigned).  That table is a read-out: it is not sorted by set and
+ * must not be handed to the calls that take an instance's rows.  *nregions (may be NULL) = its rows; it may be 0,
+ * *out is then an empty table, not NULL.  per_universe (may be NULL) receives 3 values per universe, over the
+ * reported regions: their number, their bases, the longest.  Integer arithmetic throughout; the result does not
+ * depend on the order of the device's atomics.  The device time is left in phase 1 of catchhip_ctx_last_kernel_ms.
+ * CATCHHIP_EINVAL: min_depth < 1, min_length < 1, min_unambig < 0, deferred or direct rows, targets of another
+ * shape. */
+int catchhip_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *rows, const catchhip_targets *targets,
+                            int32_t min_depth, int64_t min_length, int64_t min_unambig, catchhip_rows **out,
+                            int64_t *nregions, int64_t *per_universe);
+
 /* Where every set id < num_sets was seen first, on rows from catchhip_cover_scan_first_seen with one universe per
  * sequence: first_universe[s] = the first universe set s has rows in (-1: none) and first_key[s] = the key of the
  * first accepted seed there (catchhip_rows_fetch_first_seen).  Sorting the sets by (first_universe, first_key)
