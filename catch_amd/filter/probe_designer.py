@@ -276,14 +276,10 @@ class ProbeDesigner:
             return None
         if scf.identify or scf.avoided_genomes:
             return None
-        if getattr(scf, "fixed_probes", None):
-            return None                  # extending a probe set: the host front end (SetCoverFilter._filter_strs_extend)
-        if getattr(scf, "coverage_depth", 1) > 1:
-            return None                  # layers of a coverage depth: the host front end (SetCoverFilter._filter_strs_depth)
-        if getattr(scf, "prune_redundant", False):
-            return None                  # pruning needs the group's rows: the host front end, as for a coverage depth
-        if getattr(scf, "pick_gains", False):
-            return None                  # so do the gains per pick (and the probe budget that rests on them)
+        if scf.needs_rows:
+            # extending a probe set, layers of a coverage depth, pruning, the gains per pick (and the probe budget that
+            # rests on them) work on the group's rows: the host front end (SetCoverFilter._filter_strs_keeping_rows)
+            return None
         skip, L = self.seq_length_to_skip, self.probe_length
         total, ngroups = 0, 0
         if isinstance(genomes, ClusteredFragments):

@@ -9,9 +9,9 @@ CPU fallback: without the library or a GPU the filter raises.
 
 Beyond the reference: `fixed_probes` (a trailing keyword) names probes the user
 owns already; the filter then selects only what they leave uncovered
-(_filter_strs_extend).  `coverage_depth` (after it) asks for every base to be
-covered by that many selected probes, one greedy layer per unit of depth
-(_filter_strs_depth).  `prune_redundant` (a keyword too) looks back at the picks
+(_filter_strs_keeping_rows).  `coverage_depth` (after it) asks for every base to
+be covered by that many selected probes, one greedy layer per unit of depth
+(the same method).  `prune_redundant` (a keyword too) looks back at the picks
 once the design is complete and drops those that cover nothing alone
 (engine.Rows.prune).  `pick_gains` (a keyword) reports what every pick added
 when it was taken and the coverage after the first k picks
@@ -135,7 +135,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         self.scan_mode = engine.SCAN_AUTO
         self.last_timings = {}
         # probes the user owns already (strings or Probe objects; not an argument of the reference's class): the
-        # filter then selects only what they leave uncovered (_filter_strs_extend)
+        # filter then selects only what they leave uncovered (_filter_strs_keeping_rows)
         self.fixed_probes = [q if isinstance(q, str) else q.seq_str
                              for q in (fixed_probes if fixed_probes is not None else ())]
         self.coverage_depth = 1     # (SetCoverFilter(..., coverage_depth=D) sets it: _KeywordsBeyondInit)
@@ -194,7 +194,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
     def _set_coverage_depth(self, coverage_depth):
         """How many selected probes are to cover every base (not an argument of
         the reference's class): 1 is the reference's set cover, more runs one
-        greedy layer per unit of depth (_filter_strs_depth)."""
+        greedy layer per unit of depth (_filter_strs_keeping_rows)."""
         if (isinstance(coverage_depth, bool) or not isinstance(coverage_depth, (int, np.integer))
                 or coverage_depth < 1):
             raise ValueError("coverage_depth must be an integer >= 1, not %r" % (coverage_depth,))
@@ -207,29 +207,61 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
     def _context(self):
         return engine.default_context()
 
+    @property
+    def needs_rows(self):
+        """Whether an option is on that works on a group's cover rows after the
+        scan (_filter_strs_keeping_rows): the fused scan-and-solve call and the
+        device front end never hand the rows out."""
+        return bool(self.fixed_probes) or self.coverage_depth > 1 or self.prune_redundant or self.pick_gains
+
+    def _anchor_table(self, strs, assume_unique=False, tolerant=False):
+        """probe.anchor_table of `strs` under the strict hybridization model, or
+        the tolerant one (the ranks)."""
+        mismatches, lcf_thres = ((self.mismatches_tolerant, self.lcf_thres_tolerant) if tolerant
+                                 else (self.mismatches, self.lcf_thres))
+        return probe.anchor_table(strs, mismatches, lcf_thres, min_k=self.kmer_probe_map_k,
+                                  k=self.kmer_probe_map_k, assume_unique=assume_unique)
+
+    def _model_args(self):
+        """The hybridization model and scan mode, as the keywords that
+        engine.Rows.scan, setcover_filter and setcover_filter_many share."""
+        return dict(mismatches=self.mismatches, lcf_thres=self.lcf_thres, island=self.island_of_exact_match,
+                    cover_extension=self.cover_extension, mode=self.scan_mode)
+
+    def _open_group(self, ctx, held, strs, genomes, assume_unique=False, table=None, targets=None):
+        """(Targets, Probes) of one instance on `ctx`: the anchor table of `strs`
+        (or `table`, drawn earlier) and the sequences of `genomes` (or `targets`,
+        which stays the caller's).  What is made here is appended to `held`; the
+        caller closes it."""
+        k, uniq, owner, ep, eo = table if table is not None else self._anchor_table(strs, assume_unique)
+        if targets is None:
+            targets = engine.Targets(ctx, [g.seqs for g in genomes])
+            held.append(targets)
+        probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
+        held.append(probes)
+        return targets, probes
+
+    def _scan_group(self, ctx, held, strs, genomes, assume_unique=False, table=None, targets=None):
+        """_open_group and the cover rows of the probes on the targets ->
+        (Targets, Probes, Rows), the Rows in `held` too."""
+        targets, probes = self._open_group(ctx, held, strs, genomes, assume_unique, table, targets)
+        rows = engine.Rows.scan(ctx, probes, targets, **self._model_args())
+        held.append(rows)
+        return targets, probes, rows
+
     def _make_sets(self, candidate_probes, target_genomes, ctx=None,
                    targets=None):
         """Device rows for one group (:359-470).  Returns (rows, owner) where
         rows is an engine.Rows (set ids = indices into candidate_probes)."""
         ctx = ctx or self._context()
-        strs = [p.seq_str for p in candidate_probes]
-        k, uniq, owner, ep, eo = probe.anchor_table(
-            strs, self.mismatches, self.lcf_thres,
-            min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k)
-        own_targets = targets is None
-        if own_targets:
-            targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
-        probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
+        held = []
         try:
-            rows = engine.Rows.scan(ctx, probes, targets, self.mismatches,
-                                    self.lcf_thres,
-                                    self.island_of_exact_match,
-                                    self.cover_extension, self.scan_mode)
+            targets, probes = self._open_group(ctx, held, [p.seq_str for p in candidate_probes],
+                                               target_genomes, targets=targets)
+            return engine.Rows.scan(ctx, probes, targets, **self._model_args())
         finally:
-            probes.close()
-            if own_targets:
-                targets.close()
-        return rows
+            for h in reversed(held):
+                h.close()
 
     def _tolerant_bp_over(self, ctx, probes_dev, n_uniq, sequences):
         """Sum over `sequences` and their reverse complements of the bp each
@@ -263,9 +295,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         if not need:
             return np.zeros(n, dtype=np.int64)
         ctx = ctx or self._context()
-        k, uniq, _owner, ep, eo = probe.anchor_table(
-            strs, self.mismatches_tolerant, self.lcf_thres_tolerant,
-            min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k)
+        k, uniq, _owner, ep, eo = self._anchor_table(strs, tolerant=True)
         ident = np.arange(len(uniq), dtype=np.int32)
         pd = engine.Probes(ctx, uniq, ident, ep, eo, k)
         try:
@@ -328,19 +358,14 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         the ranks and every rank returns the complete selection."""
         import os
         from catch_amd import parallel
-        if self.fixed_probes:
-            return self._filter_strs_extend(input_strs, target_genomes_grouped,
-                                            assume_unique)
-        if self.coverage_depth > 1 or self.prune_redundant or self.pick_gains:
-            # (pruning and the gains need the group's rows: the layered path keeps them, at depth 1 too)
-            return self._filter_strs_depth(input_strs, target_genomes_grouped,
-                                           assume_unique)
+        if self.needs_rows:
+            return self._filter_strs_keeping_rows(input_strs, target_genomes_grouped,
+                                                  assume_unique)
         if only is None and parallel.world().size > 1:
             return self._filter_strs_multirank(input_strs, target_genomes_grouped,
                                                assume_unique, parallel.world())
         selected = [[] for _ in input_strs]
-        timings = dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0,
-                       rows=0, scan_launches=0, greedy_launches=0)
+        timings = _new_timings()
         nonempty = [i for i, pp in enumerate(input_strs) if len(pp) > 0]
         todo = [i for i in nonempty if only is None or i in only]
         random_anchors = any(probe.anchors_use_random(
@@ -388,16 +413,9 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                         input_strs[gi], target_genomes_grouped[gi]
                     logger.info("Building set cover sets input (group %d of %d)",
                                 gi + 1, len(input_strs))
-                    k, uniq, owner, ep, eo = (
-                        tables.pop(gi) if tables is not None else
-                        probe.anchor_table(
-                            strs, self.mismatches, self.lcf_thres,
-                            min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
-                            assume_unique=assume_unique))
-                    targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
-                    held.append(targets)
-                    probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
-                    held.append(probes)
+                    targets, probes = self._open_group(
+                        ctx, held, strs, target_genomes, assume_unique,
+                        table=tables.pop(gi) if tables is not None else None)
                     ranks = self._make_ranks_strs(strs, target_genomes_grouped,
                                                   ctx)
                     all_ranks.append(ranks)
@@ -406,270 +424,163 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                                   self._make_universe_p(target_genomes)))
                 logger.info("Solving set cover instances (groups %s of %d)",
                             [gi + 1 for gi in chunk], len(input_strs))
-                results = engine.setcover_filter_many(
-                    specs, self.mismatches, self.lcf_thres,
-                    self.island_of_exact_match, self.cover_extension,
-                    self.scan_mode)
+                results = engine.setcover_filter_many(specs, **self._model_args())
             finally:
                 for h in held:
                     h.close()
             for ctx, gi, ranks, (ids, nrows) in zip(ctxs, chunk, all_ranks,
                                                     results):
                 _accumulate(timings, ctx, nrows, len(ids))
-                num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
-                if num_bad > 0:
-                    logger.warning(("Group %d: forced to choose %d less-than-ideal "
-                                    "probe%s (i.e., probes that 'hit' more than "
-                                    "one grouping during identification or probes "
-                                    "that cover an avoided genome)"), gi + 1,
-                                   num_bad, "" if num_bad == 1 else "s")
+                _warn_less_than_ideal(gi, ranks, ids)
                 selected[gi] = list(ids)
         self.last_timings = timings
         return selected
 
+    def _filter_strs_keeping_rows(self, input_strs, target_genomes_grouped,
+                                  assume_unique=False):
+        """_filter_strs for the options that work on a group's cover rows
+        (needs_rows): one group after the other on one context, in input order,
+        one scan of the candidates per group.  Per group:
 
-    def _filter_strs_extend(self, input_strs, target_genomes_grouped,
-                            assume_unique=False):
-        """_filter_strs with fixed probes: per group the candidates that bring
-        its genomes up to the required coverage GIVEN the fixed probes, in pick
-        order.  The fixed probes count as sets picked before the first round of
-        the greedy loop (catch/utils/set_cover.py:362-550): their coverage C0_u
-        (the filter's own hybridization model, strands as given) leaves every
-        universe and every candidate's rows, and as many bases may stay
-        uncovered as in U_u = (union of the candidates' rows) + C0_u
-        (extension_fraction).  The solvers run unchanged on the reduced
-        instance.  One group after the other on one context, in input order; the
-        fixed probes' anchors are drawn first."""
+        1. The scan -> `rows`.
+        2. The first table.  With fixed probes they count as sets picked before
+           the first round of the greedy loop (catch/utils/set_cover.py:362-550):
+           their coverage C0_u (one more scan; the filter's own hybridization
+           model, strands as given) leaves every universe and every candidate's
+           rows (Rows.subtract), and as many bases may stay uncovered as in U_u =
+           (union of the candidates' rows) + C0_u (extension_fraction).  Without
+           them the first table is `rows` under the user's fractions.
+        3. coverage_depth = D layers, depth(b) = the number of candidates picked
+           so far with a cover row over base b.  Layer 1 solves the first table.
+           Layer k > 1 is the rows of the unpicked candidates cut into their runs
+           of bases with depth < k (Rows.below_depth); its universe u is those
+           n2[u] bases together with the reached[u] bases at depth >= k, of which
+           int(|U| - p |U|) may stay below k (extension_fraction restates p for
+           the n2[u] bases the solver sees).  The solvers run unchanged, with the
+           same ranks in every layer; the first k layers are the design at depth
+           k.  A layer with no row left is empty and logged.  (The constructor
+           refuses D > 1 with fixed probes: with them this is one layer.)
+        4. prune_redundant: the picks of all layers go through Rows.prune at
+           depth D, beside the fixed probes' rows, which stay whatever happens
+           (the nesting of the layers is lost: a pick of layer 1 may be dropped
+           for picks of layer 2); last_layer_sizes stays what the layers picked,
+           last_pruned[group] the dropped ones.
+        5. pick_gains / max_probes: _Budget, on the first table -- the one that
+           went to the solver --, beside it the bases the fixed probes cover.
+
+        The fixed probes' anchors are drawn first, once.  What a run with fixed
+        probes reports (last_timings' keys, last_layer_sizes, log lines) differs
+        from one without in ways its callers rely on and no stage requires: the
+        comments marked (quirk)."""
         from catch_amd import parallel
+        fixed = bool(self.fixed_probes)
         if parallel.world().size > 1:
             raise NotImplementedError(
-                "fixed probes (extending an existing probe set) run on one rank")
+                "fixed probes (extending an existing probe set) run on one rank" if fixed else
+                "coverage_depth > 1, prune_redundant, pick_gains and max_probes run on one rank")
         ctx = self._context()
+        ngroups = len(input_strs)
         selected = [[] for _ in input_strs]
         self.last_pruned = [[] for _ in input_strs]
-        if self.prune_redundant:
-            self.last_layer_sizes = [[] for _ in input_strs]     # (one layer: what the extension's solve picked)
-        timings = dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0, rows=0,
-                       scan_launches=0, greedy_launches=0, fixed_scan_ms=0.0,
-                       subtract_ms=0.0, rows_fixed=0, rows_reduced=0)
+        # (quirk) an extension reports its one layer only when it prunes, and leaves last_layer_sizes alone otherwise
+        keeps_sizes = not fixed or self.prune_redundant
+        if keeps_sizes:
+            self.last_layer_sizes = [[] for _ in input_strs]
+        # (quirk) depth_ms only without fixed probes -- depth_launches only once a layer above 1 ran --, and rows_reduced
+        # counts the rows of the reduced table with them, of the layers above 1 without
+        timings = _new_timings(rows_reduced=0, **(dict(fixed_scan_ms=0.0, subtract_ms=0.0, rows_fixed=0) if fixed
+                                                  else dict(depth_ms=0.0)))
         if self.prune_redundant:
             timings.update(prune_ms=0.0, prune_launches=0, prune_rounds=0, pruned=0)
-        budget = _Budget(self, ctx, len(input_strs), timings)
-
-        def add_phases(names):
-            for name, ph in names:
-                ms, nl = ctx.kernel_ms(ph)
-                timings[name] = timings.get(name, 0.0) + ms
-                ln = name.replace("_ms", "_launches")
-                timings[ln] = timings.get(ln, 0) + nl
-
-        fk, funiq, _fowner, fep, feo = probe.anchor_table(
-            self.fixed_probes, self.mismatches, self.lcf_thres,
-            min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k)
-        fowner = np.zeros(len(funiq), dtype=np.int32)     # one set: only their union matters
-        scan_args = (self.mismatches, self.lcf_thres, self.island_of_exact_match,
-                     self.cover_extension, self.scan_mode)
+        budget = _Budget(self, ctx, ngroups, timings)
+        if fixed:
+            fk, funiq, _fowner, fep, feo = self._anchor_table(self.fixed_probes)
+            fixed_table = (fk, funiq, np.zeros(len(funiq), dtype=np.int32), fep, feo)    # one set: only their union matters
         try:
             for gi, strs in enumerate(input_strs):
                 if len(strs) == 0:
                     continue
                 target_genomes = target_genomes_grouped[gi]
                 ng = len(target_genomes)
-                logger.info("Building set cover sets input (group %d of %d), %d fixed probes",
-                            gi + 1, len(input_strs), len(funiq))
-                k, uniq, owner, ep, eo = probe.anchor_table(
-                    strs, self.mismatches, self.lcf_thres,
-                    min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
-                    assume_unique=assume_unique)
+                if fixed:
+                    logger.info("Building set cover sets input (group %d of %d), %d fixed probes",
+                                gi + 1, ngroups, len(funiq))
+                else:
+                    logger.info("Building set cover sets input (group %d of %d), coverage depth %d",
+                                gi + 1, ngroups, self.coverage_depth)
                 held = []
                 try:
-                    targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
-                    held.append(targets)
-                    probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
-                    held.append(probes)
-                    rows = engine.Rows.scan(ctx, probes, targets, *scan_args)
-                    held.append(rows)
-                    add_phases((("scan_ms", engine.PHASE_SCAN), ("verify_ms", engine.PHASE_VERIFY),
-                                ("rows_ms", engine.PHASE_ROWS)))
-                    fprobes = engine.Probes(ctx, funiq, fowner, fep, feo, fk)
-                    held.append(fprobes)
-                    frows = engine.Rows.scan(ctx, fprobes, targets, *scan_args)
-                    held.append(frows)
-                    timings["fixed_scan_ms"] += sum(ctx.kernel_ms(ph)[0] for ph in (
-                        engine.PHASE_SCAN, engine.PHASE_ROWS))     # (the verify phase lies inside the scan phase)
-                    reduced = rows.subtract(frows)
-                    held.append(reduced)
-                    timings["subtract_ms"] += ctx.kernel_ms(engine.PHASE_ROWS)[0]
-                    n2 = reduced.stats(ng)[1]
-                    c0 = frows.stats(ng)[1]
-                    universe_p = [extension_fraction(int(a), int(b), p) for a, b, p in
-                                  zip(n2, c0, self._make_universe_p(target_genomes))]
-                    ranks = self._make_ranks_strs(strs, target_genomes_grouped, ctx)
-                    logger.info("Solving the set cover instance of group %d of %d",
-                                gi + 1, len(input_strs))
-                    ids = reduced.greedy(
-                        len(strs), ranks if ranks.any() else None,
-                        None if all(p == 1.0 for p in universe_p) else universe_p)
-                    add_phases((("greedy_ms", engine.PHASE_GREEDY),
-                                ("rounds_ms", engine.PHASE_GREEDY_ROUNDS),
-                                ("claim_ms", engine.PHASE_CLAIM)))
-                    timings["rows"] += rows.n
-                    timings["rows_fixed"] += frows.n
-                    timings["rows_reduced"] += reduced.n
-                    if self.prune_redundant:
-                        # the new probes beside the fixed ones, which stay whatever happens
-                        self.last_layer_sizes[gi] = [len(ids)]
-                        ids, self.last_pruned[gi] = _prune(ctx, rows, len(strs), ids, 1, frows, timings)
-                    timings["picks"] += len(ids)
-                    if self.pick_gains:
-                        # the table that went to the solver; beside it the bases the fixed probes cover
-                        budget.group(gi, reduced, len(strs), ids, n2 + c0, c0)
-                finally:
-                    for h in reversed(held):
-                        if not budget.holds(h):
-                            h.close()
-                num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
-                if num_bad > 0:
-                    logger.warning(("Group %d: forced to choose %d less-than-ideal "
-                                    "probe%s (i.e., probes that 'hit' more than "
-                                    "one grouping during identification or probes "
-                                    "that cover an avoided genome)"), gi + 1,
-                                   num_bad, "" if num_bad == 1 else "s")
-                selected[gi] = list(ids)
-            budget.finish(selected, input_strs)
-        finally:
-            budget.release()         # (a group that raised: the tables kept for the cut)
-        self.last_timings = timings
-        return selected
-
-    def _filter_strs_depth(self, input_strs, target_genomes_grouped,
-                           assume_unique=False):
-        """_filter_strs with coverage_depth = D > 1 (or D = 1 with
-        prune_redundant, which needs the rows): per group the candidates of
-        D greedy layers, in layer order and then pick order.  depth(b) = the
-        number of candidates picked so far with a cover row over base b.  Layer
-        1 is the ordinary instance (the scanned rows, the user's fractions).
-        Layer k > 1 is the rows of the unpicked candidates cut into their runs
-        of bases with depth < k (Rows.below_depth); its universe u is those
-        n2[u] bases together with the reached[u] bases at depth >= k, of which
-        int(|U| - p |U|) may stay below k (extension_fraction restates p for the
-        n2[u] bases the solver sees).  The solvers run unchanged, with the same
-        ranks in every layer; the first k layers are the design at depth k.  A
-        layer with no row left is empty and logged.  One group after the other
-        on one context, in input order, one scan per group.  With
-        prune_redundant the picks of all layers go through Rows.prune at depth D
-        after the last layer (the nesting of the layers is lost: a pick of layer
-        1 may be dropped for picks of layer 2); last_layer_sizes stays what the
-        layers picked, last_pruned[group] the dropped ones."""
-        from catch_amd import parallel
-        if parallel.world().size > 1:
-            raise NotImplementedError("coverage_depth > 1, prune_redundant, pick_gains and max_probes run on one rank")
-        ctx = self._context()
-        selected = [[] for _ in input_strs]
-        self.last_layer_sizes = [[] for _ in input_strs]
-        self.last_pruned = [[] for _ in input_strs]
-        timings = dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0, rows=0,
-                       scan_launches=0, greedy_launches=0, depth_ms=0.0,
-                       rows_reduced=0)
-        if self.prune_redundant:
-            timings.update(prune_ms=0.0, prune_launches=0, prune_rounds=0, pruned=0)
-        budget = _Budget(self, ctx, len(input_strs), timings)
-
-        def add_phases(names):
-            for name, ph in names:
-                ms, nl = ctx.kernel_ms(ph)
-                timings[name] = timings.get(name, 0.0) + ms
-                ln = name.replace("_ms", "_launches")
-                timings[ln] = timings.get(ln, 0) + nl
-
-        greedy_phases = (("greedy_ms", engine.PHASE_GREEDY),
-                         ("rounds_ms", engine.PHASE_GREEDY_ROUNDS),
-                         ("claim_ms", engine.PHASE_CLAIM))
-        try:
-            for gi, strs in enumerate(input_strs):
-                if len(strs) == 0:
-                    continue
-                target_genomes = target_genomes_grouped[gi]
-                ng = len(target_genomes)
-                logger.info("Building set cover sets input (group %d of %d), coverage depth %d",
-                            gi + 1, len(input_strs), self.coverage_depth)
-                k, uniq, owner, ep, eo = probe.anchor_table(
-                    strs, self.mismatches, self.lcf_thres,
-                    min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
-                    assume_unique=assume_unique)
-                held = []
-                try:
-                    targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
-                    held.append(targets)
-                    probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
-                    held.append(probes)
-                    rows = engine.Rows.scan(ctx, probes, targets, self.mismatches, self.lcf_thres,
-                                            self.island_of_exact_match, self.cover_extension,
-                                            self.scan_mode)
-                    held.append(rows)
-                    add_phases((("scan_ms", engine.PHASE_SCAN), ("verify_ms", engine.PHASE_VERIFY),
-                                ("rows_ms", engine.PHASE_ROWS)))
+                    targets, _probes, rows = self._scan_group(ctx, held, strs, target_genomes, assume_unique)
+                    _add_phase_times(timings, ctx, _SCAN_PHASES)
                     timings["rows"] += rows.n
                     p = self._make_universe_p(target_genomes)
+                    if fixed:
+                        frows = self._scan_group(ctx, held, None, None, table=fixed_table, targets=targets)[2]
+                        timings["fixed_scan_ms"] += sum(ctx.kernel_ms(ph)[0] for ph in (
+                            engine.PHASE_SCAN, engine.PHASE_ROWS))     # (the verify phase lies inside the scan phase)
+                        first = rows.subtract(frows)
+                        held.append(first)
+                        timings["subtract_ms"] += ctx.kernel_ms(engine.PHASE_ROWS)[0]
+                        timings["rows_fixed"] += frows.n
+                        timings["rows_reduced"] += first.n
+                        n2, covered0 = first.stats(ng)[1], frows.stats(ng)[1]
+                        first_p = [extension_fraction(int(a), int(b), q) for a, b, q in zip(n2, covered0, p)]
+                        denom = n2 + covered0
+                    else:
+                        frows, first, first_p, covered0 = None, rows, p, None
                     ranks = self._make_ranks_strs(strs, target_genomes_grouped, ctx)
                     rk = ranks if ranks.any() else None
                     ids, sizes = [], []
                     for layer in range(1, self.coverage_depth + 1):
                         if layer == 1:
-                            table, universe_p = rows, p
+                            table, universe_p = first, first_p
                         else:
                             table, reached = rows.below_depth(len(strs), ids, layer)
                             held.append(table)
-                            ms, nl = ctx.kernel_ms(engine.PHASE_ROWS)
-                            timings["depth_ms"] += ms
-                            timings["depth_launches"] = timings.get("depth_launches", 0) + nl
+                            _add_phase_times(timings, ctx, (("depth_ms", engine.PHASE_ROWS),))
                             timings["rows_reduced"] += table.n
                             if table.n == 0:
                                 # (not the end: a base that `layer` picks hold lies below the next layer's depth)
                                 logger.info("Group %d of %d: no candidate is left to raise any base to "
-                                            "depth %d; layer %d is empty", gi + 1, len(input_strs),
-                                            layer, layer)
+                                            "depth %d; layer %d is empty", gi + 1, ngroups, layer, layer)
                                 held.remove(table)
                                 table.close()
                                 sizes.append(0)
                                 continue
-                            n2 = table.stats(ng)[1]
                             universe_p = [extension_fraction(int(a), int(b), q)
-                                          for a, b, q in zip(n2, reached, p)]
-                        logger.info("Solving the set cover instance of group %d of %d, layer %d of %d",
-                                    gi + 1, len(input_strs), layer, self.coverage_depth)
-                        got = table.greedy(len(strs), rk,
-                                           None if all(q == 1.0 for q in universe_p) else universe_p)
-                        add_phases(greedy_phases)
-                        if table is not rows:
+                                          for a, b, q in zip(table.stats(ng)[1], reached, p)]
+                        if fixed:
+                            logger.info("Solving the set cover instance of group %d of %d", gi + 1, ngroups)
+                        else:
+                            logger.info("Solving the set cover instance of group %d of %d, layer %d of %d",
+                                        gi + 1, ngroups, layer, self.coverage_depth)
+                        got = table.greedy(len(strs), rk, _solver_fractions(universe_p))
+                        _add_phase_times(timings, ctx, _GREEDY_PHASES)
+                        if layer > 1:
                             held.remove(table)
                             table.close()
                         ids += got
                         sizes.append(len(got))
                     if self.prune_redundant:
-                        ids, self.last_pruned[gi] = _prune(ctx, rows, len(strs), ids, self.coverage_depth, None,
+                        ids, self.last_pruned[gi] = _prune(ctx, rows, len(strs), ids, self.coverage_depth, frows,
                                                            timings)
                     timings["picks"] += len(ids)
                     if self.pick_gains:
-                        budget.group(gi, rows, len(strs), ids, rows.stats(ng)[1], None)
+                        budget.group(gi, first, len(strs), ids, denom if fixed else rows.stats(ng)[1], covered0)
                 finally:
                     for h in reversed(held):
                         if not budget.holds(h):
                             h.close()
-                logger.info("Group %d of %d: picks per layer %s", gi + 1, len(input_strs),
-                            " / ".join(str(x) for x in sizes))
-                if self.prune_redundant:
-                    logger.info("Group %d of %d: %d picked, %d redundant", gi + 1, len(input_strs),
-                                sum(sizes), len(self.last_pruned[gi]))
-                num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
-                if num_bad > 0:
-                    logger.warning(("Group %d: forced to choose %d less-than-ideal "
-                                    "probe%s (i.e., probes that 'hit' more than "
-                                    "one grouping during identification or probes "
-                                    "that cover an avoided genome)"), gi + 1,
-                                   num_bad, "" if num_bad == 1 else "s")
+                if not fixed:       # (quirk) an extension logs neither line
+                    logger.info("Group %d of %d: picks per layer %s", gi + 1, ngroups,
+                                " / ".join(str(x) for x in sizes))
+                    if self.prune_redundant:
+                        logger.info("Group %d of %d: %d picked, %d redundant", gi + 1, ngroups,
+                                    sum(sizes), len(self.last_pruned[gi]))
+                _warn_less_than_ideal(gi, ranks, ids)
                 selected[gi] = list(ids)
-                self.last_layer_sizes[gi] = sizes
+                if keeps_sizes:
+                    self.last_layer_sizes[gi] = sizes
             budget.finish(selected, input_strs)
         finally:
             budget.release()         # (a group that raised: the tables kept for the cut)
@@ -695,20 +606,9 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
             self.last_timings = timings
             return [], []
         ctx = self._context()
-        k, uniq, owner, ep, eo = probe.anchor_table(
-            probe_strs, self.mismatches, self.lcf_thres,
-            min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
-            assume_unique=True)
         held = []
         try:
-            targets = engine.Targets(ctx, [g.seqs for g in target_genomes])
-            held.append(targets)
-            probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
-            held.append(probes)
-            rows = engine.Rows.scan(ctx, probes, targets, self.mismatches, self.lcf_thres,
-                                    self.island_of_exact_match, self.cover_extension,
-                                    self.scan_mode)
-            held.append(rows)
+            rows = self._scan_group(ctx, held, probe_strs, target_genomes, assume_unique=True)[2]
             timings["scan_ms"] = ctx.kernel_ms(engine.PHASE_SCAN)[0]
             timings["rows_ms"] = ctx.kernel_ms(engine.PHASE_ROWS)[0]
             timings["rows"] = rows.n
@@ -729,11 +629,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                                             self.lcf_thres, self.kmer_probe_map_k)
                    for i in nonempty):
             return None
-        return {i: probe.anchor_table(input_strs[i], self.mismatches, self.lcf_thres,
-                                      min_k=self.kmer_probe_map_k,
-                                      k=self.kmer_probe_map_k,
-                                      assume_unique=assume_unique)
-                for i in nonempty}
+        return {i: self._anchor_table(input_strs[i], assume_unique) for i in nonempty}
 
     def _filter_strs_multirank(self, input_strs, target_genomes_grouped,
                                assume_unique, W):
@@ -769,8 +665,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
             if eligible else float("inf"),
             eligible=[len(target_genomes_grouped[i]) >= W.size for i in range(n)])
         selected = [[] for _ in range(n)]
-        timings = dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0, rows=0,
-                       scan_launches=0, greedy_launches=0, sharded_groups=list(sharded))
+        timings = _new_timings(sharded_groups=list(sharded))
         ctx = W.comm_ctx
         fallback = []
         nonempty = [i for i in range(n) if len(input_strs[i]) > 0]
@@ -785,24 +680,16 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
             strs, genomes = input_strs[gi], target_genomes_grouped[gi]
             logger.info("Set cover of group %d of %d sharded over %d ranks",
                         gi + 1, n, W.size)
-            rows = shard = probes = targets = None
+            rows = shard = None
+            held = []
             err, qualifies = None, False
             try:
                 # a failure on one rank (out of memory, a library error) is reported to ALL ranks below:
                 # nobody may walk into the solver's all-reduces alone
                 try:
-                    k, uniq, owner, ep, eo = (
-                        tables[gi] if tables is not None else
-                        probe.anchor_table(
-                            strs, self.mismatches, self.lcf_thres,
-                            min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
-                            assume_unique=assume_unique))
                     b = parallel.split_universes([g.size() for g in genomes], W.size)
-                    targets = engine.Targets(ctx, [g.seqs for g in genomes[b[W.rank]:b[W.rank + 1]]])
-                    probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
-                    rows = engine.Rows.scan(ctx, probes, targets, self.mismatches,
-                                            self.lcf_thres, self.island_of_exact_match,
-                                            self.cover_extension, self.scan_mode)
+                    rows = self._scan_group(ctx, held, strs, genomes[b[W.rank]:b[W.rank + 1]], assume_unique,
+                                            table=tables[gi] if tables is not None else None)[2]
                     ranks = (self._make_ranks_strs(strs, target_genomes_grouped, ctx)
                              if (self.identify or self.avoided_genomes) else None)
                     try:
@@ -814,6 +701,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                         shard = engine.Shard(rows, len(strs), ranks,
                                              up_all[b[W.rank]:b[W.rank + 1]] if part else None,
                                              instance_partial=part)
+                        held.append(shard)
                         qualifies = True
                     except ValueError as exc:
                         # the expected refusal: rows too long or too many sets for the sharded kernels -> whole group
@@ -834,9 +722,8 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                 else:
                     fallback.append(gi)
             finally:
-                for h in (shard, rows, probes, targets):
-                    if h is not None:
-                        h.close()
+                for h in reversed(held):
+                    h.close()
         # groups that could not be sharded after all go whole to the least loaded rank
         loads = [sum(costs[i] for i in w) for w in whole]
         for gi in fallback:
@@ -879,9 +766,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         import os
         assert not self.identify and not self.avoided_genomes
         out = [[] for _ in target_genomes_grouped]
-        timings = dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0,
-                       rows=0, scan_launches=0, greedy_launches=0,
-                       candidates=0, unique_candidates=0)
+        timings = _new_timings(candidates=0, unique_candidates=0)
         import time as _time
         events, t_call = [], _time.perf_counter()      # (stage, item, start, end): the pipeline's timeline
         todo = [i for i, g in enumerate(target_genomes_grouped) if len(g) > 0]
@@ -1118,9 +1003,8 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                                 logger.warning("There are no candidate probes for a "
                                                "grouping of genomes")
                             ids, nrows = engine.setcover_filter(
-                                ctx, probes, targets, self.mismatches, self.lcf_thres,
-                                self.island_of_exact_match, self.cover_extension, cands.n, None,
-                                universe_p_of(gi), self.scan_mode)
+                                ctx, probes, targets, num_sets=cands.n, universe_p=universe_p_of(gi),
+                                **self._model_args())
                             t_s1 = _time.perf_counter()
                             finish(ctx, gi, targets, cands, probes, ncand, nuniq, ids, nrows, res_lock)
                             events.append(("solve lane %d" % li, gi, t_s0 - t_call, t_s1 - t_call))
@@ -1175,10 +1059,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                                 logger.warning("There are no candidate probes for a "
                                                "grouping of genomes")
                             specs.append((ctx, probes, targets, cands.n, None, universe_p_of(gi)))
-                        results = engine.setcover_filter_many(
-                            specs, self.mismatches, self.lcf_thres,
-                            self.island_of_exact_match, self.cover_extension,
-                            self.scan_mode)
+                        results = engine.setcover_filter_many(specs, **self._model_args())
                         for ctx, gi, b, (ids, nrows) in zip(ctxs, chunk, built, results):
                             finish(ctx, gi, b[0], b[1], b[2], b[3], b[4], ids, nrows)
                     finally:
@@ -1209,9 +1090,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         assert not self.identify and not self.avoided_genomes
         ngroups = len(target_genomes_grouped)
         out = [[] for _ in range(ngroups)]
-        timings = dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0,
-                       rows=0, scan_launches=0, greedy_launches=0,
-                       candidates=0, unique_candidates=0)
+        timings = _new_timings(candidates=0, unique_candidates=0)
         ctx = engine.default_context()
         # the clusters of a clustered design may come as views of the genomes' storage (probe_designer.
         # ClusteredFragments: every member a single-sequence genome): sizes, targets and the selected probes' text
@@ -1219,17 +1098,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         views = target_genomes_grouped if hasattr(target_genomes_grouped, "table") else None
         group_bases = (views.group_bases().tolist() if views is not None
                        else [sum(g.size() for g in grp) for grp in target_genomes_grouped])
-        chunks, at = [], 0
-        while at < ngroups:
-            chunk, bases = [], 0
-            while at < ngroups:
-                b = group_bases[at]
-                if chunk and bases + b > max_bases:
-                    break
-                chunk.append(at)
-                bases += b
-                at += 1
-            chunks.append(chunk)
+        chunks = _pack_under_cap(group_bases, max_bases)
 
         # Two stages, one chunk apart (CATCHHIP_PREFETCH_DEPTH, 0 = one after the other): a helper thread packs the
         # NEXT chunk's targets, enumerates and de-duplicates its candidates and runs the near-duplicate filter on the
@@ -1370,9 +1239,8 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                     t0 = _time.perf_counter()
                     probes = _probes_of_candidates(cands, anch)
                     ids, nrows = engine.setcover_filter(
-                        ctx, probes, targets, self.mismatches, self.lcf_thres,
-                        self.island_of_exact_match, self.cover_extension, cands.n,
-                        None, universe_p, self.scan_mode, as_array=True)
+                        ctx, probes, targets, num_sets=cands.n, universe_p=universe_p, as_array=True,
+                        **self._model_args())
                     stage_s["solve_s"] += _time.perf_counter() - t0
                     events.append(("solve", chunk_no[id(chunk)], t0 - t_call, _time.perf_counter() - t_call))
                     # candidate-probe x target-bp of the chunk: every cluster's own candidates x its bases
@@ -1422,46 +1290,28 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         choose the same anchor rule and k as the union does, and the union's
         np.random draws are the groups' draws back to back) and no ranks."""
         ctx = engine.default_context()
-        at = 0
-        while at < len(todo):
-            chunk, bases, ncand = [], 0, 0
-            while at < len(todo):
-                gi = todo[at]
-                b = sum(g.size() for g in target_genomes_grouped[gi])
-                if chunk and (bases + b > max_bases or
-                              ncand + len(input_strs[gi]) > max_candidates):
-                    break
-                chunk.append(gi)
-                bases += b
-                ncand += len(input_strs[gi])
-                at += 1
+        packed = _pack_under_cap([sum(g.size() for g in target_genomes_grouped[gi]) for gi in todo], max_bases,
+                                 [len(input_strs[gi]) for gi in todo], max_candidates)
+        for chunk in ([todo[j] for j in part] for part in packed):
             logger.info("Set cover over groups %d..%d of %d as one instance",
                         chunk[0] + 1, chunk[-1] + 1, len(input_strs))
             counts = np.array([len(input_strs[gi]) for gi in chunk], dtype=np.int64)
             offsets = np.concatenate(([0], np.cumsum(counts)))
             strs = [s for gi in chunk for s in input_strs[gi]]
-            k, uniq, owner, ep, eo = probe.anchor_table(
-                strs, self.mismatches, self.lcf_thres,
-                min_k=self.kmer_probe_map_k, k=self.kmer_probe_map_k,
-                assume_unique=True)
-            genomes = [g.seqs for gi in chunk for g in target_genomes_grouped[gi]]
             ngen = [len(target_genomes_grouped[gi]) for gi in chunk]
             universe_p = [p for gi in chunk
                           for p in self._make_universe_p(target_genomes_grouped[gi])]
-            targets = engine.Targets(ctx, genomes)
+            held = []
             try:
-                probes = engine.Probes(ctx, uniq, owner, ep, eo, k)
-                try:
-                    probes.set_groups(np.repeat(np.arange(len(chunk)), counts))
-                    targets.set_groups(np.repeat(np.arange(len(chunk)), ngen))
-                    ids, nrows = engine.setcover_filter(
-                        ctx, probes, targets, self.mismatches, self.lcf_thres,
-                        self.island_of_exact_match, self.cover_extension,
-                        len(strs), None, universe_p, self.scan_mode)
-                finally:
-                    probes.close()
+                targets, probes = self._open_group(
+                    ctx, held, strs, [g for gi in chunk for g in target_genomes_grouped[gi]], assume_unique=True)
+                probes.set_groups(np.repeat(np.arange(len(chunk)), counts))
+                targets.set_groups(np.repeat(np.arange(len(chunk)), ngen))
+                ids, nrows = engine.setcover_filter(ctx, probes, targets, num_sets=len(strs),
+                                                    universe_p=universe_p, **self._model_args())
             finally:
-                targets.close()
+                for h in reversed(held):
+                    h.close()
             ids = np.asarray(ids, dtype=np.int64)
             grp = np.searchsorted(offsets, ids, side="right") - 1
             for j, gi in enumerate(chunk):
@@ -1471,7 +1321,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
 
 def extension_fraction(n2, covered, p):
     """The coverage fraction to ask of a universe of the REDUCED instance
-    (SetCoverFilter._filter_strs_extend): n2 elements are left of a universe of
+    (SetCoverFilter._filter_strs_keeping_rows): n2 elements are left of a universe of
     n2 + covered after the fixed probes took theirs, and of the whole universe
     the fraction p was to be covered.  catch/utils/set_cover.py:366-367 lets
     can = int(|U| - p |U|) elements (IEEE double) stay uncovered; the solver
@@ -1533,7 +1383,7 @@ def curve_checkpoints(n, points, extra=()):
 
 
 class _Budget:
-    """The pick_gains / max_probes part of a _filter_strs_* run over all its
+    """The pick_gains / max_probes part of a _filter_strs_keeping_rows run over all its
     groups: one Rows.pick_gains call per group on the table that went to the
     solver, and with max_probes the cut over all groups once the last one is
     solved -- until then every group's table stays on the device (a second
@@ -1616,21 +1466,73 @@ def _prune(ctx, rows, num_sets, ids, depth, fixed_rows, timings):
     return kept, removed
 
 
+def _solver_fractions(universe_p):
+    """What the solvers take as universe_p: None selects their full-coverage
+    path when every universe is to be covered whole."""
+    return None if all(p == 1.0 for p in universe_p) else universe_p
+
+
+def _warn_less_than_ideal(gi, ranks, ids):
+    """The reference's warning (:176-186) when picks of group `gi` have a rank
+    above the best one."""
+    num_bad = int(np.count_nonzero(ranks[ids] > 0)) if len(ids) else 0
+    if num_bad > 0:
+        logger.warning(("Group %d: forced to choose %d less-than-ideal "
+                        "probe%s (i.e., probes that 'hit' more than "
+                        "one grouping during identification or probes "
+                        "that cover an avoided genome)"), gi + 1,
+                       num_bad, "" if num_bad == 1 else "s")
+
+
+def _pack_under_cap(sizes, cap, counts=None, count_cap=None):
+    """Consecutive items 0 .. len(sizes) - 1 in chunks, each as long as it can
+    be with sum(sizes) <= cap (and, given counts, sum(counts) <= count_cap); an
+    item that alone exceeds a cap is a chunk of its own.  -> [[item]]."""
+    chunks = []
+    for i, size in enumerate(sizes):
+        count = counts[i] if counts is not None else 0
+        if chunks and total + size <= cap and (counts is None or ncount + count <= count_cap):
+            chunks[-1].append(i)
+            total, ncount = total + size, ncount + count
+        else:
+            chunks.append([i])
+            total, ncount = size, count
+    return chunks
+
+
 def _lpt(costs, nbins):
     from catch_amd import parallel
     return parallel.lpt_assign(costs, nbins)
 
 
-def _accumulate(timings, ctx, nrows, npicks):
-    """Adds the device times (HIP events per phase) and work counters of the
-    context's last fused filter call to `timings`."""
-    for name, ph in (("scan_ms", engine.PHASE_SCAN), ("verify_ms", engine.PHASE_VERIFY),
-                     ("rows_ms", engine.PHASE_ROWS), ("greedy_ms", engine.PHASE_GREEDY),
-                     ("rounds_ms", engine.PHASE_GREEDY_ROUNDS), ("claim_ms", engine.PHASE_CLAIM)):
+def _new_timings(**extra):
+    """A fresh last_timings: the keys every path of the filter reports, and
+    those of `extra`."""
+    return dict(scan_ms=0.0, rows_ms=0.0, greedy_ms=0.0, picks=0, rows=0,
+                scan_launches=0, greedy_launches=0, **extra)
+
+
+_SCAN_PHASES = (("scan_ms", engine.PHASE_SCAN), ("verify_ms", engine.PHASE_VERIFY),
+                ("rows_ms", engine.PHASE_ROWS))
+_GREEDY_PHASES = (("greedy_ms", engine.PHASE_GREEDY), ("rounds_ms", engine.PHASE_GREEDY_ROUNDS),
+                  ("claim_ms", engine.PHASE_CLAIM))
+
+
+def _add_phase_times(timings, ctx, phases):
+    """Adds the device time (HIP events) and the launches that the context's
+    last call spent in each (name_ms, phase) to timings[name_ms] and
+    timings[name_launches]."""
+    for name, ph in phases:
         ms, nl = ctx.kernel_ms(ph)
         timings[name] = timings.get(name, 0.0) + ms
         ln = name.replace("_ms", "_launches")
         timings[ln] = timings.get(ln, 0) + nl
+
+
+def _accumulate(timings, ctx, nrows, npicks):
+    """Adds the device times and work counters of the context's last fused
+    filter call to `timings`."""
+    _add_phase_times(timings, ctx, _SCAN_PHASES + _GREEDY_PHASES)
     timings["rows"] = timings.get("rows", 0) + nrows
     timings["picks"] = timings.get("picks", 0) + npicks
     for k, v in ctx.counters().items():
