@@ -118,7 +118,7 @@ template <typename T> struct DevBuf {
 };
 
 enum { PHASE_SCAN = 0, PHASE_ROWS = 1, PHASE_GREEDY = 2, PHASE_NDF = 3, PHASE_GREEDY_ROUNDS = 4, PHASE_VERIFY = 5,
-       PHASE_CLAIM = 6, PHASE_VCOUNT = 7, PHASE_POOL = 8, NPHASE = 9 };
+       PHASE_CLAIM = 6, PHASE_VCOUNT = 7, PHASE_POOL = 8, PHASE_PREFILTER = 9, NPHASE = 10 };
 #define CHIP_EVX 16   // event pairs for per-launch timing inside a batch of solver rounds (PHASE_CLAIM)
 
 struct catchhip_ctx {
@@ -330,7 +330,7 @@ static inline int chip_rows_new(catchhip_ctx *ctx, i64 total, i32 ngenomes, cons
     return 0;
 }
 
-// unique candidate probes of a targets object (candidates.hip; the poly(A) pre-filter of prefilter.hip edits the list)
+// unique candidate probes of a targets object (candidates.hip; the pre-filters of prefilter.hip edit the list)
 struct catchhip_candidates {
     catchhip_ctx *ctx = nullptr;
     const catchhip_targets *T = nullptr;   // borrowed: must outlive this object

@@ -21,7 +21,10 @@ greedy layer per unit of depth; --prune-redundant (nor this) drops the selected
 probes that cover nothing alone; --max-probes N (nor this) keeps, over all
 datasets, the N set cover picks that added the most coverage when they were
 taken, and --write-coverage-curve writes how coverage grows with the number
-of probes.  --print-analysis and the
+of probes; --filter-gc, --max-homopolymer and --filter-low-complexity (nor
+these) drop candidates by their composition, one filter right after the
+poly(A) filter (catch_amd/filter/composition_filter.py has the rules).
+--print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
 """
@@ -31,6 +34,7 @@ import os
 import random
 import sys
 
+from catch_amd.filter import composition_filter
 from catch_amd.filter import duplicate_filter, near_duplicate_filter
 from catch_amd.filter import probe_designer, set_cover_filter
 from catch_amd.utils import seq_io
@@ -120,6 +124,7 @@ def parse_args(argv=None, args_type="basic"):
     p.add_argument("--filter-polya", nargs=2, type=int,
                    help="<X> <Y>: drop candidate probes with a stretch of X or "
                         "more 'A' bases, tolerating up to Y mismatches (likewise 'T')")
+    composition_filter.add_arguments(p)     # --filter-gc, --max-homopolymer, --filter-low-complexity (not in the reference)
     p.add_argument("--add-reverse-complements", dest="add_reverse_complements",
                    action="store_true",
                    help="add the reverse complement of each probe to the output")
@@ -191,6 +196,7 @@ def parse_args(argv=None, args_type="basic"):
     p.add_argument("--verbose", action="store_true")
     args = p.parse_args(argv)
     args.args_type = args_type
+    composition_filter.from_args(args, p.error)     # (bad values are argparse errors; main builds the filter)
     return args
 
 
@@ -405,6 +411,9 @@ def main(args):
                             "lead to many probes being filtered"),
                            polya_mismatches)
         filters.append(polya_filter.PolyAFilter(polya_length, polya_mismatches))
+    composition = composition_filter.from_args(args)
+    if composition is not None:     # one filter for the three rules: a function of the candidate alone, like poly(A)
+        filters.append(composition)
     if (args.filter_with_lsh_hamming is not None and
             args.filter_with_lsh_minhash is not None):
         raise Exception("Cannot use both --filter-with-lsh-hamming "
@@ -475,6 +484,9 @@ def main(args):
                                  if args.cluster_and_design_separately
                                  else None))
     pb.design()
+    if composition is not None:
+        logger.info("composition filter: %d candidates dropped (GC %d, homopolymer %d, low complexity %d)",
+                    composition.dropped[3], *composition.dropped[:3])
     if args.coverage_depth > 1:
         for fn, sizes in zip(args.dataset, scf.last_layer_sizes):
             logger.info("%s: %s probes in the layers of depth 1 to %d",

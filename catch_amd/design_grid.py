@@ -18,6 +18,7 @@ import os
 import sys
 
 from catch_amd import grid
+from catch_amd.filter import composition_filter
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.design_grid")
@@ -81,6 +82,7 @@ def parse_args(argv=None):
     p.add_argument("--filter-polya", nargs=2, type=int,
                    help="<X> <Y>: drop candidate probes with a stretch of X or "
                         "more 'A' bases, tolerating up to Y mismatches (likewise 'T')")
+    composition_filter.add_arguments(p)     # as catch_amd.design's
     p.add_argument("--small-seq-skip", type=int)
     p.add_argument("--small-seq-min", type=int)
     p.add_argument("--kmer-probe-map-k", type=int)
@@ -113,6 +115,7 @@ def parse_args(argv=None):
     p.add_argument("-e", "--cover-extension", type=int, help=S)
     args = p.parse_args(argv)
     check_args(args, p.error)
+    composition_filter.from_args(args, p.error)     # (bad values are argparse errors; main builds the filter)
     return args
 
 
@@ -150,6 +153,7 @@ def main(args):
         format="%(asctime)s - %(name)s [%(levelname)s] %(message)s")
     from catch_amd import probe
     datasets = [seq_io.read_genomes_from_fasta(fn) for fn in args.dataset]
+    composition = composition_filter.from_args(args)
     got = grid.design_grid(
         datasets, args.grid_mismatches, args.grid_cover_extension,
         probe_length=args.probe_length, probe_stride=args.probe_stride,
@@ -157,7 +161,11 @@ def main(args):
         coverage=args.coverage, filter_with_lsh_hamming=args.filter_with_lsh_hamming,
         filter_with_lsh_minhash=args.filter_with_lsh_minhash,
         small_seq_skip=args.small_seq_skip, small_seq_min=args.small_seq_min,
-        kmer_probe_map_k=args.kmer_probe_map_k, filter_polya=args.filter_polya)
+        kmer_probe_map_k=args.kmer_probe_map_k, filter_polya=args.filter_polya,
+        filter_composition=composition)
+    if composition is not None:
+        logger.info("composition filter: %d candidates dropped (GC %d, homopolymer %d, low complexity %d)",
+                    composition.dropped[3], *composition.dropped[:3])
     os.makedirs(args.output_dir, exist_ok=True)
     counts = []
     for di, name in enumerate(args.names):

@@ -633,6 +633,21 @@ class Candidates:
             ctypes.byref(nk)))
         self.n = nk.value
 
+    def drop_composition(self, gc_lo=-1, gc_hi=-1, max_run=-1, dust_x10=-1, dust_window=64):
+        """catchhip_candidates_drop_composition (not in the reference): the
+        unique candidates without those a composition rule drops (GC count
+        outside gc_lo..gc_hi, a homopolymer run above max_run, a window of
+        dust_window bytes scoring above dust_x10; -1: rule off), order,
+        multiplicities and groups kept.  Returns the candidates dropped, with
+        multiplicity: [GC, homopolymer, low complexity, any rule]."""
+        nk = ctypes.c_int64(0)
+        dropped = np.zeros(4, dtype=np.int64)
+        check(self.ctx._L.catchhip_candidates_drop_composition(
+            self.ctx._h, self._h, int(gc_lo), int(gc_hi), int(max_run), int(dust_x10),
+            int(dust_window), _ptr(dropped, c_i64p), ctypes.byref(nk)))
+        self.n = nk.value
+        return [int(x) for x in dropped]
+
     def multiplicities(self):
         """How many candidates equal every unique one (before a near-duplicate filter)."""
         out = np.zeros(max(self.n, 1), dtype=np.uint32)

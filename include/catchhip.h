@@ -85,7 +85,9 @@ int catchhip_pool_trim(void);
  * 0 launches when the last solve used the other kernels), 7 = only the
  * counting pass of the key-grouped join (part of phase 0; 5 is its writing
  * pass), 8 = the launches of
- * catchhip_pool_solve (one per dataset + the walk back).
+ * catchhip_pool_solve (one per dataset + the walk back), 9 = the flag kernel of
+ * the last candidate pre-filter (catchhip_candidates_drop_polya or
+ * catchhip_candidates_drop_composition; the compaction after it is not in it).
  * *launches = kernel launches timed. */
 int catchhip_ctx_last_kernel_ms(catchhip_ctx *ctx, int phase, double *ms,
                                 int64_t *launches);
@@ -973,6 +975,26 @@ int catchhip_candidates_groups(catchhip_ctx *ctx, const catchhip_candidates *can
 int catchhip_candidates_drop_polya(catchhip_ctx *ctx, catchhip_candidates *cands,
                                    int32_t length, int32_t mismatches,
                                    int32_t min_exact, int64_t *nkept);
+/* NOT IN THE REFERENCE (catch_amd/filter/composition_filter.py states the rules and
+ * is their oracle): unique candidates that fail a composition rule are dropped, as
+ * catchhip_candidates_drop_polya drops its own -- order, multiplicities and groups
+ * kept, before any near-duplicate filter (EINVAL after one), 0 candidates valid.
+ * Only the bytes 'A', 'C', 'G', 'T' are bases; L = probe_length.
+ *   GC: kept iff gc_lo <= number of 'G' or 'C' <= gc_hi (gc_lo = -1: no lower bound,
+ *       gc_hi = -1: no upper bound; gc_lo <= 0 with gc_hi >= L is "off" as well).
+ *   homopolymer: kept iff the longest run of one base is <= max_run (>= 1; -1: off).
+ *   low complexity: with We = min(dust_window, L), dropped iff for some window start
+ *       i in 0 .. L - We the triplets j in i .. i + We - 3 whose three bytes are all
+ *       bases -- T of them, c_t with code t -- have T >= 2 and
+ *       10 * sum_t c_t (c_t - 1) / 2 > dust_x10 * (T - 1)  (dust_x10 >= 0; -1: off;
+ *       3 <= dust_window <= 256, read only when the rule is on).
+ * dropped (4 words, may be NULL) receives the candidates each rule dropped, counted
+ * WITH multiplicity: [0] GC, [1] homopolymer, [2] low complexity, [3] any rule (a
+ * candidate that fails two rules counts for both and once in [3]). */
+int catchhip_candidates_drop_composition(catchhip_ctx *ctx, catchhip_candidates *cands,
+                                         int32_t gc_lo, int32_t gc_hi, int32_t max_run,
+                                         int32_t dust_x10, int32_t dust_window,
+                                         int64_t dropped[4], int64_t *nkept);
 /* multiplicity[i] = how many candidates equal unique candidate i (the priority of
  * near_duplicate_filter.py:60-66); EINVAL once a catchhip_candidates_ndf_* call ran */
 int catchhip_candidates_multiplicities(catchhip_ctx *ctx, const catchhip_candidates *cands,
