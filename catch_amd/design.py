@@ -23,7 +23,10 @@ datasets, the N set cover picks that added the most coverage when they were
 taken, and --write-coverage-curve writes how coverage grows with the number
 of probes; --filter-gc, --max-homopolymer and --filter-low-complexity (nor
 these) drop candidates by their composition, one filter right after the
-poly(A) filter (catch_amd/filter/composition_filter.py has the rules).
+poly(A) filter (catch_amd/filter/composition_filter.py has the rules);
+--max-hairpin-stem (with --hairpin-min-loop) and --max-self-dimer (nor these)
+drop candidates that fold on themselves or bind a second copy, one filter
+right after that one (catch_amd/filter/structure_filter.py has the rules).
 --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
@@ -37,6 +40,7 @@ import sys
 from catch_amd.filter import composition_filter
 from catch_amd.filter import duplicate_filter, near_duplicate_filter
 from catch_amd.filter import probe_designer, set_cover_filter
+from catch_amd.filter import structure_filter
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.design")
@@ -125,6 +129,7 @@ def parse_args(argv=None, args_type="basic"):
                    help="<X> <Y>: drop candidate probes with a stretch of X or "
                         "more 'A' bases, tolerating up to Y mismatches (likewise 'T')")
     composition_filter.add_arguments(p)     # --filter-gc, --max-homopolymer, --filter-low-complexity (not in the reference)
+    structure_filter.add_arguments(p)       # --max-hairpin-stem, --hairpin-min-loop, --max-self-dimer (not in the reference)
     p.add_argument("--add-reverse-complements", dest="add_reverse_complements",
                    action="store_true",
                    help="add the reverse complement of each probe to the output")
@@ -197,6 +202,7 @@ def parse_args(argv=None, args_type="basic"):
     args = p.parse_args(argv)
     args.args_type = args_type
     composition_filter.from_args(args, p.error)     # (bad values are argparse errors; main builds the filter)
+    structure_filter.from_args(args, p.error)
     return args
 
 
@@ -414,6 +420,9 @@ def main(args):
     composition = composition_filter.from_args(args)
     if composition is not None:     # one filter for the three rules: a function of the candidate alone, like poly(A)
         filters.append(composition)
+    structure = structure_filter.from_args(args)
+    if structure is not None:       # one filter for both rules, likewise a function of the candidate alone
+        filters.append(structure)
     if (args.filter_with_lsh_hamming is not None and
             args.filter_with_lsh_minhash is not None):
         raise Exception("Cannot use both --filter-with-lsh-hamming "
@@ -487,6 +496,9 @@ def main(args):
     if composition is not None:
         logger.info("composition filter: %d candidates dropped (GC %d, homopolymer %d, low complexity %d)",
                     composition.dropped[3], *composition.dropped[:3])
+    if structure is not None:
+        logger.info("structure filter: %d candidates dropped (hairpin %d, self-dimer %d)",
+                    structure.dropped[2], *structure.dropped[:2])
     if args.coverage_depth > 1:
         for fn, sizes in zip(args.dataset, scf.last_layer_sizes):
             logger.info("%s: %s probes in the layers of depth 1 to %d",

@@ -18,7 +18,7 @@ import os
 import sys
 
 from catch_amd import grid
-from catch_amd.filter import composition_filter
+from catch_amd.filter import composition_filter, structure_filter
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.design_grid")
@@ -83,6 +83,7 @@ def parse_args(argv=None):
                    help="<X> <Y>: drop candidate probes with a stretch of X or "
                         "more 'A' bases, tolerating up to Y mismatches (likewise 'T')")
     composition_filter.add_arguments(p)     # as catch_amd.design's
+    structure_filter.add_arguments(p)       # likewise
     p.add_argument("--small-seq-skip", type=int)
     p.add_argument("--small-seq-min", type=int)
     p.add_argument("--kmer-probe-map-k", type=int)
@@ -116,6 +117,7 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     check_args(args, p.error)
     composition_filter.from_args(args, p.error)     # (bad values are argparse errors; main builds the filter)
+    structure_filter.from_args(args, p.error)
     return args
 
 
@@ -154,6 +156,7 @@ def main(args):
     from catch_amd import probe
     datasets = [seq_io.read_genomes_from_fasta(fn) for fn in args.dataset]
     composition = composition_filter.from_args(args)
+    structure = structure_filter.from_args(args)
     got = grid.design_grid(
         datasets, args.grid_mismatches, args.grid_cover_extension,
         probe_length=args.probe_length, probe_stride=args.probe_stride,
@@ -162,10 +165,13 @@ def main(args):
         filter_with_lsh_minhash=args.filter_with_lsh_minhash,
         small_seq_skip=args.small_seq_skip, small_seq_min=args.small_seq_min,
         kmer_probe_map_k=args.kmer_probe_map_k, filter_polya=args.filter_polya,
-        filter_composition=composition)
+        filter_composition=composition, filter_structure=structure)
     if composition is not None:
         logger.info("composition filter: %d candidates dropped (GC %d, homopolymer %d, low complexity %d)",
                     composition.dropped[3], *composition.dropped[:3])
+    if structure is not None:
+        logger.info("structure filter: %d candidates dropped (hairpin %d, self-dimer %d)",
+                    structure.dropped[2], *structure.dropped[:2])
     os.makedirs(args.output_dir, exist_ok=True)
     counts = []
     for di, name in enumerate(args.names):

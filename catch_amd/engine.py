@@ -648,6 +648,22 @@ class Candidates:
         self.n = nk.value
         return [int(x) for x in dropped]
 
+    def drop_structure(self, max_stem=-1, min_loop=3, max_dimer=-1):
+        """catchhip_candidates_drop_structure (not in the reference): the
+        unique candidates without those a secondary-structure rule drops (a
+        hairpin stem of more than max_stem base pairs around a loop of at
+        least min_loop characters, a self-dimer of more than max_dimer
+        consecutive base pairs; -1: rule off), order, multiplicities and groups
+        kept.  Returns the candidates dropped, with multiplicity: [hairpin,
+        self-dimer, any rule]."""
+        nk = ctypes.c_int64(0)
+        dropped = np.zeros(3, dtype=np.int64)
+        check(self.ctx._L.catchhip_candidates_drop_structure(
+            self.ctx._h, self._h, int(max_stem), int(min_loop), int(max_dimer),
+            _ptr(dropped, c_i64p), ctypes.byref(nk)))
+        self.n = nk.value
+        return [int(x) for x in dropped]
+
     def multiplicities(self):
         """How many candidates equal every unique one (before a near-duplicate filter)."""
         out = np.zeros(max(self.n, 1), dtype=np.uint32)

@@ -132,7 +132,7 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
                 filter_with_lsh_minhash=None, small_seq_skip=None,
                 small_seq_min=None, kmer_probe_map_k=None,
                 scan_mode=engine.SCAN_AUTO, stats=None, filter_polya=None,
-                filter_composition=None):
+                filter_composition=None, filter_structure=None):
     """Probes for every (dataset, m, e) point.
 
     datasets: list of datasets, each a list of Genome objects (one FASTA file =
@@ -142,7 +142,8 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
     so it is part of the front end every grid point shares;
     filter_composition: a composition_filter.CompositionFilter, applied right
     after it in the same way, its `dropped` counts summed over the
-    datasets).  Returns {(dataset index, m, e): probe
+    datasets; filter_structure: a structure_filter.StructureFilter, after
+    that one, likewise).  Returns {(dataset index, m, e): probe
     sequences in the order the set cover picked them}.  stats (a dict, may be
     None) receives the number of grid calls (scans of a (dataset, m)), derived
     row tables and solves."""
@@ -202,6 +203,8 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
         pre_filters.append(polya_filter.PolyAFilter(polya_length, polya_mismatches))
     if filter_composition is not None:
         pre_filters.append(filter_composition)
+    if filter_structure is not None:
+        pre_filters.append(filter_structure)
 
     np_state0, py_state0 = np.random.get_state(), random.getstate()
     out = {}

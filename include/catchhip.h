@@ -86,8 +86,9 @@ int catchhip_pool_trim(void);
  * counting pass of the key-grouped join (part of phase 0; 5 is its writing
  * pass), 8 = the launches of
  * catchhip_pool_solve (one per dataset + the walk back), 9 = the flag kernel of
- * the last candidate pre-filter (catchhip_candidates_drop_polya or
- * catchhip_candidates_drop_composition; the compaction after it is not in it).
+ * the last candidate pre-filter (catchhip_candidates_drop_polya,
+ * catchhip_candidates_drop_composition or catchhip_candidates_drop_structure; the
+ * compaction after it is not in it).
  * *launches = kernel launches timed. */
 int catchhip_ctx_last_kernel_ms(catchhip_ctx *ctx, int phase, double *ms,
                                 int64_t *launches);
@@ -995,6 +996,25 @@ int catchhip_candidates_drop_composition(catchhip_ctx *ctx, catchhip_candidates 
                                          int32_t gc_lo, int32_t gc_hi, int32_t max_run,
                                          int32_t dust_x10, int32_t dust_window,
                                          int64_t dropped[4], int64_t *nkept);
+/* NOT IN THE REFERENCE (catch_amd/filter/structure_filter.py states the rules and is
+ * their oracle): unique candidates that fail a secondary-structure rule are dropped,
+ * as catchhip_candidates_drop_composition drops its own -- order, multiplicities and
+ * groups kept, before any near-duplicate filter (EINVAL after one), 0 candidates
+ * valid.  Only the bytes 'A', 'C', 'G', 'T' are bases; pairs(x, y) iff both are bases
+ * and complementary (A-T, C-G); L = probe_length.
+ *   hairpin: dropped iff there are i < j with pairs(i + t, j - t) for t = 0 .. max_stem
+ *       and (j - max_stem) - (i + max_stem) - 1 >= min_loop  (max_stem >= 1; -1: off;
+ *       min_loop >= 0, read only when the rule is on).
+ *   self-dimer: dropped iff there are a, b with 0 <= a, a + max_dimer <= L - 1,
+ *       b - max_dimer >= 0, b <= L - 1 and pairs(a + t, b - t) for t = 0 .. max_dimer
+ *       (max_dimer >= 1; -1: off).
+ * dropped (3 words, may be NULL) receives the candidates each rule dropped, counted
+ * WITH multiplicity: [0] hairpin, [1] self-dimer, [2] any rule (a candidate that fails
+ * both counts for both and once in [2]).  The flag kernel is phase 9 of
+ * catchhip_ctx_last_kernel_ms. */
+int catchhip_candidates_drop_structure(catchhip_ctx *ctx, catchhip_candidates *cands,
+                                       int32_t max_stem, int32_t min_loop, int32_t max_dimer,
+                                       int64_t dropped[3], int64_t *nkept);
 /* multiplicity[i] = how many candidates equal unique candidate i (the priority of
  * near_duplicate_filter.py:60-66); EINVAL once a catchhip_candidates_ndf_* call ran */
 int catchhip_candidates_multiplicities(catchhip_ctx *ctx, const catchhip_candidates *cands,
