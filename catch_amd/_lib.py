@@ -225,6 +225,9 @@ PROTOTYPES = {
         ctypes.c_int32, c_i64p, c_i64p]),
     "catchhip_candidates_drop_structure": (ctypes.c_int, [
         c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_i64p, c_i64p]),
+    "catchhip_candidates_drop_tm": (ctypes.c_int, [
+        c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+        ctypes.c_int32, c_i64p, c_u64p, c_i64p]),
     "catchhip_candidates_multiplicities": (ctypes.c_int, [c_vp, c_vp, c_u32p]),
     "catchhip_probes_from_candidates": (ctypes.c_int, [
         c_vp, c_vp, c_i32p, c_i32p, ctypes.c_int64, ctypes.c_int32, c_vpp]),

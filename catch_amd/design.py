@@ -26,7 +26,11 @@ these) drop candidates by their composition, one filter right after the
 poly(A) filter (catch_amd/filter/composition_filter.py has the rules);
 --max-hairpin-stem (with --hairpin-min-loop) and --max-self-dimer (nor these)
 drop candidates that fold on themselves or bind a second copy, one filter
-right after that one (catch_amd/filter/structure_filter.py has the rules).
+right after that one (catch_amd/filter/structure_filter.py has the rules);
+--filter-tm (with --tm-sodium, --tm-oligo, --tm-formamide; nor these) drops
+candidates by their nearest-neighbour melting temperature and
+--write-tm-histogram writes its distribution, one filter right after that one
+(catch_amd/filter/tm_filter.py has the rule).
 --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
@@ -40,7 +44,7 @@ import sys
 from catch_amd.filter import composition_filter
 from catch_amd.filter import duplicate_filter, near_duplicate_filter
 from catch_amd.filter import probe_designer, set_cover_filter
-from catch_amd.filter import structure_filter
+from catch_amd.filter import structure_filter, tm_filter
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.design")
@@ -130,6 +134,7 @@ def parse_args(argv=None, args_type="basic"):
                         "more 'A' bases, tolerating up to Y mismatches (likewise 'T')")
     composition_filter.add_arguments(p)     # --filter-gc, --max-homopolymer, --filter-low-complexity (not in the reference)
     structure_filter.add_arguments(p)       # --max-hairpin-stem, --hairpin-min-loop, --max-self-dimer (not in the reference)
+    tm_filter.add_arguments(p)              # --filter-tm, --tm-..., --write-tm-histogram (not in the reference)
     p.add_argument("--add-reverse-complements", dest="add_reverse_complements",
                    action="store_true",
                    help="add the reverse complement of each probe to the output")
@@ -203,6 +208,7 @@ def parse_args(argv=None, args_type="basic"):
     args.args_type = args_type
     composition_filter.from_args(args, p.error)     # (bad values are argparse errors; main builds the filter)
     structure_filter.from_args(args, p.error)
+    tm_filter.from_args(args, p.error)
     return args
 
 
@@ -423,6 +429,9 @@ def main(args):
     structure = structure_filter.from_args(args)
     if structure is not None:       # one filter for both rules, likewise a function of the candidate alone
         filters.append(structure)
+    tm = tm_filter.from_args(args)
+    if tm is not None:              # melting temperature: a filter, a measurement (--write-tm-histogram), or both
+        filters.append(tm)
     if (args.filter_with_lsh_hamming is not None and
             args.filter_with_lsh_minhash is not None):
         raise Exception("Cannot use both --filter-with-lsh-hamming "
@@ -499,6 +508,10 @@ def main(args):
     if structure is not None:
         logger.info("structure filter: %d candidates dropped (hairpin %d, self-dimer %d)",
                     structure.dropped[2], *structure.dropped[:2])
+    if tm is not None:
+        logger.info("tm filter: %d candidates dropped (below %d, above %d)", tm.dropped[2], *tm.dropped[:2])
+        if args.write_tm_histogram:
+            tm.write_histogram(args.write_tm_histogram)
     if args.coverage_depth > 1:
         for fn, sizes in zip(args.dataset, scf.last_layer_sizes):
             logger.info("%s: %s probes in the layers of depth 1 to %d",

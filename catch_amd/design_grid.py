@@ -18,7 +18,7 @@ import os
 import sys
 
 from catch_amd import grid
-from catch_amd.filter import composition_filter, structure_filter
+from catch_amd.filter import composition_filter, structure_filter, tm_filter
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.design_grid")
@@ -84,6 +84,7 @@ def parse_args(argv=None):
                         "more 'A' bases, tolerating up to Y mismatches (likewise 'T')")
     composition_filter.add_arguments(p)     # as catch_amd.design's
     structure_filter.add_arguments(p)       # likewise
+    tm_filter.add_arguments(p)              # likewise
     p.add_argument("--small-seq-skip", type=int)
     p.add_argument("--small-seq-min", type=int)
     p.add_argument("--kmer-probe-map-k", type=int)
@@ -118,6 +119,7 @@ def parse_args(argv=None):
     check_args(args, p.error)
     composition_filter.from_args(args, p.error)     # (bad values are argparse errors; main builds the filter)
     structure_filter.from_args(args, p.error)
+    tm_filter.from_args(args, p.error)
     return args
 
 
@@ -157,6 +159,7 @@ def main(args):
     datasets = [seq_io.read_genomes_from_fasta(fn) for fn in args.dataset]
     composition = composition_filter.from_args(args)
     structure = structure_filter.from_args(args)
+    tm = tm_filter.from_args(args)
     got = grid.design_grid(
         datasets, args.grid_mismatches, args.grid_cover_extension,
         probe_length=args.probe_length, probe_stride=args.probe_stride,
@@ -165,13 +168,18 @@ def main(args):
         filter_with_lsh_minhash=args.filter_with_lsh_minhash,
         small_seq_skip=args.small_seq_skip, small_seq_min=args.small_seq_min,
         kmer_probe_map_k=args.kmer_probe_map_k, filter_polya=args.filter_polya,
-        filter_composition=composition, filter_structure=structure)
+        filter_composition=composition, filter_structure=structure,
+        filter_tm=tm)
     if composition is not None:
         logger.info("composition filter: %d candidates dropped (GC %d, homopolymer %d, low complexity %d)",
                     composition.dropped[3], *composition.dropped[:3])
     if structure is not None:
         logger.info("structure filter: %d candidates dropped (hairpin %d, self-dimer %d)",
                     structure.dropped[2], *structure.dropped[:2])
+    if tm is not None:
+        logger.info("tm filter: %d candidates dropped (below %d, above %d)", tm.dropped[2], *tm.dropped[:2])
+        if args.write_tm_histogram:
+            tm.write_histogram(args.write_tm_histogram)
     os.makedirs(args.output_dir, exist_ok=True)
     counts = []
     for di, name in enumerate(args.names):

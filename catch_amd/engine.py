@@ -664,6 +664,27 @@ class Candidates:
         self.n = nk.value
         return [int(x) for x in dropped]
 
+    def drop_tm(self, q, offset_c, lo_c=None, hi_c=None, histogram=True):
+        """catchhip_candidates_drop_tm (not in the reference): the nearest-
+        neighbour melting temperature tm_c of every unique candidate
+        (catch_amd/filter/tm_filter.py has the rule; q = Q(L), offset_c =
+        27315 + f).  With lo_c and hi_c the candidates outside lo_c..hi_c are
+        dropped, order, multiplicities and groups kept; without them the list
+        is untouched.  Returns ([below, above, any] dropped, with multiplicity,
+        the 128 bins of whole degrees over the candidates the call saw, with
+        multiplicity -- None if histogram is false)."""
+        if (lo_c is None) != (hi_c is None):
+            raise ValueError("drop_tm: lo_c and hi_c go together")
+        nk = ctypes.c_int64(0)
+        dropped = np.zeros(3, dtype=np.int64)
+        hist = np.zeros(128, dtype=np.uint64) if histogram else None
+        check(self.ctx._L.catchhip_candidates_drop_tm(
+            self.ctx._h, self._h, int(q), int(offset_c), 0 if lo_c is None else 1,
+            0 if lo_c is None else int(lo_c), 0 if hi_c is None else int(hi_c),
+            _ptr(dropped, c_i64p), None if hist is None else _ptr(hist, c_u64p), ctypes.byref(nk)))
+        self.n = nk.value
+        return [int(x) for x in dropped], None if hist is None else [int(x) for x in hist]
+
     def multiplicities(self):
         """How many candidates equal every unique one (before a near-duplicate filter)."""
         out = np.zeros(max(self.n, 1), dtype=np.uint32)

@@ -20,6 +20,7 @@ from catch_amd.filter.near_duplicate_filter import (
 from catch_amd.filter.polya_filter import PolyAFilter
 from catch_amd.filter.set_cover_filter import SetCoverFilter
 from catch_amd.filter.structure_filter import StructureFilter
+from catch_amd.filter.tm_filter import TmFilter
 from catch_amd.utils import cluster
 
 logger = logging.getLogger(__name__)
@@ -213,8 +214,8 @@ class ProbeDesigner:
     def _design_on_strings(self, genomes, filters):
         """[pre-filters ..., DuplicateFilter | near-duplicate filter,
         SetCoverFilter] -- the filter lists bin/design.py:255-340 builds, the
-        pre-filters being FastaFilter, PolyAFilter, CompositionFilter and
-        StructureFilter -- on plain strings:
+        pre-filters being FastaFilter, PolyAFilter, CompositionFilter,
+        StructureFilter and TmFilter -- on plain strings:
         candidates are sliced, filtered, de-duplicated (dict, or the LSH filter
         on the device) and handed to the set cover filter without a Probe object
         per candidate (a design over 8,000 genomes spent 0.85 of its 1.0 s
@@ -258,15 +259,15 @@ class ProbeDesigner:
         """Candidates and the duplicate (or near-duplicate) filter on the device:
         one of the usual filter pairs without ranks, no --small-seq-min, every
         sequence a str at least a probe long (or skipped), and no pre-filter but
-        the poly(A), composition and structure filters (a kernel each; the FASTA
-        filter is a look-up on the host).
+        the poly(A), composition, structure and Tm filters (a kernel each; the
+        FASTA filter is a look-up on the host).
         "per group": few or large groups, each its own instance; "union": many
         small groups (clusters) as one instance with group numbers; None: host
         front end."""
         import os
         if os.environ.get("CATCHHIP_HOST_FRONT_END"):
             return None
-        if any(type(f) not in (PolyAFilter, CompositionFilter, StructureFilter) for f in pre_filters):
+        if any(type(f) not in (PolyAFilter, CompositionFilter, StructureFilter, TmFilter) for f in pre_filters):
             return None
         if self.allow_small_seqs:
             return None
@@ -326,11 +327,11 @@ class ProbeDesigner:
     @staticmethod
     def _strings_prefix(filters):
         """Length of the leading [FastaFilter | PolyAFilter | CompositionFilter |
-        StructureFilter ..., DuplicateFilter | near-duplicate filter,
+        StructureFilter | TmFilter ..., DuplicateFilter | near-duplicate filter,
         SetCoverFilter] the strings path runs; 0: none."""
         n = 0
         while n < len(filters) and type(filters[n]) in (
-                FastaFilter, PolyAFilter, CompositionFilter, StructureFilter):
+                FastaFilter, PolyAFilter, CompositionFilter, StructureFilter, TmFilter):
             n += 1
         if (len(filters) >= n + 2 and type(filters[n]) in (
                 DuplicateFilter, NearDuplicateFilterWithHammingDistance,

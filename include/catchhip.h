@@ -87,8 +87,8 @@ int catchhip_pool_trim(void);
  * pass), 8 = the launches of
  * catchhip_pool_solve (one per dataset + the walk back), 9 = the flag kernel of
  * the last candidate pre-filter (catchhip_candidates_drop_polya,
- * catchhip_candidates_drop_composition or catchhip_candidates_drop_structure; the
- * compaction after it is not in it).
+ * catchhip_candidates_drop_composition, catchhip_candidates_drop_structure or
+ * catchhip_candidates_drop_tm; the compaction after it is not in it).
  * *launches = kernel launches timed. */
 int catchhip_ctx_last_kernel_ms(catchhip_ctx *ctx, int phase, double *ms,
                                 int64_t *launches);
@@ -1015,6 +1015,31 @@ int catchhip_candidates_drop_composition(catchhip_ctx *ctx, catchhip_candidates 
 int catchhip_candidates_drop_structure(catchhip_ctx *ctx, catchhip_candidates *cands,
                                        int32_t max_stem, int32_t min_loop, int32_t max_dimer,
                                        int64_t dropped[3], int64_t *nkept);
+/* NOT IN THE REFERENCE (catch_amd/filter/tm_filter.py states the rule and is its
+ * oracle): the nearest-neighbour melting temperature of every unique candidate, as a
+ * filter and as a histogram.  With H and E the sums of the unified parameters of
+ * SantaLucia 1998 over the candidate's dinucleotides and its two terminal characters
+ * (h in 100 cal/mol, e in 0.1 cal/(K mol); only 'A', 'C', 'G', 'T' are bases, a
+ * dinucleotide with another byte adds nothing),
+ *     E' = 100 E + q,  T = H < 0 ? floor(10^7 (-H) / (-E')) : 0,  tm_c = T - offset_c
+ * in 64-bit integers: q = Q(probe_length), the salt and concentration term the caller
+ * computes once, q <= -8200 (EINVAL otherwise); offset_c = 27315 + f, f the formamide
+ * correction; tm_c is in hundredths of a degree Celsius.
+ *   filter_on != 0: candidates with tm_c < lo_c or tm_c > hi_c are dropped (EINVAL if
+ *       lo_c > hi_c), as catchhip_candidates_drop_composition drops its own -- order,
+ *       multiplicities and groups kept, before any near-duplicate filter (EINVAL after
+ *       one), 0 candidates valid; nothing dropped: the list stands as it is.
+ *   filter_on == 0: the list is untouched; lo_c and hi_c are not read.
+ * dropped (3 words, may be NULL) receives the candidates dropped, counted WITH
+ * multiplicity: [0] below lo_c, [1] above hi_c, [2] both together.  hist (128 words,
+ * may be NULL) receives the candidates the call saw, before it dropped any, WITH
+ * multiplicity, per whole degree: bin min(max(floor(tm_c / 100), 0), 127).
+ * probe_length < 2: nothing is dropped and nothing counted.  The flag kernel is phase 9
+ * of catchhip_ctx_last_kernel_ms. */
+int catchhip_candidates_drop_tm(catchhip_ctx *ctx, catchhip_candidates *cands, int64_t q,
+                                int32_t offset_c, int32_t filter_on, int32_t lo_c,
+                                int32_t hi_c, int64_t dropped[3], uint64_t hist[128],
+                                int64_t *nkept);
 /* multiplicity[i] = how many candidates equal unique candidate i (the priority of
  * near_duplicate_filter.py:60-66); EINVAL once a catchhip_candidates_ndf_* call ran */
 int catchhip_candidates_multiplicities(catchhip_ctx *ctx, const catchhip_candidates *cands,
