@@ -48,6 +48,7 @@ PROTOTYPES = {
     "catchhip_ctx_last_seeds_dropped": (ctypes.c_int, [c_vp, c_i64p]),
     "catchhip_ctx_last_rows_direct": (ctypes.c_int, [c_vp, c_i64p]),
     "catchhip_ctx_last_join_counters": (ctypes.c_int, [c_vp, c_i64p]),
+    "catchhip_ctx_last_capacity_events": (ctypes.c_int, [c_vp, c_i64p]),
     "catchhip_ctx_last_solver_counters": (ctypes.c_int, [c_vp, c_i64p]),
     "catchhip_ctx_last_solver_levels": (ctypes.c_int, [c_vp, c_i64p]),
     "catchhip_ctx_last_solver_band_groups": (ctypes.c_int, [c_vp, c_i64p]),

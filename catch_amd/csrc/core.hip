@@ -337,6 +337,12 @@ extern "C" int catchhip_ctx_last_join_counters(catchhip_ctx *c, i64 *out4) {
     return 0;
 }
 
+extern "C" int catchhip_ctx_last_capacity_events(catchhip_ctx *c, i64 *out8) {
+    ARG_CHECK(c != nullptr && out8 != nullptr);
+    for (int i = 0; i < NCAPEV; ++i) out8[i] = c->capacity_events[i];
+    return 0;
+}
+
 extern "C" int catchhip_ctx_last_rows_direct(catchhip_ctx *c, i64 *out) {
     ARG_CHECK(c != nullptr && out != nullptr);
     *out = c->rows_direct;

@@ -30,6 +30,7 @@ extern "C" int catchhip_setcover_filter(catchhip_ctx *ctx, const catchhip_probes
         for (i32 u = 0; u < T->ngenomes && full; ++u) full = universe_p[u] == 1.0;
     const auto t_in = std::chrono::steady_clock::now();
     ctx->rows_direct = 0;
+    chip_capacity_events_reset(ctx);
     // (tests: small instances through the synchronous branch below)
     if (full && chip_test_env("CATCHHIP_FILTER_NO_DEFER")) full = false;
     if (full) {

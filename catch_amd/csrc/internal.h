@@ -137,6 +137,9 @@ struct catchhip_ctx {
     i64 seeds_dropped = 0;   // of counters[1]: work-list entries the seed look-up's anchor-pair filter left empty
     i64 join_counters[4] = {};     // last key-grouped join: hit positions, pairs verified, lane slots of wave-wide runs, tasks of cut runs
     i64 grid_counters[4] = {};     // last catchhip_setcover_grid: scans, derived tables, solves, rows of the e = 0 scan
+    // last scan / near-duplicate filter: how often the host found a device buffer too small for what the device counted
+    // and ran again at the exact size, or took the slower path (CAPEV_*; catchhip_ctx_last_capacity_events)
+    i64 capacity_events[8] = {};
     // pinned staging word(s) for small device->host reads
     u64 *h_pin = nullptr;
     // larger pinned staging area (grown on demand) so that result read-backs are
@@ -148,6 +151,16 @@ struct catchhip_ctx {
     int nranks = 1, rank = 0;
     int num_cus = 256;
 };
+
+enum { CAPEV_SEED_LIST = 0,     // seed-list scan: work list re-run
+       CAPEV_GENERAL_SEED = 1,  // general scan, table look-up: work list re-run
+       CAPEV_BYTE_JOIN = 2,     // general scan, join of byte hashes: match list re-run
+       CAPEV_FAST_HIT = 3,      // tiled scan: hit list re-run
+       CAPEV_CUT_LIST = 4,      // general scan: more cut windows than the list holds, every seed extended by bytes
+       CAPEV_GIANT_TASKS = 5,   // key-grouped join: more tasks of cut runs than the list holds, the seed-list scan instead
+       CAPEV_NDF_EDGES = 6,     // near-duplicate filters, edge-list form: edge list re-run
+       NCAPEV = 8 };            // ([7] spare)
+static inline void chip_capacity_events_reset(catchhip_ctx *ctx) { memset(ctx->capacity_events, 0, sizeof(ctx->capacity_events)); }
 
 // pinned host scratch of at least `bytes` (contents not preserved on growth)
 int chip_pinned_reserve(catchhip_ctx *ctx, size_t bytes);

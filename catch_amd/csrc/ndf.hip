@@ -811,11 +811,17 @@ static int ndf_lazy_rounds(catchhip_ctx *ctx, u32 nn, size_t tn, DevBuf<u32> &co
         TRY(st2.alloc(((size_t)nn + 15) / 16 + 1));
         HIP_TRY(hipMemsetAsync(st2.p, 0, sizeof(u32) * (((size_t)nn + 15) / 16 + 1), s));
     }
-    const u32 dq_segcap = (u32)(tn / ES_SHARDS) + 64u * 2u;      // (wavefronts file round-robin: a shard gets at most its share + one wavefront's)
-    DevBuf<u32> dq_count, dq_overflow;
+    u32 dq_segcap = (u32)(tn / ES_SHARDS) + 64u * 2u;      // (wavefronts file round-robin: a shard gets at most its share + one wavefront's)
+    {   // tests: a segment too small for its share (the call then fails below; nothing is written past it)
+        const long long forced = chip_test_env_int("CATCHHIP_NDF_QUEUE_SEGCAP", -1);
+        if (forced >= 0) dq_segcap = (u32)std::min<long long>(std::max<long long>(1, forced), (long long)dq_segcap);
+    }
+    DevBuf<u32> dq_count;
     if (queued) { TRY(dq.alloc((size_t)dq_segcap * ES_SHARDS)); TRY(dq_count.alloc(ES_SHARDS * ES_STRIDE)); }
-    TRY(dq_overflow.alloc(1));
-    HIP_TRY(hipMemsetAsync(dq_overflow.p, 0, sizeof(u32), s));
+    // the queue's overflow flag sits behind the round's three words and comes back with them: a walk that found its
+    // segment full is lost, and the rounds after it would wait for it (or give up with another message)
+    u32 *dq_overflow = undecided + 3;
+    HIP_TRY(hipMemsetAsync(dq_overflow, 0, sizeof(u32), s));
     if (wake) {
         TRY(inv.alloc((size_t)nn * TS));
         TRY(left_tables.alloc(nn));
@@ -862,7 +868,7 @@ static int ndf_lazy_rounds(catchhip_ctx *ctx, u32 nn, size_t tn, DevBuf<u32> &co
         }
         HIP_TRY(hipMemsetAsync(undecided, 0, 3 * sizeof(u32), s));       // ([2]: the wake-up launch dropped somebody)
         if (queued) HIP_TRY(hipMemsetAsync(dq_count.p, 0, sizeof(u32) * ES_SHARDS * ES_STRIDE, s));
-        Q.dq = queued ? dq.p : (u32 *)nullptr; Q.dq_count = dq_count.p; Q.segcap = dq_segcap; Q.st2 = st2.p; Q.overflow = dq_overflow.p;
+        Q.dq = queued ? dq.p : (u32 *)nullptr; Q.dq_count = dq_count.p; Q.segcap = dq_segcap; Q.st2 = st2.p; Q.overflow = dq_overflow;
         if (nlist) {
             const u32 *cur_list = round ? (const u32 *)lists[round & 1].p : (const u32 *)nullptr;
             const int mode = (probe_pass && (round || probe_round0)) ? 2 : 0;
@@ -875,8 +881,9 @@ static int ndf_lazy_rounds(catchhip_ctx *ctx, u32 nn, size_t tn, DevBuf<u32> &co
         if (wake) hipLaunchKernelGGL(ndf_wake_kernel, dim3((unsigned)div_up(nn, 1024)), dim3(1024), 0, s, status.p, flags.p, nn, lists[(round & 1) ^ 1].p, undecided, trace ? 1 : 0, st2.p);
         else hipLaunchKernelGGL(ndf_node_round_kernel, dim3(nb), dim3(256), 0, s, status.p, flags.p, nn, undecided);
         tm.launch(2);
-        u32 h_und[3];
+        u32 h_und[4];
         TRY(chip_read_back(ctx, undecided, sizeof(h_und), h_und));
+        if (h_und[3]) { chip_set_error("ndf: the queue of deferred walks overflowed a shard's segment"); return CATCHHIP_EINVAL; }
         if (trace) {
             const auto t1 = std::chrono::steady_clock::now();
             u64 hp[2 * ES_SHARDS], cmp = 0;
@@ -903,12 +910,9 @@ static int ndf_lazy_rounds(catchhip_ctx *ctx, u32 nn, size_t tn, DevBuf<u32> &co
     if (left) { chip_set_error("ndf: %u probes undecided after %u rounds", left, nn + 2); return CATCHHIP_EINVAL; }
     tm.stop();
     std::vector<u64> h_pairs(2 * ES_SHARDS);
-    u32 h_overflow = 0;
     HIP_TRY(hipMemcpyAsync(h_pairs.data(), pairs.p, sizeof(u64) * 2 * ES_SHARDS, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&h_overflow, dq_overflow.p, sizeof(u32), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     tm.finish();
-    if (h_overflow) { chip_set_error("ndf: the queue of deferred walks overflowed a shard's segment"); return CATCHHIP_EINVAL; }
     // pairs compared / of them near (the all-pairs variant reports the length of its edge list there)
     for (int sh = 0; sh < ES_SHARDS; ++sh) { ctx->ndf_counters[2] += (i64)h_pairs[sh]; ctx->ndf_counters[3] += (i64)h_pairs[ES_SHARDS + sh]; }
     return ndf_keep_out(ctx, nn, status.p, keep);
@@ -933,6 +937,13 @@ static int ndf_fullest_shard(catchhip_ctx *ctx, const u32 *count, u32 *out) {
     ctx->ndf_counters[3] = edges;   // of them within the distance
     *out = m;
     return 0;
+}
+
+// a shard's first share of the edge list (tests: CATCHHIP_NDF_EDGE_CAP; a re-run takes the fullest shard's count)
+static u32 ndf_edge_capacity(i64 n) {
+    const i64 cap = std::max<i64>((i64)1 << 14, std::min<i64>(n * 16, (i64)1 << 28) / ES_SHARDS);
+    const long long forced = chip_test_env_int("CATCHHIP_NDF_EDGE_CAP", -1);
+    return (u32)(forced >= 0 ? std::min<long long>(std::max<long long>(1, forced), (long long)1 << 22) : cap);
 }
 
 // segused: edges in the fullest shard (the round kernel only looks at that many slots per shard)
@@ -965,6 +976,7 @@ static int ndf_resolve(catchhip_ctx *ctx, u32 nn, u32 segused, u32 segcap, DevBu
 int chip_ndf_hamming_device(catchhip_ctx *ctx, const u8 *d_rows, i64 n, i32 L, const i32 *positions, i32 ntables,
                             i32 k, i32 dist_thres, u8 *keep_host, const u32 *d_grp, i64 ngroups, u32 *d_keep_flags) {
     ARG_CHECK(ctx && n >= 0 && L > 0 && ntables >= 1 && k >= 1 && positions);
+    chip_capacity_events_reset(ctx);
     if (n == 0) return 0;
     ARG_CHECK(d_rows && (keep_host || d_keep_flags));
     const NdfKeep keep{keep_host, d_keep_flags};
@@ -1041,7 +1053,7 @@ int chip_ndf_hamming_device(catchhip_ctx *ctx, const u8 *d_rows, i64 n, i32 L, c
                                    (unsigned long long *)pairs.p, list, nlist, next, next_count, left_tables, inv, (u32)ntables, nslot, TS, false, Q);
         }, skeys, svals, cursor, (u32)ntables);
     }
-    u32 cap = (u32)std::max<i64>((i64)1 << 14, std::min<i64>(n * 16, (i64)1 << 28) / ES_SHARDS);   // per shard
+    u32 cap = ndf_edge_capacity(n);
     u32 ne = 0;
     for (int attempt = 0;; ++attempt) {
         TRY(e_i.reserve((size_t)cap * ES_SHARDS));
@@ -1064,6 +1076,7 @@ int chip_ndf_hamming_device(catchhip_ctx *ctx, const u8 *d_rows, i64 n, i32 L, c
         if (ne <= cap) break;
         if (attempt >= 2) { chip_set_error("ndf: edge buffer overflow"); return CATCHHIP_ENOMEM; }
         cap = ne;
+        ++ctx->capacity_events[CAPEV_NDF_EDGES];
     }
     return ndf_resolve(ctx, nn, ne, cap, e_i, e_j, count, status, flags, tm, keep);
 }
@@ -1664,6 +1677,7 @@ static int ndf_minhash_impl(catchhip_ctx *ctx, const u8 *bytes, const i64 *probe
                             NdfKeep keep, bool bytes_on_device = false, i64 equal_len = 0, const u32 *d_grp_dev = nullptr) {
     ARG_CHECK(ctx && n >= 0 && kmer_size >= 1 && kmer_size <= 16 && ntables >= 1 && k >= 1 && k <= 16 && ab);
     PoolScope pool_scope(ctx);
+    chip_capacity_events_reset(ctx);
     if (n == 0) return 0;
     ARG_CHECK(bytes && (keep.host || keep.d_flags));
     ARG_CHECK(probe_off ? probe_off[0] == 0 : (bytes_on_device && equal_len > 0));
@@ -1866,7 +1880,7 @@ static int ndf_minhash_impl(catchhip_ctx *ctx, const u8 *bytes, const i64 *probe
         lap("rounds", t_lap);
         return rc;
     }
-    u32 cap = (u32)std::max<i64>((i64)1 << 14, std::min<i64>(n * 16, (i64)1 << 28) / ES_SHARDS);   // per shard
+    u32 cap = ndf_edge_capacity(n);
     u32 ne = 0;
     for (int attempt = 0;; ++attempt) {
         TRY(e_i.reserve((size_t)cap * ES_SHARDS));
@@ -1896,6 +1910,7 @@ static int ndf_minhash_impl(catchhip_ctx *ctx, const u8 *bytes, const i64 *probe
         if (ne <= cap) break;
         if (attempt >= 2) { chip_set_error("ndf: edge buffer overflow"); return CATCHHIP_ENOMEM; }
         cap = ne;
+        ++ctx->capacity_events[CAPEV_NDF_EDGES];
     }
     return ndf_resolve(ctx, nn, ne, cap, e_i, e_j, count, status, flags, tm, keep);
 }

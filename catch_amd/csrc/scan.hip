@@ -1140,11 +1140,18 @@ static bool fast_path_ok(const catchhip_probes *P, const catchhip_targets *T, in
     return seed_path_ok(P, T, mm, lcf_thres, island) && P->pigeonhole && P->L / P->k > mm;
 }
 
+// tests: the first capacity of a list the device counts past, forced by an integer hook (-1: not set); a re-run
+// still takes the device's exact count
+static u32 forced_capacity(long long forced, u32 cap) {
+    return forced >= 0 ? (u32)std::min<long long>(std::max<long long>(1, forced), 0xffffffffll) : cap;
+}
+
 static int run_fast(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, int mm,
                     RawHits &H, PhaseTimer &tm) {
     const bool use_n = P->has_n || T->has_n;
     const u32 tailmask = probe_tail_mask(P->L);
     u32 cap = (u32)std::max<i64>((i64)1 << 20, std::min<i64>(P->nprobes * 64, (i64)1 << 28));
+    cap = forced_capacity(chip_test_env_int("CATCHHIP_FAST_HIT_CAP", -1), cap);
     TRY(H.count.alloc(1));
     // enough workgroups to fill 256 CUs several times over
     const u32 ntiles = (u32)div_up(T->total, SF2_TILE);
@@ -1175,6 +1182,7 @@ static int run_fast(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
         TRY(read_count(ctx, H.count.p, &n));
         if (n <= cap) { H.n = n; H.has_end = false; ctx->counters[0] = n; ctx->counters[1] = 0; ctx->seeds_dropped = 0; return 0; }
         cap = n;  // overflow: rerun with the exact size
+        ++ctx->capacity_events[CAPEV_FAST_HIT];
     }
     chip_set_error("fast scan: hit buffer overflow");
     return CATCHHIP_ENOMEM;
@@ -1336,7 +1344,7 @@ static int run_general(catchhip_ctx *ctx, const catchhip_probes *P, const catchh
     const i32 *e_probe = P->ent_probe.p, *e_pos = P->ent_pos.p;
     u32 nseeds = 0;
     if (table) {
-        S.scap = seed_capacity(P, T);
+        S.scap = forced_capacity(chip_test_env_int("CATCHHIP_SEED_CAP", -1), seed_capacity(P, T));
         for (int attempt = 0;; ++attempt) {
             TRY(seed_table_lookup_async(ctx, P, T, 0xffffffffu, 0, false, S, nullptr, 0, nullptr, tm));
             HIP_TRY(hipGetLastError());
@@ -1344,6 +1352,7 @@ static int run_general(catchhip_ctx *ctx, const catchhip_probes *P, const catchh
             if (nseeds <= S.scap) break;
             if (attempt >= 2) { chip_set_error("seed lookup: work list overflow"); return CATCHHIP_ENOMEM; }
             S.scap = nseeds;
+            ++ctx->capacity_events[CAPEV_GENERAL_SEED];
         }
         seed_ent = S.sent.p; seed_pos = S.spos.p;
         // the table's entries are the anchors sorted by (probe, position)
@@ -1358,6 +1367,7 @@ static int run_general(catchhip_ctx *ctx, const catchhip_probes *P, const catchh
         TRY(chip_radix_sort_pairs(ctx, keys, keys_alt, vals, vals_alt, nent, 64));
         TRY(scount.alloc(1));
         u32 cap = (u32)std::max<i64>((i64)1 << 20, std::min<i64>(T->total * 2, (i64)1 << 28));
+        cap = forced_capacity(chip_test_env_int("CATCHHIP_BYTE_JOIN_CAP", -1), cap);
         for (int attempt = 0;; ++attempt) {
             TRY(sa.reserve(cap));
             TRY(sb.reserve(cap));
@@ -1372,6 +1382,7 @@ static int run_general(catchhip_ctx *ctx, const catchhip_probes *P, const catchh
             if (nseeds <= cap) break;
             if (attempt >= 2) { chip_set_error("seed join: hit buffer overflow"); return CATCHHIP_ENOMEM; }
             cap = nseeds;
+            ++ctx->capacity_events[CAPEV_BYTE_JOIN];
         }
         seed_ent = sa.p; seed_pos = sb.p;
     }
@@ -1390,7 +1401,7 @@ static int run_general(catchhip_ctx *ctx, const catchhip_probes *P, const catchh
                  H.want_seed ? H.e.p : nullptr};
     extend_planes_fn planes = table ? pick_extend_planes((int)P->pwords) : nullptr;
     DevBuf<u32> cut;
-    const u32 cut_cap = 1u << 22;
+    const u32 cut_cap = forced_capacity(chip_test_env_int("CATCHHIP_CUT_CAP", -1), 1u << 22);
     if (planes) {
         // packed images: the window's mismatch mask in a few words, bit scans around the anchor
         TRY(cut.alloc((size_t)cut_cap + 1));
@@ -1410,6 +1421,7 @@ static int run_general(catchhip_ctx *ctx, const catchhip_probes *P, const catchh
         u32 ncut = 0;
         TRY(read_count(ctx, cut.p, &ncut));
         if (ncut > cut_cap) {   // never seen: more cut windows than the list holds -> everything by bytes
+            ++ctx->capacity_events[CAPEV_CUT_LIST];
             HIP_TRY(hipMemsetAsync(H.count.p, 0, sizeof(u32), ctx->stream));
             planes = nullptr;
         }
@@ -1642,7 +1654,8 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
     J.ngiant = 0;
     TRY(J.ecnt.reserve((size_t)nent + 1));
     TRY(J.ebase.reserve((size_t)nent + 1));
-    TRY(J.giant.reserve(KJ_GIANT_CAP));
+    const u32 giant_cap = forced_capacity(chip_test_env_int("CATCHHIP_GIANT_CAP", -1), KJ_GIANT_CAP);
+    TRY(J.giant.reserve(giant_cap));
     TRY(J.giant_n.reserve(4));
     TRY(J.pairs.reserve(192));   // [0..128) statistics (sharded), [128..192) the mask store's cursors
     HIP_TRY(hipMemsetAsync(J.ecnt.p, 0, sizeof(u32) * ((size_t)nent + 1), s));
@@ -1660,7 +1673,7 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
     A.ecnt = J.ecnt.p; A.ebase = (const u32 *)J.ebase.p; A.S = nullptr;
     A.bucket_of = sink.bucket_of; A.seq_genome = sink.seq_genome; A.ext = sink.ext;
     A.probe_group = sink.probe_group; A.seq_group = sink.seq_group;
-    A.giant = J.giant.p; A.giant_n = J.giant_n.p; A.giant_cap = KJ_GIANT_CAP;
+    A.giant = J.giant.p; A.giant_n = J.giant_n.p; A.giant_cap = giant_cap;
     // hit masks of the counting pass for the writing pass (scan_join.inc): 6 words per hit position hold S4's
     // (2 per position there); a run that finds the store full is simply verified again
     A.masks = nullptr; A.mbase = A.gmbase = nullptr; A.mcursor = J.pairs.p + 128; A.mask_cap = 0;   // (zeroed with the statistics)
@@ -1668,7 +1681,7 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
         const size_t mcap = (size_t)std::min<u64>((u64)1 << 26, std::max<u64>((u64)1 << 20, 6ull * J.nhit));
         TRY(J.masks.reserve(mcap));
         TRY(J.mbase.reserve(J.nhit));
-        TRY(J.gmbase.reserve(KJ_GIANT_CAP));
+        TRY(J.gmbase.reserve(giant_cap));
         A.masks = J.masks.p; A.mbase = J.mbase.p; A.gmbase = J.gmbase.p; A.mask_cap = (u32)mcap;
     }
     A.pairs = J.pairs.p;
@@ -1709,7 +1722,10 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
     if (getenv("CATCHHIP_TIMING"))
         fprintf(stderr, "[catchhip]   join: %u hit positions, %llu pairs, %llu lane slots in wave-wide runs, %u hits, %u tasks of cut runs\n",
                 J.nhit, pairs, slots, nhits, J.ngiant);
-    if (J.ngiant > KJ_GIANT_CAP) return 1;   // absurdly repetitive input: the seed-list scan copes (slowly)
+    if (J.ngiant > giant_cap) {   // absurdly repetitive input: the seed-list scan copes (slowly)
+        ++ctx->capacity_events[CAPEV_GIANT_TASKS];
+        return 1;
+    }
     ctx->counters[1] = (i64)pairs;
     ctx->seeds_dropped = 0;
     ctx->join_counters[0] = J.nhit; ctx->join_counters[1] = (i64)pairs; ctx->join_counters[2] = (i64)slots; ctx->join_counters[3] = J.ngiant;
@@ -1825,6 +1841,7 @@ struct ScanOut {
 static int scan_and_group(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, int mismatches,
                           int lcf_thres, int island, u32 ext, bool by_sequence, int mode, ScanOut &O,
                           bool dedupe = false, bool want_first = false) {
+    chip_capacity_events_reset(ctx);
     const bool seed_ok = seed_path_ok(P, T, mismatches, lcf_thres, island);
     const bool tiled_ok = fast_path_ok(P, T, mismatches, lcf_thres, island);
     const bool want_tiled = mode == CATCHHIP_SCAN_FAST;
@@ -1875,9 +1892,7 @@ static int scan_and_group(catchhip_ctx *ctx, const catchhip_probes *P, const cat
     if (use_join) {
     } else if (use_seed) {
         O.from_seeds = true;
-        O.S.scap = seed_capacity(P, T);
-        const long long forced_cap = chip_test_env_int("CATCHHIP_SEED_CAP", -1);     // tests: force the retry
-        if (forced_cap >= 0) O.S.scap = (u32)std::max<long long>(1, forced_cap);
+        O.S.scap = forced_capacity(chip_test_env_int("CATCHHIP_SEED_CAP", -1), seed_capacity(P, T));
         for (int attempt = 0;; ++attempt) {
             const auto dbg0 = std::chrono::steady_clock::now();
             TRY(bucket_prepare(O.B, nb, O.S.scap, true));
@@ -1904,6 +1919,7 @@ static int scan_and_group(catchhip_ctx *ctx, const catchhip_probes *P, const cat
             if (nseeds > O.S.scap) {
                 if (attempt >= 2) { chip_set_error("seed scan: work list overflow"); return CATCHHIP_ENOMEM; }
                 O.S.scap = nseeds;
+                ++ctx->capacity_events[CAPEV_SEED_LIST];
                 continue;
             }
             ctx->counters[1] = nseeds;
@@ -1968,6 +1984,7 @@ static void rows_emit(catchhip_ctx *ctx, catchhip_rows *R, const u32 *rstart, u3
 int chip_cover_scan_nosync(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, i32 mismatches,
                            i32 lcf_thres, i32 island, i32 cover_extension, i32 mode, catchhip_rows **out) {
     *out = nullptr;
+    chip_capacity_events_reset(ctx);
     if (P->nprobes == 0 || T->total == 0) return 1;
     if (!seed_path_ok(P, T, mismatches, lcf_thres, island)) return 1;
     if (!(mode == CATCHHIP_SCAN_SEED || mode == CATCHHIP_SCAN_AUTO)) return 1;
@@ -2078,6 +2095,7 @@ static int cover_scan_impl(catchhip_ctx *ctx, const catchhip_probes *P, const ca
                            const u32 *anchor_order = nullptr, bool allow_direct = false) {
     ARG_CHECK(ctx && P && T && out && cover_extension >= 0);
     PoolScope pool_scope(ctx);
+    chip_capacity_events_reset(ctx);
     ARG_CHECK(P->ctx == ctx && T->ctx == ctx);
     *out = nullptr;
     if (nrows) *nrows = 0;

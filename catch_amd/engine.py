@@ -228,6 +228,16 @@ class Context:
         d["flat_band_groups"] = int(lv[0])   # groups with band boundaries of their own (1: one row of boundaries)
         return d
 
+    CAPACITY_EVENTS = ("seed_list_rerun", "general_seed_rerun", "byte_join_rerun", "fast_hit_rerun",
+                       "cut_list_fallback", "giant_task_fallback", "ndf_edge_rerun", "_")
+
+    def capacity_events(self):
+        """catchhip_ctx_last_capacity_events -> dict: how often the last scan or near-duplicate filter on this
+        context found a device buffer too small and ran again at the exact size (or took the slower path)."""
+        out = np.zeros(8, dtype=np.int64)
+        check(self._L.catchhip_ctx_last_capacity_events(self._h, _ptr(out, c_i64p)))
+        return dict(zip(self.CAPACITY_EVENTS, (int(x) for x in out)))
+
     def grid_counters(self):
         """catchhip_ctx_last_grid_counters of the last setcover_grid call."""
         out = np.zeros(4, dtype=np.int64)

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define CATCHHIP_ABI_VERSION 1
+#define CATCHHIP_ABI_VERSION 2
 
 #define CATCHHIP_OK 0
 #define CATCHHIP_EINVAL (-1)   /* bad argument */
@@ -105,6 +105,16 @@ int catchhip_ctx_last_counters(catchhip_ctx *ctx, int64_t *out8);
  * catch/probe.py:1062-1069), [2] = lane slots the wave-wide runs occupied (64 per window chunk and entry; pairs /
  * slots = lane utilisation), [3] = tasks of runs that were cut by entries.  Zeros after a seed-list scan. */
 int catchhip_ctx_last_join_counters(catchhip_ctx *ctx, int64_t *out4);
+/* Capacity events of the last cover scan (catchhip_cover_scan and its kin, catchhip_tolerant_bp, the scan inside
+ * catchhip_setcover_filter) or near-duplicate filter (catchhip_ndf_*, catchhip_candidates_ndf_*) on this context;
+ * each of these calls zeroes all eight on entry (catchhip_setcover_grid: those of its last scan).  Many device
+ * buffers are sized by an estimate: a kernel counts past the capacity without writing past it, the host reads the
+ * count and runs again at the exact size, or takes a slower exact path.  out8[i] = how often that happened:
+ * [0] the seed-list scan's work list, [1] the work list of the general scan's table look-up, [2] the general scan's
+ * join of byte hashes, [3] the tiled scan's hit list, [4] the general scan's list of cut windows (every seed was then
+ * extended by bytes), [5] the key-grouped join's list of tasks of cut runs (the seed-list scan ran instead),
+ * [6] the edge list of a near-duplicate filter, [7] spare (0).  Results never depend on them. */
+int catchhip_ctx_last_capacity_events(catchhip_ctx *ctx, int64_t *out8);
 
 /* Of counter [1] (entries of the last seed scan's work list): those the
  * look-up's anchor-pair filter left without a seed -- a lower anchor of the same

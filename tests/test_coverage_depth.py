@@ -196,7 +196,7 @@ def test_symbol_is_declared_bound_and_wrapped():
     assert list(inspect.signature(engine.Rows.below_depth).parameters) == ["self", "num_sets", "picks", "depth"]
     mk = open(os.path.join(REPO, "catch_amd", "csrc", "Makefile")).read()
     assert "depth.hip" in mk and "subtract.hip" in mk
-    assert "#define CATCHHIP_ABI_VERSION 1\n" in hdr
+    assert "#define CATCHHIP_ABI_VERSION 2\n" in hdr
 
 
 def test_filter_keeps_the_reference_signature_and_takes_a_depth():

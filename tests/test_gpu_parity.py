@@ -1683,14 +1683,23 @@ def test_fused_filter_many_groups_matches_separate_calls(ctx, oracle):
 
 def test_seed_work_list_overflow_retries(ctx, oracle, monkeypatch):
     """A seed work list that is too small is detected on the device and the
-    scan re-runs with the exact size (same rows)."""
+    scan re-runs with the exact size (same rows).  The work list is the
+    seed-list scan's (CATCHHIP_SEED_LIST: the key-grouped join, which these
+    pigeonhole probes take otherwise, has none and never reads the capacity);
+    capacity_events() says that the re-run happened
+    (tests/test_capacity_paths.py has the other capacities)."""
     engine = _engine()
     genomes = small_species(seed=8)
     probes = candidates(genomes, 100, 50)
     exp = _oracle_rows(oracle, probes, genomes, 2, 100, 0, 50)
+    monkeypatch.setenv("CATCHHIP_SEED_LIST", "1")
+    assert _scan_rows(ctx, probes, genomes, 2, 100, 0, 50, engine.SCAN_SEED) == exp
+    assert ctx.capacity_events()["seed_list_rerun"] == 0
     monkeypatch.setenv("CATCHHIP_SEED_CAP", "100")
     assert _scan_rows(ctx, probes, genomes, 2, 100, 0, 50, engine.SCAN_SEED) == exp
     assert ctx.counters()["seed_hits"] > 100
+    assert ctx.counters()["join_hit_positions"] == 0
+    assert ctx.capacity_events()["seed_list_rerun"] == 1
 
 
 def test_fused_filter_falls_back_when_rows_are_long(ctx, oracle):

@@ -27,7 +27,7 @@ def test_cabi_library_exports_every_declared_symbol():
         assert hasattr(L, name), name
         assert name in _lib.PROTOTYPES, name
     assert set(_lib.PROTOTYPES) == declared
-    assert L.catchhip_abi_version() == 1
+    assert L.catchhip_abi_version() == 2
 
 
 def test_no_cpu_fallback_without_gpu():

@@ -108,7 +108,7 @@ def test_symbol_is_declared_bound_and_wrapped():
     assert all(sig[name].default is None for name in ("checkpoints", "denom", "covered0"))
     mk = open(os.path.join(REPO, "catch_amd", "csrc", "Makefile")).read()
     assert "gains.hip" in mk
-    assert "#define CATCHHIP_ABI_VERSION 1\n" in hdr
+    assert "#define CATCHHIP_ABI_VERSION 2\n" in hdr
     src = open(os.path.join(REPO, "catch_amd", "csrc", "gains.hip")).read()
     assert '#include "wave.h"' in src and "find_segment" in src and "chip_depth_marks" in src
     assert "double" not in src and "float" not in src                    # integer arithmetic only

@@ -159,7 +159,7 @@ def test_symbol_is_declared_bound_and_wrapped():
     assert sig["depth"].default == 1 and sig["fixed"].default is None
     mk = open(os.path.join(REPO, "catch_amd", "csrc", "Makefile")).read()
     assert "prune.hip" in mk and "depth.hip" in mk
-    assert "#define CATCHHIP_ABI_VERSION 1\n" in hdr
+    assert "#define CATCHHIP_ABI_VERSION 2\n" in hdr
     src = open(os.path.join(REPO, "catch_amd", "csrc", "prune.hip")).read()
     # the depth machinery is shared with depth.hip, not copied
     for name in ("chip_depth_marks", "chip_depth_array", "chip_depth_bitmap"):
