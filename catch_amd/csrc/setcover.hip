@@ -116,11 +116,12 @@ __device__ __forceinline__ u32 range_popcount_l2(const unsigned long long *bm, u
 // rate).  p is 8-byte aligned; the arrays have >= 8 words of slack at the end.
 struct __attribute__((aligned(8))) u64x2 { unsigned long long a, b; };
 // Only the loads that hold a word flagged in fl are issued (the others read as
-// 0): a lane that sits out a load costs no look-up, and a 200-base row spans
+// `fill`, 0 unless given): a lane that sits out a load costs no look-up, and a 200-base row spans
 // four words nine times out of ten, so the third load is rarely needed.
-__device__ __forceinline__ void load_words5(const unsigned long long *p, unsigned long long (&v)[RP_MAXW], u32 fl) {
-    u64x2 q0 = {0ull, 0ull}, q1 = {0ull, 0ull};
-    unsigned long long q2 = 0ull;
+__device__ __forceinline__ void load_words5(const unsigned long long *p, unsigned long long (&v)[RP_MAXW], u32 fl,
+                                            unsigned long long fill = 0ull) {
+    u64x2 q0 = {fill, fill}, q1 = {fill, fill};
+    unsigned long long q2 = fill;
     if (fl & 0x03u) q0 = *(const u64x2 *)p;
     if (fl & 0x0cu) q1 = *(const u64x2 *)(p + 2);
     if (fl & 0x10u) q2 = p[4];

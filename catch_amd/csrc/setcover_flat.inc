@@ -191,15 +191,27 @@ __device__ __forceinline__ u32 gr_row_popcount(const FlatArgs &a, u32 r) {
     return range_popcount((const u64 *)a.bm, x, e);
 }
 
+// What the host knows of a walk when it launches it, as a type: a kernel instance of a form holds only that form's
+// paths.  STRIPED: striped (1) or contiguous (0) tiles, BANDED: gain bands (1) or one band (0); -1: as the arguments
+// say, decided while the kernel runs (GrAnyForm: the kernels as they were).
+template <int STRIPED, int BANDED> struct GrForm {
+    static constexpr int striped = STRIPED, banded = BANDED;
+    static __device__ __forceinline__ bool is_striped(const int tile_shift) { return STRIPED < 0 ? tile_shift < 0 : STRIPED != 0; }
+    static __device__ __forceinline__ bool is_banded(const u32 nbands) { return BANDED < 0 ? nbands > 1 : BANDED != 0; }
+};
+using GrAnyForm = GrForm<-1, -1>;
+
 // global start of a record of tile t (contiguous tiles: t << shift; striped: 4-kbase stripes dealt round robin)
+template <class FORM = GrAnyForm>
 __device__ __forceinline__ u32 gr_start(u32 loc, u32 t, int tile_shift) {
-    return tile_shift >= 0 ? (t << tile_shift) + loc : ((((loc >> 12) << 3) + t) << 12) | (loc & 4095u);
+    return !FORM::is_striped(tile_shift) ? (t << tile_shift) + loc : ((((loc >> 12) << 3) + t) << 12) | (loc & 4095u);
 }
 __device__ __forceinline__ u32 gr_loc(u32 x, int tile_shift) {
     return tile_shift >= 0 ? x & ((1u << tile_shift) - 1u) : ((x >> 15) << 12) | (x & 4095u);
 }
 
 // the GR_UNR records of this lane in a workgroup step of tile t (dead / out of range: key 0) and their global starts
+template <class FORM = GrAnyForm>
 __device__ __forceinline__ void load_records(const FlatArgs &a, u32 buf, u32 bbase, u32 end, u32 t,
                                              unsigned long long (&k)[GR_UNR], u32 (&x)[GR_UNR]) {
     const u32 wbase = bbase + (threadIdx.x >> 6) * GR_WCH + (threadIdx.x & 63);
@@ -207,7 +219,7 @@ __device__ __forceinline__ void load_records(const FlatArgs &a, u32 buf, u32 bba
     for (int u = 0; u < GR_UNR; ++u) {
         const u32 r = wbase + u * 64;
         k[u] = r < end ? a.key[buf][r] : 0ull;
-        x[u] = gr_start(GR_KEY_LOC(k[u]), t, a.tile_shift);
+        x[u] = gr_start<FORM>(GR_KEY_LOC(k[u]), t, a.tile_shift);
     }
 }
 
@@ -238,7 +250,8 @@ struct GrNoTileHook { __device__ __forceinline__ void operator()(u32, u32) const
 struct GrWalk { u32 level = 0xffffffffu, wake = 0xffffffffu; };
 // f(sub-tile, bbase, end, tile start, k, x, fresh): fresh = a step of a band that wakes (uniform over the workgroup)
 // on_tile(tile, steps of this XCD in all): called by the whole workgroup before its first step in a tile
-template <class F, class G = GrNoTileHook>
+// FORM: the walk's form where the caller's instance knows it (GrForm)
+template <class FORM = GrAnyForm, class F, class G = GrNoTileHook>
 __device__ __forceinline__ void for_each_step(const FlatArgs &a, u32 buf, F f, G on_tile = G(), GrWalk wk = GrWalk()) {
     __shared__ u32 s_first[GR_MAXTX + 1];   // first step number of the XCD's j-th tile
     __shared__ u32 s_tstart[GR_MAXTX], s_tcnt[GR_MAXTX];
@@ -246,13 +259,14 @@ __device__ __forceinline__ void for_each_step(const FlatArgs &a, u32 buf, F f, G
     const u32 xcd = blockIdx.x & 7;
     const u32 nbx = (gridDim.x + 7 - xcd) >> 3;        // workgroups on this XCD
     const u32 ntx = min(a.xcd_ntiles[xcd], (u32)GR_MAXTX);
+    const bool banded = FORM::is_banded(a.nbands);
     // the tiles' ranges: loaded side by side, kept in LDS for the walk
     if (threadIdx.x < ntx) {
         const u32 tl = a.xcd_tile[xcd * GR_MAXTX + threadIdx.x];
-        const u32 band = a.nbands > 1 ? tl % a.nbands : 0u;
-        const bool fresh = a.nbands > 1 && band == wk.wake;
+        const u32 band = banded ? tl % a.nbands : 0u;
+        const bool fresh = banded && band == wk.wake;
         s_tile[threadIdx.x] = tl;
-        s_ctile[threadIdx.x] = a.nbands > 1 ? tl / a.nbands : tl;
+        s_ctile[threadIdx.x] = banded ? tl / a.nbands : tl;
         s_fresh[threadIdx.x] = fresh ? 1u : 0u;
         s_tstart[threadIdx.x] = a.tile_ptr[tl];
         // (a sleeping band's sub-tiles count as empty: nothing of theirs is read)
@@ -275,7 +289,7 @@ __device__ __forceinline__ void for_each_step(const FlatArgs &a, u32 buf, F f, G
         while (s_first[j + 1] <= g) ++j;              // steps only move forward
         bbase = s_tstart[j] + (g - s_first[j]) * GR_BCH;
         end = s_tstart[j] + s_tcnt[j];
-        load_records(a, s_fresh[j] ? 0u : buf, bbase, end, s_ctile[j], kc, xc);
+        load_records<FORM>(a, banded && s_fresh[j] ? 0u : buf, bbase, end, s_ctile[j], kc, xc);
     }
     u32 jprev = 0xffffffffu;
     while (g < total) {
@@ -286,9 +300,9 @@ __device__ __forceinline__ void for_each_step(const FlatArgs &a, u32 buf, F f, G
             while (s_first[j + 1] <= gn) ++j;
             bbase = s_tstart[j] + (gn - s_first[j]) * GR_BCH;
             end = s_tstart[j] + s_tcnt[j];
-            load_records(a, s_fresh[j] ? 0u : buf, bbase, end, s_ctile[j], kn, xn);
+            load_records<FORM>(a, banded && s_fresh[j] ? 0u : buf, bbase, end, s_ctile[j], kn, xn);
         }
-        f(s_tile[jc], bc, ec, s_tstart[jc], kc, xc, s_fresh[jc] != 0u);
+        f(s_tile[jc], bc, ec, s_tstart[jc], kc, xc, banded && s_fresh[jc] != 0u);
 #pragma unroll
         for (int u = 0; u < GR_UNR; ++u) { kc[u] = kn[u]; xc[u] = xn[u]; }
         g = gn;
@@ -299,43 +313,93 @@ __device__ __forceinline__ void for_each_step(const FlatArgs &a, u32 buf, F f, G
 #define GR_USEL_CAP 3072   // words of a universe with uncovered bits that gr_usel lists in LDS (more: it reads them again)
 struct __attribute__((aligned(4))) u32x2 { u32 a, b; };
 
-template <bool PARTIAL>
+// The uncovered positions of a row of a COVERED bitmap (FlatArgs::inv = ~0) from its words as load_words5 gives them
+// with fill ~0 -- a word that was not loaded reads as covered, and an unflagged word of the row that came along with
+// its neighbour IS covered in the row's positions, so no word asks for its flag: word 0 is cut at the row's first
+// bit, the row's last word at its last bit, what lies past it is masked whole (the masks are made once per row), and
+// a word between them costs an OR with zero and its two bit counts.  What is counted is the COVERED
+// positions, those outside the row with them (the masks are OR-ed in): 64 in a word that has nothing left, and the
+// loaded words are used as they arrive -- a NOT on them is placed by the compiler beside the load, inside the lanes'
+// branch, and makes every load wait for its data before the next one is issued.
+// Returns the row's uncovered positions; *nf: bit w = word w still holds some (it counted fewer than 64).
+// A dead record (key 0, nothing loaded) counts 0 and has no flags.
+__device__ __forceinline__ u32 gr_row_uncovered(const unsigned long long (&v)[RP_MAXW], u32 x, u32 len, u32 *nf) {
+    const u32 sh = x & 63u, eb = sh + len - 1u, last = eb >> 6;    // the row's last bit, counted from word 0, and its word
+    const u64 n0 = ~(~0ull << sh);                                 // below the row's first bit
+    const u64 n1 = ~1ull << (eb & 63u);                            // above its last one
+    // What lies past the row's last word: load_words5 loads words 0-1 and 2-3 in pairs, so word 1 of a one-word row and
+    // word 3 of a three-word row may hold the bitmap of somebody else and are masked whole; word 2 is never loaded past
+    // the last word (a flag of word 2 or 3 puts the last word at 2 or beyond), and word 4 only as the last word.
+    static_assert(RP_MAXW == 5, "the masks below are written out for five words");
+    const bool one = last == 0, upto2 = last <= 2;
+    const u64 nw[RP_MAXW] = {n0 | (one ? n1 : 0ull), one ? ~0ull : last > 1 ? 0ull : n1, upto2 ? n1 : 0ull,
+                             upto2 ? ~0ull : last > 3 ? 0ull : n1, n1};
+    u32 covered = 0, full = 0;
+#pragma unroll
+    for (u32 w = 0; w < RP_MAXW; ++w) {
+        const u64 o = v[w] | nw[w];
+        const u32 c = (u32)__popcll(o);
+        full |= (c >> 6) << w;                                      // (bit 6 of a count: all 64; taken from the count, so
+        covered += c;                                               //  that the word itself need not be kept for it)
+    }
+    *nf = full ^ ((1u << RP_MAXW) - 1u);
+    return 64u * RP_MAXW - covered;
+}
+
+// LEAN: the instance of the rounds of a full-coverage solve on one device (covered bitmap, round >= 1, no statistics),
+// of the form FORM -- it holds neither round 0, nor the changed-word statistics, nor the other tile form, nor a
+// select on FlatArgs::inv.  !LEAN: every path, decided while the kernel runs (FORM = GrAnyForm).
+template <bool PARTIAL, bool LEAN = false, class FORM = GrAnyForm>
 __global__ void __launch_bounds__(GR_THREADS)
-gr_count_kernel(FlatArgs a, u32 round) {
+gr_count_kernel(FlatArgs a, u32 round_arg) {
+    static_assert(!LEAN || !PARTIAL, "partial coverage keeps an uncovered bitmap");
     __shared__ u32 s_done, s_wcnt[2][GR_WAVES], s_base[2];     // (by step parity: a step's values are read while the next step's are written)
     __shared__ unsigned long long s_rows[4];
     GreedyState *st = a.st;
     if (threadIdx.x == 0) { s_done = st->done; s_rows[0] = s_rows[1] = s_rows[2] = s_rows[3] = 0; }
     __syncthreads();
     if (s_done) return;
-    const u32 ob = round & 1, ib = round ? ob ^ 1 : 0;    // round 0 counts buffer 0 in place
+    const u32 round = LEAN ? round_arg | 2u : round_arg;  // (LEAN: only its parity and "not 0" are used below)
+    const u32 ob = round_arg & 1, ib = round ? ob ^ 1 : 0;    // round 0 counts buffer 0 in place
     u32 *acc = a.acc[ob];
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->iters = round + 1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->iters = round_arg + 1;
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // LEAN: the rows are counted from the step's ballots, the same in every lane, and the rows counted again are the rows
     u32 cnt_rows = 0, cnt_dirty = 0, cnt_words = 0, cnt_own = 0, step_par = 0;
     // statistics (off in timed runs): words that changed in the previous round's apply launch
-    const u32 *chg = a.changed[0] ? a.changed[ob ^ 1] : nullptr;
+    const u32 *chg = !LEAN && a.changed[0] ? a.changed[ob ^ 1] : nullptr;
     // gain bands: the level of this round; a level other than the last round's means that its band wakes now
     GrWalk wk;
-    if (a.nbands > 1) {
+    if (FORM::is_banded(a.nbands)) {
         wk.level = st->level[ob];
         if (round && st->level[ob ^ 1] != wk.level) wk.wake = wk.level;
     }
-    for_each_step(a, ib, [&](u32 t, u32 bbase, u32 end, u32 tstart, unsigned long long (&k)[GR_UNR], u32 (&x)[GR_UNR], bool fresh) {
+    for_each_step<FORM>(a, ib, [&](u32 t, u32 bbase, u32 end, u32 tstart, unsigned long long (&k)[GR_UNR], u32 (&x)[GR_UNR], bool fresh) {
         // A band that wakes is read from buffer 0.  In an even round that is the buffer being written as well: its
         // records then stay where they are, the dead ones without flags (they claim nothing, and the next count
         // launch drops them), and the step adds its slots to the sub-tile's counter
         const bool inplace = fresh && ob == 0;
         unsigned long long v[GR_UNR][RP_MAXW];
 #pragma unroll
-        for (int u = 0; u < GR_UNR; ++u)
-            if (round && GR_KEY_FLAGS(k[u])) load_words5(a.bm + (x[u] >> 6), v[u], GR_KEY_FLAGS(k[u]));   // unflagged words: covered for this row
+        for (int u = 0; u < GR_UNR; ++u) {
+            if (LEAN) load_words5(a.bm + (x[u] >> 6), v[u], GR_KEY_FLAGS(k[u]), ~0ull);   // unflagged words: covered for this row
+            else if (round && GR_KEY_FLAGS(k[u])) load_words5(a.bm + (x[u] >> 6), v[u], GR_KEY_FLAGS(k[u]));
+        }
         u32 nf[GR_UNR], uv[GR_UNR], rc[GR_UNR];
         unsigned long long alive[GR_UNR];
         u32 wtot = 0;
 #pragma unroll
         for (int u = 0; u < GR_UNR; ++u) {
             const u32 fl = GR_KEY_FLAGS(k[u]), len = GR_KEY_LEN(k[u]);
+            if (LEAN) {
+                rc[u] = gr_row_uncovered(v[u], x[u], len, &nf[u]);
+                cnt_words += (u32)__popc(fl);
+                cnt_own += (u32)__popc(nf[u]);
+                alive[u] = __ballot(rc[u] != 0);                // (a row holds uncovered positions iff some word of it does)
+                cnt_rows += (u32)__popcll(__ballot(fl != 0));
+                wtot += (u32)__popcll(alive[u]);
+                continue;
+            }
             const u32 e = x[u] + len;
             const u32 w0 = x[u] >> 6, nwd = fl ? ((e - 1) >> 6) - w0 + 1 : 1;
             u32 cnt = 0;
@@ -430,7 +494,8 @@ gr_count_kernel(FlatArgs a, u32 round) {
             o += (u32)__popcll(alive[u]);
         }
     }, GrNoTileHook(), wk);
-    wave_sum_n(cnt_rows, cnt_dirty, cnt_words, cnt_own);
+    if (LEAN) { wave_sum_n(cnt_words, cnt_own); cnt_dirty = cnt_rows; }
+    else wave_sum_n(cnt_rows, cnt_dirty, cnt_words, cnt_own);
     if (lane == 0) {
         atomicAdd(&s_rows[0], (unsigned long long)cnt_rows);
         atomicAdd(&s_rows[1], (unsigned long long)cnt_dirty);
@@ -1728,7 +1793,16 @@ struct FlatSolve {
             hipLaunchKernelGGL(gr_count_kernel<true>, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
             hipLaunchKernelGGL(gr_fixup_kernel, dim3((unsigned)std::min<i64>(div_up((i64)nsets, 4), (i64)ctx->num_cus * 8)), dim3(256), 0,
                                ctx->stream, fa, round);
-        } else hipLaunchKernelGGL(gr_count_kernel<false>, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
+        } else if (round == 0 || fa.changed[0] || !fa.inv) {
+            // round 0, the changed-word statistics, an uncovered bitmap (ranks): the instance that holds every path
+            hipLaunchKernelGGL(gr_count_kernel<false>, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
+        } else {
+            // the rounds of a full-coverage solve: the instance of its tile form, with or without gain bands
+            const bool striped = fa.tile_shift < 0, banded = fa.nbands > 1;
+            auto kern = striped ? (banded ? gr_count_kernel<false, true, GrForm<1, 1>> : gr_count_kernel<false, true, GrForm<1, 0>>)
+                                : (banded ? gr_count_kernel<false, true, GrForm<0, 1>> : gr_count_kernel<false, true, GrForm<0, 0>>);
+            hipLaunchKernelGGL(kern, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
+        }
     }
     void launch_claim(u32 round) {
         if (fa.set_thr) hipLaunchKernelGGL(gr_claim_kernel<true>, dim3(gblocks), dim3(GR_THREADS), 0, ctx->stream, fa, round);
