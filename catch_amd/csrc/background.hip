@@ -1,0 +1,376 @@
+// Background k-mer screen (not in the reference; catch_amd/filter/background_filter.py defines the rule and is its
+// oracle): a candidate is dropped when more than H of its k-mers occur, as they are or reverse-complemented, in a
+// background (a host genome, rRNA, a vector), on the device's candidate list, before the near-duplicate filter and the
+// set cover like the pre-filters of prefilter.hip and thermo.hip.
+//
+// Code of a k-mer: 2 bits per character, (c >> 1) & 3 ('A' 0, 'C' 1, 'T' 2, 'G' 3), the first character in the most
+// significant of the 2K bits of a u64; the complement of a code is code ^ 2, and canonical(w) = the smaller of code(w)
+// and code(revcomp(w)), unsigned.  Both are rolled: fwd = ((fwd << 2) | c) & mask, rc = (rc >> 2) | ((c ^ 2) << (2K - 2)),
+// next to the length of the run of bases that ends here; from run >= K on the two registers hold exactly the last K
+// characters (K shifts push everything older out, whatever it was).  K = 32 fills the 64 bits: the mask is all ones
+// (made on the host by a comparison, not by a shift of 64) and 2K - 2 = 62.
+//
+// The index (catchhip_kmer_index): the sorted distinct canonical codes of the background's valid k-mers, and a prefix
+// directory dir[p] = index of the first code whose top P bits are >= p (2^P + 1 entries, dir[2^P] = n_unique), with
+// P = clamp(ceil(log2(n_unique)), 8, min(2K, 30)): a bucket holds about one code.  Built with the scan and the sort of
+// primitives.hip: kmer_emit_kernel counts, then writes, the canonical code of every valid position (a thread per
+// BG_CHUNK end positions, K - 1 bytes of run-up), chip_radix_sort_pairs sorts on 2K key bits (its 4-byte values are
+// dead weight here), a flag / scan / compact pass makes the list distinct.  codes and dir are plain hipMalloc blocks
+// owned by the index, not by a context's block cache: every context of the device may read them, and they outlive the
+// context that built them.
+//
+// background_flag_kernel: one thread per unique candidate, the rows staged as the Tm kernel stages them (stage.h), one
+// pass over its L bytes.  Per byte the rolling update; from run >= K on one look-up: dir[p] and dir[p + 1] (one gather
+// of two neighbouring words), then the bucket -- halved while it is longer than 4, then compared one by one.  Counting
+// as in tm_flag_kernel: BG_WORDS 64-bit counters per workgroup in LDS behind the rows -- the 256 bins of hits, then
+// "dropped".  Bin 0 and "dropped" are one address each for most threads, so they are summed over the wave first and
+// added once per wave; the other bins take LDS atomics.  After a barrier thread t adds counter t, if it is not zero, to
+// one of BG_SLOTS copies in global memory, which the host adds up.  No thread returns before the barrier.
+#include "internal.h"
+#include "wave.h"
+#include "stage.h"
+
+#define BG_BINS 256u
+#define BG_WORDS 257u                // the bins, dropped
+#define BG_SLOTS 64u
+#define BG_SLOT_WORDS 272u           // 17 whole 128-byte lines
+#define BG_EXTRA_BYTES (BG_WORDS * 8u)
+#define BG_CHUNK 64u                 // end positions per thread of the emit kernel
+#define BG_MAX_BYTES 0xfffff000ull   // the scans count in 32 bits
+
+struct catchhip_kmer_index {
+    int device = 0;
+    i32 k = 0;
+    u64 n_valid = 0, n_unique = 0;
+    u32 P = 8;                       // directory bits
+    u64 *codes = nullptr;            // n_unique (at least one word allocated)
+    u32 *dir = nullptr;              // 2^P + 1
+    ~catchhip_kmer_index() {
+        if (codes) (void)hipFree(codes);
+        if (dir) (void)hipFree(dir);
+    }
+};
+
+// ---- the index --------------------------------------------------------------------------------------------------
+// WRITE = false: cnt[chunk] = valid k-mers that END in the chunk's positions; WRITE = true: their canonical codes from
+// keys[at[chunk]] on.  A k-mer never spans two records: the run of bases starts again at every record start.
+template <bool WRITE>
+__global__ void __launch_bounds__(256)
+kmer_emit_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ off, u32 nseq, u32 total, u32 nchunks, u32 K,
+                 u64 mask, u32 rc_shift, u32 *__restrict__ cnt, const u32 *__restrict__ at, u64 *__restrict__ keys) {
+    const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nchunks) return;
+    const u64 e0 = (u64)c * BG_CHUNK;
+    const u32 e1 = e0 + BG_CHUNK < (u64)total ? (u32)(e0 + BG_CHUNK) : total;
+    const u32 w0 = e0 >= K - 1u ? (u32)e0 - (K - 1u) : 0u;
+    u32 rec = find_segment(off, nseq, w0);
+    u32 next = off[rec + 1];
+    u64 fwd = 0, rc = 0;
+    u32 run = 0, made = 0;
+    const u32 base = WRITE ? at[c] : 0u;
+    for (u32 j = w0; j < e1; ++j) {
+        while (j >= next) { ++rec; next = off[rec + 1]; run = 0; }     // (j < total = off[nseq]: rec stays below nseq)
+        const u8 ch = bytes[j];
+        const u64 code = (ch >> 1) & 3u;
+        fwd = ((fwd << 2) | code) & mask;
+        rc = (rc >> 2) | ((code ^ 2ull) << rc_shift);
+        run = is_base(ch) ? run + 1u : 0u;
+        if (run >= K && j >= e0) {
+            if (WRITE) keys[base + made] = fwd < rc ? fwd : rc;
+            ++made;
+        }
+    }
+    if (!WRITE) cnt[c] = made;
+}
+
+__global__ void __launch_bounds__(256)
+kmer_head_kernel(const u64 *__restrict__ keys, u32 n, u32 *__restrict__ flag) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) flag[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(256)
+kmer_compact_kernel(const u64 *__restrict__ keys, const u32 *__restrict__ flag, const u32 *__restrict__ at, u32 n,
+                    u64 *__restrict__ codes) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && flag[i]) codes[at[i]] = keys[i];
+}
+
+// dir[p] = i for every prefix p above code i - 1's and up to code i's (i = n: up to 2^P): each entry written once
+__global__ void __launch_bounds__(256)
+kmer_dir_kernel(const u64 *__restrict__ codes, u32 n, u32 shift, u32 nprefix, u32 *__restrict__ dir) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    const u32 first = i == 0 ? 0u : (u32)(codes[i - 1] >> shift) + 1u;
+    const u32 last = i == n ? nprefix : (u32)(codes[i] >> shift);
+    for (u32 p = first; p <= last; ++p) dir[p] = i;
+}
+
+static int kmer_index_build(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, i64 nseq, catchhip_kmer_index *X) {
+    hipStream_t s = ctx->stream;
+    const u32 K = (u32)X->k;
+    const u64 mask = K == 32 ? ~0ull : (((u64)1 << (2 * K)) - 1);
+    const u32 total = (u32)off[nseq];
+    u32 n_valid = 0, n_unique = 0;
+    DevBuf<u64> keys, keys_alt;
+    PhaseTimer tm(ctx, PHASE_PREFILTER);
+    if (total >= K) {
+        DevBuf<u8> d_bytes;
+        DevBuf<u32> d_off, cnt, at, tmp;
+        std::vector<u32> h_off((size_t)nseq + 1);
+        for (i64 i = 0; i <= nseq; ++i) h_off[(size_t)i] = (u32)off[i];
+        TRY(d_bytes.alloc(total));
+        TRY(d_off.alloc((size_t)nseq + 1));
+        HIP_TRY(hipMemcpyAsync(d_bytes.p, bytes, total, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_off.p, h_off.data(), sizeof(u32) * ((size_t)nseq + 1), hipMemcpyHostToDevice, s));
+        tm.restart();                                          // (the build's time starts behind the upload)
+        const u32 nchunks = (u32)div_up((i64)total, BG_CHUNK);
+        const dim3 grid((unsigned)div_up((i64)nchunks, 256)), block(256);
+        TRY(cnt.alloc((size_t)nchunks + 1));
+        TRY(at.alloc((size_t)nchunks + 1));
+        HIP_TRY(hipMemsetAsync(cnt.p + nchunks, 0, sizeof(u32), s));
+        hipLaunchKernelGGL(kmer_emit_kernel<false>, grid, block, 0, s, (const u8 *)d_bytes.p, (const u32 *)d_off.p,
+                           (u32)nseq, total, nchunks, K, mask, 2 * K - 2, cnt.p, (const u32 *)nullptr, (u64 *)nullptr);
+        TRY(chip_exclusive_scan_u32(ctx, cnt.p, at.p, (i64)nchunks + 1, tmp));
+        TRY(read_count(ctx, at.p + nchunks, &n_valid));       // (also orders the pageable uploads before h_off goes)
+        tm.launch(3);
+        if (n_valid) {
+            TRY(keys.alloc(n_valid));
+            hipLaunchKernelGGL(kmer_emit_kernel<true>, grid, block, 0, s, (const u8 *)d_bytes.p, (const u32 *)d_off.p,
+                               (u32)nseq, total, nchunks, K, mask, 2 * K - 2, (u32 *)nullptr, (const u32 *)at.p, keys.p);
+            HIP_TRY(hipGetLastError());
+            tm.launch();
+        }
+    }
+    X->n_valid = n_valid;
+    if (n_valid) {
+        // the pair sort's values carry nothing; behind it the two value buffers serve the distinct pass
+        DevBuf<u32> vals, vals_alt, tmp;
+        TRY(vals.alloc((size_t)n_valid + 1));
+        TRY(vals_alt.alloc((size_t)n_valid + 1));
+        HIP_TRY(hipMemsetAsync(vals.p, 0, sizeof(u32) * ((size_t)n_valid + 1), s));
+        TRY(chip_radix_sort_pairs(ctx, keys, keys_alt, vals, vals_alt, n_valid, 2 * (int)K));
+        tm.launch(3 * ((2 * K + 7) / 8));
+        const dim3 grid((unsigned)div_up((i64)n_valid, 256)), block(256);
+        hipLaunchKernelGGL(kmer_head_kernel, grid, block, 0, s, (const u64 *)keys.p, n_valid, vals.p);
+        HIP_TRY(hipMemsetAsync(vals.p + n_valid, 0, sizeof(u32), s));
+        TRY(chip_exclusive_scan_u32(ctx, vals.p, vals_alt.p, (i64)n_valid + 1, tmp));
+        TRY(read_count(ctx, vals_alt.p + n_valid, &n_unique));
+        HIP_TRY(hipMalloc((void **)&X->codes, sizeof(u64) * (size_t)n_unique));
+        hipLaunchKernelGGL(kmer_compact_kernel, grid, block, 0, s, (const u64 *)keys.p, (const u32 *)vals.p,
+                           (const u32 *)vals_alt.p, n_valid, X->codes);
+        HIP_TRY(hipGetLastError());
+        tm.launch(4);
+        HIP_TRY(hipStreamSynchronize(s));                      // (the scratch goes back to the pool below)
+    } else {
+        HIP_TRY(hipMalloc((void **)&X->codes, sizeof(u64)));
+        HIP_TRY(hipMemsetAsync(X->codes, 0, sizeof(u64), s));
+    }
+    X->n_unique = n_unique;
+    int P = ceil_log2_u64(n_unique);
+    const int pmax = 2 * (int)K < 30 ? 2 * (int)K : 30;
+    P = P < 8 ? 8 : P > pmax ? pmax : P;
+    X->P = (u32)P;
+    const u32 nprefix = (u32)1 << P;
+    HIP_TRY(hipMalloc((void **)&X->dir, sizeof(u32) * ((size_t)nprefix + 1)));
+    hipLaunchKernelGGL(kmer_dir_kernel, dim3((unsigned)div_up((i64)n_unique + 1, 256)), dim3(256), 0, s,
+                       (const u64 *)X->codes, n_unique, 2 * K - (u32)P, nprefix, X->dir);
+    HIP_TRY(hipGetLastError());
+    tm.launch();
+    tm.stop();
+    HIP_TRY(hipStreamSynchronize(s));
+    tm.finish();
+    return 0;
+}
+
+extern "C" int catchhip_kmer_index_create(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, i64 nseq, i32 k,
+                                          catchhip_kmer_index **out, i64 *n_valid, i64 *n_unique) {
+    ARG_CHECK(ctx && out && off && nseq >= 0);
+    *out = nullptr;
+    if (k < 8 || k > 32) {
+        chip_set_error("kmer_index_create: k must lie in 8 .. 32 (got %d)", (int)k);
+        return CATCHHIP_EINVAL;
+    }
+    if (nseq >= ((i64)1 << 31)) {
+        chip_set_error("kmer_index_create: 2^31 records and more are not supported (got %lld)", (long long)nseq);
+        return CATCHHIP_EINVAL;
+    }
+    ARG_CHECK(off[0] == 0);
+    for (i64 i = 0; i < nseq; ++i) ARG_CHECK(off[i + 1] >= off[i]);
+    if ((u64)off[nseq] >= BG_MAX_BYTES) {
+        // (the valid positions are at most the bytes: this refuses every background of 2^32 valid positions and more)
+        chip_set_error("kmer_index_create: a background of %lld bytes has too many positions for one index: the sort "
+                       "and the scans count in 32 bits (fewer than %llu bytes; split the background)",
+                       (long long)off[nseq], (unsigned long long)BG_MAX_BYTES);
+        return CATCHHIP_EINVAL;
+    }
+    ARG_CHECK(off[nseq] == 0 || bytes);
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<catchhip_kmer_index> X(new catchhip_kmer_index());
+    X->device = ctx->device;
+    X->k = k;
+    TRY(kmer_index_build(ctx, bytes, off, nseq, X.get()));
+    if (n_valid) *n_valid = (i64)X->n_valid;
+    if (n_unique) *n_unique = (i64)X->n_unique;
+    *out = X.release();
+    return 0;
+}
+
+extern "C" int catchhip_kmer_index_fetch(catchhip_ctx *ctx, const catchhip_kmer_index *X, u64 *out) {
+    ARG_CHECK(ctx && X && ctx->device == X->device);
+    if (X->n_unique == 0) return 0;
+    ARG_CHECK(out);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(out, X->codes, sizeof(u64) * (size_t)X->n_unique, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" void catchhip_kmer_index_destroy(catchhip_kmer_index *X) {
+    if (!X) return;
+    (void)hipSetDevice(X->device);
+    delete X;                                                  // (hipFree waits for the device's work)
+}
+
+// ---- the filter ---------------------------------------------------------------------------------------------------
+template <bool STAGE, bool FILTER, bool HIST>
+__global__ void __launch_bounds__(256)
+background_flag_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ upos, const u32 *__restrict__ mult, u32 n, u32 L,
+                       u32 K, u64 mask, u32 rc_shift, const u64 *__restrict__ codes, const u32 *__restrict__ dir,
+                       u32 dir_shift, u32 max_hits, u32 nchunk, u32 pitch_dw, u32 extra_off_dw, u32 *__restrict__ flag,
+                       u64 *__restrict__ totals) {
+    extern __shared__ u32 bg_lds[];
+    const u32 rows = blockDim.x, r = threadIdx.x;
+    const u32 i = blockIdx.x * rows + r;
+    unsigned long long *cnt = (unsigned long long *)(bg_lds + extra_off_dw);        // (extra_off_dw is even: 8-byte aligned)
+    for (u32 t = r; t < BG_WORDS; t += rows) cnt[t] = 0;
+    if (STAGE) stage_rows(bytes, upos, n, L, nchunk, pitch_dw, bg_lds);             // (ends with a barrier)
+    else __syncthreads();
+    u64 t_zero = 0, t_drop = 0;
+    if (i < n) {                                              // (no early return: the wave sums and the barrier below)
+        const u32 s = upos[i];
+        const u8 *p = STAGE ? (const u8 *)(bg_lds + r * pitch_dw) + (s & 15u) : bytes + s;
+        u64 fwd = 0, rc = 0;
+        u32 run = 0, hits = 0;
+        for (u32 j = 0; j < L; ++j) {
+            const u8 c = p[j];
+            const u64 code = (c >> 1) & 3u;
+            fwd = ((fwd << 2) | code) & mask;
+            rc = (rc >> 2) | ((code ^ 2ull) << rc_shift);
+            run = is_base(c) ? run + 1u : 0u;
+            if (run >= K) {
+                const u64 canon = fwd < rc ? fwd : rc;
+                const u32 b = (u32)(canon >> dir_shift);
+                u32 lo = dir[b], hi = dir[b + 1u];
+                while (hi - lo > 4u) {                        // (canon, if it is there at all, stays inside [lo, hi))
+                    const u32 mid = (lo + hi) >> 1;
+                    if (codes[mid] <= canon) lo = mid; else hi = mid;
+                }
+                u32 hit = 0;
+                for (u32 t = lo; t < hi; ++t) hit |= codes[t] == canon ? 1u : 0u;
+                hits += hit;
+            }
+        }
+        const u32 m = mult[i];
+        if (HIST) {
+            if (hits == 0) t_zero = m;
+            else atomicAdd(cnt + (hits < BG_BINS - 1u ? hits : BG_BINS - 1u), (unsigned long long)m);
+        }
+        if (FILTER) {
+            const bool drop = hits > max_hits;
+            flag[i] = drop ? 0u : 1u;
+            t_drop = drop ? m : 0u;
+        }
+    }
+    wave_sum_n(t_zero, t_drop);
+    if ((r & 63u) == 0) {
+        if (t_zero) atomicAdd(cnt, (unsigned long long)t_zero);
+        if (t_drop) atomicAdd(cnt + BG_BINS, (unsigned long long)t_drop);
+    }
+    __syncthreads();
+    unsigned long long *t = (unsigned long long *)totals + (blockIdx.x & (BG_SLOTS - 1u)) * BG_SLOT_WORDS;
+    for (u32 w = r; w < BG_WORDS; w += rows) {
+        const unsigned long long v = cnt[w];
+        if (v) atomicAdd(t + w, v);
+    }
+}
+
+template <bool FILTER, bool HIST>
+static int launch_background(catchhip_ctx *ctx, const catchhip_candidates *C, const catchhip_kmer_index *X, u32 max_hits,
+                             u32 *flag, u64 *totals) {
+    const u32 n = (u32)C->nuniq, L = (u32)C->L, K = (u32)X->k;
+    const u64 mask = K == 32 ? ~0ull : (((u64)1 << (2 * K)) - 1);
+    // the rows as the Tm kernel stages them, and behind them the counters, once per workgroup
+    const u32 nchunk = (L + 15u + 15u) / 16u, pitch_dw = 4u * nchunk + 1u;
+    const size_t row_bytes = (size_t)pitch_dw * 4;
+    u32 rows = 256;
+    while (rows > 64 && rows * row_bytes + BG_EXTRA_BYTES > POLYA_LDS_BUDGET) rows >>= 1;
+    const bool stage = rows * row_bytes + BG_EXTRA_BYTES <= POLYA_LDS_BUDGET && ((uintptr_t)C->T->bytes.p & 15u) == 0;
+    if (stage)
+        hipLaunchKernelGGL((background_flag_kernel<true, FILTER, HIST>), dim3((unsigned)div_up((i64)n, rows)), dim3(rows),
+                           rows * row_bytes + BG_EXTRA_BYTES, ctx->stream, (const u8 *)C->T->bytes.p,
+                           (const u32 *)C->upos.p, (const u32 *)C->mult.p, n, L, K, mask, 2 * K - 2,
+                           (const u64 *)X->codes, (const u32 *)X->dir, 2 * K - X->P, max_hits, nchunk, pitch_dw,
+                           rows * pitch_dw, flag, totals);
+    else
+        hipLaunchKernelGGL((background_flag_kernel<false, FILTER, HIST>), dim3((unsigned)div_up((i64)n, 256)), dim3(256),
+                           BG_EXTRA_BYTES, ctx->stream, (const u8 *)C->T->bytes.p, (const u32 *)C->upos.p,
+                           (const u32 *)C->mult.p, n, L, K, mask, 2 * K - 2, (const u64 *)X->codes,
+                           (const u32 *)X->dir, 2 * K - X->P, max_hits, nchunk, pitch_dw, 0u, flag, totals);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int catchhip_candidates_drop_background(catchhip_ctx *ctx, catchhip_candidates *C, const catchhip_kmer_index *X,
+                                                   i32 filter_on, i64 max_hits, i64 dropped[1], u64 hist[256],
+                                                   i64 *nkept) {
+    ARG_CHECK(ctx && C && C->ctx == ctx && X);
+    if (C->filtered) {
+        chip_set_error("candidates_drop_background: a near-duplicate filter was already applied (the background filter "
+                       "comes first)");
+        return CATCHHIP_EINVAL;
+    }
+    if (X->device != ctx->device) {
+        chip_set_error("candidates_drop_background: the index lives on device %d, the candidates on device %d", X->device,
+                       ctx->device);
+        return CATCHHIP_EINVAL;
+    }
+    if (filter_on && max_hits < 0) {
+        chip_set_error("candidates_drop_background: max_hits must be >= 0 (got %lld)", (long long)max_hits);
+        return CATCHHIP_EINVAL;
+    }
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (nkept) *nkept = C->nuniq;
+    if (dropped) dropped[0] = 0;
+    if (hist) memset(hist, 0, sizeof(u64) * BG_BINS);
+    if (C->nuniq == 0 || C->L < X->k || !(filter_on || hist)) return 0;
+    const u32 n = (u32)C->nuniq;
+    const u32 H = max_hits > (i64)0xffffffffll ? 0xffffffffu : (u32)max_hits;
+    DevBuf<u32> flag;
+    DevBuf<u64> totals;
+    if (filter_on) TRY(flag.alloc((size_t)n + 1));
+    const size_t totals_bytes = sizeof(u64) * BG_SLOTS * BG_SLOT_WORDS;
+    TRY(totals.alloc(BG_SLOTS * BG_SLOT_WORDS));
+    TRY(chip_pinned_reserve(ctx, totals_bytes));
+    HIP_TRY(hipMemsetAsync(totals.p, 0, totals_bytes, ctx->stream));
+    PhaseTimer tm(ctx, PHASE_PREFILTER);
+    if (filter_on && hist) TRY((launch_background<true, true>(ctx, C, X, H, flag.p, totals.p)));
+    else if (filter_on) TRY((launch_background<true, false>(ctx, C, X, H, flag.p, totals.p)));
+    else TRY((launch_background<false, true>(ctx, C, X, 0u, nullptr, totals.p)));
+    tm.launch();
+    tm.stop();
+    HIP_TRY(hipMemcpyAsync(ctx->h_big, totals.p, totals_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    tm.finish();
+    u64 gone = 0;
+    for (u32 slot = 0; slot < BG_SLOTS; ++slot) {
+        const u64 *w = (const u64 *)ctx->h_big + slot * BG_SLOT_WORDS;
+        if (hist) for (u32 b = 0; b < BG_BINS; ++b) hist[b] += w[b];
+        gone += w[BG_BINS];
+    }
+    if (dropped) dropped[0] = (i64)gone;
+    if (gone == 0) return 0;                                  // nothing dropped (or not filtering): the list stands
+    return chip_candidates_keep_flagged(ctx, C, flag, nkept);
+}

@@ -30,7 +30,11 @@ right after that one (catch_amd/filter/structure_filter.py has the rules);
 --filter-tm (with --tm-sodium, --tm-oligo, --tm-formamide; nor these) drops
 candidates by their nearest-neighbour melting temperature and
 --write-tm-histogram writes its distribution, one filter right after that one
-(catch_amd/filter/tm_filter.py has the rule).
+(catch_amd/filter/tm_filter.py has the rule); --background (with
+--background-kmer, --background-max-hits; nor these) drops candidates that
+share k-mers with a host genome or another background and
+--write-background-histogram writes how many share how many, one filter right
+after that one (catch_amd/filter/background_filter.py has the rule).
 --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
@@ -41,7 +45,7 @@ import os
 import random
 import sys
 
-from catch_amd.filter import composition_filter
+from catch_amd.filter import background_filter, composition_filter
 from catch_amd.filter import duplicate_filter, near_duplicate_filter
 from catch_amd.filter import probe_designer, set_cover_filter
 from catch_amd.filter import structure_filter, tm_filter
@@ -135,6 +139,7 @@ def parse_args(argv=None, args_type="basic"):
     composition_filter.add_arguments(p)     # --filter-gc, --max-homopolymer, --filter-low-complexity (not in the reference)
     structure_filter.add_arguments(p)       # --max-hairpin-stem, --hairpin-min-loop, --max-self-dimer (not in the reference)
     tm_filter.add_arguments(p)              # --filter-tm, --tm-..., --write-tm-histogram (not in the reference)
+    background_filter.add_arguments(p)      # --background, --background-..., --write-background-histogram (not in the reference)
     p.add_argument("--add-reverse-complements", dest="add_reverse_complements",
                    action="store_true",
                    help="add the reverse complement of each probe to the output")
@@ -209,6 +214,7 @@ def parse_args(argv=None, args_type="basic"):
     composition_filter.from_args(args, p.error)     # (bad values are argparse errors; main builds the filter)
     structure_filter.from_args(args, p.error)
     tm_filter.from_args(args, p.error)
+    background_filter.from_args(args, p.error, load=False)      # (the options alone: main reads the background)
     return args
 
 
@@ -432,6 +438,9 @@ def main(args):
     tm = tm_filter.from_args(args)
     if tm is not None:              # melting temperature: a filter, a measurement (--write-tm-histogram), or both
         filters.append(tm)
+    background = background_filter.from_args(args)
+    if background is not None:      # k-mers shared with a background: a filter, a measurement, or both, likewise
+        filters.append(background)
     if (args.filter_with_lsh_hamming is not None and
             args.filter_with_lsh_minhash is not None):
         raise Exception("Cannot use both --filter-with-lsh-hamming "
@@ -512,6 +521,13 @@ def main(args):
         logger.info("tm filter: %d candidates dropped (below %d, above %d)", tm.dropped[2], *tm.dropped[:2])
         if args.write_tm_histogram:
             tm.write_histogram(args.write_tm_histogram)
+    if background is not None:
+        if logger.isEnabledFor(logging.INFO):       # (counting the k-mers can mean building an index)
+            logger.info("background filter: %d candidates dropped; %d background bases, %d distinct k-mers",
+                        background.dropped, background.background_bases, background.distinct_kmers())
+        if args.write_background_histogram:
+            background.write_histogram(args.write_background_histogram)
+        background.close()
     if args.coverage_depth > 1:
         for fn, sizes in zip(args.dataset, scf.last_layer_sizes):
             logger.info("%s: %s probes in the layers of depth 1 to %d",

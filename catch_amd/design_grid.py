@@ -18,7 +18,7 @@ import os
 import sys
 
 from catch_amd import grid
-from catch_amd.filter import composition_filter, structure_filter, tm_filter
+from catch_amd.filter import background_filter, composition_filter, structure_filter, tm_filter
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.design_grid")
@@ -85,6 +85,7 @@ def parse_args(argv=None):
     composition_filter.add_arguments(p)     # as catch_amd.design's
     structure_filter.add_arguments(p)       # likewise
     tm_filter.add_arguments(p)              # likewise
+    background_filter.add_arguments(p)      # likewise
     p.add_argument("--small-seq-skip", type=int)
     p.add_argument("--small-seq-min", type=int)
     p.add_argument("--kmer-probe-map-k", type=int)
@@ -120,6 +121,7 @@ def parse_args(argv=None):
     composition_filter.from_args(args, p.error)     # (bad values are argparse errors; main builds the filter)
     structure_filter.from_args(args, p.error)
     tm_filter.from_args(args, p.error)
+    background_filter.from_args(args, p.error, load=False)      # (the options alone: main reads the background)
     return args
 
 
@@ -160,6 +162,7 @@ def main(args):
     composition = composition_filter.from_args(args)
     structure = structure_filter.from_args(args)
     tm = tm_filter.from_args(args)
+    background = background_filter.from_args(args)
     got = grid.design_grid(
         datasets, args.grid_mismatches, args.grid_cover_extension,
         probe_length=args.probe_length, probe_stride=args.probe_stride,
@@ -169,7 +172,7 @@ def main(args):
         small_seq_skip=args.small_seq_skip, small_seq_min=args.small_seq_min,
         kmer_probe_map_k=args.kmer_probe_map_k, filter_polya=args.filter_polya,
         filter_composition=composition, filter_structure=structure,
-        filter_tm=tm)
+        filter_tm=tm, filter_background=background)
     if composition is not None:
         logger.info("composition filter: %d candidates dropped (GC %d, homopolymer %d, low complexity %d)",
                     composition.dropped[3], *composition.dropped[:3])
@@ -180,6 +183,13 @@ def main(args):
         logger.info("tm filter: %d candidates dropped (below %d, above %d)", tm.dropped[2], *tm.dropped[:2])
         if args.write_tm_histogram:
             tm.write_histogram(args.write_tm_histogram)
+    if background is not None:
+        if logger.isEnabledFor(logging.INFO):       # (counting the k-mers can mean building an index)
+            logger.info("background filter: %d candidates dropped; %d background bases, %d distinct k-mers",
+                        background.dropped, background.background_bases, background.distinct_kmers())
+        if args.write_background_histogram:
+            background.write_histogram(args.write_background_histogram)
+        background.close()
     os.makedirs(args.output_dir, exist_ok=True)
     counts = []
     for di, name in enumerate(args.names):

@@ -598,6 +598,45 @@ class Probes:
             pass
 
 
+class KmerIndex:
+    """The k-mers of a background on the device (catchhip_kmer_index, not in
+    the reference): the sorted distinct canonical codes of every valid k-mer of
+    `seqs` (strings; only A, C, G, T are bases, no k-mer spans two of them) and
+    a prefix directory, for Candidates.drop_background.  Built on ctx, usable
+    from every context of ctx's device, and it outlives ctx.  n_valid: valid
+    k-mer positions; n_unique: distinct canonical codes."""
+
+    def __init__(self, ctx, seqs, k):
+        self.ctx, self.device, self.k = ctx, ctx.device, int(k)
+        self._L = ctx._L
+        self._h = ctypes.c_void_p()
+        seqs = list(seqs)
+        buf, off = _concat(seqs)
+        nv, nu = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self._L.catchhip_kmer_index_create(
+            ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), len(seqs), self.k,
+            ctypes.byref(self._h), ctypes.byref(nv), ctypes.byref(nu)))
+        self.n_valid, self.n_unique = nv.value, nu.value
+
+    def fetch(self, ctx=None):
+        """The sorted distinct canonical codes (uint64), through any context of
+        the device (default: the one it was built on)."""
+        out = np.zeros(max(self.n_unique, 1), dtype=np.uint64)
+        check(self._L.catchhip_kmer_index_fetch((ctx or self.ctx)._h, self._h, _ptr(out, c_u64p)))
+        return out[:self.n_unique]
+
+    def close(self):
+        if self._h:
+            self._L.catchhip_kmer_index_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Candidates:
     """Unique candidate probes of a Targets object, on the device
     (catchhip_candidates): sliding windows + exact de-duplication."""
@@ -694,6 +733,25 @@ class Candidates:
             _ptr(dropped, c_i64p), None if hist is None else _ptr(hist, c_u64p), ctypes.byref(nk)))
         self.n = nk.value
         return [int(x) for x in dropped], None if hist is None else [int(x) for x in hist]
+
+    def drop_background(self, index, max_hits=None, histogram=True):
+        """catchhip_candidates_drop_background (not in the reference): the
+        number of k-mers every unique candidate shares with the background
+        behind `index` (a KmerIndex of this device; catch_amd/filter/
+        background_filter.py has the rule).  With max_hits the candidates with
+        more hits are dropped, order, multiplicities and groups kept; without
+        it the list is untouched.  Returns (candidates dropped, with
+        multiplicity, the 256 bins of min(hits, 255) over the candidates the
+        call saw, with multiplicity -- None if histogram is false)."""
+        nk = ctypes.c_int64(0)
+        dropped = np.zeros(1, dtype=np.int64)
+        hist = np.zeros(256, dtype=np.uint64) if histogram else None
+        check(self.ctx._L.catchhip_candidates_drop_background(
+            self.ctx._h, self._h, index._h, 0 if max_hits is None else 1,
+            0 if max_hits is None else int(max_hits), _ptr(dropped, c_i64p),
+            None if hist is None else _ptr(hist, c_u64p), ctypes.byref(nk)))
+        self.n = nk.value
+        return int(dropped[0]), None if hist is None else [int(x) for x in hist]
 
     def multiplicities(self):
         """How many candidates equal every unique one (before a near-duplicate filter)."""

@@ -12,6 +12,7 @@ from catch_amd import engine
 from catch_amd import genome
 from catch_amd import probe
 from catch_amd.filter import candidate_probes
+from catch_amd.filter.background_filter import BackgroundFilter
 from catch_amd.filter.composition_filter import CompositionFilter
 from catch_amd.filter.duplicate_filter import DuplicateFilter
 from catch_amd.filter.fasta_filter import FastaFilter
@@ -215,7 +216,7 @@ class ProbeDesigner:
         """[pre-filters ..., DuplicateFilter | near-duplicate filter,
         SetCoverFilter] -- the filter lists bin/design.py:255-340 builds, the
         pre-filters being FastaFilter, PolyAFilter, CompositionFilter,
-        StructureFilter and TmFilter -- on plain strings:
+        StructureFilter, TmFilter and BackgroundFilter -- on plain strings:
         candidates are sliced, filtered, de-duplicated (dict, or the LSH filter
         on the device) and handed to the set cover filter without a Probe object
         per candidate (a design over 8,000 genomes spent 0.85 of its 1.0 s
@@ -259,7 +260,7 @@ class ProbeDesigner:
         """Candidates and the duplicate (or near-duplicate) filter on the device:
         one of the usual filter pairs without ranks, no --small-seq-min, every
         sequence a str at least a probe long (or skipped), and no pre-filter but
-        the poly(A), composition, structure and Tm filters (a kernel each; the
+        the poly(A), composition, structure, Tm and background filters (a kernel each; the
         FASTA filter is a look-up on the host).
         "per group": few or large groups, each its own instance; "union": many
         small groups (clusters) as one instance with group numbers; None: host
@@ -267,7 +268,8 @@ class ProbeDesigner:
         import os
         if os.environ.get("CATCHHIP_HOST_FRONT_END"):
             return None
-        if any(type(f) not in (PolyAFilter, CompositionFilter, StructureFilter, TmFilter) for f in pre_filters):
+        if any(type(f) not in (PolyAFilter, CompositionFilter, StructureFilter, TmFilter, BackgroundFilter)
+               for f in pre_filters):
             return None
         if self.allow_small_seqs:
             return None
@@ -327,11 +329,11 @@ class ProbeDesigner:
     @staticmethod
     def _strings_prefix(filters):
         """Length of the leading [FastaFilter | PolyAFilter | CompositionFilter |
-        StructureFilter | TmFilter ..., DuplicateFilter | near-duplicate filter,
+        StructureFilter | TmFilter | BackgroundFilter ..., DuplicateFilter | near-duplicate filter,
         SetCoverFilter] the strings path runs; 0: none."""
         n = 0
         while n < len(filters) and type(filters[n]) in (
-                FastaFilter, PolyAFilter, CompositionFilter, StructureFilter, TmFilter):
+                FastaFilter, PolyAFilter, CompositionFilter, StructureFilter, TmFilter, BackgroundFilter):
             n += 1
         if (len(filters) >= n + 2 and type(filters[n]) in (
                 DuplicateFilter, NearDuplicateFilterWithHammingDistance,

@@ -132,7 +132,8 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
                 filter_with_lsh_minhash=None, small_seq_skip=None,
                 small_seq_min=None, kmer_probe_map_k=None,
                 scan_mode=engine.SCAN_AUTO, stats=None, filter_polya=None,
-                filter_composition=None, filter_structure=None, filter_tm=None):
+                filter_composition=None, filter_structure=None, filter_tm=None,
+                filter_background=None):
     """Probes for every (dataset, m, e) point.
 
     datasets: list of datasets, each a list of Genome objects (one FASTA file =
@@ -145,8 +146,9 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
     datasets; filter_structure: a structure_filter.StructureFilter, after
     that one, likewise; filter_tm: a tm_filter.TmFilter, after that one,
     likewise -- every dataset passes it once, so its histogram counts a dataset's
-    candidates once, not once per grid point).  Returns {(dataset index, m, e): probe
-    sequences in the order the set cover picked them}.  stats (a dict, may be
+    candidates once, not once per grid point; filter_background: a
+    background_filter.BackgroundFilter, after that one, likewise).  Returns
+    {(dataset index, m, e): probe sequences in the order the set cover picked them}.  stats (a dict, may be
     None) receives the number of grid calls (scans of a (dataset, m)), derived
     row tables and solves."""
     mismatches = check_grid_values("mismatches", mismatches)
@@ -209,6 +211,8 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
         pre_filters.append(filter_structure)
     if filter_tm is not None:
         pre_filters.append(filter_tm)
+    if filter_background is not None:
+        pre_filters.append(filter_background)
 
     np_state0, py_state0 = np.random.get_state(), random.getstate()
     out = {}

@@ -87,8 +87,10 @@ int catchhip_pool_trim(void);
  * pass), 8 = the launches of
  * catchhip_pool_solve (one per dataset + the walk back), 9 = the flag kernel of
  * the last candidate pre-filter (catchhip_candidates_drop_polya,
- * catchhip_candidates_drop_composition, catchhip_candidates_drop_structure or
- * catchhip_candidates_drop_tm; the compaction after it is not in it).
+ * catchhip_candidates_drop_composition, catchhip_candidates_drop_structure,
+ * catchhip_candidates_drop_tm or catchhip_candidates_drop_background; the
+ * compaction after it is not in it), or the build of the last
+ * catchhip_kmer_index_create.
  * *launches = kernel launches timed. */
 int catchhip_ctx_last_kernel_ms(catchhip_ctx *ctx, int phase, double *ms,
                                 int64_t *launches);
@@ -1050,6 +1052,60 @@ int catchhip_candidates_drop_tm(catchhip_ctx *ctx, catchhip_candidates *cands, i
                                 int32_t offset_c, int32_t filter_on, int32_t lo_c,
                                 int32_t hi_c, int64_t dropped[3], uint64_t hist[128],
                                 int64_t *nkept);
+/* NOT IN THE REFERENCE (catch_amd/filter/background_filter.py states the rule and is
+ * its oracle): an index of the k-mers of a background -- the sequences probes must not
+ * match -- for catchhip_candidates_drop_background.
+ *   bytes, off[nseq + 1]: the records side by side, record i = bytes[off[i] .. off[i+1]),
+ *       off[0] = 0; only 'A', 'C', 'G', 'T' are bases, a k-mer is valid iff its k bytes
+ *       are bases and lie in ONE record; 8 <= k <= 32 (EINVAL otherwise).
+ *   code of a k-mer: 2 bits per character, (c >> 1) & 3 ('A' 0, 'C' 1, 'T' 2, 'G' 3), the
+ *       first character in the most significant of the 2k bits of a uint64_t; the
+ *       complement of a code is code ^ 2; canonical(w) = the smaller of code(w) and
+ *       code(reverse complement of w), unsigned.
+ * The index holds the sorted distinct canonical codes of the valid k-mers and a prefix
+ * directory over them, in device memory of its own (not a context's block cache): every
+ * context of ctx's device may use it, and it outlives ctx.  *n_valid = valid k-mer
+ * positions, *n_unique = distinct canonical codes (either may be NULL).  nseq = 0, records
+ * shorter than k and records without a valid k-mer are fine: an empty index.  A background
+ * of 2^32 - 4096 bytes or more is refused (EINVAL): the build sorts and scans with 32-bit
+ * counts, so 2^32 valid positions and more cannot be indexed in one piece.  The build
+ * takes about 24 bytes of scratch from ctx's pool per valid position, the index keeps
+ * 8 bytes per distinct code plus the directory (4 bytes per entry, about one entry per
+ * code).  The call synchronises before it returns; its kernels are phase 9 of
+ * catchhip_ctx_last_kernel_ms, from behind the upload on. */
+typedef struct catchhip_kmer_index catchhip_kmer_index;
+int catchhip_kmer_index_create(catchhip_ctx *ctx, const uint8_t *bytes, const int64_t *off,
+                               int64_t nseq, int32_t k, catchhip_kmer_index **index,
+                               int64_t *n_valid, int64_t *n_unique);
+/* out[0 .. n_unique): the sorted distinct canonical codes; ctx: any context of the
+ * index's device */
+int catchhip_kmer_index_fetch(catchhip_ctx *ctx, const catchhip_kmer_index *index,
+                              uint64_t *out);
+/* frees the index's device memory (waits for the device's work); NULL is fine */
+void catchhip_kmer_index_destroy(catchhip_kmer_index *index);
+/* NOT IN THE REFERENCE (catch_amd/filter/background_filter.py): the background k-mer
+ * screen on the unique candidates, as a filter and as a histogram.  w HITS iff w or its
+ * reverse complement is a valid k-mer of the background, i.e. iff canonical(w) is in the
+ * index; hits(s) = the positions j in 0 .. probe_length - k whose k-mer s[j .. j + k) is
+ * valid (k bases, bytes as they are) and hits.
+ *   filter_on != 0: candidates with hits > max_hits are dropped (max_hits >= 0, EINVAL
+ *       otherwise), as catchhip_candidates_drop_tm drops its own -- order, multiplicities
+ *       and groups kept, before any near-duplicate filter (EINVAL after one), 0 candidates
+ *       valid; nothing dropped: the list stands as it is.
+ *   filter_on == 0: the list is untouched; max_hits is not read.
+ * dropped (1 word, may be NULL) receives the candidates dropped, counted WITH
+ * multiplicity.  hist (256 words, may be NULL) receives the candidates the call saw,
+ * before it dropped any, WITH multiplicity, per hit count: bin min(hits, 255).  An empty
+ * index drops nothing and counts every candidate in bin 0.  probe_length < k: nothing is
+ * dropped and nothing counted; neither then nor with 0 candidates nor with filter_on == 0
+ * and hist == NULL is anything launched.  ctx must be the candidates' context and the
+ * index must live on its device (EINVAL otherwise); the index may have been built on
+ * another context of that device.  The flag kernel is phase 9 of
+ * catchhip_ctx_last_kernel_ms. */
+int catchhip_candidates_drop_background(catchhip_ctx *ctx, catchhip_candidates *cands,
+                                        const catchhip_kmer_index *index, int32_t filter_on,
+                                        int64_t max_hits, int64_t dropped[1],
+                                        uint64_t hist[256], int64_t *nkept);
 /* multiplicity[i] = how many candidates equal unique candidate i (the priority of
  * near_duplicate_filter.py:60-66); EINVAL once a catchhip_candidates_ndf_* call ran */
 int catchhip_candidates_multiplicities(catchhip_ctx *ctx, const catchhip_candidates *cands,

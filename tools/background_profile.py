@@ -1,0 +1,114 @@
+"""The background screen's index build and flag kernel against backgrounds of three sizes, on one resident candidate
+list.  (GPU box)
+    python tools/background_profile.py S4 1.0 [--repeats 10] [--kmer 24] [--bases 200000 8000000 64000000]
+Builds the synthetic dataset, puts all its genomes into ONE targets object and makes the unique candidates (L = 100,
+stride 50) on the device.  For every background size -- uniformly random bases, one record; by default one whose index
+fits an XCD's 4 MiB L2, one that fits the 256 MiB Infinity Cache and one well beyond it -- it
+    builds the index a few times      catchhip_kmer_index_create            (emit, scan, pair sort, distinct, directory)
+    and times three calls on the list catchhip_candidates_drop_background   (background_flag_kernel<STAGE, FILTER, HIST>)
+        filter + histogram, filter only, histogram only
+alternating, after a warm-up of each, with max_hits = L, which drops nothing, so that every repeat sees the same list:
+the walk has no early exit and every valid position is looked up whatever the threshold.  The Tm kernel (filter only)
+and the composition kernel (GC only) run in the same rounds for scale.  The times are the library's own, HIP events
+around the flag kernel alone, and for the build from behind the upload to the finished directory (phase 9 of
+catchhip_ctx_last_kernel_ms); the compaction and the read-back are outside them.  Prints the median, the least and the
+greatest of the repeats, the index's size, and the histogram (a random background shares next to nothing with the
+candidates: the look-ups are all there, the hits are not)."""
+import os
+import statistics
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from catch_amd import engine  # noqa: E402
+from catch_amd.filter.tm_filter import TmFilter  # noqa: E402
+from catch_amd.utils import synthetic  # noqa: E402
+
+PHASE_PREFILTER = 9
+
+
+def _option(name, default, many=False):
+    if name not in sys.argv:
+        return default
+    at = sys.argv.index(name) + 1
+    if not many:
+        return int(sys.argv[at])
+    out = []
+    while at < len(sys.argv) and sys.argv[at].isdigit():
+        out.append(int(sys.argv[at]))
+        at += 1
+    return out
+
+
+def _line(tag, v, n, per="candidate"):
+    print("%-34s median %.3f ms, min %.3f, max %.3f over %d calls (%.2f ns per %s)" % (
+        tag, statistics.median(v), min(v), max(v), len(v), 1e6 * statistics.median(v) / max(n, 1), per), flush=True)
+
+
+def main():
+    name = sys.argv[1] if len(sys.argv) > 1 else "S2"
+    scale = float(sys.argv[2]) if len(sys.argv) > 2 else 1.0
+    repeats = _option("--repeats", 10)
+    K = _option("--kmer", 24)
+    sizes = _option("--bases", [200_000, 8_000_000, 64_000_000], many=True)
+    L, stride = 100, 50
+    genomes = [g for grp in synthetic.dataset(name, scale=scale) for g in grp]
+    ctx = engine.Context(0)
+    targets = engine.Targets(ctx, genomes)
+    cands = engine.Candidates(ctx, targets, L, stride)
+    n = cands.n
+    print("%s x %g: %d bases, %d candidates, %d unique; K = %d, %d look-ups per candidate" % (
+        name, scale, sum(len(s) for g in genomes for s in g), cands.ncandidates, n, K, L - K + 1), flush=True)
+    tm = TmFilter()
+    q, off = tm._q(L), tm.offset_c
+    rng = np.random.default_rng(1)
+    letters = np.frombuffer(b"ACGT", dtype=np.uint8)
+    for bases in sizes:
+        background = [letters[rng.integers(0, 4, size=bases, dtype=np.uint8)].tobytes().decode("ascii")]
+        build = []
+        index = None
+        for rep in range(4):                 # (the first build is warm-up)
+            if index is not None:
+                index.close()
+            index = engine.KmerIndex(ctx, background, K)
+            t, launches = ctx.kernel_ms(PHASE_PREFILTER)
+            if rep:
+                build.append(t)
+        P = min(max(int(index.n_unique - 1).bit_length(), 8), min(2 * K, 30))
+        resident = 8 * index.n_unique + 4 * ((1 << P) + 1)
+        print("background of %d bases: %d valid positions, %d distinct k-mers, directory of 2^%d; resident %.1f MiB "
+              "(%.1f bytes per distinct k-mer), build scratch about %.1f MiB; %d launches per build" % (
+                  bases, index.n_valid, index.n_unique, P, resident / 2 ** 20, resident / max(index.n_unique, 1),
+                  24 * index.n_valid / 2 ** 20, launches), flush=True)
+        _line("  index build", build, index.n_valid, "valid position")
+        calls = [
+            ("  background filter + histogram", lambda: cands.drop_background(index, L, histogram=True)),
+            ("  background filter only", lambda: cands.drop_background(index, L, histogram=False)),
+            ("  background histogram only", lambda: cands.drop_background(index, None, histogram=True)),
+            ("  Tm filter only", lambda: cands.drop_tm(q, off, -30000, 30000, histogram=False)),
+            ("  GC only", lambda: cands.drop_composition(0, L - 1, -1, -1, 64)),
+        ]
+        ms = {tag: [] for tag, _ in calls}
+        hist = None
+        for rep in range(-2, repeats):       # (two rounds of warm-up)
+            for tag, call in calls:
+                got = call()
+                assert cands.n == n, "the timing thresholds must drop nothing"
+                t, launches = ctx.kernel_ms(PHASE_PREFILTER)
+                assert launches == 1
+                if tag.endswith("histogram only"):
+                    hist = got[1]
+                if rep >= 0:
+                    ms[tag].append(t)
+        for tag, _ in calls:
+            _line(tag, ms[tag], n)
+        filled = [b for b, v in enumerate(hist) if v]
+        print("  histogram: %d candidates, %d with hits, most hits %d" % (sum(hist), sum(hist[1:]), filled[-1]), flush=True)
+        index.close()
+    cands.close()
+    targets.close()
+
+
+if __name__ == "__main__":
+    main()
