@@ -235,6 +235,9 @@ PROTOTYPES = {
     "catchhip_kmer_index_destroy": (None, [c_vp]),
     "catchhip_candidates_drop_background": (ctypes.c_int, [
         c_vp, c_vp, c_vp, ctypes.c_int32, ctypes.c_int64, c_i64p, c_u64p, c_i64p]),
+    "catchhip_candidates_measure": (ctypes.c_int, [
+        c_vp, c_vp, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+        c_vp, ctypes.c_int32, c_u16p, c_u16p, c_u16p, c_u16p, c_u16p, c_i32p, c_u32p, c_u64p]),
     "catchhip_candidates_multiplicities": (ctypes.c_int, [c_vp, c_vp, c_u32p]),
     "catchhip_probes_from_candidates": (ctypes.c_int, [
         c_vp, c_vp, c_i32p, c_i32p, ctypes.c_int64, ctypes.c_int32, c_vpp]),

@@ -38,19 +38,6 @@
 #define BG_CHUNK 64u                 // end positions per thread of the emit kernel
 #define BG_MAX_BYTES 0xfffff000ull   // the scans count in 32 bits
 
-struct catchhip_kmer_index {
-    int device = 0;
-    i32 k = 0;
-    u64 n_valid = 0, n_unique = 0;
-    u32 P = 8;                       // directory bits
-    u64 *codes = nullptr;            // n_unique (at least one word allocated)
-    u32 *dir = nullptr;              // 2^P + 1
-    ~catchhip_kmer_index() {
-        if (codes) (void)hipFree(codes);
-        if (dir) (void)hipFree(dir);
-    }
-};
-
 // ---- the index --------------------------------------------------------------------------------------------------
 // WRITE = false: cnt[chunk] = valid k-mers that END in the chunk's positions; WRITE = true: their canonical codes from
 // keys[at[chunk]] on.  A k-mer never spans two records: the run of bases starts again at every record start.

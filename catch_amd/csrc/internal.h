@@ -360,6 +360,20 @@ struct catchhip_candidates {
 // upos, mult and (grouped) ugrp compacted, nuniq updated (candidates.hip: cand_scan + cand_compact_kernel)
 int chip_candidates_keep_flagged(catchhip_ctx *ctx, catchhip_candidates *C, DevBuf<u32> &flag, i64 *nkept);
 
+// The k-mers of a background on the device (background.hip builds it and says what it holds; measure.hip reads it)
+struct catchhip_kmer_index {
+    int device = 0;
+    i32 k = 0;
+    u64 n_valid = 0, n_unique = 0;
+    u32 P = 8;                       // directory bits
+    u64 *codes = nullptr;            // n_unique (at least one word allocated)
+    u32 *dir = nullptr;              // 2^P + 1
+    ~catchhip_kmer_index() {
+        if (codes) (void)hipFree(codes);
+        if (dir) (void)hipFree(dir);
+    }
+};
+
 // MinHash signatures of sequences on the device (cluster.hip; linkage.hip reads them)
 struct catchhip_sigs {
     catchhip_ctx *ctx = nullptr;

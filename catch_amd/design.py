@@ -34,7 +34,12 @@ candidates by their nearest-neighbour melting temperature and
 --background-kmer, --background-max-hits; nor these) drops candidates that
 share k-mers with a host genome or another background and
 --write-background-histogram writes how many share how many, one filter right
-after that one (catch_amd/filter/background_filter.py has the rule).
+after that one (catch_amd/filter/background_filter.py has the rule);
+--write-candidate-profile (nor this) measures the candidates instead of
+judging them, one QualityProfile right after the poly(A) filter that drops
+nothing (catch_amd/filter/quality.py has the quantities), and
+--write-probe-report (nor this) writes what the designed probes are like, the
+report of catch_amd.probe_report for the output FASTA.
 --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
@@ -47,7 +52,7 @@ import sys
 
 from catch_amd.filter import background_filter, composition_filter
 from catch_amd.filter import duplicate_filter, near_duplicate_filter
-from catch_amd.filter import probe_designer, set_cover_filter
+from catch_amd.filter import probe_designer, quality, set_cover_filter
 from catch_amd.filter import structure_filter, tm_filter
 from catch_amd.utils import seq_io
 
@@ -140,6 +145,15 @@ def parse_args(argv=None, args_type="basic"):
     structure_filter.add_arguments(p)       # --max-hairpin-stem, --hairpin-min-loop, --max-self-dimer (not in the reference)
     tm_filter.add_arguments(p)              # --filter-tm, --tm-..., --write-tm-histogram (not in the reference)
     background_filter.add_arguments(p)      # --background, --background-..., --write-background-histogram (not in the reference)
+    quality.add_arguments(p)                # --write-candidate-profile (not in the reference)
+    p.add_argument("--write-probe-report", metavar="FILE",
+                   help="write what the designed probes are like to FILE: the "
+                        "report python -m catch_amd.probe_report -f writes "
+                        "for the output FASTA with the same parameters and "
+                        "thresholds, byte for byte -- the records written to "
+                        "-o, in their order, adapters and N expansion "
+                        "included (design without adapters to judge the "
+                        "target part alone)")
     p.add_argument("--add-reverse-complements", dest="add_reverse_complements",
                    action="store_true",
                    help="add the reverse complement of each probe to the output")
@@ -429,6 +443,9 @@ def main(args):
                             "lead to many probes being filtered"),
                            polya_mismatches)
         filters.append(polya_filter.PolyAFilter(polya_length, polya_mismatches))
+    profile = quality.from_args(args)
+    if profile is not None:         # --write-candidate-profile: looks at what the filters below are about to judge
+        filters.append(profile)
     composition = composition_filter.from_args(args)
     if composition is not None:     # one filter for the three rules: a function of the candidate alone, like poly(A)
         filters.append(composition)
@@ -511,6 +528,8 @@ def main(args):
                                  if args.cluster_and_design_separately
                                  else None))
     pb.design()
+    if profile is not None:
+        quality.finish(profile, args, logger)
     if composition is not None:
         logger.info("composition filter: %d candidates dropped (GC %d, homopolymer %d, low complexity %d)",
                     composition.dropped[3], *composition.dropped[:3])
@@ -554,6 +573,14 @@ def main(args):
             write_coverage_curve(args.write_coverage_curve, names, scf)
     if args.write_probe_fasta:
         seq_io.write_probe_fasta(pb.final_probes, args.write_probe_fasta)
+    if args.write_probe_report:
+        # the records of the output FASTA as probe_report would read them back, judged with this run's options
+        from catch_amd import probe_report
+        judge = probe_report.Judge(args)
+        try:
+            probe_report.write_report(judge, probe_report.records_of_probes(pb.final_probes), args.write_probe_report)
+        finally:
+            judge.close()
     if (args.print_analysis or args.write_analysis_to_tsv or
             args.write_sliding_window_coverage or
             args.write_probe_map_counts_to_tsv or

@@ -18,7 +18,7 @@ import os
 import sys
 
 from catch_amd import grid
-from catch_amd.filter import background_filter, composition_filter, structure_filter, tm_filter
+from catch_amd.filter import background_filter, composition_filter, quality, structure_filter, tm_filter
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.design_grid")
@@ -86,6 +86,7 @@ def parse_args(argv=None):
     structure_filter.add_arguments(p)       # likewise
     tm_filter.add_arguments(p)              # likewise
     background_filter.add_arguments(p)      # likewise
+    quality.add_arguments(p)                # likewise (--write-candidate-profile)
     p.add_argument("--small-seq-skip", type=int)
     p.add_argument("--small-seq-min", type=int)
     p.add_argument("--kmer-probe-map-k", type=int)
@@ -163,6 +164,7 @@ def main(args):
     structure = structure_filter.from_args(args)
     tm = tm_filter.from_args(args)
     background = background_filter.from_args(args)
+    profile = quality.from_args(args)
     got = grid.design_grid(
         datasets, args.grid_mismatches, args.grid_cover_extension,
         probe_length=args.probe_length, probe_stride=args.probe_stride,
@@ -172,7 +174,9 @@ def main(args):
         small_seq_skip=args.small_seq_skip, small_seq_min=args.small_seq_min,
         kmer_probe_map_k=args.kmer_probe_map_k, filter_polya=args.filter_polya,
         filter_composition=composition, filter_structure=structure,
-        filter_tm=tm, filter_background=background)
+        filter_tm=tm, filter_background=background, candidate_profile=profile)
+    if profile is not None:
+        quality.finish(profile, args, logger)
     if composition is not None:
         logger.info("composition filter: %d candidates dropped (GC %d, homopolymer %d, low complexity %d)",
                     composition.dropped[3], *composition.dropped[:3])

@@ -753,6 +753,61 @@ class Candidates:
         self.n = nk.value
         return int(dropped[0]), None if hist is None else [int(x) for x in hist]
 
+    MEASURE_FAMILIES = {"composition": (1, ("gc", "homopolymer", "dust")), "structure": (2, ("stem", "dimer")),
+                        "tm": (4, ("tm_c",)), "hits": (8, ("hits",))}
+
+    def measure(self, what=("composition", "structure"), min_loop=3, dust_window=64, tm=None, index=None,
+                values=False, histograms=True):
+        """catchhip_candidates_measure (not in the reference): the value behind
+        every rule, for every unique candidate (catch_amd/filter/quality.py has
+        the definitions); the list is left exactly as it was.  what: the
+        families to compute, of "composition" (gc, homopolymer, dust),
+        "structure" (stem, dimer), "tm" (tm_c; tm = (q, offset_c) as for
+        drop_tm) and "hits" (index = a KmerIndex of this device); none is
+        valid.  Returns a dict: with values, a NumPy array per quantity of the
+        families asked for (uint16; tm_c int32, None where the candidates have
+        fewer than 2 characters; hits uint32); with histograms, under
+        "histograms", {quantity: 1,280 bins of min(value, 1279), with
+        multiplicity} for the quantities of "composition" and "structure"."""
+        if isinstance(what, str):
+            what = (what,)
+        what = list(what)
+        for w in what:
+            if w not in self.MEASURE_FAMILIES:
+                raise ValueError("measure: unknown family %r (one of %s)" % (w, ", ".join(self.MEASURE_FAMILIES)))
+        if "tm" in what and tm is None:
+            raise ValueError("measure: \"tm\" needs tm = (q, offset_c)")
+        if "hits" in what and index is None:
+            raise ValueError("measure: \"hits\" needs an index")
+        mask = 0
+        for w in what:
+            mask |= self.MEASURE_FAMILIES[w][0]
+        n = max(self.n, 1)
+        arrays = {}
+        if values:
+            for w in what:
+                for name in self.MEASURE_FAMILIES[w][1]:
+                    arrays[name] = np.zeros(n, dtype={"tm_c": np.int32, "hits": np.uint32}.get(name, np.uint16))
+        hist = np.zeros(5 * 1280, dtype=np.uint64) if histograms else None
+        q, offset_c = (0, 0) if "tm" not in what else (int(tm[0]), int(tm[1]))
+
+        def p(name, t):
+            return _ptr(arrays[name], t) if name in arrays else None
+        check(self.ctx._L.catchhip_candidates_measure(
+            self.ctx._h, self._h, mask, int(min_loop), int(dust_window), q, offset_c,
+            index._h if "hits" in what else None, 1 if values else 0,
+            p("gc", c_u16p), p("homopolymer", c_u16p), p("dust", c_u16p), p("stem", c_u16p), p("dimer", c_u16p),
+            p("tm_c", c_i32p), p("hits", c_u32p), None if hist is None else _ptr(hist, c_u64p)))
+        out = {name: a[:self.n] for name, a in arrays.items()}
+        if "tm_c" in out and self.L < 2:
+            out["tm_c"] = None
+        if histograms:
+            names = ("gc", "homopolymer", "dust", "stem", "dimer")
+            asked = [name for w in what for name in self.MEASURE_FAMILIES[w][1]]
+            out["histograms"] = {name: hist[1280 * k:1280 * (k + 1)].astype(np.int64)
+                                 for k, name in enumerate(names) if name in asked}
+        return out
+
     def multiplicities(self):
         """How many candidates equal every unique one (before a near-duplicate filter)."""
         out = np.zeros(max(self.n, 1), dtype=np.uint32)

@@ -19,6 +19,7 @@ from catch_amd.filter.fasta_filter import FastaFilter
 from catch_amd.filter.near_duplicate_filter import (
     NearDuplicateFilterWithHammingDistance, NearDuplicateFilterWithMinHash)
 from catch_amd.filter.polya_filter import PolyAFilter
+from catch_amd.filter.quality import QualityProfile
 from catch_amd.filter.set_cover_filter import SetCoverFilter
 from catch_amd.filter.structure_filter import StructureFilter
 from catch_amd.filter.tm_filter import TmFilter
@@ -215,8 +216,9 @@ class ProbeDesigner:
     def _design_on_strings(self, genomes, filters):
         """[pre-filters ..., DuplicateFilter | near-duplicate filter,
         SetCoverFilter] -- the filter lists bin/design.py:255-340 builds, the
-        pre-filters being FastaFilter, PolyAFilter, CompositionFilter,
-        StructureFilter, TmFilter and BackgroundFilter -- on plain strings:
+        pre-filters being FastaFilter, PolyAFilter, QualityProfile (which only
+        measures), CompositionFilter, StructureFilter, TmFilter and
+        BackgroundFilter -- on plain strings:
         candidates are sliced, filtered, de-duplicated (dict, or the LSH filter
         on the device) and handed to the set cover filter without a Probe object
         per candidate (a design over 8,000 genomes spent 0.85 of its 1.0 s
@@ -260,7 +262,8 @@ class ProbeDesigner:
         """Candidates and the duplicate (or near-duplicate) filter on the device:
         one of the usual filter pairs without ranks, no --small-seq-min, every
         sequence a str at least a probe long (or skipped), and no pre-filter but
-        the poly(A), composition, structure, Tm and background filters (a kernel each; the
+        the poly(A), composition, structure, Tm and background filters and the
+        candidate profile (a kernel each; the
         FASTA filter is a look-up on the host).
         "per group": few or large groups, each its own instance; "union": many
         small groups (clusters) as one instance with group numbers; None: host
@@ -268,7 +271,7 @@ class ProbeDesigner:
         import os
         if os.environ.get("CATCHHIP_HOST_FRONT_END"):
             return None
-        if any(type(f) not in (PolyAFilter, CompositionFilter, StructureFilter, TmFilter, BackgroundFilter)
+        if any(type(f) not in (PolyAFilter, QualityProfile, CompositionFilter, StructureFilter, TmFilter, BackgroundFilter)
                for f in pre_filters):
             return None
         if self.allow_small_seqs:
@@ -328,12 +331,12 @@ class ProbeDesigner:
 
     @staticmethod
     def _strings_prefix(filters):
-        """Length of the leading [FastaFilter | PolyAFilter | CompositionFilter |
+        """Length of the leading [FastaFilter | PolyAFilter | QualityProfile | CompositionFilter |
         StructureFilter | TmFilter | BackgroundFilter ..., DuplicateFilter | near-duplicate filter,
         SetCoverFilter] the strings path runs; 0: none."""
         n = 0
         while n < len(filters) and type(filters[n]) in (
-                FastaFilter, PolyAFilter, CompositionFilter, StructureFilter, TmFilter, BackgroundFilter):
+                FastaFilter, PolyAFilter, QualityProfile, CompositionFilter, StructureFilter, TmFilter, BackgroundFilter):
             n += 1
         if (len(filters) >= n + 2 and type(filters[n]) in (
                 DuplicateFilter, NearDuplicateFilterWithHammingDistance,

@@ -201,7 +201,8 @@ def add_arguments(p):
                         "what is left")
     p.add_argument("--hairpin-min-loop", type=int, default=None, metavar="P",
                    help="least number of unpaired characters between the two "
-                        "arms of a --max-hairpin-stem stem (default 3)")
+                        "arms of a --max-hairpin-stem stem, and of the stems "
+                        "--write-candidate-profile measures (default 3)")
     p.add_argument("--max-self-dimer", type=int, metavar="D",
                    help="drop candidate probes of which two copies can "
                         "anneal over more than D consecutive base pairs "
@@ -218,7 +219,7 @@ def from_args(args, error=_value_error):
     if args.max_hairpin_stem is not None and args.max_hairpin_stem < 1:
         error("--max-hairpin-stem must be at least 1, not %d" % args.max_hairpin_stem)
     if args.hairpin_min_loop is not None:
-        if args.max_hairpin_stem is None:
+        if args.max_hairpin_stem is None and getattr(args, "write_candidate_profile", None) is None:
             error("--hairpin-min-loop needs --max-hairpin-stem")
         if args.hairpin_min_loop < 0:
             error("--hairpin-min-loop must be at least 0, not %d" % args.hairpin_min_loop)

@@ -133,7 +133,7 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
                 small_seq_min=None, kmer_probe_map_k=None,
                 scan_mode=engine.SCAN_AUTO, stats=None, filter_polya=None,
                 filter_composition=None, filter_structure=None, filter_tm=None,
-                filter_background=None):
+                filter_background=None, candidate_profile=None):
     """Probes for every (dataset, m, e) point.
 
     datasets: list of datasets, each a list of Genome objects (one FASTA file =
@@ -147,7 +147,9 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
     that one, likewise; filter_tm: a tm_filter.TmFilter, after that one,
     likewise -- every dataset passes it once, so its histogram counts a dataset's
     candidates once, not once per grid point; filter_background: a
-    background_filter.BackgroundFilter, after that one, likewise).  Returns
+    background_filter.BackgroundFilter, after that one, likewise;
+    candidate_profile: a quality.QualityProfile, which only measures, right
+    after the poly(A) filter -- once per dataset, like the Tm histogram).  Returns
     {(dataset index, m, e): probe sequences in the order the set cover picked them}.  stats (a dict, may be
     None) receives the number of grid calls (scans of a (dataset, m)), derived
     row tables and solves."""
@@ -205,6 +207,8 @@ def design_grid(datasets, mismatches, cover_extensions, probe_length=100,
                             "lead to many probes being filtered"),
                            polya_mismatches)
         pre_filters.append(polya_filter.PolyAFilter(polya_length, polya_mismatches))
+    if candidate_profile is not None:
+        pre_filters.append(candidate_profile)
     if filter_composition is not None:
         pre_filters.append(filter_composition)
     if filter_structure is not None:

@@ -81,8 +81,10 @@ def write_probe_fasta(probes, out_fn):
     last 10 hex digits of sha224(sequence), catch/probe.py:303-322)."""
     with open(out_fn, "w") as f:
         for p in probes:
-            header = p.header
-            if not header:
-                header = "probe_" + hashlib.sha224(p.seq_str.encode()).hexdigest()[-10:]
-            f.write(">" + header + "\n")
+            f.write(">" + probe_header(p) + "\n")
             f.write(p.seq_str + "\n")
+
+
+def probe_header(p):
+    """The name write_probe_fasta gives a probe."""
+    return p.header or "probe_" + hashlib.sha224(p.seq_str.encode()).hexdigest()[-10:]

@@ -1106,6 +1106,46 @@ int catchhip_candidates_drop_background(catchhip_ctx *ctx, catchhip_candidates *
                                         const catchhip_kmer_index *index, int32_t filter_on,
                                         int64_t max_hits, int64_t dropped[1],
                                         uint64_t hist[256], int64_t *nkept);
+/* NOT IN THE REFERENCE (catch_amd/filter/quality.py states the five quantities and is
+ * their oracle): the value behind every candidate rule, for every unique candidate, as
+ * per-candidate arrays and as histograms.  The list is only read: order, multiplicities
+ * and groups stay exactly as they were.  Before any near-duplicate filter (EINVAL after
+ * one), 0 candidates valid.  Only the bytes 'A', 'C', 'G', 'T' are bases.
+ *   what: a mask of the families to compute; 0 is valid and computes nothing.
+ *     CATCHHIP_MEASURE_COMPOSITION  gc (number of 'G' or 'C'), homopolymer (longest run of
+ *         one base) and dust (the smallest dust_x10 at which
+ *         catchhip_candidates_drop_composition keeps the candidate: the maximum over its
+ *         windows with T >= 2 of ceil(10 S / (T - 1)), 0 without one; 3 <= dust_window <= 256)
+ *     CATCHHIP_MEASURE_STRUCTURE    stem (the base pairs of the longest hairpin stem around
+ *         a loop of at least min_loop >= 0 characters: catchhip_candidates_drop_structure
+ *         drops the candidate iff stem > max_stem) and dimer (the longest run of
+ *         consecutive base pairs of two copies: dropped iff dimer > max_dimer); 0 if none
+ *     CATCHHIP_MEASURE_TM           tm_c of catchhip_candidates_drop_tm with the same q (<= -8200)
+ *         and offset_c, clamped to +-(2^31 - 1); CATCHHIP_MEASURE_NO_TM for probe_length < 2
+ *     CATCHHIP_MEASURE_HITS         hits of catchhip_candidates_drop_background against
+ *         index (of ctx's device, EINVAL otherwise; not read without this bit); 0 for
+ *         probe_length < k
+ *   want_values != 0: gc, homopolymer, dust, stem, dimer, tm_c and hits (host arrays of one
+ *       entry per unique candidate) receive the values of the families asked for; the
+ *       arrays of the other families are not touched and may be NULL.  want_values == 0:
+ *       none of the seven is read.
+ *   hist (5 * 1280 words, may be NULL) receives five histograms over the candidates, WITH
+ *       multiplicity: words [1280 q, 1280 q + 1280) for q = gc, homopolymer, dust, stem,
+ *       dimer in this order, bin min(value, 1279); the histograms of a family not asked
+ *       for are 0.  Tm and hits have histograms of their own in their filter calls.
+ * probe_length > 65,535 is refused (EINVAL): the five values are 16-bit.  The kernels are
+ * phase 9 of catchhip_ctx_last_kernel_ms. */
+#define CATCHHIP_MEASURE_COMPOSITION 1u
+#define CATCHHIP_MEASURE_STRUCTURE 2u
+#define CATCHHIP_MEASURE_TM 4u
+#define CATCHHIP_MEASURE_HITS 8u
+#define CATCHHIP_MEASURE_NO_TM (-2147483647 - 1)
+int catchhip_candidates_measure(catchhip_ctx *ctx, const catchhip_candidates *cands,
+                                uint32_t what, int32_t min_loop, int32_t dust_window,
+                                int64_t q, int32_t offset_c, const catchhip_kmer_index *index,
+                                int32_t want_values, uint16_t *gc, uint16_t *homopolymer,
+                                uint16_t *dust, uint16_t *stem, uint16_t *dimer,
+                                int32_t *tm_c, uint32_t *hits, uint64_t *hist);
 /* multiplicity[i] = how many candidates equal unique candidate i (the priority of
  * near_duplicate_filter.py:60-66); EINVAL once a catchhip_candidates_ndf_* call ran */
 int catchhip_candidates_multiplicities(catchhip_ctx *ctx, const catchhip_candidates *cands,
