@@ -233,6 +233,9 @@ PROTOTYPES = {
         c_vp, c_u8p, c_i64p, ctypes.c_int64, ctypes.c_int32, c_vpp, c_i64p, c_i64p]),
     "catchhip_kmer_index_fetch": (ctypes.c_int, [c_vp, c_vp, c_u64p]),
     "catchhip_kmer_index_destroy": (None, [c_vp]),
+    "catchhip_kmer_index_create_tolerant": (ctypes.c_int, [
+        c_vp, c_u8p, c_i64p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_vpp, c_i64p, c_i64p]),
+    "catchhip_kmer_index_fetch_view": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int32, c_u64p]),
     "catchhip_candidates_drop_background": (ctypes.c_int, [
         c_vp, c_vp, c_vp, ctypes.c_int32, ctypes.c_int64, c_i64p, c_u64p, c_i64p]),
     "catchhip_candidates_measure": (ctypes.c_int, [

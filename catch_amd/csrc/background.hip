@@ -26,9 +26,20 @@
 // "dropped".  Bin 0 and "dropped" are one address each for most threads, so they are summed over the wave first and
 // added once per wave; the other bins take LDS atomics.  After a barrier thread t adds counter t, if it is not zero, to
 // one of BG_SLOTS copies in global memory, which the host adds up.  No thread returns before the barrier.
+//
+// Mismatches (catchhip_kmer_index_create_tolerant, mismatches = M in 1, 2, K >= 8 (M + 1)): a valid k-mer hits iff some
+// code of the index lies within M characters of fwd or of rc.  Block b = 0 .. M of a k-mer is its characters
+// [s_b, s_(b+1)), s_b = floor(b K / (M + 1)); two k-mers within M mismatches agree in one block.  The index then holds
+// M + 1 VIEWS: view 0 is codes / dir as above, view b the same codes rotated left by 2 s_b bits inside their 2K bits
+// (block b leads), sorted again, with a directory of P_b = clamp(ceil(log2(n_unique)), 8, min(2 (s_(b+1) - s_b), 30))
+// bits -- never finer than the block (view 0's P is capped the same way), so ONE bucket holds every code that agrees
+// with a query in block b.  kmer_rotate_kernel, chip_radix_sort_pairs and kmer_dir_kernel build a view: no second emit,
+// no second distinct pass (a rotation is a bijection).  background_flag_tolerant_kernel is background_flag_kernel with
+// kmer_lookup.h's tolerant look-up; an index with M = 0 launches background_flag_kernel as before.
 #include "internal.h"
 #include "wave.h"
 #include "stage.h"
+#include "kmer_lookup.h"
 
 #define BG_BINS 256u
 #define BG_WORDS 257u                // the bins, dropped
@@ -93,6 +104,27 @@ kmer_dir_kernel(const u64 *__restrict__ codes, u32 n, u32 shift, u32 nprefix, u3
     for (u32 p = first; p <= last; ++p) dir[p] = i;
 }
 
+// view b of a tolerant index, unsorted: every code rotated left by rot bits (0 < rot < bits) inside its `bits` bits
+__global__ void __launch_bounds__(256)
+kmer_rotate_kernel(const u64 *__restrict__ codes, u32 n, u32 rot, u32 bits, u64 mask, u64 *__restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = ((codes[i] << rot) | (codes[i] >> (bits - rot))) & mask;
+}
+
+// the directory of one view: P = clamp(ceil(log2 n), 8, min(pcap, 30)) bits over the sorted codes (pcap >= 8)
+static int kmer_view_dir(catchhip_ctx *ctx, const u64 *codes, u32 n, u32 K, u32 pcap, u32 *P_out, u32 **dir_out) {
+    int P = ceil_log2_u64(n);
+    const int pmax = (int)pcap < 30 ? (int)pcap : 30;
+    P = P < 8 ? 8 : P > pmax ? pmax : P;
+    *P_out = (u32)P;
+    const u32 nprefix = (u32)1 << P;
+    HIP_TRY(hipMalloc((void **)dir_out, sizeof(u32) * ((size_t)nprefix + 1)));
+    hipLaunchKernelGGL(kmer_dir_kernel, dim3((unsigned)div_up((i64)n + 1, 256)), dim3(256), 0, ctx->stream, codes, n,
+                       2 * K - (u32)P, nprefix, *dir_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 static int kmer_index_build(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, i64 nseq, catchhip_kmer_index *X) {
     hipStream_t s = ctx->stream;
     const u32 K = (u32)X->k;
@@ -154,28 +186,54 @@ static int kmer_index_build(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, 
         HIP_TRY(hipMemsetAsync(X->codes, 0, sizeof(u64), s));
     }
     X->n_unique = n_unique;
-    int P = ceil_log2_u64(n_unique);
-    const int pmax = 2 * (int)K < 30 ? 2 * (int)K : 30;
-    P = P < 8 ? 8 : P > pmax ? pmax : P;
-    X->P = (u32)P;
-    const u32 nprefix = (u32)1 << P;
-    HIP_TRY(hipMalloc((void **)&X->dir, sizeof(u32) * ((size_t)nprefix + 1)));
-    hipLaunchKernelGGL(kmer_dir_kernel, dim3((unsigned)div_up((i64)n_unique + 1, 256)), dim3(256), 0, s,
-                       (const u64 *)X->codes, n_unique, 2 * K - (u32)P, nprefix, X->dir);
-    HIP_TRY(hipGetLastError());
+    const u32 M = (u32)X->mismatches;
+    // view 0: the codes as they are.  A tolerant index keeps every directory no finer than its view's block
+    TRY(kmer_view_dir(ctx, X->codes, n_unique, K, M ? 2 * (K / (M + 1)) : 2 * K, &X->P, &X->dir));
     tm.launch();
+    for (u32 b = 1; b <= M; ++b) {
+        const u32 s0 = b * K / (M + 1), s1 = (b + 1) * K / (M + 1);
+        X->view_start[b - 1] = s0;
+        HIP_TRY(hipMalloc((void **)&X->view_codes[b - 1], sizeof(u64) * (size_t)(n_unique ? n_unique : 1)));
+        if (n_unique) {
+            // rotate, sort again (a bijection: the list stays distinct), keep; the scratch is the first sort's
+            DevBuf<u32> vals, vals_alt;
+            TRY(keys.reserve(n_unique));
+            TRY(vals.alloc((size_t)n_unique + 1));
+            HIP_TRY(hipMemsetAsync(vals.p, 0, sizeof(u32) * ((size_t)n_unique + 1), s));
+            hipLaunchKernelGGL(kmer_rotate_kernel, dim3((unsigned)div_up((i64)n_unique, 256)), dim3(256), 0, s,
+                               (const u64 *)X->codes, n_unique, 2 * s0, 2 * K, mask, keys.p);
+            HIP_TRY(hipGetLastError());
+            TRY(chip_radix_sort_pairs(ctx, keys, keys_alt, vals, vals_alt, n_unique, 2 * (int)K));
+            HIP_TRY(hipMemcpyAsync(X->view_codes[b - 1], keys.p, sizeof(u64) * (size_t)n_unique, hipMemcpyDeviceToDevice, s));
+            tm.launch(1 + 3 * ((2 * K + 7) / 8));
+            HIP_TRY(hipStreamSynchronize(s));                  // (the scratch goes back to the pool below)
+        } else {
+            HIP_TRY(hipMemsetAsync(X->view_codes[b - 1], 0, sizeof(u64), s));
+        }
+        TRY(kmer_view_dir(ctx, X->view_codes[b - 1], n_unique, K, 2 * (s1 - s0), &X->view_P[b - 1], &X->view_dir[b - 1]));
+        tm.launch();
+    }
     tm.stop();
     HIP_TRY(hipStreamSynchronize(s));
     tm.finish();
     return 0;
 }
 
-extern "C" int catchhip_kmer_index_create(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, i64 nseq, i32 k,
-                                          catchhip_kmer_index **out, i64 *n_valid, i64 *n_unique) {
+static int kmer_index_create(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, i64 nseq, i32 k, i32 mismatches,
+                             catchhip_kmer_index **out, i64 *n_valid, i64 *n_unique) {
     ARG_CHECK(ctx && out && off && nseq >= 0);
     *out = nullptr;
     if (k < 8 || k > 32) {
         chip_set_error("kmer_index_create: k must lie in 8 .. 32 (got %d)", (int)k);
+        return CATCHHIP_EINVAL;
+    }
+    if (mismatches < 0 || mismatches > 2) {
+        chip_set_error("kmer_index_create: mismatches must lie in 0 .. 2 (got %d)", (int)mismatches);
+        return CATCHHIP_EINVAL;
+    }
+    if (k < 8 * (mismatches + 1)) {
+        chip_set_error("kmer_index_create: %d mismatches need k >= %d, blocks of 8 characters at least (got k = %d)",
+                       (int)mismatches, 8 * ((int)mismatches + 1), (int)k);
         return CATCHHIP_EINVAL;
     }
     if (nseq >= ((i64)1 << 31)) {
@@ -197,6 +255,7 @@ extern "C" int catchhip_kmer_index_create(catchhip_ctx *ctx, const u8 *bytes, co
     std::unique_ptr<catchhip_kmer_index> X(new catchhip_kmer_index());
     X->device = ctx->device;
     X->k = k;
+    X->mismatches = mismatches;
     TRY(kmer_index_build(ctx, bytes, off, nseq, X.get()));
     if (n_valid) *n_valid = (i64)X->n_valid;
     if (n_unique) *n_unique = (i64)X->n_unique;
@@ -204,14 +263,34 @@ extern "C" int catchhip_kmer_index_create(catchhip_ctx *ctx, const u8 *bytes, co
     return 0;
 }
 
-extern "C" int catchhip_kmer_index_fetch(catchhip_ctx *ctx, const catchhip_kmer_index *X, u64 *out) {
+extern "C" int catchhip_kmer_index_create(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, i64 nseq, i32 k,
+                                          catchhip_kmer_index **out, i64 *n_valid, i64 *n_unique) {
+    return kmer_index_create(ctx, bytes, off, nseq, k, 0, out, n_valid, n_unique);
+}
+
+extern "C" int catchhip_kmer_index_create_tolerant(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, i64 nseq, i32 k,
+                                                   i32 mismatches, catchhip_kmer_index **out, i64 *n_valid,
+                                                   i64 *n_unique) {
+    return kmer_index_create(ctx, bytes, off, nseq, k, mismatches, out, n_valid, n_unique);
+}
+
+extern "C" int catchhip_kmer_index_fetch_view(catchhip_ctx *ctx, const catchhip_kmer_index *X, i32 view, u64 *out) {
     ARG_CHECK(ctx && X && ctx->device == X->device);
+    if (view < 0 || view > X->mismatches) {
+        chip_set_error("kmer_index_fetch_view: the index has the views 0 .. %d (got %d)", (int)X->mismatches, (int)view);
+        return CATCHHIP_EINVAL;
+    }
     if (X->n_unique == 0) return 0;
     ARG_CHECK(out);
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(out, X->codes, sizeof(u64) * (size_t)X->n_unique, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, view ? X->view_codes[view - 1] : X->codes, sizeof(u64) * (size_t)X->n_unique,
+                           hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+extern "C" int catchhip_kmer_index_fetch(catchhip_ctx *ctx, const catchhip_kmer_index *X, u64 *out) {
+    return catchhip_kmer_index_fetch_view(ctx, X, 0, out);
 }
 
 extern "C" void catchhip_kmer_index_destroy(catchhip_kmer_index *X) {
@@ -221,12 +300,12 @@ extern "C" void catchhip_kmer_index_destroy(catchhip_kmer_index *X) {
 }
 
 // ---- the filter ---------------------------------------------------------------------------------------------------
-template <bool STAGE, bool FILTER, bool HIST>
-__global__ void __launch_bounds__(256)
-background_flag_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ upos, const u32 *__restrict__ mult, u32 n, u32 L,
-                       u32 K, u64 mask, u32 rc_shift, const u64 *__restrict__ codes, const u32 *__restrict__ dir,
-                       u32 dir_shift, u32 max_hits, u32 nchunk, u32 pitch_dw, u32 extra_off_dw, u32 *__restrict__ flag,
-                       u64 *__restrict__ totals) {
+// M = 0: the exact look-up in view 0; M > 0: the tolerant one in the views 0 .. M
+template <int M, bool STAGE, bool FILTER, bool HIST>
+__device__ __forceinline__ void
+background_flag_body(const u8 *__restrict__ bytes, const u32 *__restrict__ upos, const u32 *__restrict__ mult, u32 n, u32 L,
+                     u32 K, u64 mask, u32 rc_shift, const KmerViews &views, u32 max_hits, u32 nchunk, u32 pitch_dw,
+                     u32 extra_off_dw, u32 *__restrict__ flag, u64 *__restrict__ totals) {
     extern __shared__ u32 bg_lds[];
     const u32 rows = blockDim.x, r = threadIdx.x;
     const u32 i = blockIdx.x * rows + r;
@@ -247,16 +326,8 @@ background_flag_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ upo
             rc = (rc >> 2) | ((code ^ 2ull) << rc_shift);
             run = is_base(c) ? run + 1u : 0u;
             if (run >= K) {
-                const u64 canon = fwd < rc ? fwd : rc;
-                const u32 b = (u32)(canon >> dir_shift);
-                u32 lo = dir[b], hi = dir[b + 1u];
-                while (hi - lo > 4u) {                        // (canon, if it is there at all, stays inside [lo, hi))
-                    const u32 mid = (lo + hi) >> 1;
-                    if (codes[mid] <= canon) lo = mid; else hi = mid;
-                }
-                u32 hit = 0;
-                for (u32 t = lo; t < hi; ++t) hit |= codes[t] == canon ? 1u : 0u;
-                hits += hit;
+                if constexpr (M == 0) hits += kmer_lookup_exact(fwd, rc, views.codes[0], views.dir[0], views.dir_shift[0]);
+                else hits += kmer_lookup_tolerant<M>(fwd, rc, mask, 2u * K, views);
             }
         }
         const u32 m = mult[i];
@@ -283,6 +354,31 @@ background_flag_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ upo
     }
 }
 
+template <bool STAGE, bool FILTER, bool HIST>
+__global__ void __launch_bounds__(256)
+background_flag_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ upos, const u32 *__restrict__ mult, u32 n, u32 L,
+                       u32 K, u64 mask, u32 rc_shift, const u64 *__restrict__ codes, const u32 *__restrict__ dir,
+                       u32 dir_shift, u32 max_hits, u32 nchunk, u32 pitch_dw, u32 extra_off_dw, u32 *__restrict__ flag,
+                       u64 *__restrict__ totals) {
+    KmerViews views = {};
+    views.codes[0] = codes;
+    views.dir[0] = dir;
+    views.dir_shift[0] = dir_shift;
+    background_flag_body<0, STAGE, FILTER, HIST>(bytes, upos, mult, n, L, K, mask, rc_shift, views, max_hits, nchunk,
+                                                 pitch_dw, extra_off_dw, flag, totals);
+}
+
+// the same kernel against a tolerant index (M = 1, 2): per position 2 (M + 1) buckets instead of one (kmer_lookup.h)
+template <int M, bool STAGE, bool FILTER, bool HIST>
+__global__ void __launch_bounds__(256)
+background_flag_tolerant_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ upos, const u32 *__restrict__ mult,
+                                u32 n, u32 L, u32 K, u64 mask, u32 rc_shift, const KmerViews views, u32 max_hits,
+                                u32 nchunk, u32 pitch_dw, u32 extra_off_dw, u32 *__restrict__ flag,
+                                u64 *__restrict__ totals) {
+    background_flag_body<M, STAGE, FILTER, HIST>(bytes, upos, mult, n, L, K, mask, rc_shift, views, max_hits, nchunk,
+                                                 pitch_dw, extra_off_dw, flag, totals);
+}
+
 template <bool FILTER, bool HIST>
 static int launch_background(catchhip_ctx *ctx, const catchhip_candidates *C, const catchhip_kmer_index *X, u32 max_hits,
                              u32 *flag, u64 *totals) {
@@ -294,7 +390,18 @@ static int launch_background(catchhip_ctx *ctx, const catchhip_candidates *C, co
     u32 rows = 256;
     while (rows > 64 && rows * row_bytes + BG_EXTRA_BYTES > POLYA_LDS_BUDGET) rows >>= 1;
     const bool stage = rows * row_bytes + BG_EXTRA_BYTES <= POLYA_LDS_BUDGET && ((uintptr_t)C->T->bytes.p & 15u) == 0;
-    if (stage)
+    if (X->mismatches) {                                      // the same launch, the tolerant kernel of the index's budget
+        const bool two = X->mismatches == 2;
+        auto kernel = stage ? (two ? background_flag_tolerant_kernel<2, true, FILTER, HIST>
+                                   : background_flag_tolerant_kernel<1, true, FILTER, HIST>)
+                            : (two ? background_flag_tolerant_kernel<2, false, FILTER, HIST>
+                                   : background_flag_tolerant_kernel<1, false, FILTER, HIST>);
+        if (!stage) rows = 256;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)div_up((i64)n, rows)), dim3(rows),
+                           (stage ? rows * row_bytes : 0) + BG_EXTRA_BYTES, ctx->stream, (const u8 *)C->T->bytes.p,
+                           (const u32 *)C->upos.p, (const u32 *)C->mult.p, n, L, K, mask, 2 * K - 2, kmer_views(X), max_hits,
+                           nchunk, pitch_dw, stage ? rows * pitch_dw : 0u, flag, totals);
+    } else if (stage)
         hipLaunchKernelGGL((background_flag_kernel<true, FILTER, HIST>), dim3((unsigned)div_up((i64)n, rows)), dim3(rows),
                            rows * row_bytes + BG_EXTRA_BYTES, ctx->stream, (const u8 *)C->T->bytes.p,
                            (const u32 *)C->upos.p, (const u32 *)C->mult.p, n, L, K, mask, 2 * K - 2,

@@ -368,9 +368,20 @@ struct catchhip_kmer_index {
     u32 P = 8;                       // directory bits
     u64 *codes = nullptr;            // n_unique (at least one word allocated)
     u32 *dir = nullptr;              // 2^P + 1
+    // a tolerant index (mismatches = M > 0): codes / dir / P are view 0; view b = 1 .. M is [b - 1] below -- the same
+    // codes rotated left by 2 * view_start[b - 1] bits inside their 2k bits, sorted, and a directory of view_P bits
+    i32 mismatches = 0;
+    u32 view_start[2] = {0, 0};      // s_b: the first character of block b
+    u32 view_P[2] = {8, 8};
+    u64 *view_codes[2] = {nullptr, nullptr};
+    u32 *view_dir[2] = {nullptr, nullptr};
     ~catchhip_kmer_index() {
         if (codes) (void)hipFree(codes);
         if (dir) (void)hipFree(dir);
+        for (int b = 0; b < 2; ++b) {
+            if (view_codes[b]) (void)hipFree(view_codes[b]);
+            if (view_dir[b]) (void)hipFree(view_dir[b]);
+        }
     }
 };
 

@@ -3,11 +3,12 @@
 // hits are TmFilter._tm_c and BackgroundFilter._hits), on the device's candidate list, before the near-duplicate
 // filter.  The list is only read.  Two kernels, because their LDS holds different things:
 //
-// measure_rows_kernel<STAGE, COMP, TM, HITS>: gc, homopolymer, dust, tm_c and hits -- one thread per unique candidate,
+// measure_rows_kernel<STAGE, COMP, TM, HITS, M>: gc, homopolymer, dust, tm_c and hits -- one thread per unique candidate,
 //   one pass over its L bytes, the rows staged as the poly(A) kernel stages them (stage.h).  The per-byte work of each
 //   family is that of its flag kernel (prefilter.hip, thermo.hip, background.hip: the triplet counters of a thread one
 //   byte each in LDS at a lane pitch of one dword, the dinucleotide table in LDS, the rolled canonical code and the
-//   directory look-up), restated here so that the flag kernels stay as they are; what differs is the end:
+//   directory look-up -- kmer_lookup.h, exact or within the index's mismatches), restated here so that the flag kernels
+//   stay as they are; what differs is the end:
 //   dust.  The flag kernel compares every window with ONE threshold; the measure keeps the running maximum `best` of
 //   ceil(10 S / (T - 1)) and asks the flag kernel's question with it, 10 S > best (T - 1), which is true iff the
 //   window's quotient exceeds best.  Only then is the quotient formed: one integer division per RISE of the maximum,
@@ -49,6 +50,7 @@
 #include "internal.h"
 #include "wave.h"
 #include "stage.h"
+#include "kmer_lookup.h"
 
 typedef uint16_t u16;
 
@@ -84,9 +86,11 @@ struct MeasureRowsArgs {
     i32 *tm_c;
     u32 *hits;
     u64 *hist;                       // MEASURE_SLOTS copies of the five histograms
+    KmerViews views;                 // hits against a tolerant index (mismatches > 0)
 };
 
-template <bool STAGE, bool COMP, bool TM, bool HITS>
+// M: the mismatch budget of the index behind `hits` (0: the exact look-up; 1, 2: HITS is on)
+template <bool STAGE, bool COMP, bool TM, bool HITS, int M = 0>
 __global__ void __launch_bounds__(256)
 measure_rows_kernel(const MeasureRowsArgs a) {
     extern __shared__ u32 mr_lds[];
@@ -161,16 +165,8 @@ measure_rows_kernel(const MeasureRowsArgs a) {
                 rc = (rc >> 2) | (((u64)code ^ 2ull) << a.rc_shift);
                 brun = b ? brun + 1u : 0u;
                 if (brun >= a.K) {
-                    const u64 canon = fwd < rc ? fwd : rc;
-                    const u32 bk = (u32)(canon >> a.dir_shift);
-                    u32 lo = a.dir[bk], hi = a.dir[bk + 1u];
-                    while (hi - lo > 4u) {                    // (canon, if it is there at all, stays inside [lo, hi))
-                        const u32 mid = (lo + hi) >> 1;
-                        if (a.codes[mid] <= canon) lo = mid; else hi = mid;
-                    }
-                    u32 hit = 0;
-                    for (u32 t = lo; t < hi; ++t) hit |= a.codes[t] == canon ? 1u : 0u;
-                    hits += hit;
+                    if constexpr (M == 0) hits += kmer_lookup_exact(fwd, rc, a.codes, a.dir, a.dir_shift);
+                    else hits += kmer_lookup_tolerant<M>(fwd, rc, a.mask, 2u * a.K, a.views);
                 }
             }
         }
@@ -356,9 +352,16 @@ static measure_rows_fn measure_rows_instance(bool comp, bool tm, bool hits) {
         measure_rows_kernel<STAGE, true, true, true>};
     return table[(comp ? 1 : 0) | (tm ? 2 : 0) | (hits ? 4 : 0)];
 }
+template <bool STAGE, int M>
+static measure_rows_fn measure_rows_tolerant_instance(bool comp, bool tm) {
+    static const measure_rows_fn table[4] = {
+        measure_rows_kernel<STAGE, false, false, true, M>, measure_rows_kernel<STAGE, true, false, true, M>,
+        measure_rows_kernel<STAGE, false, true, true, M>, measure_rows_kernel<STAGE, true, true, true, M>};
+    return table[(comp ? 1 : 0) | (tm ? 2 : 0)];
+}
 
 static int launch_measure_rows(catchhip_ctx *ctx, const catchhip_candidates *C, bool comp, bool tm, bool hits,
-                               bool histograms, MeasureRowsArgs a) {
+                               i32 mismatches, bool histograms, MeasureRowsArgs a) {
     const u32 n = (u32)C->nuniq, L = (u32)C->L;
     a.bytes = (const u8 *)C->T->bytes.p;
     a.upos = (const u32 *)C->upos.p;
@@ -381,7 +384,11 @@ static int launch_measure_rows(catchhip_ctx *ctx, const catchhip_candidates *C, 
     a.tbl_off_dw = a.cnt_off_dw + rows * (u32)(cnt_bytes / 4);
     a.bin_off_dw = (a.tbl_off_dw + (tm ? MEASURE_TABLE_DW : 0u) + 1u) & ~1u;          // (+ 4 above: this rounding)
     const size_t lds = (size_t)a.bin_off_dw * 4 + (size_t)(2u * a.nb_len + a.nb_dust) * 8;
-    const measure_rows_fn fn = stage ? measure_rows_instance<true>(comp, tm, hits) : measure_rows_instance<false>(comp, tm, hits);
+    measure_rows_fn fn = stage ? measure_rows_instance<true>(comp, tm, hits) : measure_rows_instance<false>(comp, tm, hits);
+    if (hits && mismatches == 1)
+        fn = stage ? measure_rows_tolerant_instance<true, 1>(comp, tm) : measure_rows_tolerant_instance<false, 1>(comp, tm);
+    if (hits && mismatches == 2)
+        fn = stage ? measure_rows_tolerant_instance<true, 2>(comp, tm) : measure_rows_tolerant_instance<false, 2>(comp, tm);
     hipLaunchKernelGGL(fn, dim3((unsigned)div_up((i64)n, rows)), dim3(rows), lds, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -510,10 +517,11 @@ extern "C" int catchhip_candidates_measure(catchhip_ctx *ctx, const catchhip_can
             a.dir_shift = 2 * a.K - X->P;
             a.codes = X->codes;
             a.dir = X->dir;
+            a.views = kmer_views(X);
         }
         a.gc = d_gc.p; a.run = d_run.p; a.dust = d_dust.p; a.tm_c = d_tm.p; a.hits = d_hits.p;
         a.hist = d_hist.p;
-        TRY(launch_measure_rows(ctx, C, comp, tm_on, bg_on, hist != nullptr, a));
+        TRY(launch_measure_rows(ctx, C, comp, tm_on, bg_on, bg_on ? X->mismatches : 0, hist != nullptr, a));
         timer.launch();
     }
     if (structure) {

@@ -31,7 +31,7 @@ right after that one (catch_amd/filter/structure_filter.py has the rules);
 candidates by their nearest-neighbour melting temperature and
 --write-tm-histogram writes its distribution, one filter right after that one
 (catch_amd/filter/tm_filter.py has the rule); --background (with
---background-kmer, --background-max-hits; nor these) drops candidates that
+--background-kmer, --background-mismatches, --background-max-hits; nor these) drops candidates that
 share k-mers with a host genome or another background and
 --write-background-histogram writes how many share how many, one filter right
 after that one (catch_amd/filter/background_filter.py has the rule);
@@ -542,8 +542,7 @@ def main(args):
             tm.write_histogram(args.write_tm_histogram)
     if background is not None:
         if logger.isEnabledFor(logging.INFO):       # (counting the k-mers can mean building an index)
-            logger.info("background filter: %d candidates dropped; %d background bases, %d distinct k-mers",
-                        background.dropped, background.background_bases, background.distinct_kmers())
+            logger.info(background.summary())
         if args.write_background_histogram:
             background.write_histogram(args.write_background_histogram)
         background.close()

@@ -189,8 +189,7 @@ def main(args):
             tm.write_histogram(args.write_tm_histogram)
     if background is not None:
         if logger.isEnabledFor(logging.INFO):       # (counting the k-mers can mean building an index)
-            logger.info("background filter: %d candidates dropped; %d background bases, %d distinct k-mers",
-                        background.dropped, background.background_bases, background.distinct_kmers())
+            logger.info(background.summary())
         if args.write_background_histogram:
             background.write_histogram(args.write_background_histogram)
         background.close()

@@ -604,18 +604,26 @@ class KmerIndex:
     `seqs` (strings; only A, C, G, T are bases, no k-mer spans two of them) and
     a prefix directory, for Candidates.drop_background.  Built on ctx, usable
     from every context of ctx's device, and it outlives ctx.  n_valid: valid
-    k-mer positions; n_unique: distinct canonical codes."""
+    k-mer positions; n_unique: distinct canonical codes.  mismatches = M > 0
+    (catchhip_kmer_index_create_tolerant, k >= 8 (M + 1), M <= 2) makes the
+    index tolerant: M + 1 views of the codes, and drop_background and measure
+    then count k-mers within M mismatches of the background."""
 
-    def __init__(self, ctx, seqs, k):
-        self.ctx, self.device, self.k = ctx, ctx.device, int(k)
+    def __init__(self, ctx, seqs, k, mismatches=0):
+        self.ctx, self.device, self.k, self.mismatches = ctx, ctx.device, int(k), int(mismatches)
         self._L = ctx._L
         self._h = ctypes.c_void_p()
         seqs = list(seqs)
         buf, off = _concat(seqs)
         nv, nu = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(self._L.catchhip_kmer_index_create(
-            ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), len(seqs), self.k,
-            ctypes.byref(self._h), ctypes.byref(nv), ctypes.byref(nu)))
+        if self.mismatches == 0:
+            check(self._L.catchhip_kmer_index_create(
+                ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), len(seqs), self.k,
+                ctypes.byref(self._h), ctypes.byref(nv), ctypes.byref(nu)))
+        else:
+            check(self._L.catchhip_kmer_index_create_tolerant(
+                ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), len(seqs), self.k, self.mismatches,
+                ctypes.byref(self._h), ctypes.byref(nv), ctypes.byref(nu)))
         self.n_valid, self.n_unique = nv.value, nu.value
 
     def fetch(self, ctx=None):
@@ -623,6 +631,13 @@ class KmerIndex:
         the device (default: the one it was built on)."""
         out = np.zeros(max(self.n_unique, 1), dtype=np.uint64)
         check(self._L.catchhip_kmer_index_fetch((ctx or self.ctx)._h, self._h, _ptr(out, c_u64p)))
+        return out[:self.n_unique]
+
+    def fetch_view(self, b, ctx=None):
+        """The sorted codes of view b = 0 .. mismatches (uint64): every code
+        rotated left by 2 * floor(b k / (mismatches + 1)) bits inside its 2k."""
+        out = np.zeros(max(self.n_unique, 1), dtype=np.uint64)
+        check(self._L.catchhip_kmer_index_fetch_view((ctx or self.ctx)._h, self._h, int(b), _ptr(out, c_u64p)))
         return out[:self.n_unique]
 
     def close(self):
@@ -738,7 +753,8 @@ class Candidates:
         """catchhip_candidates_drop_background (not in the reference): the
         number of k-mers every unique candidate shares with the background
         behind `index` (a KmerIndex of this device; catch_amd/filter/
-        background_filter.py has the rule).  With max_hits the candidates with
+        background_filter.py has the rule), within index.mismatches
+        substitutions.  With max_hits the candidates with
         more hits are dropped, order, multiplicities and groups kept; without
         it the list is untouched.  Returns (candidates dropped, with
         multiplicity, the 256 bins of min(hits, 255) over the candidates the

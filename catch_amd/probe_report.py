@@ -4,7 +4,8 @@
 One row per record, in file order: probe (the record's name), length, gc,
 homopolymer, dust, stem, dimer (catch_amd/filter/quality.py has the
 definitions), tm_c (TmFilter._tm_c, hundredths of a degree Celsius) and
-background_hits (BackgroundFilter._hits; with --background) -- NA for what was
+background_hits (BackgroundFilter._hits; with --background, within
+--background-mismatches) -- NA for what was
 not computed or is undefined.  With a threshold option a last column, verdict,
 lists the rules the probe fails, or ok; the thresholds are the design
 command's and are compared as it compares them.  Not in the reference.
@@ -54,7 +55,8 @@ def parse_args(argv=None):
         if getattr(args, dest) is not None:
             p.error("%s is an option of the design commands: the report lists every probe's value" % flag)
     if args.background is None:
-        for flag, value in (("--background-kmer", args.background_kmer), ("--background-max-hits", args.background_max_hits)):
+        for flag, value in (("--background-kmer", args.background_kmer), ("--background-max-hits", args.background_max_hits),
+                            ("--background-mismatches", args.background_mismatches)):
             if value is not None:
                 p.error("%s needs --background" % flag)
     try:
@@ -88,7 +90,7 @@ class Judge:
             seqs = [s for fn in args.background for s in seq_io.read_fasta(fn).values()] if load else ["ACGT" * 8]
             self.background = background_filter.BackgroundFilter(
                 seqs, kmer=background_filter.KMER_DEFAULT if args.background_kmer is None else args.background_kmer,
-                max_hits=args.background_max_hits)
+                max_hits=args.background_max_hits, mismatches=getattr(args, "background_mismatches", None) or 0)
         elif args.background_max_hits is not None:
             raise ValueError("--background-max-hits needs --background")
         self.thresholds = any(x is not None for x in (

@@ -1083,6 +1083,29 @@ int catchhip_kmer_index_fetch(catchhip_ctx *ctx, const catchhip_kmer_index *inde
                               uint64_t *out);
 /* frees the index's device memory (waits for the device's work); NULL is fine */
 void catchhip_kmer_index_destroy(catchhip_kmer_index *index);
+/* NOT IN THE REFERENCE (catch_amd/filter/background_filter.py states the rule): the index
+ * of catchhip_kmer_index_create for matching within `mismatches` = M substitutions, M in
+ * 0 .. 2 and k >= 8 (M + 1) (EINVAL otherwise).  M = 0 builds exactly what
+ * catchhip_kmer_index_create builds.  M > 0: block b = 0 .. M of a k-mer is its characters
+ * [s_b, s_(b+1)), s_b = floor(b k / (M + 1)); two k-mers at most M mismatches apart agree
+ * in one block.  The index holds M + 1 VIEWS of the distinct canonical codes: view b is
+ * every code rotated left by 2 s_b bits inside its 2k bits (block b in the most
+ * significant bits; view 0 is the codes as they are), sorted, with a directory of its own
+ * of P_b = clamp(ceil(log2 n_unique), 8, min(2 (s_(b+1) - s_b), 30)) bits -- never finer
+ * than the block, so one bucket holds every code that agrees with a query in block b.
+ * 8 (M + 1) bytes per distinct code plus the directories.  The mismatch budget travels in
+ * the index: catchhip_candidates_drop_background and catchhip_candidates_measure count a
+ * k-mer w as a hit iff some code c of the index lies within M mismatches of code(w) or of
+ * code(reverse complement of w). */
+int catchhip_kmer_index_create_tolerant(catchhip_ctx *ctx, const uint8_t *bytes,
+                                        const int64_t *off, int64_t nseq, int32_t k,
+                                        int32_t mismatches, catchhip_kmer_index **index,
+                                        int64_t *n_valid, int64_t *n_unique);
+/* NOT IN THE REFERENCE: out[0 .. n_unique): the sorted rotated codes of one view, 0 <= view
+ * <= the index's mismatches (EINVAL otherwise); view 0 is what catchhip_kmer_index_fetch
+ * returns */
+int catchhip_kmer_index_fetch_view(catchhip_ctx *ctx, const catchhip_kmer_index *index,
+                                   int32_t view, uint64_t *out);
 /* NOT IN THE REFERENCE (catch_amd/filter/background_filter.py): the background k-mer
  * screen on the unique candidates, as a filter and as a histogram.  w HITS iff w or its
  * reverse complement is a valid k-mer of the background, i.e. iff canonical(w) is in the
