@@ -1596,7 +1596,7 @@ static bool join_path_ok(const catchhip_probes *P, int mm) {
 // the write pass alone (again after a row build that fell back to the radix sort: the merge works in place)
 static void join_write_pass(catchhip_ctx *ctx, JoinRun &J) {
     if (!J.nhit) return;
-    hipLaunchKernelGGL(J.write_main, dim3((unsigned)div_up((i64)J.nhit, 256)), dim3(256), 0, ctx->stream, J.A);
+    hipLaunchKernelGGL(J.write_main, dim3((unsigned)div_up((i64)J.nhit, 64 * KJ_VERIFY_WAVES)), dim3(64 * KJ_VERIFY_WAVES), 0, ctx->stream, J.A);
     if (J.ngiant) (void)hipMemsetAsync(J.giant_n.p + 2, 0, sizeof(u32), ctx->stream);   // the write pass's task cursor
     if (J.ngiant)
         hipLaunchKernelGGL(J.write_giant, dim3((unsigned)std::min<i64>(div_up((i64)J.ngiant, 4), (i64)ctx->num_cus * 8)),
@@ -1678,7 +1678,9 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
     // (2 per position there); a run that finds the store full is simply verified again
     A.masks = nullptr; A.mbase = A.gmbase = nullptr; A.mcursor = J.pairs.p + 128; A.mask_cap = 0;   // (zeroed with the statistics)
     if (J.nhit) {
-        const size_t mcap = (size_t)std::min<u64>((u64)1 << 26, std::max<u64>((u64)1 << 20, 6ull * J.nhit));
+        // (CATCHHIP_MASK_CAP, tests: a store too small for some runs; nothing is run again, the writing pass verifies those runs itself)
+        const size_t mcap = forced_capacity(chip_test_env_int("CATCHHIP_MASK_CAP", -1),
+                                            (u32)std::min<u64>((u64)1 << 26, std::max<u64>((u64)1 << 20, 6ull * J.nhit)));
         TRY(J.masks.reserve(mcap));
         TRY(J.mbase.reserve(J.nhit));
         TRY(J.gmbase.reserve(giant_cap));
@@ -1697,7 +1699,7 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
         TRY(chip_radix_sort_pairs(ctx, J.hkey, J.hkey_alt, J.hsq, J.hsq_alt, (i64)J.nhit, ceil_log2_u64((u64)capacity), 32));
         A.hkey = (const unsigned long long *)J.hkey.p; A.hsq = (const u32 *)J.hsq.p;
         (void)hipEventRecord(ctx->ev[2 * PHASE_VCOUNT], s);
-        hipLaunchKernelGGL(pick_kj_verify<false>(NW), dim3((unsigned)div_up((i64)J.nhit, 256)), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(pick_kj_verify<false>(NW), dim3((unsigned)div_up((i64)J.nhit, 64 * KJ_VERIFY_WAVES)), dim3(64 * KJ_VERIFY_WAVES), 0, s, A);
         hipLaunchKernelGGL(pick_kj_giant<false>(NW), dim3((unsigned)ctx->num_cus * 2), dim3(256), 0, s, A);
         (void)hipEventRecord(ctx->ev[2 * PHASE_VCOUNT + 1], s);
         ctx->phase_launches[PHASE_VCOUNT] = 1;

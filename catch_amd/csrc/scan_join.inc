@@ -444,12 +444,20 @@ __device__ __forceinline__ void kj_lanes(const JoinArgs &A, bool active, u32 idx
 }
 
 // 3./4. a wavefront looks at 64 consecutive records of the sorted hit list and takes every run that STARTS there
+//
+// Round 12: ONE wavefront per workgroup (until then four).  Most wavefronts find no wave-wide run in their 64 records
+// and are through at once, but in a workgroup of four their wave slots and the workgroup's LDS (4 KjLds) stayed taken
+// until its one heavy wavefront had verified its runs: a CU held few heavy wavefronts, and those waited for their loads
+// with nobody to issue in their place.  Alone, a wavefront gives back its 4,864 B (NW = 4) and its slot when it exits.
+// S4, per step, counting + writing launch: 6.3 + 4.8 ms with four, 5.0 + 4.3 with two, 4.4 + 4.3 with one
+// (DESIGN.md section 4 K1d, round 12; issuing the next window's loads ahead of the tests added nothing to that).
+#define KJ_VERIFY_WAVES 1
 template <int NW, bool WRITE>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(64 * KJ_VERIFY_WAVES)
 kj_verify_kernel(JoinArgs A) {
-    __shared__ KjLds<NW> s_lds[4];
+    __shared__ KjLds<NW> s_lds[KJ_VERIFY_WAVES];
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u32 c64 = (blockIdx.x * 4u + wave) * 64u;
+    const u32 c64 = (blockIdx.x * (u32)KJ_VERIFY_WAVES + wave) * 64u;
     if (c64 >= A.nhit) return;                         // wave-uniform
     const u32 i = c64 + lane;
     const bool valid = i < A.nhit;
