@@ -3,7 +3,7 @@
 Random groups of genomes (several chromosomes, N runs, repeats, short
 sequences), random -pl/-ps/-m/-l/-e/-c/island/identify settings, with and
 without duplicate candidates; compares the cover rows and the selected probe
-sets, and the near-duplicate filters.  Not part of the pytest suite: run by
+sets, and the near-duplicate filters (MinHash k-mers of 6, 8, 10, 13 or 16).  Not part of the pytest suite: run by
 hand after kernel changes; every failure prints the seed that reproduces it."""
 import os
 os.environ.setdefault("CATCHHIP_TEST_HOOKS", "1")
@@ -49,7 +49,18 @@ SOLVER_ENV = ("CATCHHIP_FLAT_MIN_ROWS", "CATCHHIP_FLAT_STRIPED", "CATCHHIP_GF_LO
               "CATCHHIP_FLAT_COUNT_ROUND0")
 
 
-def one_case(seed, ctx):
+MINHASH_KMER_SIZES = (6, 8, 10, 13, 16)      # below and on a SipHash block, the compiled-in size, two id words, no 2-bit codes
+
+
+def minhash_kmer_size(seed):
+    """The k-mer size of a seed's MinHash filter: from a generator of its own, so that the sizes can change without
+    moving any other draw of the seed."""
+    return random.Random(seed * 7919 + 29).choice(MINHASH_KMER_SIZES)
+
+
+def one_case(seed, ctx, kmer_size=None):
+    """kmer_size: the MinHash filter's k-mer size instead of the seed's own (a pinned case keeps the size it was found
+    with)."""
     rnd = random.Random(seed)
     # which of the equivalent kernel families run (all must give the oracle's result)
     for name in SOLVER_ENV:
@@ -179,7 +190,10 @@ def one_case(seed, ctx):
         gh = sorted(p.seq_str for p in fh.filter([probe.Probe.from_str(s) for s in strs]))
         assert gh == sorted(oracle.ndf_hamming(strs, d, pos)), (desc, "ndf hamming")
         dj = rnd.choice([0.3, 0.5, 0.6])
-        fm = near_duplicate_filter.NearDuplicateFilterWithMinHash(dj, rnd.choice([8, 10]))
+        drawn = rnd.choice([8, 10])      # (the sizes of rounds 1-6; still drawn: the later draws of a seed stay what they were)
+        ks = kmer_size or minhash_kmer_size(seed)
+        desc.update(minhash_kmer_size=ks, minhash_kmer_size_of_rounds_1_to_6=drawn)
+        fm = near_duplicate_filter.NearDuplicateFilterWithMinHash(dj, ks)
         par = fm._draw_params()
         fm._draw_params = lambda: par
         gm = sorted(p.seq_str for p in fm.filter([probe.Probe.from_str(s) for s in strs]))

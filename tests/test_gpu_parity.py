@@ -2173,7 +2173,24 @@ def test_fuzz_case_whose_wake_ups_only_drop(ctx):
     after a compaction keeps probes whose last tables ran out, a round without a pass only DROPS probes (parked on
     the newly kept ones) and wakes nobody; the loop must go on (its first stuck-check stopped there)."""
     import fuzz_parity
-    fuzz_parity.one_case(31188, ctx)
+    fuzz_parity.one_case(31188, ctx, kmer_size=10)       # (k-mers of 10: the size the seed drew when it was found)
+
+
+@pytest.mark.parametrize("seed,kmer_size", [(28, 6), (2, 13), (7, 16)])
+def test_fuzz_cases_at_the_other_minhash_kmer_sizes(ctx, seed, kmer_size):
+    """tests/fuzz_parity.py draws the MinHash filter's k-mer size from 6, 8, 10, 13 and 16 (8 and 10 until round 6):
+    one seed of each of the other sizes -- below a SipHash block, two id words, no 2-bit codes."""
+    import fuzz_parity
+    assert fuzz_parity.minhash_kmer_size(seed) == kmer_size
+    saved = {name: os.environ.get(name) for name in fuzz_parity.SOLVER_ENV}
+    try:
+        assert fuzz_parity.one_case(seed, ctx)["minhash_kmer_size"] == kmer_size
+    finally:                                    # (a case sets the switches of its solver variant: put back what was there)
+        for name, value in saved.items():
+            if value is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = value
 
 
 def test_cluster_with_minhash_signatures_golden(ctx):
