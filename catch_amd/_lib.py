@@ -255,6 +255,13 @@ PROTOTYPES = {
         c_i64p, c_u64p, c_u32p, ctypes.c_int64]),
     "catchhip_rows_uncovered": (ctypes.c_int, [
         c_vp, c_vp, c_vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, c_vpp, c_i64p, c_i64p]),
+    "catchhip_basemask_create": (ctypes.c_int, [
+        c_vp, c_i64p, ctypes.c_int32, c_i32p, c_i64p, c_i64p, ctypes.c_int64, c_vpp, c_i64p]),
+    "catchhip_basemask_fetch": (ctypes.c_int, [c_vp, c_vp, c_u64p]),
+    "catchhip_basemask_destroy": (ctypes.c_int, [c_vp]),
+    "catchhip_rows_restrict": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vpp, c_i64p]),
+    "catchhip_rows_uncovered_within": (ctypes.c_int, [
+        c_vp, c_vp, c_vp, c_vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, c_vpp, c_i64p, c_i64p]),
     "catchhip_rows_first_seen_per_set": (ctypes.c_int, [
         c_vp, c_vp, ctypes.c_int64, c_i32p, c_u64p]),
     "catchhip_rows_cover_check": (ctypes.c_int, [

@@ -25,6 +25,7 @@ from catch_amd import combine_pooled
 from catch_amd import coverage_analysis
 from catch_amd import grid
 from catch_amd import probe
+from catch_amd import target_regions
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.analyze_probe_coverage")
@@ -59,6 +60,7 @@ def parse_args(argv=None):
                    help="sequences each probe maps to, not counting reverse "
                         "complements")
     coverage_analysis.add_uncovered_arguments(p)
+    target_regions.add_arguments(p)     # --target-regions, --exclude-regions: the uncovered-region outputs list wanted bases only
 
     def check_max_num_processes(val):
         ival = int(val)
@@ -83,12 +85,21 @@ def parse_args(argv=None):
                     "(or --params)")
         if args.cover_extension is None:
             args.cover_extension = 0
+    if target_regions.given(args) and not (args.write_uncovered_regions or args.write_uncovered_fasta):
+        p.error("--target-regions / --exclude-regions say which bases the uncovered-region outputs list: they "
+                "need --write-uncovered-regions or --write-uncovered-fasta (every other output describes "
+                "whole genomes)")
     return args
 
 
 def read_genomes(datasets, limit_target_genomes=None):
     """(genomes per dataset, their names), bin/analyze_probe_coverage.py:19-43."""
-    genomes_grouped, names = [], []
+    return read_named_genomes(datasets, limit_target_genomes)[:2]
+
+
+def read_named_genomes(datasets, limit_target_genomes=None):
+    """read_genomes and, third, the FASTA headers of every dataset's genomes (what target regions name)."""
+    genomes_grouped, names, records_grouped = [], [], []
     for ds in datasets:
         if ds.startswith("download:"):
             raise ValueError("dataset '%s': downloading a taxonomy ID from NCBI is "
@@ -98,11 +109,13 @@ def read_genomes(datasets, limit_target_genomes=None):
             raise ValueError("dataset '%s' is not a file: only FASTA files are "
                              "accepted as datasets; please check that the path "
                              "is valid" % ds)
-        genomes_grouped.append(seq_io.read_genomes_from_fasta(ds))
+        genomes, records = seq_io.read_named_genomes_from_fasta(ds)
+        genomes_grouped.append(genomes)
+        records_grouped.append(records)
         names.append(os.path.basename(ds))
     if limit_target_genomes:
         genomes_grouped = [g[:limit_target_genomes] for g in genomes_grouped]
-    return genomes_grouped, names
+    return genomes_grouped, names, records_grouped
 
 
 def params_per_dataset(params_tsv, datasets):
@@ -132,7 +145,13 @@ def main(args):
     logging.basicConfig(
         level=args.log_level,
         format="%(asctime)s - %(name)s [%(levelname)s] %(message)s")
-    genomes_grouped, names = read_genomes(args.dataset, args.limit_target_genomes)
+    genomes_grouped, names, records_grouped = read_named_genomes(args.dataset)
+    # (resolved against every record read; the regions then follow the records that --limit-target-genomes keeps)
+    regions = target_regions.from_args(args, records_grouped, genomes_grouped)
+    if args.limit_target_genomes:
+        genomes_grouped = [g[:args.limit_target_genomes] for g in genomes_grouped]
+        if regions is not None:
+            regions = regions.select([range(len(g)) for g in genomes_grouped])
     if args.params is not None:
         params = params_per_dataset(args.params, args.dataset)
     else:
@@ -152,7 +171,8 @@ def main(args):
             probes, m, args.lcf_thres, [genomes_grouped[d] for d in ds],
             [names[d] for d in ds],
             island_of_exact_match=args.island_of_exact_match,
-            cover_extension=e, kmer_probe_map_k=args.kmer_probe_map_k)
+            cover_extension=e, kmer_probe_map_k=args.kmer_probe_map_k,
+            target_regions=None if regions is None else regions.select_groups(ds))
         a.run()
         analyzers.append(a)
         for local, d in enumerate(ds):

@@ -38,10 +38,14 @@ class Analyzer:
     def __init__(self, probes, mismatches, lcf_thres, target_genomes,
                  target_genomes_names=None, island_of_exact_match=0,
                  custom_cover_range_fn=None, cover_extension=0,
-                 kmer_probe_map_k=10, rc_too=True):
+                 kmer_probe_map_k=10, rc_too=True, target_regions=None):
         if custom_cover_range_fn is not None:
             raise NotImplementedError(
                 "custom hybridization functions cannot run on the GPU path")
+        # the bases that were to be covered at all (catch_amd.target_regions.TargetRegions, or None: every base; not
+        # an argument of the reference's class): uncovered_regions() then lists runs of wanted bases only.  Everything
+        # else the analyzer reports keeps describing whole genomes.
+        self.target_regions = target_regions
         self.probes = probes
         self.target_genomes = target_genomes
         if target_genomes_names:
@@ -337,7 +341,10 @@ class Analyzer:
         self.uncovered_summary[i][j][rc] = (regions, bases, longest).  After
         run(); one scan per strand, the row table stays on the device
         (Rows.uncovered) and only the regions come back.  With no probes every
-        sequence that passes the filters is one region."""
+        sequence that passes the filters is one region.  With target_regions the
+        runs are runs of WANTED bases: an unwanted base ends a run as a covered
+        one does (one BaseMask per strand; with no probes every wanted interval
+        that passes the filters is one region)."""
         key = (int(min_depth), int(min_length), int(min_unambig))
         if key not in self._uncovered:
             self._uncovered[key] = self._find_uncovered(*key)
@@ -369,10 +376,16 @@ class Analyzer:
                         rows = self._scan(ctx, probes_dev, targets)
                     else:       # no probes: a table without rows over the same sequences
                         rows = engine.Rows.from_host(ctx, [], [], [], [], np.diff(targets.seq_off))
+                    mask = None
                     try:
-                        univ, st, en, ua, per = rows.uncovered(targets, min_depth, min_length, min_unambig)
+                        if self.target_regions is not None:     # one mask per strand, a universe per sequence
+                            mask = engine.BaseMask(ctx, np.diff(targets.seq_off),
+                                                   *self.target_regions.sequence_intervals(flat, rc))
+                        univ, st, en, ua, per = rows.uncovered(targets, min_depth, min_length, min_unambig, mask=mask)
                         self.last_uncovered_ms += rows.last_uncovered_ms
                     finally:
+                        if mask is not None:
+                            mask.close()
                         rows.close()
                 finally:
                     targets.close()

@@ -8,6 +8,8 @@
 //                           atomicOr: commutes)
 //      gp_acgt_kernel       with targets: acgt = the bitmap of the bases that are A, C, G or T (a lane per base,
 //                           one __ballot per 64-bit word)
+//      gp_mask_kernel       catchhip_rows_uncovered_within only: cov |= the mask's unwanted bases (a lane per word), so
+//                           that a base nobody wants ends a run as a covered base does
 //   3. gp_count_kernel      a lane per word: U = the uncovered bits; a run starts at an uncovered base whose
 //                           predecessor is covered or which is a universe's first (bnd), and ends at one whose
 //                           successor is covered or a universe's first -- shifts, one carry bit from each neighbour
@@ -191,11 +193,19 @@ gp_compact_kernel(const u32 *__restrict__ rs, const u32 *__restrict__ re, const 
     }
 }
 
-extern "C" int catchhip_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_targets *T,
-                                       i32 min_depth, i64 min_length, i64 min_unambig, catchhip_rows **out,
-                                       i64 *nregions, i64 *per_universe) {
+// cov[w] |= unwanted[w]: a base that is not wanted ends a run as a covered base does (a lane per word)
+__global__ void __launch_bounds__(256)
+gp_mask_kernel(const ull *__restrict__ unwanted, u32 nw, ull *__restrict__ cov) {
+    const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w < nw) cov[w] |= unwanted[w];
+}
+
+// catchhip_rows_uncovered (mask == null: it launches what it always launched) and catchhip_rows_uncovered_within
+static int gp_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_targets *T,
+                             const catchhip_basemask *mask, i32 min_depth, i64 min_length, i64 min_unambig,
+                             catchhip_rows **out, i64 *nregions, i64 *per_universe) {
     ARG_CHECK(ctx && R0 && out);
-    ARG_CHECK(R0->ctx == ctx && (!T || T->ctx == ctx));
+    ARG_CHECK(R0->ctx == ctx && (!T || T->ctx == ctx) && (!mask || mask->ctx == ctx));
     *out = nullptr;
     if (nregions) *nregions = 0;
     if (R0->deferred) {
@@ -218,6 +228,12 @@ extern "C" int catchhip_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R
         chip_set_error("rows_uncovered: the targets (%lld bases, %lld sequences in %d genomes) are not one genome per "
                        "sequence over the coordinate space of the rows (%lld bases in %d universes)",
                        (long long)T->total, (long long)T->nseq, (int)T->ngenomes, (long long)R0->total, (int)ng);
+        return CATCHHIP_EINVAL;
+    }
+    if (mask && (mask->total != R0->total || mask->ngenomes != ng || mask->h_genome_off != R0->h_genome_off)) {
+        chip_set_error("rows_uncovered: the mask is not over the coordinate space of the rows "
+                       "(%lld bases in %d universes against %lld in %d)",
+                       (long long)mask->total, (int)mask->ngenomes, (long long)R0->total, (int)ng);
         return CATCHHIP_EINVAL;
     }
     if (per_universe) for (i64 k = 0; k < 3 * (i64)ng; ++k) per_universe[k] = 0;
@@ -255,6 +271,11 @@ extern "C" int catchhip_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R
     hipLaunchKernelGGL(gp_boundary_kernel, dim3((unsigned)div_up(ngu, 256)), blk, 0, s, (const u32 *)R0->genome_off.p,
                        ngu, bnd.p);
     tm.launch(1);
+    if (mask) {
+        hipLaunchKernelGGL(gp_mask_kernel, dim3((unsigned)div_up(nw, 256)), blk, 0, s, (const ull *)mask->unwanted.p, nw,
+                           cov.p);
+        tm.launch(1);
+    }
     if (T) {
         TRY(acgt.alloc((size_t)nw));
         const i64 nwaves = div_up(nw, GP_WORDS);
@@ -319,4 +340,17 @@ extern "C" int catchhip_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R
     if (nregions) *nregions = R->n;
     *out = R.release();
     return 0;
+}
+
+extern "C" int catchhip_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_targets *T,
+                                       i32 min_depth, i64 min_length, i64 min_unambig, catchhip_rows **out,
+                                       i64 *nregions, i64 *per_universe) {
+    return gp_rows_uncovered(ctx, R0, T, nullptr, min_depth, min_length, min_unambig, out, nregions, per_universe);
+}
+
+extern "C" int catchhip_rows_uncovered_within(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_targets *T,
+                                              const catchhip_basemask *mask, i32 min_depth, i64 min_length,
+                                              i64 min_unambig, catchhip_rows **out, i64 *nregions, i64 *per_universe) {
+    ARG_CHECK(mask);
+    return gp_rows_uncovered(ctx, R0, T, mask, min_depth, min_length, min_unambig, out, nregions, per_universe);
 }

@@ -469,6 +469,17 @@ int chip_rows_copy(catchhip_ctx *ctx, const catchhip_rows *R0, catchhip_rows *R)
 int chip_rows_cut(catchhip_ctx *ctx, const catchhip_rows *R0, const unsigned long long *bm, const u8 *skip, u32 nskip,
                   catchhip_rows *R, PhaseTimer &tm, const char *who);
 
+// ---- the wanted bases of a coordinate space (mask.hip; catchhip_rows_restrict, catchhip_rows_uncovered_within) ---
+struct catchhip_basemask {
+    catchhip_ctx *ctx = nullptr;
+    i64 total = 0;       // size of the coordinate space (universes concatenated, as catchhip_rows_from_host lays them out)
+    i32 ngenomes = 0;
+    std::vector<i64> h_genome_off;
+    // bit b set = base b is not wanted; total / 64 + 2 + 8 words (subtract.hip's sizing: chip_rows_cut reads it as it
+    // reads its own), the bits at and beyond `total` set
+    DevBuf<unsigned long long> unwanted;
+};
+
 // ---- depth per base from a pick list (depth.hip; catchhip_rows_below_depth and catchhip_rows_prune) -------------
 // the refusals the two share: depth < 1, rows chip_rows_cut_check refuses, 2^32 - 1 bases and more, 2^31 rows and
 // more, more picks than sets

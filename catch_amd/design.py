@@ -40,6 +40,9 @@ judging them, one QualityProfile right after the poly(A) filter that drops
 nothing (catch_amd/filter/quality.py has the quantities), and
 --write-probe-report (nor this) writes what the designed probes are like, the
 report of catch_amd.probe_report for the output FASTA.
+--target-regions / --exclude-regions (nor these) say which bases are to be
+covered at all: BED intervals per FASTA record, the cover rows cut to them
+after the scan (catch_amd/target_regions.py has the rules).
 --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
@@ -111,6 +114,8 @@ def parse_args(argv=None, args_type="basic"):
     p.add_argument("--write-probe-map-counts-to-tsv")
     from catch_amd import coverage_analysis
     coverage_analysis.add_uncovered_arguments(p)
+    from catch_amd import target_regions
+    target_regions.add_arguments(p)         # --target-regions, --exclude-regions (not in the reference)
     def dissimilarity(val):
         fval = float(val)
         if fval == 0:
@@ -270,6 +275,33 @@ def write_coverage_curve(path, names, scf):
                 f.write("*\t%d\t%d\t%d\t%s\tNA\tNA\n" % (k, cov, coverable, frac(cov, coverable)))
 
 
+def limit_target_genomes(args, genomes_grouped, regions=None):
+    """--limit-target-genomes / --limit-target-genomes-randomly-with-replacement
+    (bin/design.py:101-112: before anything else draws from `random`) ->
+    (genomes_grouped, regions): the target regions (or None) follow the records
+    kept.  The draws from `random` are those of the reference's
+    random.choices(genomes, k=k) per dataset: it draws the same numbers for a
+    population of the same size, whatever it holds."""
+    if (args.limit_target_genomes and
+            args.limit_target_genomes_randomly_with_replacement):
+        raise Exception(("Cannot --limit-target-genomes and "
+                         "--limit-target-genomes-randomly-with-replacement at "
+                         "the same time"))
+    kept = None
+    if args.limit_target_genomes:
+        kept = [list(range(len(genomes)))[:args.limit_target_genomes]
+                for genomes in genomes_grouped]
+    elif args.limit_target_genomes_randomly_with_replacement:
+        k = args.limit_target_genomes_randomly_with_replacement
+        kept = [random.choices(range(len(genomes)), k=k)
+                for genomes in genomes_grouped]
+    if kept is not None:
+        genomes_grouped = [[genomes[i] for i in idx] for genomes, idx in zip(genomes_grouped, kept)]
+        if regions is not None:
+            regions = regions.select(kept)
+    return genomes_grouped, regions
+
+
 def main(args):
     logging.basicConfig(
         level=logging.INFO if args.verbose else logging.WARNING,
@@ -352,6 +384,24 @@ def main(args):
                              "--cluster-from-fragments (a default of "
                              "design_large.py): nothing is clustered; set "
                              "--cluster-from-fragments to 0 as well"))
+    from catch_amd import target_regions
+    if target_regions.given(args):
+        opt = "--target-regions" if args.target_regions else "--exclude-regions"
+        if args.skip_set_cover:
+            raise Exception(("Cannot use %s with --skip-set-cover: it is the "
+                             "set cover that designs for the wanted bases") % opt)
+        if args.cluster_and_design_separately:
+            raise Exception(("Cannot use %s with "
+                             "--cluster-and-design-separately (a default of "
+                             "design_large.py): the regions are set against "
+                             "each dataset as a whole; set "
+                             "--cluster-and-design-separately to 0 (and, where "
+                             "it is set, --cluster-from-fragments to 0 too)") % opt)
+        if args.cluster_from_fragments:
+            raise Exception(("Cannot use %s with "
+                             "--cluster-from-fragments (a default of "
+                             "design_large.py): nothing is clustered; set "
+                             "--cluster-from-fragments to 0 as well") % opt)
     want_gains = args.max_probes is not None or bool(args.write_coverage_curve)
     if args.coverage_curve_points < 1:
         raise Exception("--coverage-curve-points must be at least 1, not %d"
@@ -391,20 +441,11 @@ def main(args):
         raise Exception(("Adapter sequences were provided with --adapter-a "
                          "and --adapter-b, but --add-adapters is required to "
                          "add adapter sequences onto the ends of probes"))
-    genomes_grouped = [seq_io.read_genomes_from_fasta(fn) for fn in args.dataset]
-    # bin/design.py:101-112: before anything else draws from `random`
-    if (args.limit_target_genomes and
-            args.limit_target_genomes_randomly_with_replacement):
-        raise Exception(("Cannot --limit-target-genomes and "
-                         "--limit-target-genomes-randomly-with-replacement at "
-                         "the same time"))
-    elif args.limit_target_genomes:
-        genomes_grouped = [genomes[:args.limit_target_genomes]
-                           for genomes in genomes_grouped]
-    elif args.limit_target_genomes_randomly_with_replacement:
-        k = args.limit_target_genomes_randomly_with_replacement
-        genomes_grouped = [random.choices(genomes, k=k)
-                           for genomes in genomes_grouped]
+    named = [seq_io.read_named_genomes_from_fasta(fn) for fn in args.dataset]
+    genomes_grouped = [genomes for genomes, _names in named]
+    # the wanted bases, resolved against every record read: the regions then follow the records the limits keep
+    regions = target_regions.from_args(args, [names for _genomes, names in named], genomes_grouped)
+    genomes_grouped, regions = limit_target_genomes(args, genomes_grouped, regions)
 
     # bin/design.py:180-205, :232: argument checks and the k-mer length each
     # consumer of the probe map uses (20 / 20 / 10 unless given)
@@ -491,7 +532,8 @@ def main(args):
         coverage_depth=args.coverage_depth,
         prune_redundant=args.prune_redundant,
         max_probes=args.max_probes, pick_gains=want_gains,
-        curve_points=args.coverage_curve_points)
+        curve_points=args.coverage_curve_points,
+        target_regions=regions)
     filters.append(scf)
     if args.add_adapters:      # bin/design.py:345-365 (default sequences :350, :354)
         from catch_amd.filter import adapter_filter
@@ -546,6 +588,11 @@ def main(args):
         if args.write_background_histogram:
             background.write_histogram(args.write_background_histogram)
         background.close()
+    if regions is not None:
+        for gi, fn in enumerate(args.dataset):
+            coverable = scf.last_coverable_bases[gi] if gi < len(scf.last_coverable_bases) else 0
+            logger.info("%s: target regions: %d intervals, %d wanted bases of %d in %d of %d sequences; %d coverable",
+                        *((os.path.basename(fn),) + regions.summary(gi, genomes_grouped[gi]) + (coverable,)))
     if args.coverage_depth > 1:
         for fn, sizes in zip(args.dataset, scf.last_layer_sizes):
             logger.info("%s: %s probes in the layers of depth 1 to %d",
@@ -597,7 +644,8 @@ def main(args):
             island_of_exact_match=args.island_of_exact_match,
             cover_extension=args.cover_extension,
             kmer_probe_map_k=k_analyzer,
-            rc_too=args.add_reverse_complements)
+            rc_too=args.add_reverse_complements,
+            target_regions=regions)
         analyzer.run()
         if args.write_analysis_to_tsv:
             analyzer.write_data_matrix_as_tsv(args.write_analysis_to_tsv)

@@ -1023,8 +1023,10 @@ class Rows:
                  int(window_stride), _ptr(per_span, c_i64p), _ptr(sums, c_u64p), _ptr(counts, c_u32p), nwin))
         return sums[:nwin], counts[:nwin], win_off
 
-    def uncovered(self, targets=None, min_depth=1, min_length=1, min_unambig=1):
-        """catchhip_rows_uncovered -> (universe int32[n], start int64[n], end int64[n], unambig int64[n],
+    def uncovered(self, targets=None, min_depth=1, min_length=1, min_unambig=1, mask=None):
+        """catchhip_rows_uncovered (mask, a BaseMask over these universes: catchhip_rows_uncovered_within, the runs
+        of WANTED bases -- an unwanted base ends a run as a covered one does)
+        -> (universe int32[n], start int64[n], end int64[n], unambig int64[n],
         per_universe int64[ngenomes, 3]): the maximal runs of bases, inside one universe, that fewer than
         `min_depth` rows cover, in (universe, start) order, start and end local to the universe; reported are the
         runs of `min_length` bases and more of which at least `min_unambig` are A, C, G or T in `targets` (Targets
@@ -1037,9 +1039,15 @@ class Rows:
         per = np.zeros((max(ng, 1), 3), dtype=np.int64)
         h = ctypes.c_void_p()
         n = ctypes.c_int64(0)
-        check(self.ctx._L.catchhip_rows_uncovered(
-            self.ctx._h, self._h, None if targets is None else targets._h, int(min_depth), int(min_length),
-            int(min_unambig), ctypes.byref(h), ctypes.byref(n), _ptr(per, c_i64p)))
+        th = None if targets is None else targets._h
+        if mask is None:
+            check(self.ctx._L.catchhip_rows_uncovered(
+                self.ctx._h, self._h, th, int(min_depth), int(min_length),
+                int(min_unambig), ctypes.byref(h), ctypes.byref(n), _ptr(per, c_i64p)))
+        else:
+            check(self.ctx._L.catchhip_rows_uncovered_within(
+                self.ctx._h, self._h, th, mask._h, int(min_depth), int(min_length),
+                int(min_unambig), ctypes.byref(h), ctypes.byref(n), _ptr(per, c_i64p)))
         self.last_uncovered_ms, self.last_uncovered_launches = self.ctx.kernel_ms(PHASE_ROWS)
         regions = Rows(self.ctx, h, n.value, ng)
         try:
@@ -1110,6 +1118,16 @@ class Rows:
         n = ctypes.c_int64(0)
         check(self.ctx._L.catchhip_rows_subtract(
             self.ctx._h, self._h, covered._h, ctypes.byref(h), ctypes.byref(n)))
+        return Rows(self.ctx, h, n.value, self.ngenomes)
+
+    def restrict(self, mask):
+        """catchhip_rows_restrict: these rows cut to their maximal runs of the
+        bases `mask` (a BaseMask over the same universes) wants -- set, universe
+        and order kept."""
+        h = ctypes.c_void_p()
+        n = ctypes.c_int64(0)
+        check(self.ctx._L.catchhip_rows_restrict(
+            self.ctx._h, self._h, mask._h, ctypes.byref(h), ctypes.byref(n)))
         return Rows(self.ctx, h, n.value, self.ngenomes)
 
     def below_depth(self, num_sets, picks, depth):
@@ -1256,8 +1274,59 @@ class Rows:
             pass
 
 
+class BaseMask:
+    """The wanted bases of a coordinate space on the device (catchhip_basemask,
+    csrc/mask.hip): universes of genome_len[u] bases, and the wanted intervals
+    (universe[i], [start[i], end[i]) local to it) in normal form -- sorted by
+    (universe, start), non-empty, inside their universe, neither overlapping
+    nor touching (anything else: ValueError).  `wanted` (int64 per universe) =
+    the wanted bases, counted on the device.  For Rows.restrict and
+    Rows.uncovered(mask=...)."""
+
+    def __init__(self, ctx, genome_len, universe, start, end):
+        gl = np.ascontiguousarray(genome_len, dtype=np.int64)
+        un = np.ascontiguousarray(universe, dtype=np.int32)
+        st = np.ascontiguousarray(start, dtype=np.int64)
+        en = np.ascontiguousarray(end, dtype=np.int64)
+        if not (un.size == st.size == en.size):
+            raise ValueError("BaseMask: universe, start and end must have one entry per interval")
+        self.ctx = ctx
+        self.ngenomes = int(gl.size)
+        self.total = int(gl.sum()) if gl.size else 0
+        self.n = int(un.size)
+        wanted = np.zeros(max(self.ngenomes, 1), dtype=np.int64)
+        self._h = ctypes.c_void_p()
+        h = ctypes.c_void_p()
+        check(ctx._L.catchhip_basemask_create(
+            ctx._h, _ptr(gl, c_i64p) if gl.size else None, self.ngenomes,
+            _ptr(un, c_i32p) if self.n else None, _ptr(st, c_i64p) if self.n else None,
+            _ptr(en, c_i64p) if self.n else None, self.n, ctypes.byref(h), _ptr(wanted, c_i64p)))
+        self._h = h
+        self.wanted = wanted[:self.ngenomes]
+        self.last_build_ms = ctx.kernel_ms(PHASE_ROWS)[0]
+
+    def fetch(self):
+        """uint64[(total + 63) // 64]: bit b % 64 of word b // 64 is set iff base
+        b is NOT wanted; the bits behind the last base are set."""
+        nw = (self.total + 63) // 64
+        out = np.zeros(max(nw, 1), dtype=np.uint64)
+        check(self.ctx._L.catchhip_basemask_fetch(self.ctx._h, self._h, _ptr(out, c_u64p)))
+        return out[:nw]
+
+    def close(self):
+        if self._h and self.ctx._h:      # (see Context.close)
+            self.ctx._L.catchhip_basemask_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 REDUNDANT_SHIFT, REDUNDANT_LCF = 0, 1
-REDUNDANT_MAX_LENGTH = 256     # bases per probe the pair kernel is compiled for (csrc/redundant.hip)
+REDUNDANT_MAX_LENGTH = 256    # bases per probe the pair kernel is compiled for (csrc/redundant.hip)
 
 
 class RedundancyGraph:

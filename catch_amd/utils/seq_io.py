@@ -55,6 +55,14 @@ def read_genomes_from_fasta(fn):
     return [genome.Genome.from_one_seq(s) for s in read_fasta(fn).values()]
 
 
+def read_named_genomes_from_fasta(fn):
+    """read_genomes_from_fasta with the records' names beside them -> (genomes,
+    names): names[i] is the whole header line of genome i, as read_fasta keys it
+    (what a BED file of target regions names, catch_amd.target_regions)."""
+    records = read_fasta(fn)
+    return [genome.Genome.from_one_seq(s) for s in records.values()], list(records.keys())
+
+
 def iterate_fasta(fn, replace_degenerate=True):
     """Yield each sequence (catch/utils/seq_io.py:178-233)."""
     with _open(fn) as f:

@@ -1246,6 +1246,41 @@ int catchhip_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *rows, const 
                             int32_t min_depth, int64_t min_length, int64_t min_unambig, catchhip_rows **out,
                             int64_t *nregions, int64_t *per_universe);
 
+/* ---- target regions: the wanted bases of a coordinate space (csrc/mask.hip) ----
+ * A base mask says, for every base of a coordinate space (ngenomes universes of genome_len[u] bases, concatenated as
+ * catchhip_rows_from_host lays them out), whether it is WANTED: whether a design has to cover it at all.  The
+ * reference has no counterpart (it designs for every base of its genomes).  The n wanted intervals (universe[i],
+ * [start[i], end[i]) local to the universe) come in normal form: sorted by (universe, start), 0 <= start < end <=
+ * genome_len[universe], and inside a universe every start greater than the end before it (neither overlapping nor
+ * touching).  Anything else is CATCHHIP_EINVAL with a message that names the first offending interval, as are
+ * 2^32 - 1 bases and more.  n == 0: nothing is wanted.  The bitmap is built word-parallel (a lane per 64 bases, every
+ * word stored once; the time does not depend on the intervals' lengths) and wanted_per_universe[ngenomes] (may be
+ * NULL) receives the wanted bases of every universe, counted on the device.  Timed as phase 1. */
+typedef struct catchhip_basemask catchhip_basemask;
+int catchhip_basemask_create(catchhip_ctx *ctx, const int64_t *genome_len, int32_t ngenomes, const int32_t *universe,
+                             const int64_t *start, const int64_t *end, int64_t n, catchhip_basemask **out,
+                             int64_t *wanted_per_universe);
+/* words[(total + 63) / 64]: bit b % 64 of word b / 64 is set iff base b (global) is NOT wanted; the bits behind the
+ * last base are set. */
+int catchhip_basemask_fetch(catchhip_ctx *ctx, const catchhip_basemask *mask, uint64_t *words);
+int catchhip_basemask_destroy(catchhip_basemask *mask);
+/* out = every row of `rows` cut into its maximal runs of wanted bases, with the row's set and universe, in the order
+ * of `rows`: catchhip_rows_subtract with "covered" = the bases nobody wants.  `rows` as there; the result is sorted
+ * and normalised like `rows`, carries gain0 when `rows` does (as catchhip_rows_subtract carries it) and goes to
+ * catchhip_setcover_greedy as it is.  *nrows (may be NULL) = its row count; an empty table gives an empty table.
+ * CATCHHIP_EINVAL for deferred, direct or grouped rows, a mask over another coordinate space (other universe lengths),
+ * 2^32 - 1 target bases and more, 2^31 rows or pieces and more.  Timed as phase 1. */
+int catchhip_rows_restrict(catchhip_ctx *ctx, const catchhip_rows *rows, const catchhip_basemask *mask,
+                           catchhip_rows **out, int64_t *nrows);
+/* catchhip_rows_uncovered over the wanted bases only: a region is a maximal run of WANTED bases at depth < min_depth
+ * inside one universe -- an unwanted base ends a run as a covered base does, so two wanted stretches that touch only
+ * through unwanted bases give two regions.  Everything else as catchhip_rows_uncovered; CATCHHIP_EINVAL also for a
+ * mask over another coordinate space. */
+int catchhip_rows_uncovered_within(catchhip_ctx *ctx, const catchhip_rows *rows, const catchhip_targets *targets,
+                                   const catchhip_basemask *mask, int32_t min_depth, int64_t min_length,
+                                   int64_t min_unambig, catchhip_rows **out, int64_t *nregions,
+                                   int64_t *per_universe);
+
 /* Where every set id < num_sets was seen first, on rows from catchhip_cover_scan_first_seen with one universe per
  * sequence: first_universe[s] = the first universe set s has rows in (-1: none) and first_key[s] = the key of the
  * first accepted seed there (catchhip_rows_fetch_first_seen).  Sorting the sets by (first_universe, first_key)
