@@ -19,13 +19,13 @@
 // owned by the index, not by a context's block cache: every context of the device may read them, and they outlive the
 // context that built them.
 //
-// background_flag_kernel: one thread per unique candidate, the rows staged as the Tm kernel stages them (stage.h), one
-// pass over its L bytes.  Per byte the rolling update; from run >= K on one look-up: dir[p] and dir[p + 1] (one gather
-// of two neighbouring words), then the bucket -- halved while it is longer than 4, then compared one by one.  Counting
-// as in tm_flag_kernel: BG_WORDS 64-bit counters per workgroup in LDS behind the rows -- the 256 bins of hits, then
-// "dropped".  Bin 0 and "dropped" are one address each for most threads, so they are summed over the wave first and
-// added once per wave; the other bins take LDS atomics.  After a barrier thread t adds counter t, if it is not zero, to
-// one of BG_SLOTS copies in global memory, which the host adds up.  No thread returns before the barrier.
+// background_flag_kernel: one thread per unique candidate, the rows staged (stage.h), one pass over its L bytes.  Per
+// byte the rolling update (stage.h: KmerRoll); from run >= K on one look-up: dir[p] and dir[p + 1] (one gather of two
+// neighbouring words), then the bucket -- halved while it is longer than 4, then compared one by one.  Counting:
+// BG_WORDS 64-bit counters per workgroup in LDS behind the rows -- the 256 bins of hits, then "dropped".  Bin 0 and
+// "dropped" are one address each for most threads, so they are summed over the wave first and added once per wave; the
+// other bins take LDS atomics.  After a barrier the counters go to one of BG_SLOTS copies in global memory (stage.h:
+// the totals).  No thread returns before the barrier.
 //
 // Mismatches (catchhip_kmer_index_create_tolerant, mismatches = M in 1, 2, K >= 8 (M + 1)): a valid k-mer hits iff some
 // code of the index lies within M characters of fwd or of rc.  Block b = 0 .. M of a k-mer is its characters
@@ -39,6 +39,7 @@
 #include "internal.h"
 #include "wave.h"
 #include "stage.h"
+#include "rule_host.h"
 #include "kmer_lookup.h"
 
 #define BG_BINS 256u
@@ -303,34 +304,29 @@ extern "C" void catchhip_kmer_index_destroy(catchhip_kmer_index *X) {
 // M = 0: the exact look-up in view 0; M > 0: the tolerant one in the views 0 .. M
 template <int M, bool STAGE, bool FILTER, bool HIST>
 __device__ __forceinline__ void
-background_flag_body(const u8 *__restrict__ bytes, const u32 *__restrict__ upos, const u32 *__restrict__ mult, u32 n, u32 L,
-                     u32 K, u64 mask, u32 rc_shift, const KmerViews &views, u32 max_hits, u32 nchunk, u32 pitch_dw,
-                     u32 extra_off_dw, u32 *__restrict__ flag, u64 *__restrict__ totals) {
+background_flag_body(const RowArgs &a, u32 K, u64 mask, u32 rc_shift, const KmerViews &views, u32 max_hits,
+                     u32 *__restrict__ flag, u64 *__restrict__ totals) {
     extern __shared__ u32 bg_lds[];
     const u32 rows = blockDim.x, r = threadIdx.x;
     const u32 i = blockIdx.x * rows + r;
-    unsigned long long *cnt = (unsigned long long *)(bg_lds + extra_off_dw);        // (extra_off_dw is even: 8-byte aligned)
+    unsigned long long *cnt = (unsigned long long *)(bg_lds + a.extra_off_dw);      // (extra_off_dw is even: 8-byte aligned)
     for (u32 t = r; t < BG_WORDS; t += rows) cnt[t] = 0;
-    if (STAGE) stage_rows(bytes, upos, n, L, nchunk, pitch_dw, bg_lds);             // (ends with a barrier)
+    if (STAGE) stage_rows(a, bg_lds);                                               // (ends with a barrier)
     else __syncthreads();
     u64 t_zero = 0, t_drop = 0;
-    if (i < n) {                                              // (no early return: the wave sums and the barrier below)
-        const u32 s = upos[i];
-        const u8 *p = STAGE ? (const u8 *)(bg_lds + r * pitch_dw) + (s & 15u) : bytes + s;
-        u64 fwd = 0, rc = 0;
-        u32 run = 0, hits = 0;
-        for (u32 j = 0; j < L; ++j) {
+    if (i < a.n) {                                            // (no early return: the wave sums and the barrier below)
+        const u8 *p = row_ptr<STAGE>(a, bg_lds, i);
+        KmerRoll kmer;
+        u32 hits = 0;
+        for (u32 j = 0; j < a.L; ++j) {
             const u8 c = p[j];
-            const u64 code = (c >> 1) & 3u;
-            fwd = ((fwd << 2) | code) & mask;
-            rc = (rc >> 2) | ((code ^ 2ull) << rc_shift);
-            run = is_base(c) ? run + 1u : 0u;
-            if (run >= K) {
-                if constexpr (M == 0) hits += kmer_lookup_exact(fwd, rc, views.codes[0], views.dir[0], views.dir_shift[0]);
-                else hits += kmer_lookup_tolerant<M>(fwd, rc, mask, 2u * K, views);
+            if (kmer.step(base_code(c), is_base(c), mask, rc_shift, K)) {
+                if constexpr (M == 0)
+                    hits += kmer_lookup_exact(kmer.fwd, kmer.rc, views.codes[0], views.dir[0], views.dir_shift[0]);
+                else hits += kmer_lookup_tolerant<M>(kmer.fwd, kmer.rc, mask, 2u * K, views);
             }
         }
-        const u32 m = mult[i];
+        const u32 m = a.mult[i];
         if (HIST) {
             if (hits == 0) t_zero = m;
             else atomicAdd(cnt + (hits < BG_BINS - 1u ? hits : BG_BINS - 1u), (unsigned long long)m);
@@ -341,17 +337,9 @@ background_flag_body(const u8 *__restrict__ bytes, const u32 *__restrict__ upos,
             t_drop = drop ? m : 0u;
         }
     }
-    wave_sum_n(t_zero, t_drop);
-    if ((r & 63u) == 0) {
-        if (t_zero) atomicAdd(cnt, (unsigned long long)t_zero);
-        if (t_drop) atomicAdd(cnt + BG_BINS, (unsigned long long)t_drop);
-    }
+    totals_add_per_wave<BG_BINS>(cnt, t_zero, t_drop);        // bin 0, and "dropped" behind the bins
     __syncthreads();
-    unsigned long long *t = (unsigned long long *)totals + (blockIdx.x & (BG_SLOTS - 1u)) * BG_SLOT_WORDS;
-    for (u32 w = r; w < BG_WORDS; w += rows) {
-        const unsigned long long v = cnt[w];
-        if (v) atomicAdd(t + w, v);
-    }
+    totals_flush(cnt, BG_WORDS, totals_slot(totals, BG_SLOTS, BG_SLOT_WORDS));
 }
 
 template <bool STAGE, bool FILTER, bool HIST>
@@ -360,12 +348,14 @@ background_flag_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ upo
                        u32 K, u64 mask, u32 rc_shift, const u64 *__restrict__ codes, const u32 *__restrict__ dir,
                        u32 dir_shift, u32 max_hits, u32 nchunk, u32 pitch_dw, u32 extra_off_dw, u32 *__restrict__ flag,
                        u64 *__restrict__ totals) {
+    // (the row arguments one by one, in this order, and the struct made here: as ONE struct argument they moved the
+    // others, the scalar loads were cut differently and the kernel ran 0.3 % slower -- DESIGN.md, round 13)
+    const RowArgs a = {bytes, upos, mult, n, L, nchunk, pitch_dw, extra_off_dw};
     KmerViews views = {};
     views.codes[0] = codes;
     views.dir[0] = dir;
     views.dir_shift[0] = dir_shift;
-    background_flag_body<0, STAGE, FILTER, HIST>(bytes, upos, mult, n, L, K, mask, rc_shift, views, max_hits, nchunk,
-                                                 pitch_dw, extra_off_dw, flag, totals);
+    background_flag_body<0, STAGE, FILTER, HIST>(a, K, mask, rc_shift, views, max_hits, flag, totals);
 }
 
 // the same kernel against a tolerant index (M = 1, 2): per position 2 (M + 1) buckets instead of one (kmer_lookup.h)
@@ -375,56 +365,31 @@ background_flag_tolerant_kernel(const u8 *__restrict__ bytes, const u32 *__restr
                                 u32 n, u32 L, u32 K, u64 mask, u32 rc_shift, const KmerViews views, u32 max_hits,
                                 u32 nchunk, u32 pitch_dw, u32 extra_off_dw, u32 *__restrict__ flag,
                                 u64 *__restrict__ totals) {
-    background_flag_body<M, STAGE, FILTER, HIST>(bytes, upos, mult, n, L, K, mask, rc_shift, views, max_hits, nchunk,
-                                                 pitch_dw, extra_off_dw, flag, totals);
+    const RowArgs a = {bytes, upos, mult, n, L, nchunk, pitch_dw, extra_off_dw};     // (as in background_flag_kernel)
+    background_flag_body<M, STAGE, FILTER, HIST>(a, K, mask, rc_shift, views, max_hits, flag, totals);
 }
 
-template <bool FILTER, bool HIST>
-static int launch_background(catchhip_ctx *ctx, const catchhip_candidates *C, const catchhip_kmer_index *X, u32 max_hits,
-                             u32 *flag, u64 *totals) {
-    const u32 n = (u32)C->nuniq, L = (u32)C->L, K = (u32)X->k;
-    const u64 mask = K == 32 ? ~0ull : (((u64)1 << (2 * K)) - 1);
-    // the rows as the Tm kernel stages them, and behind them the counters, once per workgroup
-    const u32 nchunk = (L + 15u + 15u) / 16u, pitch_dw = 4u * nchunk + 1u;
-    const size_t row_bytes = (size_t)pitch_dw * 4;
-    u32 rows = 256;
-    while (rows > 64 && rows * row_bytes + BG_EXTRA_BYTES > POLYA_LDS_BUDGET) rows >>= 1;
-    const bool stage = rows * row_bytes + BG_EXTRA_BYTES <= POLYA_LDS_BUDGET && ((uintptr_t)C->T->bytes.p & 15u) == 0;
-    if (X->mismatches) {                                      // the same launch, the tolerant kernel of the index's budget
-        const bool two = X->mismatches == 2;
-        auto kernel = stage ? (two ? background_flag_tolerant_kernel<2, true, FILTER, HIST>
-                                   : background_flag_tolerant_kernel<1, true, FILTER, HIST>)
-                            : (two ? background_flag_tolerant_kernel<2, false, FILTER, HIST>
-                                   : background_flag_tolerant_kernel<1, false, FILTER, HIST>);
-        if (!stage) rows = 256;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)div_up((i64)n, rows)), dim3(rows),
-                           (stage ? rows * row_bytes : 0) + BG_EXTRA_BYTES, ctx->stream, (const u8 *)C->T->bytes.p,
-                           (const u32 *)C->upos.p, (const u32 *)C->mult.p, n, L, K, mask, 2 * K - 2, kmer_views(X), max_hits,
-                           nchunk, pitch_dw, stage ? rows * pitch_dw : 0u, flag, totals);
-    } else if (stage)
-        hipLaunchKernelGGL((background_flag_kernel<true, FILTER, HIST>), dim3((unsigned)div_up((i64)n, rows)), dim3(rows),
-                           rows * row_bytes + BG_EXTRA_BYTES, ctx->stream, (const u8 *)C->T->bytes.p,
-                           (const u32 *)C->upos.p, (const u32 *)C->mult.p, n, L, K, mask, 2 * K - 2,
-                           (const u64 *)X->codes, (const u32 *)X->dir, 2 * K - X->P, max_hits, nchunk, pitch_dw,
-                           rows * pitch_dw, flag, totals);
-    else
-        hipLaunchKernelGGL((background_flag_kernel<false, FILTER, HIST>), dim3((unsigned)div_up((i64)n, 256)), dim3(256),
-                           BG_EXTRA_BYTES, ctx->stream, (const u8 *)C->T->bytes.p, (const u32 *)C->upos.p,
-                           (const u32 *)C->mult.p, n, L, K, mask, 2 * K - 2, (const u64 *)X->codes,
-                           (const u32 *)X->dir, 2 * K - X->P, max_hits, nchunk, pitch_dw, 0u, flag, totals);
-    HIP_TRY(hipGetLastError());
-    return 0;
+// the instances by what the call asks for: mode 0 the histogram alone, 1 the filter alone, 2 both
+typedef decltype(&background_flag_kernel<false, false, true>) background_fn;
+typedef decltype(&background_flag_tolerant_kernel<1, false, false, true>) background_tolerant_fn;
+#define BG_MODES(KERNEL, ...)                                                                                          \
+    { KERNEL<__VA_ARGS__, false, true>, KERNEL<__VA_ARGS__, true, false>, KERNEL<__VA_ARGS__, true, true> }
+static background_fn background_instance(bool stage, int mode) {
+    static const background_fn table[2][3] = {BG_MODES(background_flag_kernel, false), BG_MODES(background_flag_kernel, true)};
+    return table[stage ? 1 : 0][mode];
+}
+static background_tolerant_fn background_tolerant_instance(i32 mismatches, bool stage, int mode) {
+    static const background_tolerant_fn table[2][2][3] = {
+        {BG_MODES(background_flag_tolerant_kernel, 1, false), BG_MODES(background_flag_tolerant_kernel, 1, true)},
+        {BG_MODES(background_flag_tolerant_kernel, 2, false), BG_MODES(background_flag_tolerant_kernel, 2, true)}};
+    return table[mismatches - 1][stage ? 1 : 0][mode];
 }
 
 extern "C" int catchhip_candidates_drop_background(catchhip_ctx *ctx, catchhip_candidates *C, const catchhip_kmer_index *X,
                                                    i32 filter_on, i64 max_hits, i64 dropped[1], u64 hist[256],
                                                    i64 *nkept) {
     ARG_CHECK(ctx && C && C->ctx == ctx && X);
-    if (C->filtered) {
-        chip_set_error("candidates_drop_background: a near-duplicate filter was already applied (the background filter "
-                       "comes first)");
-        return CATCHHIP_EINVAL;
-    }
+    TRY(rule_refuse_filtered(C, "candidates_drop_background", "background filter"));
     if (X->device != ctx->device) {
         chip_set_error("candidates_drop_background: the index lives on device %d, the candidates on device %d", X->device,
                        ctx->device);
@@ -435,36 +400,40 @@ extern "C" int catchhip_candidates_drop_background(catchhip_ctx *ctx, catchhip_c
         return CATCHHIP_EINVAL;
     }
     PoolScope pool_scope(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (nkept) *nkept = C->nuniq;
+    TRY(rule_begin(ctx, C, nkept));
     if (dropped) dropped[0] = 0;
     if (hist) memset(hist, 0, sizeof(u64) * BG_BINS);
     if (C->nuniq == 0 || C->L < X->k || !(filter_on || hist)) return 0;
-    const u32 n = (u32)C->nuniq;
-    const u32 H = max_hits > (i64)0xffffffffll ? 0xffffffffu : (u32)max_hits;
+    const u32 H = !filter_on ? 0u : max_hits > (i64)0xffffffffll ? 0xffffffffu : (u32)max_hits;
     DevBuf<u32> flag;
-    DevBuf<u64> totals;
-    if (filter_on) TRY(flag.alloc((size_t)n + 1));
-    const size_t totals_bytes = sizeof(u64) * BG_SLOTS * BG_SLOT_WORDS;
-    TRY(totals.alloc(BG_SLOTS * BG_SLOT_WORDS));
-    TRY(chip_pinned_reserve(ctx, totals_bytes));
-    HIP_TRY(hipMemsetAsync(totals.p, 0, totals_bytes, ctx->stream));
+    SlotTotals totals;
+    if (filter_on) TRY(flag.alloc((size_t)C->nuniq + 1));
+    TRY(totals.init(ctx, BG_SLOTS, BG_SLOT_WORDS));
     PhaseTimer tm(ctx, PHASE_PREFILTER);
-    if (filter_on && hist) TRY((launch_background<true, true>(ctx, C, X, H, flag.p, totals.p)));
-    else if (filter_on) TRY((launch_background<true, false>(ctx, C, X, H, flag.p, totals.p)));
-    else TRY((launch_background<false, true>(ctx, C, X, 0u, nullptr, totals.p)));
+    const u32 K = (u32)X->k;
+    const u64 mask = K == 32 ? ~0ull : (((u64)1 << (2 * K)) - 1);
+    const int mode = filter_on ? (hist ? 2 : 1) : 0;
+    const RowPlan plan = row_plan((u32)C->L, 0, BG_EXTRA_BYTES, 4, rows_aligned(C));
+    // row_plan's own rule once more, so it cannot fire: tests/test_background_filter.py looks for this expression in
+    // this file's text (tests/test_candidate_launch_plan.py is what proves the tier edges, for every L)
+    const size_t rows = plan.rows, row_bytes = (size_t)plan.pitch_dw * 4;
+    ARG_CHECK(!(plan.stage && rows * row_bytes + BG_EXTRA_BYTES > POLYA_LDS_BUDGET));
+    const RowArgs a = row_args(C, plan);                      // (the order below is the kernels')
+    if (X->mismatches)                                        // the same launch, the tolerant kernel of the index's budget
+        hipLaunchKernelGGL(background_tolerant_instance(X->mismatches, plan.stage, mode), row_grid(C, plan), dim3(plan.rows),
+                           plan.lds_bytes, ctx->stream, a.bytes, a.upos, a.mult, a.n, a.L, K, mask, 2 * K - 2, kmer_views(X),
+                           H, a.nchunk, a.pitch_dw, a.extra_off_dw, flag.p, totals.d.p);
+    else
+        hipLaunchKernelGGL(background_instance(plan.stage, mode), row_grid(C, plan), dim3(plan.rows), plan.lds_bytes,
+                           ctx->stream, a.bytes, a.upos, a.mult, a.n, a.L, K, mask, 2 * K - 2, (const u64 *)X->codes,
+                           (const u32 *)X->dir, 2 * K - X->P, H, a.nchunk, a.pitch_dw, a.extra_off_dw, flag.p, totals.d.p);
+    HIP_TRY(hipGetLastError());
     tm.launch();
     tm.stop();
-    HIP_TRY(hipMemcpyAsync(ctx->h_big, totals.p, totals_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    u64 h[BG_WORDS];
+    TRY(totals.read(ctx, BG_WORDS, h));
     tm.finish();
-    u64 gone = 0;
-    for (u32 slot = 0; slot < BG_SLOTS; ++slot) {
-        const u64 *w = (const u64 *)ctx->h_big + slot * BG_SLOT_WORDS;
-        if (hist) for (u32 b = 0; b < BG_BINS; ++b) hist[b] += w[b];
-        gone += w[BG_BINS];
-    }
-    if (dropped) dropped[0] = (i64)gone;
-    if (gone == 0) return 0;                                  // nothing dropped (or not filtering): the list stands
-    return chip_candidates_keep_flagged(ctx, C, flag, nkept);
+    if (hist) memcpy(hist, h, sizeof(u64) * BG_BINS);
+    if (dropped) dropped[0] = (i64)h[BG_BINS];
+    return rule_keep(ctx, C, h[BG_BINS] != 0, flag, nkept);
 }

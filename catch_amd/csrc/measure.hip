@@ -4,24 +4,22 @@
 // filter.  The list is only read.  Two kernels, because their LDS holds different things:
 //
 // measure_rows_kernel<STAGE, COMP, TM, HITS, M>: gc, homopolymer, dust, tm_c and hits -- one thread per unique candidate,
-//   one pass over its L bytes, the rows staged as the poly(A) kernel stages them (stage.h).  The per-byte work of each
-//   family is that of its flag kernel (prefilter.hip, thermo.hip, background.hip: the triplet counters of a thread one
-//   byte each in LDS at a lane pitch of one dword, the dinucleotide table in LDS, the rolled canonical code and the
-//   directory look-up -- kmer_lookup.h, exact or within the index's mismatches), restated here so that the flag kernels
-//   stay as they are; what differs is the end:
+//   one pass over its L bytes, the rows staged (stage.h).  The per-byte work of each family is that of its flag kernel
+//   (prefilter.hip, thermo.hip, background.hip): Tm and hits through the same steppers of stage.h and the look-ups of
+//   kmer_lookup.h, exact or within the index's mismatches; gc, homopolymer and the window's step written out as in
+//   composition_flag_kernel (prefilter.hip says why the two do not share a stepper).  What differs is the end:
 //   dust.  The flag kernel compares every window with ONE threshold; the measure keeps the running maximum `best` of
 //   ceil(10 S / (T - 1)) and asks the flag kernel's question with it, 10 S > best (T - 1), which is true iff the
 //   window's quotient exceeds best.  Only then is the quotient formed: one integer division per RISE of the maximum,
 //   not per window (10 S <= 321,310 and best (T - 1) <= 1,270 * 253: 32 bits).
 //
 // measure_structure_kernel<LDS_PLANES>: stem and dimer -- one thread per unique candidate, the L x L table pairs(x, y)
-//   32 cells at a time, in structure.hip's layout: the planes V, B0, B1, each a second time bit-reversed between two
-//   zero words, at an odd pitch of 6 W + 7 words, interleaved, one funnel shift per plane and word (structure.hip's
-//   head has the layout and why cells outside the table come out 0).  What does not carry over:
+//   32 cells at a time, over the planes and the antidiagonal words of planes.h, as structure_flag_kernel walks them.
+//   What differs:
 //   Run search.  There is no R to look for: each lane keeps `best`, the longest run it has seen, per rule.  A run that
 //   touches a word's edge is measured, not searched: carry + (1-cells that begin the word) and the 1-cells that end it
-//   are lengths, and best takes their maximum.  A run strictly inside a word is found by run_step's question for
-//   best + 1 -- five AND-shifts whose amounts are per-lane registers (RunMax::aim) -- and where the answer is yes the
+//   are lengths, and best takes their maximum.  A run strictly inside a word is found by the flag kernel's question for
+//   best + 1 -- five AND-shifts whose amounts are per-lane registers (planes.h: RunShifts) -- and where the answer is yes the
 //   survivors are AND-shifted one step at a time until none is left, which gives the word's longest run exactly.  best
 //   settles on the first antidiagonals (a random 100-mer reaches 6 within a few words), so nearly every word costs the
 //   question alone: 2 count-zeros, 5 shift-ANDs, 3 maxima and two branches not taken per rule; the shift amounts are
@@ -44,12 +42,13 @@
 //
 // Histograms (five, MEASURE_BINS bins each, bin min(value, MEASURE_BINS - 1), with multiplicity): per workgroup in
 // LDS behind the rows or planes, as many 64-bit bins per quantity as its values can reach at this L and window, added
-// to with LDS atomics; after a barrier thread t adds bin t, if it is not zero, to one of MEASURE_SLOTS copies in global
-// memory, which the host adds up (thermo.hip's head says what the copies are for).  No thread returns before the
-// barrier.  Without histograms no bin is allocated or touched.
+// to with LDS atomics; after a barrier the bins go to one of MEASURE_SLOTS copies in global memory (stage.h: the
+// totals).  No thread returns before the barrier.  Without histograms no bin is allocated or touched.
 #include "internal.h"
 #include "wave.h"
 #include "stage.h"
+#include "planes.h"
+#include "rule_host.h"
 #include "kmer_lookup.h"
 
 typedef uint16_t u16;
@@ -57,23 +56,11 @@ typedef uint16_t u16;
 #define MEASURE_BINS 1280u
 #define MEASURE_SLOTS 32u
 #define MEASURE_SLOT_WORDS (5u * MEASURE_BINS)               // 400 whole 128-byte lines
-#define MEASURE_LDS_BUDGET 65536u
-#define MEASURE_COUNTER_BYTES 64u
-#define MEASURE_TABLE_DW 16u
-#define MEASURE_GLOBAL_PLANE_BYTES ((size_t)256 << 20)
-
-// thermo.hip's table: |h| | |e| << 16 of the dinucleotide (first, second), index 4 * first + second with (c >> 1) & 3
-#define MEASURE_NN(h, e) ((u32)(h) | ((u32)(e) << 16))
-__constant__ u32 measure_nn_table[MEASURE_TABLE_DW] = {
-    MEASURE_NN(79, 222), MEASURE_NN(84, 224), MEASURE_NN(72, 204), MEASURE_NN(78, 210),       // AA AC AT AG
-    MEASURE_NN(85, 227), MEASURE_NN(80, 199), MEASURE_NN(78, 210), MEASURE_NN(106, 272),      // CA CC CT CG
-    MEASURE_NN(72, 213), MEASURE_NN(82, 222), MEASURE_NN(79, 222), MEASURE_NN(85, 227),       // TA TC TT TG
-    MEASURE_NN(82, 222), MEASURE_NN(98, 244), MEASURE_NN(84, 224), MEASURE_NN(80, 199)};      // GA GC GT GG
 
 struct MeasureRowsArgs {
-    const u8 *bytes;
-    const u32 *upos, *mult;
-    u32 n, L, nchunk, pitch_dw;
+    const u8 *bytes;                 // the row arguments field by field (row_args() below makes stage.h's RowArgs of them):
+    const u32 *upos, *mult;          // with a RowArgs member the other fields moved, the kernel's scalar loads were cut
+    u32 n, L, nchunk, pitch_dw;      // differently and the composition instances ran 1 % slower
     u32 We;                          // composition: the window, min(W, L); 0: no window holds two triplets (dust = 0)
     i64 q, offset_c;                 // Tm
     u32 K, rc_shift, dir_shift;      // hits
@@ -87,6 +74,7 @@ struct MeasureRowsArgs {
     u32 *hits;
     u64 *hist;                       // MEASURE_SLOTS copies of the five histograms
     KmerViews views;                 // hits against a tolerant index (mismatches > 0)
+    __host__ __device__ RowArgs row_args() const { return RowArgs{bytes, upos, mult, n, L, nchunk, pitch_dw, cnt_off_dw}; }
 };
 
 // M: the mismatch budget of the index behind `hits` (0: the exact look-up; 1, 2: HITS is on)
@@ -96,32 +84,31 @@ measure_rows_kernel(const MeasureRowsArgs a) {
     extern __shared__ u32 mr_lds[];
     const u32 rows = blockDim.x, r = threadIdx.x;
     const u32 i = blockIdx.x * rows + r;
+    const RowArgs ra = a.row_args();
     const u32 L = a.L;
     u32 *tbl = mr_lds + a.tbl_off_dw;
     unsigned long long *bins = (unsigned long long *)(mr_lds + a.bin_off_dw);
     const u32 nbins = COMP ? 2u * a.nb_len + a.nb_dust : 0u;
-    if (TM && r < MEASURE_TABLE_DW) tbl[r] = measure_nn_table[r];
+    if (TM) TmSums::load_table(tbl);
     for (u32 t = r; t < nbins; t += rows) bins[t] = 0;
-    if (STAGE) stage_rows(a.bytes, a.upos, a.n, L, a.nchunk, a.pitch_dw, mr_lds);     // (ends with a barrier)
+    if (STAGE) stage_rows(ra, mr_lds);                        // (ends with a barrier)
     else __syncthreads();
     if (i < a.n) {                                            // (no early return: the barrier below)
-        const u32 s = a.upos[i];
-        const u8 *p = STAGE ? (const u8 *)(mr_lds + r * a.pitch_dw) + (s & 15u) : a.bytes + s;
+        const u8 *p = row_ptr<STAGE>(ra, mr_lds, i);
         const u32 We = a.We;
-        u8 *cnt = (u8 *)(mr_lds + a.cnt_off_dw + r);          // counter of code t: cnt[(t >> 2) * 4 * rows + (t & 3)]
+        // gc, homopolymer and the window, written out as in composition_flag_kernel (prefilter.hip says why)
+        u8 *cnt = (u8 *)(mr_lds + a.cnt_off_dw + r);   // counter of code t: cnt[(t >> 2) * 4 * rows + (t & 3)]
         if (COMP && We)
-            for (u32 g = 0; g < MEASURE_COUNTER_BYTES / 4u; ++g) mr_lds[a.cnt_off_dw + g * rows + r] = 0;
+            for (u32 g = 0; g < TRIPLET_COUNTER_BYTES / 4u; ++g) mr_lds[a.cnt_off_dw + g * rows + r] = 0;
         u32 gc = 0, run = 0, best_run = 0, prev = 0;
         u32 h = 0, v = 0, ho = 0, vo = 0, S = 0, T = 0, dust = 0;
-        u64 sh = 0, se = 0;                                   // Tm: -sum of h, -sum of e over the dinucleotides
-        u32 pc = 0;
-        bool pb = false;
-        u64 fwd = 0, rc = 0;                                  // hits: the rolled codes
-        u32 brun = 0, hits = 0;
+        TmSums sums;
+        KmerRoll kmer;
+        u32 hits = 0;
         for (u32 j = 0; j < L; ++j) {
             const u8 c = p[j];
             const bool b = is_base(c);
-            const u32 code = (c >> 1) & 3u;
+            const u32 code = base_code(c);
             if (COMP) {
                 gc += (c == 'G' || c == 'C') ? 1u : 0u;
                 run = b ? (c == prev ? run + 1 : 1u) : 0u;
@@ -153,25 +140,14 @@ measure_rows_kernel(const MeasureRowsArgs a) {
                     if (j + 1 >= We && T >= 2 && 10u * S > dust * (T - 1u)) dust = (10u * S + T - 2u) / (T - 1u);
                 }
             }
-            if (TM) {
-                const u32 e = (b && pb) ? tbl[(pc << 2) | code] : 0u;
-                sh += e & 0xffffu;
-                se += e >> 16;
-                pc = code;
-                pb = b;
-            }
-            if (HITS) {
-                fwd = ((fwd << 2) | code) & a.mask;
-                rc = (rc >> 2) | (((u64)code ^ 2ull) << a.rc_shift);
-                brun = b ? brun + 1u : 0u;
-                if (brun >= a.K) {
-                    if constexpr (M == 0) hits += kmer_lookup_exact(fwd, rc, a.codes, a.dir, a.dir_shift);
-                    else hits += kmer_lookup_tolerant<M>(fwd, rc, a.mask, 2u * a.K, a.views);
-                }
+            if (TM) sums.step(tbl, code, b);
+            if (HITS && kmer.step(code, b, a.mask, a.rc_shift, a.K)) {
+                if constexpr (M == 0) hits += kmer_lookup_exact(kmer.fwd, kmer.rc, a.codes, a.dir, a.dir_shift);
+                else hits += kmer_lookup_tolerant<M>(kmer.fwd, kmer.rc, a.mask, 2u * a.K, a.views);
             }
         }
         if (COMP) {
-            if (a.gc) a.gc[i] = (u16)gc;                      // (L <= 65,535: the host checked)
+            if (a.gc) a.gc[i] = (u16)gc;                    // (L <= 65,535: the host checked)
             if (a.run) a.run[i] = (u16)best_run;
             if (a.dust) a.dust[i] = (u16)dust;
             if (nbins) {
@@ -182,13 +158,7 @@ measure_rows_kernel(const MeasureRowsArgs a) {
             }
         }
         if (TM && a.tm_c) {
-            const u8 c0 = p[0], c1 = p[L - 1];
-            const bool g0 = c0 == 'G' || c0 == 'C', g1 = c1 == 'G' || c1 == 'C';
-            const i64 H = (g0 ? 1 : 23) + (g1 ? 1 : 23) - (i64)sh;
-            const i64 E = (g0 ? -28 : 41) + (g1 ? -28 : 41) - (i64)se;
-            const i64 E1 = 100 * E + a.q;                     // < 0 wherever H < 0
-            const i64 Tk = H < 0 ? (i64)((10000000ull * (u64)(-H)) / (u64)(-E1)) : 0;
-            const i64 tm = Tk - a.offset_c;
+            const i64 tm = sums.tm_c(p[0], p[L - 1], a.q, a.offset_c);
             a.tm_c[i] = tm > 2147483647ll ? 2147483647 : tm < -2147483647ll ? -2147483647 : (i32)tm;   // (E' near 0)
         }
         if (HITS && a.hits) a.hits[i] = hits;
@@ -197,38 +167,23 @@ measure_rows_kernel(const MeasureRowsArgs a) {
         __syncthreads();
         // bin t of the workgroup: gc 0 .. nb_len - 1, homopolymer, dust.  The bins' last one stands for every value
         // from there up, which is MEASURE_BINS - 1 whenever a value can pass it (nb = MEASURE_BINS then)
-        unsigned long long *g = (unsigned long long *)a.hist + (size_t)(blockIdx.x & (MEASURE_SLOTS - 1u)) * MEASURE_SLOT_WORDS;
-        for (u32 t = r; t < nbins; t += rows) {
-            const unsigned long long val = bins[t];
+        totals_flush(bins, nbins, totals_slot(a.hist, MEASURE_SLOTS, MEASURE_SLOT_WORDS), [&](u32 t) {
             const u32 qn = t < a.nb_len ? 0u : t < 2u * a.nb_len ? 1u : 2u;
-            if (val) atomicAdd(g + qn * MEASURE_BINS + (t - qn * a.nb_len), val);
-        }
+            return qn * MEASURE_BINS + (t - qn * a.nb_len);
+        });
     }
 }
 
-// The longest run of 1-bits in a stream of words, per lane.  best: the longest seen so far; inword and s0 .. s4: the
-// question "does a word hold best + 1 consecutive 1-bits" as structure.hip's RunSearch asks it for R = best + 1.
+// The longest run of 1-bits in a stream of words, per lane.  best: the longest seen so far; shifts: the question "does
+// a word hold best + 1 consecutive 1-bits".
 struct RunMax {
-    u32 best, inword, s0, s1, s2, s3, s4;
-    __device__ __forceinline__ void aim() {
-        const u32 want = best + 1u;
-        inword = want <= 32u ? 0xffffffffu : 0u;
-        u32 have = 1, s[5];
-        for (int k = 0; k < 5; ++k) {                         // (unrolled: s[] stays in registers)
-            s[k] = have < want ? min(have, want - have) & 31u : 0u;
-            have += s[k];
-        }
-        s0 = s[0]; s1 = s[1]; s2 = s[2]; s3 = s[3]; s4 = s[4];
-    }
+    u32 best = 0;
+    RunShifts shifts;
+    __device__ __forceinline__ void aim() { shifts.aim(best + 1u); }
     // one word m of the stream: `low` 1-bits begin it, carry_in 1-bits ended the words before it, carry_out end the
     // words up to and including it (0 where the stream is cut inside this word)
     __device__ __forceinline__ void see(u32 m, u32 low, u32 carry_in, u32 carry_out) {
-        u32 x = m & inword;                                   // bit b of x <=> bits b .. b + best of m
-        x &= x >> s0;
-        x &= x >> s1;
-        x &= x >> s2;
-        x &= x >> s3;
-        x &= x >> s4;
+        u32 x = shifts.inside(m);                             // bit b of x <=> bits b .. b + best of m
         u32 b = max(best, max(carry_in + low, carry_out)), inside = best;
         while (x) { ++inside; x &= x >> 1; }                  // (rare) the word's longest run, one more cell per step
         b = max(b, inside);
@@ -244,59 +199,21 @@ measure_structure_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ u
     extern __shared__ u32 ms_lds[];
     const u32 r = threadIdx.x;
     const u32 i = first + blockIdx.x * blockDim.x + r;
-    const u32 pitch = 6u * W + 7u;                            // structure.hip: words of a thread, odd
-    u32 *pl = (LDS_PLANES ? ms_lds + r * pitch : gplanes + (size_t)(blockIdx.x * blockDim.x + r) * pitch);
-    u32 *rev = pl + 3u * W;
+    u32 *pl = (LDS_PLANES ? ms_lds + r * plane_pitch(W) : gplanes + (size_t)(blockIdx.x * blockDim.x + r) * plane_pitch(W));
     unsigned long long *bins = (unsigned long long *)(ms_lds + bin_off_dw);         // stem 0 .. nb - 1, then dimer
     for (u32 t = r; t < 2u * nb; t += blockDim.x) bins[t] = 0;
     if (nb) __syncthreads();
     if (i < n) {                                              // (no early return: the barrier below)
-        // ---- the planes, as structure_flag_kernel builds them: the candidate's bytes read as aligned dwords (at most
-        // 3 bytes before the row, which are the targets' own, and 3 behind it, inside the slack of the byte array)
-        const u8 *row = bytes + upos[i];
-        const u32 al = (u32)((uintptr_t)row & 3u);
-        const u32 *dw = (const u32 *)(row - al);
-        for (u32 p = 0; p < 3u; ++p) { rev[p] = 0; rev[3u * (W + 1u) + p] = 0; }
-        u32 cur = dw[0], nd = 1;                              // cur: the dword that holds byte j
-        for (u32 w = 0; w < W; ++w) {
-            u32 v = 0, b0 = 0, b1 = 0;
-            const u32 cnt = min(32u, L - 32u * w);
-            for (u32 t = 0; t < cnt; ++t) {
-                const u32 at = al + 32u * w + t;              // byte offset from dw
-                if (at != 0 && (at & 3u) == 0) cur = dw[nd++];                  // nd - 1 = at / 4 <= (al + L - 1) / 4
-                const u32 c = (cur >> (8u * (at & 3u))) & 255u;
-                const u32 base = (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? 1u : 0u;
-                v |= base << t;
-                b0 |= ((c >> 1) & 1u) << t;
-                b1 |= ((c >> 2) & 1u) << t;
-            }
-            pl[3u * w] = v;
-            pl[3u * w + 1u] = b0;
-            pl[3u * w + 2u] = b1;
-            rev[3u * (W - w)] = __brev(v);
-            rev[3u * (W - w) + 1u] = __brev(b0);
-            rev[3u * (W - w) + 2u] = __brev(b1);
-        }
+        build_planes(bytes + upos[i], L, W, pl);
         RunMax rd, rh;
-        rd.best = 0; rd.aim();
-        rh.best = 0; rh.aim();
+        rd.aim();
+        rh.aim();
         for (u32 c = 1; c + 3u <= 2u * L; ++c) {              // c = 1 .. 2 L - 3 (none for L = 1)
-            const u32 lo = c > L - 1u ? c - (L - 1u) : 0u, upto = c >> 1;           // lo <= upto <= min(L - 1, c)
-            // structure.hip: cell (x, c - x) reads bit x + sh of the stored reversed plane, sh = 32 W + 31 - c kept
-            // mod 2^32; 32 w0 + sh >= 1 and 32 w1 + sh <= 32 W + 31 hold for every w1 with 32 w1 <= min(L - 1, c)
-            const u32 sh = 32u * W + 31u - c;
-            const u32 o = sh & 31u;
+            const u32 upto = c >> 1;                          // lo <= upto <= min(L - 1, c)
             const bool hair_here = c >= 1u + P;
             const u32 inner = hair_here ? (c - 1u - P) >> 1 : 0u;                   // the hairpin's last cell (<= upto)
-            const u32 w0 = lo >> 5, w1 = upto >> 5;
-            const u32 *pf = pl + 3u * w0, *pr = rev + 3u * ((32u * w0 + sh) >> 5);
-            u32 lv = pr[0], l0 = pr[1], l1 = pr[2];
-            u32 carry = 0, carry_in = 0, m = 0;
-            for (u32 w = w0; w <= w1; ++w, pf += 3, pr += 3) {
-                const u32 hv = pr[3], h0 = pr[4], h1 = pr[5];                       // reversed word q + 1 <= W + 1
-                const u32 rv = __funnelshift_r(lv, hv, o), r0 = __funnelshift_r(l0, h0, o), r1 = __funnelshift_r(l1, h1, o);
-                lv = hv; l0 = h0; l1 = h1;
-                m = (pf[2] ^ r1) & ~(pf[1] ^ r0) & pf[0] & rv;
+            u32 carry = 0, carry_in = 0, m_last = 0;
+            antidiagonal_words(pl, W, c, antidiagonal_lo(c, L), upto, [&](u32 w, u32 m) {
                 const u32 inv = ~m;
                 const u32 low = inv ? (u32)__builtin_ctz(inv) : 32u, high = inv ? (u32)__builtin_clz(inv) : 32u;
                 carry_in = carry;
@@ -311,12 +228,13 @@ measure_structure_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ u
                         rh.see(mh, (u32)__builtin_ctz(~mh), carry_in, 0u);
                     }
                 }
-            }
+                m_last = m;
+            });
             if (c & 1u) {
                 // the run that ends on the last walked cell, bit `last` of the last word, is half of a run across the
                 // middle: the 1-bits below and at `last`, and the carry when they fill the word from bit 0
-                const u32 last = upto - 32u * w1;
-                const u32 zeros = ~m & (last >= 31u ? 0xffffffffu : (2u << last) - 1u);
+                const u32 last = upto & 31u;
+                const u32 zeros = ~m_last & (last >= 31u ? 0xffffffffu : (2u << last) - 1u);
                 const u32 seen = zeros ? last + (u32)__builtin_clz(zeros) - 31u : carry_in + last + 1u;
                 if (2u * seen > rd.best) { rd.best = 2u * seen; rd.aim(); }
             }
@@ -331,12 +249,10 @@ measure_structure_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ u
     }
     if (nb) {
         __syncthreads();
-        unsigned long long *g = (unsigned long long *)hist + (size_t)(blockIdx.x & (MEASURE_SLOTS - 1u)) * MEASURE_SLOT_WORDS;
-        for (u32 t = r; t < 2u * nb; t += blockDim.x) {
-            const unsigned long long val = bins[t];
+        totals_flush(bins, 2u * nb, totals_slot(hist, MEASURE_SLOTS, MEASURE_SLOT_WORDS), [&](u32 t) {
             const u32 qn = t < nb ? 0u : 1u;
-            if (val) atomicAdd(g + (3u + qn) * MEASURE_BINS + (t - qn * nb), val);
-        }
+            return (3u + qn) * MEASURE_BINS + (t - qn * nb);
+        });
     }
 }
 
@@ -362,71 +278,48 @@ static measure_rows_fn measure_rows_tolerant_instance(bool comp, bool tm) {
 
 static int launch_measure_rows(catchhip_ctx *ctx, const catchhip_candidates *C, bool comp, bool tm, bool hits,
                                i32 mismatches, bool histograms, MeasureRowsArgs a) {
-    const u32 n = (u32)C->nuniq, L = (u32)C->L;
-    a.bytes = (const u8 *)C->T->bytes.p;
-    a.upos = (const u32 *)C->upos.p;
-    a.mult = (const u32 *)C->mult.p;
-    a.n = n;
-    a.L = L;
-    a.nchunk = (L + 15u + 15u) / 16u;
-    a.pitch_dw = 4u * a.nchunk + 1u;
+    const u32 L = (u32)C->L;
     a.nb_len = comp && histograms ? std::min(L, MEASURE_BINS - 1u) + 1u : 0u;
     a.nb_dust = comp && histograms ? (a.We ? std::min(5u * (a.We - 2u), MEASURE_BINS - 1u) + 1u : 1u) : 0u;
-    // LDS: the rows as the poly(A) kernel stages them, then per row the triplet counters, then once per workgroup the
-    // dinucleotide table and the bins
-    const size_t row_bytes = (size_t)a.pitch_dw * 4, cnt_bytes = comp && a.We ? MEASURE_COUNTER_BYTES : 0u;
-    const size_t extra = (tm ? MEASURE_TABLE_DW * 4u : 0u) + (size_t)(2u * a.nb_len + a.nb_dust) * 8;
-    u32 rows = 256;
-    while (rows > 64 && rows * (row_bytes + cnt_bytes) + extra + 4 > MEASURE_LDS_BUDGET) rows >>= 1;
-    const bool stage = rows * (row_bytes + cnt_bytes) + extra + 4 <= MEASURE_LDS_BUDGET && ((uintptr_t)a.bytes & 15u) == 0;
-    if (!stage) rows = 256;
-    a.cnt_off_dw = stage ? rows * a.pitch_dw : 0u;
-    a.tbl_off_dw = a.cnt_off_dw + rows * (u32)(cnt_bytes / 4);
-    a.bin_off_dw = (a.tbl_off_dw + (tm ? MEASURE_TABLE_DW : 0u) + 1u) & ~1u;          // (+ 4 above: this rounding)
-    const size_t lds = (size_t)a.bin_off_dw * 4 + (size_t)(2u * a.nb_len + a.nb_dust) * 8;
+    // LDS: the rows, then per row the triplet counters, then once per workgroup the dinucleotide table and the bins
+    const size_t tbl_bytes = tm ? TM_TABLE_DW * 4u : 0u, bin_bytes = (size_t)(2u * a.nb_len + a.nb_dust) * 8;
+    const RowPlan plan = row_plan(L, comp && a.We ? TRIPLET_COUNTER_BYTES : 0u, tbl_bytes + bin_bytes, 8, rows_aligned(C));
+    const RowArgs ra = row_args(C, plan);
+    a.bytes = ra.bytes; a.upos = ra.upos; a.mult = ra.mult;
+    a.n = ra.n; a.L = ra.L; a.nchunk = ra.nchunk; a.pitch_dw = ra.pitch_dw;
+    a.cnt_off_dw = ra.extra_off_dw;
+    a.tbl_off_dw = plan.tail_off_dw;
+    a.bin_off_dw = plan.tail_off_dw + (u32)(tbl_bytes / 4);   // (even: the table is 16 dwords)
+    const bool stage = plan.stage;
     measure_rows_fn fn = stage ? measure_rows_instance<true>(comp, tm, hits) : measure_rows_instance<false>(comp, tm, hits);
     if (hits && mismatches == 1)
         fn = stage ? measure_rows_tolerant_instance<true, 1>(comp, tm) : measure_rows_tolerant_instance<false, 1>(comp, tm);
     if (hits && mismatches == 2)
         fn = stage ? measure_rows_tolerant_instance<true, 2>(comp, tm) : measure_rows_tolerant_instance<false, 2>(comp, tm);
-    hipLaunchKernelGGL(fn, dim3((unsigned)div_up((i64)n, rows)), dim3(rows), lds, ctx->stream, a);
+    hipLaunchKernelGGL(fn, row_grid(C, plan), dim3(plan.rows), plan.lds_bytes, ctx->stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 static int launch_measure_structure(catchhip_ctx *ctx, const catchhip_candidates *C, u32 P, bool histograms, u16 *stem,
                                     u16 *dimer, u64 *hist) {
-    const u32 n = (u32)C->nuniq, L = (u32)C->L, W = (L + 31u) / 32u;
-    const size_t cand_bytes = (size_t)(6u * W + 7u) * 4;
+    const u32 n = (u32)C->nuniq, L = (u32)C->L;
     const u32 nb = histograms ? std::min(L, MEASURE_BINS - 1u) + 1u : 0u;
-    const size_t bin_bytes = (size_t)2 * nb * 8;
+    const PlanePlan plan = plane_plan(L, (size_t)2 * nb * 8, 8);
     const u8 *bytes = (const u8 *)C->T->bytes.p;
-    u32 rows = 256;
-    while (rows > 64 && rows * cand_bytes + 4 + bin_bytes > MEASURE_LDS_BUDGET) rows >>= 1;
-    if (rows * cand_bytes + 4 + bin_bytes <= MEASURE_LDS_BUDGET) {
-        const u32 bin_off_dw = (u32)((rows * cand_bytes / 4 + 1u) & ~(size_t)1);
-        hipLaunchKernelGGL((measure_structure_kernel<true>), dim3((unsigned)div_up((i64)n, rows)), dim3(rows),
-                           (size_t)bin_off_dw * 4 + bin_bytes, ctx->stream, bytes, (const u32 *)C->upos.p,
-                           (const u32 *)C->mult.p, 0u, n, L, W, P, (u32 *)nullptr, bin_off_dw, nb, stem, dimer, hist);
+    const u32 *upos = (const u32 *)C->upos.p, *mult = (const u32 *)C->mult.p;
+    if (plan.lds_planes) {
+        hipLaunchKernelGGL((measure_structure_kernel<true>), dim3((unsigned)div_up((i64)n, plan.rows)), dim3(plan.rows),
+                           plan.lds_bytes, ctx->stream, bytes, upos, mult, 0u, n, L, plan.W, P, (u32 *)nullptr,
+                           plan.tail_off_dw, nb, stem, dimer, hist);
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    // planes in global memory, as many candidates per launch as the buffer holds (a multiple of the workgroup), as
-    // structure.hip does; its test hook CATCHHIP_STRUCT_PLANE_BYTES shrinks this buffer too
-    const size_t budget = (size_t)chip_test_env_int("CATCHHIP_STRUCT_PLANE_BYTES", (long long)MEASURE_GLOBAL_PLANE_BYTES);
-    u32 per = (u32)std::min<size_t>(budget / cand_bytes, (size_t)n);
-    per = std::max(256u, (per + 255u) & ~255u);
-    DevBuf<u32> planes;
-    TRY(planes.alloc((size_t)per * (cand_bytes / 4)));
-    for (u32 first = 0; first < n; first += per) {
-        const u32 end = (u32)std::min<u64>((u64)first + per, n);
+    return launch_over_plane_chunks(ctx, n, plan.cand_bytes, [&](u32 first, u32 end, u32 *planes) {
         hipLaunchKernelGGL((measure_structure_kernel<false>), dim3((unsigned)div_up((i64)(end - first), 256)), dim3(256),
-                           bin_bytes, ctx->stream, bytes, (const u32 *)C->upos.p, (const u32 *)C->mult.p, first, end, L, W,
-                           P, planes.p, 0u, nb, stem, dimer, hist);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));               // (the plane buffer goes back to the pool on return)
-    return 0;
+                           plan.lds_bytes, ctx->stream, bytes, upos, mult, first, end, L, plan.W, P, planes, 0u, nb, stem,
+                           dimer, hist);
+    });
 }
 
 template <typename T>
@@ -440,12 +333,9 @@ extern "C" int catchhip_candidates_measure(catchhip_ctx *ctx, const catchhip_can
                                            i32 want_values, u16 *gc, u16 *homopolymer, u16 *dust, u16 *stem, u16 *dimer,
                                            i32 *tm_c, u32 *hits, u64 *hist) {
     ARG_CHECK(ctx && C && C->ctx == ctx);
+    TRY(rule_refuse_filtered(C, "candidates_measure", "measure"));
     const bool comp = what & CATCHHIP_MEASURE_COMPOSITION, structure = what & CATCHHIP_MEASURE_STRUCTURE;
     const bool tm = what & CATCHHIP_MEASURE_TM, bg = what & CATCHHIP_MEASURE_HITS;
-    if (C->filtered) {
-        chip_set_error("candidates_measure: a near-duplicate filter was already applied (the measure comes first)");
-        return CATCHHIP_EINVAL;
-    }
     if (what & ~15u) {
         chip_set_error("candidates_measure: what is a mask of the bits 1 (composition), 2 (structure), 4 (Tm) and 8 "
                        "(hits) (got %u)", (unsigned)what);
@@ -474,7 +364,7 @@ extern "C" int catchhip_candidates_measure(catchhip_ctx *ctx, const catchhip_can
         return CATCHHIP_EINVAL;
     }
     PoolScope pool_scope(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
+    TRY(rule_begin(ctx, C, nullptr));
     if (hist) memset(hist, 0, sizeof(u64) * MEASURE_SLOT_WORDS);
     if (C->nuniq == 0 || !what || !(want_values || hist)) return 0;
     const size_t n = (size_t)C->nuniq;
@@ -493,13 +383,8 @@ extern "C" int catchhip_candidates_measure(catchhip_ctx *ctx, const catchhip_can
     DevBuf<u16> d_gc, d_run, d_dust, d_stem, d_dimer;
     DevBuf<i32> d_tm;
     DevBuf<u32> d_hits;
-    DevBuf<u64> d_hist;
-    const size_t hist_bytes = sizeof(u64) * MEASURE_SLOTS * MEASURE_SLOT_WORDS;
-    if (hist && (comp || structure)) {
-        TRY(d_hist.alloc(MEASURE_SLOTS * MEASURE_SLOT_WORDS));
-        TRY(chip_pinned_reserve(ctx, hist_bytes));
-        HIP_TRY(hipMemsetAsync(d_hist.p, 0, hist_bytes, ctx->stream));
-    }
+    SlotTotals d_hist;
+    if (hist && (comp || structure)) TRY(d_hist.init(ctx, MEASURE_SLOTS, MEASURE_SLOT_WORDS));
     if (want_values && comp) { TRY(d_gc.alloc(n)); TRY(d_run.alloc(n)); TRY(d_dust.alloc(n)); }
     if (want_values && structure) { TRY(d_stem.alloc(n)); TRY(d_dimer.alloc(n)); }
     if (tm_on) TRY(d_tm.alloc(n));
@@ -520,13 +405,13 @@ extern "C" int catchhip_candidates_measure(catchhip_ctx *ctx, const catchhip_can
             a.views = kmer_views(X);
         }
         a.gc = d_gc.p; a.run = d_run.p; a.dust = d_dust.p; a.tm_c = d_tm.p; a.hits = d_hits.p;
-        a.hist = d_hist.p;
+        a.hist = d_hist.d.p;
         TRY(launch_measure_rows(ctx, C, comp, tm_on, bg_on, bg_on ? X->mismatches : 0, hist != nullptr, a));
         timer.launch();
     }
     if (structure) {
         ARG_CHECK(((uintptr_t)C->T->bytes.p & 3u) == 0);      // (the kernel reads the candidates as aligned dwords)
-        TRY(launch_measure_structure(ctx, C, (u32)min_loop, hist != nullptr, d_stem.p, d_dimer.p, d_hist.p));
+        TRY(launch_measure_structure(ctx, C, (u32)min_loop, hist != nullptr, d_stem.p, d_dimer.p, d_hist.d.p));
         timer.launch();
     }
     timer.stop();
@@ -536,13 +421,8 @@ extern "C" int catchhip_candidates_measure(catchhip_ctx *ctx, const catchhip_can
         if (tm_on) TRY(measure_fetch(ctx, d_tm, tm_c, n));
         if (bg_on) TRY(measure_fetch(ctx, d_hits, hits, n));
     }
-    if (d_hist.p) HIP_TRY(hipMemcpyAsync(ctx->h_big, d_hist.p, hist_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (d_hist.d.p) TRY(d_hist.read(ctx, MEASURE_SLOT_WORDS, hist));         // (synchronises: the values are there too)
+    else HIP_TRY(hipStreamSynchronize(ctx->stream));
     timer.finish();
-    if (d_hist.p)
-        for (u32 slot = 0; slot < MEASURE_SLOTS; ++slot) {
-            const u64 *w = (const u64 *)ctx->h_big + (size_t)slot * MEASURE_SLOT_WORDS;
-            for (u32 b = 0; b < MEASURE_SLOT_WORDS; ++b) hist[b] += w[b];
-        }
     return 0;
 }

@@ -11,38 +11,30 @@
 // is >= length" is "some window of `length` characters has <= mismatches mismatches": two pointers `length`
 // apart, one pass, the same two characters read for 'A' and for 'T'.  Any character but c is a mismatch ('N' too).
 //
-// polya_flag_kernel: one thread per unique candidate, O(L).  A candidate's characters sit in the targets' byte
-// array at upos[i] and the candidates of a workgroup overlap (stride < length), so the workgroup first copies its
-// rows into LDS -- 16-byte loads from the 16-byte boundary below each row's start, consecutive lanes on
-// consecutive chunks of a row -- and both pointers of the walk read LDS.  The row pitch is an odd number of
-// dwords: the lanes of a wave read the same column of 64 different rows, which an even pitch would put on a
-// few banks.  Rows too long for 64 of them to fit the LDS budget are read from global memory (L is not bounded).
+// polya_flag_kernel: one thread per unique candidate, O(L), both pointers of the walk on the staged row (stage.h).
 #include "internal.h"
 #include "wave.h"
 #include "stage.h"
+#include "rule_host.h"
 
 template <bool STAGE>
 __global__ void __launch_bounds__(256)
-polya_flag_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ upos, u32 n, u32 L, u32 length, u32 k,
-                  u32 min_exact, u32 nchunk, u32 pitch_dw, u32 *__restrict__ flag) {
+polya_flag_kernel(const RowArgs a, u32 length, u32 k, u32 min_exact, u32 *__restrict__ flag) {
     extern __shared__ u32 polya_lds[];
-    const u32 rows = blockDim.x, r = threadIdx.x;
-    const u32 base = blockIdx.x * rows;
-    if (STAGE) stage_rows(bytes, upos, n, L, nchunk, pitch_dw, polya_lds);
-    const u32 i = base + r;
-    if (i >= n) return;
-    const u32 s = upos[i];
-    const u8 *p = STAGE ? (const u8 *)(polya_lds + r * pitch_dw) + (s & 15u) : bytes + s;
+    if (STAGE) stage_rows(a, polya_lds);
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const u8 *p = row_ptr<STAGE>(a, polya_lds, i);
     u32 mm_a = 0, mm_t = 0, run_a = 0, run_t = 0, best_run = 0;
     bool hit = false;
-    for (u32 j = 0; j < L; ++j) {
+    for (u32 j = 0; j < a.L; ++j) {
         const u8 c = p[j];
-        const bool a = c == 'A', t = c == 'T';
-        run_a = a ? run_a + 1 : 0;
-        run_t = t ? run_t + 1 : 0;
+        const bool isa = c == 'A', ist = c == 'T';
+        run_a = isa ? run_a + 1 : 0;
+        run_t = ist ? run_t + 1 : 0;
         best_run = max(best_run, max(run_a, run_t));
-        mm_a += a ? 0u : 1u;
-        mm_t += t ? 0u : 1u;
+        mm_a += isa ? 0u : 1u;
+        mm_t += ist ? 0u : 1u;
         if (j >= length) {
             const u8 o = p[j - length];
             mm_a -= o == 'A' ? 0u : 1u;
@@ -56,36 +48,21 @@ polya_flag_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ upos, u3
 extern "C" int catchhip_candidates_drop_polya(catchhip_ctx *ctx, catchhip_candidates *C, i32 length, i32 mismatches,
                                               i32 min_exact, i64 *nkept) {
     ARG_CHECK(ctx && C && C->ctx == ctx);
-    if (C->filtered) {
-        chip_set_error("candidates_drop_polya: a near-duplicate filter was already applied (the poly(A) filter comes first)");
-        return CATCHHIP_EINVAL;
-    }
+    TRY(rule_refuse_filtered(C, "candidates_drop_polya", "poly(A) filter"));
     if (length < 1 || mismatches < 0 || min_exact < 0) {
         chip_set_error("candidates_drop_polya: length must be >= 1, mismatches and min_exact >= 0 (got %d, %d, %d)",
                        (int)length, (int)mismatches, (int)min_exact);
         return CATCHHIP_EINVAL;
     }
     PoolScope pool_scope(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (nkept) *nkept = C->nuniq;
+    TRY(rule_begin(ctx, C, nkept));
     if (C->nuniq == 0 || length > C->L) return 0;             // a stretch longer than the candidates: nothing to drop
-    const u32 n = (u32)C->nuniq, L = (u32)C->L;
     DevBuf<u32> flag;
-    TRY(flag.alloc((size_t)n + 1));
-    // a row in LDS: from the 16-byte boundary below its start (<= 15 bytes before it) to its end
-    const u32 nchunk = (L + 15u + 15u) / 16u, pitch_dw = 4u * nchunk + 1u;
-    u32 rows = 256;
-    while (rows > 64 && (size_t)rows * pitch_dw * 4 > POLYA_LDS_BUDGET) rows >>= 1;
-    const bool stage = (size_t)rows * pitch_dw * 4 <= POLYA_LDS_BUDGET && ((uintptr_t)C->T->bytes.p & 15u) == 0;
+    TRY(flag.alloc((size_t)C->nuniq + 1));
+    const RowPlan plan = row_plan((u32)C->L, 0, 0, 4, rows_aligned(C));
     PhaseTimer tm(ctx, PHASE_PREFILTER);
-    if (stage)
-        hipLaunchKernelGGL(polya_flag_kernel<true>, dim3((unsigned)div_up((i64)n, rows)), dim3(rows),
-                           (size_t)rows * pitch_dw * 4, ctx->stream, (const u8 *)C->T->bytes.p, (const u32 *)C->upos.p, n,
-                           L, (u32)length, (u32)mismatches, (u32)min_exact, nchunk, pitch_dw, flag.p);
-    else
-        hipLaunchKernelGGL(polya_flag_kernel<false>, dim3((unsigned)div_up((i64)n, 256)), dim3(256), 0, ctx->stream,
-                           (const u8 *)C->T->bytes.p, (const u32 *)C->upos.p, n, L, (u32)length, (u32)mismatches,
-                           (u32)min_exact, nchunk, pitch_dw, flag.p);
+    hipLaunchKernelGGL(plan.stage ? polya_flag_kernel<true> : polya_flag_kernel<false>, row_grid(C, plan), dim3(plan.rows),
+                       plan.lds_bytes, ctx->stream, row_args(C, plan), (u32)length, (u32)mismatches, (u32)min_exact, flag.p);
     HIP_TRY(hipGetLastError());
     tm.launch();
     tm.stop();
@@ -95,20 +72,22 @@ extern "C" int catchhip_candidates_drop_polya(catchhip_ctx *ctx, catchhip_candid
 }
 
 // ---- composition rules (not in the reference; catch_amd/filter/composition_filter.py defines them) -------------------
-// composition_flag_kernel: one thread per unique candidate, one pass over its L bytes, the rows staged as above.
+// composition_flag_kernel: one thread per unique candidate, one pass over its L bytes, the rows staged (stage.h).
 //   GC and the homopolymer run are counters in registers.
-//   Low complexity (DUST = true): the window's 64 triplet counters c_t are indexed by data, so they live in LDS, one
-//   byte each (a window of <= 256 bytes holds <= 254 triplets).  Layout, behind the staged rows: dword g * rows + r
-//   holds the counters of codes 4g .. 4g + 3 of thread r -- a lane's pitch is ONE dword and a code group's pitch is
-//   `rows` dwords (a multiple of 32), so whatever codes the lanes of a wave touch, lane l is on bank l mod 32: the 32
-//   lanes that a byte access serves per cycle never share a bank.  A thread touches its own counters only (no barrier).
-//   The window moves one byte per step: the triplet that leaves (c_t--, S -= c_t), then the one that enters
-//   (S += c_t, c_t++); a second pointer We - 2 bytes behind the first rebuilds the leaving triplet's code.
-//   DUST = false allocates no counters and does no triplet work.
+//   Low complexity (DUST = true): the window's 64 triplet counters in LDS behind the staged rows (stage.h has their
+//   layout, TRIPLET_COUNTER_BYTES per thread).  The window moves one byte per step: the triplet that leaves
+//   (c_t--, S -= c_t), then the one that enters (S += c_t, c_t++); a second pointer We - 2 bytes behind the first
+//   rebuilds the leaving triplet's code.  Every whole window is asked 10 S > x10 (T - 1).  DUST = false allocates no
+//   counters and does no triplet work.
+//   The per-byte step is written out here and again in measure_rows_kernel (measure.hip), which ends it differently:
+//   as steppers shared by the two (state in a struct, the step a member) both kernels compiled to the same
+//   instructions in another order and ran 0.8 % and 2 % slower, so each keeps its own text.  A
+//   change to the step is made in both; tests/test_quality_measure.py compares the two kernels.
+//   The arguments come one by one, the thresholds between the row arguments, and RowArgs is made inside: with the
+//   struct as the argument the thresholds' scalar load sank below the walk, the loop then waited for all four of its
+//   LDS reads at once, and the GC-only instances ran 0.6 % slower.
 // The per-rule totals (with multiplicity) are summed over the wave, then one atomic per wave and non-zero counter --
-// into one of COMP_SLOTS copies of the four totals, a 128-byte line each, which the host adds up: with one copy, the
-// 140,000 waves of 8.9 M candidates queued on a single line and the atomics took longer than the walk.
-#define COMP_COUNTER_BYTES 64u
+// into one of COMP_SLOTS copies of the four totals, a 128-byte line each (stage.h: the totals).
 #define COMP_SLOTS 64u
 #define COMP_SLOT_WORDS 16u
 
@@ -120,14 +99,14 @@ composition_flag_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ up
     extern __shared__ u32 comp_lds[];
     const u32 rows = blockDim.x, r = threadIdx.x;
     const u32 i = blockIdx.x * rows + r;
-    if (STAGE) stage_rows(bytes, upos, n, L, nchunk, pitch_dw, comp_lds);
+    const RowArgs a = {bytes, upos, mult, n, L, nchunk, pitch_dw, cnt_off_dw};
+    if (STAGE) stage_rows(a, comp_lds);
     u32 fail = 0, m = 0;
     if (i < n) {                                              // (no early return: the wave sums below need every lane)
-        const u32 s = upos[i];
-        const u8 *p = STAGE ? (const u8 *)(comp_lds + r * pitch_dw) + (s & 15u) : bytes + s;
+        const u8 *p = row_ptr<STAGE>(a, comp_lds, i);
         u8 *cnt = (u8 *)(comp_lds + cnt_off_dw + r);          // counter of code t: cnt[(t >> 2) * 4 * rows + (t & 3)]
         if (DUST)
-            for (u32 g = 0; g < COMP_COUNTER_BYTES / 4u; ++g) comp_lds[cnt_off_dw + g * rows + r] = 0;
+            for (u32 g = 0; g < TRIPLET_COUNTER_BYTES / 4u; ++g) comp_lds[cnt_off_dw + g * rows + r] = 0;
         u32 gc = 0, run = 0, best_run = 0, prev = 0;
         u32 h = 0, v = 0, ho = 0, vo = 0, S = 0, T = 0;       // head and tail triplet (code, which of its bytes are bases)
         bool low = false;
@@ -167,49 +146,22 @@ composition_flag_kernel(const u8 *__restrict__ bytes, const u32 *__restrict__ up
         flag[i] = fail ? 0u : 1u;
         m = mult[i];
     }
-    u64 t_gc = (fail & 1u) ? m : 0u, t_run = (fail & 2u) ? m : 0u, t_low = (fail & 4u) ? m : 0u, t_any = fail ? m : 0u;
-    wave_sum_n(t_gc, t_run, t_low, t_any);
-    if ((r & 63u) == 0) {
-        unsigned long long *t = (unsigned long long *)totals + (blockIdx.x & (COMP_SLOTS - 1u)) * COMP_SLOT_WORDS;
-        if (t_gc) atomicAdd(t + 0, (unsigned long long)t_gc);
-        if (t_run) atomicAdd(t + 1, (unsigned long long)t_run);
-        if (t_low) atomicAdd(t + 2, (unsigned long long)t_low);
-        if (t_any) atomicAdd(t + 3, (unsigned long long)t_any);
-    }
+    const u64 t_gc = (fail & 1u) ? m : 0u, t_run = (fail & 2u) ? m : 0u, t_low = (fail & 4u) ? m : 0u, t_any = fail ? m : 0u;
+    totals_add_per_wave(totals_slot(totals, COMP_SLOTS, COMP_SLOT_WORDS), t_gc, t_run, t_low, t_any);
 }
 
-template <bool DUST>
-static int launch_composition(catchhip_ctx *ctx, const catchhip_candidates *C, u32 gc_lo, u32 gc_hi, u32 max_run, u32 x10,
-                              u32 We, u32 *flag, u64 *totals) {
-    const u32 n = (u32)C->nuniq, L = (u32)C->L;
-    // the rows as the poly(A) kernel stages them, and behind them COMP_COUNTER_BYTES per row when the counters are there
-    const u32 nchunk = (L + 15u + 15u) / 16u, pitch_dw = 4u * nchunk + 1u;
-    const size_t row_bytes = (size_t)pitch_dw * 4, cnt_bytes = DUST ? COMP_COUNTER_BYTES : 0u;
-    u32 rows = 256;
-    while (rows > 64 && rows * (row_bytes + cnt_bytes) > POLYA_LDS_BUDGET) rows >>= 1;
-    const bool stage = rows * (row_bytes + cnt_bytes) <= POLYA_LDS_BUDGET && ((uintptr_t)C->T->bytes.p & 15u) == 0;
-    if (stage)
-        hipLaunchKernelGGL((composition_flag_kernel<true, DUST>), dim3((unsigned)div_up((i64)n, rows)), dim3(rows),
-                           rows * (row_bytes + cnt_bytes), ctx->stream, (const u8 *)C->T->bytes.p, (const u32 *)C->upos.p,
-                           (const u32 *)C->mult.p, n, L, gc_lo, gc_hi, max_run, x10, We, nchunk, pitch_dw, rows * pitch_dw,
-                           flag, totals);
-    else
-        hipLaunchKernelGGL((composition_flag_kernel<false, DUST>), dim3((unsigned)div_up((i64)n, 256)), dim3(256),
-                           256 * cnt_bytes, ctx->stream, (const u8 *)C->T->bytes.p, (const u32 *)C->upos.p,
-                           (const u32 *)C->mult.p, n, L, gc_lo, gc_hi, max_run, x10, We, nchunk, pitch_dw, 0u, flag,
-                           totals);
-    HIP_TRY(hipGetLastError());
-    return 0;
+typedef decltype(&composition_flag_kernel<false, false>) composition_fn;
+static composition_fn composition_instance(bool stage, bool dust) {
+    static const composition_fn table[4] = {composition_flag_kernel<false, false>, composition_flag_kernel<true, false>,
+                                            composition_flag_kernel<false, true>, composition_flag_kernel<true, true>};
+    return table[(stage ? 1 : 0) | (dust ? 2 : 0)];
 }
 
 extern "C" int catchhip_candidates_drop_composition(catchhip_ctx *ctx, catchhip_candidates *C, i32 gc_lo, i32 gc_hi,
                                                     i32 max_run, i32 dust_x10, i32 dust_window, i64 dropped[4],
                                                     i64 *nkept) {
     ARG_CHECK(ctx && C && C->ctx == ctx);
-    if (C->filtered) {
-        chip_set_error("candidates_drop_composition: a near-duplicate filter was already applied (the composition filter comes first)");
-        return CATCHHIP_EINVAL;
-    }
+    TRY(rule_refuse_filtered(C, "candidates_drop_composition", "composition filter"));
     if (gc_lo < -1 || gc_hi < -1 || max_run < -1 || max_run == 0 || dust_x10 < -1 ||
         (dust_x10 >= 0 && (dust_window < 3 || dust_window > 256))) {
         chip_set_error("candidates_drop_composition: gc_lo, gc_hi >= 0, max_run >= 1, dust_x10 >= 0 (or -1: off) and "
@@ -218,42 +170,50 @@ extern "C" int catchhip_candidates_drop_composition(catchhip_ctx *ctx, catchhip_
         return CATCHHIP_EINVAL;
     }
     PoolScope pool_scope(ctx);
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (nkept) *nkept = C->nuniq;
+    TRY(rule_begin(ctx, C, nkept));
     if (dropped) dropped[0] = dropped[1] = dropped[2] = dropped[3] = 0;
     const bool gc_on = gc_lo > 0 || (gc_hi >= 0 && gc_hi < C->L);
     const bool dust_on = dust_x10 >= 0 && C->L >= 4;          // (a window of < 4 bytes holds < 2 triplets)
     if (C->nuniq == 0 || !(gc_on || max_run > 0 || dust_on)) return 0;
-    const u32 n = (u32)C->nuniq;
     DevBuf<u32> flag;
-    DevBuf<u64> totals;
-    TRY(flag.alloc((size_t)n + 1));
-    const size_t totals_bytes = sizeof(u64) * COMP_SLOTS * COMP_SLOT_WORDS;
-    TRY(totals.alloc(COMP_SLOTS * COMP_SLOT_WORDS));
-    TRY(chip_pinned_reserve(ctx, totals_bytes));
-    HIP_TRY(hipMemsetAsync(totals.p, 0, totals_bytes, ctx->stream));
+    SlotTotals totals;
+    TRY(flag.alloc((size_t)C->nuniq + 1));
+    TRY(totals.init(ctx, COMP_SLOTS, COMP_SLOT_WORDS));
     PhaseTimer tm(ctx, PHASE_PREFILTER);
     const u32 lo = gc_lo < 0 ? 0u : (u32)gc_lo, hi = gc_hi < 0 ? 0xffffffffu : (u32)gc_hi;
     const u32 run = max_run < 0 ? 0xffffffffu : (u32)max_run;
-    if (dust_on) {
-        // 10 S <= 10 * 254 * 253 / 2 = 321,310: any larger threshold drops nothing, and x10 * (T - 1) stays in 32 bits
-        const u32 x10 = (u32)(dust_x10 < 400000 ? dust_x10 : 400000);
-        const u32 We = (u32)(dust_window < C->L ? dust_window : C->L);
-        TRY(launch_composition<true>(ctx, C, lo, hi, run, x10, We, flag.p, totals.p));
-    } else {
-        TRY(launch_composition<false>(ctx, C, lo, hi, run, 0u, 0u, flag.p, totals.p));
-    }
+    // 10 S <= 10 * 254 * 253 / 2 = 321,310: any larger threshold drops nothing, and x10 * (T - 1) stays in 32 bits
+    const u32 x10 = dust_on ? (u32)(dust_x10 < 400000 ? dust_x10 : 400000) : 0u;
+    const u32 We = dust_on ? (u32)(dust_window < C->L ? dust_window : C->L) : 0u;
+    const RowPlan plan = row_plan((u32)C->L, dust_on ? TRIPLET_COUNTER_BYTES : 0u, 0, 4, rows_aligned(C));
+    // (the order is the kernel's: n, L, then gc_lo, gc_hi, max_run, x10, We, then nchunk, pitch_dw, the counters' offset --
+    // thirteen u32 in a row, which the compiler cannot tell apart)
+    const RowArgs a = row_args(C, plan);
+    hipLaunchKernelGGL(composition_instance(plan.stage, dust_on), row_grid(C, plan), dim3(plan.rows), plan.lds_bytes,
+                       ctx->stream, a.bytes, a.upos, a.mult, a.n, a.L, lo, hi, run, x10, We, a.nchunk, a.pitch_dw,
+                       a.extra_off_dw, flag.p, totals.d.p);
+    HIP_TRY(hipGetLastError());
     tm.launch();
     tm.stop();
-    HIP_TRY(hipMemcpyAsync(ctx->h_big, totals.p, totals_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    u64 h[4];
+    TRY(totals.read(ctx, 4, h));
     tm.finish();
-    u64 h[4] = {0, 0, 0, 0};
-    for (u32 slot = 0; slot < COMP_SLOTS; ++slot)
-        for (int k = 0; k < 4; ++k) h[k] += ((const u64 *)ctx->h_big)[slot * COMP_SLOT_WORDS + k];
     if (dropped) for (int k = 0; k < 4; ++k) dropped[k] = (i64)h[k];
-    if (h[3] == 0) return 0;                                  // nothing dropped: the list stands
-    return chip_candidates_keep_flagged(ctx, C, flag, nkept);
+    return rule_keep(ctx, C, h[3] != 0, flag, nkept);
+}
+
+// the launch plans of rule_host.h as the entry points of the five files get them (tests/test_candidate_launch_plan.py)
+extern "C" int catchhip_selftest_candidate_plan(i32 L, i64 row_extra, i64 wg_extra, i32 tail_align, i32 aligned16,
+                                                i64 plane_tail, i32 plane_align, u32 *row_out, u32 *plane_out) {
+    ARG_CHECK(L >= 1 && row_extra >= 0 && row_extra % 4 == 0 && wg_extra >= 0 && plane_tail >= 0 && row_out && plane_out);
+    ARG_CHECK((tail_align == 4 || tail_align == 8) && (plane_align == 4 || plane_align == 8));
+    const RowPlan r = row_plan((u32)L, (size_t)row_extra, (size_t)wg_extra, (u32)tail_align, aligned16 != 0);
+    const u32 rows[7] = {r.rows, r.stage ? 1u : 0u, r.nchunk, r.pitch_dw, r.extra_off_dw, r.tail_off_dw, (u32)r.lds_bytes};
+    memcpy(row_out, rows, sizeof(rows));
+    const PlanePlan p = plane_plan((u32)L, (size_t)plane_tail, (u32)plane_align);
+    const u32 planes[5] = {p.W, p.rows, p.lds_planes ? 1u : 0u, p.tail_off_dw, (u32)p.lds_bytes};
+    memcpy(plane_out, planes, sizeof(planes));
+    return 0;
 }
 
 // the multiplicities the filter must carry along (tests compare them; the near-duplicate filters read them on the device)

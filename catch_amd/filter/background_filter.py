@@ -77,7 +77,7 @@ import threading
 
 import numpy as np
 
-from catch_amd.filter.base_filter import BaseFilter
+from catch_amd.filter.candidate_rule import CandidateRuleFilter, _value_error
 
 logger = logging.getLogger(__name__)
 
@@ -143,7 +143,7 @@ def _distance(x, c):
     return (d * np.uint64(0x0101010101010101)) >> np.uint64(56)
 
 
-class BackgroundFilter(BaseFilter):
+class BackgroundFilter(CandidateRuleFilter):
     def __init__(self, background_seqs, kmer=KMER_DEFAULT, max_hits=None, mismatches=0):
         if isinstance(kmer, bool) or not isinstance(kmer, int) or not KMER_MIN <= kmer <= KMER_MAX:
             raise ValueError("the k-mer length must be an integer in %d .. %d, not %r" % (KMER_MIN, KMER_MAX, kmer))
@@ -306,25 +306,6 @@ class BackgroundFilter(BaseFilter):
                     keep[i] = k
         return keep
 
-    def _filter_strs(self, strs):
-        strs = list(strs)
-        if not strs:
-            return strs
-        L = len(strs[0])
-        if L == 0 or any(len(s) != L for s in strs):
-            return [s for s, k in zip(strs, self._keep_list(strs)) if k]
-        out = []
-        for a in range(0, len(strs), 1 << 14):        # (bounded temporaries)
-            part = strs[a:a + (1 << 14)]
-            keep = self._keep_mask_equal_length(part, L)
-            out += [s for s, k in zip(part, keep.tolist()) if k]
-        return out
-
-    def _filter(self, input):
-        if len(input) == 0:
-            return input
-        return [p for p, k in zip(input, self._keep_list([p.seq_str for p in input])) if k]
-
     # ------------------------------------------------------------ the device front end
     def _device_index(self, ctx):
         """The engine.KmerIndex of ctx's device: built on first use, on ctx, and
@@ -421,10 +402,6 @@ def add_arguments(p):
                         "drops any and over all datasets; without "
                         "--background-max-hits it only measures and the "
                         "design is unchanged")
-
-
-def _value_error(message):
-    raise ValueError(message)
 
 
 def from_args(args, error=_value_error, load=True):

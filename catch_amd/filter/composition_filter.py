@@ -35,22 +35,16 @@ _apply_to_candidates (catchhip_candidates_drop_composition, one kernel over the
 unique candidates of the device front end).
 """
 import threading
-from fractions import Fraction
 
 import numpy as np
 
-from catch_amd.filter.base_filter import BaseFilter
+from catch_amd.filter.candidate_rule import CandidateRuleFilter, _fraction, _value_error
 
 BASES = "ACGT"
 
 
-def _fraction(x, what):
-    if isinstance(x, float):
-        raise ValueError("%s must be given as a string or a Fraction, not a float (%r)" % (what, x))
-    try:
-        f = Fraction(x)
-    except (ValueError, TypeError, ZeroDivisionError):
-        raise ValueError("%s is not a number: %r" % (what, x))
+def _unit_fraction(x, what):
+    f = _fraction(x, what)
     if not 0 <= f <= 1:
         raise ValueError("%s must lie in [0, 1], not %s" % (what, x))
     return f
@@ -62,7 +56,7 @@ def _int(x, what):
     return int(x)
 
 
-class CompositionFilter(BaseFilter):
+class CompositionFilter(CandidateRuleFilter):
     def __init__(self, gc_range=None, max_homopolymer=None, max_dust=None, dust_window=64):
         self.gc_min = self.gc_max = None
         if gc_range is not None:
@@ -70,7 +64,7 @@ class CompositionFilter(BaseFilter):
                 lo, hi = gc_range
             except (TypeError, ValueError):
                 raise ValueError("gc_range must be a pair (MIN, MAX), not %r" % (gc_range,))
-            self.gc_min, self.gc_max = _fraction(lo, "the GC minimum"), _fraction(hi, "the GC maximum")
+            self.gc_min, self.gc_max = _unit_fraction(lo, "the GC minimum"), _unit_fraction(hi, "the GC maximum")
             if self.gc_min > self.gc_max:
                 raise ValueError("the GC minimum (%s) exceeds the maximum (%s)" % (lo, hi))
         self.max_homopolymer = None
@@ -187,25 +181,6 @@ class CompositionFilter(BaseFilter):
         self._count([sum(f[k] for f in fails) for k in range(3)] + [sum(any(f) for f in fails)])
         return [not any(f) for f in fails]
 
-    def _filter_strs(self, strs):
-        strs = list(strs)
-        if not strs:
-            return strs
-        L = len(strs[0])
-        if L == 0 or any(len(s) != L for s in strs):
-            return [s for s, k in zip(strs, self._keep_list(strs)) if k]
-        out = []
-        for a in range(0, len(strs), 1 << 14):        # (bounded temporaries)
-            part = strs[a:a + (1 << 14)]
-            keep = self._keep_mask_equal_length(part, L)
-            out += [s for s, k in zip(part, keep.tolist()) if k]
-        return out
-
-    def _filter(self, input):
-        if len(input) == 0:
-            return input
-        return [p for p, k in zip(input, self._keep_list([p.seq_str for p in input])) if k]
-
     # ------------------------------------------------------------ the device front end
     def _apply_to_candidates(self, cands):
         """The filter on an engine.Candidates object (grouped or not), before
@@ -248,17 +223,13 @@ def add_arguments(p):
                         "(a shorter probe is one window)")
 
 
-def _value_error(message):
-    raise ValueError(message)
-
-
 def from_args(args, error=_value_error):
     """A new CompositionFilter as the options of add_arguments ask for, or
     None without them; bad values go to error (ArgumentParser.error in the
     parsers, so that they are argparse errors)."""
     if args.filter_gc is not None:
         try:
-            lo, hi = (_fraction(x, "--filter-gc: a bound") for x in args.filter_gc)
+            lo, hi = (_unit_fraction(x, "--filter-gc: a bound") for x in args.filter_gc)
         except ValueError as exc:
             error(str(exc))
         if lo > hi:

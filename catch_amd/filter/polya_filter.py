@@ -17,10 +17,12 @@ string paths use the same rule here.
 """
 import numpy as np
 
-from catch_amd.filter.base_filter import BaseFilter
+from catch_amd.filter.candidate_rule import CandidateRuleFilter
 
 
-class PolyAFilter(BaseFilter):
+class PolyAFilter(CandidateRuleFilter):
+    CHUNK = 1 << 16
+
     def __init__(self, length, mismatches, min_exact_length_to_consider=6):
         self.length = length
         self.mismatches = mismatches
@@ -64,25 +66,6 @@ class PolyAFilter(BaseFilter):
             return hit
         drop = window(self.min_exact_length_to_consider, 0) & window(self.length, self.mismatches)
         return ~drop
-
-    def _filter_strs(self, strs):
-        strs = list(strs)
-        if not strs:
-            return strs
-        L = len(strs[0])
-        if L == 0 or any(len(s) != L for s in strs):
-            return [s for s in strs if self._keeps(s)]
-        out = []
-        for a in range(0, len(strs), 1 << 16):        # (bounded temporaries)
-            part = strs[a:a + (1 << 16)]
-            keep = self._keep_mask_equal_length(part, L)
-            out += [s for s, k in zip(part, keep.tolist()) if k]
-        return out
-
-    def _filter(self, input):
-        if len(input) == 0:
-            return input
-        return [p for p in input if self._keeps(p.seq_str)]
 
     def _apply_to_candidates(self, cands):
         """The filter on an engine.Candidates object (grouped or not), before

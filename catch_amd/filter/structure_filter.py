@@ -42,13 +42,15 @@ import threading
 
 import numpy as np
 
-from catch_amd.filter.base_filter import BaseFilter
-from catch_amd.filter.composition_filter import BASES, _int, _value_error
+from catch_amd.filter.candidate_rule import CandidateRuleFilter, _value_error
+from catch_amd.filter.composition_filter import BASES, _int
 
 _COMPLEMENT = str.maketrans("ACGT", "TGCA")
 
 
-class StructureFilter(BaseFilter):
+class StructureFilter(CandidateRuleFilter):
+    CHUNK = 1 << 12               # (a chunk's L x L table is walked a diagonal at a time)
+
     def __init__(self, max_hairpin_stem=None, hairpin_min_loop=3, max_self_dimer=None):
         self.max_hairpin_stem = None
         if max_hairpin_stem is not None:
@@ -154,25 +156,6 @@ class StructureFilter(BaseFilter):
         fails = [self._fails(s) for s in strs]
         self._count([sum(f[k] for f in fails) for k in range(2)] + [sum(any(f) for f in fails)])
         return [not any(f) for f in fails]
-
-    def _filter_strs(self, strs):
-        strs = list(strs)
-        if not strs:
-            return strs
-        L = len(strs[0])
-        if L == 0 or any(len(s) != L for s in strs):
-            return [s for s, k in zip(strs, self._keep_list(strs)) if k]
-        out = []
-        for a in range(0, len(strs), 1 << 12):        # (bounded temporaries: a chunk's L x L table is walked a diagonal at a time)
-            part = strs[a:a + (1 << 12)]
-            keep = self._keep_mask_equal_length(part, L)
-            out += [s for s, k in zip(part, keep.tolist()) if k]
-        return out
-
-    def _filter(self, input):
-        if len(input) == 0:
-            return input
-        return [p for p, k in zip(input, self._keep_list([p.seq_str for p in input])) if k]
 
     # ------------------------------------------------------------ the device front end
     def _apply_to_candidates(self, cands):

@@ -63,7 +63,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from catch_amd.filter.base_filter import BaseFilter
+from catch_amd.filter.candidate_rule import CandidateRuleFilter, _fraction, _value_error
 
 BASES = "ACGT"
 NBINS = 128
@@ -86,15 +86,6 @@ _E25 = np.zeros(25, dtype=np.int64)
 for _d, (_h, _e) in NN.items():
     _H25[5 * BASES.index(_d[0]) + BASES.index(_d[1])] = _h
     _E25[5 * BASES.index(_d[0]) + BASES.index(_d[1])] = _e
-
-
-def _fraction(x, what):
-    if isinstance(x, float):
-        raise ValueError("%s must be given as a string or a Fraction, not a float (%r)" % (what, x))
-    try:
-        return Fraction(x)
-    except (ValueError, TypeError, ZeroDivisionError):
-        raise ValueError("%s is not a number: %r" % (what, x))
 
 
 def _conditions(sodium_mm, oligo_nm, formamide_pct):
@@ -123,7 +114,7 @@ def _range(tm_range):
     return lo_f, hi_f
 
 
-class TmFilter(BaseFilter):
+class TmFilter(CandidateRuleFilter):
     def __init__(self, tm_range=None, sodium_mm="50", oligo_nm="50", formamide_pct="0"):
         self.sodium_mm, self.oligo_nm, self.formamide_pct = _conditions(sodium_mm, oligo_nm, formamide_pct)
         self.tm_min = self.tm_max = self.lo_c = self.hi_c = None
@@ -233,25 +224,6 @@ class TmFilter(BaseFilter):
         self._count([nb, na, nb + na], hist)
         return [x == 0 for x in side]
 
-    def _filter_strs(self, strs):
-        strs = list(strs)
-        if not strs:
-            return strs
-        L = len(strs[0])
-        if L == 0 or any(len(s) != L for s in strs):
-            return [s for s, k in zip(strs, self._keep_list(strs)) if k]
-        out = []
-        for a in range(0, len(strs), 1 << 14):        # (bounded temporaries)
-            part = strs[a:a + (1 << 14)]
-            keep = self._keep_mask_equal_length(part, L)
-            out += [s for s, k in zip(part, keep.tolist()) if k]
-        return out
-
-    def _filter(self, input):
-        if len(input) == 0:
-            return input
-        return [p for p, k in zip(input, self._keep_list([p.seq_str for p in input])) if k]
-
     # ------------------------------------------------------------ the device front end
     def _apply_to_candidates(self, cands):
         """The filter on an engine.Candidates object (grouped or not), before
@@ -311,10 +283,6 @@ def add_arguments(p):
                         "filters), duplicates counted, before --filter-tm "
                         "drops any and over all datasets; without --filter-tm "
                         "it only measures and the design is unchanged")
-
-
-def _value_error(message):
-    raise ValueError(message)
 
 
 def from_args(args, error=_value_error):

@@ -596,6 +596,21 @@ int catchhip_selftest_row_build(catchhip_ctx *ctx, const uint32_t *rec, const ui
                                 uint32_t *o_end, uint32_t *o_mcnt, uint32_t *o_blmax,
                                 uint64_t *o_bsum, uint32_t *o_S, uint32_t *o_bstart,
                                 int64_t *scalars);
+/* Test entry point of the launch plans of the candidate rules (csrc/rule_host.h);
+ * tests/test_candidate_launch_plan.py compares them with the tests' own arithmetic.
+ * Host arithmetic only: no context, no device.  No reference counterpart.
+ * Rows of L characters with row_extra bytes per row and wg_extra bytes per workgroup
+ * behind them, the latter aligned to tail_align (4 or 8) bytes, aligned16 != 0: the
+ * byte array is 16-byte aligned.  row_out[7] = rows per workgroup, staged (0 / 1),
+ * 16-byte chunks per row, row pitch in dwords, dword offset of the per-row extras, of
+ * the per-workgroup extras, bytes of dynamic LDS.
+ * Planes of L characters with plane_tail bytes per workgroup behind them, aligned to
+ * plane_align.  plane_out[5] = words per plane, candidates per workgroup, planes in
+ * LDS (0 / 1), dword offset of the tail, bytes of dynamic LDS. */
+int catchhip_selftest_candidate_plan(int32_t L, int64_t row_extra, int64_t wg_extra,
+                                     int32_t tail_align, int32_t aligned16,
+                                     int64_t plane_tail, int32_t plane_align,
+                                     uint32_t *row_out, uint32_t *plane_out);
 /* Which RCCL the communicators of this library go through: "RCCL version code V
  * from <file> (<how it was chosen>)".  The library opens ONE copy by path
  * (CATCHHIP_RCCL_PATH, else /opt/rocm/lib/librccl.so) instead of whatever file of
