@@ -145,6 +145,9 @@ PROTOTYPES = {
         c_vp, c_u32p, c_u32p, c_u32p, ctypes.c_int64, c_u32p, c_u32p, ctypes.c_int64, c_i32p, c_u32p, ctypes.c_int32,
         ctypes.c_int32, c_u32p, ctypes.c_int64, c_i32p, c_i32p, c_i32p, c_u32p, c_u32p, c_u32p, c_u32p, c_u64p,
         c_u32p, c_u32p, c_i64p]),
+    "catchhip_selftest_seed_table": (ctypes.c_int, [
+        c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_u32p, c_u32p, c_u32p, c_u32p,
+        c_i64p]),
     "catchhip_comm_info": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int64]),
     "catchhip_shard_create": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_i64p, c_vpp]),
     "catchhip_shard_destroy": (ctypes.c_int, [c_vp]),

@@ -109,6 +109,7 @@ struct SeedTable {
     // memory-side cache.
     u32 *present;
     u32 pmask;                  // presence bits - 1
+    u32 pkey;                   // bits a key sets in its presence word (1 .. 3; see seed_presence)
     __device__ __forceinline__ unsigned long long *key_at(u32 s) const { return (unsigned long long *)(slot + s); }
 };
 #define SEED_EMPTY 0xffffffffffffffffull
@@ -125,9 +126,24 @@ __device__ __forceinline__ u32 seed_hash(unsigned long long k) {
     k ^= k >> 29; k *= 0xbf58476d1ce4e5b9ull; k ^= k >> 32;
     return (u32)k;
 }
-__device__ __forceinline__ u32 seed_hash2(unsigned long long k) {
+__device__ __forceinline__ unsigned long long seed_mix2(unsigned long long k) {
     k ^= k >> 31; k *= 0x94d049bb133111ebull; k ^= k >> 29;
-    return (u32)k;
+    return k;
+}
+__device__ __forceinline__ u32 seed_hash2(unsigned long long k) { return (u32)seed_mix2(k); }
+
+// Presence filter: the word a key belongs to and the bits it sets / tests there.  The word and the first bit come
+// from the low half of the second hash, as ever; with t.pkey > 1 one or two further bits of the SAME word from its
+// upper half, which "& pmask" never uses (a blocked Bloom filter of one 32-bit word: still one gather per
+// position).  Two of a key's bits may coincide.  Builder and look-ups all come through here.
+__device__ __forceinline__ u32 seed_presence(const SeedTable &t, unsigned long long key, u32 *word) {
+    const unsigned long long h = seed_mix2(key);
+    const u32 b = (u32)h & t.pmask;
+    *word = b >> 5;
+    u32 m = 1u << (b & 31u);
+    if (t.pkey > 1) m |= 1u << ((u32)(h >> 32) & 31u);
+    if (t.pkey > 2) m |= 1u << ((u32)(h >> 37) & 31u);
+    return m;
 }
 
 // 2-plane key of kb bases starting at base offset `o` of a plane pair
@@ -185,9 +201,10 @@ seed_count_kernel(const uint4 *__restrict__ pplanes, const u32 *__restrict__ ent
         if (fresh || prev == key) break;
         s = (s + 1) & t.mask;
     }
-    if (t.present && fresh) {                        // (whoever creates the key's slot sets its presence bit)
-        const u32 b = seed_hash2(key) & t.pmask;
-        atomicOr(&t.present[b >> 5], 1u << (b & 31u));
+    if (t.present && fresh) {                        // (whoever creates the key's slot sets its presence bits)
+        u32 pw;
+        const u32 pm = seed_presence(t, key, &pw);
+        atomicOr(&t.present[pw], pm);
     }
     // (the anchor-pair filter wants the slot of EVERY anchor's k-mer, also of those that stay out of the table
     // -- a key without entries; bit 31: the anchor holds an N -- it then equals no target k-mer exactly)
@@ -214,15 +231,24 @@ seed_init_kernel(uint4 *__restrict__ slot, u32 *__restrict__ cnt, u32 capacity, 
 // 16-wave workgroup waits for a whole CU's worth of free wave slots, and this
 // kernel then took milliseconds (S4, four groups in flight: 3.5 ms on average,
 // 33 ms at worst, 16 % of all kernel time).
-#define SA_SLOTS 1024
+// Round 14: SA_PER slots per thread (in runs of four, 1,024 slots apart), 4,096 per workgroup.  The launch was
+// bound by its cursor, not by its bytes: one atomic per 1,024 slots was 82 k atomics on one address per S4 step,
+// ~11 ns each, 0.9 of the launch's 1.06 ms.
+#define SA_PER 16
+#define SA_SLOTS (256 * SA_PER)
 __global__ void __launch_bounds__(256)
 seed_alloc_kernel(SeedTable t, u32 *__restrict__ cursor) {
     __shared__ u32 s_part[4], s_base;
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u32 s0 = blockIdx.x * SA_SLOTS + threadIdx.x * 4;
-    uint4 n = make_uint4(0, 0, 0, 0);
-    if (s0 + 3 <= t.mask) n = *(const uint4 *)(t.cnt + s0);   // the table size is a multiple of 1024
-    const u32 mine = n.x + n.y + n.z + n.w;
+    const u32 s0 = blockIdx.x * SA_SLOTS + threadIdx.x * 4;   // its runs: slots s0 + 1024 q .. + 3
+    uint4 n[SA_PER / 4];
+    u32 mine = 0;
+#pragma unroll
+    for (int q = 0; q < SA_PER / 4; ++q) {
+        // (the table size is a multiple of 1024: a run is inside it or outside)
+        n[q] = s0 + 1024 * q + 3 <= t.mask ? *(const uint4 *)(t.cnt + s0 + 1024 * q) : make_uint4(0, 0, 0, 0);
+        mine += n[q].x + n[q].y + n[q].z + n[q].w;
+    }
     u32 total;
     const u32 ex = wave_excl_scan(mine, &total);
     if (lane == 0) s_part[wave] = total;
@@ -231,13 +257,41 @@ seed_alloc_kernel(SeedTable t, u32 *__restrict__ cursor) {
     for (int w = 0; w < 4; ++w) { if (w < (int)wave) woff += s_part[w]; tot += s_part[w]; }
     if (threadIdx.x == 0) s_base = tot ? atomicAdd(cursor, tot) : 0u;
     __syncthreads();
-    if (s0 + 3 <= t.mask) {
-        const u32 b = s_base + woff + ex;
-        uint2 *r = (uint2 *)(t.slot + s0);       // the (first, count) half of slots s0 .. s0 + 3
-        r[1] = make_uint2(b, n.x);
-        r[3] = make_uint2(b + n.x, n.y);
-        r[5] = make_uint2(b + n.x + n.y, n.z);
-        r[7] = make_uint2(b + n.x + n.y + n.z, n.w);
+    u32 b = s_base + woff + ex;
+#pragma unroll
+    for (int q = 0; q < SA_PER / 4; ++q) {
+        if (s0 + 1024 * q + 3 > t.mask) break;
+        uint2 *r = (uint2 *)(t.slot + s0 + 1024 * q);   // the (first, count) half of the run's four slots
+        // (only a slot WITH entries is written: nine in ten are empty and keep the (0, 0) of the init launch)
+        if (n[q].x) r[1] = make_uint2(b, n[q].x);
+        b += n[q].x;
+        if (n[q].y) r[3] = make_uint2(b, n[q].y);
+        b += n[q].y;
+        if (n[q].z) r[5] = make_uint2(b, n[q].z);
+        b += n[q].z;
+        if (n[q].w) r[7] = make_uint2(b, n[q].w);
+        b += n[q].w;
+    }
+}
+
+// What nobody had measured (round 14): the slots with entries and the set presence bits of a finished table, for the
+// CATCHHIP_TIMING line of the join and the table dump of the tests.  A launch of its own, only when somebody asks:
+// counted inside seed_alloc, two more atomics per workgroup on the cursor's cache line cost 1.7 ms per S4 step.
+__global__ void __launch_bounds__(256)
+seed_stats_kernel(SeedTable t, u32 *__restrict__ out) {
+    __shared__ u32 s_keys[4], s_bits[4];
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 i0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    u32 keys = 0, bits = 0;
+    for (u32 s = i0; s <= t.mask; s += stride) keys += t.slot[s].w ? 1u : 0u;
+    if (t.present)
+        for (u32 w = i0; w <= (t.pmask >> 5); w += stride) bits += __popc(t.present[w]);
+    wave_sum_n(keys, bits);
+    if (lane == 0) { s_keys[wave] = keys; s_bits[wave] = bits; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(out, s_keys[0] + s_keys[1] + s_keys[2] + s_keys[3]);
+        atomicAdd(out + 1, s_bits[0] + s_bits[1] + s_bits[2] + s_bits[3]);
     }
 }
 
@@ -316,8 +370,9 @@ seed_lookup_kernel(const u32 *__restrict__ tplanes, i64 nwords, u32 total, const
     };
     auto find_slot = [&](unsigned long long key, uint2 *range) {
         if (t.present) {
-            const u32 b = seed_hash2(key) & t.pmask;
-            if (!((t.present[b >> 5] >> (b & 31u)) & 1u)) return SEED_SLOT_NONE;
+            u32 pw;
+            const u32 pm = seed_presence(t, key, &pw);
+            if ((t.present[pw] & pm) != pm) return SEED_SLOT_NONE;
         }
         u32 sl_i = seed_hash(key) & t.mask;
         for (;;) {
@@ -1216,20 +1271,44 @@ struct SeedRun {
     u32 nranges = 0;         // 0: unfiltered
     DevBuf<u32> cnt, ents, slot_of, ctr, spos, sent, sseq, dummy;
     u32 scap = 0;
+    // the table as its builder left it (seed_list_table_async / join_table_async)
+    SeedTable t = {};
+    u32 capacity = 0;
+    int nanch_tab = 0;       // seed-list scan: anchors per probe of a pigeonhole table (0: random anchors)
+    bool filt = false;       // seed-list scan: the anchor-pair filter is on
 };
 
-// table of the anchor k-mers + one lookup per target position -> seed work
-// list (S.spos / S.sent / S.sseq, count in S.ctr[1]).  pos_limit: anchors at or
-// beyond this probe offset stay out of the table.  bcnt/nb/res: arrays of the
-// bucketed row build zeroed by the same init launch (may be null / 0).
-static int seed_table_lookup_async(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, u32 pos_limit,
-                                   int mm, bool allow_filter, SeedRun &S, u32 *bcnt, u32 nb, u32 *res, PhaseTimer &tm) {
+// slots with entries and set presence bits of S.t (seed_stats_kernel), read back
+static int seed_table_stats(catchhip_ctx *ctx, const SeedRun &S, u32 out[2]) {
+    DevBuf<u32> d;
+    TRY(d.alloc(2));
+    HIP_TRY(hipMemsetAsync(d.p, 0, 2 * sizeof(u32), ctx->stream));
+    hipLaunchKernelGGL(seed_stats_kernel, dim3(256), dim3(256), 0, ctx->stream, S.t, d.p);
+    HIP_TRY(hipGetLastError());
+    return chip_read_back(ctx, d.p, 2 * sizeof(u32), out);
+}
+
+// A power of two of at least `keys` x 2 slots: the probe chains of seed_count_kernel, seed_lookup_kernel,
+// seed_find_slot and kj_hitpos_kernel end at an EMPTY slot, and there always is one because at most `keys`
+// distinct keys (<= the entries that claim a slot) enter a table of twice as many slots.  No builder may size
+// its table below that.
+static u32 seed_table_capacity(u64 keys) {
+    u32 capacity = 1024;
+    while ((u64)capacity < 2 * keys) capacity <<= 1;
+    return capacity;
+}
+
+// The seed-list scan's table of the anchor k-mers (S.t).  pos_limit: anchors at or beyond this probe offset stay
+// out of the table.  bcnt/nb/res: arrays of the bucketed row build zeroed by the same init launch (may be null /
+// 0).
+static int seed_list_table_async(catchhip_ctx *ctx, const catchhip_probes *P, u32 pos_limit, bool allow_filter,
+                                 SeedRun &S, u32 *bcnt, u32 nb, u32 *res, PhaseTimer &tm) {
     const int k = P->k, kb = std::min(k, 32);
     const u64 nent64 = (u64)P->nent;
     if (nent64 >= ((u64)1 << 31)) { chip_set_error("seed scan: too many anchors"); return CATCHHIP_EINVAL; }
     const u32 nent = (u32)nent64;
-    u32 capacity = 1024;
-    while ((u64)capacity < 2 * nent64) capacity <<= 1;
+    // (the filtered look-up wants a slot for EVERY anchor's k-mer, also of those beyond pos_limit: all nent may claim one)
+    const u32 capacity = seed_table_capacity(nent64);
     TRY(S.slot.reserve(capacity));
     TRY(S.cnt.reserve(capacity));
     TRY(S.ents.reserve(nent));
@@ -1245,34 +1324,47 @@ static int seed_table_lookup_async(catchhip_ctx *ctx, const catchhip_probes *P, 
     const bool filt = allow_filter && k <= 30 && !chip_test_env("CATCHHIP_SEED_KEEP_ALL") &&
                       (P->pigeonhole ? nanch_tab >= 2 && nanch_tab <= SEED_SIB + 1 && pos_limit != 0xffffffffu && (nanch_tab - 1) * k <= SL_HALO
                                      : filt_random);
-    const int need2 = filt && nanch_tab - mm >= 2 ? 1 : 0;
-    const u32 nblk = (u32)div_up(T->total, SL_TILE);
-    S.nranges = filt ? nblk : 0;
-    if (filt) { TRY(S.aslot.reserve(nent)); TRY(S.sib.reserve((size_t)nent)); TRY(S.ranges.reserve(nblk)); }
-    TRY(S.spos.reserve(S.scap));
-    TRY(S.sent.reserve(S.scap));
-    TRY(S.sseq.reserve(S.scap));
+    S.filt = filt; S.nanch_tab = nanch_tab; S.capacity = capacity;
+    if (filt) { TRY(S.aslot.reserve(nent)); TRY(S.sib.reserve((size_t)nent)); }
     if (!res) { TRY(S.dummy.reserve(8)); res = S.dummy.p; }
-    // presence bits: for the pigeonhole tables of a whole-genome scan (most positions miss); 4 per slot
+    // presence bits: for the pigeonhole tables of a whole-genome scan (most positions miss); 4 per slot, of which
+    // a key sets one (round 14: more bits per key are the join's; here they stay at one until a kernel trace of
+    // S5 shows seed_lookup_kernel faster with more)
     const bool pres = P->pigeonhole && capacity >= (1u << 16) && capacity <= (1u << 29);
     const u32 pwords = pres ? capacity / 8 : 0;      // 4 * capacity bits
     if (pres) TRY(S.present.reserve(pwords));
-    SeedTable t = {S.slot.p, S.cnt.p, S.ents.p, capacity - 1, filt ? (const uint4 *)S.sib.p : nullptr,
-                   pres ? S.present.p : (u32 *)nullptr, pres ? 4 * capacity - 1 : 0u};
+    S.t = {S.slot.p, S.cnt.p, S.ents.p, capacity - 1, filt ? (const uint4 *)S.sib.p : nullptr,
+           pres ? S.present.p : (u32 *)nullptr, pres ? 4 * capacity - 1 : 0u, 1u};
     const dim3 eb((unsigned)div_up((i64)nent, 256)), tb(256);
     hipLaunchKernelGGL(seed_init_kernel, dim3((unsigned)std::min<i64>(div_up((i64)capacity, 256), 2048)), tb, 0,
                        ctx->stream, S.slot.p, S.cnt.p, capacity, S.ctr.p, bcnt, nb, res, pres ? S.present.p : (u32 *)nullptr, pwords);
     hipLaunchKernelGGL(seed_count_kernel, eb, tb, 0, ctx->stream, (const uint4 *)P->planes.p,
                        (const u32 *)P->sent_probe.p, (const u32 *)P->sent_pos.p, nent, pos_limit,
-                       nanch_tab, k, (int)P->pwords, kb, t, S.slot_of.p, filt ? S.aslot.p : (u32 *)nullptr);
-    hipLaunchKernelGGL(seed_alloc_kernel, dim3(capacity / SA_SLOTS), dim3(256), 0, ctx->stream, t, S.ctr.p);
-    hipLaunchKernelGGL(seed_fill_kernel, eb, tb, 0, ctx->stream, nent, t, (const u32 *)S.slot_of.p, nanch_tab,
+                       nanch_tab, k, (int)P->pwords, kb, S.t, S.slot_of.p, filt ? S.aslot.p : (u32 *)nullptr);
+    hipLaunchKernelGGL(seed_alloc_kernel, dim3((unsigned)div_up((i64)capacity, SA_SLOTS)), dim3(256), 0, ctx->stream, S.t, S.ctr.p);
+    hipLaunchKernelGGL(seed_fill_kernel, eb, tb, 0, ctx->stream, nent, S.t, (const u32 *)S.slot_of.p, nanch_tab,
                        (const u32 *)S.aslot.p, filt ? S.sib.p : nullptr, (const u32 *)P->sent_probe.p, (const u32 *)P->sent_pos.p);
-    hipLaunchKernelGGL(seed_lookup_kernel, dim3((unsigned)div_up(T->total, SL_TILE)), dim3(SL_THREADS), 0, ctx->stream,
+    tm.launch(4);
+    return 0;
+}
+
+// that table + one lookup per target position -> seed work list (S.spos / S.sent / S.sseq, count in S.ctr[1])
+static int seed_table_lookup_async(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, u32 pos_limit,
+                                   int mm, bool allow_filter, SeedRun &S, u32 *bcnt, u32 nb, u32 *res, PhaseTimer &tm) {
+    TRY(seed_list_table_async(ctx, P, pos_limit, allow_filter, S, bcnt, nb, res, tm));
+    const int k = P->k, kb = std::min(k, 32);
+    const int need2 = S.filt && S.nanch_tab - mm >= 2 ? 1 : 0;
+    const u32 nblk = (u32)div_up(T->total, SL_TILE);
+    S.nranges = S.filt ? nblk : 0;
+    if (S.filt) TRY(S.ranges.reserve(nblk));
+    TRY(S.spos.reserve(S.scap));
+    TRY(S.sent.reserve(S.scap));
+    TRY(S.sseq.reserve(S.scap));
+    hipLaunchKernelGGL(seed_lookup_kernel, dim3(nblk), dim3(SL_THREADS), 0, ctx->stream,
                        (const u32 *)T->planes.p, T->nwords, (u32)T->total, (const u32 *)T->seq_off.p,
-                       (u32)T->nseq, k, kb, nanch_tab, need2, T->has_n ? 1 : 0, t, S.spos.p, S.sent.p, S.sseq.p,
-                       S.ctr.p + 1, S.scap, filt ? S.ranges.p : (uint2 *)nullptr);
-    tm.launch(5);
+                       (u32)T->nseq, k, kb, S.nanch_tab, need2, T->has_n ? 1 : 0, S.t, S.spos.p, S.sent.p, S.sseq.p,
+                       S.ctr.p + 1, S.scap, S.filt ? S.ranges.p : (uint2 *)nullptr);
+    tm.launch(1);
     return 0;
 }
 
@@ -1603,19 +1695,18 @@ static void join_write_pass(catchhip_ctx *ctx, JoinRun &J) {
                            dim3(256), 0, ctx->stream, J.A);
 }
 
-static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, int mm, SeedRun &S, JoinRun &J,
-                    const HitSink &sink, BucketBuild &B, u32 nb, PhaseTimer &tm) {
+// The join's table of the anchor k-mers (S.t): as the seed-list scan builds it, without the sibling records.
+static int join_table_async(catchhip_ctx *ctx, const catchhip_probes *P, int mm, SeedRun &S, u32 *bcnt, u32 nb, u32 *res) {
     hipStream_t s = ctx->stream;
     const int k = P->k, kb = std::min(k, 32), NW = (int)P->pwords;
     const int nanch = (int)(P->L / k);
     const u32 pos_limit = (u32)std::min<i64>((i64)(mm + 1) * k, P->L);
-    const int ntab = (int)std::min<i64>(nanch, div_up((i64)pos_limit, k));
     const u64 nent64 = (u64)P->nent;
     if (nent64 >= ((u64)1 << 31)) { chip_set_error("seed scan: too many anchors"); return CATCHHIP_EINVAL; }
     const u32 nent = (u32)nent64;
-    // ---- table of the anchor k-mers (as the seed-list scan builds it, without the sibling records) ----------
-    u32 capacity = 1024;
-    while ((u64)capacity < 2 * nent64) capacity <<= 1;
+    // (Sized by all anchors although only the ntab below pos_limit claim a slot: 2 x nprobes x ntab was measured in
+    // round 14 -- two of S4's four tables halve -- and its kernels fell by 0.1 ms per step, below what a part must earn.)
+    const u32 capacity = seed_table_capacity(nent64);
     TRY(S.slot.reserve(capacity));
     TRY(S.cnt.reserve(capacity));
     TRY(S.ents.reserve(nent));
@@ -1625,19 +1716,34 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
     // One presence bit per slot (4 MB for the 32 M slots of S4's largest group: mostly L2 hits; the seed-list scan's
     // 4 bits per slot are 16 MB: every probe a trip to the memory-side cache).  Measured on S4, whole scan phase:
     // 4 bits 33.8 ms, 1 bit 30.5, half a bit 30.4, a quarter 30.8 (more false positives go on to the slot array).
+    // Round 14: a key sets and tests up to KJ_PRESENCE_BITS bits of its word (seed_presence); the words stay.
     const u32 pbits = pres ? std::max<u32>(capacity, 1u << 16) : 0;
     const u32 pwords = pbits / 32;
     if (pres) TRY(S.present.reserve(pwords));
-    SeedTable t = {S.slot.p, S.cnt.p, S.ents.p, capacity - 1, nullptr, pres ? S.present.p : (u32 *)nullptr,
-                   pres ? pbits - 1 : 0u};
+    const u32 pkey = (u32)std::min<long long>(3, std::max<long long>(1, chip_test_env_int("CATCHHIP_PRESENCE_BITS", KJ_PRESENCE_BITS)));
+    S.capacity = capacity; S.filt = false; S.nanch_tab = nanch;
+    S.t = {S.slot.p, S.cnt.p, S.ents.p, capacity - 1, nullptr, pres ? S.present.p : (u32 *)nullptr, pres ? pbits - 1 : 0u, pkey};
     const dim3 eb((unsigned)div_up((i64)nent, 256)), tb(256);
     hipLaunchKernelGGL(seed_init_kernel, dim3((unsigned)std::min<i64>(div_up((i64)capacity, 256), 2048)), tb, 0, s,
-                       S.slot.p, S.cnt.p, capacity, S.ctr.p, B.bcnt.p, nb, B.res.p, pres ? S.present.p : (u32 *)nullptr, pwords);
+                       S.slot.p, S.cnt.p, capacity, S.ctr.p, bcnt, nb, res, pres ? S.present.p : (u32 *)nullptr, pwords);
     hipLaunchKernelGGL(seed_count_kernel, eb, tb, 0, s, (const uint4 *)P->planes.p, (const u32 *)P->sent_probe.p,
-                       (const u32 *)P->sent_pos.p, nent, pos_limit, nanch, k, NW, kb, t, S.slot_of.p, (u32 *)nullptr);
-    hipLaunchKernelGGL(seed_alloc_kernel, dim3(capacity / SA_SLOTS), dim3(256), 0, s, t, S.ctr.p);
-    hipLaunchKernelGGL(seed_fill_kernel, eb, tb, 0, s, nent, t, (const u32 *)S.slot_of.p, nanch, (const u32 *)nullptr,
+                       (const u32 *)P->sent_pos.p, nent, pos_limit, nanch, k, NW, kb, S.t, S.slot_of.p, (u32 *)nullptr);
+    hipLaunchKernelGGL(seed_alloc_kernel, dim3((unsigned)div_up((i64)capacity, SA_SLOTS)), dim3(256), 0, s, S.t, S.ctr.p);
+    hipLaunchKernelGGL(seed_fill_kernel, eb, tb, 0, s, nent, S.t, (const u32 *)S.slot_of.p, nanch, (const u32 *)nullptr,
                        (uint4 *)nullptr, (const u32 *)nullptr, (const u32 *)nullptr);
+    return 0;
+}
+
+static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_targets *T, int mm, SeedRun &S, JoinRun &J,
+                    const HitSink &sink, BucketBuild &B, u32 nb, PhaseTimer &tm) {
+    hipStream_t s = ctx->stream;
+    const int k = P->k, kb = std::min(k, 32), NW = (int)P->pwords;
+    const int nanch = (int)(P->L / k);
+    const u32 pos_limit = (u32)std::min<i64>((i64)(mm + 1) * k, P->L);
+    const int ntab = (int)std::min<i64>(nanch, div_up((i64)pos_limit, k));
+    TRY(join_table_async(ctx, P, mm, S, B.bcnt.p, nb, B.res.p));
+    const u32 nent = (u32)P->nent, capacity = S.capacity;
+    const SeedTable t = S.t;
     // ---- hit positions, in position order ------------------------------------------------------------------
     const u32 nblk = (u32)div_up(T->total, KJ_TILE);
     TRY(J.stage_key.reserve((size_t)nblk * KJ_TILE));
@@ -1721,9 +1827,13 @@ static int run_join(catchhip_ctx *ctx, const catchhip_probes *P, const catchhip_
     J.ngiant = ((volatile u32 *)h)[1];
     unsigned long long pairs = 0, slots = 0;
     for (int i = 0; i < 64; ++i) { pairs += ((volatile unsigned long long *)hp)[i]; slots += ((volatile unsigned long long *)hp)[64 + i]; }
-    if (getenv("CATCHHIP_TIMING"))
-        fprintf(stderr, "[catchhip]   join: %u hit positions, %llu pairs, %llu lane slots in wave-wide runs, %u hits, %u tasks of cut runs\n",
-                J.nhit, pairs, slots, nhits, J.ngiant);
+    if (getenv("CATCHHIP_TIMING")) {
+        u32 tab[2] = {0, 0};   // slots with entries, set presence bits
+        TRY(seed_table_stats(ctx, S, tab));
+        fprintf(stderr, "[catchhip]   join: %u hit positions, %llu pairs, %llu lane slots in wave-wide runs, %u hits, %u tasks of cut runs; "
+                        "table of %u slots, %u keys, %u presence bits set (%u per key)\n",
+                J.nhit, pairs, slots, nhits, J.ngiant, capacity, tab[0], tab[1], S.t.present ? S.t.pkey : 0u);
+    }
     if (J.ngiant > giant_cap) {   // absurdly repetitive input: the seed-list scan copes (slowly)
         ++ctx->capacity_events[CAPEV_GIANT_TASKS];
         return 1;
@@ -2827,5 +2937,46 @@ extern "C" int catchhip_rows_from_host(catchhip_ctx *ctx, const i32 *set_id, con
     HIP_TRY(hipMemcpyAsync(R->genome_off.p, go.data(), sizeof(u32) * (ngenomes + 1), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
     *out = R.release();
+    return 0;
+}
+
+// ------------------------------------------------------------------------
+// Test entry point of the seed table (tests/test_seed_table.py): the table of P's anchor k-mers for `mm` mismatches,
+// built by join_table_async (as_list == 0) or seed_list_table_async (as_list != 0; allow_filter as run_seed_async
+// passes it) exactly as the scans call them, and copied out.  No logic of its own beyond the copies.
+// ------------------------------------------------------------------------
+extern "C" int catchhip_selftest_seed_table(catchhip_ctx *ctx, const catchhip_probes *P, i32 mm, i32 as_list,
+                                            i32 allow_filter, i64 slot_room, u32 *o_slots, u32 *o_ents, u32 *o_present,
+                                            u32 *o_aslot, i64 *scalars) {
+    ARG_CHECK(ctx && P && o_slots && o_ents && o_present && o_aslot && scalars && mm >= 0);
+    ARG_CHECK(P->dna5 && P->L > 0 && P->L <= 256 && P->pwords >= 1 && P->pwords <= 8 && P->nent > 0 && P->k > 0 && P->k <= P->L);
+    ARG_CHECK(as_list || join_path_ok(P, mm));
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    SeedRun S;
+    DevBuf<u32> res;
+    TRY(res.alloc(8));
+    PhaseTimer tm(ctx, PHASE_SCAN);
+    if (as_list) {
+        const u32 pos_limit = P->pigeonhole ? (u32)std::min<i64>((i64)(mm + 1) * P->k, P->L) : 0xffffffffu;
+        TRY(seed_list_table_async(ctx, P, pos_limit, allow_filter != 0, S, nullptr, 0, res.p, tm));
+    } else {
+        TRY(join_table_async(ctx, P, mm, S, nullptr, 0, res.p));
+    }
+    HIP_TRY(hipGetLastError());
+    const size_t nent = (size_t)P->nent, pwords = S.t.present ? ((size_t)S.t.pmask + 1) / 32 : 0;
+    ARG_CHECK((i64)S.capacity <= slot_room && (i64)pwords * 8 <= slot_room);
+    u32 ctr[4], tab[2];
+    TRY(seed_table_stats(ctx, S, tab));
+    HIP_TRY(hipMemcpyAsync(o_slots, S.slot.p, sizeof(uint4) * S.capacity, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(o_ents, S.ents.p, sizeof(u32) * nent, hipMemcpyDeviceToHost, s));
+    if (pwords) HIP_TRY(hipMemcpyAsync(o_present, S.present.p, sizeof(u32) * pwords, hipMemcpyDeviceToHost, s));
+    if (S.filt) HIP_TRY(hipMemcpyAsync(o_aslot, S.aslot.p, sizeof(u32) * nent, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ctr, S.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    tm.finish();
+    scalars[0] = S.capacity; scalars[1] = tab[0]; scalars[2] = tab[1]; scalars[3] = (i64)pwords;
+    scalars[4] = S.t.present ? S.t.pkey : 0; scalars[5] = ctr[0]; scalars[6] = S.filt ? 1 : 0; scalars[7] = S.nanch_tab;
     return 0;
 }

@@ -34,11 +34,13 @@
 #define KJ_LANES_W 48u                 // runs of fewer windows ...
 #define KJ_LANES_PAIRS 4096u           // ... and at most this many pairs get a lane per window (kj_lanes)
 #define KJ_GIANT_PAIRS (1u << 15)      // pairs of one run a single wavefront takes; beyond: tasks of fewer entries
+#define KJ_PRESENCE_BITS 3             // bits of its presence word a key sets and kj_hitpos tests (seed_presence)
 
 __device__ __forceinline__ u32 seed_find_slot(const SeedTable &t, unsigned long long key, uint2 *range) {
     if (t.present) {
-        const u32 b = seed_hash2(key) & t.pmask;
-        if (!((t.present[b >> 5] >> (b & 31u)) & 1u)) return SEED_SLOT_NONE;
+        u32 pw;
+        const u32 pm = seed_presence(t, key, &pw);
+        if ((t.present[pw] & pm) != pm) return SEED_SLOT_NONE;
     }
     u32 sl_i = seed_hash(key) & t.mask;
     for (;;) {
@@ -75,11 +77,11 @@ kj_hitpos_kernel(const u32 *__restrict__ tplanes, i64 nwords, u32 total, const u
         at[j] = seed_hash(key[j]) & t.mask;
     }
     if (t.present) {
-        u32 pw[KJ_PPT];
+        u32 pw[KJ_PPT], pm[KJ_PPT];
 #pragma unroll
-        for (int j = 0; j < KJ_PPT; ++j) { const u32 b = seed_hash2(key[j]) & t.pmask; pw[j] = cand[j] ? (t.present[b >> 5] >> (b & 31u)) & 1u : 0u; }
+        for (int j = 0; j < KJ_PPT; ++j) { u32 w; pm[j] = seed_presence(t, key[j], &w); pw[j] = cand[j] ? t.present[w] : 0u; }
 #pragma unroll
-        for (int j = 0; j < KJ_PPT; ++j) cand[j] = cand[j] && pw[j];
+        for (int j = 0; j < KJ_PPT; ++j) cand[j] = cand[j] && (pw[j] & pm[j]) == pm[j];
     }
     uint4 first[KJ_PPT];
 #pragma unroll

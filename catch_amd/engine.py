@@ -435,6 +435,32 @@ class Context:
                 "S": o_S[:n], "hits": int(scalars[0]), "rows": rows, "lmax": int(scalars[2]),
                 "overflow": bool(scalars[3]), "radix": bool(scalars[4])}
 
+    # -- test entry point of the seed table (tests/test_seed_table.py) -----
+    def selftest_seed_table(self, probes, nent, mismatches, as_list=False, allow_filter=True):
+        """catchhip_selftest_seed_table: the table of `probes`' anchor k-mers (nent anchor entries) as the key-grouped
+        join builds it, or with as_list as the seed-list scan does.  Returns a dict: capacity, slots ((capacity, 4)
+        uint32 {key lo, key hi, first, count}), ents (nent), present (the presence words; empty without the filter),
+        bits_per_key, keys (slots with entries) and set_bits as the device counted them, entries (in the table),
+        filtered, aslot (nent; only when filtered), anchors_per_probe."""
+        nent = int(nent)
+        room = 1024
+        while room < 2 * nent:
+            room *= 2
+        slots = np.zeros((room, 4), dtype=np.uint32)
+        ents = np.zeros(max(nent, 1), dtype=np.uint32)
+        present = np.zeros(room // 8, dtype=np.uint32)
+        aslot = np.zeros(max(nent, 1), dtype=np.uint32)
+        scalars = np.zeros(8, dtype=np.int64)
+        check(self._L.catchhip_selftest_seed_table(
+            self._h, probes._h, int(mismatches), int(bool(as_list)), int(bool(allow_filter)), room,
+            _ptr(slots, c_u32p), _ptr(ents, c_u32p), _ptr(present, c_u32p), _ptr(aslot, c_u32p), _ptr(scalars, c_i64p)))
+        cap = int(scalars[0])
+        filt = bool(scalars[6])
+        return {"capacity": cap, "slots": slots[:cap], "ents": ents[:nent], "present": present[:int(scalars[3])],
+                "bits_per_key": int(scalars[4]), "keys": int(scalars[1]), "set_bits": int(scalars[2]),
+                "entries": int(scalars[5]), "filtered": filt, "aslot": aslot[:nent] if filt else None,
+                "anchors_per_probe": int(scalars[7])}
+
     # -- near-duplicate filter --------------------------------------------
     def ndf_hamming(self, probe_strs, L, positions, dist_thres):
         n = len(probe_strs)

@@ -596,6 +596,22 @@ int catchhip_selftest_row_build(catchhip_ctx *ctx, const uint32_t *rec, const ui
                                 uint32_t *o_end, uint32_t *o_mcnt, uint32_t *o_blmax,
                                 uint64_t *o_bsum, uint32_t *o_S, uint32_t *o_bstart,
                                 int64_t *scalars);
+/* Test entry point of the seed table (the hash table of the anchor k-mers that both
+ * seed scans look target k-mers up in; csrc/scan.hip); tests/test_seed_table.py
+ * compares it with a dictionary built in NumPy.  No reference counterpart.  Builds the
+ * table of P for `mismatches` as the key-grouped join does (as_list == 0) or as the
+ * seed-list scan does (as_list != 0; allow_filter: its anchor-pair filter may apply)
+ * and copies it out.  slot_room: slots the caller has room for -- o_slots 4 words per
+ * slot {key lo, key hi, first, count}, o_present slot_room / 8 words; o_ents and
+ * o_aslot one word per anchor entry of P (o_aslot is written only with the filter on).
+ * scalars[8] = capacity (slots), slots with entries, set presence bits, presence
+ * words (0: no presence filter), bits a key sets in its word, entries in the table,
+ * filter on (0 / 1), anchors per probe (0: not a pigeonhole table).
+ * CATCHHIP_EINVAL when the table does not fit slot_room. */
+int catchhip_selftest_seed_table(catchhip_ctx *ctx, const catchhip_probes *P, int32_t mismatches,
+                                 int32_t as_list, int32_t allow_filter, int64_t slot_room,
+                                 uint32_t *o_slots, uint32_t *o_ents, uint32_t *o_present,
+                                 uint32_t *o_aslot, int64_t *scalars);
 /* Test entry point of the launch plans of the candidate rules (csrc/rule_host.h);
  * tests/test_candidate_launch_plan.py compares them with the tests' own arithmetic.
  * Host arithmetic only: no context, no device.  No reference counterpart.
