@@ -105,6 +105,8 @@ PROTOTYPES = {
     "catchhip_rows_extend": (ctypes.c_int, [
         c_vp, c_vp, c_vp, ctypes.c_int32, c_i32p, c_vpp, c_i64p]),
     "catchhip_rows_subtract": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vpp, c_i64p]),
+    "catchhip_rows_union": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vpp, c_i64p]),
+    "catchhip_rows_longest": (ctypes.c_int, [c_vp, c_u32p]),
     "catchhip_rows_below_depth": (ctypes.c_int, [
         c_vp, c_vp, ctypes.c_int64, c_i64p, ctypes.c_int64, ctypes.c_int32, c_vpp, c_i64p, c_i64p]),
     "catchhip_rows_prune": (ctypes.c_int, [

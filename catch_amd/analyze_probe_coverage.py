@@ -53,6 +53,12 @@ def parse_args(argv=None):
                         "cover_extension (instead of -m / -e)")
     p.add_argument("--limit-target-genomes", type=int,
                    help="use only the first N target genomes of each dataset")
+    p.add_argument("--either-strand", action="store_true",
+                   help="the probes capture a locus whichever strand of it was "
+                        "deposited (design --either-strand): analyse the "
+                        "forward strands only, under the probes followed by "
+                        "their reverse complements; a probe's map count is the "
+                        "sum over its two orientations")
     p.add_argument("--print-analysis", action="store_true")
     p.add_argument("--write-analysis-to-tsv")
     p.add_argument("--write-sliding-window-coverage")
@@ -172,7 +178,8 @@ def main(args):
             [names[d] for d in ds],
             island_of_exact_match=args.island_of_exact_match,
             cover_extension=e, kmer_probe_map_k=args.kmer_probe_map_k,
-            target_regions=None if regions is None else regions.select_groups(ds))
+            target_regions=None if regions is None else regions.select_groups(ds),
+            **(dict(rc_too=False, either_strand=True) if args.either_strand else {}))
         a.run()
         analyzers.append(a)
         for local, d in enumerate(ds):

@@ -38,15 +38,26 @@ class Analyzer:
     def __init__(self, probes, mismatches, lcf_thres, target_genomes,
                  target_genomes_names=None, island_of_exact_match=0,
                  custom_cover_range_fn=None, cover_extension=0,
-                 kmer_probe_map_k=10, rc_too=True, target_regions=None):
+                 kmer_probe_map_k=10, rc_too=True, either_strand=False,
+                 target_regions=None):
         if custom_cover_range_fn is not None:
             raise NotImplementedError(
                 "custom hybridization functions cannot run on the GPU path")
+        # either_strand (not an argument of the reference's class): the probes capture a locus whichever strand of it
+        # was deposited (design --either-strand).  The analysed list is then the probes followed by their reverse
+        # complements, against the forward strand only: bases covered, average depth, sliding-window depth and
+        # uncovered regions describe the forward strand's loci under either orientation of a probe.  probe_map_counts
+        # folds each reverse complement's count onto its probe: a sequence that both orientations map to counts twice.
+        if either_strand and rc_too:
+            raise ValueError("either_strand analyses the forward strand under both orientations of the probes; "
+                             "rc_too must be False with it")
+        self.either_strand = bool(either_strand)
         # the bases that were to be covered at all (catch_amd.target_regions.TargetRegions, or None: every base; not
         # an argument of the reference's class): uncovered_regions() then lists runs of wanted bases only.  Everything
         # else the analyzer reports keeps describing whole genomes.
         self.target_regions = target_regions
         self.probes = probes
+        self._analysed = (list(probes) + [p.reverse_complement() for p in probes]) if self.either_strand else probes
         self.target_genomes = target_genomes
         if target_genomes_names:
             if len(target_genomes_names) != len(target_genomes):
@@ -125,7 +136,7 @@ class Analyzer:
         self._covers = None
         self._sliding = self._windows = None
         self._uncovered = {}
-        strs = [p.seq_str for p in self.probes]
+        strs = [p.seq_str for p in self._analysed]
         flat = self._flat_genomes()
         self._scan_inputs = None
         if not strs or not flat:
@@ -156,10 +167,18 @@ class Analyzer:
                     self.bp_covered[i][j][rc] = int(uni[g])
                     self._total_covered[i][j][rc] = int(tot[g])
                 if not rc:
-                    for pi in np.nonzero(per_probe)[0]:
-                        self.probe_map_counts[self.probes[pi]] += int(per_probe[pi])
+                    self._fold_map_counts(per_probe)
         finally:
             probes_dev.close()
+
+    def _fold_map_counts(self, per_probe):
+        """per_probe[a] = the sequences entry `a` of the analysed list maps to,
+        added to probe_map_counts; under either_strand entry n + i, the reverse
+        complement of probe i, counts for probe i (a sequence that both
+        orientations map to counts twice)."""
+        n = len(self.probes)
+        for a in np.nonzero(per_probe)[0]:
+            self.probe_map_counts[self.probes[a % n if self.either_strand else a]] += int(per_probe[a])
 
     @property
     def target_covers(self):
@@ -534,7 +553,7 @@ class Analyzer:
         first sequence and the key inside it are picked on the device."""
         if self._scan_inputs is None:
             return []
-        strs = [p.seq_str for p in self.probes]
+        strs = [p.seq_str for p in self._analysed]
         state = np.random.get_state()
         np.random.set_state(self._np_state)
         try:
@@ -543,7 +562,7 @@ class Analyzer:
                 k=self.kmer_probe_map_k, with_draws=True)
         finally:
             np.random.set_state(state)
-        order = probe.anchor_order(self.probes, strs, uniq, ep, eo, draws, k)
+        order = probe.anchor_order(self._analysed, strs, uniq, ep, eo, draws, k)
         ctx = engine.default_context()
         probes_dev = engine.Probes(ctx, uniq, owner, ep, eo, k)
         try:
@@ -563,8 +582,10 @@ class Analyzer:
 
     def ordered_probe_map_counts(self):
         """[(probe, sequences it maps to)] in the reference's order."""
-        return [(self.probes[pi], self.probe_map_counts[self.probes[pi]])
-                for pi in self._map_count_order()]
+        order = self._map_count_order()
+        if self.either_strand:      # a probe stands where its first orientation is met
+            order = list(dict.fromkeys(a % len(self.probes) for a in order))
+        return [(self.probes[pi], self.probe_map_counts[self.probes[pi]]) for pi in order]
 
     def write_probe_map_counts(self, fn):
         write_probe_map_counts(self.ordered_probe_map_counts(), fn)

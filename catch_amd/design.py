@@ -43,6 +43,8 @@ report of catch_amd.probe_report for the output FASTA.
 --target-regions / --exclude-regions (nor these) say which bases are to be
 covered at all: BED intervals per FASTA record, the cover rows cut to them
 after the scan (catch_amd/target_regions.py has the rules).
+--either-strand (nor this) lets a candidate cover what its reverse complement
+hybridises to as well: targets filed in mixed orientations get one probe set.
 --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
@@ -195,6 +197,17 @@ def parse_args(argv=None, args_type="basic"):
                         "existing probes count and stay; with --coverage-depth "
                         "above 1 the first k layers are no longer the design "
                         "at depth k")
+    p.add_argument("--either-strand", action="store_true",
+                   help="design for double-stranded libraries: a candidate "
+                        "covers a base when its own sequence OR its reverse "
+                        "complement hybridises there (both under -m, -l, "
+                        "--island-of-exact-match and -e), so that targets "
+                        "deposited in mixed orientations are not covered "
+                        "twice, once per strand; the output holds the picked "
+                        "candidates as they are (--add-reverse-complements "
+                        "still adds the other orientation); an analysis then "
+                        "describes the targets under either orientation of "
+                        "the probes")
     p.add_argument("--max-probes", type=int, default=None, metavar="N",
                    help="a probe budget: after the set cover, keep only N of "
                         "its picks over all datasets -- the picks are merged "
@@ -384,6 +397,23 @@ def main(args):
                              "--cluster-from-fragments (a default of "
                              "design_large.py): nothing is clustered; set "
                              "--cluster-from-fragments to 0 as well"))
+    if args.either_strand:
+        if args.skip_set_cover:
+            raise Exception(("Cannot use --either-strand with "
+                             "--skip-set-cover: it is the set cover's sets "
+                             "that take in the other strand"))
+        if args.cluster_and_design_separately:
+            raise Exception(("Cannot use --either-strand with "
+                             "--cluster-and-design-separately (a default of "
+                             "design_large.py): the two strands are set against "
+                             "each dataset as a whole; set "
+                             "--cluster-and-design-separately to 0 (and, where "
+                             "it is set, --cluster-from-fragments to 0 too)"))
+        if args.cluster_from_fragments:
+            raise Exception(("Cannot use --either-strand with "
+                             "--cluster-from-fragments (a default of "
+                             "design_large.py): nothing is clustered; set "
+                             "--cluster-from-fragments to 0 as well"))
     from catch_amd import target_regions
     if target_regions.given(args):
         opt = "--target-regions" if args.target_regions else "--exclude-regions"
@@ -533,7 +563,7 @@ def main(args):
         prune_redundant=args.prune_redundant,
         max_probes=args.max_probes, pick_gains=want_gains,
         curve_points=args.coverage_curve_points,
-        target_regions=regions)
+        target_regions=regions, either_strand=args.either_strand)
     filters.append(scf)
     if args.add_adapters:      # bin/design.py:345-365 (default sequences :350, :354)
         from catch_amd.filter import adapter_filter
@@ -645,7 +675,9 @@ def main(args):
             cover_extension=args.cover_extension,
             kmer_probe_map_k=k_analyzer,
             rc_too=args.add_reverse_complements,
-            target_regions=regions)
+            target_regions=regions,
+            # (with both orientations in the output the usual two-strand analysis is the report)
+            either_strand=args.either_strand and not args.add_reverse_complements)
         analyzer.run()
         if args.write_analysis_to_tsv:
             analyzer.write_data_matrix_as_tsv(args.write_analysis_to_tsv)

@@ -1146,6 +1146,24 @@ class Rows:
             self.ctx._h, self._h, covered._h, ctypes.byref(h), ctypes.byref(n)))
         return Rows(self.ctx, h, n.value, self.ngenomes)
 
+    def union(self, other):
+        """catchhip_rows_union: per (set, universe) the union of these rows and
+        `other`'s (Rows in the solver's form over the same universes, any set
+        ids), rows that overlap or touch merged -- sorted by (set, universe,
+        start), ready for greedy()."""
+        h = ctypes.c_void_p()
+        n = ctypes.c_int64(0)
+        check(self.ctx._L.catchhip_rows_union(
+            self.ctx._h, self._h, other._h, ctypes.byref(h), ctypes.byref(n)))
+        return Rows(self.ctx, h, n.value, self.ngenomes)
+
+    def longest(self):
+        """catchhip_rows_longest: the length of the longest row, as the table
+        holds it for the solvers."""
+        out = ctypes.c_uint32(0)
+        check(self.ctx._L.catchhip_rows_longest(self._h, ctypes.byref(out)))
+        return int(out.value)
+
     def restrict(self, mask):
         """catchhip_rows_restrict: these rows cut to their maximal runs of the
         bases `mask` (a BaseMask over the same universes) wants -- set, universe

@@ -19,7 +19,10 @@ when it was taken and the coverage after the first k picks
 the N picks with the largest such gains (allocate_budget).  `target_regions` (a
 keyword) says which bases are to be covered at all: after the scan the cover
 rows are cut to their runs of wanted bases (engine.BaseMask, Rows.restrict), and
-everything above then works on wanted bases only.
+everything above then works on wanted bases only.  `either_strand` (a keyword)
+makes a candidate cover what its own string OR its reverse complement
+hybridises to: a second scan of the reverse-complemented strings against the
+same targets and the union of the two row tables, set by set (Rows.union).
 
 Not supported (raises NotImplementedError): custom hybridization functions
 loaded from a Python file (`custom_cover_range_fn`, :288-299) -- an arbitrary
@@ -59,15 +62,16 @@ def _reverse_complement(s):
 class _KeywordsBeyondInit(type):
     """SetCoverFilter(..., fixed_probes=None, coverage_depth=1,
     prune_redundant=False, max_probes=None, pick_gains=False,
-    curve_points=100, target_regions=None): everything after `fixed_probes` is a keyword of the CALL
+    curve_points=100, target_regions=None, either_strand=False): everything after `fixed_probes` is a keyword of the CALL
     of the class, taken here and handed to the new object after __init__ ran.
     __init__ itself stays the reference's argument list followed by
     `fixed_probes`, the form its callers and the signature checks of the
     extension know; the others can only be given by name."""
 
     def __call__(cls, *args, coverage_depth=1, prune_redundant=False, max_probes=None, pick_gains=False,
-                 curve_points=100, target_regions=None, **kwargs):
+                 curve_points=100, target_regions=None, either_strand=False, **kwargs):
         obj = super().__call__(*args, **kwargs)
+        obj._set_either_strand(either_strand)
         obj._set_coverage_depth(coverage_depth)
         obj._set_prune_redundant(prune_redundant)
         obj._set_budget(max_probes, pick_gains, curve_points)
@@ -155,6 +159,21 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         self.target_regions = None  # (SetCoverFilter(..., target_regions=R) sets it: _KeywordsBeyondInit)
         self.last_wanted_bases = []
         self.last_coverable_bases = []
+        self.either_strand = False  # (SetCoverFilter(..., either_strand=True) sets it: _KeywordsBeyondInit)
+        self._strand_scan = None    # what the last _scan_group did under either_strand (_either_strand_rows)
+
+    def _set_either_strand(self, either_strand):
+        """Whether a candidate covers a locus whichever strand of it was
+        deposited (not an argument of the reference's class): its cover set is
+        then rows(scan of s) | rows(scan of revcomp(s)), both scans against the
+        targets as given and under the filter's own hybridization model and
+        cover extension (_scan_group).  The fixed probes and prune_probe_strs
+        get the same.  The picks are the candidates as handed in; of two
+        candidates that are each other's reverse complement the first one wins
+        the tie and the other then gains nothing."""
+        if not isinstance(either_strand, (bool, np.bool_)):
+            raise ValueError("either_strand must be True or False, not %r" % (either_strand,))
+        self.either_strand = bool(either_strand)
 
     def _set_target_regions(self, target_regions):
         """The bases that are to be covered at all (not an argument of the
@@ -234,7 +253,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         scan (_filter_strs_keeping_rows): the fused scan-and-solve call and the
         device front end never hand the rows out."""
         return (bool(self.fixed_probes) or self.coverage_depth > 1 or self.prune_redundant or self.pick_gains
-                or self.target_regions is not None)
+                or self.target_regions is not None or self.either_strand)
 
     def _anchor_table(self, strs, assume_unique=False, tolerant=False):
         """probe.anchor_table of `strs` under the strict hybridization model, or
@@ -266,10 +285,71 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
     def _scan_group(self, ctx, held, strs, genomes, assume_unique=False, table=None, targets=None):
         """_open_group and the cover rows of the probes on the targets ->
         (Targets, Probes, Rows), the Rows in `held` too."""
+        if self.either_strand and table is None:
+            table = self._anchor_table(strs, assume_unique)     # (the call _open_group would make)
         targets, probes = self._open_group(ctx, held, strs, genomes, assume_unique, table, targets)
         rows = engine.Rows.scan(ctx, probes, targets, **self._model_args())
+        if self.either_strand:
+            rows = self._either_strand_rows(ctx, rows, table, targets)
         held.append(rows)
         return targets, probes, rows
+
+    def _either_strand_rows(self, ctx, rows, table, targets):
+        """`rows` (the scan of `table`'s strings on `targets`, just made on
+        `ctx`) united, set by set, with the rows of the reverse-complemented
+        strings on the same targets; the two inputs are closed.  The anchors of
+        the reverse complements are a table of their own (drawn after the
+        forward one where anchors are random), the owners stay.  What the three
+        calls took is left in self._strand_scan for _add_scan_times."""
+        _k, uniq, owner, _ep, _eo = table
+        done = dict(phases={name: ctx.kernel_ms(ph) for name, ph in _SCAN_PHASES}, rows=rows.n)
+        rc_probes = rc_rows = None
+        try:
+            rc_uniq = [_reverse_complement(s) for s in uniq]
+            rk, _u, _o, rep, reo = self._anchor_table(rc_uniq, assume_unique=True)
+            rc_probes = engine.Probes(ctx, rc_uniq, owner, rep, reo, rk)
+            rc_rows = engine.Rows.scan(ctx, rc_probes, targets, **self._model_args())
+            # (the verify phase lies inside the scan phase)
+            done["rc_scan_ms"] = sum(ctx.kernel_ms(ph)[0] for ph in (engine.PHASE_SCAN, engine.PHASE_ROWS))
+            done["rows_rc"] = rc_rows.n
+            both = rows.union(rc_rows)
+            done["union_ms"] = ctx.kernel_ms(engine.PHASE_ROWS)[0]
+            done["rows_union"] = both.n
+        finally:
+            for h in (rc_rows, rc_probes, rows):
+                if h is not None:
+                    h.close()
+        self._strand_scan = done
+        return both
+
+    def _add_scan_times(self, timings, ctx, rows, group=None):
+        """The device times and the row count of the _scan_group call that made
+        `rows` into `timings`.  Under either_strand scan_ms / rows_ms / rows stay
+        those of the forward scan, beside them rc_scan_ms, union_ms, rows_rc and
+        rows_union; group = (number, of): the group's log line."""
+        if not self.either_strand:
+            _add_phase_times(timings, ctx, _SCAN_PHASES)
+            timings["rows"] += rows.n
+            return
+        done = self._strand_scan
+        for name, (ms, nl) in done["phases"].items():
+            timings[name] = timings.get(name, 0.0) + ms
+            ln = name.replace("_ms", "_launches")
+            timings[ln] = timings.get(ln, 0) + nl
+        timings["rows"] += done["rows"]
+        for name in ("rc_scan_ms", "union_ms", "rows_rc", "rows_union"):
+            timings[name] = timings.get(name, 0) + done[name]
+        if group is not None:
+            logger.info("Group %d of %d: either strand: %d rows forward, %d reverse, %d in the union",
+                        group[0], group[1], done["rows"], done["rows_rc"], done["rows_union"])
+
+    def _scan_ms(self, ctx):
+        """Device time of the last _scan_group call on `ctx`, all of it."""
+        ms = sum(ctx.kernel_ms(ph)[0] for ph in (engine.PHASE_SCAN, engine.PHASE_ROWS))     # (the verify phase lies inside the scan phase)
+        if self.either_strand:
+            done = self._strand_scan
+            ms = done["phases"]["scan_ms"][0] + done["phases"]["rows_ms"][0] + done["rc_scan_ms"] + done["union_ms"]
+        return ms
 
     def _make_sets(self, candidate_probes, target_genomes, ctx=None,
                    targets=None):
@@ -465,6 +545,9 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         one scan of the candidates per group.  Per group:
 
         1. The scan -> `rows`.
+           Under either_strand it is the union of two scans, the candidates'
+           and their reverse complements' (_scan_group), and so is the fixed
+           probes' table below.
         2. The first table.  With fixed probes they count as sets picked before
            the first round of the greedy loop (catch/utils/set_cover.py:362-550):
            their coverage C0_u (one more scan; the filter's own hybridization
@@ -501,6 +584,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
             raise NotImplementedError(
                 "fixed probes (extending an existing probe set) run on one rank" if fixed else
                 "target regions run on one rank" if regions is not None else
+                "either_strand runs on one rank" if self.either_strand else
                 "coverage_depth > 1, prune_redundant, pick_gains and max_probes run on one rank")
         ctx = self._context()
         ngroups = len(input_strs)
@@ -516,6 +600,8 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                                                   else dict(depth_ms=0.0)))
         if self.prune_redundant:
             timings.update(prune_ms=0.0, prune_launches=0, prune_rounds=0, pruned=0)
+        if self.either_strand:
+            timings.update(rc_scan_ms=0.0, union_ms=0.0, rows_rc=0, rows_union=0)
         if regions is not None:
             timings.update(mask_ms=0.0, restrict_ms=0.0, rows_restricted=0)
             self.last_wanted_bases = [0] * ngroups
@@ -539,8 +625,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                 held = []
                 try:
                     targets, _probes, rows = self._scan_group(ctx, held, strs, target_genomes, assume_unique)
-                    _add_phase_times(timings, ctx, _SCAN_PHASES)
-                    timings["rows"] += rows.n
+                    self._add_scan_times(timings, ctx, rows, (gi + 1, ngroups))
                     p = self._make_universe_p(target_genomes)
                     mask = None
                     if regions is not None:
@@ -563,8 +648,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                             p = [_bases_fraction(int(n), self.coverage) for n in coverable]
                     if fixed:
                         frows = self._scan_group(ctx, held, None, None, table=fixed_table, targets=targets)[2]
-                        timings["fixed_scan_ms"] += sum(ctx.kernel_ms(ph)[0] for ph in (
-                            engine.PHASE_SCAN, engine.PHASE_ROWS))     # (the verify phase lies inside the scan phase)
+                        timings["fixed_scan_ms"] += self._scan_ms(ctx)
                         if mask is not None:
                             frows = self._restrict_rows(ctx, held, frows, mask, timings)
                         first = rows.subtract(frows)
@@ -669,9 +753,12 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         held = []
         try:
             rows = self._scan_group(ctx, held, probe_strs, target_genomes, assume_unique=True)[2]
-            timings["scan_ms"] = ctx.kernel_ms(engine.PHASE_SCAN)[0]
-            timings["rows_ms"] = ctx.kernel_ms(engine.PHASE_ROWS)[0]
-            timings["rows"] = rows.n
+            if self.either_strand:
+                self._add_scan_times(timings, ctx, rows)
+            else:
+                timings["scan_ms"] = ctx.kernel_ms(engine.PHASE_SCAN)[0]
+                timings["rows_ms"] = ctx.kernel_ms(engine.PHASE_ROWS)[0]
+                timings["rows"] = rows.n
             kept, removed = _prune(ctx, rows, len(probe_strs), list(range(len(probe_strs))),
                                    self.coverage_depth, None, timings)
             timings["picks"] = len(kept)

@@ -10,7 +10,8 @@ against all the genomes under the set cover filter's definition of coverage
 (-m, -l, -e, --island-of-exact-match); then they are examined from the last
 record to the first, and one is dropped when every base it covers is covered
 by more than --coverage-depth of the probes still there
-(SetCoverFilter.prune_probe_strs).  Every base the set covered D times stays
+(SetCoverFilter.prune_probe_strs); with --either-strand a probe covers what its
+sequence or its reverse complement hybridises to.  Every base the set covered D times stays
 covered D times; the kept records are written in file order, and the two
 counts (kept, dropped) are printed.
 """
@@ -48,6 +49,11 @@ def parse_args(argv=None):
     p.add_argument("--coverage-depth", type=int, default=1, metavar="D",
                    help="keep every base covered by D probes that is covered "
                         "by D now (and every base covered by fewer as it is)")
+    p.add_argument("--either-strand", action="store_true",
+                   help="a probe covers a base when its sequence or its reverse "
+                        "complement hybridises there (double-stranded "
+                        "libraries): a record is redundant when the others "
+                        "cover its bases in either orientation")
     p.add_argument("--verbose", action="store_true")
     return p.parse_args(argv)
 
@@ -68,7 +74,7 @@ def main(args):
         island_of_exact_match=args.island_of_exact_match,
         cover_extension=args.cover_extension,
         kmer_probe_map_k=args.kmer_probe_map_k,
-        coverage_depth=args.coverage_depth)
+        coverage_depth=args.coverage_depth, either_strand=args.either_strand)
     kept, removed = scf.prune_probe_strs(strs, [g for genomes in genomes_grouped for g in genomes])
     logger.info("%d probes, %d redundant; %s", len(strs), len(removed), scf.last_timings)
     seq_io.write_probe_fasta([probe.Probe.from_str(strs[i]) for i in kept], args.write_probe_fasta)

@@ -340,6 +340,36 @@ int catchhip_rows_fetch_gain0(catchhip_ctx *ctx, const catchhip_rows *rows,
 int catchhip_rows_subtract(catchhip_ctx *ctx, const catchhip_rows *rows,
                            const catchhip_rows *covered,
                            catchhip_rows **out, int64_t *nrows);
+/* ---- either strand: the union of two row tables, set by set -----------------
+ * out = for every (set, universe) the normal form of the union of that pair's
+ * rows in `a` and in `b`: rows that overlap or touch merge, rows of different
+ * universes never do (not even where the last base of one universe and the
+ * first of the next are neighbours in global coordinates).  It is the cover
+ * set of a candidate that covers what its own string or another one -- its
+ * reverse complement -- hybridises to (SetCoverFilter(either_strand=True)); the
+ * reference looks at reverse complements for its ranks only
+ * (catch/filter/set_cover_filter.py:472-529) and has no counterpart.  `a`, `b`:
+ * row tables in the solver's form (a merged cover scan, rows_from_host,
+ * rows_extend, the result of rows_subtract / rows_restrict) over the same
+ * coordinate space (equal universe lengths); set ids are any non-negative
+ * values, a set may have rows in one table only.  The result is sorted by
+ * (set, universe, start), carries its exact longest row and -- when both
+ * tables carry gain0 -- gain0 summed from its own rows, sized to the larger of
+ * the two: it goes to catchhip_setcover_greedy as it is.  *nrows (may be NULL)
+ * = its row count.  One table empty gives a copy of the other.
+ * CATCHHIP_EINVAL for deferred, direct or grouped rows (either table), another
+ * coordinate space, 2^32 - 1 target bases and more, 2^31 rows and more, or a
+ * table found not to be in the solver's form.  Scratch: 16 bytes per input
+ * row.  Timed as phase 1. */
+int catchhip_rows_union(catchhip_ctx *ctx, const catchhip_rows *a,
+                        const catchhip_rows *b, catchhip_rows **out,
+                        int64_t *nrows);
+/* *longest = the length of the longest row as the table holds it on the host
+ * (the solvers size their tiles by it): exact for rows_from_host, rows_union,
+ * rows_subtract, rows_restrict and rows_below_depth, 0 for an empty table.  No
+ * device work.  CATCHHIP_EINVAL for deferred rows (the scan has not reported
+ * yet). */
+int catchhip_rows_longest(const catchhip_rows *rows, uint32_t *longest);
 /* ---- coverage depth: rows below depth k under the picks so far --------------
  * out = every row of `rows` whose set is not in picks[0..npicks), cut into its
  * maximal runs of bases b with depth(b) < depth, where depth(b) = the number of
