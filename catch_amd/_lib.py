@@ -140,6 +140,8 @@ PROTOTYPES = {
         c_vp, c_u64p, c_u32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     "catchhip_selftest_wave": (ctypes.c_int, [c_vp, c_u32p, ctypes.c_int64, c_u32p, c_u64p]),
     "catchhip_selftest_find_segment": (ctypes.c_int, [c_vp, c_u32p, ctypes.c_int64, c_u32p, ctypes.c_int64, c_u32p]),
+    "catchhip_selftest_spans": (ctypes.c_int, [c_vp, c_u64p, ctypes.c_int64, c_u32p, c_u32p, ctypes.c_int64,
+                                               ctypes.c_uint32, c_u32p, c_u64p, c_u64p, c_u32p]),
     "catchhip_selftest_candidate_plan": (ctypes.c_int, [
         ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
         c_u32p, c_u32p]),

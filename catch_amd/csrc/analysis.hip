@@ -3,8 +3,7 @@
 // (catchhip_rows_window_depth): the part of the analysis (catch/coverage_analysis.py:336-413) that walks every
 // base of every genome.
 //
-//   1. wd_diff_kernel      d[gs] += 1, d[ge] -= 1 over the global coordinates (u32, wrapping; integer atomics, so
-//                          the result does not depend on the order of the rows)
+//   1. chip_depth_diff     (depth.hip) span_mark_diff of every row: d[gs] += 1, d[ge] -= 1 over the global coordinates
 //   2. chip_exclusive_scan_u32 in place: d[i] = sum of the differences before i, depth[pos] = d[pos + 1].  A row
 //                          never leaves its universe, so the depth is 0 across every universe boundary and one scan
 //                          over the whole coordinate space serves every span.
@@ -14,7 +13,7 @@
 //   5. wd_window_kernel    one window per thread: P(end) - P(start) with P(x) = tile_off[x / WD_TILE] + d[x + 1]
 //
 // Everything is integer arithmetic; the host divides sum by count.
-#include "internal.h"
+#include "rows_host.h"
 #include "wave.h"
 
 #include <algorithm>
@@ -24,14 +23,6 @@
 #define WD_TILE (WD_THREADS * WD_ITEMS)
 #define WD_TILE_SHIFT 11
 static_assert(WD_TILE == 1 << WD_TILE_SHIFT, "tile index is a shift");
-
-__global__ void __launch_bounds__(256)
-wd_diff_kernel(const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n, u32 *__restrict__ d) {
-    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    atomicAdd(&d[gs[r]], 1u);
-    atomicAdd(&d[ge[r]], 0xffffffffu);
-}
 
 // d[pos + 1] holds depth[pos] (mod 2^32) on entry and the sum of (depth mod 2^16) over [tile start, pos) on exit,
 // for every pos <= total (the depth at pos == total counts as 0)
@@ -175,9 +166,7 @@ extern "C" int catchhip_rows_window_depth(catchhip_ctx *ctx, const catchhip_rows
     HIP_TRY(hipMemcpyAsync(d_n.p, h_n.data(), sizeof(u32) * (size_t)nspans, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_off.p, h_off.data(), sizeof(u64) * ((size_t)nspans + 1), hipMemcpyHostToDevice, st));
     PhaseTimer tm(ctx, PHASE_ROWS);
-    if (R->n)
-        hipLaunchKernelGGL(wd_diff_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, st, (const u32 *)R->gs.p,
-                           (const u32 *)R->ge.p, (u32)R->n, d.p);
+    (void)chip_depth_diff(ctx, R, nullptr, 0u, d.p);
     TRY(chip_exclusive_scan_u32(ctx, d.p, d.p, (i64)total + 1, tmp));
     hipLaunchKernelGGL(wd_tile_kernel, dim3((unsigned)ntiles), dim3(WD_THREADS), 0, st, d.p, total, tile_off.p);
     hipLaunchKernelGGL(wd_tilescan_kernel, dim3(1), dim3(1024), 0, st, tile_off.p, ntiles);

@@ -6,9 +6,9 @@
 // rows of the unpicked sets, each cut into its maximal runs of bases at depth < k, where depth(b) = the number of
 // picked sets with a row over b.  The rows of one set never overlap, so that is the number of picked ROWS over b.
 //
-//   1. dp_mark_kernel       picked[set] = 1; a set named twice or out of range raises a flag
-//   2. dp_diff_kernel       over the picked rows: d[gs] += 1, d[ge] -= 1 (u32, wrapping; integer atomics, so the
-//                           result does not depend on the order of the rows) -- total + 1 entries, a row may end at total
+//   1. dp_mark_kernel       the pick table: rank[set] = the pick's position, picked[set] = 1; a set named twice or out
+//                           of range raises a flag
+//   2. dp_diff_kernel       over the picked rows: span_mark_diff (spans.h)
 //   3. chip_exclusive_scan_u32 in place: depth[b] = d[b + 1].  A row never leaves its universe, so the depth falls
 //                           to 0 at every universe boundary and one scan serves the whole coordinate space.
 //   4. dp_threshold_kernel  a lane per base: __ballot(depth >= k) is one 64-bit word of the bitmap of bases that need
@@ -16,41 +16,35 @@
 //   5. chip_rows_cut        subtract.hip's count, scan and emit over that bitmap, the picked sets left out whole
 //
 // Everything is integer arithmetic.  Steps 1 to 4 are also host calls of their own (chip_depth_marks, chip_depth_array,
-// chip_depth_bitmap; internal.h): catchhip_rows_prune (prune.hip) starts from the same depth array and bitmap.
-#include "internal.h"
+// chip_depth_bitmap; rows_host.h): catchhip_rows_prune (prune.hip) starts from the same depth array and bitmap,
+// catchhip_rows_pick_gains (gains.hip) from the pick table, catchhip_rows_window_depth (analysis.hip) from step 2.
+#include "rows_host.h"
+#include "spans.h"
 #include "wave.h"
 
 #define DP_WORDS 32   // bitmap words (of 64 bases) per wavefront of dp_threshold_kernel: one atomic per wave and universe
 
-// flag[0] |= 1: an id outside [0, num_sets); |= 2: an id given twice
+// rank / picked: all ones / zero beforehand.  flag[0] |= 1: an id outside [0, num_sets); |= 2: an id given twice
 __global__ void __launch_bounds__(256)
-dp_mark_kernel(const i64 *__restrict__ picks, u32 npicks, i64 num_sets, u32 *__restrict__ picked32,
+dp_mark_kernel(const i64 *__restrict__ picks, u32 npicks, i64 num_sets, u32 *__restrict__ rank, u8 *__restrict__ picked,
                u32 *__restrict__ flag) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= npicks) return;
     const i64 s = picks[i];
     if (s < 0 || s >= num_sets) { atomicOr(&flag[0], 1u); return; }
-    if (atomicExch(&picked32[s], 1u)) atomicOr(&flag[0], 2u);
+    if (atomicCAS(&rank[s], CHIP_NOT_PICKED, i) != CHIP_NOT_PICKED) atomicOr(&flag[0], 2u);
+    picked[s] = 1;
 }
 
-// the marks as bytes (what chip_rows_cut's kernels index per row)
-__global__ void __launch_bounds__(256)
-dp_pack_kernel(const u32 *__restrict__ picked32, u32 num_sets, u8 *__restrict__ picked) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < num_sets) picked[i] = (u8)picked32[i];
-}
-
+// the rows of the picked sets (picked == null: every row) on the difference array d; empty rows leave no mark
 __global__ void __launch_bounds__(256)
 dp_diff_kernel(const i32 *__restrict__ set_id, const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n,
                const u8 *__restrict__ picked, u32 num_sets, u32 *__restrict__ d) {
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
-    const u32 s = (u32)set_id[r];
-    if (picked && (s >= num_sets || !picked[s])) return;     // (picked == null: every row counts)
+    if (picked && ((u32)set_id[r] >= num_sets || !picked[(u32)set_id[r]])) return;
     const u32 a = gs[r], b = ge[r];
-    if (b <= a) return;
-    atomicAdd(&d[a], 1u);
-    atomicAdd(&d[b], 0xffffffffu);
+    if (b > a) span_mark_diff(d, a, b);
 }
 
 // d[b + 1] = depth of base b.  Wavefront v takes the words [v * DP_WORDS, (v + 1) * DP_WORDS) of the bitmap, lowest
@@ -85,8 +79,7 @@ dp_threshold_kernel(const u32 *__restrict__ d, u32 total, u32 k, const u32 *__re
                     acc += (u32)__popcll(rest);
                     break;
                 }
-                const u32 nb = uend > base ? (u32)(uend - base) : 0u;    // bits [0, nb) are universe u's: nb <= 63
-                const u64 m = nb ? ~0ull >> (64 - nb) : 0ull;
+                const u64 m = uend > base ? span_in_word(base, base, uend) : 0ull;    // universe u's bits: 63 at most
                 acc += (u32)__popcll(rest & m);
                 rest &= ~m;
                 if (rest) {                                 // on to the next universe
@@ -101,24 +94,22 @@ dp_threshold_kernel(const u32 *__restrict__ d, u32 total, u32 k, const u32 *__re
     if (lane == 0 && acc && reached) atomicAdd(&reached[u], acc);
 }
 
-// ---- the three steps above as host calls (internal.h), for catchhip_rows_below_depth and catchhip_rows_prune ----------
-// picked[set] = 1 for the sets of picks[0..npicks) (npicks > 0), as bytes; d_picks = the picks on the device
+// ---- the steps above as host calls (rows_host.h) ---------------------------------------------------------------------
 int chip_depth_marks(catchhip_ctx *ctx, const i64 *picks, i64 npicks, i64 num_sets, DevBuf<i64> &d_picks,
-                     DevBuf<u8> &picked, PhaseTimer &tm, const char *who) {
+                     DevBuf<u32> &rank, DevBuf<u8> &picked, PhaseTimer &tm, const char *who) {
     hipStream_t s = ctx->stream;
-    DevBuf<u32> picked32, flag;
+    DevBuf<u32> flag;
     TRY(d_picks.alloc((size_t)npicks));
-    TRY(picked32.alloc((size_t)num_sets));
+    TRY(rank.alloc((size_t)num_sets));
     TRY(picked.alloc((size_t)num_sets));
     TRY(flag.alloc(1));
     HIP_TRY(hipMemcpyAsync(d_picks.p, picks, sizeof(i64) * (size_t)npicks, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(picked32.p, 0, sizeof(u32) * (size_t)num_sets, s));
+    HIP_TRY(hipMemsetAsync(rank.p, 0xff, sizeof(u32) * (size_t)num_sets, s));
+    HIP_TRY(hipMemsetAsync(picked.p, 0, (size_t)num_sets, s));
     HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(u32), s));
     hipLaunchKernelGGL(dp_mark_kernel, dim3((unsigned)div_up(npicks, 256)), dim3(256), 0, s, (const i64 *)d_picks.p,
-                       (u32)npicks, num_sets, picked32.p, flag.p);
-    hipLaunchKernelGGL(dp_pack_kernel, dim3((unsigned)div_up(num_sets, 256)), dim3(256), 0, s,
-                       (const u32 *)picked32.p, (u32)num_sets, picked.p);
-    tm.launch(2);
+                       (u32)npicks, num_sets, rank.p, picked.p, flag.p);
+    tm.launch(1);
     HIP_TRY(hipGetLastError());
     u32 h_flag = 0;
     TRY(read_count(ctx, flag.p, &h_flag));                   // (also: the pageable picks[] has been read)
@@ -129,6 +120,14 @@ int chip_depth_marks(catchhip_ctx *ctx, const i64 *picks, i64 npicks, i64 num_se
     return 0;
 }
 
+// the one difference kernel over the rows of R (picked null: all of them); returns its launches, 0 for an empty table
+i64 chip_depth_diff(catchhip_ctx *ctx, const catchhip_rows *R, const u8 *picked, u32 num_sets, u32 *d) {
+    if (!R->n) return 0;
+    hipLaunchKernelGGL(dp_diff_kernel, dim3((unsigned)div_up(R->n, 256)), dim3(256), 0, ctx->stream,
+                       (const i32 *)R->set_id.p, (const u32 *)R->gs.p, (const u32 *)R->ge.p, (u32)R->n, picked, num_sets, d);
+    return 1;
+}
+
 // d[b + 1] = the picked rows of R0 over base b, plus the rows of F (may be null: none) over it; total + 2 entries
 int chip_depth_array(catchhip_ctx *ctx, const catchhip_rows *R0, const u8 *picked, u32 num_sets, const catchhip_rows *F,
                      DevBuf<u32> &d, DevBuf<u32> &tmp, PhaseTimer &tm) {
@@ -137,18 +136,8 @@ int chip_depth_array(catchhip_ctx *ctx, const catchhip_rows *R0, const u8 *picke
     TRY(d.alloc(total + 2));
     TRY(chip_exclusive_scan_reserve(tmp, (i64)total + 1));
     HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(u32) * (total + 2), s));
-    if (R0->n) {
-        hipLaunchKernelGGL(dp_diff_kernel, dim3((unsigned)div_up(R0->n, 256)), dim3(256), 0, s,
-                           (const i32 *)R0->set_id.p, (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, (u32)R0->n, picked,
-                           num_sets, d.p);
-        tm.launch(1);
-    }
-    if (F && F->n) {
-        hipLaunchKernelGGL(dp_diff_kernel, dim3((unsigned)div_up(F->n, 256)), dim3(256), 0, s,
-                           (const i32 *)F->set_id.p, (const u32 *)F->gs.p, (const u32 *)F->ge.p, (u32)F->n,
-                           (const u8 *)nullptr, 0u, d.p);
-        tm.launch(1);
-    }
+    tm.launch(chip_depth_diff(ctx, R0, picked, num_sets, d.p));
+    if (F) tm.launch(chip_depth_diff(ctx, F, nullptr, 0u, d.p));
     TRY(chip_exclusive_scan_u32(ctx, d.p, d.p, (i64)total + 1, tmp));
     tm.launch(1);
     HIP_TRY(hipGetLastError());
@@ -167,21 +156,14 @@ int chip_depth_bitmap(catchhip_ctx *ctx, const u32 *d, u64 total, u32 k, const u
     return 0;
 }
 
-// the refusals catchhip_rows_below_depth and catchhip_rows_prune share (R0 passed ARG_CHECK)
+// (R0 passed ARG_CHECK)
 int chip_depth_check(const catchhip_rows *R0, i64 num_sets, i64 npicks, i32 depth, const char *who) {
     if (depth < 1) {
         chip_set_error("%s: depth %d; the smallest depth is 1", who, (int)depth);
         return CATCHHIP_EINVAL;
     }
-    TRY(chip_rows_cut_check(R0, who, "the rows"));
-    if (R0->total >= ((i64)1 << 32) - 1) {
-        chip_set_error("%s: more than 2^32 - 2 target bases", who);
-        return CATCHHIP_EINVAL;
-    }
-    if (R0->n >= ((i64)1 << 31)) {
-        chip_set_error("%s: too many rows", who);
-        return CATCHHIP_EINVAL;
-    }
+    TRY(chip_rows_form_check(R0, who, "the rows"));
+    TRY(chip_rows_limits_check(who, R0->total, R0->n));
     if (npicks > num_sets) {
         chip_set_error("%s: %lld picks of %lld sets (an id is repeated or out of range)", who,
                        (long long)npicks, (long long)num_sets);
@@ -203,36 +185,30 @@ extern "C" int catchhip_rows_below_depth(catchhip_ctx *ctx, const catchhip_rows 
     PoolScope pool_scope(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    std::unique_ptr<catchhip_rows> R;
-    TRY(chip_rows_new(ctx, R0->total, ng, R0->h_genome_off, R0->genome_off.p, false, R));
-    R->ext = -1;
-    PhaseTimer tm(ctx, PHASE_ROWS);
+    DerivedRows D(ctx, R0);
+    TRY(D.err);
+    catchhip_rows *R = D.R.get();
     if (npicks == 0) {                                       // depth 0 everywhere: a copy, nothing reached
-        if (R0->n) TRY(chip_rows_copy(ctx, R0, R.get()));
-        else HIP_TRY(hipStreamSynchronize(s));               // (genome_off is on its way)
-        tm.finish();
-        if (nrows) *nrows = R->n;
-        *out = R.release();
-        return 0;
+        TRY(D.copy_of(R0));
+        return D.finish(out, nrows);
     }
-    // the picked sets
+    // the picked sets (their ranks are not needed here)
     DevBuf<i64> d_picks;
+    DevBuf<u32> rank;
     DevBuf<u8> picked;
-    TRY(chip_depth_marks(ctx, picks, npicks, num_sets, d_picks, picked, tm, "rows_below_depth"));
+    TRY(chip_depth_marks(ctx, picks, npicks, num_sets, d_picks, rank, picked, D.tm, "rows_below_depth"));
     // depth per base -> the bitmap of bases at depth >= `depth`, and their number per universe
     const u64 total = (u64)R0->total;
-    const size_t nwords = (size_t)(total / 64 + 2) + 8;
     DevBuf<unsigned long long> bm, d_reached;
-    TRY(bm.alloc(nwords));
+    TRY(chip_cut_bitmap(ctx, R0->total, true, bm));
     TRY(d_reached.alloc((size_t)ng));
-    HIP_TRY(hipMemsetAsync(bm.p, 0, sizeof(unsigned long long) * nwords, s));
     HIP_TRY(hipMemsetAsync(d_reached.p, 0, sizeof(unsigned long long) * (size_t)(ng ? ng : 1), s));
     if (R0->n && total && ng > 0) {
         DevBuf<u32> d, tmp;
-        TRY(chip_depth_array(ctx, R0, (const u8 *)picked.p, (u32)num_sets, nullptr, d, tmp, tm));
+        TRY(chip_depth_array(ctx, R0, (const u8 *)picked.p, (u32)num_sets, nullptr, d, tmp, D.tm));
         TRY(chip_depth_bitmap(ctx, (const u32 *)d.p, total, (u32)depth, (const u32 *)R0->genome_off.p, (u32)ng, bm.p,
-                              d_reached.p, tm));
-        TRY(chip_rows_cut(ctx, R0, (const unsigned long long *)bm.p, (const u8 *)picked.p, (u32)num_sets, R.get(), tm,
+                              d_reached.p, D.tm));
+        TRY(chip_rows_cut(ctx, R0, (const unsigned long long *)bm.p, (const u8 *)picked.p, (u32)num_sets, R, D.tm,
                           "rows_below_depth"));
     }
     if (R->n == 0 && R0->gain0_n) {                          // nothing left of any set: gain0 is carried all the same
@@ -240,19 +216,7 @@ extern "C" int catchhip_rows_below_depth(catchhip_ctx *ctx, const catchhip_rows 
         HIP_TRY(hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)R0->gain0_n, s));
         R->gain0_n = R0->gain0_n;
     }
-    tm.stop();
-    if (reached && ng > 0) {
-        TRY(chip_pinned_reserve(ctx, sizeof(unsigned long long) * (size_t)ng));
-        HIP_TRY(hipMemcpyAsync(ctx->h_big, d_reached.p, sizeof(unsigned long long) * (size_t)ng,
-                               hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        const unsigned long long *h = (const unsigned long long *)ctx->h_big;
-        for (i32 u = 0; u < ng; ++u) reached[u] = (i64)h[u];
-    } else {
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    tm.finish();
-    if (nrows) *nrows = R->n;
-    *out = R.release();
-    return 0;
+    D.tm.stop();
+    TRY(chip_fetch_counters(ctx, d_reached.p, (size_t)(ng > 0 ? ng : 0), reached));
+    return D.finish(out, nrows);
 }

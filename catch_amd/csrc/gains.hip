@@ -7,8 +7,8 @@
 // the bases of u with first(b) < k; per checkpoint the sum over the universes and the universe with the smallest
 // cov_u / denom[u] are reported.
 //
-//   1. chip_depth_marks (depth.hip)  the picks on the device; a pick out of range or given twice is refused
-//      gn_rank_kernel                rank[set] = position of the pick of that set (GN_NONE: not picked)
+//   1. chip_depth_marks (depth.hip)  the pick table: rank[set] = position of the pick of that set (GN_NONE: not
+//                                    picked); a pick out of range or given twice is refused
 //   2. gn_first_kernel               first[] = u32 per base, all ones beforehand.  A wavefront per row of a picked
 //                                    set, its lanes on consecutive bases: every wave instruction reads and (where the
 //                                    row's rank is lower) atomicMin's a contiguous 256 bytes
@@ -25,17 +25,10 @@
 // the launch geometry nor on the order of the atomics.  Scratch: 4 bytes per target base (first[]) plus 4 bytes x
 // checkpoints x universes (the table).  Tables of up to 2^31 - 1 rows: the two row passes compute the row of a
 // wavefront in 64 bits.
-#include "internal.h"
+#include "rows_host.h"
 #include "wave.h"
 
-#define GN_NONE 0xffffffffu
-
-// The picks have passed dp_mark_kernel: in range, none twice.
-__global__ void __launch_bounds__(256)
-gn_rank_kernel(const i64 *__restrict__ picks, u32 npicks, u32 *__restrict__ rank) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < npicks) rank[(u32)picks[i]] = i;
-}
+#define GN_NONE CHIP_NOT_PICKED
 
 // One row's bases by one wavefront: *rk = the rank of its set (GN_NONE: not picked, or a set id out of range),
 // [*a, *b) = its bases, cut at `total`
@@ -195,14 +188,13 @@ extern "C" int catchhip_rows_pick_gains(catchhip_ctx *ctx, const catchhip_rows *
     const u32 np = (u32)npicks, ns = (u32)num_sets, n0 = (u32)R0->n, nc = (u32)ncheck, ngu = (u32)ng;
     const u32 total = (u32)R0->total;
     DevBuf<i64> d_picks;
+    DevBuf<u32> rank;
     DevBuf<u8> picked;
-    TRY(chip_depth_marks(ctx, picks, npicks, num_sets, d_picks, picked, tm, "rows_pick_gains"));
-    DevBuf<u32> rank, first, d_gains, ck_off, table, d_denom, d_cov0;
+    TRY(chip_depth_marks(ctx, picks, npicks, num_sets, d_picks, rank, picked, tm, "rows_pick_gains"));
+    DevBuf<u32> first, d_gains, ck_off, table, d_denom, d_cov0;
     DevBuf<u64> d_out;
-    TRY(rank.alloc(ns));
     TRY(first.alloc(total));
     TRY(d_gains.alloc(np));
-    HIP_TRY(hipMemsetAsync(rank.p, 0xff, sizeof(u32) * (size_t)ns, s));
     HIP_TRY(hipMemsetAsync(first.p, 0xff, sizeof(u32) * (size_t)total, s));
     HIP_TRY(hipMemsetAsync(d_gains.p, 0, sizeof(u32) * (size_t)np, s));
     const size_t ntab = (size_t)nc * ngu;
@@ -230,8 +222,6 @@ extern "C" int catchhip_rows_pick_gains(catchhip_ctx *ctx, const catchhip_rows *
         }
     }
     const dim3 blk(256);
-    hipLaunchKernelGGL(gn_rank_kernel, dim3((unsigned)div_up(np, 256)), blk, 0, s, (const i64 *)d_picks.p, np, rank.p);
-    tm.launch(1);
     if (n0 && total) {
         const dim3 per_row((unsigned)div_up(n0, 256 / WAVE));
         hipLaunchKernelGGL(gn_first_kernel, per_row, blk, 0, s, (const i32 *)R0->set_id.p, (const u32 *)R0->gs.p,

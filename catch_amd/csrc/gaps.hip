@@ -32,7 +32,8 @@
 // arrays.  Scratch: 4 (total + 2) bytes of depth, given back before step 3; three bitmaps of total / 8 bytes (cov,
 // bnd, acgt); 8 bytes per 64 bases of counts; 20 bytes per region before the filters (rs, re, unambiguous count,
 // flag, place); the output table has 16 bytes per reported region.
-#include "internal.h"
+#include "rows_host.h"
+#include "spans.h"
 #include "wave.h"
 
 #define GP_WORDS 32   // bitmap words per wavefront of gp_acgt_kernel
@@ -65,9 +66,7 @@ gp_acgt_kernel(const u8 *__restrict__ bytes, u32 total, u32 nw, ull *__restrict_
 
 // the uncovered bases of word w < nw (cov: bit = depth >= min_depth; the bits from `total` on are nobody's)
 __device__ __forceinline__ u64 gp_uncovered(const ull *__restrict__ cov, u32 w, u32 nw, u32 total) {
-    u64 u = ~cov[w];
-    if (w == nw - 1 && (total & 63u)) u &= ~0ull >> (64 - (total & 63u));
-    return u;
+    return ~cov[w] & span_in_word((u64)w << 6, 0, total);
 }
 
 // the marks of word w < nw: bit b of *S = a region starts at base b, bit b of *E = a region's last base is b
@@ -110,14 +109,6 @@ gp_emit_kernel(const ull *__restrict__ cov, const ull *__restrict__ bnd, u32 nw,
     for (u32 o = ce[w]; E && o < nreg; ++o, E &= E - 1) re[o] = base + (u32)__ffsll((ull)E);
 }
 
-// the bits of [a, b) that lie in word w, w0 = a >> 6 <= w <= w1 = (b - 1) >> 6
-__device__ __forceinline__ u32 gp_popc(const ull *__restrict__ bm, u32 w, u32 w0, u32 w1, u32 a, u32 b) {
-    u64 m = ~0ull;
-    if (w == w0) m &= ~0ull << (a & 63u);
-    if (w == w1) m &= ~0ull >> (63u - ((b - 1) & 63u));
-    return (u32)__popcll(bm[w] & m);
-}
-
 // ua[i] = the bases of region i whose bit in acgt is set (acgt null: all of them); flag[i] = it is reported,
 // flag[nreg] = 0.  Every lane of a wavefront stays to the end: the long regions are counted by all 64.
 __global__ void __launch_bounds__(256)
@@ -126,22 +117,17 @@ gp_measure_kernel(const u32 *__restrict__ rs, const u32 *__restrict__ re, u32 nr
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     const u32 lane = threadIdx.x & 63u;
     const bool have = i < (i64)nreg;
-    const u32 a = have ? rs[i] : 0u, b = have ? re[i] : 0u;
+    const u32 a = have ? rs[i] : 0u, b = have ? re[i] : 1u;  // (an idle lane: one base, so that it has a span)
     const u32 len = b - a;                                   // >= 1 for a region
     u32 cnt = len;
     if (acgt) {
-        const u32 w0 = a >> 6, w1 = have ? (b - 1) >> 6 : 0u;
-        const bool is_long = have && w1 - w0 >= GP_SHORT;
-        if (have && !is_long) {
-            cnt = 0;
-            for (u32 w = w0; w <= w1; ++w) cnt += gp_popc(acgt, w, w0, w1, a, b);
-        }
+        const bool is_long = have && span_of(a, b).nw > GP_SHORT;
+        if (have && !is_long) cnt = span_popc(acgt, a, b);
         for (ull rest = __ballot(is_long); rest; rest &= rest - 1) {
             const int src = __ffsll(rest) - 1;
-            const u32 la = (u32)__shfl((int)a, src, WAVE), lb = (u32)__shfl((int)b, src, WAVE);
-            const u32 lw0 = la >> 6, lw1 = (lb - 1) >> 6;
+            const Span sp = span_of((u32)__shfl((int)a, src, WAVE), (u32)__shfl((int)b, src, WAVE));
             u32 part = 0;
-            for (u64 w = (u64)lw0 + lane; w <= lw1; w += WAVE) part += gp_popc(acgt, (u32)w, lw0, lw1, la, lb);
+            for (u32 j = lane; j < sp.nw; j += WAVE) part += span_popc_word(acgt, sp, j);
             part = wave_sum_all(part);
             if ((int)lane == src) cnt = part;
         }
@@ -208,14 +194,7 @@ static int gp_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R0, const c
     ARG_CHECK(R0->ctx == ctx && (!T || T->ctx == ctx) && (!mask || mask->ctx == ctx));
     *out = nullptr;
     if (nregions) *nregions = 0;
-    if (R0->deferred) {
-        chip_set_error("rows_uncovered: the rows are deferred rows (a fused scan that was never synchronised)");
-        return CATCHHIP_EINVAL;
-    }
-    if (R0->rows4.p) {
-        chip_set_error("rows_uncovered: the rows are in the direct form of the fused filter, not a row table");
-        return CATCHHIP_EINVAL;
-    }
+    TRY(chip_rows_form_check(R0, "rows_uncovered", "the rows", true));    // (grouped rows are fine)
     if (min_depth < 1 || min_length < 1 || min_unambig < 0) {
         chip_set_error("rows_uncovered: min_depth %d, min_length %lld, min_unambig %lld; the smallest are 1, 1 and 0",
                        (int)min_depth, (long long)min_length, (long long)min_unambig);
@@ -223,33 +202,20 @@ static int gp_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R0, const c
     }
     ARG_CHECK(R0->total >= 0 && R0->total < ((i64)1 << 32) - 4096 && R0->n >= 0 && R0->n < ((i64)1 << 31));
     const i32 ng = R0->ngenomes;
-    if (T && (T->nseq != (i64)T->ngenomes || T->ngenomes != ng || T->total != R0->total ||
-              T->h_genome_off != R0->h_genome_off)) {
-        chip_set_error("rows_uncovered: the targets (%lld bases, %lld sequences in %d genomes) are not one genome per "
-                       "sequence over the coordinate space of the rows (%lld bases in %d universes)",
-                       (long long)T->total, (long long)T->nseq, (int)T->ngenomes, (long long)R0->total, (int)ng);
-        return CATCHHIP_EINVAL;
-    }
-    if (mask && (mask->total != R0->total || mask->ngenomes != ng || mask->h_genome_off != R0->h_genome_off)) {
-        chip_set_error("rows_uncovered: the mask is not over the coordinate space of the rows "
-                       "(%lld bases in %d universes against %lld in %d)",
-                       (long long)mask->total, (int)mask->ngenomes, (long long)R0->total, (int)ng);
-        return CATCHHIP_EINVAL;
-    }
+    if (T) TRY(chip_targets_space_check(T, R0, "rows_uncovered"));
+    if (mask) TRY(chip_space_check(mask, R0, "rows_uncovered", "the mask is not over the coordinate space of the rows"));
     if (per_universe) for (i64 k = 0; k < 3 * (i64)ng; ++k) per_universe[k] = 0;
     PoolScope pool_scope(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    std::unique_ptr<catchhip_rows> R;
-    TRY(chip_rows_new(ctx, R0->total, ng, R0->h_genome_off, R0->genome_off.p, false, R));
-    R->ext = -1;
-    PhaseTimer tm(ctx, PHASE_ROWS);
+    DerivedRows D(ctx, R0);
+    TRY(D.err);
+    catchhip_rows *R = D.R.get();
+    PhaseTimer &tm = D.tm;
     const u64 total = (u64)R0->total;
     if (total == 0 || ng <= 0) {                             // no bases: no regions
-        HIP_TRY(hipStreamSynchronize(s));                    // (genome_off is on its way)
-        tm.finish();
-        *out = R.release();
-        return 0;
+        TRY(D.copy_of(nullptr));
+        return D.finish(out, nregions);
     }
     const u32 nw = (u32)((total + 63) >> 6), ngu = (u32)ng;
     const dim3 blk(256);
@@ -315,7 +281,7 @@ static int gp_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R0, const c
             return CATCHHIP_EINVAL;
         }
         if (nkept) {
-            TRY(chip_rows_alloc_soa(R.get(), nkept));
+            TRY(chip_rows_alloc_soa(R, nkept));
             hipLaunchKernelGGL(gp_compact_kernel, per_region, blk, 0, s, (const u32 *)rs.p, (const u32 *)re.p,
                                (const u32 *)ua.p, (const u32 *)flag.p, (const u32 *)place.p, nreg,
                                (const u32 *)R0->genome_off.p, ngu, R->set_id.p, R->univ.p, R->gs.p, R->ge.p, pu.p);
@@ -324,22 +290,16 @@ static int gp_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R0, const c
         }
     }
     tm.stop();
-    const size_t pu_bytes = sizeof(ull) * 3 * (size_t)ngu;
-    TRY(chip_pinned_reserve(ctx, pu_bytes));
-    HIP_TRY(hipMemcpyAsync(ctx->h_big, pu.p, pu_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const ull *h = (const ull *)ctx->h_big;
-    u64 longest = 0;
-    for (size_t k = 0; k < 3 * (size_t)ngu; ++k) {
-        if (per_universe) per_universe[k] = (i64)h[k];
-        if (k % 3 == 2 && h[k] > longest) longest = h[k];
+    std::vector<i64> h(3 * (size_t)ngu);
+    TRY(chip_fetch_counters(ctx, pu.p, h.size(), h.data()));
+    i64 longest = 0;
+    for (size_t k = 0; k < h.size(); ++k) {
+        if (per_universe) per_universe[k] = h[k];
+        if (k % 3 == 2) longest = std::max(longest, h[k]);
     }
-    tm.finish();
     R->n = (i64)nkept;
     R->lmax = (u32)longest;
-    if (nregions) *nregions = R->n;
-    *out = R.release();
-    return 0;
+    return D.finish(out, nregions);
 }
 
 extern "C" int catchhip_rows_uncovered(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_targets *T,

@@ -20,7 +20,7 @@
 #include <algorithm>
 #include <chrono>
 
-#include "internal.h"
+#include "rows_host.h"
 #include "wave.h"
 
 #define GRID_NEVER 0xffffffffu

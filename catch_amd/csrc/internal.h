@@ -319,30 +319,6 @@ struct catchhip_rows {
     const i32 *bucket_set = nullptr;   // (the probes' array: they outlive the filter call the rows live in)
 };
 
-// the four SoA arrays of n rows
-static inline int chip_rows_alloc_soa(catchhip_rows *R, size_t n) {
-    TRY(R->set_id.alloc(n));
-    TRY(R->univ.alloc(n));
-    TRY(R->gs.alloc(n));
-    TRY(R->ge.alloc(n));
-    return 0;
-}
-// an empty rows object over a coordinate space that is on the device already (a targets object's, or other rows'):
-// the host facts, and genome_off copied on the context's stream.  Call under the caller's PoolScope, device set.
-static inline int chip_rows_new(catchhip_ctx *ctx, i64 total, i32 ngenomes, const std::vector<i64> &h_genome_off,
-                                const u32 *d_genome_off, bool grouped, std::unique_ptr<catchhip_rows> &R) {
-    R.reset(new catchhip_rows());
-    R->ctx = ctx;
-    R->total = total;
-    R->ngenomes = ngenomes;
-    R->h_genome_off = h_genome_off;
-    R->grouped = grouped;
-    TRY(R->genome_off.alloc((size_t)ngenomes + 1));
-    HIP_TRY(hipMemcpyAsync(R->genome_off.p, d_genome_off, sizeof(u32) * ((size_t)ngenomes + 1), hipMemcpyDeviceToDevice,
-                           ctx->stream));
-    return 0;
-}
-
 // unique candidate probes of a targets object (candidates.hip; the pre-filters of prefilter.hip edit the list)
 struct catchhip_candidates {
     catchhip_ctx *ctx = nullptr;
@@ -457,45 +433,16 @@ struct PhaseTimer {
     }
 };
 
-// ---- rows cut by a bitmap of bases (subtract.hip; catchhip_rows_subtract and catchhip_rows_below_depth) --------
-// CATCHHIP_EINVAL (message "<who>: <which> are ...") for deferred, direct or grouped rows
-int chip_rows_cut_check(const catchhip_rows *R, const char *who, const char *which);
-// a copy of the SoA table R0 (with its gain0 and lmax) into R, made by chip_rows_new over the same coordinate space
-int chip_rows_copy(catchhip_ctx *ctx, const catchhip_rows *R0, catchhip_rows *R);
-// every row of R0 (non-empty, fewer than 2^31 rows) cut into its maximal runs of bases whose bit in bm is clear
-// (total / 64 + 1 words at least); the rows of the sets with skip[set] != 0 (set < nskip; skip may be null) are left
-// out whole.  Order and normal form of R0 are kept; R gets n, lmax and, when R0 has it, gain0.  tm: the caller's
-// running timer (its launches are counted and its stop event recorded here).
-int chip_rows_cut(catchhip_ctx *ctx, const catchhip_rows *R0, const unsigned long long *bm, const u8 *skip, u32 nskip,
-                  catchhip_rows *R, PhaseTimer &tm, const char *who);
-
 // ---- the wanted bases of a coordinate space (mask.hip; catchhip_rows_restrict, catchhip_rows_uncovered_within) ---
 struct catchhip_basemask {
     catchhip_ctx *ctx = nullptr;
     i64 total = 0;       // size of the coordinate space (universes concatenated, as catchhip_rows_from_host lays them out)
     i32 ngenomes = 0;
     std::vector<i64> h_genome_off;
-    // bit b set = base b is not wanted; total / 64 + 2 + 8 words (subtract.hip's sizing: chip_rows_cut reads it as it
+    // bit b set = base b is not wanted; chip_cut_bitmap_words(total) words (rows_host.h: chip_rows_cut reads it as it
     // reads its own), the bits at and beyond `total` set
     DevBuf<unsigned long long> unwanted;
 };
-
-// ---- depth per base from a pick list (depth.hip; catchhip_rows_below_depth and catchhip_rows_prune) -------------
-// the refusals the two share: depth < 1, rows chip_rows_cut_check refuses, 2^32 - 1 bases and more, 2^31 rows and
-// more, more picks than sets
-int chip_depth_check(const catchhip_rows *R0, i64 num_sets, i64 npicks, i32 depth, const char *who);
-// picked[set] = 1 (bytes, num_sets of them) for the sets of the host array picks[0..npicks), npicks > 0; d_picks = the
-// picks on the device.  CATCHHIP_EINVAL ("<who>: a pick ...") for an id outside [0, num_sets) or given twice.
-int chip_depth_marks(catchhip_ctx *ctx, const i64 *picks, i64 npicks, i64 num_sets, DevBuf<i64> &d_picks,
-                     DevBuf<u8> &picked, PhaseTimer &tm, const char *who);
-// d[b + 1] = depth of base b = the rows of R0's picked sets over it, plus the rows of F over it (F may be null;
-// otherwise any table over R0's coordinate space, every row counts).  d gets total + 2 entries; tmp = the scan's scratch.
-int chip_depth_array(catchhip_ctx *ctx, const catchhip_rows *R0, const u8 *picked, u32 num_sets, const catchhip_rows *F,
-                     DevBuf<u32> &d, DevBuf<u32> &tmp, PhaseTimer &tm);
-// bit b of bm = d[b + 1] >= k (bm: total / 64 + 1 words at least, zeroed by the caller); reached[u] (device, zeroed
-// by the caller; may be null) += the bits of universe u
-int chip_depth_bitmap(catchhip_ctx *ctx, const u32 *d, u64 total, u32 k, const u32 *genome_off, u32 ng,
-                      unsigned long long *bm, unsigned long long *reached, PhaseTimer &tm);
 
 // ---- device primitives (primitives.hip) ---------------------------------
 // exclusive prefix sum of n u32 values (in place allowed: out may equal in);

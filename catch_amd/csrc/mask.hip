@@ -21,19 +21,11 @@
 // the bitmap: the interval boundaries (8 bytes per interval) and 12 bytes per universe.
 #include <algorithm>
 
-#include "internal.h"
+#include "rows_host.h"
+#include "spans.h"
 #include "wave.h"
 
 typedef unsigned long long ull;
-
-// the bits of word `base` .. base + 63 that lie in [a, b) (a < b, the two overlap)
-__device__ __forceinline__ u64 bm_span(u64 base, u64 a, u64 b) {
-    const u32 lo = a > base ? (u32)(a - base) : 0u;          // < 64
-    const u64 hi = b - base;                                 // >= 1
-    u64 m = ~0ull << lo;
-    if (hi < 64) m &= ~0ull >> (64 - (u32)hi);
-    return m;
-}
 
 // gs / ge: the n intervals in global coordinates, ascending, each start greater than the end before it; bm: nwords
 // words; wanted[ng]: zeroed by the caller.  Every lane of a wavefront stays to the end (the reductions need all 64).
@@ -53,7 +45,7 @@ bm_build_kernel(const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n, u
         for (u32 i = lo; i < n; ++i) {
             const u64 a = gs[i];
             if (a >= base + 64) break;
-            want |= bm_span(base, a, (u64)ge[i]);
+            want |= span_in_word(base, a, (u64)ge[i]);
         }
     }
     if (w < nwords) bm[w] = ~want;
@@ -72,7 +64,7 @@ bm_build_kernel(const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n, u
         const u64 a = genome_off[u], b = genome_off[u + 1];
         if (a >= wend) break;
         u64 m = 0;
-        if (b > a && a < base + 64 && b > base) m = bm_span(base, a, b);
+        if (b > a && a < base + 64 && b > base) m = span_in_word(base, a, b);
         const ull t = wave_sum((ull)__popcll(want & m));
         if (lane == 0 && t) atomicAdd(&wanted[u], t);
     }
@@ -121,11 +113,11 @@ extern "C" int catchhip_basemask_create(catchhip_ctx *ctx, const i64 *genome_len
     PoolScope pool_scope(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const size_t nwords = (size_t)(M->total / 64 + 2) + 8;
+    const size_t nwords = chip_cut_bitmap_words(M->total);
     const size_t ngu = (size_t)ngenomes;
     DevBuf<u32> d_gs, d_ge, d_go;
     DevBuf<ull> d_wanted;
-    TRY(M->unwanted.alloc(nwords));
+    TRY(chip_cut_bitmap(ctx, M->total, false, M->unwanted));  // (the kernel stores every word)
     TRY(d_gs.alloc((size_t)n));
     TRY(d_ge.alloc((size_t)n));
     TRY(d_go.alloc(ngu + 1));
@@ -143,16 +135,8 @@ extern "C" int catchhip_basemask_create(catchhip_ctx *ctx, const i64 *genome_len
     tm.launch(1);
     HIP_TRY(hipGetLastError());
     tm.stop();
-    if (ngu) {
-        TRY(chip_pinned_reserve(ctx, sizeof(ull) * ngu));
-        HIP_TRY(hipMemcpyAsync(ctx->h_big, d_wanted.p, sizeof(ull) * ngu, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));                        // (also: the pageable gs / ge / go have been read)
+    TRY(chip_fetch_counters(ctx, d_wanted.p, ngu, wanted_per_universe));    // (also: the pageable gs / ge / go have been read)
     tm.finish();
-    if (wanted_per_universe) {
-        const ull *h = (const ull *)ctx->h_big;
-        for (size_t u = 0; u < ngu; ++u) wanted_per_universe[u] = (i64)h[u];
-    }
     *out = M.release();
     return 0;
 }
@@ -181,32 +165,14 @@ extern "C" int catchhip_rows_restrict(catchhip_ctx *ctx, const catchhip_rows *R0
     ARG_CHECK(R0->ctx == ctx && mask->ctx == ctx);
     *out = nullptr;
     if (nrows) *nrows = 0;
-    TRY(chip_rows_cut_check(R0, "rows_restrict", "the rows"));
-    if (R0->total != mask->total || R0->ngenomes != mask->ngenomes || R0->h_genome_off != mask->h_genome_off) {
-        chip_set_error("rows_restrict: the mask is not over the coordinate space of the rows "
-                       "(%lld bases in %d universes against %lld in %d)",
-                       (long long)mask->total, (int)mask->ngenomes, (long long)R0->total, (int)R0->ngenomes);
-        return CATCHHIP_EINVAL;
-    }
-    if (R0->total >= ((i64)1 << 32) - 1) {
-        chip_set_error("rows_restrict: more than 2^32 - 2 target bases");
-        return CATCHHIP_EINVAL;
-    }
-    if (R0->n >= ((i64)1 << 31)) {
-        chip_set_error("rows_restrict: too many rows");
-        return CATCHHIP_EINVAL;
-    }
+    TRY(chip_rows_form_check(R0, "rows_restrict", "the rows"));
+    TRY(chip_space_check(mask, R0, "rows_restrict", "the mask is not over the coordinate space of the rows"));
+    TRY(chip_rows_limits_check("rows_restrict", R0->total, R0->n));
     PoolScope pool_scope(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    std::unique_ptr<catchhip_rows> R;
-    TRY(chip_rows_new(ctx, R0->total, R0->ngenomes, R0->h_genome_off, R0->genome_off.p, false, R));
-    R->ext = -1;
-    PhaseTimer tm(ctx, PHASE_ROWS);
-    if (R0->n) TRY(chip_rows_cut(ctx, R0, (const ull *)mask->unwanted.p, nullptr, 0, R.get(), tm, "rows_restrict"));
-    HIP_TRY(hipStreamSynchronize(s));                        // (genome_off is on its way)
-    tm.finish();
-    if (nrows) *nrows = R->n;
-    *out = R.release();
-    return 0;
+    DerivedRows D(ctx, R0);
+    TRY(D.err);
+    if (R0->n) TRY(chip_rows_cut(ctx, R0, (const ull *)mask->unwanted.p, nullptr, 0, D.R.get(), D.tm, "rows_restrict"));
+    else TRY(D.copy_of(nullptr));
+    return D.finish(out, nrows);
 }

@@ -3,6 +3,7 @@
 // value) pairs.  Hand-written for gfx950: 64-lane wavefronts, wave-level
 // multi-split through __ballot, LDS for the per-workgroup digit tables.
 #include "internal.h"
+#include "spans.h"
 #include "wave.h"
 
 // ------------------------------------------------------------------------
@@ -356,5 +357,67 @@ extern "C" int catchhip_selftest_find_segment(catchhip_ctx *ctx, const u32 *off,
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(u32) * (size_t)nx, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// every helper of spans.h on one interval [a[i], b[i]) per thread, over the caller's bitmap: out32[k * n + i] = first
+// word, words, span_popc, span_all_set; out64[k * n + i] = m0, m1, span_in_word for word `view` (0: they do not overlap)
+__global__ void __launch_bounds__(256)
+selftest_spans_kernel(const unsigned long long *__restrict__ bm, const u32 *__restrict__ a, const u32 *__restrict__ b, u32 n,
+                      u32 view, u32 *__restrict__ out32, u64 *__restrict__ out64) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const Span sp = span_of(a[i], b[i]);
+    const u64 base = (u64)view << 6;
+    const u32 r[4] = {sp.w0, sp.nw, span_popc(bm, a[i], b[i]), span_all_set(bm, a[i], b[i]) ? 1u : 0u};
+    for (int k = 0; k < 4; ++k) out32[(size_t)k * n + i] = r[k];
+    out64[i] = sp.m0;
+    out64[(size_t)n + i] = sp.m1;
+    out64[2 * (size_t)n + i] = (a[i] < base + 64 && b[i] > base) ? span_in_word(base, a[i], b[i]) : 0ull;
+}
+// all intervals into one zeroed bitmap and one zeroed difference array
+__global__ void __launch_bounds__(256)
+selftest_spans_paint_kernel(const u32 *__restrict__ a, const u32 *__restrict__ b, u32 n, unsigned long long *__restrict__ bm,
+                            u32 *__restrict__ d) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    span_paint(bm, a[i], b[i]);
+    span_mark_diff(d, a[i], b[i]);
+}
+
+extern "C" int catchhip_selftest_spans(catchhip_ctx *ctx, const u64 *bm, i64 nwords, const u32 *a, const u32 *b, i64 n,
+                                       u32 view, u32 *out32, u64 *out64, u64 *painted, u32 *diff) {
+    ARG_CHECK(ctx && bm && a && b && out32 && out64 && painted && diff);
+    ARG_CHECK(nwords >= 1 && nwords <= ((i64)1 << 20) && n >= 1 && n <= ((i64)1 << 20) && (i64)view < nwords);
+    for (i64 i = 0; i < n; ++i) ARG_CHECK(a[i] < b[i] && (i64)b[i] <= 64 * nwords);      // (the kernels index by them)
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t nw = (size_t)nwords, nd = 64 * nw + 1, ni = (size_t)n;
+    DevBuf<unsigned long long> d_bm, d_painted;
+    DevBuf<u32> d_ab, d_out32, d_diff;                       // (a, then b)
+    DevBuf<u64> d_out64;
+    TRY(d_bm.alloc(nw));
+    TRY(d_painted.alloc(nw));
+    TRY(d_ab.alloc(2 * ni));
+    TRY(d_out32.alloc(4 * ni));
+    TRY(d_out64.alloc(3 * ni));
+    TRY(d_diff.alloc(nd));
+    HIP_TRY(hipMemcpyAsync(d_bm.p, bm, sizeof(u64) * nw, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_ab.p, a, sizeof(u32) * ni, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_ab.p + ni, b, sizeof(u32) * ni, hipMemcpyHostToDevice, s));
+    const u32 *d_a = d_ab.p, *d_b = d_ab.p + ni;
+    HIP_TRY(hipMemsetAsync(d_painted.p, 0, sizeof(u64) * nw, s));
+    HIP_TRY(hipMemsetAsync(d_diff.p, 0, sizeof(u32) * nd, s));
+    const dim3 grid((unsigned)div_up(n, 256)), blk(256);
+    hipLaunchKernelGGL(selftest_spans_kernel, grid, blk, 0, s, (const unsigned long long *)d_bm.p, d_a, d_b, (u32)n, view,
+                       d_out32.p, d_out64.p);
+    hipLaunchKernelGGL(selftest_spans_paint_kernel, grid, blk, 0, s, d_a, d_b, (u32)n, d_painted.p, d_diff.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out32, d_out32.p, sizeof(u32) * 4 * ni, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out64, d_out64.p, sizeof(u64) * 3 * ni, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(painted, d_painted.p, sizeof(u64) * nw, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(diff, d_diff.p, sizeof(u32) * nd, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }

@@ -30,22 +30,20 @@
 // Everything is integer arithmetic, and the result is the walk's whatever the launch geometry or the order of the
 // atomics.  The rows of a set are contiguous in a row table of the solver's form (sorted by set): pr_ranges_kernel
 // takes each set's range of rows from that and raises a flag when a set comes in two runs.
-#include "internal.h"
+#include "rows_host.h"
+#include "spans.h"
 #include "wave.h"
 
 #define PR_TAIL_BELOW 8          // a round that removes fewer picks hands the rest to the one-workgroup walk
 #define PR_NONE 0xffffffffu
 enum { PR_UNDECIDED = 0, PR_KEPT = 1, PR_REMOVED = 2 };
 
-// exam[set] = examination index of the pick of that set (PR_NONE beforehand); set_of[e] = the set examined e-th.
-// The picks have passed dp_mark_kernel: in range, none twice.
+// set_of[e] = the set examined e-th; the examination index of the pick of a set is npicks - 1 - rank[set] (the pick
+// table of chip_depth_marks).  The picks have passed dp_mark_kernel: in range, none twice.
 __global__ void __launch_bounds__(256)
-pr_order_kernel(const i64 *__restrict__ picks, u32 npicks, u32 *__restrict__ exam, u32 *__restrict__ set_of) {
+pr_order_kernel(const i64 *__restrict__ picks, u32 npicks, u32 *__restrict__ set_of) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npicks) return;
-    const u32 s = (u32)picks[i], e = npicks - 1 - i;
-    exam[s] = e;
-    set_of[e] = s;
+    if (i < npicks) set_of[npicks - 1 - i] = (u32)picks[i];
 }
 
 // rbeg1[s] = 1 + the first row of set s (0: no rows), rend[s] = one past its last.  flag[0] |= 4: a set in two runs
@@ -65,23 +63,16 @@ pr_ranges_kernel(const i32 *__restrict__ set_id, u32 n, u32 num_sets, u32 *__res
 // bm bit b = depth(b) >= D + 1.  A row of a picked set with a clear bit under it: the set is not removable
 __global__ void __launch_bounds__(256)
 pr_classify_rows_kernel(const i32 *__restrict__ set_id, const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n,
-                        u32 num_sets, const u32 *__restrict__ exam, const unsigned long long *__restrict__ bm,
-                        u32 *__restrict__ state) {
+                        u32 num_sets, const u32 *__restrict__ rank, u32 npicks,
+                        const unsigned long long *__restrict__ bm, u32 *__restrict__ state) {
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const u32 s = (u32)set_id[r];
     if (s >= num_sets) return;
-    const u32 e = exam[s];
-    if (e == PR_NONE) return;
+    const u32 rk = rank[s];
+    if (rk == CHIP_NOT_PICKED) return;
     const u32 a = gs[r], b = ge[r];
-    if (b <= a) return;
-    const u32 w0 = a >> 6, w1 = (b - 1) >> 6;
-    for (u32 w = w0; w <= w1; ++w) {
-        u64 m = ~0ull;
-        if (w == w0) m &= ~0ull << (a & 63);
-        if (w == w1) m &= ~0ull >> (63 - ((b - 1) & 63));
-        if ((bm[w] & m) != m) { state[e] = PR_KEPT; return; }
-    }
+    if (b > a && !span_all_set(bm, a, b)) state[npicks - 1 - rk] = PR_KEPT;
 }
 
 // list[0 .. ctr[0]) = the undecided picks (examination indices, any order); a thread per pick, one atomic per wavefront
@@ -240,17 +231,9 @@ extern "C" int catchhip_rows_prune(catchhip_ctx *ctx, const catchhip_rows *R0, c
             chip_set_error("rows_prune: the fixed rows belong to another context");
             return CATCHHIP_EINVAL;
         }
-        TRY(chip_rows_cut_check(F, "rows_prune", "the fixed rows"));
-        if (R0->total != F->total || R0->ngenomes != F->ngenomes || R0->h_genome_off != F->h_genome_off) {
-            chip_set_error("rows_prune: the fixed rows are not over the coordinate space of the rows "
-                           "(%lld bases in %d universes against %lld in %d)",
-                           (long long)F->total, (int)F->ngenomes, (long long)R0->total, (int)R0->ngenomes);
-            return CATCHHIP_EINVAL;
-        }
-        if (F->n >= ((i64)1 << 31)) {
-            chip_set_error("rows_prune: too many rows");
-            return CATCHHIP_EINVAL;
-        }
+        TRY(chip_rows_form_check(F, "rows_prune", "the fixed rows"));
+        TRY(chip_space_check(F, R0, "rows_prune", "the fixed rows are not over the coordinate space of the rows"));
+        TRY(chip_rows_limits_check("rows_prune", F->total, F->n));
     }
     if (npicks == 0) return 0;
     PoolScope pool_scope(ctx);
@@ -260,8 +243,9 @@ extern "C" int catchhip_rows_prune(catchhip_ctx *ctx, const catchhip_rows *R0, c
     const u32 np = (u32)npicks, ns = (u32)num_sets, n0 = (u32)R0->n;
     const u64 total = (u64)R0->total;
     DevBuf<i64> d_picks;
+    DevBuf<u32> rank;
     DevBuf<u8> picked;
-    TRY(chip_depth_marks(ctx, picks, npicks, num_sets, d_picks, picked, tm, "rows_prune"));
+    TRY(chip_depth_marks(ctx, picks, npicks, num_sets, d_picks, rank, picked, tm, "rows_prune"));
     if (n0 == 0 || total == 0) {                             // no pick has a row: each covers nothing alone
         memset(removed_flags, 1, (size_t)npicks);
         if (nremoved) *nremoved = npicks;
@@ -269,11 +253,9 @@ extern "C" int catchhip_rows_prune(catchhip_ctx *ctx, const catchhip_rows *R0, c
         return 0;
     }
     // examination order, every set's range of rows, the depth array and the bitmap of depth >= D + 1
-    DevBuf<u32> exam, set_of, rbeg1, rend, state, flag, ctr, list, next, dep, scan_tmp, cand, first;
+    DevBuf<u32> set_of, rbeg1, rend, state, flag, ctr, list, next, dep, scan_tmp, cand, first;
     DevBuf<unsigned long long> bm;
-    const size_t nwords = (size_t)(total / 64 + 2) + 8;
     const u32 D = (u32)depth;
-    TRY(exam.alloc(ns));
     TRY(set_of.alloc(np));
     TRY(rbeg1.alloc(ns));
     TRY(rend.alloc(ns));
@@ -282,23 +264,21 @@ extern "C" int catchhip_rows_prune(catchhip_ctx *ctx, const catchhip_rows *R0, c
     TRY(ctr.alloc(2));
     TRY(list.alloc(np));
     TRY(next.alloc(np));
-    TRY(bm.alloc(nwords));
-    HIP_TRY(hipMemsetAsync(exam.p, 0xff, sizeof(u32) * (size_t)ns, s));
+    TRY(chip_cut_bitmap(ctx, R0->total, true, bm));
     HIP_TRY(hipMemsetAsync(rbeg1.p, 0, sizeof(u32) * (size_t)ns, s));
     HIP_TRY(hipMemsetAsync(rend.p, 0, sizeof(u32) * (size_t)ns, s));
     HIP_TRY(hipMemsetAsync(state.p, 0, sizeof(u32) * (size_t)np, s));
     HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(u32), s));
     HIP_TRY(hipMemsetAsync(ctr.p, 0, sizeof(u32) * 2, s));
-    HIP_TRY(hipMemsetAsync(bm.p, 0, sizeof(unsigned long long) * nwords, s));
     const dim3 blk(256), per_pick((unsigned)div_up(np, 256)), per_row((unsigned)div_up(n0, 256));
-    hipLaunchKernelGGL(pr_order_kernel, per_pick, blk, 0, s, (const i64 *)d_picks.p, np, exam.p, set_of.p);
+    hipLaunchKernelGGL(pr_order_kernel, per_pick, blk, 0, s, (const i64 *)d_picks.p, np, set_of.p);
     hipLaunchKernelGGL(pr_ranges_kernel, per_row, blk, 0, s, (const i32 *)R0->set_id.p, n0, ns, rbeg1.p, rend.p, flag.p);
     tm.launch(2);
     TRY(chip_depth_array(ctx, R0, (const u8 *)picked.p, ns, F, dep, scan_tmp, tm));
     TRY(chip_depth_bitmap(ctx, (const u32 *)dep.p, total, D + 1u, (const u32 *)R0->genome_off.p, (u32)R0->ngenomes, bm.p,
                           nullptr, tm));
     hipLaunchKernelGGL(pr_classify_rows_kernel, per_row, blk, 0, s, (const i32 *)R0->set_id.p, (const u32 *)R0->gs.p,
-                       (const u32 *)R0->ge.p, n0, ns, (const u32 *)exam.p, (const unsigned long long *)bm.p, state.p);
+                       (const u32 *)R0->ge.p, n0, ns, (const u32 *)rank.p, np, (const unsigned long long *)bm.p, state.p);
     hipLaunchKernelGGL(pr_compact_kernel, per_pick, blk, 0, s, (const u32 *)state.p, np, list.p, ctr.p);
     tm.launch(2);
     HIP_TRY(hipGetLastError());

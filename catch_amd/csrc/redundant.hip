@@ -31,7 +31,7 @@
 // without a sort.
 #include <algorithm>
 
-#include "internal.h"
+#include "rows_host.h"
 #include "wave.h"
 
 #define RG_TILE 64

@@ -21,7 +21,8 @@
 #include <algorithm>
 #include <chrono>
 
-#include "internal.h"
+#include "rows_host.h"
+#include "spans.h"
 #include "wave.h"
 
 // ------------------------------------------------------------------------
@@ -2631,15 +2632,7 @@ rows_stats_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__ univ, 
     // (set, universe) group counts one universe for its set
     if (per_set && (r == 0 || set_id[r - 1] != set_id[r] || univ[r - 1] != univ[r]))
         atomicAdd(&per_set[set_id[r]], 1ull);
-    if (e > s) {
-        const u32 w0 = s >> 6, w1 = (e - 1) >> 6;
-        for (u32 w = w0; w <= w1; ++w) {
-            u64 m = ~0ull;
-            if (w == w0) m &= ~0ull << (s & 63);
-            if (w == w1) m &= ~0ull >> (63 - ((e - 1) & 63));
-            if ((bm[w] & m) != m) atomicOr(&bm[w], m);
-        }
-    }
+    if (e > s) span_paint(bm, s, e);
 }
 
 __global__ void __launch_bounds__(256)
@@ -2650,13 +2643,8 @@ rows_union_kernel(const unsigned long long *__restrict__ bm, const u32 *__restri
     const u32 s = genome_off[u], e = genome_off[u + 1];
     u32 c = 0;
     if (e > s) {
-        const u32 w0 = s >> 6, w1 = (e - 1) >> 6;
-        for (u32 w = w0 + threadIdx.x; w <= w1; w += blockDim.x) {
-            u64 m = ~0ull;
-            if (w == w0) m &= ~0ull << (s & 63);
-            if (w == w1) m &= ~0ull >> (63 - ((e - 1) & 63));
-            c += (u32)__popcll(bm[w] & m);
-        }
+        const Span sp = span_of(s, e);
+        for (u32 j = threadIdx.x; j < sp.nw; j += blockDim.x) c += span_popc_word(bm, sp, j);
     }
     c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;

@@ -13,7 +13,8 @@
 // own and the sets that leave the table whole.
 #include <algorithm>
 
-#include "internal.h"
+#include "rows_host.h"
+#include "spans.h"
 #include "wave.h"
 
 #define SUB_MAXW 5   // rows of at most 5 words (<= 257 bases) load all their words before the first use (RP_MAXW of setcover.hip)
@@ -24,23 +25,11 @@ sub_bitmap_kernel(const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n,
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const u32 s = gs[r], e = ge[r];
-    if (e <= s) return;
-    const u32 w0 = s >> 6, w1 = (e - 1) >> 6;
-    for (u32 w = w0; w <= w1; ++w) {
-        u64 m = ~0ull;
-        if (w == w0) m &= ~0ull << (s & 63);
-        if (w == w1) m &= ~0ull >> (63 - ((e - 1) & 63));
-        if ((bm[w] & m) != m) atomicOr(&bm[w], m);
-    }
+    if (e > s) span_paint(bm, s, e);
 }
 
-// the uncovered bases of word j (of nw) of a row: v = the bitmap word, m0 / m1 = the masks of the row's two ends
-__device__ __forceinline__ u64 sub_free(u64 v, u32 j, u32 nw, u64 m0, u64 m1) {
-    u64 m = ~0ull;
-    if (j == 0) m &= m0;
-    if (j == nw - 1) m &= m1;
-    return ~v & m;
-}
+// the uncovered bases of word j of a row's span: v = the bitmap word
+__device__ __forceinline__ u64 sub_free(u64 v, const Span &sp, u32 j) { return ~v & span_mask(sp, j); }
 // pieces that START in a word: an uncovered base whose predecessor is covered or lies before the row
 // (prev = the word before, 0 for the first)
 __device__ __forceinline__ u32 sub_starts(u64 f, u64 prev) { return (u32)__popcll(f & ~((f << 1) | (prev >> 63))); }
@@ -60,8 +49,8 @@ sub_count_kernel(const i32 *__restrict__ set_id, const u32 *__restrict__ gs, con
     if (r < n) {
         const u32 s = gs[r], e = ge[r];
         if (e > s && !sub_skipped(skip, nskip, set_id[r])) {
-            const u32 w0 = s >> 6, nw = ((e - 1) >> 6) - w0 + 1;
-            const u64 m0 = ~0ull << (s & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
+            const Span sp = span_of(s, e);
+            const u32 w0 = sp.w0, nw = sp.nw;
             u64 prev = 0;
             if (nw <= SUB_MAXW) {
                 u64 v[SUB_MAXW];
@@ -69,13 +58,13 @@ sub_count_kernel(const i32 *__restrict__ set_id, const u32 *__restrict__ gs, con
                 for (u32 j = 0; j < SUB_MAXW; ++j) v[j] = (j < nw) ? bm[w0 + j] : ~0ull;
 #pragma unroll
                 for (u32 j = 0; j < SUB_MAXW; ++j) {
-                    const u64 f = (j < nw) ? sub_free(v[j], j, nw, m0, m1) : 0ull;
+                    const u64 f = (j < nw) ? sub_free(v[j], sp, j) : 0ull;
                     c += sub_starts(f, prev);
                     prev = f;
                 }
             } else {
                 for (u32 j = 0; j < nw; ++j) {
-                    const u64 f = sub_free(bm[w0 + j], j, nw, m0, m1);
+                    const u64 f = sub_free(bm[w0 + j], sp, j);
                     c += sub_starts(f, prev);
                     prev = f;
                 }
@@ -144,17 +133,17 @@ sub_emit_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__ univ, co
         w.sid = set_id[r]; w.un = univ[r];
         w.start = 0; w.open = false; w.sum = 0; w.longest = 0;
         if (e > s && !sub_skipped(skip, nskip, w.sid)) {
-            const u32 w0 = s >> 6, nw = ((e - 1) >> 6) - w0 + 1;
-            const u64 m0 = ~0ull << (s & 63), m1 = ~0ull >> (63 - ((e - 1) & 63));
+            const Span sp = span_of(s, e);
+            const u32 w0 = sp.w0, nw = sp.nw;
             if (nw <= SUB_MAXW) {
                 u64 v[SUB_MAXW];
 #pragma unroll
                 for (u32 j = 0; j < SUB_MAXW; ++j) v[j] = (j < nw) ? bm[w0 + j] : ~0ull;
 #pragma unroll
                 for (u32 j = 0; j < SUB_MAXW; ++j)
-                    if (j < nw) w.word(sub_free(v[j], j, nw, m0, m1), (w0 + j) << 6);
+                    if (j < nw) w.word(sub_free(v[j], sp, j), (w0 + j) << 6);
             } else {
-                for (u32 j = 0; j < nw; ++j) w.word(sub_free(bm[w0 + j], j, nw, m0, m1), (w0 + j) << 6);
+                for (u32 j = 0; j < nw; ++j) w.word(sub_free(bm[w0 + j], sp, j), (w0 + j) << 6);
             }
             w.finish(e);
         }
@@ -163,22 +152,6 @@ sub_emit_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__ univ, co
     }
     longest = wave_max(longest);
     if ((threadIdx.x & 63u) == 0 && longest) atomicMax(&info[1], (unsigned long long)longest);
-}
-
-int chip_rows_cut_check(const catchhip_rows *R, const char *who, const char *which) {
-    if (R->deferred) {
-        chip_set_error("%s: %s are deferred rows (a fused scan that was never synchronised)", who, which);
-        return CATCHHIP_EINVAL;
-    }
-    if (R->rows4.p) {
-        chip_set_error("%s: %s are in the direct form of the fused filter, not a row table", who, which);
-        return CATCHHIP_EINVAL;
-    }
-    if (R->grouped) {
-        chip_set_error("%s: %s come from a scan with group numbers (a union of instances), which is not supported", who, which);
-        return CATCHHIP_EINVAL;
-    }
-    return 0;
 }
 
 // a copy of R0 (nothing is covered)
@@ -201,7 +174,7 @@ int chip_rows_copy(catchhip_ctx *ctx, const catchhip_rows *R0, catchhip_rows *R)
     return 0;
 }
 
-// The rows of R0 (a non-empty table that passed chip_rows_cut_check, fewer than 2^31 rows) cut into their maximal
+// The rows of R0 (a non-empty table that passed chip_rows_form_check, fewer than 2^31 rows) cut into their maximal
 // runs of bases whose bit in bm is clear, into R (made by chip_rows_new over R0's coordinate space); the rows of the
 // sets with skip[set] != 0 (set < nskip; skip may be null) are left out whole.  count -> exclusive scan -> read-back
 // of the number of pieces -> emit; R gets n, lmax and, when R0 has it, gain0.  tm is the caller's running timer: its
@@ -257,48 +230,24 @@ extern "C" int catchhip_rows_subtract(catchhip_ctx *ctx, const catchhip_rows *R0
     ARG_CHECK(R0->ctx == ctx && C->ctx == ctx);
     *out = nullptr;
     if (nrows) *nrows = 0;
-    TRY(chip_rows_cut_check(R0, "rows_subtract", "the rows"));
-    TRY(chip_rows_cut_check(C, "rows_subtract", "the covered rows"));
-    if (R0->total != C->total || R0->ngenomes != C->ngenomes || R0->h_genome_off != C->h_genome_off) {
-        chip_set_error("rows_subtract: the covered rows are not over the coordinate space of the rows "
-                       "(%lld bases in %d universes against %lld in %d)",
-                       (long long)C->total, (int)C->ngenomes, (long long)R0->total, (int)R0->ngenomes);
-        return CATCHHIP_EINVAL;
-    }
-    if (R0->total >= ((i64)1 << 32) - 1) {
-        chip_set_error("rows_subtract: more than 2^32 - 2 target bases");
-        return CATCHHIP_EINVAL;
-    }
-    if (R0->n >= ((i64)1 << 31) || C->n >= ((i64)1 << 31)) {
-        chip_set_error("rows_subtract: too many rows");
-        return CATCHHIP_EINVAL;
-    }
+    TRY(chip_rows_form_check(R0, "rows_subtract", "the rows"));
+    TRY(chip_rows_form_check(C, "rows_subtract", "the covered rows"));
+    TRY(chip_space_check(C, R0, "rows_subtract", "the covered rows are not over the coordinate space of the rows"));
+    TRY(chip_rows_limits_check("rows_subtract", R0->total, R0->n, C->n));
     PoolScope pool_scope(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    std::unique_ptr<catchhip_rows> R;
-    TRY(chip_rows_new(ctx, R0->total, R0->ngenomes, R0->h_genome_off, R0->genome_off.p, false, R));
-    R->ext = -1;
-    PhaseTimer tm(ctx, PHASE_ROWS);
-    if (R0->n == 0 || C->n == 0) {
-        if (R0->n) TRY(chip_rows_copy(ctx, R0, R.get()));
-        else HIP_TRY(hipStreamSynchronize(s));   // (genome_off is on its way)
-        tm.finish();
-        if (nrows) *nrows = R->n;
-        *out = R.release();
-        return 0;
+    DerivedRows D(ctx, R0);
+    TRY(D.err);
+    if (R0->n == 0 || C->n == 0) {                           // nothing to cut, or nothing covered: a copy
+        TRY(D.copy_of(R0));
+        return D.finish(out, nrows);
     }
     const u32 nc = (u32)C->n;
-    const size_t nwords = (size_t)(R0->total / 64 + 2) + 8;
     DevBuf<unsigned long long> bm;
-    TRY(bm.alloc(nwords));
-    HIP_TRY(hipMemsetAsync(bm.p, 0, sizeof(unsigned long long) * nwords, s));
-    hipLaunchKernelGGL(sub_bitmap_kernel, dim3((unsigned)div_up(nc, 256)), dim3(256), 0, s, (const u32 *)C->gs.p,
+    TRY(chip_cut_bitmap(ctx, R0->total, true, bm));
+    hipLaunchKernelGGL(sub_bitmap_kernel, dim3((unsigned)div_up(nc, 256)), dim3(256), 0, ctx->stream, (const u32 *)C->gs.p,
                        (const u32 *)C->ge.p, nc, bm.p);
-    tm.launch(1);
-    TRY(chip_rows_cut(ctx, R0, (const unsigned long long *)bm.p, nullptr, 0, R.get(), tm, "rows_subtract"));
-    tm.finish();
-    if (nrows) *nrows = R->n;
-    *out = R.release();
-    return 0;
+    D.tm.launch(1);
+    TRY(chip_rows_cut(ctx, R0, (const unsigned long long *)bm.p, nullptr, 0, D.R.get(), D.tm, "rows_subtract"));
+    return D.finish(out, nrows);
 }

@@ -28,7 +28,7 @@
 // does not depend on the launch geometry.  Scratch: 16 bytes per input row.
 #include <algorithm>
 
-#include "internal.h"
+#include "rows_host.h"
 #include "wave.h"
 
 typedef unsigned long long ull;
@@ -167,37 +167,20 @@ extern "C" int catchhip_rows_union(catchhip_ctx *ctx, const catchhip_rows *Ra, c
     ARG_CHECK(Ra->ctx == ctx && Rb->ctx == ctx);
     *out = nullptr;
     if (nrows) *nrows = 0;
-    TRY(chip_rows_cut_check(Ra, "rows_union", "the first rows"));
-    TRY(chip_rows_cut_check(Rb, "rows_union", "the second rows"));
-    if (Ra->total != Rb->total || Ra->ngenomes != Rb->ngenomes || Ra->h_genome_off != Rb->h_genome_off) {
-        chip_set_error("rows_union: the two tables are not over one coordinate space "
-                       "(%lld bases in %d universes against %lld in %d)",
-                       (long long)Ra->total, (int)Ra->ngenomes, (long long)Rb->total, (int)Rb->ngenomes);
-        return CATCHHIP_EINVAL;
-    }
-    if (Ra->total >= ((i64)1 << 32) - 1) {
-        chip_set_error("rows_union: more than 2^32 - 2 target bases");
-        return CATCHHIP_EINVAL;
-    }
-    if (Ra->n >= ((i64)1 << 31) || Rb->n >= ((i64)1 << 31)) {
-        chip_set_error("rows_union: too many rows");
-        return CATCHHIP_EINVAL;
-    }
+    TRY(chip_rows_form_check(Ra, "rows_union", "the first rows"));
+    TRY(chip_rows_form_check(Rb, "rows_union", "the second rows"));
+    TRY(chip_space_check(Ra, Rb, "rows_union", "the two tables are not over one coordinate space"));
+    TRY(chip_rows_limits_check("rows_union", Ra->total, Ra->n, Rb->n));
     PoolScope pool_scope(ctx);
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    std::unique_ptr<catchhip_rows> R;
-    TRY(chip_rows_new(ctx, Ra->total, Ra->ngenomes, Ra->h_genome_off, Ra->genome_off.p, false, R));
-    R->ext = -1;
-    PhaseTimer tm(ctx, PHASE_ROWS);
-    if (Ra->n == 0 || Rb->n == 0) {
-        const catchhip_rows *src = Ra->n ? Ra : Rb;
-        if (src->n) TRY(chip_rows_copy(ctx, src, R.get()));
-        else HIP_TRY(hipStreamSynchronize(s));   // (genome_off is on its way)
-        tm.finish();
-        if (nrows) *nrows = R->n;
-        *out = R.release();
-        return 0;
+    DerivedRows D(ctx, Ra);
+    TRY(D.err);
+    catchhip_rows *R = D.R.get();
+    PhaseTimer &tm = D.tm;
+    if (Ra->n == 0 || Rb->n == 0) {                          // the other table, or nothing
+        TRY(D.copy_of(Ra->n ? Ra : Rb));
+        return D.finish(out, nrows);
     }
     const u32 na = (u32)Ra->n, nb = (u32)Rb->n;
     const size_t nin = (size_t)na + nb;
@@ -239,7 +222,7 @@ extern "C" int catchhip_rows_union(catchhip_ctx *ctx, const catchhip_rows *Ra, c
     }
     const u32 cap = (u32)ends[0];
     const u32 ng = (Ra->gain0_n && Rb->gain0_n) ? std::max(Ra->gain0_n, Rb->gain0_n) : 0u;
-    TRY(chip_rows_alloc_soa(R.get(), cap));
+    TRY(chip_rows_alloc_soa(R, cap));
     if (ng) {
         TRY(R->gain0.alloc(ng));
         HIP_TRY(hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)ng, s));
@@ -254,10 +237,7 @@ extern "C" int catchhip_rows_union(catchhip_ctx *ctx, const catchhip_rows *Ra, c
     ull longest = 0;
     tm.stop();
     TRY(chip_read_back(ctx, info.p, sizeof(longest), &longest));
-    tm.finish();
     R->n = (i64)cap;
     R->lmax = (u32)longest;
-    if (nrows) *nrows = R->n;
-    *out = R.release();
-    return 0;
+    return D.finish(out, nrows);
 }

@@ -343,6 +343,30 @@ class Context:
                                                      int(x.size), _ptr(out, c_u32p)))
         return out[:x.size]
 
+    SPAN_RESULTS_32 = ("first_word", "words", "popcount", "all_set")
+    SPAN_RESULTS_64 = ("first_mask", "last_mask", "word_view")
+
+    def selftest_spans(self, bitmap, a, b, view=0):
+        """catchhip_selftest_spans: what the helpers of csrc/spans.h returned for every interval [a[i], b[i]) over
+        `bitmap` (uint64 words), by name; "word_view" is span_in_word for word `view`.  "painted" / "diff": all the
+        intervals painted into one zeroed bitmap and marked on one zeroed difference array (64 * words + 1 entries)."""
+        bm = np.ascontiguousarray(bitmap, dtype=np.uint64)
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        b = np.ascontiguousarray(b, dtype=np.uint32)
+        if a.size != b.size:
+            raise ValueError("selftest_spans: a and b must have one length")
+        o32 = np.zeros((len(self.SPAN_RESULTS_32), a.size), dtype=np.uint32)
+        o64 = np.zeros((len(self.SPAN_RESULTS_64), a.size), dtype=np.uint64)
+        painted = np.zeros(bm.size, dtype=np.uint64)
+        diff = np.zeros(64 * bm.size + 1, dtype=np.uint32)
+        check(self._L.catchhip_selftest_spans(self._h, _ptr(bm, c_u64p), int(bm.size), _ptr(a, c_u32p), _ptr(b, c_u32p),
+                                              int(a.size), int(view), _ptr(o32, c_u32p), _ptr(o64, c_u64p),
+                                              _ptr(painted, c_u64p), _ptr(diff, c_u32p)))
+        out = dict(zip(self.SPAN_RESULTS_32, o32))
+        out.update(zip(self.SPAN_RESULTS_64, o64))
+        out.update(painted=painted, diff=diff)
+        return out
+
     # -- test entry point of the row build (tests/test_row_build.py) -------
     ROW_BUILDS = {"bucketed": 0, "radix": 1, "radix_if_overflow": 2}
     BK_NONE = 0xffffffff

@@ -596,6 +596,17 @@ int catchhip_selftest_wave(catchhip_ctx *ctx, const uint32_t *in, int64_t n,
                            uint32_t *out32, uint64_t *out64);
 int catchhip_selftest_find_segment(catchhip_ctx *ctx, const uint32_t *off, int64_t n,
                                    const uint32_t *x, int64_t nx, uint32_t *out);
+/* Test entry point of the base-interval helpers of csrc/spans.h: n intervals [a[i], b[i]),
+ * a[i] < b[i] <= 64 * nwords, one per thread, over the bitmap bm of nwords words.
+ * out32 holds 4 arrays of n: 0 first word, 1 number of words, 2 span_popc, 3 span_all_set;
+ * out64 holds 3 arrays of n: 0 mask of the first word, 1 of the last, 2 span_in_word for
+ * word `view` (0 where the interval does not reach that word).  A second launch has all
+ * threads span_paint into one zeroed bitmap (painted: nwords words) and span_mark_diff
+ * into one zeroed difference array (diff: 64 * nwords + 1 words). */
+int catchhip_selftest_spans(catchhip_ctx *ctx, const uint64_t *bm, int64_t nwords,
+                            const uint32_t *a, const uint32_t *b, int64_t n, uint32_t view,
+                            uint32_t *out32, uint64_t *out64, uint64_t *painted,
+                            uint32_t *diff);
 /* Test entry point of the bucketed row build (csrc/rows_bucket.inc and its host side
  * in csrc/scan.hip); tests/test_row_build.py compares it with a sequential merge in
  * NumPy.  No reference counterpart.  Hit records go in as a producer files them, the

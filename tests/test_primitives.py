@@ -17,6 +17,10 @@ arithmetic of the segmented sort near 2^32.  The full-size digests of bench.py r
 The wavefront-level helpers of csrc/wave.h (reductions, scans, DPP sums, find_segment) are below the two, through
 catchhip_selftest_wave and catchhip_selftest_find_segment: one kernel that calls every helper on one value per thread
 and hands back what every thread got.
+
+The base-interval helpers of csrc/spans.h (the words and end masks of [a, b) on a bitmap, paint, all-set test,
+popcount, difference mark) are at the end, through catchhip_selftest_spans: one interval per thread, over every pair
+of the points at which a mask can be off by one, against a model of one boolean per base.
 """
 import os
 import re
@@ -91,12 +95,13 @@ def test_selftest_symbols_declared_bound_and_wrapped():
     hdr = open(os.path.join(REPO, "include", "catchhip.h")).read()
     src = open(os.path.join(REPO, "catch_amd", "csrc", "primitives.hip")).read()
     for name in ("catchhip_selftest_scan_u32", "catchhip_selftest_sort_pairs", "catchhip_selftest_wave",
-                 "catchhip_selftest_find_segment"):
+                 "catchhip_selftest_find_segment", "catchhip_selftest_spans"):
         assert re.search(r"\b%s\s*\(" % name, hdr), name
         assert re.search(r'extern "C" int %s\s*\(' % name, src), name
         assert name in _lib.PROTOTYPES, name
     assert callable(engine.Context.selftest_scan_u32) and callable(engine.Context.selftest_sort_pairs)
     assert callable(engine.Context.selftest_wave) and callable(engine.Context.selftest_find_segment)
+    assert callable(engine.Context.selftest_spans)
     # the structural sizes this file is written around
     assert re.search(r"#define SCAN_THREADS 256\b", src) and re.search(r"#define SCAN_ITEMS 8\b", src)
     assert re.search(r"#define RS_THREADS 256\b", src) and re.search(r"#define RS_ROUNDS 16\b", src)
@@ -390,3 +395,76 @@ def test_find_segment_equals_searchsorted(ctx, table):
     bad = np.nonzero(got != want)[0]
     assert bad.size == 0, (table, bad[:5].tolist(), got[bad[:5]].tolist(), want[bad[:5]].tolist())
     assert (off[got] <= x).all() and (x < off[got + 1]).all()
+
+
+# ------------------------------------------------------------------ spans.h
+SPAN_T = 449                # bases of the space: no multiple of 64, and more than SUB_MAXW + 1 = 6 words
+SPAN_WORDS = 8
+SPAN_POINTS = (0, 1, 62, 63, 64, 65, 127, 128, 129, 319, 320, 321, 384, 385, SPAN_T - 1, SPAN_T)
+SPAN_INTERVALS = [(a, b) for a in SPAN_POINTS for b in SPAN_POINTS if a < b]
+
+
+def _words(bits):
+    """uint64 words of a boolean per base (rows of 64 * k booleans -> rows of k words), bit i of a word = base i."""
+    bits = np.asarray(bits, dtype=bool)
+    return np.packbits(bits.reshape(bits.shape[:-1] + (-1, 64)), axis=-1, bitorder="little").view("<u8")[..., 0]
+
+
+def _span_bitmap(kind):
+    if kind == "random":
+        return np.random.default_rng(449).integers(0, 2, size=64 * SPAN_WORDS).astype(bool)
+    return np.full(64 * SPAN_WORDS, kind == "ones")
+
+
+def _span_expected(bm_bits, view):
+    """The model: one boolean per base.  Nothing here shifts or masks a word."""
+    a = np.array([i[0] for i in SPAN_INTERVALS])[:, None]
+    b = np.array([i[1] for i in SPAN_INTERVALS])[:, None]
+    pos = np.arange(64 * SPAN_WORDS)[None, :]
+    inside = (pos >= a) & (pos < b)                                  # [interval][base]
+    in_word = np.arange(64)[None, :]
+    masks = _words(inside)                                           # [interval][word]
+    diff = np.zeros(64 * SPAN_WORDS + 1, dtype=np.uint64)
+    np.add.at(diff, a[:, 0], 1)
+    np.add.at(diff, b[:, 0], 0xffffffff)
+    return {
+        "first_word": a[:, 0] // 64, "words": (b[:, 0] - 1) // 64 - a[:, 0] // 64 + 1,
+        "first_mask": _words(in_word >= a % 64)[:, 0], "last_mask": _words(in_word <= (b - 1) % 64)[:, 0],
+        "word_view": masks[:, view],
+        "popcount": (inside & bm_bits[None, :]).sum(axis=1), "all_set": (~inside | bm_bits[None, :]).all(axis=1),
+        "painted": np.bitwise_or.reduce(masks, axis=0), "diff": diff & np.uint64(0xffffffff),
+    }
+
+
+def test_span_model_on_cases_written_down():
+    assert len(SPAN_INTERVALS) == 120 and SPAN_T > 6 * 64 and SPAN_T % 64 and SPAN_T <= 64 * SPAN_WORDS
+    lens = {(b - 1) // 64 - a // 64 + 1 for a, b in SPAN_INTERVALS}
+    assert {1, 2, 5, 6, 8} <= lens and (0, 64) in SPAN_INTERVALS and (63, 64) in SPAN_INTERVALS
+    assert (SPAN_T - 1, SPAN_T) in SPAN_INTERVALS and (64, 384) in SPAN_INTERVALS      # one base; five whole words
+    assert _words(np.arange(128) == 65).tolist() == [0, 2] and int(_words(np.ones(64, bool))[0]) == MASK64
+    e = _span_expected(_span_bitmap("random"), 1)
+    i = SPAN_INTERVALS.index((63, 129))
+    assert (int(e["first_word"][i]), int(e["words"][i])) == (0, 3)
+    assert (int(e["first_mask"][i]), int(e["last_mask"][i]), int(e["word_view"][i])) == (1 << 63, 1, MASK64)
+    i = SPAN_INTERVALS.index((1, 62))                                # one word: the two masks overlap
+    assert (int(e["first_mask"][i]), int(e["last_mask"][i])) == (MASK64 - 1, MASK64 >> 2) and int(e["word_view"][i]) == 0
+    assert int(e["diff"][0]) == 15 and int(e["diff"][SPAN_T]) == (-15) & 0xffffffff and int(e["diff"].sum()) % (1 << 32) == 0
+    assert e["painted"].tolist() == [MASK64] * 7 + [(1 << (SPAN_T - 448)) - 1]
+    ones = _span_expected(_span_bitmap("ones"), 0)
+    assert ones["all_set"].all() and ones["popcount"].tolist() == [b - a for a, b in SPAN_INTERVALS]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["zeros", "ones", "random"])
+def test_span_helpers_equal_bit_model(ctx, kind):
+    bm_bits = _span_bitmap(kind)
+    a, b = np.array(SPAN_INTERVALS, dtype=np.uint32).T
+    for view in range(SPAN_WORDS):
+        got, want = ctx.selftest_spans(_words(bm_bits), a, b, view), _span_expected(bm_bits, view)
+        assert set(got) == set(want)
+        for name in got:
+            g, w = got[name].astype(np.uint64), np.asarray(want[name]).astype(np.uint64)
+            assert g.shape == w.shape, (kind, view, name)
+            bad = np.nonzero(g != w)[0]
+            where = [SPAN_INTERVALS[k] for k in bad[:5]] if g.size == len(SPAN_INTERVALS) else bad[:5].tolist()
+            assert bad.size == 0, (kind, view, name, where, g[bad[:5]].tolist(), w[bad[:5]].tolist())

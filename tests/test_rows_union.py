@@ -206,7 +206,7 @@ def test_rows_union_chain_across_every_launch_edge(ctx, broken):
 @pytest.mark.gpu
 def test_rows_union_refusals(ctx):
     """Refused: another coordinate space (an unmerged range table of a scan over other targets among them -- over the
-    SAME targets chip_rows_cut_check does not tell unmerged ranges from rows, as catchhip_rows_subtract cannot), and
+    SAME targets chip_rows_form_check does not tell unmerged ranges from rows, as catchhip_rows_subtract cannot), and
     rows of a scan with group numbers, on either side."""
     from catch_amd import engine, probe
     R = _from_host(ctx, _table([(0, 0, 10, 50), (0, 1, 0, 5)]), [100, 50])
