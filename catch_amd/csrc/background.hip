@@ -120,6 +120,7 @@ static int kmer_view_dir(catchhip_ctx *ctx, const u64 *codes, u32 n, u32 K, u32 
     *P_out = (u32)P;
     const u32 nprefix = (u32)1 << P;
     HIP_TRY(hipMalloc((void **)dir_out, sizeof(u32) * ((size_t)nprefix + 1)));
+    chip_poison_fill(*dir_out, sizeof(u32) * ((size_t)nprefix + 1));
     hipLaunchKernelGGL(kmer_dir_kernel, dim3((unsigned)div_up((i64)n + 1, 256)), dim3(256), 0, ctx->stream, codes, n,
                        2 * K - (u32)P, nprefix, *dir_out);
     HIP_TRY(hipGetLastError());
@@ -177,6 +178,7 @@ static int kmer_index_build(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, 
         TRY(chip_exclusive_scan_u32(ctx, vals.p, vals_alt.p, (i64)n_valid + 1, tmp));
         TRY(read_count(ctx, vals_alt.p + n_valid, &n_unique));
         HIP_TRY(hipMalloc((void **)&X->codes, sizeof(u64) * (size_t)n_unique));
+        chip_poison_fill(X->codes, sizeof(u64) * (size_t)n_unique);
         hipLaunchKernelGGL(kmer_compact_kernel, grid, block, 0, s, (const u64 *)keys.p, (const u32 *)vals.p,
                            (const u32 *)vals_alt.p, n_valid, X->codes);
         HIP_TRY(hipGetLastError());
@@ -184,6 +186,7 @@ static int kmer_index_build(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, 
         HIP_TRY(hipStreamSynchronize(s));                      // (the scratch goes back to the pool below)
     } else {
         HIP_TRY(hipMalloc((void **)&X->codes, sizeof(u64)));
+        chip_poison_fill(X->codes, sizeof(u64));
         HIP_TRY(hipMemsetAsync(X->codes, 0, sizeof(u64), s));
     }
     X->n_unique = n_unique;
@@ -195,6 +198,7 @@ static int kmer_index_build(catchhip_ctx *ctx, const u8 *bytes, const i64 *off, 
         const u32 s0 = b * K / (M + 1), s1 = (b + 1) * K / (M + 1);
         X->view_start[b - 1] = s0;
         HIP_TRY(hipMalloc((void **)&X->view_codes[b - 1], sizeof(u64) * (size_t)(n_unique ? n_unique : 1)));
+        chip_poison_fill(X->view_codes[b - 1], sizeof(u64) * (size_t)(n_unique ? n_unique : 1));
         if (n_unique) {
             // rotate, sort again (a bijection: the list stays distinct), keep; the scratch is the first sort's
             DevBuf<u32> vals, vals_alt;

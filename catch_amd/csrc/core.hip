@@ -86,6 +86,19 @@ static size_t pool_soft_limit() {
 
 size_t chip_pool_soft_limit() { return pool_soft_limit(); }
 
+// Test hook CATCHHIP_POOL_POISON=<0..255>: every block handed out is filled with that byte, its whole size class, so
+// that a result that depends on memory nobody wrote differs from run to run of tests/test_poisoned_memory.py
+// instead of reading zeros (a fresh block) or the previous call's values (a cached one).  A cached block may still
+// be read by work queued earlier on its owner's stream, and owners need not be contexts, so the fill is synchronous
+// between two device-wide waits.  Unset, this costs the hook's look-up and nothing else.
+void chip_poison_fill(void *p, size_t bytes) {
+    const long long v = chip_test_env_int("CATCHHIP_POOL_POISON", -1);
+    if (v < 0 || v > 255 || !p || !bytes) return;
+    (void)hipDeviceSynchronize();
+    (void)hipMemset(p, (int)v, bytes);
+    (void)hipDeviceSynchronize();
+}
+
 const void *chip_pool_set_owner(const void *owner) {
     const void *prev = g_pool_owner;
     g_pool_owner = owner;
@@ -95,6 +108,8 @@ const void *chip_pool_set_owner(const void *owner) {
 void *chip_pool_alloc(size_t bytes) {
     const void *owner = g_pool_owner;
     const size_t cls = pool_class(bytes);
+    void *cached = nullptr;
+    size_t cached_cls = 0;
     {
         std::lock_guard<std::mutex> lk(g_pool_mu);
         // exact size class only: a looser fit lets one request take the block the
@@ -115,8 +130,13 @@ void *chip_pool_alloc(size_t bytes) {
             g_pool_free.erase(it);
             g_pool_live[p] = PoolLive{owner, got};
             g_pool_stats[2] -= (long long)got;
-            return p;
+            cached = p;
+            cached_cls = got;
         }
+    }
+    if (cached) {
+        chip_poison_fill(cached, cached_cls);
+        return cached;
     }
     // The cache keeps what it was given; a request it cannot serve while the library already holds most
     // of the device (a union instance of a clustered design: work lists of 100+ GB whose sizes differ from
@@ -161,9 +181,12 @@ void *chip_pool_alloc(size_t bytes) {
             return nullptr;
         }
     }
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    g_pool_live[p] = PoolLive{owner, cls};
-    g_pool_stats[1] += (long long)cls;
+    {
+        std::lock_guard<std::mutex> lk(g_pool_mu);
+        g_pool_live[p] = PoolLive{owner, cls};
+        g_pool_stats[1] += (long long)cls;
+    }
+    chip_poison_fill(p, cls);
     return p;
 }
 

@@ -82,6 +82,9 @@ struct PoolScope {
     ~PoolScope() { chip_pool_set_owner(prev); }
 };
 void chip_pool_free(void *p);
+// test hook CATCHHIP_POOL_POISON: fills `bytes` at p with the hook's byte (core.hip); the pool calls it at every
+// hand-out, and so does every direct hipMalloc whose memory kernels read
+void chip_poison_fill(void *p, size_t bytes);
 // what the cache may hold (bytes): 0.87 of the device, or CATCHHIP_POOL_SOFT_LIMIT_GB
 size_t chip_pool_soft_limit();
 
