@@ -280,6 +280,13 @@ PROTOTYPES = {
     "catchhip_targets_set_groups": (ctypes.c_int, [c_vp, c_vp, c_i32p]),
 }
 
+# the entry points of include/catchhip_cross.h, bound like the ones above
+CROSS_PROTOTYPES = {
+    "catchhip_cross_dimer": (ctypes.c_int, [c_vp, c_u8p, c_i64p, ctypes.c_int64, c_i32p, c_i32p]),
+    "catchhip_cross_dimer_graph": (ctypes.c_int, [
+        c_vp, c_u8p, c_i64p, ctypes.c_int64, ctypes.c_int32, c_vpp, c_i64p]),
+}
+
 _lib = None
 
 
@@ -298,7 +305,7 @@ def lib():
                 "`make -C catch_amd/csrc`.  There is no CPU fallback."
                 % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in list(PROTOTYPES.items()) + list(CROSS_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -31,23 +31,13 @@
 // without a sort.
 #include <algorithm>
 
+#include "redgraph.h"
 #include "rows_host.h"
 #include "wave.h"
 
-#define RG_TILE 64
-#define RG_BLOCK 256
-#define RG_MAXLEN 256          // bases per probe: W = 4 words per plane
 #define RN_ROUNDS 8            // frontier rounds per read-back of the naive pass
 #define RN_FEW 64              // a round that decides fewer vertices hands over to the one-workgroup walk
 #define RN_BLOCK 1024
-
-struct catchhip_redgraph {
-    catchhip_ctx *ctx = nullptr;
-    i64 n = 0;
-    i64 nedges = 0;          // directed: every undirected pair counts twice
-    DevBuf<i64> ptr;         // n + 1
-    DevBuf<u32> idx;         // nedges, every row ascending
-};
 
 // one 64-base word of a probe's three planes: A = 0, C = 1, G = 2, T = 3, N = code 0 with the N bit
 __host__ __device__ static inline void rg_pack_word(const u8 *chars, u32 len, int w, u64 *c0, u64 *c1, u64 *cn) {
@@ -424,22 +414,30 @@ extern "C" int catchhip_redundancy_graph(catchhip_ctx *ctx, const u8 *bytes, con
     if (W == 1) rg_launch_pairs<1>(s, grid, kind, planes.p, lens.p, (u32)n, (u32)npad, p0, p1, bitmap.p, (u32)tiles);
     else if (W == 2) rg_launch_pairs<2>(s, grid, kind, planes.p, lens.p, (u32)n, (u32)npad, p0, p1, bitmap.p, (u32)tiles);
     else rg_launch_pairs<4>(s, grid, kind, planes.p, lens.p, (u32)n, (u32)npad, p0, p1, bitmap.p, (u32)tiles);
-    hipLaunchKernelGGL(rg_degree_kernel, dim3((unsigned)div_up(n, 4)), dim3(256), 0, s,
-                       (const unsigned long long *)bitmap.p, (u32)n, (u32)tiles, deg.p);
-    hipLaunchKernelGGL(rg_scan_kernel, dim3(1), dim3(RN_BLOCK), 0, s, (const u32 *)deg.p, (u32)n, G->ptr.p);
-    timer.launch(4);
+    timer.launch(2);
+    TRY(chip_redgraph_from_bitmap(ctx, timer, bitmap.p, tiles, deg.p, G.get()));
+    if (nedges) *nedges = G->nedges;
+    *out = G.release();
+    return 0;
+}
+
+int chip_redgraph_from_bitmap(catchhip_ctx *ctx, PhaseTimer &timer, const unsigned long long *bitmap, i64 tiles, u32 *deg,
+                              catchhip_redgraph *G) {
+    hipStream_t s = ctx->stream;
+    const i64 n = G->n;
+    hipLaunchKernelGGL(rg_degree_kernel, dim3((unsigned)div_up(n, 4)), dim3(256), 0, s, bitmap, (u32)n, (u32)tiles, deg);
+    hipLaunchKernelGGL(rg_scan_kernel, dim3(1), dim3(RN_BLOCK), 0, s, (const u32 *)deg, (u32)n, G->ptr.p);
+    timer.launch(2);
     HIP_TRY(hipGetLastError());
-    TRY(chip_read_back(ctx, G->ptr.p + n, sizeof(i64), &G->nedges));   // (rel[] and the caller's bytes are free again)
+    TRY(chip_read_back(ctx, G->ptr.p + n, sizeof(i64), &G->nedges));   // (the caller's host arrays are free again)
     TRY(G->idx.alloc((size_t)std::max<i64>(G->nedges, 1)));
-    hipLaunchKernelGGL(rg_fill_kernel, dim3((unsigned)div_up(n, 4)), dim3(256), 0, s,
-                       (const unsigned long long *)bitmap.p, (u32)n, (u32)tiles, (const i64 *)G->ptr.p, G->idx.p);
+    hipLaunchKernelGGL(rg_fill_kernel, dim3((unsigned)div_up(n, 4)), dim3(256), 0, s, bitmap, (u32)n, (u32)tiles,
+                       (const i64 *)G->ptr.p, G->idx.p);
     timer.launch(1);
     timer.stop();
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     timer.finish();
-    if (nedges) *nedges = G->nedges;
-    *out = G.release();
     return 0;
 }
 

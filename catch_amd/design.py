@@ -45,6 +45,10 @@ covered at all: BED intervals per FASTA record, the cover rows cut to them
 after the scan (catch_amd/target_regions.py has the rules).
 --either-strand (nor this) lets a candidate cover what its reverse complement
 hybridises to as well: targets filed in mixed orientations get one probe set.
+--max-cross-dimer (nor this) drops picked probes that anneal to an earlier
+kept one, one CrossDimerFilter right after the set cover filter over the picks
+of all datasets (catch_amd/filter/cross_dimer.py has the rule); --cross-dimer
+adds its two columns to --write-probe-report.
 --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
@@ -58,7 +62,7 @@ import sys
 from catch_amd.filter import background_filter, composition_filter
 from catch_amd.filter import duplicate_filter, near_duplicate_filter
 from catch_amd.filter import probe_designer, quality, set_cover_filter
-from catch_amd.filter import structure_filter, tm_filter
+from catch_amd.filter import cross_dimer, structure_filter, tm_filter
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.design")
@@ -153,6 +157,7 @@ def parse_args(argv=None, args_type="basic"):
     tm_filter.add_arguments(p)              # --filter-tm, --tm-..., --write-tm-histogram (not in the reference)
     background_filter.add_arguments(p)      # --background, --background-..., --write-background-histogram (not in the reference)
     quality.add_arguments(p)                # --write-candidate-profile (not in the reference)
+    cross_dimer.add_arguments(p)            # --cross-dimer, --max-cross-dimer (not in the reference)
     p.add_argument("--write-probe-report", metavar="FILE",
                    help="write what the designed probes are like to FILE: the "
                         "report python -m catch_amd.probe_report -f writes "
@@ -247,6 +252,16 @@ def parse_args(argv=None, args_type="basic"):
     structure_filter.from_args(args, p.error)
     tm_filter.from_args(args, p.error)
     background_filter.from_args(args, p.error, load=False)      # (the options alone: main reads the background)
+    cross_dimer.check_args(args, p.error)
+    if args.cross_dimer and args.write_probe_report is None:
+        p.error("--cross-dimer adds columns to --write-probe-report and needs it (--max-cross-dimer X filters)")
+    if args.max_cross_dimer is not None:
+        if args.add_reverse_complements:
+            p.error("--max-cross-dimer cannot go with --add-reverse-complements: every probe then has a perfect "
+                    "partner by construction")
+        if args.skip_set_cover:
+            p.error("--max-cross-dimer cannot go with --skip-set-cover: it would pair all candidates with each "
+                    "other, a quadratic pass")
     return args
 
 
@@ -565,6 +580,10 @@ def main(args):
         curve_points=args.coverage_curve_points,
         target_regions=regions, either_strand=args.either_strand)
     filters.append(scf)
+    cross = None
+    if args.max_cross_dimer is not None:    # (not in the reference) one filter over the picks of all datasets
+        cross = cross_dimer.CrossDimerFilter(args.max_cross_dimer)
+        filters.append(cross)
     if args.add_adapters:      # bin/design.py:345-365 (default sequences :350, :354)
         from catch_amd.filter import adapter_filter
         filters.append(adapter_filter.AdapterFilter(
@@ -618,6 +637,9 @@ def main(args):
         if args.write_background_histogram:
             background.write_histogram(args.write_background_histogram)
         background.close()
+    if cross is not None:
+        logger.info("cross-dimer filter: %d of %d probes dropped (largest cross-dimer %d before, %d after)",
+                    cross.dropped, cross.seen, cross.largest_before, cross.largest_after)
     if regions is not None:
         for gi, fn in enumerate(args.dataset):
             coverable = scf.last_coverable_bases[gi] if gi < len(scf.last_coverable_bases) else 0

@@ -1414,6 +1414,22 @@ class RedundancyGraph:
             ctypes.byref(self._h), ctypes.byref(ne)))
         self.nedges = ne.value
 
+    @classmethod
+    def cross_dimer(cls, ctx, strs, above):
+        """catchhip_cross_dimer_graph: records i and j (i != j) are neighbours
+        iff run(s_i, s_j) > above (catch_amd/filter/cross_dimer.py; any
+        characters, at most REDUNDANT_MAX_LENGTH each, above >= 1)."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self._h = ctypes.c_void_p()
+        buf, off = _concat_records(strs)
+        self.n = off.size - 1
+        ne = ctypes.c_int64(0)
+        check(ctx._L.catchhip_cross_dimer_graph(
+            ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), self.n, int(above), ctypes.byref(self._h), ctypes.byref(ne)))
+        self.nedges = ne.value
+        return self
+
     def fetch(self):
         """(ptr int64[n + 1], idx uint32[nedges]): the neighbours of i are
         idx[ptr[i]:ptr[i + 1]], ascending."""
@@ -1447,6 +1463,33 @@ class RedundancyGraph:
             self.close()
         except Exception:
             pass
+
+
+def _concat_records(strs):
+    """_concat for records of any characters: what latin-1 cannot hold becomes
+    '?', which is no base either."""
+    strs = list(strs)
+    off = np.zeros(len(strs) + 1, dtype=np.int64)
+    if strs:
+        np.cumsum([len(s) for s in strs], out=off[1:])
+    buf = np.frombuffer("".join(strs).encode("latin-1", "replace"), dtype=np.uint8)
+    if buf.size == 0:
+        buf = np.zeros(1, dtype=np.uint8)
+    return np.ascontiguousarray(buf), off
+
+
+def cross_dimer(ctx, strs):
+    """catchhip_cross_dimer -> (values int32[n], partners int32[n]): for every
+    record the longest antiparallel pairing with another record of the list
+    and the smallest index that reaches it, -1 where the value is 0
+    (catch_amd/filter/cross_dimer.py has the definition)."""
+    buf, off = _concat_records(strs)
+    n = off.size - 1
+    values = np.zeros(max(n, 1), dtype=np.int32)
+    partners = np.full(max(n, 1), -1, dtype=np.int32)
+    check(ctx._L.catchhip_cross_dimer(
+        ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), n, _ptr(values, c_i32p), _ptr(partners, c_i32p)))
+    return values[:n], partners[:n]
 
 
 class Shard:

@@ -9,6 +9,13 @@ background_hits (BackgroundFilter._hits; with --background, within
 not computed or is undefined.  With a threshold option a last column, verdict,
 lists the rules the probe fails, or ok; the thresholds are the design
 command's and are compared as it compares them.  Not in the reference.
+--cross-dimer puts two columns behind background_hits: cross_dimer, the longest
+antiparallel pairing with ANOTHER record of the file, and cross_partner, the
+number of the first record that reaches it (1-based, in file order; NA when
+the value is 0); --max-cross-dimer X implies it and adds the rule cross-dimer
+to every record whose value exceeds X, so both members of a pair fail
+(catch_amd/filter/cross_dimer.py has the definition).  For these two columns
+all records of the file are ONE list, whatever their lengths.
 
 Records are read with seq_io.iterate_fasta: bytes as they are (lower case is
 no base), any lengths.  On the device the records are grouped by length: a
@@ -25,14 +32,16 @@ import sys
 
 import numpy as np
 
-from catch_amd.filter import background_filter, composition_filter, quality
+from catch_amd.filter import background_filter, composition_filter, cross_dimer, quality
 from catch_amd.filter import structure_filter, tm_filter
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.probe_report")
 
 COLUMNS = ("probe", "length") + quality.QUANTITIES + ("tm_c", "background_hits")
+CROSS_COLUMNS = ("cross_dimer", "cross_partner")
 RULES = ("gc", "homopolymer", "low-complexity", "hairpin", "self-dimer", "tm", "background")
+CROSS_RULE = "cross-dimer"              # the one rule that looks at the other records of the file
 
 
 def parse_args(argv=None):
@@ -43,6 +52,7 @@ def parse_args(argv=None):
     structure_filter.add_arguments(p)
     tm_filter.add_arguments(p)
     background_filter.add_arguments(p)
+    cross_dimer.add_arguments(p)
     p.add_argument("--write-kept", metavar="FASTA", help="the records that fail no rule, as they were read")
     p.add_argument("--write-failed", metavar="FASTA", help="the records that fail a rule")
     p.add_argument("--verbose", action="store_true")
@@ -59,6 +69,7 @@ def parse_args(argv=None):
                             ("--background-mismatches", args.background_mismatches)):
             if value is not None:
                 p.error("%s needs --background" % flag)
+    cross_dimer.check_args(args, p.error)
     try:
         Judge(args, load=False)
     except ValueError as exc:
@@ -93,9 +104,14 @@ class Judge:
                 max_hits=args.background_max_hits, mismatches=getattr(args, "background_mismatches", None) or 0)
         elif args.background_max_hits is not None:
             raise ValueError("--background-max-hits needs --background")
+        # (the design commands without the two cross-dimer options hand over a namespace without them)
+        self.max_cross_dimer = getattr(args, "max_cross_dimer", None)
+        if self.max_cross_dimer is not None:
+            self.max_cross_dimer = cross_dimer._threshold(self.max_cross_dimer, "--max-cross-dimer")
+        self.cross_dimer = bool(getattr(args, "cross_dimer", False)) or self.max_cross_dimer is not None
         self.thresholds = any(x is not None for x in (
             args.filter_gc, args.max_homopolymer, args.filter_low_complexity, args.max_hairpin_stem,
-            args.max_self_dimer, args.filter_tm, args.background_max_hits))
+            args.max_self_dimer, args.filter_tm, args.background_max_hits, self.max_cross_dimer))
 
     @property
     def min_loop(self):
@@ -105,7 +121,7 @@ class Judge:
     def dust_window(self):
         return self.composition.dust_window
 
-    def failed(self, length, five, tm_c, hits):
+    def failed(self, length, five, tm_c, hits, cross=0):
         """The names of the rules a probe with these values fails, with the ties of the design command."""
         gc, run, dust, stem, dimer = five
         c, s, out = self.composition, self.structure, []
@@ -124,6 +140,8 @@ class Judge:
             out.append(RULES[5])
         if self.background is not None and self.background.max_hits is not None and hits > self.background.max_hits:
             out.append(RULES[6])
+        if self.max_cross_dimer is not None and cross > self.max_cross_dimer:
+            out.append(CROSS_RULE)
         return out
 
     def close(self):
@@ -232,15 +250,21 @@ def report_lines(judge, records):
     empty without thresholds)."""
     seqs = [s for _, s in records]
     five, tm_c, hits = measure_records(judge, seqs)
-    lines = ["\t".join(COLUMNS + (("verdict",) if judge.thresholds else ()))]
+    cross = partner = None
+    if judge.cross_dimer:
+        cross, partner = cross_dimer.measure(seqs)
+    lines = ["\t".join(COLUMNS + (CROSS_COLUMNS if judge.cross_dimer else ()) + (("verdict",) if judge.thresholds else ()))]
     failed = []
     for i, (name, s) in enumerate(records):
         row = [name, str(len(s))] + [str(int(v)) for v in five[i]]
         row.append("NA" if tm_c[i] is None else str(tm_c[i]))
         row.append("NA" if hits is None else str(int(hits[i])))
+        if cross is not None:
+            row += [str(int(cross[i])), str(int(partner[i]) + 1) if cross[i] > 0 else "NA"]
         bad = []
         if judge.thresholds:
-            bad = judge.failed(len(s), [int(v) for v in five[i]], tm_c[i], 0 if hits is None else int(hits[i]))
+            bad = judge.failed(len(s), [int(v) for v in five[i]], tm_c[i], 0 if hits is None else int(hits[i]),
+                               0 if cross is None else int(cross[i]))
             row.append(",".join(bad) if bad else "ok")
         failed.append(bad)
         lines.append("\t".join(row))
