@@ -287,6 +287,15 @@ CROSS_PROTOTYPES = {
         c_vp, c_u8p, c_i64p, ctypes.c_int64, ctypes.c_int32, c_vpp, c_i64p]),
 }
 
+# the entry points of include/catchhip_redesign.h, bound like the ones above
+REDESIGN_PROTOTYPES = {
+    "catchhip_cross_against": (ctypes.c_int, [
+        c_vp, c_u8p, c_i64p, ctypes.c_int64, c_u8p, c_i64p, ctypes.c_int64, c_i32p, c_i32p]),
+    "catchhip_cross_against_flags": (ctypes.c_int, [
+        c_vp, c_u8p, c_i64p, ctypes.c_int64, c_u8p, c_i64p, ctypes.c_int64, ctypes.c_int32, c_u8p]),
+    "catchhip_rows_drop_sets": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_u8p, c_vpp, c_i64p]),
+}
+
 _lib = None
 
 
@@ -305,7 +314,8 @@ def lib():
                 "`make -C catch_amd/csrc`.  There is no CPU fallback."
                 % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(CROSS_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(CROSS_PROTOTYPES.items()) \
+                + list(REDESIGN_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

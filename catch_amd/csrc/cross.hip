@@ -32,9 +32,13 @@
 //
 // The graph entry is the same kernel with the threshold fixed at `above` and an exit at the first run beyond it; its
 // hits are bits of the adjacency bitmap, collected per tile in LDS, and the graph is redundant.hip's from there.
+//
+// One list against another (catchhip_cross_against / _flags) is at the end of the file: the same planes and the same
+// cd_pair, a tile of B held against the stream of A's tiles.
 #include <algorithm>
 
 #include "../../include/catchhip_cross.h"
+#include "../../include/catchhip_redesign.h"
 #include "redgraph.h"
 
 #define CD_MAXN (RG_TILE * 16384)      // records of one catchhip_cross_dimer call: 16,384 tiles a side
@@ -386,4 +390,171 @@ extern "C" int catchhip_cross_dimer_graph(catchhip_ctx *ctx, const u8 *bytes, co
     if (nedges) *nedges = G->nedges;
     *out = G.release();
     return 0;
+}
+
+// ---- one list against another (catchhip_cross_against / _flags; include/catchhip_redesign.h) --------------------------
+// cross_against(b, A) = max over a in A of run(b, a), nothing exempted.  A block owns one tile of 64 records of B,
+// staged once on the reversed (column) side, and streams a range of A's tiles through the plain (row) side with the
+// one-list kernel's skewed order: step k pairs column `lane` with row (lane + k) mod 64, a wave taking 16 steps of
+// every tile.  A column's best (a key as above, the partner an index into A) or flag lives in LDS for the whole
+// stream and goes out once at the end: by atomic maximum, since gridDim.y blocks share a B tile when B alone would not
+// fill the device (block y takes A's tiles y * per .. ), or as a byte that is only ever written as 1.  What a block
+// searches depends on the keys it read; the maximum, and the smallest partner of equal values, do not.
+// FLAGS: the threshold is `above` throughout, a pair ends at its first run beyond it, a flagged column is skipped and
+// a tile whose columns are all flagged leaves the stream.
+template <int W, bool FLAGS>
+__global__ void __launch_bounds__(RG_BLOCK)
+cd_against_kernel(const u64 *__restrict__ a_fwd, const u32 *__restrict__ a_lens, u32 na, u32 a_npad, u32 a_tiles, u32 per,
+                  const u64 *__restrict__ b_rev, const u32 *__restrict__ b_lens, u32 nb, u32 b_npad, i32 above,
+                  unsigned long long *best, u8 *flag) {
+    const u32 tb = blockIdx.x;
+    const u32 t_lo = blockIdx.y * per, t_hi = t_lo + per < a_tiles ? t_lo + per : a_tiles;
+    if (t_lo >= t_hi) return;
+    __shared__ u64 s_pl[2][3][2 * W][RG_TILE];
+    __shared__ u32 s_len[2][RG_TILE];
+    __shared__ unsigned long long s_acc[RG_TILE];
+    for (u32 t = threadIdx.x; t < 3 * 2 * W * RG_TILE; t += RG_BLOCK) {
+        const u32 pr = t % RG_TILE, w = (t / RG_TILE) % (2 * W), pl = t / (RG_TILE * 2 * W);
+        s_pl[1][pl][w][pr] = w < (u32)W ? b_rev[((size_t)(pl * W + w)) * b_npad + tb * RG_TILE + pr] : 0ull;   // < b_npad
+    }
+    if (threadIdx.x < RG_TILE) {
+        const u32 g = tb * RG_TILE + threadIdx.x;
+        s_len[1][threadIdx.x] = b_lens[g];
+        s_acc[threadIdx.x] = FLAGS ? 0ull : __hip_atomic_load(best + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 gb = tb * RG_TILE + lane;
+    for (u32 ta = t_lo; ta < t_hi; ++ta) {
+        for (u32 t = threadIdx.x; t < 3 * 2 * W * RG_TILE; t += RG_BLOCK) {
+            const u32 pr = t % RG_TILE, w = (t / RG_TILE) % (2 * W), pl = t / (RG_TILE * 2 * W);
+            s_pl[0][pl][w][pr] = w < (u32)W ? a_fwd[((size_t)(pl * W + w)) * a_npad + ta * RG_TILE + pr] : 0ull;   // < a_npad
+        }
+        if (threadIdx.x < RG_TILE) s_len[0][threadIdx.x] = a_lens[ta * RG_TILE + threadIdx.x];
+        __syncthreads();
+        const int lb = (int)s_len[1][lane];
+        for (u32 k = wave * (RG_TILE * 64 / RG_BLOCK); k < (wave + 1) * (RG_TILE * 64 / RG_BLOCK); ++k) {
+            const u32 r = (lane + k) & (RG_TILE - 1);
+            const u32 ga = ta * RG_TILE + r;
+            if (!(ga < na && gb < nb)) continue;
+            const unsigned long long mine = __hip_atomic_load(&s_acc[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (FLAGS && mine) continue;
+            const int t = FLAGS ? above : cd_threshold(mine, ga);
+            const int v = cd_pair<W, FLAGS>(&s_pl[0][0][0][r], &s_pl[1][0][0][lane], (int)s_len[0][r], lb, t);
+            if (v <= t) continue;
+            if (FLAGS) __hip_atomic_store(&s_acc[lane], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else atomicMax(&s_acc[lane], ((unsigned long long)(u32)v << 32) | (unsigned long long)(0xFFFFFFFFu - ga));
+        }
+        // (the barrier in front of the next tile's staging; a flag set behind this read costs one more tile, no more)
+        const int done = FLAGS && (gb >= nb || __hip_atomic_load(&s_acc[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        if (__syncthreads_and(done)) break;
+    }
+    __syncthreads();
+    if (threadIdx.x < RG_TILE) {
+        const u32 g = tb * RG_TILE + threadIdx.x;
+        const unsigned long long acc = s_acc[threadIdx.x];
+        if (g < nb && acc) {
+            if (FLAGS) flag[g] = 1;
+            else atomicMax(&best[g], acc);
+        }
+    }
+}
+
+#define CA_MAXN ((i64)1 << 30)         // records of either list: the padded count and the tiles stay 32-bit
+// Blocks wanted before A's range is split no further: 256 CUs hold 8 blocks of 256 threads each, and blocks end at
+// uneven times (the early exits), so the device is level only with several rounds of them -- at 1,563 B tiles and one
+// range a CU got 6 or 7 blocks, each as long as the whole stream of A: 1.63 x 10^9 pairs/s for the flags of 100,000
+// random 100-mers against 1,000, 2.07 x 10^9 at the 6 ranges this asks for (tools/cross_against_profile.py).
+#define CA_FILL 8192
+
+template <int W>
+static void ca_launch(hipStream_t s, dim3 grid, bool flags, const CdInput &A, u32 na, u32 per, const CdInput &B, u32 nb,
+                      i32 above, unsigned long long *best, u8 *flag) {
+    if (flags)
+        hipLaunchKernelGGL((cd_against_kernel<W, true>), grid, dim3(RG_BLOCK), 0, s, (const u64 *)A.fwd.p, (const u32 *)A.lens.p,
+                           na, (u32)A.npad, (u32)A.tiles, per, (const u64 *)B.rev.p, (const u32 *)B.lens.p, nb, (u32)B.npad,
+                           above, best, flag);
+    else
+        hipLaunchKernelGGL((cd_against_kernel<W, false>), grid, dim3(RG_BLOCK), 0, s, (const u64 *)A.fwd.p, (const u32 *)A.lens.p,
+                           na, (u32)A.npad, (u32)A.tiles, per, (const u64 *)B.rev.p, (const u32 *)B.lens.p, nb, (u32)B.npad,
+                           above, best, flag);
+}
+
+// both entries: checks, both lists packed with one W, the stream of A's tiles; value / partner or flag on the host
+static int ca_run(catchhip_ctx *ctx, const char *who, const u8 *b_bytes, const i64 *b_off, i64 nb, const u8 *a_bytes,
+                  const i64 *a_off, i64 na, bool flags, i32 above, i32 *value, i32 *partner, u8 *flag) {
+    if (flags && above < 1) {
+        chip_set_error("%s: the threshold must be at least 1 (%d)", who, above);
+        return CATCHHIP_EINVAL;
+    }
+    if (na > CA_MAXN || nb > CA_MAXN) {
+        chip_set_error("%s: %lld records against %lld; one call takes at most %lld in a list", who, (long long)nb,
+                       (long long)na, (long long)CA_MAXN);
+        return CATCHHIP_EINVAL;
+    }
+    CdInput A, B;
+    TRY(cd_check(who, b_off, nb, &B.W));
+    TRY(cd_check(who, a_off, na, &A.W));
+    for (i64 i = 0; i < nb; ++i) {                           // an empty A, or nothing to ask
+        if (flags) flag[i] = 0;
+        else { value[i] = 0; partner[i] = -1; }
+    }
+    if (na == 0 || nb == 0) return 0;
+    A.W = B.W = std::max(A.W, B.W);
+    HIP_TRY(hipSetDevice(ctx->device));
+    PoolScope pool_scope(ctx);
+    hipStream_t s = ctx->stream;
+    const i64 b_npad = div_up(nb, RG_TILE) * RG_TILE;
+    DevBuf<unsigned long long> best;
+    DevBuf<i32> d_out;
+    DevBuf<u8> d_flag;
+    if (flags) {
+        TRY(d_flag.alloc((size_t)b_npad));
+        HIP_TRY(hipMemsetAsync(d_flag.p, 0, (size_t)b_npad, s));
+    } else {
+        TRY(best.alloc((size_t)b_npad));
+        TRY(d_out.alloc((size_t)2 * nb));
+        HIP_TRY(hipMemsetAsync(best.p, 0, sizeof(unsigned long long) * (size_t)b_npad, s));
+    }
+    TRY(cd_stage(ctx, a_bytes, a_off, na, &A));
+    TRY(cd_stage(ctx, b_bytes, b_off, nb, &B));
+    // A's tiles in gridDim.y ranges of `per`: one range while B's tiles fill the device by themselves
+    const i64 want = std::min<i64>(std::min<i64>(A.tiles, 65535), std::max<i64>(1, div_up((i64)CA_FILL, B.tiles)));
+    const u32 per = (u32)div_up(A.tiles, want);
+    const dim3 grid((unsigned)B.tiles, (unsigned)div_up(A.tiles, (i64)per));
+    PhaseTimer timer(ctx, PHASE_NDF);
+    hipLaunchKernelGGL(cd_pack_kernel, dim3((unsigned)div_up(na, 256)), dim3(256), 0, s, (const u8 *)A.d_bytes.p,
+                       (const i64 *)A.d_off.p, (u32)na, (u32)A.npad, A.W, A.fwd.p, A.rev.p, A.lens.p);
+    hipLaunchKernelGGL(cd_pack_kernel, dim3((unsigned)div_up(nb, 256)), dim3(256), 0, s, (const u8 *)B.d_bytes.p,
+                       (const i64 *)B.d_off.p, (u32)nb, (u32)B.npad, B.W, B.fwd.p, B.rev.p, B.lens.p);
+    if (A.W == 1) ca_launch<1>(s, grid, flags, A, (u32)na, per, B, (u32)nb, above, best.p, d_flag.p);
+    else if (A.W == 2) ca_launch<2>(s, grid, flags, A, (u32)na, per, B, (u32)nb, above, best.p, d_flag.p);
+    else ca_launch<4>(s, grid, flags, A, (u32)na, per, B, (u32)nb, above, best.p, d_flag.p);
+    if (!flags)
+        hipLaunchKernelGGL(cd_result_kernel, dim3((unsigned)div_up(nb, 256)), dim3(256), 0, s,
+                           (const unsigned long long *)best.p, (u32)nb, d_out.p, d_out.p + nb);
+    timer.launch(flags ? 3 : 4);
+    timer.stop();
+    HIP_TRY(hipGetLastError());
+    if (flags) {
+        HIP_TRY(hipMemcpyAsync(flag, d_flag.p, (size_t)nb, hipMemcpyDeviceToHost, s));
+    } else {
+        HIP_TRY(hipMemcpyAsync(value, d_out.p, sizeof(i32) * (size_t)nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(partner, d_out.p + nb, sizeof(i32) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    timer.finish();
+    return 0;
+}
+
+extern "C" int catchhip_cross_against(catchhip_ctx *ctx, const u8 *b_bytes, const i64 *b_off, i64 nb, const u8 *a_bytes,
+                                      const i64 *a_off, i64 na, i32 *value, i32 *partner) {
+    ARG_CHECK(ctx && na >= 0 && nb >= 0 && (nb == 0 || (b_bytes && b_off && value && partner)) &&
+              (na == 0 || (a_bytes && a_off)));
+    return ca_run(ctx, "cross_against", b_bytes, b_off, nb, a_bytes, a_off, na, false, 0, value, partner, nullptr);
+}
+
+extern "C" int catchhip_cross_against_flags(catchhip_ctx *ctx, const u8 *b_bytes, const i64 *b_off, i64 nb, const u8 *a_bytes,
+                                            const i64 *a_off, i64 na, i32 above, u8 *flag) {
+    ARG_CHECK(ctx && na >= 0 && nb >= 0 && (nb == 0 || (b_bytes && b_off && flag)) && (na == 0 || (a_bytes && a_off)));
+    return ca_run(ctx, "cross_against_flags", b_bytes, b_off, nb, a_bytes, a_off, na, true, above, nullptr, nullptr, flag);
 }

@@ -13,6 +13,7 @@
 // own and the sets that leave the table whole.
 #include <algorithm>
 
+#include "../../include/catchhip_redesign.h"
 #include "rows_host.h"
 #include "spans.h"
 #include "wave.h"
@@ -222,6 +223,109 @@ int chip_rows_cut(catchhip_ctx *ctx, const catchhip_rows *R0, const unsigned lon
         R->lmax = (u32)longest;
     }
     return 0;
+}
+
+// ---- rows without some sets (catchhip_rows_drop_sets; include/catchhip_redesign.h) -----------------------------------
+// No row is cut: a row stays or goes with its set, so count / scan / emit move whole rows and need no bitmap.
+// cnt[r] = 1 iff row r stays; info[0] += the rows that stay, info[2] = 1 if a row's set id is not below num_sets
+__global__ void __launch_bounds__(256)
+drop_count_kernel(const i32 *__restrict__ set_id, const u32 *__restrict__ gs, const u32 *__restrict__ ge, u32 n,
+                  const u8 *__restrict__ drop, u32 num_sets, u32 *__restrict__ cnt, unsigned long long *__restrict__ info) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    u32 c = 0;
+    if (r < n) {
+        const u32 sid = (u32)set_id[r];
+        if (sid >= num_sets) info[2] = 1ull;                 // (every writer writes 1)
+        else c = (ge[r] > gs[r] && !drop[sid]) ? 1u : 0u;
+        cnt[r] = c;
+    }
+    const unsigned long long t = wave_sum((unsigned long long)c);
+    if ((threadIdx.x & 63u) == 0 && t) atomicAdd(&info[0], t);
+}
+
+// row r to row pos[r] of the output where cnt[r]; lengths into gain0[set], the longest into info[1]
+__global__ void __launch_bounds__(256)
+drop_emit_kernel(const i32 *__restrict__ set_id, const i32 *__restrict__ univ, const u32 *__restrict__ gs,
+                 const u32 *__restrict__ ge, u32 n, const u32 *__restrict__ cnt, const u32 *__restrict__ pos, u32 cap,
+                 i32 *__restrict__ o_set, i32 *__restrict__ o_univ, u32 *__restrict__ o_gs, u32 *__restrict__ o_ge,
+                 u32 *__restrict__ gain0, u32 ng, unsigned long long *__restrict__ info) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    u32 longest = 0;
+    if (r < n && cnt[r]) {
+        const u32 o = pos[r], s = gs[r], e = ge[r];
+        const i32 sid = set_id[r];
+        if (o < cap) { o_set[o] = sid; o_univ[o] = univ[r]; o_gs[o] = s; o_ge[o] = e; }
+        if (gain0 && (u32)sid < ng) atomicAdd(&gain0[(u32)sid], e - s);
+        longest = e - s;
+    }
+    longest = wave_max(longest);
+    if ((threadIdx.x & 63u) == 0 && longest) atomicMax(&info[1], (unsigned long long)longest);
+}
+
+extern "C" int catchhip_rows_drop_sets(catchhip_ctx *ctx, const catchhip_rows *R0, i64 num_sets, const u8 *drop,
+                                       catchhip_rows **out, i64 *nrows) {
+    ARG_CHECK(ctx && R0 && out);
+    ARG_CHECK(R0->ctx == ctx);
+    *out = nullptr;
+    if (nrows) *nrows = 0;
+    ARG_CHECK(num_sets >= 0 && num_sets < ((i64)1 << 31) && (num_sets == 0 || drop));
+    TRY(chip_rows_form_check(R0, "rows_drop_sets", "the rows"));
+    TRY(chip_rows_limits_check("rows_drop_sets", R0->total, R0->n));
+    PoolScope pool_scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    DerivedRows D(ctx, R0);
+    TRY(D.err);
+    catchhip_rows *R = D.R.get();
+    if (R0->n == 0) {                                        // nothing to drop from
+        TRY(D.copy_of(R0));
+        return D.finish(out, nrows);
+    }
+    const u32 n0 = (u32)R0->n;
+    DevBuf<u8> d_drop;
+    DevBuf<unsigned long long> info;
+    DevBuf<u32> cnt, pos, scan_tmp;
+    TRY(d_drop.alloc((size_t)num_sets + 1));
+    TRY(info.alloc(3));
+    TRY(cnt.alloc(n0));
+    TRY(pos.alloc(n0));
+    if (num_sets) HIP_TRY(hipMemcpyAsync(d_drop.p, drop, (size_t)num_sets, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(info.p, 0, sizeof(unsigned long long) * 3, s));
+    const dim3 grid((unsigned)div_up(n0, 256)), blk(256);
+    hipLaunchKernelGGL(drop_count_kernel, grid, blk, 0, s, (const i32 *)R0->set_id.p, (const u32 *)R0->gs.p,
+                       (const u32 *)R0->ge.p, n0, (const u8 *)d_drop.p, (u32)num_sets, cnt.p, info.p);
+    TRY(chip_exclusive_scan_u32(ctx, cnt.p, pos.p, n0, scan_tmp));
+    D.tm.launch(2);
+    HIP_TRY(hipGetLastError());
+    unsigned long long head[3] = {0, 0, 0};                  // (also: `drop` is the caller's again)
+    TRY(chip_read_back(ctx, info.p, sizeof(head), head));
+    if (head[2]) {
+        chip_set_error("rows_drop_sets: a row's set id is not below the %lld flags given", (long long)num_sets);
+        return CATCHHIP_EINVAL;
+    }
+    const u32 cap = (u32)head[0], ng = R0->gain0_n;
+    if (ng) {                                                // carried whatever stays
+        TRY(R->gain0.alloc(ng));
+        HIP_TRY(hipMemsetAsync(R->gain0.p, 0, sizeof(u32) * (size_t)ng, s));
+        R->gain0_n = ng;
+    }
+    if (cap) {
+        TRY(chip_rows_alloc_soa(R, cap));
+        hipLaunchKernelGGL(drop_emit_kernel, grid, blk, 0, s, (const i32 *)R0->set_id.p, (const i32 *)R0->univ.p,
+                           (const u32 *)R0->gs.p, (const u32 *)R0->ge.p, n0, (const u32 *)cnt.p, (const u32 *)pos.p, cap,
+                           R->set_id.p, R->univ.p, R->gs.p, R->ge.p, ng ? R->gain0.p : (u32 *)nullptr, ng, info.p);
+        D.tm.launch(1);
+        HIP_TRY(hipGetLastError());
+        unsigned long long longest = 0;
+        D.tm.stop();
+        TRY(chip_read_back(ctx, info.p + 1, sizeof(longest), &longest));
+        R->n = (i64)cap;
+        R->lmax = (u32)longest;
+    } else {
+        D.tm.stop();
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return D.finish(out, nrows);
 }
 
 extern "C" int catchhip_rows_subtract(catchhip_ctx *ctx, const catchhip_rows *R0, const catchhip_rows *C,

@@ -49,6 +49,10 @@ hybridises to as well: targets filed in mixed orientations get one probe set.
 kept one, one CrossDimerFilter right after the set cover filter over the picks
 of all datasets (catch_amd/filter/cross_dimer.py has the rule); --cross-dimer
 adds its two columns to --write-probe-report.
+--cross-dimer-redesign (nor this; with --max-cross-dimer) designs around the
+conflicts instead: the set cover filter never offers a candidate that anneals
+to a kept or an existing probe and covers again what a dropped pick would have
+covered, in at most --cross-dimer-rounds solves per dataset.
 --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
@@ -158,6 +162,23 @@ def parse_args(argv=None, args_type="basic"):
     background_filter.add_arguments(p)      # --background, --background-..., --write-background-histogram (not in the reference)
     quality.add_arguments(p)                # --write-candidate-profile (not in the reference)
     cross_dimer.add_arguments(p)            # --cross-dimer, --max-cross-dimer (not in the reference)
+    p.add_argument("--cross-dimer-redesign", action="store_true",
+                   help="with --max-cross-dimer X: instead of dropping "
+                        "conflicting probes behind the set cover, design "
+                        "around them.  Candidates that anneal to a probe "
+                        "already kept (of any dataset, or of --extend-probes) "
+                        "over more than X bases are never offered to the set "
+                        "cover; its picks are walked in pick order, a pick that "
+                        "conflicts with an earlier one is dropped for good, and "
+                        "the set cover runs again on what the kept picks leave "
+                        "uncovered, until no pick is dropped.  The output is "
+                        "free of conflicts and covers what the remaining "
+                        "candidates can cover "
+                        "(catch_amd/filter/set_cover_filter.py: _cross_rounds)")
+    p.add_argument("--cross-dimer-rounds", type=int, metavar="R",
+                   help="with --cross-dimer-redesign: at most R set cover "
+                        "solves per dataset (default 8); picks the last one "
+                        "drops stay dropped, with a warning")
     p.add_argument("--write-probe-report", metavar="FILE",
                    help="write what the designed probes are like to FILE: the "
                         "report python -m catch_amd.probe_report -f writes "
@@ -262,6 +283,23 @@ def parse_args(argv=None, args_type="basic"):
         if args.skip_set_cover:
             p.error("--max-cross-dimer cannot go with --skip-set-cover: it would pair all candidates with each "
                     "other, a quadratic pass")
+    if args.cross_dimer_redesign and args.max_cross_dimer is None:
+        p.error("--cross-dimer-redesign needs --max-cross-dimer X: the threshold of a conflict")
+    if args.cross_dimer_rounds is not None:
+        if not args.cross_dimer_redesign:
+            p.error("--cross-dimer-rounds needs --cross-dimer-redesign")
+        if args.cross_dimer_rounds < 1:
+            p.error("--cross-dimer-rounds must be at least 1, not %d" % args.cross_dimer_rounds)
+    if args.cross_dimer_redesign:
+        for given, opt in ((args.coverage_depth > 1, "--coverage-depth above 1"),
+                           (args.prune_redundant, "--prune-redundant"),
+                           (args.max_probes is not None, "--max-probes"),
+                           (bool(args.write_coverage_curve), "--write-coverage-curve")):
+            if given:
+                p.error("--cross-dimer-redesign cannot go with %s: the repair rounds are one greedy cover each, "
+                        "without a second look at the picks" % opt)
+        if args.cross_dimer_rounds is None:
+            args.cross_dimer_rounds = 8
     return args
 
 
@@ -429,6 +467,19 @@ def main(args):
                              "--cluster-from-fragments (a default of "
                              "design_large.py): nothing is clustered; set "
                              "--cluster-from-fragments to 0 as well"))
+    if args.cross_dimer_redesign:
+        if args.cluster_and_design_separately:
+            raise Exception(("Cannot use --cross-dimer-redesign with "
+                             "--cluster-and-design-separately (a default of "
+                             "design_large.py): the repair rounds run on each "
+                             "dataset as a whole; set "
+                             "--cluster-and-design-separately to 0 (and, where "
+                             "it is set, --cluster-from-fragments to 0 too)"))
+        if args.cluster_from_fragments:
+            raise Exception(("Cannot use --cross-dimer-redesign with "
+                             "--cluster-from-fragments (a default of "
+                             "design_large.py): nothing is clustered; set "
+                             "--cluster-from-fragments to 0 as well"))
     from catch_amd import target_regions
     if target_regions.given(args):
         opt = "--target-regions" if args.target_regions else "--exclude-regions"
@@ -578,10 +629,14 @@ def main(args):
         prune_redundant=args.prune_redundant,
         max_probes=args.max_probes, pick_gains=want_gains,
         curve_points=args.coverage_curve_points,
-        target_regions=regions, either_strand=args.either_strand)
+        target_regions=regions, either_strand=args.either_strand,
+        **(dict(max_cross_dimer=args.max_cross_dimer, cross_dimer_rounds=args.cross_dimer_rounds)
+           if args.cross_dimer_redesign else {}))
     filters.append(scf)
     cross = None
-    if args.max_cross_dimer is not None:    # (not in the reference) one filter over the picks of all datasets
+    # (not in the reference) one filter over the picks of all datasets; under --cross-dimer-redesign the set cover
+    # filter keeps its picks free of conflicts itself
+    if args.max_cross_dimer is not None and not args.cross_dimer_redesign:
         cross = cross_dimer.CrossDimerFilter(args.max_cross_dimer)
         filters.append(cross)
     if args.add_adapters:      # bin/design.py:345-365 (default sequences :350, :354)
@@ -640,6 +695,11 @@ def main(args):
     if cross is not None:
         logger.info("cross-dimer filter: %d of %d probes dropped (largest cross-dimer %d before, %d after)",
                     cross.dropped, cross.seen, cross.largest_before, cross.largest_after)
+    if args.cross_dimer_redesign:
+        for gi, fn in enumerate(args.dataset):
+            logger.info("%s: cross-dimer redesign: %d rounds, %d candidates banned, %d picks dropped, %d probes kept",
+                        os.path.basename(fn), scf.last_cross_rounds[gi], scf.last_cross_banned[gi],
+                        scf.last_cross_dropped[gi], scf.last_cross_kept[gi])
     if regions is not None:
         for gi, fn in enumerate(args.dataset):
             coverable = scf.last_coverable_bases[gi] if gi < len(scf.last_coverable_bases) else 0

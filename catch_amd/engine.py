@@ -1215,6 +1215,22 @@ class Rows:
             int(pk.size), int(depth), ctypes.byref(h), ctypes.byref(n), _ptr(reached, c_i64p)))
         return Rows(self.ctx, h, n.value, ng), reached[:ng]
 
+    def drop_sets(self, num_sets, drop):
+        """catchhip_rows_drop_sets: these rows without those of the sets s with
+        drop[s] set (one flag per set id, num_sets of them) -- order and set ids
+        kept, ready for greedy(), subtract() and below_depth()."""
+        num_sets = int(num_sets)
+        flags = np.ascontiguousarray(np.asarray(drop) != 0, dtype=np.uint8)
+        if flags.ndim != 1 or flags.size != num_sets:
+            raise ValueError("drop_sets: %d flags for %d sets" % (flags.size, num_sets))
+        if num_sets == 0:
+            flags = np.zeros(1, dtype=np.uint8)
+        h = ctypes.c_void_p()
+        n = ctypes.c_int64(0)
+        check(self.ctx._L.catchhip_rows_drop_sets(
+            self.ctx._h, self._h, num_sets, _ptr(flags, c_u8p), ctypes.byref(h), ctypes.byref(n)))
+        return Rows(self.ctx, h, n.value, self.ngenomes)
+
     def prune(self, num_sets, picks, depth=1, fixed=None):
         """catchhip_rows_prune -> (kept, removed): the picks (set ids in pick
         order) examined from the last to the first, one removed whenever every
@@ -1490,6 +1506,37 @@ def cross_dimer(ctx, strs):
     check(ctx._L.catchhip_cross_dimer(
         ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), n, _ptr(values, c_i32p), _ptr(partners, c_i32p)))
     return values[:n], partners[:n]
+
+
+def cross_against(ctx, bs, as_):
+    """catchhip_cross_against -> (values int32[len(bs)], partners
+    int32[len(bs)]): for every record of `bs` the longest antiparallel pairing
+    with a record of `as_` (an equal record included) and the smallest index
+    into `as_` that reaches it, -1 where the value is 0
+    (catch_amd/filter/cross_dimer.py has the definition)."""
+    b_buf, b_off = _concat_records(bs)
+    a_buf, a_off = _concat_records(as_)
+    nb = b_off.size - 1
+    values = np.zeros(max(nb, 1), dtype=np.int32)
+    partners = np.full(max(nb, 1), -1, dtype=np.int32)
+    check(ctx._L.catchhip_cross_against(
+        ctx._h, _ptr(b_buf, c_u8p), _ptr(b_off, c_i64p), nb, _ptr(a_buf, c_u8p), _ptr(a_off, c_i64p),
+        a_off.size - 1, _ptr(values, c_i32p), _ptr(partners, c_i32p)))
+    return values[:nb], partners[:nb]
+
+
+def cross_against_flags(ctx, bs, as_, above):
+    """catchhip_cross_against_flags -> bool[len(bs)]: whether the record of
+    `bs` pairs with some record of `as_` over more than `above` (>= 1)
+    consecutive bases."""
+    b_buf, b_off = _concat_records(bs)
+    a_buf, a_off = _concat_records(as_)
+    nb = b_off.size - 1
+    flags = np.zeros(max(nb, 1), dtype=np.uint8)
+    check(ctx._L.catchhip_cross_against_flags(
+        ctx._h, _ptr(b_buf, c_u8p), _ptr(b_off, c_i64p), nb, _ptr(a_buf, c_u8p), _ptr(a_off, c_i64p),
+        a_off.size - 1, int(above), _ptr(flags, c_u8p)))
+    return flags[:nb].astype(bool)
 
 
 class Shard:

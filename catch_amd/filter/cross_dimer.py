@@ -190,6 +190,82 @@ def walk(seqs, above):
     return keep
 
 
+# ---------------------------------------------------------------- one list against another
+def cross_against(b, A):
+    """(value, partner) from the quantifiers: the maximum of run(b, a) over the
+    records a of the list A (0 for an empty A) and the smallest index into A
+    that reaches it (-1 when the value is 0).  A member of A equal to b is a
+    partner like any other -- the value is then run(b, b); nothing is
+    exempted."""
+    best, who = 0, -1
+    for j, a in enumerate(A):
+        r = run(b, a)
+        if r > best:
+            best, who = r, j
+    return best, who
+
+
+def conflicts_with(b, A, above):
+    """Whether record b pairs with some record of A over more than `above` bases."""
+    return cross_against(b, A)[0] > above
+
+
+def cross_against_numpy(bs, as_):
+    """cross_against of every record of `bs` as (values int32[nb], partners
+    int32[nb]): run_rows' DP over the nb * na ordered pairs, a bounded number
+    of cells at a time -- the host path."""
+    bs, as_ = list(bs), list(as_)
+    nb, na = len(bs), len(as_)
+    values = np.zeros(nb, dtype=np.int32)
+    partners = np.full(nb, -1, dtype=np.int32)
+    if nb == 0 or na == 0:
+        return values, partners
+    d = _digits(as_)
+    L = d.shape[1]
+    wants = np.where(d >= 0, 3 - d, -2).astype(np.int8)
+    order = np.argsort([len(s) for s in bs], kind="stable")     # (a chunk walks as far as its longest record)
+    step = max(1, _CHUNK_CELLS // (na * (L + 1)))
+    for lo in range(0, nb, step):
+        rows = order[lo:lo + step]
+        mine = _digits([bs[i] for i in rows])
+        cells = np.zeros((len(rows), na, L + 1), dtype=np.int16)
+        best = np.zeros((len(rows), na), dtype=np.int16)
+        for x in range(_longest(mine)):
+            m = wants[None, :, :] == mine[:, x][:, None, None]
+            cells[:, :, :L] = (cells[:, :, 1:] + 1) * m
+            np.maximum(best, cells[:, :, :L].max(axis=2), out=best)
+        values[rows] = best.max(axis=1)
+        partners[rows] = np.where(values[rows] > 0, best.argmax(axis=1), -1)     # (argmax: the first of equals)
+    return values, partners
+
+
+def measure_against(bs, as_):
+    """cross_against of every record of `bs` against the list `as_`, (values
+    int32[nb], partners int32[nb]): on the device (engine.cross_against), or on
+    the host path when CATCHHIP_HOST_FRONT_END=1 is set or a record of either
+    list is longer than 256 characters -- the same values."""
+    bs, as_ = list(bs), list(as_)
+    if not bs or not as_:
+        return np.zeros(len(bs), dtype=np.int32), np.full(len(bs), -1, dtype=np.int32)
+    if _on_host(bs + as_):
+        return cross_against_numpy(bs, as_)
+    from catch_amd import engine
+    return engine.cross_against(engine.default_context(), bs, as_)
+
+
+def flags_against(bs, as_, above):
+    """bool[nb]: conflicts_with(b, as_, above) for every record of `bs`, on the
+    device (engine.cross_against_flags) or on the host path, as measure_against
+    chooses."""
+    bs, as_ = list(bs), list(as_)
+    if not bs or not as_:
+        return np.zeros(len(bs), dtype=bool)
+    if _on_host(bs + as_):
+        return cross_against_numpy(bs, as_)[0] > above
+    from catch_amd import engine
+    return engine.cross_against_flags(engine.default_context(), bs, as_, above)
+
+
 # ---------------------------------------------------------------- the filter
 def _threshold(x, what="max_cross_dimer"):
     x = _int(x, what)
@@ -269,10 +345,10 @@ def add_arguments(p):
                         "clusters as one list, are walked in output order and "
                         "a probe is dropped when it conflicts with a kept "
                         "earlier one; bases that only dropped probes covered "
-                        "become uncovered (nothing is redesigned: "
-                        "--write-uncovered-regions and --print-analysis show "
-                        "the cost, --extend-probes on the kept set is the "
-                        "manual route)")
+                        "become uncovered (--write-uncovered-regions and "
+                        "--print-analysis show the cost; the design commands' "
+                        "--cross-dimer-redesign designs around the conflicts "
+                        "instead)")
 
 
 def check_args(args, error):

@@ -23,6 +23,9 @@ everything above then works on wanted bases only.  `either_strand` (a keyword)
 makes a candidate cover what its own string OR its reverse complement
 hybridises to: a second scan of the reverse-complemented strings against the
 same targets and the union of the two row tables, set by set (Rows.union).
+`max_cross_dimer` / `cross_dimer_rounds` (keywords) keep the selection, over all
+groups and beside the fixed probes, free of probes that anneal to each other,
+and cover again what a conflicting pick would have covered (_cross_rounds).
 
 Not supported (raises NotImplementedError): custom hybridization functions
 loaded from a Python file (`custom_cover_range_fn`, :288-299) -- an arbitrary
@@ -62,20 +65,23 @@ def _reverse_complement(s):
 class _KeywordsBeyondInit(type):
     """SetCoverFilter(..., fixed_probes=None, coverage_depth=1,
     prune_redundant=False, max_probes=None, pick_gains=False,
-    curve_points=100, target_regions=None, either_strand=False): everything after `fixed_probes` is a keyword of the CALL
+    curve_points=100, target_regions=None, either_strand=False,
+    max_cross_dimer=None, cross_dimer_rounds=8): everything after `fixed_probes` is a keyword of the CALL
     of the class, taken here and handed to the new object after __init__ ran.
     __init__ itself stays the reference's argument list followed by
     `fixed_probes`, the form its callers and the signature checks of the
     extension know; the others can only be given by name."""
 
     def __call__(cls, *args, coverage_depth=1, prune_redundant=False, max_probes=None, pick_gains=False,
-                 curve_points=100, target_regions=None, either_strand=False, **kwargs):
+                 curve_points=100, target_regions=None, either_strand=False, max_cross_dimer=None,
+                 cross_dimer_rounds=8, **kwargs):
         obj = super().__call__(*args, **kwargs)
         obj._set_either_strand(either_strand)
         obj._set_coverage_depth(coverage_depth)
         obj._set_prune_redundant(prune_redundant)
         obj._set_budget(max_probes, pick_gains, curve_points)
         obj._set_target_regions(target_regions)
+        obj._set_cross_dimer(max_cross_dimer, cross_dimer_rounds)
         return obj
 
 
@@ -161,6 +167,12 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         self.last_coverable_bases = []
         self.either_strand = False  # (SetCoverFilter(..., either_strand=True) sets it: _KeywordsBeyondInit)
         self._strand_scan = None    # what the last _scan_group did under either_strand (_either_strand_rows)
+        self.max_cross_dimer = None  # (SetCoverFilter(..., max_cross_dimer=X, cross_dimer_rounds=R): _KeywordsBeyondInit)
+        self.cross_dimer_rounds = 8
+        self.last_cross_rounds = []
+        self.last_cross_banned = []
+        self.last_cross_dropped = []
+        self.last_cross_kept = []
 
     def _set_either_strand(self, either_strand):
         """Whether a candidate covers a locus whichever strand of it was
@@ -220,6 +232,33 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                 "pick_gains / max_probes cannot be combined with coverage_depth > 1: "
                 "a gain is then no longer the bases covered first")
 
+    def _set_cross_dimer(self, max_cross_dimer, cross_dimer_rounds):
+        """The cross-dimer redesign (not an argument of the reference's class):
+        with max_cross_dimer = X >= 1 no two selected probes, of any group, and
+        no selected probe and fixed probe pair with each other over more than X
+        bases (catch_amd/filter/cross_dimer.py: conflicts_with), and what a
+        conflicting pick would have covered is covered again by other
+        candidates, in at most cross_dimer_rounds = R >= 1 solves per group
+        (_cross_rounds has the definition).  last_cross_rounds[group] = the
+        solves it took, last_cross_banned[group] = the candidates that were
+        never offered to a solve because they conflict with a kept probe or a
+        fixed one, last_cross_dropped[group] = the picks dropped,
+        last_cross_kept[group] = the probes selected."""
+        if max_cross_dimer is None:
+            self.max_cross_dimer = None
+            return
+        from catch_amd.filter import cross_dimer
+        x = cross_dimer._threshold(max_cross_dimer)
+        if (isinstance(cross_dimer_rounds, bool) or not isinstance(cross_dimer_rounds, (int, np.integer))
+                or cross_dimer_rounds < 1):
+            raise ValueError("cross_dimer_rounds must be an integer >= 1, not %r" % (cross_dimer_rounds,))
+        if self.coverage_depth > 1 or self.prune_redundant or self.pick_gains:
+            raise NotImplementedError(
+                "max_cross_dimer (the cross-dimer redesign) cannot be combined with coverage_depth > 1, "
+                "prune_redundant, pick_gains or max_probes")
+        self.max_cross_dimer = x
+        self.cross_dimer_rounds = int(cross_dimer_rounds)
+
     def _set_prune_redundant(self, prune_redundant):
         """Whether the picks are looked at again once the design is complete (not
         an argument of the reference's class): from the last pick to the first,
@@ -253,7 +292,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         scan (_filter_strs_keeping_rows): the fused scan-and-solve call and the
         device front end never hand the rows out."""
         return (bool(self.fixed_probes) or self.coverage_depth > 1 or self.prune_redundant or self.pick_gains
-                or self.target_regions is not None or self.either_strand)
+                or self.target_regions is not None or self.either_strand or self.max_cross_dimer is not None)
 
     def _anchor_table(self, strs, assume_unique=False, tolerant=False):
         """probe.anchor_table of `strs` under the strict hybridization model, or
@@ -585,6 +624,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                 "fixed probes (extending an existing probe set) run on one rank" if fixed else
                 "target regions run on one rank" if regions is not None else
                 "either_strand runs on one rank" if self.either_strand else
+                "the cross-dimer redesign (max_cross_dimer) runs on one rank" if self.max_cross_dimer is not None else
                 "coverage_depth > 1, prune_redundant, pick_gains and max_probes run on one rank")
         ctx = self._context()
         ngroups = len(input_strs)
@@ -607,6 +647,14 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
             self.last_wanted_bases = [0] * ngroups
             self.last_coverable_bases = [0] * ngroups
         budget = _Budget(self, ctx, ngroups, timings)
+        redesign = self.max_cross_dimer is not None
+        if redesign:
+            timings.update(ban_ms=0.0, ban_pairs=0, cross_rounds=0)
+            self.last_cross_rounds = [0] * ngroups
+            self.last_cross_banned = [0] * ngroups
+            self.last_cross_dropped = [0] * ngroups
+            self.last_cross_kept = [0] * ngroups
+            cross_kept = []          # K: the distinct strings kept so far, over all groups
         if fixed:
             fk, funiq, _fowner, fep, feo = self._anchor_table(self.fixed_probes)
             fixed_table = (fk, funiq, np.zeros(len(funiq), dtype=np.int32), fep, feo)    # one set: only their union matters
@@ -664,7 +712,12 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                     ranks = self._make_ranks_strs(strs, target_genomes_grouped, ctx)
                     rk = ranks if ranks.any() else None
                     ids, sizes = [], []
-                    for layer in range(1, self.coverage_depth + 1):
+                    if redesign:
+                        # (target regions at a coverage above 1: p counts the bases the OFFERED candidates can cover)
+                        ids = self._cross_rounds(ctx, gi, ngroups, strs, first, p, covered0, rk, ng, cross_kept, timings,
+                                                 coverable_of=rows if mask is not None and self.coverage > 1 else None)
+                        sizes = [len(ids)]
+                    for layer in range(1, 1 if redesign else self.coverage_depth + 1):
                         if layer == 1:
                             table, universe_p = first, first_p
                         else:
@@ -730,6 +783,135 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         held.remove(rows)
         rows.close()
         return cut
+
+    def _cross_rounds(self, ctx, gi, ngroups, strs, first, p, covered0, rk, ng, kept_all, timings, coverable_of=None):
+        """The repair rounds of one group under max_cross_dimer = X and
+        cross_dimer_rounds = R -> the group's selection, in the order kept.
+
+        E = the fixed probes' strings, K = `kept_all`, the distinct strings kept
+        so far over all groups (extended here), K_g its part kept for this
+        group, C_g = `strs`.  For round r = 0, 1, ...:
+
+          A_r     = the candidates of C_g, in order, that are not in K_g and do
+                    not conflict with a record of E ++ K (conflicts_with).
+          picks_r = what SetCoverFilter(the same model, fixed_probes=E ++ K_g)
+                    selects for the one group A_r, in pick order; with E and K_g
+                    empty that is the plain filter.
+          the walk: a pick is kept iff no pick kept earlier in THIS walk
+                    conflicts with it (none can conflict with E ++ K); the kept
+                    ones join K_g, and K unless already there.  A dropped pick
+                    conflicts with a member of K now and is never offered again.
+          the end:  picks_r is empty, or nothing was dropped, or r = R - 1 --
+                    then with a warning if the last walk dropped something.
+
+        So: no two probes of the output conflict and none conflicts with E.  With
+        X at or above the longest candidate nothing is banned or dropped and the
+        result is the plain design's.  Round 0 of a group with nothing banned
+        and nothing dropped IS the filter without the option: K of other groups
+        never counts as cover, only as a source of bans.  Every continuing round
+        drops a pick for good, so the loop ends without the cap, which bounds
+        time only.  A kept probe c with run(c, c) > X bans its own copies in
+        later groups (max_self_dimer in front removes such candidates); equal
+        strings are not exempted.
+
+        One scan per group: round r's table is derived on the device from
+        `first` (the group's rows, minus the fixed probes' when there are any):
+        Rows.below_depth(K_g's ids, 1) takes the kept picks out, cuts what they
+        cover and counts it (`reached`, which joins the fixed probes' covered0 in
+        extension_fraction), Rows.drop_sets takes the banned candidates out.
+        Set ids stay C_g's, so ties fall as they do among A_r.  The bans are
+        engine.cross_against_flags of C_g against what joined E ++ K since the
+        last look; the walk is the conflict graph's naive() -- both on the host
+        path (cross_dimer.cross_against_numpy, walk) under
+        CATCHHIP_HOST_FRONT_END=1 or with a record of more than 256 characters."""
+        from catch_amd.filter import cross_dimer
+        X, R = self.max_cross_dimer, self.cross_dimer_rounds
+        n = len(strs)
+        on_host = cross_dimer._on_host(list(strs) + self.fixed_probes + kept_all)
+        index_of = {}
+        for i, s in enumerate(strs):
+            index_of.setdefault(s, []).append(i)
+        known = set(kept_all)
+        banned = np.zeros(n, dtype=bool)
+        in_kg = np.zeros(n, dtype=bool)
+        kg_ids = []                      # every index of C_g that holds a string of K_g (equal strings: equal rows)
+        selected = []
+        pending = self.fixed_probes + kept_all      # what C_g has not been held against yet
+        base0 = np.zeros(ng, dtype=np.int64) if covered0 is None else np.asarray(covered0, dtype=np.int64)
+        rounds = dropped = 0
+        while True:
+            if pending:
+                if on_host:
+                    banned |= cross_dimer.cross_against_numpy(strs, pending)[0] > X
+                else:
+                    banned |= engine.cross_against_flags(ctx, strs, pending, X)
+                    timings["ban_ms"] += ctx.kernel_ms(engine.PHASE_NDF)[0]
+                timings["ban_pairs"] += n * len(pending)
+            offered_out = banned & ~in_kg
+            held = []
+            try:
+                table, reached = first, None
+                if kg_ids:
+                    table, reached = table.below_depth(n, kg_ids, 1)
+                    held.append(table)
+                if offered_out.any():
+                    table = table.drop_sets(n, offered_out)
+                    held.append(table)
+                q = p
+                if coverable_of is not None:
+                    left = coverable_of.drop_sets(n, banned | in_kg)
+                    held.append(left)
+                    q = [_bases_fraction(int(m), self.coverage) for m in left.stats(ng)[1]]
+                if reached is None and covered0 is None:
+                    universe_p = q       # (nothing is fixed and nothing kept: the plain instance)
+                else:
+                    c0 = base0 + (0 if reached is None else reached)
+                    universe_p = [extension_fraction(int(a), int(b), f) for a, b, f in zip(table.stats(ng)[1], c0, q)]
+                logger.info("Solving the set cover instance of group %d of %d, cross-dimer round %d",
+                            gi + 1, ngroups, rounds + 1)
+                picks = table.greedy(n, rk, _solver_fractions(universe_p)) if table.n else []
+                if table.n:
+                    _add_phase_times(timings, ctx, _GREEDY_PHASES)
+            finally:
+                for h in reversed(held):
+                    h.close()
+            rounds += 1
+            pick_strs = [strs[i] for i in picks]
+            if len(picks) < 2:
+                keep = np.ones(len(picks), dtype=bool)
+            elif on_host:
+                keep = cross_dimer.walk(pick_strs, X)
+            else:
+                graph = engine.RedundancyGraph.cross_dimer(ctx, pick_strs, X)
+                try:
+                    keep = graph.naive()
+                finally:
+                    graph.close()
+            pending = []
+            for i, s, k in zip(picks, pick_strs, keep):
+                if not k or in_kg[i]:    # (dropped, or an equal string was kept a moment ago: K_g holds distinct strings)
+                    continue
+                selected.append(i)
+                for j in index_of[s]:
+                    in_kg[j] = True
+                    kg_ids.append(j)
+                if s not in known:
+                    known.add(s)
+                    kept_all.append(s)
+                    pending.append(s)
+            ndrop = len(picks) - int(np.count_nonzero(keep))
+            dropped += ndrop
+            if not picks or ndrop == 0:
+                break
+            if rounds == R:
+                logger.warning("group %d: round cap %d reached, %d picks dropped without a redesign", gi + 1, R, ndrop)
+                break
+        timings["cross_rounds"] += rounds
+        self.last_cross_rounds[gi] = rounds
+        self.last_cross_banned[gi] = int(np.count_nonzero(banned & ~in_kg))
+        self.last_cross_dropped[gi] = dropped
+        self.last_cross_kept[gi] = len(selected)
+        return selected
 
     def prune_probe_strs(self, probe_strs, target_genomes):
         """Which probes of an existing list can go without uncovering a base?

@@ -16,6 +16,12 @@ the value is 0); --max-cross-dimer X implies it and adds the rule cross-dimer
 to every record whose value exceeds X, so both members of a pair fail
 (catch_amd/filter/cross_dimer.py has the definition).  For these two columns
 all records of the file are ONE list, whatever their lengths.
+--cross-dimer-against panel.fasta puts two more columns behind them (or where
+they would stand): cross_against, the longest antiparallel pairing with a
+record of the panel (an equal record included), and cross_against_partner, the
+number of the first panel record that reaches it (1-based, NA at 0); with
+--max-cross-dimer X a record whose value exceeds X also fails the rule
+cross-against (cross_dimer.py: cross_against).
 
 Records are read with seq_io.iterate_fasta: bytes as they are (lower case is
 no base), any lengths.  On the device the records are grouped by length: a
@@ -42,6 +48,8 @@ COLUMNS = ("probe", "length") + quality.QUANTITIES + ("tm_c", "background_hits")
 CROSS_COLUMNS = ("cross_dimer", "cross_partner")
 RULES = ("gc", "homopolymer", "low-complexity", "hairpin", "self-dimer", "tm", "background")
 CROSS_RULE = "cross-dimer"              # the one rule that looks at the other records of the file
+AGAINST_COLUMNS = ("cross_against", "cross_against_partner")
+AGAINST_RULE = "cross-against"          # ... and the one that looks at another file
 
 
 def parse_args(argv=None):
@@ -53,6 +61,14 @@ def parse_args(argv=None):
     tm_filter.add_arguments(p)
     background_filter.add_arguments(p)
     cross_dimer.add_arguments(p)
+    p.add_argument("--cross-dimer-against", metavar="FASTA",
+                   help="two more columns: cross_against, the longest stretch "
+                        "over which the probe and a record of this file (a "
+                        "panel it will share a tube with) can anneal, and "
+                        "cross_against_partner, the number of the first panel "
+                        "record that reaches it (1-based, NA when the value is "
+                        "0); with --max-cross-dimer X a probe whose value "
+                        "exceeds X fails the rule cross-against")
     p.add_argument("--write-kept", metavar="FASTA", help="the records that fail no rule, as they were read")
     p.add_argument("--write-failed", metavar="FASTA", help="the records that fail a rule")
     p.add_argument("--verbose", action="store_true")
@@ -109,6 +125,10 @@ class Judge:
         if self.max_cross_dimer is not None:
             self.max_cross_dimer = cross_dimer._threshold(self.max_cross_dimer, "--max-cross-dimer")
         self.cross_dimer = bool(getattr(args, "cross_dimer", False)) or self.max_cross_dimer is not None
+        # the panel of --cross-dimer-against: its records' sequences (load = False: only that there is one)
+        self.against = getattr(args, "cross_dimer_against", None)
+        if self.against is not None and load:
+            self.against = [s for _name, s in read_records(self.against)]
         self.thresholds = any(x is not None for x in (
             args.filter_gc, args.max_homopolymer, args.filter_low_complexity, args.max_hairpin_stem,
             args.max_self_dimer, args.filter_tm, args.background_max_hits, self.max_cross_dimer))
@@ -121,7 +141,7 @@ class Judge:
     def dust_window(self):
         return self.composition.dust_window
 
-    def failed(self, length, five, tm_c, hits, cross=0):
+    def failed(self, length, five, tm_c, hits, cross=0, against=0):
         """The names of the rules a probe with these values fails, with the ties of the design command."""
         gc, run, dust, stem, dimer = five
         c, s, out = self.composition, self.structure, []
@@ -142,6 +162,8 @@ class Judge:
             out.append(RULES[6])
         if self.max_cross_dimer is not None and cross > self.max_cross_dimer:
             out.append(CROSS_RULE)
+        if self.max_cross_dimer is not None and self.against is not None and against > self.max_cross_dimer:
+            out.append(AGAINST_RULE)
         return out
 
     def close(self):
@@ -253,7 +275,11 @@ def report_lines(judge, records):
     cross = partner = None
     if judge.cross_dimer:
         cross, partner = cross_dimer.measure(seqs)
-    lines = ["\t".join(COLUMNS + (CROSS_COLUMNS if judge.cross_dimer else ()) + (("verdict",) if judge.thresholds else ()))]
+    against = against_partner = None
+    if judge.against is not None:
+        against, against_partner = cross_dimer.measure_against(seqs, judge.against)
+    lines = ["\t".join(COLUMNS + (CROSS_COLUMNS if judge.cross_dimer else ()) +
+                       (AGAINST_COLUMNS if against is not None else ()) + (("verdict",) if judge.thresholds else ()))]
     failed = []
     for i, (name, s) in enumerate(records):
         row = [name, str(len(s))] + [str(int(v)) for v in five[i]]
@@ -261,10 +287,12 @@ def report_lines(judge, records):
         row.append("NA" if hits is None else str(int(hits[i])))
         if cross is not None:
             row += [str(int(cross[i])), str(int(partner[i]) + 1) if cross[i] > 0 else "NA"]
+        if against is not None:
+            row += [str(int(against[i])), str(int(against_partner[i]) + 1) if against[i] > 0 else "NA"]
         bad = []
         if judge.thresholds:
             bad = judge.failed(len(s), [int(v) for v in five[i]], tm_c[i], 0 if hits is None else int(hits[i]),
-                               0 if cross is None else int(cross[i]))
+                               0 if cross is None else int(cross[i]), 0 if against is None else int(against[i]))
             row.append(",".join(bad) if bad else "ok")
         failed.append(bad)
         lines.append("\t".join(row))
