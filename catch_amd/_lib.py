@@ -296,6 +296,14 @@ REDESIGN_PROTOTYPES = {
     "catchhip_rows_drop_sets": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_u8p, c_vpp, c_i64p]),
 }
 
+# the entry points of include/catchhip_duplex.h, bound like the ones above
+DUPLEX_PROTOTYPES = {
+    "catchhip_cross_duplex": CROSS_PROTOTYPES["catchhip_cross_dimer"],
+    "catchhip_cross_duplex_graph": CROSS_PROTOTYPES["catchhip_cross_dimer_graph"],
+    "catchhip_cross_duplex_against": REDESIGN_PROTOTYPES["catchhip_cross_against"],
+    "catchhip_cross_duplex_against_flags": REDESIGN_PROTOTYPES["catchhip_cross_against_flags"],
+}
+
 _lib = None
 
 
@@ -315,7 +323,7 @@ def lib():
                 % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(PROTOTYPES.items()) + list(CROSS_PROTOTYPES.items()) \
-                + list(REDESIGN_PROTOTYPES.items()):
+                + list(REDESIGN_PROTOTYPES.items()) + list(DUPLEX_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

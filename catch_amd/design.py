@@ -53,6 +53,11 @@ adds its two columns to --write-probe-report.
 conflicts instead: the set cover filter never offers a candidate that anneals
 to a kept or an existing probe and covers again what a dropped pick would have
 covered, in at most --cross-dimer-rounds solves per dataset.
+--max-cross-dimer-dg G (nor this) is --max-cross-dimer with another unit: a
+pair conflicts when its firmest stretch has a nearest-neighbour dG below -G
+kcal/mol (catch_amd/filter/cross_duplex.py has the rule); one of the two per
+design, the same filter, the same redesign; --cross-dimer-dg adds its two
+columns to --write-probe-report.
 --print-analysis and the
 three --write-... options run the coverage analysis of the designed probes
 (bin/design.py:417-442).
@@ -66,7 +71,7 @@ import sys
 from catch_amd.filter import background_filter, composition_filter
 from catch_amd.filter import duplicate_filter, near_duplicate_filter
 from catch_amd.filter import probe_designer, quality, set_cover_filter
-from catch_amd.filter import cross_dimer, structure_filter, tm_filter
+from catch_amd.filter import cross_dimer, cross_duplex, structure_filter, tm_filter
 from catch_amd.utils import seq_io
 
 logger = logging.getLogger("catch_amd.design")
@@ -162,8 +167,11 @@ def parse_args(argv=None, args_type="basic"):
     background_filter.add_arguments(p)      # --background, --background-..., --write-background-histogram (not in the reference)
     quality.add_arguments(p)                # --write-candidate-profile (not in the reference)
     cross_dimer.add_arguments(p)            # --cross-dimer, --max-cross-dimer (not in the reference)
+    cross_duplex.add_arguments(p)           # --cross-dimer-dg, --max-cross-dimer-dg (not in the reference)
     p.add_argument("--cross-dimer-redesign", action="store_true",
-                   help="with --max-cross-dimer X: instead of dropping "
+                   help="with --max-cross-dimer X (or --max-cross-dimer-dg "
+                        "G, with `firmer than G` for `over more than X "
+                        "bases`): instead of dropping "
                         "conflicting probes behind the set cover, design "
                         "around them.  Candidates that anneal to a probe "
                         "already kept (of any dataset, or of --extend-probes) "
@@ -274,17 +282,23 @@ def parse_args(argv=None, args_type="basic"):
     tm_filter.from_args(args, p.error)
     background_filter.from_args(args, p.error, load=False)      # (the options alone: main reads the background)
     cross_dimer.check_args(args, p.error)
+    cross_duplex.check_args(args, p.error)
     if args.cross_dimer and args.write_probe_report is None:
         p.error("--cross-dimer adds columns to --write-probe-report and needs it (--max-cross-dimer X filters)")
-    if args.max_cross_dimer is not None:
-        if args.add_reverse_complements:
-            p.error("--max-cross-dimer cannot go with --add-reverse-complements: every probe then has a perfect "
-                    "partner by construction")
-        if args.skip_set_cover:
-            p.error("--max-cross-dimer cannot go with --skip-set-cover: it would pair all candidates with each "
-                    "other, a quadratic pass")
-    if args.cross_dimer_redesign and args.max_cross_dimer is None:
-        p.error("--cross-dimer-redesign needs --max-cross-dimer X: the threshold of a conflict")
+    if args.cross_dimer_dg and args.write_probe_report is None:
+        p.error("--cross-dimer-dg adds columns to --write-probe-report and needs it (--max-cross-dimer-dg G filters)")
+    if args.max_cross_dimer is not None and args.max_cross_dimer_dg is not None:
+        p.error("--max-cross-dimer and --max-cross-dimer-dg are two conflict rules: a design applies one")
+    for given, opt in ((args.max_cross_dimer, "--max-cross-dimer"), (args.max_cross_dimer_dg, "--max-cross-dimer-dg")):
+        if given is not None:
+            if args.add_reverse_complements:
+                p.error("%s cannot go with --add-reverse-complements: every probe then has a perfect "
+                        "partner by construction" % opt)
+            if args.skip_set_cover:
+                p.error("%s cannot go with --skip-set-cover: it would pair all candidates with each "
+                        "other, a quadratic pass" % opt)
+    if args.cross_dimer_redesign and args.max_cross_dimer is None and args.max_cross_dimer_dg is None:
+        p.error("--cross-dimer-redesign needs --max-cross-dimer X (or --max-cross-dimer-dg G): the threshold of a conflict")
     if args.cross_dimer_rounds is not None:
         if not args.cross_dimer_redesign:
             p.error("--cross-dimer-rounds needs --cross-dimer-redesign")
@@ -630,14 +644,15 @@ def main(args):
         max_probes=args.max_probes, pick_gains=want_gains,
         curve_points=args.coverage_curve_points,
         target_regions=regions, either_strand=args.either_strand,
-        **(dict(max_cross_dimer=args.max_cross_dimer, cross_dimer_rounds=args.cross_dimer_rounds)
+        **(dict(max_cross_dimer=args.max_cross_dimer, max_cross_dimer_dg=args.max_cross_dimer_dg,
+                cross_dimer_rounds=args.cross_dimer_rounds)
            if args.cross_dimer_redesign else {}))
     filters.append(scf)
     cross = None
     # (not in the reference) one filter over the picks of all datasets; under --cross-dimer-redesign the set cover
     # filter keeps its picks free of conflicts itself
-    if args.max_cross_dimer is not None and not args.cross_dimer_redesign:
-        cross = cross_dimer.CrossDimerFilter(args.max_cross_dimer)
+    if (args.max_cross_dimer is not None or args.max_cross_dimer_dg is not None) and not args.cross_dimer_redesign:
+        cross = cross_dimer.CrossDimerFilter(args.max_cross_dimer, max_cross_dimer_dg=args.max_cross_dimer_dg)
         filters.append(cross)
     if args.add_adapters:      # bin/design.py:345-365 (default sequences :350, :354)
         from catch_amd.filter import adapter_filter
@@ -693,8 +708,8 @@ def main(args):
             background.write_histogram(args.write_background_histogram)
         background.close()
     if cross is not None:
-        logger.info("cross-dimer filter: %d of %d probes dropped (largest cross-dimer %d before, %d after)",
-                    cross.dropped, cross.seen, cross.largest_before, cross.largest_after)
+        logger.info("cross-dimer filter: %d of %d probes dropped (largest %s %d before, %d after)",
+                    cross.dropped, cross.seen, cross.rule.noun, cross.largest_before, cross.largest_after)
     if args.cross_dimer_redesign:
         for gi, fn in enumerate(args.dataset):
             logger.info("%s: cross-dimer redesign: %d rounds, %d candidates banned, %d picks dropped, %d probes kept",

@@ -274,14 +274,57 @@ def _threshold(x, what="max_cross_dimer"):
     return x
 
 
-class CrossDimerFilter(BaseFilter):
-    """Drops probes that pair with an earlier kept probe over more than
-    max_cross_dimer consecutive bases.  `dropped` and `seen` accumulate over
-    the calls; largest_before / largest_after are the largest cross of the
-    last call's input and output (0 for fewer than two probes)."""
+class LengthRule:
+    """The conflict rule of --max-cross-dimer X: run > X.  What CrossDimerFilter
+    and the set cover filter's redesign rounds ask of the rule in force
+    (cross_duplex.DgRule is the other one): the measure of a list, the walk and
+    the flags on the host path, the conflict graph and the flags on the device."""
+    noun = "cross-dimer"
 
-    def __init__(self, max_cross_dimer):
-        self.max_cross_dimer = _threshold(max_cross_dimer)
+    def __init__(self, x):
+        self.above = _threshold(x)
+
+    def measure(self, seqs):
+        return measure(seqs)
+
+    def walk(self, seqs):
+        return walk(seqs, self.above)
+
+    def flags_host(self, bs, as_):
+        return cross_against_numpy(bs, as_)[0] > self.above
+
+    def graph(self, ctx, strs):
+        from catch_amd import engine
+        return engine.RedundancyGraph.cross_dimer(ctx, strs, self.above)
+
+    def flags_device(self, ctx, bs, as_):
+        from catch_amd import engine
+        return engine.cross_against_flags(ctx, bs, as_, self.above)
+
+
+def rule_of(max_cross_dimer=None, max_cross_dimer_dg=None):
+    """The one conflict rule of a design: LengthRule(X) or cross_duplex.DgRule(G)."""
+    if max_cross_dimer_dg is not None:
+        if max_cross_dimer is not None:
+            raise ValueError("max_cross_dimer and max_cross_dimer_dg are two conflict rules: a design applies one")
+        from catch_amd.filter import cross_duplex
+        return cross_duplex.DgRule(max_cross_dimer_dg)
+    return LengthRule(max_cross_dimer)
+
+
+class CrossDimerFilter(BaseFilter):
+    """Drops probes that conflict with an earlier kept probe: under
+    max_cross_dimer = X those that pair with it over more than X consecutive
+    bases, under max_cross_dimer_dg = G (a keyword; instead of X) those whose
+    firmest stretch with it is firmer than G kcal/mol
+    (catch_amd/filter/cross_duplex.py).  `dropped` and `seen` accumulate over
+    the calls; largest_before / largest_after are the largest cross (or dcross)
+    of the last call's input and output (0 for fewer than two probes)."""
+
+    def __init__(self, max_cross_dimer=None, max_cross_dimer_dg=None):
+        self.rule = rule_of(max_cross_dimer, max_cross_dimer_dg)
+        self.max_cross_dimer = self.rule.above if max_cross_dimer_dg is None else None
+        self.max_cross_dimer_dg = max_cross_dimer_dg
         self.dropped = 0
         self.seen = 0
         self.largest_before = 0
@@ -289,9 +332,9 @@ class CrossDimerFilter(BaseFilter):
 
     def _keep(self, strs):
         if _on_host(strs):
-            return walk(strs, self.max_cross_dimer)
+            return self.rule.walk(strs)
         from catch_amd import engine
-        graph = engine.RedundancyGraph.cross_dimer(engine.default_context(), strs, self.max_cross_dimer)
+        graph = self.rule.graph(engine.default_context(), strs)
         try:
             return graph.naive()
         finally:
@@ -306,8 +349,8 @@ class CrossDimerFilter(BaseFilter):
         kept = [p for p, k in zip(probes, keep) if k]
         self.seen += len(probes)
         self.dropped += len(probes) - len(kept)
-        self.largest_before = int(measure(strs)[0].max())
-        self.largest_after = int(measure([p.seq_str for p in kept])[0].max())
+        self.largest_before = int(self.rule.measure(strs)[0].max())
+        self.largest_after = int(self.rule.measure([p.seq_str for p in kept])[0].max())
         return kept
 
     def filter(self, input, target_genomes=None, input_is_grouped=False, num_processes=None):

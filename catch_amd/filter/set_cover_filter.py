@@ -66,7 +66,8 @@ class _KeywordsBeyondInit(type):
     """SetCoverFilter(..., fixed_probes=None, coverage_depth=1,
     prune_redundant=False, max_probes=None, pick_gains=False,
     curve_points=100, target_regions=None, either_strand=False,
-    max_cross_dimer=None, cross_dimer_rounds=8): everything after `fixed_probes` is a keyword of the CALL
+    max_cross_dimer=None, cross_dimer_rounds=8,
+    max_cross_dimer_dg=None): everything after `fixed_probes` is a keyword of the CALL
     of the class, taken here and handed to the new object after __init__ ran.
     __init__ itself stays the reference's argument list followed by
     `fixed_probes`, the form its callers and the signature checks of the
@@ -74,14 +75,14 @@ class _KeywordsBeyondInit(type):
 
     def __call__(cls, *args, coverage_depth=1, prune_redundant=False, max_probes=None, pick_gains=False,
                  curve_points=100, target_regions=None, either_strand=False, max_cross_dimer=None,
-                 cross_dimer_rounds=8, **kwargs):
+                 cross_dimer_rounds=8, max_cross_dimer_dg=None, **kwargs):
         obj = super().__call__(*args, **kwargs)
         obj._set_either_strand(either_strand)
         obj._set_coverage_depth(coverage_depth)
         obj._set_prune_redundant(prune_redundant)
         obj._set_budget(max_probes, pick_gains, curve_points)
         obj._set_target_regions(target_regions)
-        obj._set_cross_dimer(max_cross_dimer, cross_dimer_rounds)
+        obj._set_cross_dimer(max_cross_dimer, cross_dimer_rounds, max_cross_dimer_dg)
         return obj
 
 
@@ -168,6 +169,8 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         self.either_strand = False  # (SetCoverFilter(..., either_strand=True) sets it: _KeywordsBeyondInit)
         self._strand_scan = None    # what the last _scan_group did under either_strand (_either_strand_rows)
         self.max_cross_dimer = None  # (SetCoverFilter(..., max_cross_dimer=X, cross_dimer_rounds=R): _KeywordsBeyondInit)
+        self.max_cross_dimer_dg = None
+        self.cross_rule = None       # the conflict rule of the redesign: cross_dimer.LengthRule or cross_duplex.DgRule
         self.cross_dimer_rounds = 8
         self.last_cross_rounds = []
         self.last_cross_banned = []
@@ -232,11 +235,13 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                 "pick_gains / max_probes cannot be combined with coverage_depth > 1: "
                 "a gain is then no longer the bases covered first")
 
-    def _set_cross_dimer(self, max_cross_dimer, cross_dimer_rounds):
+    def _set_cross_dimer(self, max_cross_dimer, cross_dimer_rounds, max_cross_dimer_dg=None):
         """The cross-dimer redesign (not an argument of the reference's class):
         with max_cross_dimer = X >= 1 no two selected probes, of any group, and
         no selected probe and fixed probe pair with each other over more than X
-        bases (catch_amd/filter/cross_dimer.py: conflicts_with), and what a
+        bases (catch_amd/filter/cross_dimer.py: conflicts_with) -- or, with
+        max_cross_dimer_dg = G in its place, none form a stretch firmer than G
+        kcal/mol (catch_amd/filter/cross_duplex.py) -- and what a
         conflicting pick would have covered is covered again by other
         candidates, in at most cross_dimer_rounds = R >= 1 solves per group
         (_cross_rounds has the definition).  last_cross_rounds[group] = the
@@ -244,19 +249,21 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         never offered to a solve because they conflict with a kept probe or a
         fixed one, last_cross_dropped[group] = the picks dropped,
         last_cross_kept[group] = the probes selected."""
-        if max_cross_dimer is None:
-            self.max_cross_dimer = None
+        self.max_cross_dimer = self.max_cross_dimer_dg = self.cross_rule = None
+        if max_cross_dimer is None and max_cross_dimer_dg is None:
             return
         from catch_amd.filter import cross_dimer
-        x = cross_dimer._threshold(max_cross_dimer)
+        rule = cross_dimer.rule_of(max_cross_dimer, max_cross_dimer_dg)
         if (isinstance(cross_dimer_rounds, bool) or not isinstance(cross_dimer_rounds, (int, np.integer))
                 or cross_dimer_rounds < 1):
             raise ValueError("cross_dimer_rounds must be an integer >= 1, not %r" % (cross_dimer_rounds,))
         if self.coverage_depth > 1 or self.prune_redundant or self.pick_gains:
             raise NotImplementedError(
-                "max_cross_dimer (the cross-dimer redesign) cannot be combined with coverage_depth > 1, "
+                "max_cross_dimer / max_cross_dimer_dg (the cross-dimer redesign) cannot be combined with coverage_depth > 1, "
                 "prune_redundant, pick_gains or max_probes")
-        self.max_cross_dimer = x
+        self.cross_rule = rule
+        self.max_cross_dimer = rule.above if max_cross_dimer_dg is None else None
+        self.max_cross_dimer_dg = max_cross_dimer_dg
         self.cross_dimer_rounds = int(cross_dimer_rounds)
 
     def _set_prune_redundant(self, prune_redundant):
@@ -292,7 +299,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         scan (_filter_strs_keeping_rows): the fused scan-and-solve call and the
         device front end never hand the rows out."""
         return (bool(self.fixed_probes) or self.coverage_depth > 1 or self.prune_redundant or self.pick_gains
-                or self.target_regions is not None or self.either_strand or self.max_cross_dimer is not None)
+                or self.target_regions is not None or self.either_strand or self.cross_rule is not None)
 
     def _anchor_table(self, strs, assume_unique=False, tolerant=False):
         """probe.anchor_table of `strs` under the strict hybridization model, or
@@ -624,7 +631,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
                 "fixed probes (extending an existing probe set) run on one rank" if fixed else
                 "target regions run on one rank" if regions is not None else
                 "either_strand runs on one rank" if self.either_strand else
-                "the cross-dimer redesign (max_cross_dimer) runs on one rank" if self.max_cross_dimer is not None else
+                "the cross-dimer redesign (max_cross_dimer) runs on one rank" if self.cross_rule is not None else
                 "coverage_depth > 1, prune_redundant, pick_gains and max_probes run on one rank")
         ctx = self._context()
         ngroups = len(input_strs)
@@ -647,7 +654,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
             self.last_wanted_bases = [0] * ngroups
             self.last_coverable_bases = [0] * ngroups
         budget = _Budget(self, ctx, ngroups, timings)
-        redesign = self.max_cross_dimer is not None
+        redesign = self.cross_rule is not None
         if redesign:
             timings.update(ban_ms=0.0, ban_pairs=0, cross_rounds=0)
             self.last_cross_rounds = [0] * ngroups
@@ -787,6 +794,9 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
     def _cross_rounds(self, ctx, gi, ngroups, strs, first, p, covered0, rk, ng, kept_all, timings, coverable_of=None):
         """The repair rounds of one group under max_cross_dimer = X and
         cross_dimer_rounds = R -> the group's selection, in the order kept.
+        Under max_cross_dimer_dg = G the loop is the same and `conflicts` reads
+        duplex > floor(100 G) for run > X: the bans and the pick walk come from
+        the rule in force (self.cross_rule).
 
         E = the fixed probes' strings, K = `kept_all`, the distinct strings kept
         so far over all groups (extended here), K_g its part kept for this
@@ -825,7 +835,7 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         path (cross_dimer.cross_against_numpy, walk) under
         CATCHHIP_HOST_FRONT_END=1 or with a record of more than 256 characters."""
         from catch_amd.filter import cross_dimer
-        X, R = self.max_cross_dimer, self.cross_dimer_rounds
+        rule, R = self.cross_rule, self.cross_dimer_rounds
         n = len(strs)
         on_host = cross_dimer._on_host(list(strs) + self.fixed_probes + kept_all)
         index_of = {}
@@ -842,9 +852,9 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
         while True:
             if pending:
                 if on_host:
-                    banned |= cross_dimer.cross_against_numpy(strs, pending)[0] > X
+                    banned |= rule.flags_host(strs, pending)
                 else:
-                    banned |= engine.cross_against_flags(ctx, strs, pending, X)
+                    banned |= rule.flags_device(ctx, strs, pending)
                     timings["ban_ms"] += ctx.kernel_ms(engine.PHASE_NDF)[0]
                 timings["ban_pairs"] += n * len(pending)
             offered_out = banned & ~in_kg
@@ -880,9 +890,9 @@ class SetCoverFilter(BaseFilter, metaclass=_KeywordsBeyondInit):
             if len(picks) < 2:
                 keep = np.ones(len(picks), dtype=bool)
             elif on_host:
-                keep = cross_dimer.walk(pick_strs, X)
+                keep = rule.walk(pick_strs)
             else:
-                graph = engine.RedundancyGraph.cross_dimer(ctx, pick_strs, X)
+                graph = rule.graph(ctx, pick_strs)
                 try:
                     keep = graph.naive()
                 finally:

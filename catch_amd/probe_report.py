@@ -22,6 +22,15 @@ record of the panel (an equal record included), and cross_against_partner, the
 number of the first panel record that reaches it (1-based, NA at 0); with
 --max-cross-dimer X a record whose value exceeds X also fails the rule
 cross-against (cross_dimer.py: cross_against).
+--cross-dimer-dg puts cross_dg and cross_dg_partner behind those columns (or
+where they would stand): the stability of the probe's firmest stretch with
+another record of the file, in hundredths of a kcal/mol, and the number of the
+first record that reaches it (1-based, NA at 0); --max-cross-dimer-dg G implies
+it and adds the rule cross-dg to every record whose value exceeds
+floor(100 G).  With --cross-dimer-against, cross_dg_against and
+cross_dg_against_partner follow, and their rule is cross-dg-against
+(catch_amd/filter/cross_duplex.py has the definition).  The length options and
+the dG options are independent of each other.
 
 Records are read with seq_io.iterate_fasta: bytes as they are (lower case is
 no base), any lengths.  On the device the records are grouped by length: a
@@ -38,7 +47,7 @@ import sys
 
 import numpy as np
 
-from catch_amd.filter import background_filter, composition_filter, cross_dimer, quality
+from catch_amd.filter import background_filter, composition_filter, cross_dimer, cross_duplex, quality
 from catch_amd.filter import structure_filter, tm_filter
 from catch_amd.utils import seq_io
 
@@ -50,6 +59,10 @@ RULES = ("gc", "homopolymer", "low-complexity", "hairpin", "self-dimer", "tm", "
 CROSS_RULE = "cross-dimer"              # the one rule that looks at the other records of the file
 AGAINST_COLUMNS = ("cross_against", "cross_against_partner")
 AGAINST_RULE = "cross-against"          # ... and the one that looks at another file
+DG_COLUMNS = ("cross_dg", "cross_dg_partner")
+DG_RULE = "cross-dg"                    # the same two rules by stability (catch_amd/filter/cross_duplex.py)
+DG_AGAINST_COLUMNS = ("cross_dg_against", "cross_dg_against_partner")
+DG_AGAINST_RULE = "cross-dg-against"
 
 
 def parse_args(argv=None):
@@ -61,6 +74,7 @@ def parse_args(argv=None):
     tm_filter.add_arguments(p)
     background_filter.add_arguments(p)
     cross_dimer.add_arguments(p)
+    cross_duplex.add_arguments(p)
     p.add_argument("--cross-dimer-against", metavar="FASTA",
                    help="two more columns: cross_against, the longest stretch "
                         "over which the probe and a record of this file (a "
@@ -68,7 +82,10 @@ def parse_args(argv=None):
                         "cross_against_partner, the number of the first panel "
                         "record that reaches it (1-based, NA when the value is "
                         "0); with --max-cross-dimer X a probe whose value "
-                        "exceeds X fails the rule cross-against")
+                        "exceeds X fails the rule cross-against; with "
+                        "--cross-dimer-dg also cross_dg_against and "
+                        "cross_dg_against_partner, the same by stability "
+                        "(rule cross-dg-against under --max-cross-dimer-dg)")
     p.add_argument("--write-kept", metavar="FASTA", help="the records that fail no rule, as they were read")
     p.add_argument("--write-failed", metavar="FASTA", help="the records that fail a rule")
     p.add_argument("--verbose", action="store_true")
@@ -86,6 +103,7 @@ def parse_args(argv=None):
             if value is not None:
                 p.error("%s needs --background" % flag)
     cross_dimer.check_args(args, p.error)
+    cross_duplex.check_args(args, p.error)
     try:
         Judge(args, load=False)
     except ValueError as exc:
@@ -125,13 +143,18 @@ class Judge:
         if self.max_cross_dimer is not None:
             self.max_cross_dimer = cross_dimer._threshold(self.max_cross_dimer, "--max-cross-dimer")
         self.cross_dimer = bool(getattr(args, "cross_dimer", False)) or self.max_cross_dimer is not None
+        # ... the same by stability: the threshold in hundredths of a kcal/mol
+        self.max_cross_dg = getattr(args, "max_cross_dimer_dg", None)
+        if self.max_cross_dg is not None:
+            self.max_cross_dg = cross_duplex.threshold(self.max_cross_dg, "--max-cross-dimer-dg")
+        self.cross_dg = bool(getattr(args, "cross_dimer_dg", False)) or self.max_cross_dg is not None
         # the panel of --cross-dimer-against: its records' sequences (load = False: only that there is one)
         self.against = getattr(args, "cross_dimer_against", None)
         if self.against is not None and load:
             self.against = [s for _name, s in read_records(self.against)]
         self.thresholds = any(x is not None for x in (
             args.filter_gc, args.max_homopolymer, args.filter_low_complexity, args.max_hairpin_stem,
-            args.max_self_dimer, args.filter_tm, args.background_max_hits, self.max_cross_dimer))
+            args.max_self_dimer, args.filter_tm, args.background_max_hits, self.max_cross_dimer, self.max_cross_dg))
 
     @property
     def min_loop(self):
@@ -141,7 +164,7 @@ class Judge:
     def dust_window(self):
         return self.composition.dust_window
 
-    def failed(self, length, five, tm_c, hits, cross=0, against=0):
+    def failed(self, length, five, tm_c, hits, cross=0, against=0, dg=0, dg_against=0):
         """The names of the rules a probe with these values fails, with the ties of the design command."""
         gc, run, dust, stem, dimer = five
         c, s, out = self.composition, self.structure, []
@@ -164,6 +187,10 @@ class Judge:
             out.append(CROSS_RULE)
         if self.max_cross_dimer is not None and self.against is not None and against > self.max_cross_dimer:
             out.append(AGAINST_RULE)
+        if self.max_cross_dg is not None and dg > self.max_cross_dg:
+            out.append(DG_RULE)
+        if self.max_cross_dg is not None and self.against is not None and dg_against > self.max_cross_dg:
+            out.append(DG_AGAINST_RULE)
         return out
 
     def close(self):
@@ -278,8 +305,14 @@ def report_lines(judge, records):
     against = against_partner = None
     if judge.against is not None:
         against, against_partner = cross_dimer.measure_against(seqs, judge.against)
+    dg = dg_partner = dg_against = dg_against_partner = None
+    if judge.cross_dg:
+        dg, dg_partner = cross_duplex.measure(seqs)
+        if judge.against is not None:
+            dg_against, dg_against_partner = cross_duplex.measure_against(seqs, judge.against)
     lines = ["\t".join(COLUMNS + (CROSS_COLUMNS if judge.cross_dimer else ()) +
-                       (AGAINST_COLUMNS if against is not None else ()) + (("verdict",) if judge.thresholds else ()))]
+                       (AGAINST_COLUMNS if against is not None else ()) + (DG_COLUMNS if dg is not None else ()) +
+                       (DG_AGAINST_COLUMNS if dg_against is not None else ()) + (("verdict",) if judge.thresholds else ()))]
     failed = []
     for i, (name, s) in enumerate(records):
         row = [name, str(len(s))] + [str(int(v)) for v in five[i]]
@@ -289,10 +322,15 @@ def report_lines(judge, records):
             row += [str(int(cross[i])), str(int(partner[i]) + 1) if cross[i] > 0 else "NA"]
         if against is not None:
             row += [str(int(against[i])), str(int(against_partner[i]) + 1) if against[i] > 0 else "NA"]
+        if dg is not None:
+            row += [str(int(dg[i])), str(int(dg_partner[i]) + 1) if dg[i] > 0 else "NA"]
+        if dg_against is not None:
+            row += [str(int(dg_against[i])), str(int(dg_against_partner[i]) + 1) if dg_against[i] > 0 else "NA"]
         bad = []
         if judge.thresholds:
             bad = judge.failed(len(s), [int(v) for v in five[i]], tm_c[i], 0 if hits is None else int(hits[i]),
-                               0 if cross is None else int(cross[i]), 0 if against is None else int(against[i]))
+                               0 if cross is None else int(cross[i]), 0 if against is None else int(against[i]),
+                               0 if dg is None else int(dg[i]), 0 if dg_against is None else int(dg_against[i]))
             row.append(",".join(bad) if bad else "ok")
         failed.append(bad)
         lines.append("\t".join(row))
