@@ -1,7 +1,13 @@
-// What the two pair files of cross.hip's organisation share (cross.hip: the length of a pairing; duplex.hip: its
-// nearest-neighbour stability): the packing of records into bit planes, the AND-shift run search, the keys, the
-// staging of a call's records and the host side of the four entries.  A file brings its pair kernels and hands their
-// launchers over as a CdLaunch; cross.hip's header comment has the organisation.
+// Everything of cross.hip's organisation but the pair function (cross.hip: the length of a pairing; duplex.hip: its
+// nearest-neighbour stability): the packing of records into bit planes, an antidiagonal's match word, the AND-shift
+// run search, the keys, the two tile kernels with their launchers, the staging of a call's records and the host side
+// of the four entries.  A file brings a pair RULE, which says three things:
+//   PREFIX, prefix<W>(a, q)             whether a block stages u16 s_q[64 W][RG_TILE] beside a row tile's planes, and
+//                                       what fills one record's column of it (asked for only where PREFIX)
+//   pair<W, FIRST>(a, rb, q, la, lb, t) the pair's value where it exceeds t, else anything <= t; FIRST: any value
+//                                       beyond t, at the first run that has one
+//   MIN_ABOVE, VALUES / GRAPH / AGAINST / FLAGS   the smallest `above` of its graph and flags entries, their names
+// cross.hip's header comment has the organisation.
 #pragma once
 #include <algorithm>
 #include <memory>
@@ -84,6 +90,31 @@ template <int W> __host__ __device__ __forceinline__ bool cd_any(const u64 (&x)[
     return o != 0;
 }
 
+// The match word of antidiagonal c, d = 64 W - 1 - c.  a points at word 0 of plane V of the row record's plain planes,
+// rb at the same of the column record's reversed planes, both in a tile's layout [plane][2 W words][RG_TILE] with
+// words W .. 2 W - 1 zero (a shifted read never leaves the array).  For d >= 0 bit x of m is cell (x, c - x), for
+// d < 0 bit x is cell (x - d, c - x + d): the row's planes are then the shifted ones.  (It takes c, not d: compiled
+// on its own in front of a pair function, it then yields the code that the same lines give inside cd_pair's loop.)
+template <int W>
+__host__ __device__ __forceinline__ void cd_match(const u64 *a, const u64 *rb, int c, u64 (&m)[W]) {
+    const int d = 64 * W - 1 - c;                            // |d| <= 64 W - 1: la + lb - 2 <= 128 W - 2
+    const int s = d >= 0 ? d : -d;
+    const int ws = s >> 6;
+    const u32 bs = (u32)s & 63u;
+    const u64 *sh = d >= 0 ? rb : a, *un = d >= 0 ? a : rb;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        u64 p[3];
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) {
+            const u64 lo = sh[(size_t)(pl * 2 * W + w + ws) * RG_TILE], hi = sh[(size_t)(pl * 2 * W + w + ws + 1) * RG_TILE];
+            p[pl] = (lo >> bs) | ((hi << 1) << (63u - bs));
+        }
+        m[w] = (p[2] ^ un[(size_t)(2 * 2 * W + w) * RG_TILE]) & ~(p[1] ^ un[(size_t)(1 * 2 * W + w) * RG_TILE]) & p[0] &
+               un[(size_t)w * RG_TILE];
+    }
+}
+
 // what a pair with `other` as the partner must exceed to change the record that holds `key`
 __device__ __forceinline__ int cd_threshold(unsigned long long key, u32 other) {
     const int v = (int)(key >> 32);
@@ -111,10 +142,196 @@ struct CdInput {
     DevBuf<u32> lens;
 };
 
-// What a pair file hands to the entries below: its name in messages, the smallest threshold its graph and flags
-// entries take, and the launchers of its two kernels.
-//   pairs:   one 64 x 64 tile a block over the upper triangle of one list (values: best; graph: bitmap at `above`)
-//   against: a tile of B a block against the range of A's tiles `per` long that blockIdx.y names
+// One 64 x 64 tile of pairs (rows ti * 64 .., columns tj * 64 .., ti <= tj); pair (gi, gj) counts when gi < gj < n:
+// a diagonal tile leaves out a record's own pairing and keeps equal records at different indices.
+// s_acc: a side's keys (values) or adjacency bits (GRAPH), row side 0, column side 1.
+template <class Rule, int W, bool GRAPH>
+__global__ void __launch_bounds__(RG_BLOCK)
+cd_pairs_kernel(const u64 *__restrict__ fwd, const u64 *__restrict__ rev, const u32 *__restrict__ lens, u32 n, u32 npad,
+                i32 above, unsigned long long *best, unsigned long long *bitmap, u32 rowwords) {
+    const u32 ti = blockIdx.y, tj = blockIdx.x;
+    if (ti > tj) return;
+    __shared__ u64 s_pl[2][3][2 * W][RG_TILE];
+    __shared__ u32 s_len[2][RG_TILE];
+    __shared__ unsigned long long s_acc[2][RG_TILE];
+    for (u32 t = threadIdx.x; t < 2 * 3 * 2 * W * RG_TILE; t += RG_BLOCK) {
+        const u32 pr = t % RG_TILE, w = (t / RG_TILE) % (2 * W), pl = (t / (RG_TILE * 2 * W)) % 3, side = t / (RG_TILE * 2 * W * 3);
+        const u32 g = (side ? tj : ti) * RG_TILE + pr;      // < npad
+        s_pl[side][pl][w][pr] = w < (u32)W ? (side ? rev : fwd)[((size_t)(pl * W + w)) * npad + g] : 0ull;
+    }
+    if (threadIdx.x < 2 * RG_TILE) {
+        const u32 side = threadIdx.x / RG_TILE, pr = threadIdx.x % RG_TILE;
+        const u32 g = (side ? tj : ti) * RG_TILE + pr;
+        s_len[side][pr] = lens[g];
+        s_acc[side][pr] = GRAPH ? 0ull : __hip_atomic_load(best + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    const u16 *q = nullptr;
+    if constexpr (Rule::PREFIX) {                            // the row side's s_q behind its planes
+        __shared__ u16 s_q[64 * W][RG_TILE];
+        if (threadIdx.x < RG_TILE) Rule::template prefix<W>(&s_pl[0][0][0][threadIdx.x], &s_q[0][threadIdx.x]);
+        __syncthreads();
+        q = &s_q[0][0];
+    }
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 gj = tj * RG_TILE + lane;
+    const int lb = (int)s_len[1][lane];
+    for (u32 k = wave * (RG_TILE * 64 / RG_BLOCK); k < (wave + 1) * (RG_TILE * 64 / RG_BLOCK); ++k) {
+        const u32 r = (lane + k) & (RG_TILE - 1);
+        const u32 gi = ti * RG_TILE + r;
+        if (!(gi < gj && gj < n)) continue;
+        int t = above;
+        if (!GRAPH) {
+            const int tr = cd_threshold(__hip_atomic_load(&s_acc[0][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), gj);
+            const int tc = cd_threshold(__hip_atomic_load(&s_acc[1][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), gi);
+            t = tr < tc ? tr : tc;
+        }
+        const int v = Rule::template pair<W, GRAPH>(&s_pl[0][0][0][r], &s_pl[1][0][0][lane], Rule::PREFIX ? q + r : q,
+                                                    (int)s_len[0][r], lb, t);
+        if (v <= t) continue;
+        if (GRAPH) {
+            atomicOr(&s_acc[0][r], 1ull << lane);
+            atomicOr(&s_acc[1][lane], 1ull << r);
+        } else {
+            atomicMax(&s_acc[0][r], ((unsigned long long)(u32)v << 32) | (unsigned long long)(0xFFFFFFFFu - gj));
+            atomicMax(&s_acc[1][lane], ((unsigned long long)(u32)v << 32) | (unsigned long long)(0xFFFFFFFFu - gi));
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * RG_TILE) {
+        const u32 side = threadIdx.x / RG_TILE, pr = threadIdx.x % RG_TILE;
+        const u32 g = (side ? tj : ti) * RG_TILE + pr;
+        const unsigned long long acc = s_acc[side][pr];
+        if (g < n && acc) {
+            if (GRAPH) atomicOr(&bitmap[(size_t)g * rowwords + (side ? ti : tj)], acc);
+            else atomicMax(&best[g], acc);
+        }
+    }
+}
+
+// One list against another: pair(b, a) for every b of B over a list A, nothing exempted.  A block owns one tile of 64
+// records of B, staged once on the reversed (column) side, and streams a range of A's tiles through the plain (row)
+// side with the one-list kernel's skewed order: step k pairs column `lane` with row (lane + k) mod 64, a wave taking
+// 16 steps of every tile; it is A's records that a rule's s_q belongs to, staged with every tile.  A column's best (a
+// key as above, the partner an index into A) or flag lives in LDS for the whole stream and goes out once at the end:
+// by atomic maximum, since gridDim.y blocks share a B tile when B alone would not fill the device (block y takes A's
+// tiles y * per .. ), or as a byte that is only ever written as 1.  What a block searches depends on the keys it
+// read; the maximum, and the smallest partner of equal values, do not.
+// FLAGS: the threshold is `above` throughout, a pair ends at its first run beyond it, a flagged column is skipped and
+// a tile whose columns are all flagged leaves the stream.
+template <class Rule, int W, bool FLAGS>
+__global__ void __launch_bounds__(RG_BLOCK)
+cd_against_kernel(const u64 *__restrict__ a_fwd, const u32 *__restrict__ a_lens, u32 na, u32 a_npad, u32 a_tiles, u32 per,
+                  const u64 *__restrict__ b_rev, const u32 *__restrict__ b_lens, u32 nb, u32 b_npad, i32 above,
+                  unsigned long long *best, u8 *flag) {
+    const u32 tb = blockIdx.x;
+    const u32 t_lo = blockIdx.y * per, t_hi = t_lo + per < a_tiles ? t_lo + per : a_tiles;
+    if (t_lo >= t_hi) return;
+    __shared__ u64 s_pl[2][3][2 * W][RG_TILE];
+    __shared__ u32 s_len[2][RG_TILE];
+    __shared__ unsigned long long s_acc[RG_TILE];
+    for (u32 t = threadIdx.x; t < 3 * 2 * W * RG_TILE; t += RG_BLOCK) {
+        const u32 pr = t % RG_TILE, w = (t / RG_TILE) % (2 * W), pl = t / (RG_TILE * 2 * W);
+        s_pl[1][pl][w][pr] = w < (u32)W ? b_rev[((size_t)(pl * W + w)) * b_npad + tb * RG_TILE + pr] : 0ull;   // < b_npad
+    }
+    if (threadIdx.x < RG_TILE) {
+        const u32 g = tb * RG_TILE + threadIdx.x;
+        s_len[1][threadIdx.x] = b_lens[g];
+        s_acc[threadIdx.x] = FLAGS ? 0ull : __hip_atomic_load(best + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 gb = tb * RG_TILE + lane;
+    for (u32 ta = t_lo; ta < t_hi; ++ta) {
+        for (u32 t = threadIdx.x; t < 3 * 2 * W * RG_TILE; t += RG_BLOCK) {
+            const u32 pr = t % RG_TILE, w = (t / RG_TILE) % (2 * W), pl = t / (RG_TILE * 2 * W);
+            s_pl[0][pl][w][pr] = w < (u32)W ? a_fwd[((size_t)(pl * W + w)) * a_npad + ta * RG_TILE + pr] : 0ull;   // < a_npad
+        }
+        if (threadIdx.x < RG_TILE) s_len[0][threadIdx.x] = a_lens[ta * RG_TILE + threadIdx.x];
+        __syncthreads();
+        const u16 *q = nullptr;
+        if constexpr (Rule::PREFIX) {
+            __shared__ u16 s_q[64 * W][RG_TILE];
+            if (threadIdx.x < RG_TILE) Rule::template prefix<W>(&s_pl[0][0][0][threadIdx.x], &s_q[0][threadIdx.x]);
+            __syncthreads();
+            q = &s_q[0][0];
+        }
+        const int lb = (int)s_len[1][lane];
+        for (u32 k = wave * (RG_TILE * 64 / RG_BLOCK); k < (wave + 1) * (RG_TILE * 64 / RG_BLOCK); ++k) {
+            const u32 r = (lane + k) & (RG_TILE - 1);
+            const u32 ga = ta * RG_TILE + r;
+            if (!(ga < na && gb < nb)) continue;
+            const unsigned long long mine = __hip_atomic_load(&s_acc[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (FLAGS && mine) continue;
+            const int t = FLAGS ? above : cd_threshold(mine, ga);
+            const int v = Rule::template pair<W, FLAGS>(&s_pl[0][0][0][r], &s_pl[1][0][0][lane], Rule::PREFIX ? q + r : q,
+                                                        (int)s_len[0][r], lb, t);
+            if (v <= t) continue;
+            if (FLAGS) __hip_atomic_store(&s_acc[lane], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else atomicMax(&s_acc[lane], ((unsigned long long)(u32)v << 32) | (unsigned long long)(0xFFFFFFFFu - ga));
+        }
+        // (the barrier in front of the next tile's staging; a flag set behind this read costs one more tile, no more)
+        const int done = FLAGS && (gb >= nb || __hip_atomic_load(&s_acc[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        if (__syncthreads_and(done)) break;
+    }
+    __syncthreads();
+    if (threadIdx.x < RG_TILE) {
+        const u32 g = tb * RG_TILE + threadIdx.x;
+        const unsigned long long acc = s_acc[threadIdx.x];
+        if (g < nb && acc) {
+            if (FLAGS) flag[g] = 1;
+            else atomicMax(&best[g], acc);
+        }
+    }
+}
+
+// the pair launch of either one-list entry: one 64 x 64 tile a block over the upper triangle (values: best; graph:
+// bitmap at `above`)
+template <class Rule, int W>
+static void cd_launch_pairs(hipStream_t s, const CdInput &in, bool graph, u32 n, i32 above, unsigned long long *best,
+                            unsigned long long *bitmap) {
+    const dim3 grid((unsigned)in.tiles, (unsigned)in.tiles);
+    const u32 rowwords = (u32)in.tiles;
+    if (graph)
+        hipLaunchKernelGGL((cd_pairs_kernel<Rule, W, true>), grid, dim3(RG_BLOCK), 0, s, (const u64 *)in.fwd.p,
+                           (const u64 *)in.rev.p, (const u32 *)in.lens.p, n, (u32)in.npad, above, best, bitmap, rowwords);
+    else
+        hipLaunchKernelGGL((cd_pairs_kernel<Rule, W, false>), grid, dim3(RG_BLOCK), 0, s, (const u64 *)in.fwd.p,
+                           (const u64 *)in.rev.p, (const u32 *)in.lens.p, n, (u32)in.npad, above, best, bitmap, rowwords);
+}
+
+template <class Rule>
+static void cd_pairs(hipStream_t s, const CdInput &in, bool graph, i64 n, i32 above, unsigned long long *best,
+                     unsigned long long *bitmap) {
+    if (in.W == 1) cd_launch_pairs<Rule, 1>(s, in, graph, (u32)n, above, best, bitmap);
+    else if (in.W == 2) cd_launch_pairs<Rule, 2>(s, in, graph, (u32)n, above, best, bitmap);
+    else cd_launch_pairs<Rule, 4>(s, in, graph, (u32)n, above, best, bitmap);
+}
+
+// the pair launch of either two-list entry: a tile of B a block against the range of A's tiles `per` long that
+// blockIdx.y names
+template <class Rule, int W>
+static void ca_launch(hipStream_t s, dim3 grid, bool flags, const CdInput &A, u32 na, u32 per, const CdInput &B, u32 nb,
+                      i32 above, unsigned long long *best, u8 *flag) {
+    if (flags)
+        hipLaunchKernelGGL((cd_against_kernel<Rule, W, true>), grid, dim3(RG_BLOCK), 0, s, (const u64 *)A.fwd.p,
+                           (const u32 *)A.lens.p, na, (u32)A.npad, (u32)A.tiles, per, (const u64 *)B.rev.p,
+                           (const u32 *)B.lens.p, nb, (u32)B.npad, above, best, flag);
+    else
+        hipLaunchKernelGGL((cd_against_kernel<Rule, W, false>), grid, dim3(RG_BLOCK), 0, s, (const u64 *)A.fwd.p,
+                           (const u32 *)A.lens.p, na, (u32)A.npad, (u32)A.tiles, per, (const u64 *)B.rev.p,
+                           (const u32 *)B.lens.p, nb, (u32)B.npad, above, best, flag);
+}
+
+template <class Rule>
+static void ca_against(hipStream_t s, dim3 grid, bool flags, const CdInput &A, u32 na, u32 per, const CdInput &B, u32 nb,
+                       i32 above, unsigned long long *best, u8 *flag) {
+    if (A.W == 1) ca_launch<Rule, 1>(s, grid, flags, A, na, per, B, nb, above, best, flag);
+    else if (A.W == 2) ca_launch<Rule, 2>(s, grid, flags, A, na, per, B, nb, above, best, flag);
+    else ca_launch<Rule, 4>(s, grid, flags, A, na, per, B, nb, above, best, flag);
+}
+
+// What the host side below takes of a rule, so that it exists once: the names in messages, the smallest threshold
+// of the graph and flags entries, and the launchers of the two kernels.
 struct CdLaunch {
     const char *values_name, *graph_name, *against_name, *flags_name;
     i32 min_above;
@@ -123,6 +340,10 @@ struct CdLaunch {
     void (*against)(hipStream_t s, dim3 grid, bool flags, const CdInput &A, u32 na, u32 per, const CdInput &B, u32 nb,
                     i32 above, unsigned long long *best, u8 *flag);
 };
+
+template <class Rule> static constexpr CdLaunch cd_launch() {
+    return {Rule::VALUES, Rule::GRAPH, Rule::AGAINST, Rule::FLAGS, Rule::MIN_ABOVE, cd_pairs<Rule>, ca_against<Rule>};
+}
 
 static int cd_check(const char *who, const i64 *off, i64 n, int *W) {
     i64 maxlen = 0;

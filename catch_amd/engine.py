@@ -1431,20 +1431,25 @@ class RedundancyGraph:
         self.nedges = ne.value
 
     @classmethod
-    def cross_dimer(cls, ctx, strs, above):
-        """catchhip_cross_dimer_graph: records i and j (i != j) are neighbours
-        iff run(s_i, s_j) > above (catch_amd/filter/cross_dimer.py; any
-        characters, at most REDUNDANT_MAX_LENGTH each, above >= 1)."""
+    def _of_pairs(cls, symbol, ctx, strs, above):
+        """The graph entry `symbol` of either pair rule."""
         self = cls.__new__(cls)
         self.ctx = ctx
         self._h = ctypes.c_void_p()
         buf, off = _concat_records(strs)
         self.n = off.size - 1
         ne = ctypes.c_int64(0)
-        check(ctx._L.catchhip_cross_dimer_graph(
+        check(getattr(ctx._L, symbol)(
             ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), self.n, int(above), ctypes.byref(self._h), ctypes.byref(ne)))
         self.nedges = ne.value
         return self
+
+    @classmethod
+    def cross_dimer(cls, ctx, strs, above):
+        """catchhip_cross_dimer_graph: records i and j (i != j) are neighbours
+        iff run(s_i, s_j) > above (catch_amd/filter/cross_dimer.py; any
+        characters, at most REDUNDANT_MAX_LENGTH each, above >= 1)."""
+        return cls._of_pairs("catchhip_cross_dimer_graph", ctx, strs, above)
 
     @classmethod
     def cross_duplex(cls, ctx, strs, above):
@@ -1452,16 +1457,7 @@ class RedundancyGraph:
         iff duplex(s_i, s_j) > above (catch_amd/filter/cross_duplex.py; any
         characters, at most REDUNDANT_MAX_LENGTH each, above >= 0 in hundredths
         of a kcal/mol)."""
-        self = cls.__new__(cls)
-        self.ctx = ctx
-        self._h = ctypes.c_void_p()
-        buf, off = _concat_records(strs)
-        self.n = off.size - 1
-        ne = ctypes.c_int64(0)
-        check(ctx._L.catchhip_cross_duplex_graph(
-            ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), self.n, int(above), ctypes.byref(self._h), ctypes.byref(ne)))
-        self.nedges = ne.value
-        return self
+        return cls._of_pairs("catchhip_cross_duplex_graph", ctx, strs, above)
 
     def fetch(self):
         """(ptr int64[n + 1], idx uint32[nedges]): the neighbours of i are
@@ -1511,18 +1507,48 @@ def _concat_records(strs):
     return np.ascontiguousarray(buf), off
 
 
+def _pair_values(symbol, ctx, strs):
+    """The one-list values entry `symbol` of either pair rule."""
+    buf, off = _concat_records(strs)
+    n = off.size - 1
+    values = np.zeros(max(n, 1), dtype=np.int32)
+    partners = np.full(max(n, 1), -1, dtype=np.int32)
+    check(getattr(ctx._L, symbol)(
+        ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), n, _ptr(values, c_i32p), _ptr(partners, c_i32p)))
+    return values[:n], partners[:n]
+
+
+def _pair_values_against(symbol, ctx, bs, as_):
+    """The two-list values entry `symbol` of either pair rule."""
+    b_buf, b_off = _concat_records(bs)
+    a_buf, a_off = _concat_records(as_)
+    nb = b_off.size - 1
+    values = np.zeros(max(nb, 1), dtype=np.int32)
+    partners = np.full(max(nb, 1), -1, dtype=np.int32)
+    check(getattr(ctx._L, symbol)(
+        ctx._h, _ptr(b_buf, c_u8p), _ptr(b_off, c_i64p), nb, _ptr(a_buf, c_u8p), _ptr(a_off, c_i64p),
+        a_off.size - 1, _ptr(values, c_i32p), _ptr(partners, c_i32p)))
+    return values[:nb], partners[:nb]
+
+
+def _pair_flags_against(symbol, ctx, bs, as_, above):
+    """The two-list flags entry `symbol` of either pair rule."""
+    b_buf, b_off = _concat_records(bs)
+    a_buf, a_off = _concat_records(as_)
+    nb = b_off.size - 1
+    flags = np.zeros(max(nb, 1), dtype=np.uint8)
+    check(getattr(ctx._L, symbol)(
+        ctx._h, _ptr(b_buf, c_u8p), _ptr(b_off, c_i64p), nb, _ptr(a_buf, c_u8p), _ptr(a_off, c_i64p),
+        a_off.size - 1, int(above), _ptr(flags, c_u8p)))
+    return flags[:nb].astype(bool)
+
+
 def cross_dimer(ctx, strs):
     """catchhip_cross_dimer -> (values int32[n], partners int32[n]): for every
     record the longest antiparallel pairing with another record of the list
     and the smallest index that reaches it, -1 where the value is 0
     (catch_amd/filter/cross_dimer.py has the definition)."""
-    buf, off = _concat_records(strs)
-    n = off.size - 1
-    values = np.zeros(max(n, 1), dtype=np.int32)
-    partners = np.full(max(n, 1), -1, dtype=np.int32)
-    check(ctx._L.catchhip_cross_dimer(
-        ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), n, _ptr(values, c_i32p), _ptr(partners, c_i32p)))
-    return values[:n], partners[:n]
+    return _pair_values("catchhip_cross_dimer", ctx, strs)
 
 
 def cross_against(ctx, bs, as_):
@@ -1531,29 +1557,14 @@ def cross_against(ctx, bs, as_):
     with a record of `as_` (an equal record included) and the smallest index
     into `as_` that reaches it, -1 where the value is 0
     (catch_amd/filter/cross_dimer.py has the definition)."""
-    b_buf, b_off = _concat_records(bs)
-    a_buf, a_off = _concat_records(as_)
-    nb = b_off.size - 1
-    values = np.zeros(max(nb, 1), dtype=np.int32)
-    partners = np.full(max(nb, 1), -1, dtype=np.int32)
-    check(ctx._L.catchhip_cross_against(
-        ctx._h, _ptr(b_buf, c_u8p), _ptr(b_off, c_i64p), nb, _ptr(a_buf, c_u8p), _ptr(a_off, c_i64p),
-        a_off.size - 1, _ptr(values, c_i32p), _ptr(partners, c_i32p)))
-    return values[:nb], partners[:nb]
+    return _pair_values_against("catchhip_cross_against", ctx, bs, as_)
 
 
 def cross_against_flags(ctx, bs, as_, above):
     """catchhip_cross_against_flags -> bool[len(bs)]: whether the record of
     `bs` pairs with some record of `as_` over more than `above` (>= 1)
     consecutive bases."""
-    b_buf, b_off = _concat_records(bs)
-    a_buf, a_off = _concat_records(as_)
-    nb = b_off.size - 1
-    flags = np.zeros(max(nb, 1), dtype=np.uint8)
-    check(ctx._L.catchhip_cross_against_flags(
-        ctx._h, _ptr(b_buf, c_u8p), _ptr(b_off, c_i64p), nb, _ptr(a_buf, c_u8p), _ptr(a_off, c_i64p),
-        a_off.size - 1, int(above), _ptr(flags, c_u8p)))
-    return flags[:nb].astype(bool)
+    return _pair_flags_against("catchhip_cross_against_flags", ctx, bs, as_, above)
 
 
 def cross_duplex(ctx, strs):
@@ -1562,42 +1573,21 @@ def cross_duplex(ctx, strs):
     list, in hundredths of a kcal/mol, and the smallest index that reaches it,
     -1 where the value is 0 (catch_amd/filter/cross_duplex.py has the
     definition)."""
-    buf, off = _concat_records(strs)
-    n = off.size - 1
-    values = np.zeros(max(n, 1), dtype=np.int32)
-    partners = np.full(max(n, 1), -1, dtype=np.int32)
-    check(ctx._L.catchhip_cross_duplex(
-        ctx._h, _ptr(buf, c_u8p), _ptr(off, c_i64p), n, _ptr(values, c_i32p), _ptr(partners, c_i32p)))
-    return values[:n], partners[:n]
+    return _pair_values("catchhip_cross_duplex", ctx, strs)
 
 
 def cross_duplex_against(ctx, bs, as_):
     """catchhip_cross_duplex_against -> (values int32[len(bs)], partners
     int32[len(bs)]): cross_against with the stability of the firmest stretch in
     place of the length of the longest."""
-    b_buf, b_off = _concat_records(bs)
-    a_buf, a_off = _concat_records(as_)
-    nb = b_off.size - 1
-    values = np.zeros(max(nb, 1), dtype=np.int32)
-    partners = np.full(max(nb, 1), -1, dtype=np.int32)
-    check(ctx._L.catchhip_cross_duplex_against(
-        ctx._h, _ptr(b_buf, c_u8p), _ptr(b_off, c_i64p), nb, _ptr(a_buf, c_u8p), _ptr(a_off, c_i64p),
-        a_off.size - 1, _ptr(values, c_i32p), _ptr(partners, c_i32p)))
-    return values[:nb], partners[:nb]
+    return _pair_values_against("catchhip_cross_duplex_against", ctx, bs, as_)
 
 
 def cross_duplex_against_flags(ctx, bs, as_, above):
     """catchhip_cross_duplex_against_flags -> bool[len(bs)]: whether the record
     of `bs` forms a stretch firmer than `above` (>= 0, hundredths of a
     kcal/mol) with some record of `as_`."""
-    b_buf, b_off = _concat_records(bs)
-    a_buf, a_off = _concat_records(as_)
-    nb = b_off.size - 1
-    flags = np.zeros(max(nb, 1), dtype=np.uint8)
-    check(ctx._L.catchhip_cross_duplex_against_flags(
-        ctx._h, _ptr(b_buf, c_u8p), _ptr(b_off, c_i64p), nb, _ptr(a_buf, c_u8p), _ptr(a_off, c_i64p),
-        a_off.size - 1, int(above), _ptr(flags, c_u8p)))
-    return flags[:nb].astype(bool)
+    return _pair_flags_against("catchhip_cross_duplex_against_flags", ctx, bs, as_, above)
 
 
 class Shard:
